@@ -15,9 +15,15 @@ the global batch (weak scaling; Philox counters are global element indices, so t
 GPU would produce) and ONE all-gather over RCCL assembles the (256*N) batch inside the timed region.
 ``--scaling strong --global-batch G`` fixes the global batch instead (G/N per GPU).
 
-Rank 0 prints ONE JSON line.  Besides the contract's fields: ``roofline`` of the dominant kernel (timed live by HIP
-events on its launch stream), ``cpu_baseline`` (the oracle on this box's host cores on BASELINE config 1, bounded
-sample), per-kernel rows and the DDIM-50 rate of the same step (``--workload ddim50`` measures that one directly).
+Rank 0 prints ONE JSON line: the contract's fields and the per-denoise-step rates derived from the same timing
+(``ddim50_equiv_images_per_s``; ``--workload ddim50`` measures that one directly).  A plain run does nothing else.
+``--full`` adds the legs that take runs of their own: ``roofline`` of the dominant kernel (timed live by HIP events on
+its launch stream) with per-kernel rows, ``other_configs`` (BASELINE configs 3-5), ``train_step`` (one training
+iteration) and ``cpu_baseline`` (the oracle on the host's cores on BASELINE config 1, bounded sample).
+
+``--dump-outputs DIR`` writes the images the last timed ``sample()`` call returned to ``DIR/samples.npy`` (float32,
+(global batch, 3, 32, 32)).  Weights and noise are seeded, so the same arguments give the same inputs on every run and
+two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -40,8 +46,11 @@ IMAGE, CHANNELS, T = 32, 3, 1000
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=2, help="timed sample() calls (>= 1)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed sample() calls before them")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, other-config, training and CPU-baseline legs (the --no-* options drop one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's images to DIR/samples.npy")
     ap.add_argument("--batch", type=int, default=256, help="images per GPU per sample() call (weak scaling)")
     ap.add_argument("--workload", default="ddpm1000", choices=["ddpm1000", "ddim50"])
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
@@ -52,7 +61,10 @@ def parse():
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=20, help="DDPM steps of the CPU baseline sample (config 1)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -316,7 +328,7 @@ def train_leg(dev, with_cpu: bool, batch: int = 64, iters: int = 10, world: int 
     Trainer.train (DD/denoising_diffusion.py:1164-1190: p_losses + backward, clip_grad_norm_, Adam, ema.update) at the shipped
     ddpm_cifar.yaml shape (32x32 U-Net dim 64, train_batch_size 64, dropout 0.1), all on the GPU with device-resident
     parameters; and the same iteration through torch autograd on this box's host cores (the oracle, one iteration).
-    world > 1 (bench.py --gpus N): data-parallel as accelerate runs the reference's Trainer -- `batch` images per rank (weak
+    world > 1 (bench.py --full --gpus N): data-parallel as accelerate runs the reference's Trainer -- `batch` images per rank (weak
     scaling), ONE all-reduce of the flat gradient buffer over RCCL inside every timed iteration, every rank steps its own
     replica; the time is the maximum over ranks and the all-reduce's share comes from HIP events around it."""
     import torch
@@ -529,6 +541,11 @@ def main():
         elapsed = float(tmax.item())
     assert out.shape == (B_global, CHANNELS, IMAGE, IMAGE) and bool(torch.isfinite(out).all())
     assert unet.graph_captures <= 1, "the step graph must be captured once, not per sample() call"
+    if rank == 0 and args.dump_outputs:
+        import numpy as np
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "samples.npy"), out.float().cpu().numpy())
 
     images = B_global * args.steps
     value = images / elapsed
@@ -563,7 +580,7 @@ def main():
         "ddim50_equiv_images_per_s": value * S / 50.0,
     }
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # roofline leg: the same denoise step, eager launches, every conv bracketed by HIP events on its stream
         diff_e = dm.DenoisingDiffusion(unet, image_size=IMAGE, timesteps=T, use_graph=False)
         _lib.profile_enable(True)
@@ -622,9 +639,9 @@ def main():
             result["roofline"]["step_executed_frac"] = None
             result["roofline"]["families_source"] = brk_src
 
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_other_configs:
         result["other_configs"] = other_configs(dev)
-    if not args.no_train:  # every rank: under world > 1 the iteration holds a collective
+    if args.full and not args.no_train:  # every rank: under world > 1 the iteration holds a collective
         try:
             tr = train_leg(dev, with_cpu=world == 1 and not args.no_cpu_baseline, world=world, rank=rank, rehearse=rehearse)
         except Exception as e:  # noqa: BLE001 -- the headline above must still be reported (every rank takes this branch
@@ -638,7 +655,7 @@ def main():
             t16 = train_leg(dev, with_cpu=False, batch=16)
             result["train_step"]["batch16"] = {k: t16[k] for k in ("ms_per_iteration", "images_per_s", "iterations_timed")}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.cpu_steps)
         gpu_ddpm = value if S == T else value * S / T
         result["gpu_over_cpu"] = gpu_ddpm / result["cpu_baseline"]["value"]

@@ -25,4 +25,5 @@ bash tools/pmc_run.sh ${tag}_trainpmc
 python3 tools/pmc_summary.py gpurun_out/${tag}_trainpmc > gpurun_out/${tag}_train_pmc.json
 cp gpurun_out/${tag}_train_pmc.json profiles/${tag}_train_pmc.json
 unset PMC_ITERS PMC_CMD
-echo "== bench"; python3 bench.py --steps 3 --warmup 1 > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err; tail -c 600 gpurun_out/${tag}_bench.json
+echo "== bench"; out=$(dirname "$(ls -d */"${tag}_stats")")   # the output directory of the stats pass above
+python3 bench.py --full --steps 3 --warmup 1 > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"; tail -c 600 "$out/${tag}_bench.json"
