@@ -1,11 +1,13 @@
 // Attention cores of the denoising U-Net (gfx950).  dim_head is 32 in every reference config
-// (DD/denoising_diffusion.py:248,155,200); the kernels below are specialised for it.
+// (DD/denoising_diffusion.py:248,155,200); Unet(attn_dim_head=64) is the usual alternative.  Every core is a template on the
+// head width DH and is instantiated at 32 and 64 (one width per model); the 32-wide instantiations are the kernels the
+// benchmark model runs.  At 64 the LinearAttention context is 64 x 64 per head: 2 x 2 tiles of the 32x32x2 MFMA product.
 //
-//   LinearAttention core  DD/denoising_diffusion.py:179-192   (two softmaxes + two 32x32 products/head)
+//   LinearAttention core  DD/denoising_diffusion.py:179-192   (two softmaxes + two DH x DH products/head)
 //   Attention core        DD/denoising_diffusion.py:221-226 + DD/attend.py:109-124
 //   CrossAttention core   DD/denoising_diffusion_text_conditional.py:68-77 (same kernel, no memory kv)
 //
-// qkv tensors are NHWC, i.e. one row of 3*heads*32 floats per token: [q(h,d) | k(h,d) | v(h,d)].
+// qkv tensors are NHWC, i.e. one row of 3*heads*DH floats per token: [q(h,d) | k(h,d) | v(h,d)].
 #include "dm_common.h"
 
 #include <algorithm>
@@ -14,7 +16,12 @@
 
 namespace dm {
 
-constexpr int DH = 32;
+// log2 of a supported head width: row / column of a flattened DH x DH index by shift and mask
+template <int DH>
+constexpr int log2_dh() {
+    static_assert(DH == 32 || DH == 64, "head widths 32 and 64");
+    return DH == 32 ? 5 : 6;
+}
 
 __device__ __forceinline__ float wave_max64(float v) {
 #pragma unroll
@@ -28,24 +35,26 @@ __device__ __forceinline__ float wave_sum64(float v) {
 }
 
 // ---------------------------------------------------------------------------------------
-// LinearAttention, part 1 on the f32 MFMA: ctx[d][e] = sum_t softmax_t(k)[d][t] * v[e][t] is a (32 x n) x (n x 32)
+// LinearAttention, part 1 on the f32 MFMA: ctx[d][e] = sum_t softmax_t(k)[d][t] * v[e][t] is a (DH x n) x (n x DH)
 // product per (image, head), with the tokens as the reduction axis:
 //   A[i = d][k = token] = exp(k[token][d] - max_d),  B[k = token][j = e] = v[token][e]
-// so a lane loads ONE dword of k and ONE of v per step (lanes 0-31 / 32-63 read the 128 contiguous bytes of
-// two consecutive tokens) and the 32x32 context accumulates in 16 registers.  grid (heads, B), 4 waves; each
-// wave takes a quarter of the tokens, the partial contexts meet in LDS.  The 4 memory tokens are two extra steps.
+// so a lane loads ONE dword of k and ONE of v per step and 32-row tile (lanes 0-31 / 32-63 read the 128 contiguous bytes of
+// two consecutive tokens) and each 32x32 tile of the context accumulates in 16 registers (one tile at DH = 32, 2 x 2 at 64).
+// grid (heads, B), NW waves; each wave takes 1 / NW of the tokens, the partial contexts meet in LDS.  The 4 memory tokens
+// are two extra steps.
 // ---------------------------------------------------------------------------------------
 using f32x16_t = __attribute__((ext_vector_type(16))) float;
 
-// NW waves per (image, head): the token loop is a chain of load round trips (8 loads in flight per lane, then 4 MFMAs), so with
-// heads x B workgroups and nothing else to overlap, the kernel's time is one wave's chain; 16 waves on the 1024 tokens of a 32x32
-// stage make that chain 8 rounds instead of 32 (45 -> about 15 us in the B = 64 training step).
-template <int NW>
+// NW waves per (image, head): the token loop is a chain of load round trips (8 loads in flight per lane and tile, then the
+// MFMAs), so with heads x B workgroups and nothing else to overlap, the kernel's time is one wave's chain; 16 waves on the
+// 1024 tokens of a 32x32 stage make that chain 8 rounds instead of 32 (45 -> about 15 us in the B = 64 training step).
+template <int NW, int DH>
 __global__ __launch_bounds__(64 * NW) void linattn_ctx_mfma_kernel(const float* __restrict__ qkv,
                                                                    const float* __restrict__ mem_kv,
                                                                    float* __restrict__ ctx, float* __restrict__ kstats,
                                                                    int n, int heads) {
     constexpr int NMEM = 4;
+    constexpr int NT = DH / 32;  // 32-wide tiles per side of the context
     const int h = blockIdx.x, b = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, half = lane >> 5;
@@ -56,32 +65,48 @@ __global__ __launch_bounds__(64 * NW) void linattn_ctx_mfma_kernel(const float* 
     const float* mv = mem_kv + (size_t)(heads + h) * DH * NMEM;  // [e][j]
     __shared__ float red[NW][DH];
     __shared__ float kmax_s[DH], ksum_s[DH];
-    constexpr int NP = NW > 8 ? NW / 2 : NW;  // 16 waves fold in two rounds: 64 KB of static LDS would not fit with the rest
+    // partial-context slots: at DH = 32, 16 waves fold in two rounds (64 KB of static LDS would not fit with the rest); a
+    // 64-wide context is 16 KB, so two slots and NW / 2 - 1 rounds
+    constexpr int NP = DH == 32 ? (NW > 8 ? NW / 2 : NW) : 2;
     __shared__ __attribute__((aligned(16))) float part[NP][DH * DH];
 
     // tokens of this wave: [t0, t1), visited two at a time (one per lane half)
     const int per = ((n + 2 * NW - 1) / (2 * NW)) * 2;  // even number of tokens per wave
     const int t0 = min(n, wave * per), t1 = min(n, t0 + per);
 
-    // pass 1: max over all tokens (incl. memory) of k[.][d]
-    float m = -INFINITY;
+    // pass 1: max over all tokens (incl. memory) of k[.][d]; the lane's columns are c + 32 I
+    float m[NT];
+#pragma unroll
+    for (int I = 0; I < NT; ++I) m[I] = -INFINITY;
     {
         int t = t0;
         for (; t + 16 <= t1; t += 16) {
-            float kv[8];
+            float kv[8][NT];
 #pragma unroll
-            for (int s = 0; s < 8; ++s) kv[s] = kb[(size_t)(t + 2 * s + half) * ld];
+            for (int s = 0; s < 8; ++s)
 #pragma unroll
-            for (int s = 0; s < 8; ++s) m = fmaxf(m, kv[s]);
+                for (int I = 0; I < NT; ++I) kv[s][I] = kb[(size_t)(t + 2 * s + half) * ld + 32 * I];
+#pragma unroll
+            for (int s = 0; s < 8; ++s)
+#pragma unroll
+                for (int I = 0; I < NT; ++I) m[I] = fmaxf(m[I], kv[s][I]);
         }
-        for (t += half; t < t1; t += 2) m = fmaxf(m, kb[(size_t)t * ld]);
+        for (t += half; t < t1; t += 2)
+#pragma unroll
+            for (int I = 0; I < NT; ++I) m[I] = fmaxf(m[I], kb[(size_t)t * ld + 32 * I]);
     }
     if (wave == 0) {
-        m = fmaxf(m, mk[c * NMEM + half]);
-        m = fmaxf(m, mk[c * NMEM + 2 + half]);
+#pragma unroll
+        for (int I = 0; I < NT; ++I) {
+            m[I] = fmaxf(m[I], mk[(32 * I + c) * NMEM + half]);
+            m[I] = fmaxf(m[I], mk[(32 * I + c) * NMEM + 2 + half]);
+        }
     }
-    m = fmaxf(m, __shfl_xor(m, 32));
-    if (half == 0) red[wave][c] = m;
+#pragma unroll
+    for (int I = 0; I < NT; ++I) {
+        m[I] = fmaxf(m[I], __shfl_xor(m[I], 32));
+        if (half == 0) red[wave][32 * I + c] = m[I];
+    }
     __syncthreads();
     if (tid < DH) {
         float mm = red[0][tid];
@@ -90,63 +115,125 @@ __global__ __launch_bounds__(64 * NW) void linattn_ctx_mfma_kernel(const float* 
         kmax_s[tid] = mm;
     }
     __syncthreads();
-    const float kmax = kmax_s[c];
-
-    // pass 2: exp, row sums, and the outer-product accumulation on the matrix core
-    f32x16_t acc;
+    float kmax[NT];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    float ksum = 0.f;
+    for (int I = 0; I < NT; ++I) kmax[I] = kmax_s[32 * I + c];
+
+    // pass 2: exp, row sums, and the outer-product accumulation on the matrix core; acc[I][J] is the (d tile I, e tile J)
+    f32x16_t acc[NT][NT];
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+        for (int J = 0; J < NT; ++J)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[I][J][e] = 0.f;
+    float ksum[NT];
+#pragma unroll
+    for (int I = 0; I < NT; ++I) ksum[I] = 0.f;
     if (wave == 0) {
 #pragma unroll
         for (int j = 0; j < NMEM; j += 2) {
-            float a = __expf(mk[c * NMEM + j + half] - kmax);
-            float bv = mv[c * NMEM + j + half];
-            ksum += a;
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv, acc, 0, 0, 0);
+            float a[NT], bv[NT];
+#pragma unroll
+            for (int I = 0; I < NT; ++I) {
+                a[I] = __expf(mk[(32 * I + c) * NMEM + j + half] - kmax[I]);
+                bv[I] = mv[(32 * I + c) * NMEM + j + half];
+                ksum[I] += a[I];
+            }
+#pragma unroll
+            for (int I = 0; I < NT; ++I)
+#pragma unroll
+                for (int J = 0; J < NT; ++J) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[I], bv[J], acc[I][J], 0, 0, 0);
         }
     }
     int t = t0;
-    for (; t + 8 <= t1; t += 8) {  // 4 steps per iteration: 8 loads in flight per lane
-        float kv[4], vv[4];
+    for (; t + 8 <= t1; t += 8) {  // 4 steps per iteration: 8 loads in flight per lane and tile
+        float kv[4][NT], vv[4][NT];
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int I = 0; I < NT; ++I) {
+                kv[s][I] = kb[(size_t)(t + 2 * s + half) * ld + 32 * I];
+                vv[s][I] = vb[(size_t)(t + 2 * s + half) * ld + 32 * I];
+            }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            kv[s] = kb[(size_t)(t + 2 * s + half) * ld];
-            vv[s] = vb[(size_t)(t + 2 * s + half) * ld];
-        }
+            float a[NT];
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            float a = __expf(kv[s] - kmax);
-            ksum += a;
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, vv[s], acc, 0, 0, 0);
+            for (int I = 0; I < NT; ++I) {
+                a[I] = __expf(kv[s][I] - kmax[I]);
+                ksum[I] += a[I];
+            }
+#pragma unroll
+            for (int I = 0; I < NT; ++I)
+#pragma unroll
+                for (int J = 0; J < NT; ++J)
+                    acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[I], vv[s][J], acc[I][J], 0, 0, 0);
         }
     }
     for (; t < t1; t += 2) {  // tail: a missing token contributes a = 0
         const bool ok = t + half < t1;
-        float a = ok ? __expf(kb[(size_t)(t + half) * ld] - kmax) : 0.f;
-        float bv = ok ? vb[(size_t)(t + half) * ld] : 0.f;
-        ksum += a;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv, acc, 0, 0, 0);
+        float a[NT], bv[NT];
+#pragma unroll
+        for (int I = 0; I < NT; ++I) {
+            a[I] = ok ? __expf(kb[(size_t)(t + half) * ld + 32 * I] - kmax[I]) : 0.f;
+            bv[I] = ok ? vb[(size_t)(t + half) * ld + 32 * I] : 0.f;
+            ksum[I] += a[I];
+        }
+#pragma unroll
+        for (int I = 0; I < NT; ++I)
+#pragma unroll
+            for (int J = 0; J < NT; ++J) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[I], bv[J], acc[I][J], 0, 0, 0);
     }
-    ksum += __shfl_xor(ksum, 32);
+#pragma unroll
+    for (int I = 0; I < NT; ++I) ksum[I] += __shfl_xor(ksum[I], 32);
     __syncthreads();  // red is reused
-    if (half == 0) red[wave][c] = ksum;
-    // accumulator element e of lane: row d = (e&3) + 8*(e>>2) + 4*half, column e-index = lane&31
-    if constexpr (NP < NW) {
+    if (half == 0)
+#pragma unroll
+        for (int I = 0; I < NT; ++I) red[wave][32 * I + c] = ksum[I];
+    // accumulator element e of acc[I][J]: row d = 32 I + (e&3) + 8*(e>>2) + 4*half, column 32 J + lane&31
+#define DM_LA_SLOT(I, J, e) ((32 * (I) + ((e) & 3) + 8 * ((e) >> 2) + 4 * half) * DH + 32 * (J) + c)
+    if constexpr (DH == 32 && NP < NW) {
         if (wave >= NP) {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) part[wave - NP][((e & 3) + 8 * (e >> 2) + 4 * half) * DH + c] = acc[e];
+            for (int e = 0; e < 16; ++e) part[wave - NP][DM_LA_SLOT(0, 0, e)] = acc[0][0][e];
         }
         __syncthreads();
         if (wave < NP) {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] += part[wave][((e & 3) + 8 * (e >> 2) + 4 * half) * DH + c];
+            for (int e = 0; e < 16; ++e) acc[0][0][e] += part[wave][DM_LA_SLOT(0, 0, e)];
+        }
+    } else if constexpr (NP < NW) {  // groups of NP waves fold into waves [0, NP), the last group first
+        for (int g = NW / NP - 1; g >= 1; --g) {
+            if (wave >= g * NP && wave < (g + 1) * NP) {
+#pragma unroll
+                for (int I = 0; I < NT; ++I)
+#pragma unroll
+                    for (int J = 0; J < NT; ++J)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) part[wave - g * NP][DM_LA_SLOT(I, J, e)] = acc[I][J][e];
+            }
+            __syncthreads();
+            if (wave < NP) {
+#pragma unroll
+                for (int I = 0; I < NT; ++I)
+#pragma unroll
+                    for (int J = 0; J < NT; ++J)
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) acc[I][J][e] += part[wave][DM_LA_SLOT(I, J, e)];
+            }
+            __syncthreads();
         }
     }
     if (wave < NP) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) part[wave][((e & 3) + 8 * (e >> 2) + 4 * half) * DH + c] = acc[e];
+        for (int I = 0; I < NT; ++I)
+#pragma unroll
+            for (int J = 0; J < NT; ++J)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) part[wave][DM_LA_SLOT(I, J, e)] = acc[I][J][e];
     }
+#undef DM_LA_SLOT
     __syncthreads();
     if (tid < DH) {
         float ss = red[0][tid];
@@ -161,7 +248,7 @@ __global__ __launch_bounds__(64 * NW) void linattn_ctx_mfma_kernel(const float* 
     __syncthreads();
     float* cp = ctx + (size_t)(b * heads + h) * DH * DH;
     for (int i = tid; i < DH * DH; i += 64 * NW) {
-        const int d = i >> 5;
+        const int d = i >> log2_dh<DH>();
         float sum = part[0][i];
 #pragma unroll
         for (int w = 1; w < NP; ++w) sum += part[w][i];
@@ -174,9 +261,14 @@ __global__ __launch_bounds__(64 * NW) void linattn_ctx_mfma_kernel(const float* 
 // ctx[b][h][d][e] = sum_n softmax_n(k)[d][n] * v[e][n]  (n includes the memory tokens)
 // grid (heads, B), 256 threads.
 // ---------------------------------------------------------------------------------------
+template <int DH>
 __global__ __launch_bounds__(256) void linattn_ctx_kernel(const float* __restrict__ qkv,
                                                           const float* __restrict__ mem_kv,
                                                           float* __restrict__ ctx, int n, int heads, int n_mem) {
+    constexpr int LDH = log2_dh<DH>();
+    constexpr int NPART = 256 / DH;      // pass 1: token stripes per column
+    constexpr int EPT = DH * DH / 256;   // pass 2: context elements per thread (a run of one row)
+    constexpr int TPR = DH / EPT;        //         threads per context row
     const int h = blockIdx.x, b = blockIdx.y;
     const int tid = threadIdx.x;
     const int ld = 3 * heads * DH;
@@ -186,7 +278,7 @@ __global__ __launch_bounds__(256) void linattn_ctx_kernel(const float* __restric
     const float* mv = mem_kv + (size_t)(heads + h) * DH * n_mem;  // [e][j]
     const int ntok = n + n_mem;
 
-    __shared__ float red[8][DH];
+    __shared__ float red[NPART][DH];
     __shared__ float kmax[DH];
     __shared__ float ke[64][DH + 1];
     __shared__ __attribute__((aligned(16))) float vv[64][DH];
@@ -194,9 +286,9 @@ __global__ __launch_bounds__(256) void linattn_ctx_kernel(const float* __restric
 
     // pass 1: max over tokens for each d
     {
-        const int d = tid & 31, part = tid >> 5;
+        const int d = tid & (DH - 1), part = tid >> LDH;
         float m = -INFINITY;
-        for (int t = part; t < ntok; t += 8) {
+        for (int t = part; t < ntok; t += NPART) {
             float kv = t < n_mem ? mk[d * n_mem + t] : kbase[(size_t)(t - n_mem) * ld + d];
             m = fmaxf(m, kv);
         }
@@ -205,19 +297,22 @@ __global__ __launch_bounds__(256) void linattn_ctx_kernel(const float* __restric
         if (tid < DH) {
             float mm = red[0][tid];
 #pragma unroll
-            for (int q = 1; q < 8; ++q) mm = fmaxf(mm, red[q][tid]);
+            for (int q = 1; q < NPART; ++q) mm = fmaxf(mm, red[q][tid]);
             kmax[tid] = mm;
         }
         __syncthreads();
     }
-    // pass 2: exp, running sum and the 32x32 outer-product accumulation
-    const int d = tid >> 3, e0 = (tid & 7) * 4;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    // pass 2: exp, running sum and the DH x DH outer-product accumulation
+    constexpr int LTPR = DH == 32 ? 3 : 2;  // log2 TPR
+    const int d = tid >> LTPR, e0 = (tid & (TPR - 1)) * EPT;
+    float acc[EPT];
+#pragma unroll
+    for (int e = 0; e < EPT; ++e) acc[e] = 0.f;
     float ksum = 0.f;
     for (int t0 = 0; t0 < ntok; t0 += 64) {
         __syncthreads();
         for (int it = tid; it < 64 * DH; it += 256) {
-            int tt = it >> 5, c = it & 31;
+            int tt = it >> LDH, c = it & (DH - 1);
             int t = t0 + tt;
             float kval = 0.f, vval = 0.f;
             if (t < ntok) {
@@ -236,31 +331,42 @@ __global__ __launch_bounds__(256) void linattn_ctx_kernel(const float* __restric
 #pragma unroll 8
         for (int tt = 0; tt < 64; ++tt) {
             float kx = ke[tt][d];
-            float4 v4 = *reinterpret_cast<const float4*>(&vv[tt][e0]);
+            float4 v4[EPT / 4];
+#pragma unroll
+            for (int j = 0; j < EPT / 4; ++j) v4[j] = *reinterpret_cast<const float4*>(&vv[tt][e0 + 4 * j]);
             ksum += kx;
-            acc[0] += kx * v4.x;
-            acc[1] += kx * v4.y;
-            acc[2] += kx * v4.z;
-            acc[3] += kx * v4.w;
+#pragma unroll
+            for (int j = 0; j < EPT / 4; ++j) {
+                acc[4 * j] += kx * v4[j].x;
+                acc[4 * j + 1] += kx * v4[j].y;
+                acc[4 * j + 2] += kx * v4[j].z;
+                acc[4 * j + 3] += kx * v4[j].w;
+            }
         }
     }
-    if ((tid & 7) == 0) ksum_s[d] = ksum;
+    if ((tid & (TPR - 1)) == 0) ksum_s[d] = ksum;
     __syncthreads();
     const float inv = 1.0f / ksum_s[d];
     float* cp = ctx + ((size_t)(b * heads + h) * DH + d) * DH + e0;
-    *reinterpret_cast<float4*>(cp) = make_float4(acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv);
+#pragma unroll
+    for (int j = 0; j < EPT / 4; ++j)
+        *reinterpret_cast<float4*>(cp + 4 * j) =
+            make_float4(acc[4 * j] * inv, acc[4 * j + 1] * inv, acc[4 * j + 2] * inv, acc[4 * j + 3] * inv);
 }
 
-// LinearAttention, part 2: out[b][n][h*32+e] = sum_d ctx[b][h][d][e] * softmax_d(q[b][n][h][:])[d] * 32^-0.5
-// grid (ceil(n/64), B), block = 64*heads threads: thread = h*64 + pixel (one head per wavefront).
-__global__ void linattn_out_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
+// LinearAttention, part 2: out[b][n][h*DH+e] = sum_d ctx[b][h][d][e] * softmax_d(q[b][n][h][:])[d] * DH^-0.5
+// DH = 32: grid (ceil(n/64), B), block = 64*heads threads: thread = h*64 + pixel (one head per wavefront), every head's
+// context in LDS.  DH = 64: one head per block (16 KB of context), grid (ceil(n/64), B, heads), 64 threads.
+template <int DH>
+__global__ __launch_bounds__(DH == 32 ? 1024 : 64) void linattn_out_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
                                    float* __restrict__ out, int n, int heads, float scale) {
-    extern __shared__ __attribute__((aligned(16))) float cs[];  // [heads][DH][DH]
+    extern __shared__ __attribute__((aligned(16))) float cs[];  // [heads in the block][DH][DH]
     const int b = blockIdx.y;
     const int tid = threadIdx.x;
-    for (int i = tid; i < heads * DH * DH; i += blockDim.x) cs[i] = ctx[(size_t)b * heads * DH * DH + i];
+    const int h0 = DH == 32 ? 0 : blockIdx.z, hb = DH == 32 ? heads : 1;
+    for (int i = tid; i < hb * DH * DH; i += blockDim.x) cs[i] = ctx[((size_t)b * heads + h0) * DH * DH + i];
     __syncthreads();
-    const int h = tid >> 6;
+    const int hl = tid >> 6, h = h0 + hl;
     const int p = blockIdx.x * 64 + (tid & 63);
     if (p >= n) return;
     const int ld = 3 * heads * DH;
@@ -284,7 +390,7 @@ __global__ void linattn_out_kernel(const float* __restrict__ qkv, const float* _
     float o[DH];
 #pragma unroll
     for (int i = 0; i < DH; ++i) o[i] = 0.f;
-    const float* ch = cs + h * DH * DH;
+    const float* ch = cs + hl * DH * DH;
 #pragma unroll
     for (int dd = 0; dd < DH; ++dd) {
         const float qd = q[dd] * inv;
@@ -304,20 +410,25 @@ __global__ void linattn_out_kernel(const float* __restrict__ qkv, const float* _
 }
 
 // part 2 on the matrix core: out^T[e][token] = sum_d ctx[d][e] q_s[token][d] as 32x32x2 MFMA products with the token rows as the
-// B operand (attn_bwd.hip's linattn_bwd_*_mfma_kernel describe the layout): lane (token, half) holds the four float4 chunks
-// 2 m + half of its token's q row = the columns dset(r) = (r & 3) + 8 (r >> 2) + 4 half, the softmax over the 32 columns is 16
-// registers plus one exchange with lane ^ 32, the K index runs over d in the same order, and the result D[i = e][j = token]
-// leaves the lane with out[token][dset(r)]: four float4 stores.  grid (ceil(n / 64), heads, B), one wave = 64 tokens.
+// B operand (attn_bwd.hip's linattn_bwd_*_mfma_kernel describe the layout): lane (token, half) holds the float4 chunks
+// 2 m + half of its token's q row = the columns dset(r) = (r & 3) + 8 (r >> 2) + 4 half, r < DH / 2; the softmax over the DH
+// columns is DH / 2 registers plus one exchange with lane ^ 32, the K index runs over d in the same order, and the result
+// D[i = e][j = token] of e tile E leaves the lane with out[token][32 E + dset(r)], r < 16: four float4 stores per tile.
+// grid (ceil(n / 64), heads, B), one wave = 64 tokens.
+template <int DH>
 __global__ __launch_bounds__(64) void linattn_out_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
                                                               float* __restrict__ out, int n, int heads, float scale) {
+    constexpr int NT = DH / 32, NS = DH / 2;  // e tiles; k-steps over d
     const int blk = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const int lane = threadIdx.x, l31 = lane & 31, half = lane >> 5;
     const int ld = 3 * heads * DH, hid = heads * DH;
-    float a[16];  // A[i = e = l31][k -> d = dset(s)] = ctx[d][e]
+    float a[NT][NS];  // A[i = e = 32 E + l31][k -> d = dset(s)] = ctx[d][e]
     {
         const float* cp = ctx + (size_t)(b * heads + h) * DH * DH + l31;
 #pragma unroll
-        for (int s = 0; s < 16; ++s) a[s] = cp[((s & 3) + 8 * (s >> 2) + 4 * half) * DH];
+        for (int E = 0; E < NT; ++E)
+#pragma unroll
+            for (int s = 0; s < NS; ++s) a[E][s] = cp[((s & 3) + 8 * (s >> 2) + 4 * half) * DH + 32 * E];
     }
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
@@ -325,33 +436,40 @@ __global__ __launch_bounds__(64) void linattn_out_mfma_kernel(const float* __res
         const bool ok = tok < n;
         const size_t row = (size_t)b * n + (ok ? tok : 0);
         const float4* qp = reinterpret_cast<const float4*>(qkv + row * ld + h * DH);
-        float q[16];
+        float q[NS];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+        for (int m = 0; m < NS / 4; ++m) {
             const float4 t = qp[2 * m + half];
             q[4 * m] = t.x; q[4 * m + 1] = t.y; q[4 * m + 2] = t.z; q[4 * m + 3] = t.w;
         }
         float mx = q[0];
 #pragma unroll
-        for (int r = 1; r < 16; ++r) mx = fmaxf(mx, q[r]);
+        for (int r = 1; r < NS; ++r) mx = fmaxf(mx, q[r]);
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         float sum = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
+        for (int r = 0; r < NS; ++r) {
             q[r] = __expf(q[r] - mx);
             sum += q[r];
         }
         sum += __shfl_xor(sum, 32);
         const float inv = scale / sum;
-        f32x16_t acc;
+        f32x16_t acc[NT];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int E = 0; E < NT; ++E)
 #pragma unroll
-        for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], q[s] * inv, acc, 0, 0, 0);
+            for (int r = 0; r < 16; ++r) acc[E][r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int E = 0; E < NT; ++E) acc[E] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[E][s], q[s] * inv, acc[E], 0, 0, 0);
         if (ok) {
             float4* op = reinterpret_cast<float4*>(out + row * hid + h * DH);
 #pragma unroll
-            for (int m = 0; m < 4; ++m) op[2 * m + half] = make_float4(acc[4 * m], acc[4 * m + 1], acc[4 * m + 2], acc[4 * m + 3]);
+            for (int E = 0; E < NT; ++E)
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    op[8 * E + 2 * m + half] = make_float4(acc[E][4 * m], acc[E][4 * m + 1], acc[E][4 * m + 2], acc[E][4 * m + 3]);
         }
     }
 }
@@ -363,46 +481,61 @@ bool linattn_keeps_kstats() {
     return keep;
 }
 
-int launch_linear_attention_core(const float* qkv, const float* mem_kv, float* ctx_ws, float* out, int B, int n,
-                                 int heads, int dh, hipStream_t s, float* kstats) {
-    DM_REQUIRE(dh == DH, "LinearAttention kernel is specialised for dim_head == 32");
-    DM_REQUIRE(heads >= 1 && heads <= 16, "LinearAttention kernel supports 1..16 heads");
+template <int DH>
+static int linear_attention_core(const float* qkv, const float* mem_kv, float* ctx_ws, float* out, int B, int n, int heads,
+                                 hipStream_t s, float* kstats) {
     static const bool valu_ctx = std::getenv("DM_LINATTN_VALU") != nullptr;
     if (valu_ctx) {
         DM_REQUIRE(!kstats, "DM_LINATTN_VALU: the VALU context kernel does not keep the key statistics");
-        hipLaunchKernelGGL(linattn_ctx_kernel, dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx_ws, n, heads, 4);
+        hipLaunchKernelGGL(linattn_ctx_kernel<DH>, dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx_ws, n, heads, 4);
     } else {
         // waves per (image, head) by the sequence length alone, so that a sample's result does not depend on its batch
         static const int force = std::getenv("DM_LINATTN_CTX_WAVES") ? atoi(std::getenv("DM_LINATTN_CTX_WAVES")) : 0;
         const int nw = force ? force : n >= 1024 ? 16 : n >= 256 ? 8 : 4;
         if (nw == 16)
-            hipLaunchKernelGGL(linattn_ctx_mfma_kernel<16>, dim3(heads, B), dim3(1024), 0, s, qkv, mem_kv, ctx_ws, kstats,
-                               n, heads);
+            hipLaunchKernelGGL((linattn_ctx_mfma_kernel<16, DH>), dim3(heads, B), dim3(1024), 0, s, qkv, mem_kv, ctx_ws,
+                               kstats, n, heads);
         else if (nw == 8)
-            hipLaunchKernelGGL(linattn_ctx_mfma_kernel<8>, dim3(heads, B), dim3(512), 0, s, qkv, mem_kv, ctx_ws, kstats, n,
-                               heads);
+            hipLaunchKernelGGL((linattn_ctx_mfma_kernel<8, DH>), dim3(heads, B), dim3(512), 0, s, qkv, mem_kv, ctx_ws, kstats,
+                               n, heads);
         else
-            hipLaunchKernelGGL(linattn_ctx_mfma_kernel<4>, dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx_ws, kstats, n,
-                               heads);
+            hipLaunchKernelGGL((linattn_ctx_mfma_kernel<4, DH>), dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx_ws, kstats,
+                               n, heads);
     }
     DM_CHECK_HIP(hipGetLastError());
     if (valu_ctx) {
-        size_t lds = (size_t)heads * DH * DH * sizeof(float);
-        hipLaunchKernelGGL(linattn_out_kernel, dim3((n + 63) / 64, B), dim3(64 * heads), lds, s, qkv, ctx_ws, out, n,
-                           heads, 1.0f / sqrtf((float)dh));
+        if (DH == 32) {
+            size_t lds = (size_t)heads * DH * DH * sizeof(float);
+            hipLaunchKernelGGL(linattn_out_kernel<DH>, dim3((n + 63) / 64, B), dim3(64 * heads), lds, s, qkv, ctx_ws, out, n,
+                               heads, 1.0f / sqrtf((float)DH));
+        } else {  // one head per block: heads x 16 KB of context would not fit LDS
+            size_t lds = (size_t)DH * DH * sizeof(float);
+            DM_REQUIRE(B <= 65535, "LinearAttention: batch");
+            hipLaunchKernelGGL(linattn_out_kernel<DH>, dim3((n + 63) / 64, B, heads), dim3(64), lds, s, qkv, ctx_ws, out, n,
+                               heads, 1.0f / sqrtf((float)DH));
+        }
     } else {
         DM_REQUIRE(B <= 65535, "LinearAttention: batch");
-        hipLaunchKernelGGL(linattn_out_mfma_kernel, dim3((n + 63) / 64, heads, B), dim3(64), 0, s, qkv, ctx_ws, out, n, heads,
-                           1.0f / sqrtf((float)dh));
+        hipLaunchKernelGGL(linattn_out_mfma_kernel<DH>, dim3((n + 63) / 64, heads, B), dim3(64), 0, s, qkv, ctx_ws, out, n,
+                           heads, 1.0f / sqrtf((float)DH));
     }
     DM_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+int launch_linear_attention_core(const float* qkv, const float* mem_kv, float* ctx_ws, float* out, int B, int n,
+                                 int heads, int dh, hipStream_t s, float* kstats) {
+    DM_REQUIRE(dh == 32 || dh == 64, "LinearAttention kernels support dim_head 32 and 64");
+    DM_REQUIRE(heads >= 1 && heads <= 16, "LinearAttention kernel supports 1..16 heads");
+    return dh == 32 ? linear_attention_core<32>(qkv, mem_kv, ctx_ws, out, B, n, heads, s, kstats)
+                    : linear_attention_core<64>(qkv, mem_kv, ctx_ws, out, B, n, heads, s, kstats);
 }
 
 // ---------------------------------------------------------------------------------------
 // softmax(q k^T * scale) v for short sequences; K and V of one (batch, head) live in LDS.
 // grid (heads, B), 256 threads (4 waves, one query row per wave at a time).
 // ---------------------------------------------------------------------------------------
+template <int DH>
 __global__ __launch_bounds__(256) void attention_core_kernel(const float* __restrict__ q, int ldq,
                                                              const float* __restrict__ k,
                                                              const float* __restrict__ v, int ldk,
@@ -410,6 +543,7 @@ __global__ __launch_bounds__(256) void attention_core_kernel(const float* __rest
                                                              const float* __restrict__ mem_v, int n_mem,
                                                              float* __restrict__ out, int ldo, int nq, int nk,
                                                              float scale) {
+    constexpr int LDH = log2_dh<DH>();
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int h = blockIdx.x, b = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -419,7 +553,7 @@ __global__ __launch_bounds__(256) void attention_core_kernel(const float* __rest
     float* Ps = Vs + ntok * DH;          // [4][ntok]
     float* Qs = Ps + 4 * ntok;           // [4][DH]
     for (int it = tid; it < ntok * DH; it += 256) {
-        int t = it >> 5, c = it & 31;
+        int t = it >> LDH, c = it & (DH - 1);
         float kv, vvv;
         if (t < n_mem) {
             kv = mem_k[((size_t)h * n_mem + t) * DH + c];
@@ -457,20 +591,27 @@ __global__ __launch_bounds__(256) void attention_core_kernel(const float* __rest
         }
         sum = wave_sum64(sum);
         __builtin_amdgcn_wave_barrier();
-        // out[d] = sum_j p_j v[j][d]; lane = (half, d): halves split the keys
-        const int d = lane & 31, half = lane >> 5;
-        float acc = 0.f;
-        for (int j = half; j < ntok; j += 2) acc += pw[j] * Vs[j * DH + d];
-        acc += __shfl_xor(acc, 32);
-        if (lane < DH) out[((size_t)b * nq + i) * ldo + h * DH + d] = acc / sum;
+        if constexpr (DH == 32) {
+            // out[d] = sum_j p_j v[j][d]; lane = (half, d): halves split the keys
+            const int d = lane & 31, half = lane >> 5;
+            float acc = 0.f;
+            for (int j = half; j < ntok; j += 2) acc += pw[j] * Vs[j * DH + d];
+            acc += __shfl_xor(acc, 32);
+            if (lane < DH) out[((size_t)b * nq + i) * ldo + h * DH + d] = acc / sum;
+        } else {  // lane = d
+            float acc = 0.f;
+            for (int j = 0; j < ntok; ++j) acc += pw[j] * Vs[j * DH + lane];
+            out[((size_t)b * nq + i) * ldo + h * DH + lane] = acc / sum;
+        }
         __builtin_amdgcn_wave_barrier();
     }
 }
 
-// The same for sequences whose K and V do not fit LDS: one wave per 64 queries (lane = query, its q row and the 32
+// The same for sequences whose K and V do not fit LDS: one wave per 64 queries (lane = query, its q row and the DH
 // accumulators in registers), the keys stream through LDS in tiles of 64 twice (row maximum; then exp, row sum and P V) --
 // two passes instead of an online rescale keep the arithmetic that of softmax() followed by the product.
 // grid (ceil(nq / 64), heads, B), 64 threads.
+template <int DH>
 __global__ __launch_bounds__(64) void attention_core_tiled_kernel(const float* __restrict__ q, int ldq,
                                                                   const float* __restrict__ k,
                                                                   const float* __restrict__ v, int ldk,
@@ -478,6 +619,7 @@ __global__ __launch_bounds__(64) void attention_core_tiled_kernel(const float* _
                                                                   const float* __restrict__ mem_v, int n_mem,
                                                                   float* __restrict__ out, int ldo, int nq, int nk,
                                                                   float scale) {
+    constexpr int LDH = log2_dh<DH>();
     __shared__ float Ks[64 * (DH + 1)], Vs[64 * (DH + 1)];
     const int h = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
     const int i = blockIdx.x * 64 + lane, ntok = nk + n_mem;
@@ -493,7 +635,7 @@ __global__ __launch_bounds__(64) void attention_core_tiled_kernel(const float* _
         for (int j0 = 0; j0 < ntok; j0 += 64) {
             __syncthreads();
             for (int e = lane; e < 64 * DH; e += 64) {
-                const int t = j0 + (e >> 5), c = e & 31;
+                const int t = j0 + (e >> LDH), c = e & (DH - 1);
                 float kv = 0.f, vvv = 0.f;
                 if (t < ntok) {
                     if (t < n_mem) {
@@ -505,8 +647,8 @@ __global__ __launch_bounds__(64) void attention_core_tiled_kernel(const float* _
                         vvv = v[o];
                     }
                 }
-                Ks[(e >> 5) * (DH + 1) + c] = kv;
-                Vs[(e >> 5) * (DH + 1) + c] = vvv;
+                Ks[(e >> LDH) * (DH + 1) + c] = kv;
+                Vs[(e >> LDH) * (DH + 1) + c] = vvv;
             }
             __syncthreads();
             const int jn = min(64, ntok - j0);
@@ -532,10 +674,10 @@ __global__ __launch_bounds__(64) void attention_core_tiled_kernel(const float* _
     for (int c = 0; c < DH; c += 4) *reinterpret_cast<float4*>(o + c) = make_float4(acc[c] * inv, acc[c + 1] * inv, acc[c + 2] * inv, acc[c + 3] * inv);
 }
 
-int launch_attention_core(const float* q, int ldq, const float* k, const float* v, int ldk, const float* mem_k,
-                          const float* mem_v, int n_mem, float* out, int ldo, int B, int nq, int nk, int heads,
-                          int dh, float scale, hipStream_t s) {
-    DM_REQUIRE(dh == DH, "attention kernel is specialised for dim_head == 32");
+template <int DH>
+static int attention_core(const float* q, int ldq, const float* k, const float* v, int ldk, const float* mem_k,
+                          const float* mem_v, int n_mem, float* out, int ldo, int B, int nq, int nk, int heads, float scale,
+                          hipStream_t s) {
     int ntok = nk + n_mem;
     size_t lds = ((size_t)ntok * (DH + 1) + (size_t)ntok * DH + 4 * (size_t)ntok + 4 * DH) * sizeof(float);
     static const bool force_tiled = std::getenv("DM_ATTN_TILED") != nullptr;  // tests: the tiled form on short sequences
@@ -544,18 +686,26 @@ int launch_attention_core(const float* q, int ldq, const float* k, const float* 
     static const int tiled_min = env_int("DM_ATTN_TILED_MIN", 320);
     if (lds > 160 * 1024 || ntok > tiled_min || force_tiled) {
         DM_REQUIRE(B <= 65535 && heads <= 65535 && ldo % 4 == 0, "attention: batch / row stride");
-        hipLaunchKernelGGL(attention_core_tiled_kernel, dim3((nq + 63) / 64, heads, B), dim3(64), 0, s, q, ldq, k, v, ldk,
-                           mem_k, mem_v, n_mem, out, ldo, nq, nk, scale);
+        hipLaunchKernelGGL(attention_core_tiled_kernel<DH>, dim3((nq + 63) / 64, heads, B), dim3(64), 0, s, q, ldq, k, v,
+                           ldk, mem_k, mem_v, n_mem, out, ldo, nq, nk, scale);
         DM_CHECK_HIP(hipGetLastError());
         return 0;
     }
     static LdsOptIn lds_flag;
-    if (lds_opt_in(lds_flag, reinterpret_cast<const void*>(attention_core_kernel), 1)) return 1;
+    if (lds_opt_in(lds_flag, reinterpret_cast<const void*>(attention_core_kernel<DH>), 1)) return 1;
     const int qblocks = std::max(1, std::min((nq + 3) / 4, (512 + heads * B - 1) / (heads * B)));
-    hipLaunchKernelGGL(attention_core_kernel, dim3(heads, B, qblocks), dim3(256), lds, s, q, ldq, k, v, ldk, mem_k,
+    hipLaunchKernelGGL(attention_core_kernel<DH>, dim3(heads, B, qblocks), dim3(256), lds, s, q, ldq, k, v, ldk, mem_k,
                        mem_v, n_mem, out, ldo, nq, nk, scale);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+int launch_attention_core(const float* q, int ldq, const float* k, const float* v, int ldk, const float* mem_k,
+                          const float* mem_v, int n_mem, float* out, int ldo, int B, int nq, int nk, int heads,
+                          int dh, float scale, hipStream_t s) {
+    DM_REQUIRE(dh == 32 || dh == 64, "attention kernels support dim_head 32 and 64");
+    return dh == 32 ? attention_core<32>(q, ldq, k, v, ldk, mem_k, mem_v, n_mem, out, ldo, B, nq, nk, heads, scale, s)
+                    : attention_core<64>(q, ldq, k, v, ldk, mem_k, mem_v, n_mem, out, ldo, B, nq, nk, heads, scale, s);
 }
 
 }  // namespace dm

@@ -1,7 +1,9 @@
 // Backward of the two attention cores for the training step (autograd of DD/denoising_diffusion.py:179-192
-// LinearAttention and :221-226 + DD/attend.py:109-124 Attention).  dim_head = 32, 4 learned memory key/values.
+// LinearAttention and :221-226 + DD/attend.py:109-124 Attention).  dim_head = 32 or 64, 4 learned memory key/values.
 // qkv / dqkv are NHWC token rows [q(h,d) | k(h,d) | v(h,d)]; the cores hold < 2 % of a step's FLOPs, so these are plain
-// LDS-tiled VALU kernels with a fixed summation order (no atomics).
+// LDS-tiled VALU kernels with a fixed summation order (no atomics).  Every kernel is a template on the head width DH and is
+// instantiated at 32 and 64 (attention.hip); at 64 the 32x32x2 MFMA products of the LinearAttention backward work on 2 x 2
+// tiles of the 64 x 64 context.
 //
 // LinearAttention:  p = softmax_d(q);  qs = p * scale;  ks = softmax_tokens(k_ext);  ctx[d][e] = sum_j ks[d][j] v_ext[e][j];
 //                   out[e][i] = sum_d ctx[d][e] qs[d][i]
@@ -16,35 +18,43 @@
 
 namespace dm {
 
-constexpr int BDH = 32;
 constexpr int NMEM = 4;
+// log2 of a supported head width: row / column of a flattened DH-wide index by shift and mask
+template <int DH>
+constexpr int bwd_log2_dh() {
+    static_assert(DH == 32 || DH == 64, "head widths 32 and 64");
+    return DH == 32 ? 5 : 6;
+}
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 __device__ __forceinline__ f32x4 make_f32x4(float a, float b, float c, float d) { return f32x4{a, b, c, d}; }
 
-constexpr int LSTR = BDH + 4;  // LDS row stride of a token row: 16-byte aligned, 128-bit accesses of 8 consecutive lanes cover all banks
+// LDS row stride of a token row: 16-byte aligned, 128-bit accesses of 8 consecutive lanes cover all banks
+template <int DH>
+constexpr int lstr() { return DH + 4; }
 
 // part 1: grid (ceil(n / 64), heads, B), one wave (lane = token): dq, and this block's share of dctx.  One head per block
 // keeps the tile at 22 KB, so seven blocks share a CU and hide each other's row loads.
+template <int DH>
 __global__ __launch_bounds__(64) void linattn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
                                                            const float* __restrict__ dout, float* __restrict__ dqkv,
                                                            float* __restrict__ dctx_part, int n, int heads, float scale) {
-    __shared__ __attribute__((aligned(16))) float cs[BDH * BDH];   // ctx of this (image, head)
-    __shared__ __attribute__((aligned(16))) float ps[64 * LSTR];   // scale * p
-    __shared__ __attribute__((aligned(16))) float ds[64 * LSTR];   // dout
+    __shared__ __attribute__((aligned(16))) float cs[DH * DH];   // ctx of this (image, head)
+    __shared__ __attribute__((aligned(16))) float ps[64 * lstr<DH>()];   // scale * p
+    __shared__ __attribute__((aligned(16))) float ds[64 * lstr<DH>()];   // dout
     const int blk = blockIdx.x, nblk = gridDim.x, h = blockIdx.y, b = blockIdx.z;
     const int tl = threadIdx.x;
     const int tok = blk * 64 + tl;
-    const int ld = 3 * heads * BDH, hid = heads * BDH;
+    const int ld = 3 * heads * DH, hid = heads * DH;
     {
-        const f32x4* src = reinterpret_cast<const f32x4*>(ctx + (size_t)(b * heads + h) * BDH * BDH);
-        for (int i = tl; i < BDH * BDH / 4; i += 64) reinterpret_cast<f32x4*>(cs)[i] = src[i];
+        const f32x4* src = reinterpret_cast<const f32x4*>(ctx + (size_t)(b * heads + h) * DH * DH);
+        for (int i = tl; i < DH * DH / 4; i += 64) reinterpret_cast<f32x4*>(cs)[i] = src[i];
     }
-    float q[BDH], dq[BDH], dov[BDH];
+    float q[DH], dq[DH], dov[DH];
     const bool ok = tok < n;
-    const f32x4* qp = reinterpret_cast<const f32x4*>(qkv + ((size_t)b * n + (ok ? tok : 0)) * ld + h * BDH);
-    const f32x4* dp = reinterpret_cast<const f32x4*>(dout + ((size_t)b * n + (ok ? tok : 0)) * hid + h * BDH);
+    const f32x4* qp = reinterpret_cast<const f32x4*>(qkv + ((size_t)b * n + (ok ? tok : 0)) * ld + h * DH);
+    const f32x4* dp = reinterpret_cast<const f32x4*>(dout + ((size_t)b * n + (ok ? tok : 0)) * hid + h * DH);
 #pragma unroll
-    for (int j = 0; j < BDH / 4; ++j) {
+    for (int j = 0; j < DH / 4; ++j) {
         const f32x4 a = qp[j], c = dp[j];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -54,10 +64,10 @@ __global__ __launch_bounds__(64) void linattn_bwd_q_kernel(const float* __restri
     }
     float m = -INFINITY;
 #pragma unroll
-    for (int d = 0; d < BDH; ++d) m = fmaxf(m, q[d]);
+    for (int d = 0; d < DH; ++d) m = fmaxf(m, q[d]);
     float sum = 0.f;
 #pragma unroll
-    for (int d = 0; d < BDH; ++d) {
+    for (int d = 0; d < DH; ++d) {
         q[d] = __expf(q[d] - m);
         sum += q[d];
     }
@@ -65,122 +75,128 @@ __global__ __launch_bounds__(64) void linattn_bwd_q_kernel(const float* __restri
     __syncthreads();
     float dot = 0.f;
 #pragma unroll
-    for (int d = 0; d < BDH; ++d) {
+    for (int d = 0; d < DH; ++d) {
         q[d] *= inv;  // p
         float s = 0.f;
-        const float* cr = cs + d * BDH;
+        const float* cr = cs + d * DH;
 #pragma unroll
-        for (int e = 0; e < BDH; ++e) s += cr[e] * dov[e];
+        for (int e = 0; e < DH; ++e) s += cr[e] * dov[e];
         dq[d] = s;  // dqs
         dot += q[d] * s;
     }
     if (ok) {
-        f32x4* o = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + tok) * ld + h * BDH);
+        f32x4* o = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + tok) * ld + h * DH);
 #pragma unroll
-        for (int j = 0; j < BDH / 4; ++j)
+        for (int j = 0; j < DH / 4; ++j)
             o[j] = make_f32x4(scale * q[4 * j] * (dq[4 * j] - dot), scale * q[4 * j + 1] * (dq[4 * j + 1] - dot),
                               scale * q[4 * j + 2] * (dq[4 * j + 2] - dot), scale * q[4 * j + 3] * (dq[4 * j + 3] - dot));
     }
 #pragma unroll
-    for (int j = 0; j < BDH / 4; ++j) {
+    for (int j = 0; j < DH / 4; ++j) {
         const float z = ok ? scale : 0.f;
-        *reinterpret_cast<f32x4*>(ps + tl * LSTR + 4 * j) =
+        *reinterpret_cast<f32x4*>(ps + tl * lstr<DH>() + 4 * j) =
             make_f32x4(z * q[4 * j], z * q[4 * j + 1], z * q[4 * j + 2], z * q[4 * j + 3]);
-        *reinterpret_cast<f32x4*>(ds + tl * LSTR + 4 * j) = make_f32x4(dov[4 * j], dov[4 * j + 1], dov[4 * j + 2], dov[4 * j + 3]);
+        *reinterpret_cast<f32x4*>(ds + tl * lstr<DH>() + 4 * j) = make_f32x4(dov[4 * j], dov[4 * j + 1], dov[4 * j + 2], dov[4 * j + 3]);
     }
     __syncthreads();
-    // dctx share of this block: lane -> (d, 16 e's), tokens in order
+    // dctx share of this block: lane -> (d, EPL e's), tokens in order
     {
-        const int d = tl >> 1, e0 = (tl & 1) * 16;
-        float acc[16];
+        constexpr int EPL = DH * DH / 64, LLPR = DH == 32 ? 1 : 0;  // e's per lane (16 / 64), log2 lanes per row
+        const int d = tl >> LLPR, e0 = (tl & ((1 << LLPR) - 1)) * EPL;
+        float acc[EPL];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+        for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
         for (int t = 0; t < 64; ++t) {
-            const float pv = ps[t * LSTR + d];
-            const f32x4* dr = reinterpret_cast<const f32x4*>(ds + t * LSTR + e0);
+            const float pv = ps[t * lstr<DH>() + d];
+            const f32x4* dr = reinterpret_cast<const f32x4*>(ds + t * lstr<DH>() + e0);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
+            for (int j = 0; j < EPL / 4; ++j) {
                 const f32x4 v = dr[j];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) acc[4 * j + i] += pv * v[i];
             }
         }
-        f32x4* o = reinterpret_cast<f32x4*>(dctx_part + ((((size_t)b * nblk + blk) * heads + h) * BDH + d) * BDH + e0);
+        f32x4* o = reinterpret_cast<f32x4*>(dctx_part + ((((size_t)b * nblk + blk) * heads + h) * DH + d) * DH + e0);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = make_f32x4(acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]);
+        for (int j = 0; j < EPL / 4; ++j) o[j] = make_f32x4(acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]);
     }
 }
 
 // part 2a: grid (heads, B), 256 threads: dctx = sum of the block shares (left in share 0), per d the softmax statistics of
-// k over the tokens (memory tokens first, as the reference concatenates them) and S[d] -> stats (B, heads, 3, 32), and the
-// gradients of this image's 4 memory key/value tokens
+// k over the tokens (memory tokens first, as the reference concatenates them) and S[d] -> stats (B, heads, 3, DH), and the
+// gradients of this image's 4 memory key/value tokens.  The column passes map the 256 threads onto (token stripe, column):
+// 8 stripes of 32 columns, or 4 of 64.
+template <int DH>
 __global__ __launch_bounds__(256) void linattn_bwd_stats_kernel(const float* __restrict__ qkv, const float* __restrict__ mem_kv,
                                                                 const float* __restrict__ ctx, float* __restrict__ dctx_part,
                                                                 int nblk, float* __restrict__ stats,
                                                                 float* __restrict__ dmem_part,
                                                                 const float* __restrict__ kstats, int n, int heads) {
-    __shared__ float dctx[BDH][BDH + 1];
-    __shared__ float kmax[BDH], kinv[BDH], S[BDH];
-    __shared__ float red[8][BDH];
+    constexpr int LDH = bwd_log2_dh<DH>(), NPART = 256 / DH, NJ = DH * DH / 256;
+    __shared__ float dctx[DH][DH + 1];
+    __shared__ float kmax[DH], kinv[DH], S[DH];
+    __shared__ float red[NPART][DH];
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int ld = 3 * heads * BDH;
-    const float* kbase = qkv + (size_t)b * n * ld + heads * BDH + h * BDH;
-    const float* mk = mem_kv + (size_t)h * BDH * NMEM;  // [d][j]
+    const int ld = 3 * heads * DH;
+    const float* kbase = qkv + (size_t)b * n * ld + heads * DH + h * DH;
+    const float* mk = mem_kv + (size_t)h * DH * NMEM;  // [d][j]
     {  // the block shares of dctx, summed in block order; the 4 elements of a thread x 4 shares are in flight together
-        float s[4] = {0.f, 0.f, 0.f, 0.f};
-        const float* src = dctx_part + ((size_t)b * nblk * heads + h) * BDH * BDH + tid;
-        const size_t kst = (size_t)heads * BDH * BDH;
+        float s[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) s[j] = 0.f;
+        const float* src = dctx_part + ((size_t)b * nblk * heads + h) * DH * DH + tid;
+        const size_t kst = (size_t)heads * DH * DH;
         int k = 0;
         for (; k + 4 <= nblk; k += 4) {
-            float v[4][4];
+            float v[4][NJ];
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[kk][j] = src[(k + kk) * kst + 256 * j];
+                for (int j = 0; j < NJ; ++j) v[kk][j] = src[(k + kk) * kst + 256 * j];
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) s[j] += v[kk][j];
+                for (int j = 0; j < NJ; ++j) s[j] += v[kk][j];
         }
         for (; k < nblk; ++k)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) s[j] += src[k * kst + 256 * j];
+            for (int j = 0; j < NJ; ++j) s[j] += src[k * kst + 256 * j];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < NJ; ++j) {
             const int i = tid + 256 * j;
-            dctx[i >> 5][i & 31] = s[j];
-            dctx_part[((size_t)b * nblk * heads + h) * BDH * BDH + i] = s[j];
+            dctx[i >> LDH][i & (DH - 1)] = s[j];
+            dctx_part[((size_t)b * nblk * heads + h) * DH * DH + i] = s[j];
         }
     }
     // kstats (max and sum over tokens of exp(k - max), per column) as the forward context kernel left them on the tape; without
     // them (kstats == nullptr) the two passes over the n key rows are redone here, 8 lanes deep per column
     if (kstats) {
-        if (tid < BDH) {
-            kmax[tid] = kstats[(size_t)(b * heads + h) * 2 * BDH + tid];
-            red[0][tid] = kstats[(size_t)(b * heads + h) * 2 * BDH + BDH + tid];
-        } else if (tid < 8 * BDH) {
-            red[tid >> 5][tid & 31] = 0.f;
+        if (tid < DH) {
+            kmax[tid] = kstats[(size_t)(b * heads + h) * 2 * DH + tid];
+            red[0][tid] = kstats[(size_t)(b * heads + h) * 2 * DH + DH + tid];
+        } else if (tid < NPART * DH) {
+            red[tid >> LDH][tid & (DH - 1)] = 0.f;
         }
         __syncthreads();
     } else {
-        const int d = tid & 31, part = tid >> 5;
+        const int d = tid & (DH - 1), part = tid >> LDH;
         float m = part < NMEM ? mk[d * NMEM + part] : -INFINITY;
         {
             int t = part;
-            for (; t + 56 < n; t += 64) {  // 8 independent row loads in flight
+            for (; t + 7 * NPART < n; t += 8 * NPART) {  // 8 independent row loads in flight
                 float kv[8];
     #pragma unroll
-                for (int j = 0; j < 8; ++j) kv[j] = kbase[(size_t)(t + 8 * j) * ld + d];
+                for (int j = 0; j < 8; ++j) kv[j] = kbase[(size_t)(t + NPART * j) * ld + d];
     #pragma unroll
                 for (int j = 0; j < 8; ++j) m = fmaxf(m, kv[j]);
             }
-            for (; t < n; t += 8) m = fmaxf(m, kbase[(size_t)t * ld + d]);
+            for (; t < n; t += NPART) m = fmaxf(m, kbase[(size_t)t * ld + d]);
         }
         red[part][d] = m;
         __syncthreads();
-        if (tid < BDH) {
+        if (tid < DH) {
             float mm = red[0][tid];
-            for (int q = 1; q < 8; ++q) mm = fmaxf(mm, red[q][tid]);
+            for (int q = 1; q < NPART; ++q) mm = fmaxf(mm, red[q][tid]);
             kmax[tid] = mm;
         }
         __syncthreads();
@@ -188,145 +204,150 @@ __global__ __launch_bounds__(256) void linattn_bwd_stats_kernel(const float* __r
         float s = part < NMEM ? __expf(mk[d * NMEM + part] - km) : 0.f;
         {
             int t = part;
-            for (; t + 56 < n; t += 64) {
+            for (; t + 7 * NPART < n; t += 8 * NPART) {
                 float kv[8];
     #pragma unroll
-                for (int j = 0; j < 8; ++j) kv[j] = kbase[(size_t)(t + 8 * j) * ld + d];
+                for (int j = 0; j < 8; ++j) kv[j] = kbase[(size_t)(t + NPART * j) * ld + d];
     #pragma unroll
                 for (int j = 0; j < 8; ++j) s += __expf(kv[j] - km);
             }
-            for (; t < n; t += 8) s += __expf(kbase[(size_t)t * ld + d] - km);
+            for (; t < n; t += NPART) s += __expf(kbase[(size_t)t * ld + d] - km);
         }
         __syncthreads();
         red[part][d] = s;
         __syncthreads();
     }
-    if (tid < BDH) {
+    if (tid < DH) {
         float ss = 0.f;
-        for (int q = 0; q < 8; ++q) ss += red[q][tid];
-        const float* cr = ctx + ((size_t)(b * heads + h) * BDH + tid) * BDH;
+        for (int q = 0; q < NPART; ++q) ss += red[q][tid];
+        const float* cr = ctx + ((size_t)(b * heads + h) * DH + tid) * DH;
         float sd = 0.f;
-        for (int e = 0; e < BDH; ++e) sd += dctx[tid][e] * cr[e];
-        float* st = stats + (size_t)(b * heads + h) * 3 * BDH;
+        for (int e = 0; e < DH; ++e) sd += dctx[tid][e] * cr[e];
+        float* st = stats + (size_t)(b * heads + h) * 3 * DH;
         st[tid] = kmax[tid];
-        st[BDH + tid] = kinv[tid] = 1.0f / ss;
-        st[2 * BDH + tid] = S[tid] = sd;
+        st[DH + tid] = kinv[tid] = 1.0f / ss;
+        st[2 * DH + tid] = S[tid] = sd;
     }
     __syncthreads();
-    if (tid < NMEM * BDH) {  // memory tokens: thread (t, x) forms dk[d = x][t] and dv[e = x][t]
-        const int t = tid >> 5, x = tid & 31;
-        const float* mv = mem_kv + (size_t)(heads + h) * BDH * NMEM;  // [e][j]
+    if (tid < NMEM * DH) {  // memory tokens: thread (t, x) forms dk[d = x][t] and dv[e = x][t]
+        const int t = tid >> LDH, x = tid & (DH - 1);
+        const float* mv = mem_kv + (size_t)(heads + h) * DH * NMEM;  // [e][j]
         float sk = 0.f, sv = 0.f;
-        for (int j = 0; j < BDH; ++j) {
+        for (int j = 0; j < DH; ++j) {
             sk += dctx[x][j] * mv[j * NMEM + t];
             sv += __expf(mk[j * NMEM + t] - kmax[j]) * kinv[j] * dctx[j][x];
         }
-        float* o = dmem_part + (size_t)b * 2 * heads * BDH * NMEM;
-        o[((size_t)h * BDH + x) * NMEM + t] = __expf(mk[x * NMEM + t] - kmax[x]) * kinv[x] * (sk - S[x]);
-        o[((size_t)(heads + h) * BDH + x) * NMEM + t] = sv;
+        float* o = dmem_part + (size_t)b * 2 * heads * DH * NMEM;
+        o[((size_t)h * DH + x) * NMEM + t] = __expf(mk[x * NMEM + t] - kmax[x]) * kinv[x] * (sk - S[x]);
+        o[((size_t)(heads + h) * DH + x) * NMEM + t] = sv;
     }
 }
 
 // part 2b: grid (ceil(n / 64), heads, B), one wave (lane = token): dk, dv.  k and v rows sit in registers; dk overwrites k
 // row by row.
-__global__ __launch_bounds__(64, 3) void linattn_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ dctx_part,
+template <int DH>
+__global__ __launch_bounds__(64, DH == 32 ? 3 : 1) void linattn_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ dctx_part,
                                                             int nblk, const float* __restrict__ stats, float* __restrict__ dqkv,
                                                             int n, int heads) {
-    __shared__ __attribute__((aligned(16))) float dctx[BDH * BDH];
-    __shared__ float st[3 * BDH];
+    __shared__ __attribute__((aligned(16))) float dctx[DH * DH];
+    __shared__ float st[3 * DH];
     const int h = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
-    const int ld = 3 * heads * BDH;
+    const int ld = 3 * heads * DH;
     {
-        const f32x4* src = reinterpret_cast<const f32x4*>(dctx_part + ((size_t)b * nblk * heads + h) * BDH * BDH);
-        for (int i = lane; i < BDH * BDH / 4; i += 64) reinterpret_cast<f32x4*>(dctx)[i] = src[i];
-        for (int i = lane; i < 3 * BDH; i += 64) st[i] = stats[(size_t)(b * heads + h) * 3 * BDH + i];
+        const f32x4* src = reinterpret_cast<const f32x4*>(dctx_part + ((size_t)b * nblk * heads + h) * DH * DH);
+        for (int i = lane; i < DH * DH / 4; i += 64) reinterpret_cast<f32x4*>(dctx)[i] = src[i];
+        for (int i = lane; i < 3 * DH; i += 64) st[i] = stats[(size_t)(b * heads + h) * 3 * DH + i];
     }
     __syncthreads();
     const int t = blockIdx.x * 64 + lane;
     if (t >= n) return;
-    // two passes over dctx, so that only two 32-vectors and one dctx row are live at a time (one pass holding k, v, dv and
+    // two passes over dctx, so that only two DH-vectors and one dctx row are live at a time (one pass holding k, v, dv and
     // the prefetched rows spills at 3 waves per SIMD):  dv[e] = sum_d ks[d] dctx[d][e], then dk[d] = ks[d] (dctx[d] . v - S[d])
-    float kk[BDH], vv[BDH];
-    const f32x4* kp = reinterpret_cast<const f32x4*>(qkv + ((size_t)b * n + t) * ld + heads * BDH + h * BDH);
-    const f32x4* vp = reinterpret_cast<const f32x4*>(qkv + ((size_t)b * n + t) * ld + 2 * heads * BDH + h * BDH);
-    f32x4* ok = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + t) * ld + heads * BDH + h * BDH);
-    f32x4* ov = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + t) * ld + 2 * heads * BDH + h * BDH);
+    float kk[DH], vv[DH];
+    const f32x4* kp = reinterpret_cast<const f32x4*>(qkv + ((size_t)b * n + t) * ld + heads * DH + h * DH);
+    const f32x4* vp = reinterpret_cast<const f32x4*>(qkv + ((size_t)b * n + t) * ld + 2 * heads * DH + h * DH);
+    f32x4* ok = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + t) * ld + heads * DH + h * DH);
+    f32x4* ov = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + t) * ld + 2 * heads * DH + h * DH);
 #pragma unroll
-    for (int j = 0; j < BDH / 4; ++j) {
+    for (int j = 0; j < DH / 4; ++j) {
         const f32x4 a = kp[j];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            kk[4 * j + i] = __expf(a[i] - st[4 * j + i]) * st[BDH + 4 * j + i];  // ks
+            kk[4 * j + i] = __expf(a[i] - st[4 * j + i]) * st[DH + 4 * j + i];  // ks
             vv[4 * j + i] = 0.f;                                                 // dv
         }
     }
 #pragma unroll
-    for (int d = 0; d < BDH; ++d) {
+    for (int d = 0; d < DH; ++d) {
 #pragma unroll
-        for (int e = 0; e < BDH; ++e) vv[e] += kk[d] * dctx[d * BDH + e];
+        for (int e = 0; e < DH; ++e) vv[e] += kk[d] * dctx[d * DH + e];
         asm volatile("" ::: "memory");  // one dctx row in flight
     }
 #pragma unroll
-    for (int j = 0; j < BDH / 4; ++j) ov[j] = make_f32x4(vv[4 * j], vv[4 * j + 1], vv[4 * j + 2], vv[4 * j + 3]);
+    for (int j = 0; j < DH / 4; ++j) ov[j] = make_f32x4(vv[4 * j], vv[4 * j + 1], vv[4 * j + 2], vv[4 * j + 3]);
     asm volatile("" ::: "memory");
 #pragma unroll
-    for (int j = 0; j < BDH / 4; ++j) {
+    for (int j = 0; j < DH / 4; ++j) {
         const f32x4 c = vp[j];
 #pragma unroll
         for (int i = 0; i < 4; ++i) vv[4 * j + i] = c[i];
     }
 #pragma unroll
-    for (int d = 0; d < BDH; ++d) {
+    for (int d = 0; d < DH; ++d) {
         float s = 0.f;
 #pragma unroll
-        for (int e = 0; e < BDH; ++e) s += dctx[d * BDH + e] * vv[e];
-        kk[d] *= s - st[2 * BDH + d];  // dk
+        for (int e = 0; e < DH; ++e) s += dctx[d * DH + e] * vv[e];
+        kk[d] *= s - st[2 * DH + d];  // dk
         asm volatile("" ::: "memory");
     }
 #pragma unroll
-    for (int j = 0; j < BDH / 4; ++j) ok[j] = make_f32x4(kk[4 * j], kk[4 * j + 1], kk[4 * j + 2], kk[4 * j + 3]);
+    for (int j = 0; j < DH / 4; ++j) ok[j] = make_f32x4(kk[4 * j], kk[4 * j + 1], kk[4 * j + 2], kk[4 * j + 3]);
 }
 
 // ---- the same two passes on the matrix core (v_mfma_f32_32x32x2_f32), what the training step runs.  Every product of the
-// backward pass is a (tokens x 32) x (32 x 32) GEMM; computed TRANSPOSED -- the 32 x 32 matrix (ctx, dctx) is the A operand, the
-// token rows the B operand -- the result D[i][j = token] leaves lane (token, half) with the 16 columns
+// backward pass is a (tokens x DH) x (DH x DH) GEMM; computed TRANSPOSED -- the DH x DH matrix (ctx, dctx) is the A operand, the
+// token rows the B operand -- the result D[i][j = token] of a 32-row tile leaves lane (token, half) with the 16 columns
 //     dset(r) = (r & 3) + 8 (r >> 2) + 4 half,   r = 0 .. 15      (four float4 chunks 2 m + half of the token's 32-float row)
-// of its token, and with the K index enumerated in the same order (k-step s of half h = column dset(s)) the B operand of the
-// next product is exactly those registers: a lane loads 4 chunks of q / dout / k / v, keeps everything row-wise (softmax over
-// the columns, the dot products) in registers plus one exchange with lane ^ 32, and stores 4 chunks.  One wave = 64 tokens (two
-// 32-token tiles), 64 MFMAs per pass where the VALU form issued ~2000 FMAs and ~600 LDS broadcasts per lane.
+// of its token, and with the K index enumerated in the same order (k-step s of half h = column dset(s), s < DH / 2) the B
+// operand of the next product is exactly those registers: a lane loads DH / 8 chunks of q / dout / k / v, keeps everything
+// row-wise (softmax over the columns, the dot products) in registers plus one exchange with lane ^ 32, and stores them.  At
+// DH = 64 tile I of a result holds the columns 32 I + dset(r) = dset(16 I + r): the same registers.  One wave = 64 tokens (two
+// 32-token tiles), 64 MFMAs per pass at DH = 32 where the VALU form issued ~2000 FMAs and ~600 LDS broadcasts per lane.
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
+template <int DH>
 __global__ __launch_bounds__(64) void linattn_bwd_q_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
                                                                 const float* __restrict__ dout, float* __restrict__ dqkv,
                                                                 float* __restrict__ dctx_part, int n, int heads, float scale) {
-    __shared__ __attribute__((aligned(16))) float ps[64 * LSTR];  // scale * p, [token][d]
-    __shared__ __attribute__((aligned(16))) float ds[64 * LSTR];  // dout,      [token][e]
+    constexpr int NT = DH / 32, NS = DH / 2;  // 32-wide tiles per side; registers (k-steps) per row and lane
+    __shared__ __attribute__((aligned(16))) float ps[64 * lstr<DH>()];  // scale * p, [token][d]
+    __shared__ __attribute__((aligned(16))) float ds[64 * lstr<DH>()];  // dout,      [token][e]
     const int blk = blockIdx.x, nblk = gridDim.x, h = blockIdx.y, b = blockIdx.z;
     const int lane = threadIdx.x, l31 = lane & 31, half = lane >> 5;
-    const int ld = 3 * heads * BDH, hid = heads * BDH;
-    // A operand of dqs^T = ctx . dout^T: ctx[d = l31][e = dset(s)]
-    float actx[16];
-    {
-        const f32x4* cr = reinterpret_cast<const f32x4*>(ctx + ((size_t)(b * heads + h) * BDH + l31) * BDH);
+    const int ld = 3 * heads * DH, hid = heads * DH;
+    // A operand of dqs^T = ctx . dout^T: ctx[d = 32 I + l31][e = dset(s)]
+    float actx[NT][NS];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+    for (int I = 0; I < NT; ++I) {
+        const f32x4* cr = reinterpret_cast<const f32x4*>(ctx + ((size_t)(b * heads + h) * DH + 32 * I + l31) * DH);
+#pragma unroll
+        for (int m = 0; m < NS / 4; ++m) {
             const f32x4 v = cr[2 * m + half];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) actx[4 * m + i] = v[i];
+            for (int i = 0; i < 4; ++i) actx[I][4 * m + i] = v[i];
         }
     }
-    float p[2][16], dv[2][16];
+    float p[2][NS], dv[2][NS];
     bool okt[2];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
         const int tok = blk * 64 + nt * 32 + l31;
         okt[nt] = tok < n;
         const size_t row = (size_t)b * n + (okt[nt] ? tok : 0);
-        const f32x4* qp = reinterpret_cast<const f32x4*>(qkv + row * ld + h * BDH);
-        const f32x4* dp = reinterpret_cast<const f32x4*>(dout + row * hid + h * BDH);
+        const f32x4* qp = reinterpret_cast<const f32x4*>(qkv + row * ld + h * DH);
+        const f32x4* dp = reinterpret_cast<const f32x4*>(dout + row * hid + h * DH);
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+        for (int m = 0; m < NS / 4; ++m) {
             const f32x4 a = qp[2 * m + half], c = dp[2 * m + half];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -339,42 +360,52 @@ __global__ __launch_bounds__(64) void linattn_bwd_q_mfma_kernel(const float* __r
     for (int nt = 0; nt < 2; ++nt) {
         float m = -INFINITY;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) m = fmaxf(m, p[nt][r]);
+        for (int r = 0; r < NS; ++r) m = fmaxf(m, p[nt][r]);
         m = fmaxf(m, __shfl_xor(m, 32));
         float sum = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
+        for (int r = 0; r < NS; ++r) {
             p[nt][r] = __expf(p[nt][r] - m);
             sum += p[nt][r];
         }
         sum += __shfl_xor(sum, 32);
         const float inv = 1.0f / sum;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) p[nt][r] *= inv;
-        f32x16 acc;
+        for (int r = 0; r < NS; ++r) p[nt][r] *= inv;
+        f32x16 acc[NT];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        for (int I = 0; I < NT; ++I)
 #pragma unroll
-        for (int s = 0; s < 16; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(actx[s], dv[nt][s], acc, 0, 0, 0);
+            for (int r = 0; r < 16; ++r) acc[I][r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int I = 0; I < NT; ++I) acc[I] = __builtin_amdgcn_mfma_f32_32x32x2f32(actx[I][s], dv[nt][s], acc[I], 0, 0, 0);
         float dot = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dot += p[nt][r] * acc[r];
+        for (int I = 0; I < NT; ++I)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dot += p[nt][16 * I + r] * acc[I][r];
         dot += __shfl_xor(dot, 32);
         const int tok = blk * 64 + nt * 32 + l31;
         if (okt[nt]) {
-            f32x4* o = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + tok) * ld + h * BDH);
+            f32x4* o = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + tok) * ld + h * DH);
 #pragma unroll
-            for (int m4 = 0; m4 < 4; ++m4)
-                o[2 * m4 + half] = make_f32x4(scale * p[nt][4 * m4] * (acc[4 * m4] - dot),
-                                              scale * p[nt][4 * m4 + 1] * (acc[4 * m4 + 1] - dot),
-                                              scale * p[nt][4 * m4 + 2] * (acc[4 * m4 + 2] - dot),
-                                              scale * p[nt][4 * m4 + 3] * (acc[4 * m4 + 3] - dot));
+            for (int I = 0; I < NT; ++I)
+#pragma unroll
+                for (int m4 = 0; m4 < 4; ++m4) {
+                    const float* pp = &p[nt][16 * I + 4 * m4];
+                    o[8 * I + 2 * m4 + half] = make_f32x4(scale * pp[0] * (acc[I][4 * m4] - dot),
+                                                          scale * pp[1] * (acc[I][4 * m4 + 1] - dot),
+                                                          scale * pp[2] * (acc[I][4 * m4 + 2] - dot),
+                                                          scale * pp[3] * (acc[I][4 * m4 + 3] - dot));
+                }
         }
         const float z = okt[nt] ? scale : 0.f;
-        float* pr = ps + (nt * 32 + l31) * LSTR;
-        float* dr = ds + (nt * 32 + l31) * LSTR;
+        float* pr = ps + (nt * 32 + l31) * lstr<DH>();
+        float* dr = ds + (nt * 32 + l31) * lstr<DH>();
 #pragma unroll
-        for (int m4 = 0; m4 < 4; ++m4) {
+        for (int m4 = 0; m4 < NS / 4; ++m4) {
             *reinterpret_cast<f32x4*>(pr + 4 * (2 * m4 + half)) =
                 make_f32x4(z * p[nt][4 * m4], z * p[nt][4 * m4 + 1], z * p[nt][4 * m4 + 2], z * p[nt][4 * m4 + 3]);
             *reinterpret_cast<f32x4*>(dr + 4 * (2 * m4 + half)) =
@@ -382,37 +413,64 @@ __global__ __launch_bounds__(64) void linattn_bwd_q_mfma_kernel(const float* __r
         }
     }
     __syncthreads();
-    // dctx share of this block: D[i = d][j = e] = sum over the 64 tokens (k-step s, half -> token 2 s + half) ps[t][d] ds[t][e]
-    f32x16 acc;
+    // dctx share of this block: D[i = d][j = e] = sum over the 64 tokens (k-step s, half -> token 2 s + half) ps[t][d] ds[t][e],
+    // tile (I, J) = (d, e) in [32 I, 32 I + 32) x [32 J, 32 J + 32)
+    f32x16 acc[NT][NT];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int I = 0; I < NT; ++I)
 #pragma unroll
-    for (int s = 0; s < 32; ++s)
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ps[(2 * s + half) * LSTR + l31], ds[(2 * s + half) * LSTR + l31], acc, 0, 0, 0);
-    float* o = dctx_part + (((size_t)b * nblk + blk) * heads + h) * BDH * BDH;
+        for (int J = 0; J < NT; ++J)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2) + 4 * half) * BDH + l31] = acc[r];
+            for (int r = 0; r < 16; ++r) acc[I][J][r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < 32; ++s) {
+        float pa[NT], db[NT];
+#pragma unroll
+        for (int I = 0; I < NT; ++I) {
+            pa[I] = ps[(2 * s + half) * lstr<DH>() + 32 * I + l31];
+            db[I] = ds[(2 * s + half) * lstr<DH>() + 32 * I + l31];
+        }
+#pragma unroll
+        for (int I = 0; I < NT; ++I)
+#pragma unroll
+            for (int J = 0; J < NT; ++J) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[I], db[J], acc[I][J], 0, 0, 0);
+    }
+    float* o = dctx_part + (((size_t)b * nblk + blk) * heads + h) * DH * DH;
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+        for (int J = 0; J < NT; ++J)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[(32 * I + (r & 3) + 8 * (r >> 2) + 4 * half) * DH + 32 * J + l31] = acc[I][J][r];
 }
 
+template <int DH>
 __global__ __launch_bounds__(64) void linattn_bwd_kv_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ dctx_part,
                                                                  int nblk, const float* __restrict__ stats,
                                                                  float* __restrict__ dqkv, int n, int heads) {
+    constexpr int NT = DH / 32, NS = DH / 2;
     const int blk = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const int lane = threadIdx.x, l31 = lane & 31, half = lane >> 5;
-    const int ld = 3 * heads * BDH;
-    const float* dctx = dctx_part + ((size_t)b * nblk * heads + h) * BDH * BDH;  // share 0 holds the sum
-    // A operands: dv^T = dctx^T . ks^T needs dctx[d = dset(s)][e = l31]; dks^T = dctx . v^T needs dctx[d = l31][e = dset(s)]
-    float a3[16], a4[16], kmax[16], kinv[16], S[16];
+    const int ld = 3 * heads * DH;
+    const float* dctx = dctx_part + ((size_t)b * nblk * heads + h) * DH * DH;  // share 0 holds the sum
+    // A operands: dv^T = dctx^T . ks^T needs dctx[d = dset(s)][e = 32 J + l31]; dks^T = dctx . v^T needs
+    // dctx[d = 32 I + l31][e = dset(s)]
+    float a3[NT][NS], a4[NT][NS], kmax[NS], kinv[NS], S[NS];
     {
-        const f32x4* row = reinterpret_cast<const f32x4*>(dctx + l31 * BDH);
-        const f32x4* st = reinterpret_cast<const f32x4*>(stats + (size_t)(b * heads + h) * 3 * BDH);
+        const f32x4* st = reinterpret_cast<const f32x4*>(stats + (size_t)(b * heads + h) * 3 * DH);
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const f32x4 v = row[2 * m + half], s0 = st[2 * m + half], s1 = st[8 + 2 * m + half], s2 = st[16 + 2 * m + half];
+        for (int m = 0; m < NS / 4; ++m) {
+            f32x4 v[NT];
+#pragma unroll
+            for (int I = 0; I < NT; ++I) v[I] = reinterpret_cast<const f32x4*>(dctx + (32 * I + l31) * DH)[2 * m + half];
+            const f32x4 s0 = st[2 * m + half], s1 = st[DH / 4 + 2 * m + half], s2 = st[DH / 2 + 2 * m + half];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                a4[4 * m + i] = v[i];
-                a3[4 * m + i] = dctx[(8 * m + 4 * half + i) * BDH + l31];
+#pragma unroll
+                for (int I = 0; I < NT; ++I) {
+                    a4[I][4 * m + i] = v[I][i];
+                    a3[I][4 * m + i] = dctx[(8 * m + 4 * half + i) * DH + 32 * I + l31];
+                }
                 kmax[4 * m + i] = s0[i];
                 kinv[4 * m + i] = s1[i];
                 S[4 * m + i] = s2[i];
@@ -424,11 +482,11 @@ __global__ __launch_bounds__(64) void linattn_bwd_kv_mfma_kernel(const float* __
         const int tok = blk * 64 + nt * 32 + l31;
         const bool ok = tok < n;
         const size_t row = (size_t)b * n + (ok ? tok : 0);
-        const f32x4* kp = reinterpret_cast<const f32x4*>(qkv + row * ld + heads * BDH + h * BDH);
-        const f32x4* vp = reinterpret_cast<const f32x4*>(qkv + row * ld + 2 * heads * BDH + h * BDH);
-        float ks[16], vv[16];
+        const f32x4* kp = reinterpret_cast<const f32x4*>(qkv + row * ld + heads * DH + h * DH);
+        const f32x4* vp = reinterpret_cast<const f32x4*>(qkv + row * ld + 2 * heads * DH + h * DH);
+        float ks[NS], vv[NS];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) {
+        for (int m = 0; m < NS / 4; ++m) {
             const f32x4 a = kp[2 * m + half], c = vp[2 * m + half];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -436,59 +494,78 @@ __global__ __launch_bounds__(64) void linattn_bwd_kv_mfma_kernel(const float* __
                 vv[4 * m + i] = c[i];
             }
         }
-        f32x16 dvt, dkt;
+        f32x16 dvt[NT], dkt[NT];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dvt[r] = dkt[r] = 0.f;
+        for (int I = 0; I < NT; ++I)
 #pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            dvt = __builtin_amdgcn_mfma_f32_32x32x2f32(a3[s], ks[s], dvt, 0, 0, 0);
-            dkt = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[s], vv[s], dkt, 0, 0, 0);
+            for (int r = 0; r < 16; ++r) dvt[I][r] = dkt[I][r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+#pragma unroll
+            for (int I = 0; I < NT; ++I) {
+                dvt[I] = __builtin_amdgcn_mfma_f32_32x32x2f32(a3[I][s], ks[s], dvt[I], 0, 0, 0);
+                dkt[I] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[I][s], vv[s], dkt[I], 0, 0, 0);
+            }
         }
         if (ok) {
-            f32x4* okp = reinterpret_cast<f32x4*>(dqkv + row * ld + heads * BDH + h * BDH);
-            f32x4* ovp = reinterpret_cast<f32x4*>(dqkv + row * ld + 2 * heads * BDH + h * BDH);
+            f32x4* okp = reinterpret_cast<f32x4*>(dqkv + row * ld + heads * DH + h * DH);
+            f32x4* ovp = reinterpret_cast<f32x4*>(dqkv + row * ld + 2 * heads * DH + h * DH);
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                ovp[2 * m + half] = make_f32x4(dvt[4 * m], dvt[4 * m + 1], dvt[4 * m + 2], dvt[4 * m + 3]);
-                okp[2 * m + half] = make_f32x4(ks[4 * m] * (dkt[4 * m] - S[4 * m]), ks[4 * m + 1] * (dkt[4 * m + 1] - S[4 * m + 1]),
-                                               ks[4 * m + 2] * (dkt[4 * m + 2] - S[4 * m + 2]),
-                                               ks[4 * m + 3] * (dkt[4 * m + 3] - S[4 * m + 3]));
+#pragma unroll
+                for (int I = 0; I < NT; ++I) {
+                    const int r = 16 * I + 4 * m;  // register of column 32 I + dset(4 m)
+                    ovp[8 * I + 2 * m + half] = make_f32x4(dvt[I][4 * m], dvt[I][4 * m + 1], dvt[I][4 * m + 2], dvt[I][4 * m + 3]);
+                    okp[8 * I + 2 * m + half] = make_f32x4(ks[r] * (dkt[I][4 * m] - S[r]), ks[r + 1] * (dkt[I][4 * m + 1] - S[r + 1]),
+                                                           ks[r + 2] * (dkt[I][4 * m + 2] - S[r + 2]),
+                                                           ks[r + 3] * (dkt[I][4 * m + 3] - S[r + 3]));
+                }
             }
         }
     }
 }
 
 // block shares of dctx (the sum lands in share 0) + the per-(image, head) statistics
-size_t linattn_bwd_ws_floats(int B, int n, int heads) {
-    return (size_t)B * ((n + 63) / 64) * heads * BDH * BDH + (size_t)B * heads * 3 * BDH;
+size_t linattn_bwd_ws_floats(int B, int n, int heads, int dh) {
+    return (size_t)B * ((n + 63) / 64) * heads * dh * dh + (size_t)B * heads * 3 * dh;
 }
 
-// qkv (B, n, 3*heads*32), ctx (B, heads, 32, 32) as the forward core left it, dout (B, n, heads*32) -> dqkv (same shape as
-// qkv), dmem_part (B, 2, heads, 32, 4) per-image memory key/value gradients (the caller sums over B)
+template <int DH>
+static int linear_attention_core_bwd(const float* qkv, const float* mem_kv, const float* ctx, const float* dout, float* ws,
+                                     float* dqkv, float* dmem_part, int B, int n, int heads, hipStream_t s,
+                                     const float* kstats) {
+    const int nblk = (n + 63) / 64;
+    const float scale = 1.0f / sqrtf((float)DH);
+    float* stats = ws + (size_t)B * nblk * heads * DH * DH;
+    static const bool valu = std::getenv("DM_LINATTN_BWD_VALU") != nullptr;  // the lane-per-token VALU kernels (A/B, forced-path test)
+    if (valu)
+        hipLaunchKernelGGL(linattn_bwd_q_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ctx, dout, dqkv, ws, n, heads,
+                           scale);
+    else
+        hipLaunchKernelGGL(linattn_bwd_q_mfma_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ctx, dout, dqkv, ws, n,
+                           heads, scale);
+    DM_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(linattn_bwd_stats_kernel<DH>, dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx, ws, nblk, stats,
+                       dmem_part, kstats, n, heads);
+    DM_CHECK_HIP(hipGetLastError());
+    if (valu)
+        hipLaunchKernelGGL(linattn_bwd_kv_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ws, nblk, stats, dqkv, n, heads);
+    else
+        hipLaunchKernelGGL(linattn_bwd_kv_mfma_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ws, nblk, stats, dqkv, n,
+                           heads);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// qkv (B, n, 3*heads*dh), ctx (B, heads, dh, dh) as the forward core left it, dout (B, n, heads*dh) -> dqkv (same shape as
+// qkv), dmem_part (B, 2, heads, dh, 4) per-image memory key/value gradients (the caller sums over B)
 int launch_linear_attention_core_bwd(const float* qkv, const float* mem_kv, const float* ctx, const float* dout, float* ws,
                                      float* dqkv, float* dmem_part, int B, int n, int heads, int dh, hipStream_t s,
                                      const float* kstats) {
-    DM_REQUIRE(dh == BDH && heads >= 1 && heads <= 16, "linear attention backward: dim_head 32");
+    DM_REQUIRE((dh == 32 || dh == 64) && heads >= 1 && heads <= 16, "linear attention backward: dim_head 32 or 64");
     DM_REQUIRE(B <= 65535 && n >= 1, "linear attention backward: batch");
-    const int nblk = (n + 63) / 64;
-    float* stats = ws + (size_t)B * nblk * heads * BDH * BDH;
-    static const bool valu = std::getenv("DM_LINATTN_BWD_VALU") != nullptr;  // the lane-per-token VALU kernels (A/B, forced-path test)
-    if (valu)
-        hipLaunchKernelGGL(linattn_bwd_q_kernel, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ctx, dout, dqkv, ws, n, heads,
-                           1.0f / sqrtf((float)dh));
-    else
-        hipLaunchKernelGGL(linattn_bwd_q_mfma_kernel, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ctx, dout, dqkv, ws, n, heads,
-                           1.0f / sqrtf((float)dh));
-    DM_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(linattn_bwd_stats_kernel, dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx, ws, nblk, stats, dmem_part,
-                       kstats, n, heads);
-    DM_CHECK_HIP(hipGetLastError());
-    if (valu)
-        hipLaunchKernelGGL(linattn_bwd_kv_kernel, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ws, nblk, stats, dqkv, n, heads);
-    else
-        hipLaunchKernelGGL(linattn_bwd_kv_mfma_kernel, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ws, nblk, stats, dqkv, n, heads);
-    DM_CHECK_HIP(hipGetLastError());
-    return 0;
+    return dh == 32 ? linear_attention_core_bwd<32>(qkv, mem_kv, ctx, dout, ws, dqkv, dmem_part, B, n, heads, s, kstats)
+                    : linear_attention_core_bwd<64>(qkv, mem_kv, ctx, dout, ws, dqkv, dmem_part, B, n, heads, s, kstats);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -500,11 +577,11 @@ int launch_linear_attention_core_bwd(const float* qkv, const float* mem_kv, cons
 // cross-attention (DD/denoising_diffusion_text_conditional.py:54-78): k, v are projections of the text context, no memory.
 // ---------------------------------------------------------------------------------------
 struct AttnBwdParams {
-    const float *q, *k, *v;      // rows of ldq / ldk floats per token, head h at column h * 32
-    const float *mem_k, *mem_v;  // (heads, n_mem, 32) or nullptr
-    const float* dout;           // (B, nq, heads * 32)
+    const float *q, *k, *v;      // rows of ldq / ldk floats per token, head h at column h * dh
+    const float *mem_k, *mem_v;  // (heads, n_mem, dh) or nullptr
+    const float* dout;           // (B, nq, heads * dh)
     float *dq, *dk, *dv;         // same strides as q / k / v
-    float* dmem_part;            // (B, 2, heads, n_mem, 32) or nullptr
+    float* dmem_part;            // (B, 2, heads, n_mem, dh) or nullptr
     int ldq, ldk, nq, nk, n_mem, heads;
     float scale;
 };
@@ -513,62 +590,63 @@ struct AttnBwdParams {
 // scores q_i . k_j and dP_ij are formed ONCE and kept in LDS -- the plain form recomputes the 32-wide dot products in each of
 // its three passes over the keys and again per (key, query) in the second phase, and with one thread per query that serial
 // chain IS the kernel's time (42 us at any batch for 16 queries); same summation order within every dot product.
-template <bool CACHE>
+template <bool CACHE, int DH>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
+    constexpr int LDH = bwd_log2_dh<DH>();
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int nkt = p.nk + p.n_mem, n = p.nq;
-    float* Ks = sm;                       // [nkt][33]
-    float* Vs = Ks + nkt * (BDH + 1);     // [nkt][33]
-    float* Qs = Vs + nkt * (BDH + 1);     // [n][33]
-    float* Ds = Qs + n * (BDH + 1);       // [n][33]  dout
-    float* rm = Ds + n * (BDH + 1);       // [n] row max
+    float* Ks = sm;                       // [nkt][DH + 1]
+    float* Vs = Ks + nkt * (DH + 1);     // [nkt][DH + 1]
+    float* Qs = Vs + nkt * (DH + 1);     // [n][DH + 1]
+    float* Ds = Qs + n * (DH + 1);       // [n][DH + 1]  dout
+    float* rm = Ds + n * (DH + 1);       // [n] row max
     float* rl = rm + n;                   // [n] 1 / row sum
     float* rD = rl + n;                   // [n] D_i
     float* Pc = rD + n;                   // CACHE: [n][nkt] scores -> exp -> P_ij
     float* Sc = Pc + (CACHE ? n * nkt : 0);  // CACHE: [n][nkt] dP_ij -> dS_ij
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int hid = p.heads * BDH;
+    const int hid = p.heads * DH;
     const float scale = p.scale;
-    for (int i = tid; i < nkt * BDH; i += 256) {
-        const int j = i >> 5, d = i & 31;
+    for (int i = tid; i < nkt * DH; i += 256) {
+        const int j = i >> LDH, d = i & (DH - 1);
         float kv, vv;
         if (j < p.n_mem) {
-            kv = p.mem_k[((size_t)h * p.n_mem + j) * BDH + d];
-            vv = p.mem_v[((size_t)h * p.n_mem + j) * BDH + d];
+            kv = p.mem_k[((size_t)h * p.n_mem + j) * DH + d];
+            vv = p.mem_v[((size_t)h * p.n_mem + j) * DH + d];
         } else {
-            const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * BDH + d;
+            const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * DH + d;
             kv = p.k[row];
             vv = p.v[row];
         }
-        Ks[j * (BDH + 1) + d] = kv;
-        Vs[j * (BDH + 1) + d] = vv;
+        Ks[j * (DH + 1) + d] = kv;
+        Vs[j * (DH + 1) + d] = vv;
     }
-    for (int i = tid; i < n * BDH; i += 256) {
-        const int t = i >> 5, d = i & 31;
-        Qs[t * (BDH + 1) + d] = p.q[((size_t)b * n + t) * p.ldq + h * BDH + d];
-        Ds[t * (BDH + 1) + d] = p.dout[((size_t)b * n + t) * hid + h * BDH + d];
+    for (int i = tid; i < n * DH; i += 256) {
+        const int t = i >> LDH, d = i & (DH - 1);
+        Qs[t * (DH + 1) + d] = p.q[((size_t)b * n + t) * p.ldq + h * DH + d];
+        Ds[t * (DH + 1) + d] = p.dout[((size_t)b * n + t) * hid + h * DH + d];
     }
     __syncthreads();
     for (int i = tid; i < n; i += 256) {
-        float q[BDH], dov[BDH];
+        float q[DH], dov[DH];
 #pragma unroll
-        for (int d = 0; d < BDH; ++d) {
-            q[d] = Qs[i * (BDH + 1) + d];
-            dov[d] = Ds[i * (BDH + 1) + d];
+        for (int d = 0; d < DH; ++d) {
+            q[d] = Qs[i * (DH + 1) + d];
+            dov[d] = Ds[i * (DH + 1) + d];
         }
         float m = -INFINITY, l = 0.f, D = 0.f, linv;
-        float dq[BDH];
+        float dq[DH];
 #pragma unroll
-        for (int d = 0; d < BDH; ++d) dq[d] = 0.f;
+        for (int d = 0; d < DH; ++d) dq[d] = 0.f;
         if constexpr (CACHE) {
             float* Pi = Pc + i * nkt;
             float* Si = Sc + i * nkt;
             for (int j = 0; j < nkt; ++j) {
                 float sc = 0.f, dp = 0.f;
 #pragma unroll
-                for (int d = 0; d < BDH; ++d) {
-                    sc += q[d] * Ks[j * (BDH + 1) + d];
-                    dp += dov[d] * Vs[j * (BDH + 1) + d];
+                for (int d = 0; d < DH; ++d) {
+                    sc += q[d] * Ks[j * (DH + 1) + d];
+                    dp += dov[d] * Vs[j * (DH + 1) + d];
                 }
                 Pi[j] = sc * scale;
                 Si[j] = dp;
@@ -588,21 +666,21 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
                 Pi[j] = P;
                 Si[j] = dS;
 #pragma unroll
-                for (int d = 0; d < BDH; ++d) dq[d] += dS * Ks[j * (BDH + 1) + d];
+                for (int d = 0; d < DH; ++d) dq[d] += dS * Ks[j * (DH + 1) + d];
             }
         } else {
             for (int j = 0; j < nkt; ++j) {
                 float sc = 0.f;
 #pragma unroll
-                for (int d = 0; d < BDH; ++d) sc += q[d] * Ks[j * (BDH + 1) + d];
+                for (int d = 0; d < DH; ++d) sc += q[d] * Ks[j * (DH + 1) + d];
                 m = fmaxf(m, sc * scale);
             }
             for (int j = 0; j < nkt; ++j) {
                 float sc = 0.f, dp = 0.f;
 #pragma unroll
-                for (int d = 0; d < BDH; ++d) {
-                    sc += q[d] * Ks[j * (BDH + 1) + d];
-                    dp += dov[d] * Vs[j * (BDH + 1) + d];
+                for (int d = 0; d < DH; ++d) {
+                    sc += q[d] * Ks[j * (DH + 1) + d];
+                    dp += dov[d] * Vs[j * (DH + 1) + d];
                 }
                 const float e = __expf(sc * scale - m);
                 l += e;
@@ -613,29 +691,29 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
             for (int j = 0; j < nkt; ++j) {
                 float sc = 0.f, dp = 0.f;
 #pragma unroll
-                for (int d = 0; d < BDH; ++d) {
-                    sc += q[d] * Ks[j * (BDH + 1) + d];
-                    dp += dov[d] * Vs[j * (BDH + 1) + d];
+                for (int d = 0; d < DH; ++d) {
+                    sc += q[d] * Ks[j * (DH + 1) + d];
+                    dp += dov[d] * Vs[j * (DH + 1) + d];
                 }
                 const float dS = __expf(sc * scale - m) * linv * (dp - D);
 #pragma unroll
-                for (int d = 0; d < BDH; ++d) dq[d] += dS * Ks[j * (BDH + 1) + d];
+                for (int d = 0; d < DH; ++d) dq[d] += dS * Ks[j * (DH + 1) + d];
             }
         }
         rm[i] = m;
         rl[i] = linv;
         rD[i] = D;
-        float* o = p.dq + ((size_t)b * n + i) * p.ldq + h * BDH;
+        float* o = p.dq + ((size_t)b * n + i) * p.ldq + h * DH;
 #pragma unroll
-        for (int d = 0; d < BDH; ++d) o[d] = scale * dq[d];
+        for (int d = 0; d < DH; ++d) o[d] = scale * dq[d];
     }
     __syncthreads();
     for (int j = tid; j < nkt; j += 256) {
-        float kk[BDH], vv[BDH], dk[BDH], dv[BDH];
+        float kk[DH], vv[DH], dk[DH], dv[DH];
 #pragma unroll
-        for (int d = 0; d < BDH; ++d) {
-            kk[d] = Ks[j * (BDH + 1) + d];
-            vv[d] = Vs[j * (BDH + 1) + d];
+        for (int d = 0; d < DH; ++d) {
+            kk[d] = Ks[j * (DH + 1) + d];
+            vv[d] = Vs[j * (DH + 1) + d];
             dk[d] = 0.f;
             dv[d] = 0.f;
         }
@@ -647,30 +725,30 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
             } else {
                 float sc = 0.f, dp = 0.f;
 #pragma unroll
-                for (int d = 0; d < BDH; ++d) {
-                    sc += Qs[i * (BDH + 1) + d] * kk[d];
-                    dp += Ds[i * (BDH + 1) + d] * vv[d];
+                for (int d = 0; d < DH; ++d) {
+                    sc += Qs[i * (DH + 1) + d] * kk[d];
+                    dp += Ds[i * (DH + 1) + d] * vv[d];
                 }
                 P = __expf(sc * scale - rm[i]) * rl[i];
                 dS = P * (dp - rD[i]);
             }
 #pragma unroll
-            for (int d = 0; d < BDH; ++d) {
-                dk[d] += dS * Qs[i * (BDH + 1) + d];
-                dv[d] += P * Ds[i * (BDH + 1) + d];
+            for (int d = 0; d < DH; ++d) {
+                dk[d] += dS * Qs[i * (DH + 1) + d];
+                dv[d] += P * Ds[i * (DH + 1) + d];
             }
         }
         if (j < p.n_mem) {
-            float* o = p.dmem_part + (size_t)b * 2 * p.heads * p.n_mem * BDH;
+            float* o = p.dmem_part + (size_t)b * 2 * p.heads * p.n_mem * DH;
 #pragma unroll
-            for (int d = 0; d < BDH; ++d) {
-                o[((size_t)h * p.n_mem + j) * BDH + d] = scale * dk[d];
-                o[((size_t)(p.heads + h) * p.n_mem + j) * BDH + d] = dv[d];
+            for (int d = 0; d < DH; ++d) {
+                o[((size_t)h * p.n_mem + j) * DH + d] = scale * dk[d];
+                o[((size_t)(p.heads + h) * p.n_mem + j) * DH + d] = dv[d];
             }
         } else {
-            const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * BDH;
+            const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * DH;
 #pragma unroll
-            for (int d = 0; d < BDH; ++d) {
+            for (int d = 0; d < DH; ++d) {
                 p.dk[row + d] = scale * dk[d];
                 p.dv[row + d] = dv[d];
             }
@@ -683,45 +761,47 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
 // x three 32-wide dot products each (22 us at any batch).  Here (1) thread = (query, key) pair forms the score and dP, (2) thread
 // = query normalises its row (no dot products left), (3) thread = (query, d) forms dq, (4) thread = (key, d) forms dk and dv.
 // Every sum runs over the same index in the same order as attn_bwd_kernel's (d, then keys, then queries): identical results.
+template <int DH>
 __global__ __launch_bounds__(256) void attn_bwd_pairs_kernel(const AttnBwdParams p) {
+    constexpr int LDH = bwd_log2_dh<DH>();
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int nkt = p.nk + p.n_mem, n = p.nq;
-    float* Ks = sm;                       // [nkt][33]
-    float* Vs = Ks + nkt * (BDH + 1);     // [nkt][33]
-    float* Qs = Vs + nkt * (BDH + 1);     // [n][33]
-    float* Ds = Qs + n * (BDH + 1);       // [n][33]  dout
-    float* Pc = Ds + n * (BDH + 1) + 3 * n;  // (same offsets as attn_bwd_kernel<true>: one LDS size for both)
+    float* Ks = sm;                       // [nkt][DH + 1]
+    float* Vs = Ks + nkt * (DH + 1);     // [nkt][DH + 1]
+    float* Qs = Vs + nkt * (DH + 1);     // [n][DH + 1]
+    float* Ds = Qs + n * (DH + 1);       // [n][DH + 1]  dout
+    float* Pc = Ds + n * (DH + 1) + 3 * n;  // (same offsets as attn_bwd_kernel<true>: one LDS size for both)
     float* Sc = Pc + n * nkt;
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int hid = p.heads * BDH;
+    const int hid = p.heads * DH;
     const float scale = p.scale;
-    for (int i = tid; i < nkt * BDH; i += 256) {
-        const int j = i >> 5, d = i & 31;
+    for (int i = tid; i < nkt * DH; i += 256) {
+        const int j = i >> LDH, d = i & (DH - 1);
         float kv, vv;
         if (j < p.n_mem) {
-            kv = p.mem_k[((size_t)h * p.n_mem + j) * BDH + d];
-            vv = p.mem_v[((size_t)h * p.n_mem + j) * BDH + d];
+            kv = p.mem_k[((size_t)h * p.n_mem + j) * DH + d];
+            vv = p.mem_v[((size_t)h * p.n_mem + j) * DH + d];
         } else {
-            const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * BDH + d;
+            const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * DH + d;
             kv = p.k[row];
             vv = p.v[row];
         }
-        Ks[j * (BDH + 1) + d] = kv;
-        Vs[j * (BDH + 1) + d] = vv;
+        Ks[j * (DH + 1) + d] = kv;
+        Vs[j * (DH + 1) + d] = vv;
     }
-    for (int i = tid; i < n * BDH; i += 256) {
-        const int t = i >> 5, d = i & 31;
-        Qs[t * (BDH + 1) + d] = p.q[((size_t)b * n + t) * p.ldq + h * BDH + d];
-        Ds[t * (BDH + 1) + d] = p.dout[((size_t)b * n + t) * hid + h * BDH + d];
+    for (int i = tid; i < n * DH; i += 256) {
+        const int t = i >> LDH, d = i & (DH - 1);
+        Qs[t * (DH + 1) + d] = p.q[((size_t)b * n + t) * p.ldq + h * DH + d];
+        Ds[t * (DH + 1) + d] = p.dout[((size_t)b * n + t) * hid + h * DH + d];
     }
     __syncthreads();
     for (int idx = tid; idx < n * nkt; idx += 256) {  // (1) scores and dP
         const int i = idx / nkt, j = idx - i * nkt;
         float sc = 0.f, dp = 0.f;
 #pragma unroll
-        for (int d = 0; d < BDH; ++d) {
-            sc += Qs[i * (BDH + 1) + d] * Ks[j * (BDH + 1) + d];
-            dp += Ds[i * (BDH + 1) + d] * Vs[j * (BDH + 1) + d];
+        for (int d = 0; d < DH; ++d) {
+            sc += Qs[i * (DH + 1) + d] * Ks[j * (DH + 1) + d];
+            dp += Ds[i * (DH + 1) + d] * Vs[j * (DH + 1) + d];
         }
         Pc[idx] = sc * scale;
         Sc[idx] = dp;
@@ -747,25 +827,25 @@ __global__ __launch_bounds__(256) void attn_bwd_pairs_kernel(const AttnBwdParams
         }
     }
     __syncthreads();
-    for (int idx = tid; idx < n * BDH; idx += 256) {  // (3) dq
-        const int i = idx >> 5, d = idx & 31;
+    for (int idx = tid; idx < n * DH; idx += 256) {  // (3) dq
+        const int i = idx >> LDH, d = idx & (DH - 1);
         float dq = 0.f;
-        for (int j = 0; j < nkt; ++j) dq += Sc[i * nkt + j] * Ks[j * (BDH + 1) + d];
-        p.dq[((size_t)b * n + i) * p.ldq + h * BDH + d] = scale * dq;
+        for (int j = 0; j < nkt; ++j) dq += Sc[i * nkt + j] * Ks[j * (DH + 1) + d];
+        p.dq[((size_t)b * n + i) * p.ldq + h * DH + d] = scale * dq;
     }
-    for (int idx = tid; idx < nkt * BDH; idx += 256) {  // (4) dk, dv
-        const int j = idx >> 5, d = idx & 31;
+    for (int idx = tid; idx < nkt * DH; idx += 256) {  // (4) dk, dv
+        const int j = idx >> LDH, d = idx & (DH - 1);
         float dk = 0.f, dv = 0.f;
         for (int i = 0; i < n; ++i) {
-            dk += Sc[i * nkt + j] * Qs[i * (BDH + 1) + d];
-            dv += Pc[i * nkt + j] * Ds[i * (BDH + 1) + d];
+            dk += Sc[i * nkt + j] * Qs[i * (DH + 1) + d];
+            dv += Pc[i * nkt + j] * Ds[i * (DH + 1) + d];
         }
         if (j < p.n_mem) {
-            float* o = p.dmem_part + (size_t)b * 2 * p.heads * p.n_mem * BDH;
-            o[((size_t)h * p.n_mem + j) * BDH + d] = scale * dk;
-            o[((size_t)(p.heads + h) * p.n_mem + j) * BDH + d] = dv;
+            float* o = p.dmem_part + (size_t)b * 2 * p.heads * p.n_mem * DH;
+            o[((size_t)h * p.n_mem + j) * DH + d] = scale * dk;
+            o[((size_t)(p.heads + h) * p.n_mem + j) * DH + d] = dv;
         } else {
-            const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * BDH;
+            const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * DH;
             p.dk[row + d] = scale * dk;
             p.dv[row + d] = dv;
         }
@@ -778,33 +858,35 @@ __global__ __launch_bounds__(256) void attn_bwd_pairs_kernel(const AttnBwdParams
 //     statistics (m_i, 1 / l_i, D_i) to stats[b][h][i][3].
 // attn_bwd_kv_tiled_kernel  grid (ceil((nk + n_mem) / 64), heads, B): lane = key; the queries (q, dO, statistics) stream
 //     through LDS in tiles of 64 in order: dk, dv, memory-row gradients.  Fixed summation order, no atomics.
-constexpr int ATS = BDH + 1;
+template <int DH>
 __device__ __forceinline__ void attn_load_key(const AttnBwdParams& p, int b, int h, int j, int d, float* kv, float* vv) {
     if (j < p.n_mem) {
-        *kv = p.mem_k[((size_t)h * p.n_mem + j) * BDH + d];
-        *vv = p.mem_v[((size_t)h * p.n_mem + j) * BDH + d];
+        *kv = p.mem_k[((size_t)h * p.n_mem + j) * DH + d];
+        *vv = p.mem_v[((size_t)h * p.n_mem + j) * DH + d];
     } else {
-        const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * BDH + d;
+        const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * DH + d;
         *kv = p.k[row];
         *vv = p.v[row];
     }
 }
+template <int DH>
 __global__ __launch_bounds__(64) void attn_bwd_q_tiled_kernel(const AttnBwdParams p, float* __restrict__ stats) {
+    constexpr int LDH = bwd_log2_dh<DH>(), ATS = DH + 1;
     __shared__ float Ks[64 * ATS], Vs[64 * ATS];
     const int h = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
     const int i = blockIdx.x * 64 + lane, n = p.nq, nkt = p.nk + p.n_mem;
     const bool ok = i < n;
-    const int hid = p.heads * BDH;
+    const int hid = p.heads * DH;
     const float scale = p.scale;
-    float q[BDH], dov[BDH];
+    float q[DH], dov[DH];
 #pragma unroll
-    for (int d = 0; d < BDH; ++d) {
-        q[d] = ok ? p.q[((size_t)b * n + i) * p.ldq + h * BDH + d] : 0.f;
-        dov[d] = ok ? p.dout[((size_t)b * n + i) * hid + h * BDH + d] : 0.f;
+    for (int d = 0; d < DH; ++d) {
+        q[d] = ok ? p.q[((size_t)b * n + i) * p.ldq + h * DH + d] : 0.f;
+        dov[d] = ok ? p.dout[((size_t)b * n + i) * hid + h * DH + d] : 0.f;
     }
-    float m = -INFINITY, l = 0.f, D = 0.f, dq[BDH];
+    float m = -INFINITY, l = 0.f, D = 0.f, dq[DH];
 #pragma unroll
-    for (int d = 0; d < BDH; ++d) dq[d] = 0.f;
+    for (int d = 0; d < DH; ++d) dq[d] = 0.f;
     for (int pass = 0; pass < 3; ++pass) {
         float linv = 0.f;
         if (pass == 2) {
@@ -813,10 +895,10 @@ __global__ __launch_bounds__(64) void attn_bwd_q_tiled_kernel(const AttnBwdParam
         }
         for (int j0 = 0; j0 < nkt; j0 += 64) {
             __syncthreads();
-            for (int e = lane; e < 64 * BDH; e += 64) {
-                const int jj = e >> 5, d = e & 31;
+            for (int e = lane; e < 64 * DH; e += 64) {
+                const int jj = e >> LDH, d = e & (DH - 1);
                 float kv = 0.f, vv = 0.f;
-                if (j0 + jj < nkt) attn_load_key(p, b, h, j0 + jj, d, &kv, &vv);
+                if (j0 + jj < nkt) attn_load_key<DH>(p, b, h, j0 + jj, d, &kv, &vv);
                 Ks[jj * ATS + d] = kv;
                 Vs[jj * ATS + d] = vv;
             }
@@ -825,7 +907,7 @@ __global__ __launch_bounds__(64) void attn_bwd_q_tiled_kernel(const AttnBwdParam
             for (int jj = 0; jj < jn; ++jj) {
                 float sc = 0.f, dp = 0.f;
 #pragma unroll
-                for (int d = 0; d < BDH; ++d) {
+                for (int d = 0; d < DH; ++d) {
                     sc += q[d] * Ks[jj * ATS + d];
                     dp += dov[d] * Vs[jj * ATS + d];
                 }
@@ -838,7 +920,7 @@ __global__ __launch_bounds__(64) void attn_bwd_q_tiled_kernel(const AttnBwdParam
                 } else {
                     const float dS = __expf(sc * scale - m) * linv * (dp - D);
 #pragma unroll
-                    for (int d = 0; d < BDH; ++d) dq[d] += dS * Ks[jj * ATS + d];
+                    for (int d = 0; d < DH; ++d) dq[d] += dS * Ks[jj * ATS + d];
                 }
             }
         }
@@ -848,32 +930,34 @@ __global__ __launch_bounds__(64) void attn_bwd_q_tiled_kernel(const AttnBwdParam
         st[0] = m;
         st[1] = 1.0f / l;
         st[2] = D;
-        float* o = p.dq + ((size_t)b * n + i) * p.ldq + h * BDH;
+        float* o = p.dq + ((size_t)b * n + i) * p.ldq + h * DH;
 #pragma unroll
-        for (int d = 0; d < BDH; ++d) o[d] = scale * dq[d];
+        for (int d = 0; d < DH; ++d) o[d] = scale * dq[d];
     }
 }
+template <int DH>
 __global__ __launch_bounds__(64) void attn_bwd_kv_tiled_kernel(const AttnBwdParams p, const float* __restrict__ stats) {
+    constexpr int LDH = bwd_log2_dh<DH>(), ATS = DH + 1;
     __shared__ float Qs[64 * ATS], Ds[64 * ATS], St[64 * 3];
     const int h = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
     const int j = blockIdx.x * 64 + lane, n = p.nq, nkt = p.nk + p.n_mem;
     const bool ok = j < nkt;
-    const int hid = p.heads * BDH;
+    const int hid = p.heads * DH;
     const float scale = p.scale;
-    float kk[BDH], vv[BDH], dk[BDH], dv[BDH];
+    float kk[DH], vv[DH], dk[DH], dv[DH];
 #pragma unroll
-    for (int d = 0; d < BDH; ++d) {
+    for (int d = 0; d < DH; ++d) {
         kk[d] = vv[d] = 0.f;
-        if (ok) attn_load_key(p, b, h, j, d, &kk[d], &vv[d]);
+        if (ok) attn_load_key<DH>(p, b, h, j, d, &kk[d], &vv[d]);
         dk[d] = dv[d] = 0.f;
     }
     for (int i0 = 0; i0 < n; i0 += 64) {
         __syncthreads();
-        for (int e = lane; e < 64 * BDH; e += 64) {
-            const int ii = e >> 5, d = e & 31;
+        for (int e = lane; e < 64 * DH; e += 64) {
+            const int ii = e >> LDH, d = e & (DH - 1);
             const bool in = i0 + ii < n;
-            Qs[ii * ATS + d] = in ? p.q[((size_t)b * n + i0 + ii) * p.ldq + h * BDH + d] : 0.f;
-            Ds[ii * ATS + d] = in ? p.dout[((size_t)b * n + i0 + ii) * hid + h * BDH + d] : 0.f;
+            Qs[ii * ATS + d] = in ? p.q[((size_t)b * n + i0 + ii) * p.ldq + h * DH + d] : 0.f;
+            Ds[ii * ATS + d] = in ? p.dout[((size_t)b * n + i0 + ii) * hid + h * DH + d] : 0.f;
         }
         for (int e = lane; e < 64 * 3; e += 64)
             St[e] = i0 + e / 3 < n ? stats[(((size_t)b * p.heads + h) * n + i0) * 3 + e] : 0.f;
@@ -882,14 +966,14 @@ __global__ __launch_bounds__(64) void attn_bwd_kv_tiled_kernel(const AttnBwdPara
         for (int ii = 0; ii < in_; ++ii) {
             float sc = 0.f, dp = 0.f;
 #pragma unroll
-            for (int d = 0; d < BDH; ++d) {
+            for (int d = 0; d < DH; ++d) {
                 sc += Qs[ii * ATS + d] * kk[d];
                 dp += Ds[ii * ATS + d] * vv[d];
             }
             const float P = __expf(sc * scale - St[3 * ii]) * St[3 * ii + 1];
             const float dS = P * (dp - St[3 * ii + 2]);
 #pragma unroll
-            for (int d = 0; d < BDH; ++d) {
+            for (int d = 0; d < DH; ++d) {
                 dk[d] += dS * Qs[ii * ATS + d];
                 dv[d] += P * Ds[ii * ATS + d];
             }
@@ -897,16 +981,16 @@ __global__ __launch_bounds__(64) void attn_bwd_kv_tiled_kernel(const AttnBwdPara
     }
     if (!ok) return;
     if (j < p.n_mem) {
-        float* o = p.dmem_part + (size_t)b * 2 * p.heads * p.n_mem * BDH;
+        float* o = p.dmem_part + (size_t)b * 2 * p.heads * p.n_mem * DH;
 #pragma unroll
-        for (int d = 0; d < BDH; ++d) {
-            o[((size_t)h * p.n_mem + j) * BDH + d] = scale * dk[d];
-            o[((size_t)(p.heads + h) * p.n_mem + j) * BDH + d] = dv[d];
+        for (int d = 0; d < DH; ++d) {
+            o[((size_t)h * p.n_mem + j) * DH + d] = scale * dk[d];
+            o[((size_t)(p.heads + h) * p.n_mem + j) * DH + d] = dv[d];
         }
     } else {
-        const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * BDH;
+        const size_t row = ((size_t)b * p.nk + (j - p.n_mem)) * p.ldk + h * DH;
 #pragma unroll
-        for (int d = 0; d < BDH; ++d) {
+        for (int d = 0; d < DH; ++d) {
             p.dk[row + d] = scale * dk[d];
             p.dv[row + d] = dv[d];
         }
@@ -917,79 +1001,80 @@ static bool attn_bwd_cached(int nq, int nk, int n_mem) {
     static const bool off = std::getenv("DM_ATTN_BWD_NO_CACHE") != nullptr;  // A/B, and the tests' other path
     return !off && (size_t)nq * (nk + n_mem) <= 4096;
 }
-static size_t attn_bwd_lds_bytes(int nq, int nk, int n_mem) {
+static size_t attn_bwd_lds_bytes(int nq, int nk, int n_mem, int dh) {
     const size_t cache = attn_bwd_cached(nq, nk, n_mem) ? (size_t)2 * nq * (nk + n_mem) : 0;
-    return ((size_t)(2 * (nk + n_mem) + 2 * nq) * (BDH + 1) + 3 * nq + cache) * sizeof(float);
+    return ((size_t)(2 * (nk + n_mem) + 2 * nq) * (dh + 1) + 3 * nq + cache) * sizeof(float);
 }
-static bool attn_bwd_tiled(int nq, int nk, int n_mem) {
+static bool attn_bwd_tiled(int nq, int nk, int n_mem, int dh) {
     static const bool force = std::getenv("DM_ATTN_BWD_TILED") != nullptr;  // tests: the tiled form on small shapes too
-    return force || attn_bwd_lds_bytes(nq, nk, n_mem) > 160 * 1024;
+    return force || attn_bwd_lds_bytes(nq, nk, n_mem, dh) > 160 * 1024;
 }
 // floats of statistics workspace the tiled form needs (0 when the LDS-resident kernel takes the shape)
-size_t attn_bwd_ws_floats(int B, int nq, int nk, int n_mem, int heads) {
-    return attn_bwd_tiled(nq, nk, n_mem) ? (size_t)B * heads * nq * 3 : 0;
+size_t attn_bwd_ws_floats(int B, int nq, int nk, int n_mem, int heads, int dh) {
+    return attn_bwd_tiled(nq, nk, n_mem, dh) ? (size_t)B * heads * nq * 3 : 0;
 }
 
+template <int DH>
 static int launch_attn_bwd(const AttnBwdParams& p, int B, float* ws, hipStream_t s) {
-    const size_t lds = attn_bwd_lds_bytes(p.nq, p.nk, p.n_mem);
-    if (attn_bwd_tiled(p.nq, p.nk, p.n_mem)) {
+    const size_t lds = attn_bwd_lds_bytes(p.nq, p.nk, p.n_mem, DH);
+    if (attn_bwd_tiled(p.nq, p.nk, p.n_mem, DH)) {
         DM_REQUIRE(ws != nullptr, "attention backward: the tiled form needs its statistics workspace (attn_bwd_ws_floats)");
         DM_REQUIRE(B <= 65535 && p.heads <= 65535, "attention backward: batch");
-        hipLaunchKernelGGL(attn_bwd_q_tiled_kernel, dim3((p.nq + 63) / 64, p.heads, B), dim3(64), 0, s, p, ws);
+        hipLaunchKernelGGL(attn_bwd_q_tiled_kernel<DH>, dim3((p.nq + 63) / 64, p.heads, B), dim3(64), 0, s, p, ws);
         DM_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(attn_bwd_kv_tiled_kernel, dim3((p.nk + p.n_mem + 63) / 64, p.heads, B), dim3(64), 0, s, p, ws);
+        hipLaunchKernelGGL(attn_bwd_kv_tiled_kernel<DH>, dim3((p.nk + p.n_mem + 63) / 64, p.heads, B), dim3(64), 0, s, p, ws);
         DM_CHECK_HIP(hipGetLastError());
         return 0;
     }
     static const bool no_pairs = std::getenv("DM_ATTN_BWD_NO_PAIRS") != nullptr;
     if (attn_bwd_cached(p.nq, p.nk, p.n_mem) && !no_pairs) {
         static LdsOptIn flagp;
-        if (lds_opt_in(flagp, reinterpret_cast<const void*>(attn_bwd_pairs_kernel), 1)) return 1;
-        hipLaunchKernelGGL(attn_bwd_pairs_kernel, dim3(p.heads, B), dim3(256), lds, s, p);
+        if (lds_opt_in(flagp, reinterpret_cast<const void*>(attn_bwd_pairs_kernel<DH>), 1)) return 1;
+        hipLaunchKernelGGL(attn_bwd_pairs_kernel<DH>, dim3(p.heads, B), dim3(256), lds, s, p);
         DM_CHECK_HIP(hipGetLastError());
         return 0;
     }
     if (attn_bwd_cached(p.nq, p.nk, p.n_mem)) {
         static LdsOptIn flagc;
-        if (lds_opt_in(flagc, reinterpret_cast<const void*>(attn_bwd_kernel<true>), 1)) return 1;
-        hipLaunchKernelGGL(attn_bwd_kernel<true>, dim3(p.heads, B), dim3(256), lds, s, p);
+        if (lds_opt_in(flagc, reinterpret_cast<const void*>(attn_bwd_kernel<true, DH>), 1)) return 1;
+        hipLaunchKernelGGL((attn_bwd_kernel<true, DH>), dim3(p.heads, B), dim3(256), lds, s, p);
         DM_CHECK_HIP(hipGetLastError());
         return 0;
     }
     static LdsOptIn flag;
-    if (lds_opt_in(flag, reinterpret_cast<const void*>(attn_bwd_kernel<false>), 1)) return 1;
-    hipLaunchKernelGGL(attn_bwd_kernel<false>, dim3(p.heads, B), dim3(256), lds, s, p);
+    if (lds_opt_in(flag, reinterpret_cast<const void*>(attn_bwd_kernel<false, DH>), 1)) return 1;
+    hipLaunchKernelGGL((attn_bwd_kernel<false, DH>), dim3(p.heads, B), dim3(256), lds, s, p);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-// qkv (B, n, 3*heads*32), dout (B, n, heads*32) -> dqkv, dmem_part (B, 2, heads, 4, 32)
+// qkv (B, n, 3*heads*dh), dout (B, n, heads*dh) -> dqkv, dmem_part (B, 2, heads, 4, dh)
 int launch_attention_core_bwd(const float* qkv, const float* mem_kv, const float* dout, float* dqkv, float* dmem_part, float* ws,
                               int B, int n, int heads, int dh, hipStream_t s) {
-    DM_REQUIRE(dh == BDH, "attention backward: dim_head 32");
-    const int hid = heads * BDH;
+    DM_REQUIRE(dh == 32 || dh == 64, "attention backward: dim_head 32 or 64");
+    const int hid = heads * dh;
     AttnBwdParams p{};
     p.q = qkv; p.k = qkv + hid; p.v = qkv + 2 * hid;
-    p.mem_k = mem_kv; p.mem_v = mem_kv + (size_t)heads * NMEM * BDH;
+    p.mem_k = mem_kv; p.mem_v = mem_kv + (size_t)heads * NMEM * dh;
     p.dout = dout;
     p.dq = dqkv; p.dk = dqkv + hid; p.dv = dqkv + 2 * hid;
     p.dmem_part = dmem_part;
     p.ldq = p.ldk = 3 * hid; p.nq = p.nk = n; p.n_mem = NMEM; p.heads = heads;
     p.scale = 1.0f / sqrtf((float)dh);
-    return launch_attn_bwd(p, B, ws, s);
+    return dh == 32 ? launch_attn_bwd<32>(p, B, ws, s) : launch_attn_bwd<64>(p, B, ws, s);
 }
 
-// CrossAttention core: q (B, nq, heads*32), k / v (B, m, heads*32) projections of the context -> dq, dk, dv (same shapes)
+// CrossAttention core: q (B, nq, heads*dh), k / v (B, m, heads*dh) projections of the context -> dq, dk, dv (same shapes)
 int launch_cross_attention_core_bwd(const float* q, const float* k, const float* v, const float* dout, float* dq, float* dk,
                                     float* dv, float* ws, int B, int nq, int m, int heads, int dh, hipStream_t s) {
-    DM_REQUIRE(dh == BDH, "attention backward: dim_head 32");
+    DM_REQUIRE(dh == 32 || dh == 64, "attention backward: dim_head 32 or 64");
     AttnBwdParams p{};
     p.q = q; p.k = k; p.v = v;
     p.dout = dout;
     p.dq = dq; p.dk = dk; p.dv = dv;
-    p.ldq = p.ldk = heads * BDH; p.nq = nq; p.nk = m; p.n_mem = 0; p.heads = heads;
+    p.ldq = p.ldk = heads * dh; p.nq = nq; p.nk = m; p.n_mem = 0; p.heads = heads;
     p.scale = 1.0f / sqrtf((float)dh);
-    return launch_attn_bwd(p, B, ws, s);
+    return dh == 32 ? launch_attn_bwd<32>(p, B, ws, s) : launch_attn_bwd<64>(p, B, ws, s);
 }
 
 }  // namespace dm

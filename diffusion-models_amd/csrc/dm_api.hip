@@ -1397,7 +1397,8 @@ int dm_unet_create(const dm_unet_cfg* cfg, int device, dm_unet** out) {
     DM_REQUIRE(cfg && out, "null argument");
     DM_REQUIRE(cfg->n_stages >= 1 && cfg->n_stages <= DM_MAX_STAGES, "n_stages out of range");
     DM_REQUIRE(cfg->dim > 0 && cfg->dim % 2 == 0, "dim must be positive and even");
-    DM_REQUIRE(cfg->attn_dim_head == 32, "HIP attention kernels are specialised for attn_dim_head == 32");
+    DM_REQUIRE(cfg->attn_dim_head == 32 || cfg->attn_dim_head == 64,
+               "attn_dim_head: the HIP attention kernels support head widths 32 and 64");
     DM_REQUIRE(cfg->attn_heads >= 1 && cfg->attn_heads <= 16, "attn_heads out of range");
     for (int i = 0; i < cfg->n_stages; ++i)
         DM_REQUIRE(cfg->attn_heads_stage[i] >= 0 && cfg->attn_heads_stage[i] <= 16, "attn_heads of a stage out of range");

@@ -160,7 +160,7 @@ static int attn_op(bool full, const float* x, const float* norm_g, const float* 
                    const float* w_out, const float* b_out, const float* out_g, float* out, int B, int C, int H,
                    int W, int heads, int dim_head, void* stream) {
     DM_REQUIRE(x && norm_g && mem_kv && w_qkv && w_out && b_out && out, "null argument");
-    DM_REQUIRE(dim_head == 32, "attention kernels are specialised for dim_head == 32");
+    DM_REQUIRE(dim_head == 32 || dim_head == 64, "dim_head: the attention kernels support 32 and 64");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int hidden = heads * dim_head;
     std::vector<float> wq, wo, bo;

@@ -453,7 +453,7 @@ static int t_cross_bwd(TCtx& t, const CrossLayer& Cr, const CrossTape& ct, const
     float* dq = t.A->alloc(rows * inner);
     float* dk = t.A->alloc((size_t)t.B * m * inner);
     float* dv = t.A->alloc((size_t)t.B * m * inner);
-    float* aws = t.A->alloc(attn_bwd_ws_floats(t.B, n, m, 0, 4));
+    float* aws = t.A->alloc(attn_bwd_ws_floats(t.B, n, m, 0, 4, u->dh));
     if (!t.dry()) {
         if (launch_cross_attention_core_bwd(ct.q, ct.k, ct.v, dO, dq, dk, dv, aws, t.B, n, m, 4, u->dh, t.s)) return 1;
         if (launch_linear_wgrad(dk, inner, ctx, E, t.grad(p + ".to_k.weight"), t.B * m, E, inner, 0, t.acc, t.s)) return 1;
@@ -776,11 +776,11 @@ static int t_attn_bwd(TCtx& t, const AttnLayer& At, const AttnTape& at, const fl
     float* dmem = t.A->alloc((size_t)t.B * nmem);
     float* cw = t.A->alloc(colsum_ws_floats(t.B, (int)nmem));
     if (At.full) {
-        float* ws = t.A->alloc(attn_bwd_ws_floats(t.B, n, n, 4, heads));
+        float* ws = t.A->alloc(attn_bwd_ws_floats(t.B, n, n, 4, heads, u->dh));
         if (!t.dry() && launch_attention_core_bwd(at.qkv, At.mem_kv, dO, dqkv, dmem, ws, t.B, n, heads, u->dh, t.s))
             return 1;
     } else {
-        float* ws = t.A->alloc(linattn_bwd_ws_floats(t.B, n, heads));
+        float* ws = t.A->alloc(linattn_bwd_ws_floats(t.B, n, heads, u->dh));
         if (!t.dry() && launch_linear_attention_core_bwd(at.qkv, At.mem_kv, at.ctx, dO, ws, dqkv, dmem, t.B, n, heads,
                                                          u->dh, t.s, at.kst))
             return 1;

@@ -212,7 +212,7 @@ static int attn_bwd_op(bool full, const float* x, const float* norm_g, const flo
                        float* d_norm_g, float* d_mem_kv, float* d_w_qkv, float* d_w_out, float* d_b_out, float* d_out_g,
                        int B, int C, int H, int W, int heads, int dim_head, void* stream) {
     DM_REQUIRE(x && norm_g && mem_kv && w_qkv && w_out && b_out && dy && dx, "null argument");
-    DM_REQUIRE(dim_head == 32, "attention kernels are specialised for dim_head == 32");
+    DM_REQUIRE(dim_head == 32 || dim_head == 64, "dim_head: the attention kernels support 32 and 64");
     hipStream_t s = static_cast<hipStream_t>(stream);
     return guarded([&]() -> int {
         const int hidden = heads * dim_head;

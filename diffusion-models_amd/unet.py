@@ -59,11 +59,12 @@ class Unet:
     ):
         # learned_sinusoidal_cond / random_fourier_features (denoising_diffusion.py:86-101, :271-273): forward() only --
         # DenoisingDiffusion asserts such a U-Net away (:456-457), and so does ours
-        # attn_heads / attn_dim_head: one value or one per stage (cast_tuple, :294-295).  The attention kernels are specialised
-        # for 32-wide heads (the reference's default everywhere it builds a Unet); the head COUNT is per layer.
+        # attn_heads / attn_dim_head: one value or one per stage (cast_tuple, :294-295).  The attention kernels take one head
+        # width per model, 32 (the reference's default everywhere it builds a Unet) or 64; the head COUNT is per layer.
         if isinstance(attn_dim_head, (tuple, list)):
             if any(int(v) != int(attn_dim_head[0]) for v in attn_dim_head) or len(attn_dim_head) != len(tuple(dim_mults)):
-                raise NotImplementedError("per-stage attn_dim_head: the HIP attention kernels take one head width (32)")
+                raise NotImplementedError("per-stage attn_dim_head: the HIP attention kernels take one head width "
+                                          "per model (supported widths: 32 and 64)")
             attn_dim_head = int(attn_dim_head[0])
         if isinstance(attn_heads, (tuple, list)):
             attn_heads = tuple(int(v) for v in attn_heads)
