@@ -256,159 +256,6 @@ __global__ __launch_bounds__(64 * NW) void linattn_ctx_mfma_kernel(const float* 
     }
 }
 
-// ---------------------------------------------------------------------------------------
-// LinearAttention, part 1 (VALU version, kept as the fallback for n_mem != 4):
-// ctx[b][h][d][e] = sum_n softmax_n(k)[d][n] * v[e][n]  (n includes the memory tokens)
-// grid (heads, B), 256 threads.
-// ---------------------------------------------------------------------------------------
-template <int DH>
-__global__ __launch_bounds__(256) void linattn_ctx_kernel(const float* __restrict__ qkv,
-                                                          const float* __restrict__ mem_kv,
-                                                          float* __restrict__ ctx, int n, int heads, int n_mem) {
-    constexpr int LDH = log2_dh<DH>();
-    constexpr int NPART = 256 / DH;      // pass 1: token stripes per column
-    constexpr int EPT = DH * DH / 256;   // pass 2: context elements per thread (a run of one row)
-    constexpr int TPR = DH / EPT;        //         threads per context row
-    const int h = blockIdx.x, b = blockIdx.y;
-    const int tid = threadIdx.x;
-    const int ld = 3 * heads * DH;
-    const float* kbase = qkv + (size_t)b * n * ld + heads * DH + h * DH;
-    const float* vbase = qkv + (size_t)b * n * ld + 2 * heads * DH + h * DH;
-    const float* mk = mem_kv + (size_t)h * DH * n_mem;            // [d][j]
-    const float* mv = mem_kv + (size_t)(heads + h) * DH * n_mem;  // [e][j]
-    const int ntok = n + n_mem;
-
-    __shared__ float red[NPART][DH];
-    __shared__ float kmax[DH];
-    __shared__ float ke[64][DH + 1];
-    __shared__ __attribute__((aligned(16))) float vv[64][DH];
-    __shared__ float ksum_s[DH];
-
-    // pass 1: max over tokens for each d
-    {
-        const int d = tid & (DH - 1), part = tid >> LDH;
-        float m = -INFINITY;
-        for (int t = part; t < ntok; t += NPART) {
-            float kv = t < n_mem ? mk[d * n_mem + t] : kbase[(size_t)(t - n_mem) * ld + d];
-            m = fmaxf(m, kv);
-        }
-        red[part][d] = m;
-        __syncthreads();
-        if (tid < DH) {
-            float mm = red[0][tid];
-#pragma unroll
-            for (int q = 1; q < NPART; ++q) mm = fmaxf(mm, red[q][tid]);
-            kmax[tid] = mm;
-        }
-        __syncthreads();
-    }
-    // pass 2: exp, running sum and the DH x DH outer-product accumulation
-    constexpr int LTPR = DH == 32 ? 3 : 2;  // log2 TPR
-    const int d = tid >> LTPR, e0 = (tid & (TPR - 1)) * EPT;
-    float acc[EPT];
-#pragma unroll
-    for (int e = 0; e < EPT; ++e) acc[e] = 0.f;
-    float ksum = 0.f;
-    for (int t0 = 0; t0 < ntok; t0 += 64) {
-        __syncthreads();
-        for (int it = tid; it < 64 * DH; it += 256) {
-            int tt = it >> LDH, c = it & (DH - 1);
-            int t = t0 + tt;
-            float kval = 0.f, vval = 0.f;
-            if (t < ntok) {
-                if (t < n_mem) {
-                    kval = __expf(mk[c * n_mem + t] - kmax[c]);
-                    vval = mv[c * n_mem + t];
-                } else {
-                    kval = __expf(kbase[(size_t)(t - n_mem) * ld + c] - kmax[c]);
-                    vval = vbase[(size_t)(t - n_mem) * ld + c];
-                }
-            }
-            ke[tt][c] = kval;
-            vv[tt][c] = vval;
-        }
-        __syncthreads();
-#pragma unroll 8
-        for (int tt = 0; tt < 64; ++tt) {
-            float kx = ke[tt][d];
-            float4 v4[EPT / 4];
-#pragma unroll
-            for (int j = 0; j < EPT / 4; ++j) v4[j] = *reinterpret_cast<const float4*>(&vv[tt][e0 + 4 * j]);
-            ksum += kx;
-#pragma unroll
-            for (int j = 0; j < EPT / 4; ++j) {
-                acc[4 * j] += kx * v4[j].x;
-                acc[4 * j + 1] += kx * v4[j].y;
-                acc[4 * j + 2] += kx * v4[j].z;
-                acc[4 * j + 3] += kx * v4[j].w;
-            }
-        }
-    }
-    if ((tid & (TPR - 1)) == 0) ksum_s[d] = ksum;
-    __syncthreads();
-    const float inv = 1.0f / ksum_s[d];
-    float* cp = ctx + ((size_t)(b * heads + h) * DH + d) * DH + e0;
-#pragma unroll
-    for (int j = 0; j < EPT / 4; ++j)
-        *reinterpret_cast<float4*>(cp + 4 * j) =
-            make_float4(acc[4 * j] * inv, acc[4 * j + 1] * inv, acc[4 * j + 2] * inv, acc[4 * j + 3] * inv);
-}
-
-// LinearAttention, part 2: out[b][n][h*DH+e] = sum_d ctx[b][h][d][e] * softmax_d(q[b][n][h][:])[d] * DH^-0.5
-// DH = 32: grid (ceil(n/64), B), block = 64*heads threads: thread = h*64 + pixel (one head per wavefront), every head's
-// context in LDS.  DH = 64: one head per block (16 KB of context), grid (ceil(n/64), B, heads), 64 threads.
-template <int DH>
-__global__ __launch_bounds__(DH == 32 ? 1024 : 64) void linattn_out_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
-                                   float* __restrict__ out, int n, int heads, float scale) {
-    extern __shared__ __attribute__((aligned(16))) float cs[];  // [heads in the block][DH][DH]
-    const int b = blockIdx.y;
-    const int tid = threadIdx.x;
-    const int h0 = DH == 32 ? 0 : blockIdx.z, hb = DH == 32 ? heads : 1;
-    for (int i = tid; i < hb * DH * DH; i += blockDim.x) cs[i] = ctx[((size_t)b * heads + h0) * DH * DH + i];
-    __syncthreads();
-    const int hl = tid >> 6, h = h0 + hl;
-    const int p = blockIdx.x * 64 + (tid & 63);
-    if (p >= n) return;
-    const int ld = 3 * heads * DH;
-    const float* qp = qkv + ((size_t)b * n + p) * ld + h * DH;
-    float q[DH];
-#pragma unroll
-    for (int i = 0; i < DH / 4; ++i) {
-        float4 t = *reinterpret_cast<const float4*>(qp + 4 * i);
-        q[4 * i] = t.x; q[4 * i + 1] = t.y; q[4 * i + 2] = t.z; q[4 * i + 3] = t.w;
-    }
-    float m = q[0];
-#pragma unroll
-    for (int i = 1; i < DH; ++i) m = fmaxf(m, q[i]);
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < DH; ++i) {
-        q[i] = __expf(q[i] - m);
-        s += q[i];
-    }
-    const float inv = scale / s;
-    float o[DH];
-#pragma unroll
-    for (int i = 0; i < DH; ++i) o[i] = 0.f;
-    const float* ch = cs + hl * DH * DH;
-#pragma unroll
-    for (int dd = 0; dd < DH; ++dd) {
-        const float qd = q[dd] * inv;
-#pragma unroll
-        for (int i = 0; i < DH / 4; ++i) {
-            float4 c4 = *reinterpret_cast<const float4*>(ch + dd * DH + 4 * i);
-            o[4 * i] += qd * c4.x;
-            o[4 * i + 1] += qd * c4.y;
-            o[4 * i + 2] += qd * c4.z;
-            o[4 * i + 3] += qd * c4.w;
-        }
-    }
-    float* op = out + ((size_t)b * n + p) * (heads * DH) + h * DH;
-#pragma unroll
-    for (int i = 0; i < DH / 4; ++i)
-        *reinterpret_cast<float4*>(op + 4 * i) = make_float4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
-}
-
 // part 2 on the matrix core: out^T[e][token] = sum_d ctx[d][e] q_s[token][d] as 32x32x2 MFMA products with the token rows as the
 // B operand (attn_bwd.hip's linattn_bwd_*_mfma_kernel describe the layout): lane (token, half) holds the float4 chunks
 // 2 m + half of its token's q row = the columns dset(r) = (r & 3) + 8 (r >> 2) + 4 half, r < DH / 2; the softmax over the DH
@@ -474,51 +321,24 @@ __global__ __launch_bounds__(64) void linattn_out_mfma_kernel(const float* __res
     }
 }
 
-// the training tape keeps the key statistics unless the VALU context kernel is forced or DM_LINATTN_NO_KSTATS asks for the
-// recomputing backward (tests/test_hip_forced_dispatch.py)
-bool linattn_keeps_kstats() {
-    static const bool keep = !std::getenv("DM_LINATTN_VALU") && !std::getenv("DM_LINATTN_NO_KSTATS");
-    return keep;
-}
-
 template <int DH>
 static int linear_attention_core(const float* qkv, const float* mem_kv, float* ctx_ws, float* out, int B, int n, int heads,
                                  hipStream_t s, float* kstats) {
-    static const bool valu_ctx = std::getenv("DM_LINATTN_VALU") != nullptr;
-    if (valu_ctx) {
-        DM_REQUIRE(!kstats, "DM_LINATTN_VALU: the VALU context kernel does not keep the key statistics");
-        hipLaunchKernelGGL(linattn_ctx_kernel<DH>, dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx_ws, n, heads, 4);
-    } else {
-        // waves per (image, head) by the sequence length alone, so that a sample's result does not depend on its batch
-        static const int force = std::getenv("DM_LINATTN_CTX_WAVES") ? atoi(std::getenv("DM_LINATTN_CTX_WAVES")) : 0;
-        const int nw = force ? force : n >= 1024 ? 16 : n >= 256 ? 8 : 4;
-        if (nw == 16)
-            hipLaunchKernelGGL((linattn_ctx_mfma_kernel<16, DH>), dim3(heads, B), dim3(1024), 0, s, qkv, mem_kv, ctx_ws,
-                               kstats, n, heads);
-        else if (nw == 8)
-            hipLaunchKernelGGL((linattn_ctx_mfma_kernel<8, DH>), dim3(heads, B), dim3(512), 0, s, qkv, mem_kv, ctx_ws, kstats,
-                               n, heads);
-        else
-            hipLaunchKernelGGL((linattn_ctx_mfma_kernel<4, DH>), dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx_ws, kstats,
-                               n, heads);
-    }
+    // waves per (image, head) by the sequence length alone, so that a sample's result does not depend on its batch
+    const int nw = n >= 1024 ? 16 : n >= 256 ? 8 : 4;
+    if (nw == 16)
+        hipLaunchKernelGGL((linattn_ctx_mfma_kernel<16, DH>), dim3(heads, B), dim3(1024), 0, s, qkv, mem_kv, ctx_ws, kstats,
+                           n, heads);
+    else if (nw == 8)
+        hipLaunchKernelGGL((linattn_ctx_mfma_kernel<8, DH>), dim3(heads, B), dim3(512), 0, s, qkv, mem_kv, ctx_ws, kstats, n,
+                           heads);
+    else
+        hipLaunchKernelGGL((linattn_ctx_mfma_kernel<4, DH>), dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx_ws, kstats, n,
+                           heads);
     DM_CHECK_HIP(hipGetLastError());
-    if (valu_ctx) {
-        if (DH == 32) {
-            size_t lds = (size_t)heads * DH * DH * sizeof(float);
-            hipLaunchKernelGGL(linattn_out_kernel<DH>, dim3((n + 63) / 64, B), dim3(64 * heads), lds, s, qkv, ctx_ws, out, n,
-                               heads, 1.0f / sqrtf((float)DH));
-        } else {  // one head per block: heads x 16 KB of context would not fit LDS
-            size_t lds = (size_t)DH * DH * sizeof(float);
-            DM_REQUIRE(B <= 65535, "LinearAttention: batch");
-            hipLaunchKernelGGL(linattn_out_kernel<DH>, dim3((n + 63) / 64, B, heads), dim3(64), lds, s, qkv, ctx_ws, out, n,
-                               heads, 1.0f / sqrtf((float)DH));
-        }
-    } else {
-        DM_REQUIRE(B <= 65535, "LinearAttention: batch");
-        hipLaunchKernelGGL(linattn_out_mfma_kernel<DH>, dim3((n + 63) / 64, heads, B), dim3(64), 0, s, qkv, ctx_ws, out, n,
-                           heads, 1.0f / sqrtf((float)DH));
-    }
+    DM_REQUIRE(B <= 65535, "LinearAttention: batch");
+    hipLaunchKernelGGL(linattn_out_mfma_kernel<DH>, dim3((n + 63) / 64, heads, B), dim3(64), 0, s, qkv, ctx_ws, out, n, heads,
+                       1.0f / sqrtf((float)DH));
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -680,7 +500,7 @@ static int attention_core(const float* q, int ldq, const float* k, const float* 
                           hipStream_t s) {
     int ntok = nk + n_mem;
     size_t lds = ((size_t)ntok * (DH + 1) + (size_t)ntok * DH + 4 * (size_t)ntok + 4 * DH) * sizeof(float);
-    static const bool force_tiled = std::getenv("DM_ATTN_TILED") != nullptr;  // tests: the tiled form on short sequences
+    static const bool force_tiled = env_flag("DM_ATTN_TILED");  // tests: the tiled form on short sequences
     // beyond ~320 keys the tiled form is also the faster one (tools/attn_time.py: 512 tokens 1.29 vs 2.79 ms per layer at
     // B=64, equal at 256): the LDS-resident kernel re-stages all K / V of an (image, head) in every query block
     static const int tiled_min = env_int("DM_ATTN_TILED_MIN", 320);

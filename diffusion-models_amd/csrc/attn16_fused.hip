@@ -30,7 +30,7 @@ static constexpr int A16_OS = 132;  // row stride (floats) of the O staging tile
 static constexpr int A16_D = 4;     // weight iterations in flight
 
 bool attn16_eligible(int dim, int heads, int dh) {
-    static const bool off = std::getenv("DM_NO_ATTN16") != nullptr;
+    static const bool off = env_flag("DM_NO_ATTN16");
     return !off && heads == 4 && dh == 32 && dim % 256 == 0 && dim >= 256 && dim <= 1024;  // 4 channel tiles per wave and pass
 }
 

@@ -32,113 +32,20 @@ __device__ __forceinline__ f32x4 make_f32x4(float a, float b, float c, float d) 
 template <int DH>
 constexpr int lstr() { return DH + 4; }
 
-// part 1: grid (ceil(n / 64), heads, B), one wave (lane = token): dq, and this block's share of dctx.  One head per block
-// keeps the tile at 22 KB, so seven blocks share a CU and hide each other's row loads.
+// The LinearAttention backward is three launches: linattn_bwd_q_mfma_kernel (dq, and each 64-token block's share of dctx),
+// this kernel, then linattn_bwd_kv_mfma_kernel (dk, dv).
+// part 2: grid (heads, B), 256 threads: dctx = sum of the block shares (left in share 0), per d the softmax statistics of
+// k over the tokens (the forward pass's kstats) and S[d] -> stats (B, heads, 3, DH), and the gradients of this image's 4
+// memory key/value tokens.
 template <int DH>
-__global__ __launch_bounds__(64) void linattn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ ctx,
-                                                           const float* __restrict__ dout, float* __restrict__ dqkv,
-                                                           float* __restrict__ dctx_part, int n, int heads, float scale) {
-    __shared__ __attribute__((aligned(16))) float cs[DH * DH];   // ctx of this (image, head)
-    __shared__ __attribute__((aligned(16))) float ps[64 * lstr<DH>()];   // scale * p
-    __shared__ __attribute__((aligned(16))) float ds[64 * lstr<DH>()];   // dout
-    const int blk = blockIdx.x, nblk = gridDim.x, h = blockIdx.y, b = blockIdx.z;
-    const int tl = threadIdx.x;
-    const int tok = blk * 64 + tl;
-    const int ld = 3 * heads * DH, hid = heads * DH;
-    {
-        const f32x4* src = reinterpret_cast<const f32x4*>(ctx + (size_t)(b * heads + h) * DH * DH);
-        for (int i = tl; i < DH * DH / 4; i += 64) reinterpret_cast<f32x4*>(cs)[i] = src[i];
-    }
-    float q[DH], dq[DH], dov[DH];
-    const bool ok = tok < n;
-    const f32x4* qp = reinterpret_cast<const f32x4*>(qkv + ((size_t)b * n + (ok ? tok : 0)) * ld + h * DH);
-    const f32x4* dp = reinterpret_cast<const f32x4*>(dout + ((size_t)b * n + (ok ? tok : 0)) * hid + h * DH);
-#pragma unroll
-    for (int j = 0; j < DH / 4; ++j) {
-        const f32x4 a = qp[j], c = dp[j];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            q[4 * j + i] = a[i];
-            dov[4 * j + i] = ok ? c[i] : 0.f;
-        }
-    }
-    float m = -INFINITY;
-#pragma unroll
-    for (int d = 0; d < DH; ++d) m = fmaxf(m, q[d]);
-    float sum = 0.f;
-#pragma unroll
-    for (int d = 0; d < DH; ++d) {
-        q[d] = __expf(q[d] - m);
-        sum += q[d];
-    }
-    const float inv = 1.0f / sum;
-    __syncthreads();
-    float dot = 0.f;
-#pragma unroll
-    for (int d = 0; d < DH; ++d) {
-        q[d] *= inv;  // p
-        float s = 0.f;
-        const float* cr = cs + d * DH;
-#pragma unroll
-        for (int e = 0; e < DH; ++e) s += cr[e] * dov[e];
-        dq[d] = s;  // dqs
-        dot += q[d] * s;
-    }
-    if (ok) {
-        f32x4* o = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + tok) * ld + h * DH);
-#pragma unroll
-        for (int j = 0; j < DH / 4; ++j)
-            o[j] = make_f32x4(scale * q[4 * j] * (dq[4 * j] - dot), scale * q[4 * j + 1] * (dq[4 * j + 1] - dot),
-                              scale * q[4 * j + 2] * (dq[4 * j + 2] - dot), scale * q[4 * j + 3] * (dq[4 * j + 3] - dot));
-    }
-#pragma unroll
-    for (int j = 0; j < DH / 4; ++j) {
-        const float z = ok ? scale : 0.f;
-        *reinterpret_cast<f32x4*>(ps + tl * lstr<DH>() + 4 * j) =
-            make_f32x4(z * q[4 * j], z * q[4 * j + 1], z * q[4 * j + 2], z * q[4 * j + 3]);
-        *reinterpret_cast<f32x4*>(ds + tl * lstr<DH>() + 4 * j) = make_f32x4(dov[4 * j], dov[4 * j + 1], dov[4 * j + 2], dov[4 * j + 3]);
-    }
-    __syncthreads();
-    // dctx share of this block: lane -> (d, EPL e's), tokens in order
-    {
-        constexpr int EPL = DH * DH / 64, LLPR = DH == 32 ? 1 : 0;  // e's per lane (16 / 64), log2 lanes per row
-        const int d = tl >> LLPR, e0 = (tl & ((1 << LLPR) - 1)) * EPL;
-        float acc[EPL];
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
-        for (int t = 0; t < 64; ++t) {
-            const float pv = ps[t * lstr<DH>() + d];
-            const f32x4* dr = reinterpret_cast<const f32x4*>(ds + t * lstr<DH>() + e0);
-#pragma unroll
-            for (int j = 0; j < EPL / 4; ++j) {
-                const f32x4 v = dr[j];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[4 * j + i] += pv * v[i];
-            }
-        }
-        f32x4* o = reinterpret_cast<f32x4*>(dctx_part + ((((size_t)b * nblk + blk) * heads + h) * DH + d) * DH + e0);
-#pragma unroll
-        for (int j = 0; j < EPL / 4; ++j) o[j] = make_f32x4(acc[4 * j], acc[4 * j + 1], acc[4 * j + 2], acc[4 * j + 3]);
-    }
-}
-
-// part 2a: grid (heads, B), 256 threads: dctx = sum of the block shares (left in share 0), per d the softmax statistics of
-// k over the tokens (memory tokens first, as the reference concatenates them) and S[d] -> stats (B, heads, 3, DH), and the
-// gradients of this image's 4 memory key/value tokens.  The column passes map the 256 threads onto (token stripe, column):
-// 8 stripes of 32 columns, or 4 of 64.
-template <int DH>
-__global__ __launch_bounds__(256) void linattn_bwd_stats_kernel(const float* __restrict__ qkv, const float* __restrict__ mem_kv,
-                                                                const float* __restrict__ ctx, float* __restrict__ dctx_part,
-                                                                int nblk, float* __restrict__ stats,
-                                                                float* __restrict__ dmem_part,
-                                                                const float* __restrict__ kstats, int n, int heads) {
-    constexpr int LDH = bwd_log2_dh<DH>(), NPART = 256 / DH, NJ = DH * DH / 256;
+__global__ __launch_bounds__(256) void linattn_bwd_stats_kernel(const float* __restrict__ mem_kv, const float* __restrict__ ctx,
+                                                                float* __restrict__ dctx_part, int nblk,
+                                                                float* __restrict__ stats, float* __restrict__ dmem_part,
+                                                                const float* __restrict__ kstats, int heads) {
+    constexpr int LDH = bwd_log2_dh<DH>(), NJ = DH * DH / 256;
     __shared__ float dctx[DH][DH + 1];
     __shared__ float kmax[DH], kinv[DH], S[DH];
-    __shared__ float red[NPART][DH];
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-    const int ld = 3 * heads * DH;
-    const float* kbase = qkv + (size_t)b * n * ld + heads * DH + h * DH;
     const float* mk = mem_kv + (size_t)h * DH * NMEM;  // [d][j]
     {  // the block shares of dctx, summed in block order; the 4 elements of a thread x 4 shares are in flight together
         float s[NJ];
@@ -168,64 +75,16 @@ __global__ __launch_bounds__(256) void linattn_bwd_stats_kernel(const float* __r
             dctx_part[((size_t)b * nblk * heads + h) * DH * DH + i] = s[j];
         }
     }
-    // kstats (max and sum over tokens of exp(k - max), per column) as the forward context kernel left them on the tape; without
-    // them (kstats == nullptr) the two passes over the n key rows are redone here, 8 lanes deep per column
-    if (kstats) {
-        if (tid < DH) {
-            kmax[tid] = kstats[(size_t)(b * heads + h) * 2 * DH + tid];
-            red[0][tid] = kstats[(size_t)(b * heads + h) * 2 * DH + DH + tid];
-        } else if (tid < NPART * DH) {
-            red[tid >> LDH][tid & (DH - 1)] = 0.f;
-        }
-        __syncthreads();
-    } else {
-        const int d = tid & (DH - 1), part = tid >> LDH;
-        float m = part < NMEM ? mk[d * NMEM + part] : -INFINITY;
-        {
-            int t = part;
-            for (; t + 7 * NPART < n; t += 8 * NPART) {  // 8 independent row loads in flight
-                float kv[8];
-    #pragma unroll
-                for (int j = 0; j < 8; ++j) kv[j] = kbase[(size_t)(t + NPART * j) * ld + d];
-    #pragma unroll
-                for (int j = 0; j < 8; ++j) m = fmaxf(m, kv[j]);
-            }
-            for (; t < n; t += NPART) m = fmaxf(m, kbase[(size_t)t * ld + d]);
-        }
-        red[part][d] = m;
-        __syncthreads();
-        if (tid < DH) {
-            float mm = red[0][tid];
-            for (int q = 1; q < NPART; ++q) mm = fmaxf(mm, red[q][tid]);
-            kmax[tid] = mm;
-        }
-        __syncthreads();
-        const float km = kmax[d];
-        float s = part < NMEM ? __expf(mk[d * NMEM + part] - km) : 0.f;
-        {
-            int t = part;
-            for (; t + 7 * NPART < n; t += 8 * NPART) {
-                float kv[8];
-    #pragma unroll
-                for (int j = 0; j < 8; ++j) kv[j] = kbase[(size_t)(t + NPART * j) * ld + d];
-    #pragma unroll
-                for (int j = 0; j < 8; ++j) s += __expf(kv[j] - km);
-            }
-            for (; t < n; t += NPART) s += __expf(kbase[(size_t)t * ld + d] - km);
-        }
-        __syncthreads();
-        red[part][d] = s;
-        __syncthreads();
-    }
+    __syncthreads();
     if (tid < DH) {
-        float ss = 0.f;
-        for (int q = 0; q < NPART; ++q) ss += red[q][tid];
+        // kstats: the column max and the column sum over tokens of exp(k - max), as the forward context kernel left them
+        const float* ks = kstats + (size_t)(b * heads + h) * 2 * DH;
         const float* cr = ctx + ((size_t)(b * heads + h) * DH + tid) * DH;
         float sd = 0.f;
         for (int e = 0; e < DH; ++e) sd += dctx[tid][e] * cr[e];
         float* st = stats + (size_t)(b * heads + h) * 3 * DH;
-        st[tid] = kmax[tid];
-        st[DH + tid] = kinv[tid] = 1.0f / ss;
+        st[tid] = kmax[tid] = ks[tid];
+        st[DH + tid] = kinv[tid] = 1.0f / ks[DH + tid];
         st[2 * DH + tid] = S[tid] = sd;
     }
     __syncthreads();
@@ -243,68 +102,7 @@ __global__ __launch_bounds__(256) void linattn_bwd_stats_kernel(const float* __r
     }
 }
 
-// part 2b: grid (ceil(n / 64), heads, B), one wave (lane = token): dk, dv.  k and v rows sit in registers; dk overwrites k
-// row by row.
-template <int DH>
-__global__ __launch_bounds__(64, DH == 32 ? 3 : 1) void linattn_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ dctx_part,
-                                                            int nblk, const float* __restrict__ stats, float* __restrict__ dqkv,
-                                                            int n, int heads) {
-    __shared__ __attribute__((aligned(16))) float dctx[DH * DH];
-    __shared__ float st[3 * DH];
-    const int h = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
-    const int ld = 3 * heads * DH;
-    {
-        const f32x4* src = reinterpret_cast<const f32x4*>(dctx_part + ((size_t)b * nblk * heads + h) * DH * DH);
-        for (int i = lane; i < DH * DH / 4; i += 64) reinterpret_cast<f32x4*>(dctx)[i] = src[i];
-        for (int i = lane; i < 3 * DH; i += 64) st[i] = stats[(size_t)(b * heads + h) * 3 * DH + i];
-    }
-    __syncthreads();
-    const int t = blockIdx.x * 64 + lane;
-    if (t >= n) return;
-    // two passes over dctx, so that only two DH-vectors and one dctx row are live at a time (one pass holding k, v, dv and
-    // the prefetched rows spills at 3 waves per SIMD):  dv[e] = sum_d ks[d] dctx[d][e], then dk[d] = ks[d] (dctx[d] . v - S[d])
-    float kk[DH], vv[DH];
-    const f32x4* kp = reinterpret_cast<const f32x4*>(qkv + ((size_t)b * n + t) * ld + heads * DH + h * DH);
-    const f32x4* vp = reinterpret_cast<const f32x4*>(qkv + ((size_t)b * n + t) * ld + 2 * heads * DH + h * DH);
-    f32x4* ok = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + t) * ld + heads * DH + h * DH);
-    f32x4* ov = reinterpret_cast<f32x4*>(dqkv + ((size_t)b * n + t) * ld + 2 * heads * DH + h * DH);
-#pragma unroll
-    for (int j = 0; j < DH / 4; ++j) {
-        const f32x4 a = kp[j];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            kk[4 * j + i] = __expf(a[i] - st[4 * j + i]) * st[DH + 4 * j + i];  // ks
-            vv[4 * j + i] = 0.f;                                                 // dv
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < DH; ++d) {
-#pragma unroll
-        for (int e = 0; e < DH; ++e) vv[e] += kk[d] * dctx[d * DH + e];
-        asm volatile("" ::: "memory");  // one dctx row in flight
-    }
-#pragma unroll
-    for (int j = 0; j < DH / 4; ++j) ov[j] = make_f32x4(vv[4 * j], vv[4 * j + 1], vv[4 * j + 2], vv[4 * j + 3]);
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int j = 0; j < DH / 4; ++j) {
-        const f32x4 c = vp[j];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) vv[4 * j + i] = c[i];
-    }
-#pragma unroll
-    for (int d = 0; d < DH; ++d) {
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < DH; ++e) s += dctx[d * DH + e] * vv[e];
-        kk[d] *= s - st[2 * DH + d];  // dk
-        asm volatile("" ::: "memory");
-    }
-#pragma unroll
-    for (int j = 0; j < DH / 4; ++j) ok[j] = make_f32x4(kk[4 * j], kk[4 * j + 1], kk[4 * j + 2], kk[4 * j + 3]);
-}
-
-// ---- the same two passes on the matrix core (v_mfma_f32_32x32x2_f32), what the training step runs.  Every product of the
+// ---- parts 1 and 3 on the matrix core (v_mfma_f32_32x32x2_f32), grid (ceil(n / 64), heads, B).  Every product of the
 // backward pass is a (tokens x DH) x (DH x DH) GEMM; computed TRANSPOSED -- the DH x DH matrix (ctx, dctx) is the A operand, the
 // token rows the B operand -- the result D[i][j = token] of a 32-row tile leaves lane (token, half) with the 16 columns
 //     dset(r) = (r & 3) + 8 (r >> 2) + 4 half,   r = 0 .. 15      (four float4 chunks 2 m + half of the token's 32-float row)
@@ -312,7 +110,8 @@ __global__ __launch_bounds__(64, DH == 32 ? 3 : 1) void linattn_bwd_kv_kernel(co
 // operand of the next product is exactly those registers: a lane loads DH / 8 chunks of q / dout / k / v, keeps everything
 // row-wise (softmax over the columns, the dot products) in registers plus one exchange with lane ^ 32, and stores them.  At
 // DH = 64 tile I of a result holds the columns 32 I + dset(r) = dset(16 I + r): the same registers.  One wave = 64 tokens (two
-// 32-token tiles), 64 MFMAs per pass at DH = 32 where the VALU form issued ~2000 FMAs and ~600 LDS broadcasts per lane.
+// 32-token tiles), 64 MFMAs per pass at DH = 32 where a lane-per-token VALU form issued ~2000 FMAs and ~600 LDS broadcasts
+// per lane.
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 template <int DH>
@@ -537,22 +336,14 @@ static int linear_attention_core_bwd(const float* qkv, const float* mem_kv, cons
     const int nblk = (n + 63) / 64;
     const float scale = 1.0f / sqrtf((float)DH);
     float* stats = ws + (size_t)B * nblk * heads * DH * DH;
-    static const bool valu = std::getenv("DM_LINATTN_BWD_VALU") != nullptr;  // the lane-per-token VALU kernels (A/B, forced-path test)
-    if (valu)
-        hipLaunchKernelGGL(linattn_bwd_q_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ctx, dout, dqkv, ws, n, heads,
-                           scale);
-    else
-        hipLaunchKernelGGL(linattn_bwd_q_mfma_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ctx, dout, dqkv, ws, n,
-                           heads, scale);
+    hipLaunchKernelGGL(linattn_bwd_q_mfma_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ctx, dout, dqkv, ws, n, heads,
+                       scale);
     DM_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(linattn_bwd_stats_kernel<DH>, dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx, ws, nblk, stats,
-                       dmem_part, kstats, n, heads);
+    hipLaunchKernelGGL(linattn_bwd_stats_kernel<DH>, dim3(heads, B), dim3(256), 0, s, mem_kv, ctx, ws, nblk, stats, dmem_part,
+                       kstats, heads);
     DM_CHECK_HIP(hipGetLastError());
-    if (valu)
-        hipLaunchKernelGGL(linattn_bwd_kv_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ws, nblk, stats, dqkv, n, heads);
-    else
-        hipLaunchKernelGGL(linattn_bwd_kv_mfma_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ws, nblk, stats, dqkv, n,
-                           heads);
+    hipLaunchKernelGGL(linattn_bwd_kv_mfma_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ws, nblk, stats, dqkv, n,
+                       heads);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -564,6 +355,7 @@ int launch_linear_attention_core_bwd(const float* qkv, const float* mem_kv, cons
                                      const float* kstats) {
     DM_REQUIRE((dh == 32 || dh == 64) && heads >= 1 && heads <= 16, "linear attention backward: dim_head 32 or 64");
     DM_REQUIRE(B <= 65535 && n >= 1, "linear attention backward: batch");
+    DM_REQUIRE(kstats, "linear attention backward: the key statistics of the forward context kernel");
     return dh == 32 ? linear_attention_core_bwd<32>(qkv, mem_kv, ctx, dout, ws, dqkv, dmem_part, B, n, heads, s, kstats)
                     : linear_attention_core_bwd<64>(qkv, mem_kv, ctx, dout, ws, dqkv, dmem_part, B, n, heads, s, kstats);
 }
@@ -586,11 +378,7 @@ struct AttnBwdParams {
     float scale;
 };
 
-// CACHE (short sequences: nq * (nk + n_mem) <= 4096, e.g. the 16 tokens + 4 memory rows of the 32x32 U-Net's bottleneck): the
-// scores q_i . k_j and dP_ij are formed ONCE and kept in LDS -- the plain form recomputes the 32-wide dot products in each of
-// its three passes over the keys and again per (key, query) in the second phase, and with one thread per query that serial
-// chain IS the kernel's time (42 us at any batch for 16 queries); same summation order within every dot product.
-template <bool CACHE, int DH>
+template <int DH>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
     constexpr int LDH = bwd_log2_dh<DH>();
     extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -602,8 +390,6 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
     float* rm = Ds + n * (DH + 1);       // [n] row max
     float* rl = rm + n;                   // [n] 1 / row sum
     float* rD = rl + n;                   // [n] D_i
-    float* Pc = rD + n;                   // CACHE: [n][nkt] scores -> exp -> P_ij
-    float* Sc = Pc + (CACHE ? n * nkt : 0);  // CACHE: [n][nkt] dP_ij -> dS_ij
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int hid = p.heads * DH;
     const float scale = p.scale;
@@ -638,67 +424,35 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
         float dq[DH];
 #pragma unroll
         for (int d = 0; d < DH; ++d) dq[d] = 0.f;
-        if constexpr (CACHE) {
-            float* Pi = Pc + i * nkt;
-            float* Si = Sc + i * nkt;
-            for (int j = 0; j < nkt; ++j) {
-                float sc = 0.f, dp = 0.f;
+        for (int j = 0; j < nkt; ++j) {
+            float sc = 0.f;
 #pragma unroll
-                for (int d = 0; d < DH; ++d) {
-                    sc += q[d] * Ks[j * (DH + 1) + d];
-                    dp += dov[d] * Vs[j * (DH + 1) + d];
-                }
-                Pi[j] = sc * scale;
-                Si[j] = dp;
-                m = fmaxf(m, sc * scale);
-            }
-            for (int j = 0; j < nkt; ++j) {
-                const float e = __expf(Pi[j] - m);
-                Pi[j] = e;
-                l += e;
-                D += e * Si[j];
-            }
-            linv = 1.0f / l;
-            D *= linv;
-            for (int j = 0; j < nkt; ++j) {
-                const float P = Pi[j] * linv;
-                const float dS = P * (Si[j] - D);
-                Pi[j] = P;
-                Si[j] = dS;
+            for (int d = 0; d < DH; ++d) sc += q[d] * Ks[j * (DH + 1) + d];
+            m = fmaxf(m, sc * scale);
+        }
+        for (int j = 0; j < nkt; ++j) {
+            float sc = 0.f, dp = 0.f;
 #pragma unroll
-                for (int d = 0; d < DH; ++d) dq[d] += dS * Ks[j * (DH + 1) + d];
+            for (int d = 0; d < DH; ++d) {
+                sc += q[d] * Ks[j * (DH + 1) + d];
+                dp += dov[d] * Vs[j * (DH + 1) + d];
             }
-        } else {
-            for (int j = 0; j < nkt; ++j) {
-                float sc = 0.f;
+            const float e = __expf(sc * scale - m);
+            l += e;
+            D += e * dp;
+        }
+        linv = 1.0f / l;
+        D *= linv;
+        for (int j = 0; j < nkt; ++j) {
+            float sc = 0.f, dp = 0.f;
 #pragma unroll
-                for (int d = 0; d < DH; ++d) sc += q[d] * Ks[j * (DH + 1) + d];
-                m = fmaxf(m, sc * scale);
+            for (int d = 0; d < DH; ++d) {
+                sc += q[d] * Ks[j * (DH + 1) + d];
+                dp += dov[d] * Vs[j * (DH + 1) + d];
             }
-            for (int j = 0; j < nkt; ++j) {
-                float sc = 0.f, dp = 0.f;
+            const float dS = __expf(sc * scale - m) * linv * (dp - D);
 #pragma unroll
-                for (int d = 0; d < DH; ++d) {
-                    sc += q[d] * Ks[j * (DH + 1) + d];
-                    dp += dov[d] * Vs[j * (DH + 1) + d];
-                }
-                const float e = __expf(sc * scale - m);
-                l += e;
-                D += e * dp;
-            }
-            linv = 1.0f / l;
-            D *= linv;
-            for (int j = 0; j < nkt; ++j) {
-                float sc = 0.f, dp = 0.f;
-#pragma unroll
-                for (int d = 0; d < DH; ++d) {
-                    sc += q[d] * Ks[j * (DH + 1) + d];
-                    dp += dov[d] * Vs[j * (DH + 1) + d];
-                }
-                const float dS = __expf(sc * scale - m) * linv * (dp - D);
-#pragma unroll
-                for (int d = 0; d < DH; ++d) dq[d] += dS * Ks[j * (DH + 1) + d];
-            }
+            for (int d = 0; d < DH; ++d) dq[d] += dS * Ks[j * (DH + 1) + d];
         }
         rm[i] = m;
         rl[i] = linv;
@@ -718,20 +472,14 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
             dv[d] = 0.f;
         }
         for (int i = 0; i < n; ++i) {
-            float P, dS;
-            if constexpr (CACHE) {
-                P = Pc[i * nkt + j];
-                dS = Sc[i * nkt + j];
-            } else {
-                float sc = 0.f, dp = 0.f;
+            float sc = 0.f, dp = 0.f;
 #pragma unroll
-                for (int d = 0; d < DH; ++d) {
-                    sc += Qs[i * (DH + 1) + d] * kk[d];
-                    dp += Ds[i * (DH + 1) + d] * vv[d];
-                }
-                P = __expf(sc * scale - rm[i]) * rl[i];
-                dS = P * (dp - rD[i]);
+            for (int d = 0; d < DH; ++d) {
+                sc += Qs[i * (DH + 1) + d] * kk[d];
+                dp += Ds[i * (DH + 1) + d] * vv[d];
             }
+            const float P = __expf(sc * scale - rm[i]) * rl[i];
+            const float dS = P * (dp - rD[i]);
 #pragma unroll
             for (int d = 0; d < DH; ++d) {
                 dk[d] += dS * Qs[i * (DH + 1) + d];
@@ -756,11 +504,12 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
     }
 }
 
-// ---- short sequences (the CACHE condition), every phase spread over the 256 threads: the 16 tokens + 4 memory rows of the
-// 32x32 U-Net's bottleneck are 16 queries and 20 keys, so "thread = query" leaves 240 threads idle while 16 of them walk 20 keys
-// x three 32-wide dot products each (22 us at any batch).  Here (1) thread = (query, key) pair forms the score and dP, (2) thread
-// = query normalises its row (no dot products left), (3) thread = (query, d) forms dq, (4) thread = (key, d) forms dk and dv.
-// Every sum runs over the same index in the same order as attn_bwd_kernel's (d, then keys, then queries): identical results.
+// ---- short sequences (attn_bwd_cached: nq * (nk + n_mem) <= 4096), every phase spread over the 256 threads: the 16 tokens + 4
+// memory rows of the 32x32 U-Net's bottleneck are 16 queries and 20 keys, so "thread = query" leaves 240 threads idle while 16
+// of them walk 20 keys x three 32-wide dot products each (22 us at any batch).  Here (1) thread = (query, key) pair forms the
+// score and dP, (2) thread = query normalises its row (no dot products left), (3) thread = (query, d) forms dq, (4) thread =
+// (key, d) forms dk and dv. Every sum runs over the same index in the same order as attn_bwd_kernel's (d, then keys, then
+// queries): identical results.
 template <int DH>
 __global__ __launch_bounds__(256) void attn_bwd_pairs_kernel(const AttnBwdParams p) {
     constexpr int LDH = bwd_log2_dh<DH>();
@@ -770,7 +519,7 @@ __global__ __launch_bounds__(256) void attn_bwd_pairs_kernel(const AttnBwdParams
     float* Vs = Ks + nkt * (DH + 1);     // [nkt][DH + 1]
     float* Qs = Vs + nkt * (DH + 1);     // [n][DH + 1]
     float* Ds = Qs + n * (DH + 1);       // [n][DH + 1]  dout
-    float* Pc = Ds + n * (DH + 1) + 3 * n;  // (same offsets as attn_bwd_kernel<true>: one LDS size for both)
+    float* Pc = Ds + n * (DH + 1) + 3 * n;  // after attn_bwd_kernel's layout (attn_bwd_lds_bytes' cache term)
     float* Sc = Pc + n * nkt;
     const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const int hid = p.heads * DH;
@@ -998,7 +747,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kv_tiled_kernel(const AttnBwdPara
 }
 
 static bool attn_bwd_cached(int nq, int nk, int n_mem) {
-    static const bool off = std::getenv("DM_ATTN_BWD_NO_CACHE") != nullptr;  // A/B, and the tests' other path
+    static const bool off = env_flag("DM_ATTN_BWD_NO_CACHE");  // A/B, and the tests' other path
     return !off && (size_t)nq * (nk + n_mem) <= 4096;
 }
 static size_t attn_bwd_lds_bytes(int nq, int nk, int n_mem, int dh) {
@@ -1006,7 +755,7 @@ static size_t attn_bwd_lds_bytes(int nq, int nk, int n_mem, int dh) {
     return ((size_t)(2 * (nk + n_mem) + 2 * nq) * (dh + 1) + 3 * nq + cache) * sizeof(float);
 }
 static bool attn_bwd_tiled(int nq, int nk, int n_mem, int dh) {
-    static const bool force = std::getenv("DM_ATTN_BWD_TILED") != nullptr;  // tests: the tiled form on small shapes too
+    static const bool force = env_flag("DM_ATTN_BWD_TILED");  // tests: the tiled form on small shapes too
     return force || attn_bwd_lds_bytes(nq, nk, n_mem, dh) > 160 * 1024;
 }
 // floats of statistics workspace the tiled form needs (0 when the LDS-resident kernel takes the shape)
@@ -1026,24 +775,16 @@ static int launch_attn_bwd(const AttnBwdParams& p, int B, float* ws, hipStream_t
         DM_CHECK_HIP(hipGetLastError());
         return 0;
     }
-    static const bool no_pairs = std::getenv("DM_ATTN_BWD_NO_PAIRS") != nullptr;
-    if (attn_bwd_cached(p.nq, p.nk, p.n_mem) && !no_pairs) {
+    if (attn_bwd_cached(p.nq, p.nk, p.n_mem)) {
         static LdsOptIn flagp;
         if (lds_opt_in(flagp, reinterpret_cast<const void*>(attn_bwd_pairs_kernel<DH>), 1)) return 1;
         hipLaunchKernelGGL(attn_bwd_pairs_kernel<DH>, dim3(p.heads, B), dim3(256), lds, s, p);
         DM_CHECK_HIP(hipGetLastError());
         return 0;
     }
-    if (attn_bwd_cached(p.nq, p.nk, p.n_mem)) {
-        static LdsOptIn flagc;
-        if (lds_opt_in(flagc, reinterpret_cast<const void*>(attn_bwd_kernel<true, DH>), 1)) return 1;
-        hipLaunchKernelGGL((attn_bwd_kernel<true, DH>), dim3(p.heads, B), dim3(256), lds, s, p);
-        DM_CHECK_HIP(hipGetLastError());
-        return 0;
-    }
     static LdsOptIn flag;
-    if (lds_opt_in(flag, reinterpret_cast<const void*>(attn_bwd_kernel<false, DH>), 1)) return 1;
-    hipLaunchKernelGGL((attn_bwd_kernel<false, DH>), dim3(p.heads, B), dim3(256), lds, s, p);
+    if (lds_opt_in(flag, reinterpret_cast<const void*>(attn_bwd_kernel<DH>), 1)) return 1;
+    hipLaunchKernelGGL(attn_bwd_kernel<DH>, dim3(p.heads, B), dim3(256), lds, s, p);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -110,7 +110,6 @@ ConvGeom conv_plan(int B, int Ho, int Wo, int Cout, int KH, int KW, int stride, 
                    bool allow_split, int grid_z) {
     static const int target_wgs = env_int("DM_CONV_TARGET_WGS", 512);
     static const int min_fused_wgs = env_int("DM_CONV_MIN_FUSED_WGS", 512);
-    static const int force_tps = env_int("DM_CONV_TPS", 0);
     static const int max_splits = env_int("DM_CONV_MAX_SPLITS", 8);
     ConvGeom g{};
     g.CK = conv_ck_for(C0, C1);
@@ -173,8 +172,6 @@ ConvGeom conv_plan(int B, int Ho, int Wo, int Cout, int KH, int KW, int stride, 
     g.TPS = KW;
     if (g.WN > 1 && (g.halo_floats + 2 * KW * NT * CKP) * 4 > 80 * 1024) g.TPS = 1;
     if (KW * NT * (g.CK / 4) > 256 * wregs_for(g.WN, g.CK)) g.TPS = 1;
-    if (force_tps == 1) g.TPS = 1;
-    if (force_tps == 3) g.TPS = KW;
     g.w_floats = g.TPS * NT * CKP;
     // split-K over channel chunks when the grid would leave CUs idle
     g.splits = 1;

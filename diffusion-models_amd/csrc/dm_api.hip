@@ -6,7 +6,6 @@
 #include "dm_common.h"
 
 #include <array>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -198,8 +197,7 @@ struct Arena {
         return reinterpret_cast<float*>(origin() + at);
     }
     void release(const void* p) {
-        static const bool off = std::getenv("DM_NO_WS_REUSE") != nullptr;  // measurement switch: one fresh block per tensor
-        if (!p || off) return;
+        if (!p) return;
         const size_t at = (size_t)(static_cast<const char*>(p) - origin());
         // blocks are sorted by offset: binary search for the one that starts at `at`
         size_t lo = 0, hi = blks.size();
@@ -340,23 +338,6 @@ struct dm_unet {
         done_recorded = true;
         return 0;
     }
-    // Independent branches of a step (res_conv next to block1, the time MLP next to init_conv) are enqueued on a second
-    // stream between a fork and a join event, eagerly and inside the captured step graph alike: at small per-GPU batches no
-    // kernel fills the chip and the branch costs nothing.  Events come from a pool (distinct objects within one capture).
-    hipStream_t side = nullptr;
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_next = 0;
-    int next_event(hipEvent_t* e) {
-        if (ev_pool.size() < 64) {
-            hipEvent_t n = nullptr;
-            DM_CHECK_HIP(hipEventCreateWithFlags(&n, hipEventDisableTiming));
-            ev_pool.push_back(n);
-            *e = n;
-            return 0;
-        }
-        *e = ev_pool[ev_next++ % ev_pool.size()];
-        return 0;
-    }
     hipStream_t cap_stream = nullptr;  // capture / replay stream when the caller passes the legacy default stream
     int graph_captures = 0;            // diagnostics (dm_unet_graph_captures)
     void drop_graph() {
@@ -437,8 +418,7 @@ static int make_conv(DeviceOwner& own, ConvLayer& L, const float* oihw, const fl
                      int KW, int stride, int pad, bool up, int pad_hi = 0) {
     L.C0 = C0; L.C1 = C1; L.Cout = Cout; L.KH = KH; L.KW = KW; L.stride = stride; L.pad = pad; L.up = up;
     L.pad_hi = pad_hi;
-    static const bool no_fold = std::getenv("DM_NO_UPFOLD") != nullptr;
-    L.fold = up && KH == 3 && KW == 3 && stride == 1 && pad == 1 && !no_fold;
+    L.fold = up && KH == 3 && KW == 3 && stride == 1 && pad == 1;
     std::vector<float> packed;
     if (L.fold) {
         // nearest x2 then conv3x3 == one 2x2 conv per output parity with summed taps:
@@ -804,46 +784,8 @@ struct Ctx {
     int B;
     const float* ss;   // [Bt][ss_total]
     int ss_stride;     // 0 when one row serves the whole batch
-    bool par = false;  // independent branches go to the handle's second stream (fork / join below)
     bool dry() const { return A->dry; }
 };
-
-// fork: everything enqueued on the side stream from here on runs after what `c.s` holds now, next to what `c.s` gets next
-static int fork_side(Ctx& c, hipStream_t* side) {
-    dm_unet* u = c.u;
-    if (!u->side) DM_CHECK_HIP(hipStreamCreateWithFlags(&u->side, hipStreamNonBlocking));
-    hipEvent_t e;
-    if (u->next_event(&e)) return 1;
-    DM_CHECK_HIP(hipEventRecord(e, c.s));
-    DM_CHECK_HIP(hipStreamWaitEvent(u->side, e, 0));
-    *side = u->side;
-    return 0;
-}
-// join: what `c.s` gets next runs after everything the side stream holds
-static int join_side(Ctx& c) {
-    dm_unet* u = c.u;
-    hipEvent_t e;
-    if (u->next_event(&e)) return 1;
-    DM_CHECK_HIP(hipEventRecord(e, u->side));
-    DM_CHECK_HIP(hipStreamWaitEvent(c.s, e, 0));
-    return 0;
-}
-// Which steps fork.  Measured on MI355X (profiles/r3_fork_join_ab.txt, hipGraph replay): forking makes every batch SLOWER
-// -- B=8 @64x64 1.669 -> 1.753 ms per step, B=32 2.858 -> 2.924, B=64 @32x32 1.984 -> 2.042, B=256 4.551 -> 4.608 -- the
-// cross-queue dependencies of a forked graph (one signal wait per fork and per join, ~20 per step) cost more than the
-// overlap of a 17 us res_conv or the 20 us time-MLP chain buys.  So the default is OFF; DM_PAR=1 switches it on (the tests
-// run one model with it), DM_PAR_MAX_PIXELS limits it to small steps.
-static bool par_policy(int B, int H, int W) {
-    static const int mode = env_int("DM_PAR", 0);
-    static const int max_px = env_int("DM_PAR_MAX_PIXELS", 1 << 30);
-    return mode != 0 && (int64_t)B * H * W <= max_px;
-}
-
-// policy: which eligible layers take the Winograd kernel (DM_WINO=0 none, 1 all)
-static bool wino_use(int B, int Ho, int Wo, int Cout, int C0, int C1) {
-    static const int mode = std::getenv("DM_WINO") ? std::atoi(std::getenv("DM_WINO")) : 1;
-    return mode != 0 && wino_shape_ok(B, Ho, Wo, Cout, C0, C1);
-}
 
 // residual operand of a landing pass given as the K-split partial sums of another convolution (+ its bias)
 struct ResParts {
@@ -948,7 +890,7 @@ static int plan_conv(const Ctx& c, const ConvLayer& L, bool has_in1, int Hin, in
     const bool wino4 = P.kind == 0 && L.ww4 && !L.fold && !in_nchw && !out_nchw && padw == L.pad &&
                        wino4_shape_ok(c.B, p.Ho, p.Wo, L.Cout, L.C0, L.C1);
     const bool wino = P.kind == 0 && !wino4 && L.ww && !L.fold && !in_nchw && !out_nchw && padw == L.pad &&
-                      wino_use(c.B, p.Ho, p.Wo, L.Cout, L.C0, L.C1);
+                      wino_shape_ok(c.B, p.Ho, p.Wo, L.Cout, L.C0, L.C1);
     const bool pw = P.kind == 0 && L.wpw && !L.fold && !p.s2d && !in_nchw && !out_nchw && L.pad_hi == 0 && padw == 0 &&
                     pw_shape_ok(c.B, p.Ho, p.Wo, L.Cout, L.C0, L.C1);
     if (pw) {
@@ -1062,7 +1004,7 @@ static int run_resnet(Ctx& c, const ResBlock& R, const float* x0, const float* x
     const float* scale = c.ss ? c.ss + R.ss_off : nullptr;
     // block2(h1) + res_conv(x).  When both convolutions leave partial sums for a landing pass anyway (several cout
     // tiles under one RMSNorm, or K splits), one landing serves both: it finishes block2 and adds the res_conv partials.
-    static const bool merge = std::getenv("DM_NO_RES_MERGE") == nullptr;
+    static const bool merge = !env_flag("DM_NO_RES_MERGE");
     PlannedConv P2, Pr;
     bool merged = false;
     if (R.has_res) {
@@ -1072,15 +1014,8 @@ static int run_resnet(Ctx& c, const ResBlock& R, const float* x0, const float* x
     }
     ResParts rp{};
     float* rpart = nullptr;
-    bool forked = false;
     if (merged) {
-        // res_conv reads only x: its partial sums are produced next to block1 (second stream) when the step forks
-        Ctx cs = c;
-        if (c.par && !c.dry()) {
-            if (fork_side(c, &cs.s)) return 1;
-            forked = true;
-        }
-        if (run_conv_partial(cs, R.res, x0, x1, H, W, &rpart, &rp.nsplit)) return 1;
+        if (run_conv_partial(c, R.res, x0, x1, H, W, &rpart, &rp.nsplit)) return 1;
         rp.part = rpart;
         rp.stride = (int64_t)n;
         rp.bias = R.res.bias;
@@ -1088,7 +1023,6 @@ static int run_resnet(Ctx& c, const ResBlock& R, const float* x0, const float* x
     float* h1 = c.A->alloc(n);
     float* h2 = c.A->alloc(n);
     if (run_block(c, R.c1, x0, x1, H, W, R.g1, scale, nullptr, h1)) return 1;
-    if (forked && join_side(c)) return 1;
     if (!R.has_res) {
         if (run_block(c, R.c2, h1, nullptr, H, W, R.g2, nullptr, x0, h2)) return 1;
         c.A->release(h1);
@@ -1162,14 +1096,19 @@ static int run_attn(Ctx& c, const AttnLayer& At, const float* x, int H, int W, f
     return 0;
 }
 
+// DM_NO_CROSS1: the general CrossAttention path for one context token too (and no dead-bottleneck shortcut)
+static bool cross1_off() {
+    static const bool off = env_flag("DM_NO_CROSS1");
+    return off;
+}
+
 // CrossAttention.forward (DD/denoising_diffusion_text_conditional.py:54-78); the result REPLACES x (:173-177)
 static int run_cross(Ctx& c, const CrossLayer& Cr, const float* x, int H, int W, const float* ctx, int m,
                      float** out) {
     dm_unet* u = c.u;
     const int n = H * W, inner = 4 * u->dh, dim = Cr.out.Cout, E = u->cfg.text_emb_dim;
     const size_t rows = (size_t)c.B * n;
-    static const bool one_token_path = std::getenv("DM_NO_CROSS1") == nullptr;
-    if (m == 1 && one_token_path) {
+    if (m == 1 && !cross1_off()) {
         // One context token (what every sampler of the reference passes: (B, 512) -> (B, 1, 512), :57-58): the softmax
         // over a single key is exactly 1.0, so every query's output is v and the q / k projections drop out.  The layer
         // is z_b = RMSNorm1D(to_out(to_v(ctx_b))) spread over the pixels of image b -- three row-per-image launches and
@@ -1224,8 +1163,7 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
     const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && ctx != nullptr;
     // one context token: the three CrossAttention layers ignore their image input (run_cross), which makes everything
     // between the last skip connection and cross_attn_up dead code (DM_NO_CROSS1 computes it anyway)
-    static const bool cross1 = std::getenv("DM_NO_CROSS1") == nullptr;
-    const bool dead_bottleneck = text_cross && ctx_tokens == 1 && cross1;
+    const bool dead_bottleneck = text_cross && ctx_tokens == 1 && !cross1_off();
     // the time embedding is one row when the whole batch shares t (samplers), else one row per sample
     const int Bt = (step_times && !text_concat) ? 1 : B;
     const int Rt = step_times ? 1 : B;  // rows of the sinusoid / time_mlp
@@ -1235,15 +1173,10 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
     float* e1 = A.alloc((size_t)Rt * td);
     float* temb = A.alloc((size_t)B * td);
     float* ss = A.alloc((size_t)Bt * u->ss_total);
-    // The time embedding (sinusoid, time_mlp, every ResnetBlock.mlp: 4+ dependent launches) does not depend on x: when the
-    // step forks it runs on the second stream next to init_conv.  Nothing it allocates is released before the join.
-    c.par = !A.dry && par_policy(B, H, W);
-    hipStream_t ts = s;
-    if (c.par && fork_side(c, &ts)) return 1;
     if (!A.dry) {
-        if (launch_sinusoid(t_dev, step_times, step_dev, u->freqs, e0, Rt, (lsd > 0 ? lsd : cfg.dim) / 2, ts, lsd > 0)) return 1;
-        if (launch_linear_rows(e0, fdim, u->tw1, u->tb1, e1, td, Rt, fdim, td, 0, 2, ts)) return 1;
-        if (launch_linear_rows(e1, td, u->tw2, u->tb2, temb, td, Rt, td, td, 0, 0, ts)) return 1;
+        if (launch_sinusoid(t_dev, step_times, step_dev, u->freqs, e0, Rt, (lsd > 0 ? lsd : cfg.dim) / 2, s, lsd > 0)) return 1;
+        if (launch_linear_rows(e0, fdim, u->tw1, u->tb1, e1, td, Rt, fdim, td, 0, 2, s)) return 1;
+        if (launch_linear_rows(e1, td, u->tw2, u->tb2, temb, td, Rt, td, td, 0, 0, s)) return 1;
     }
     const float* tfinal = temb;
     float *cat = nullptr, *tf0 = nullptr;
@@ -1256,21 +1189,21 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
         if (!A.dry) {
             // left half: the time embedding of every row (one broadcast launch when the batch shares t)
             if (Rt == 1) {
-                if (launch_broadcast_rows(temb, cat, B, td, 2 * td, ts)) return 1;
+                if (launch_broadcast_rows(temb, cat, B, td, 2 * td, s)) return 1;
             } else {
                 DM_CHECK_HIP(hipMemcpy2DAsync(cat, 2 * td * sizeof(float), temb, td * sizeof(float),
-                                              td * sizeof(float), B, hipMemcpyDeviceToDevice, ts));
+                                              td * sizeof(float), B, hipMemcpyDeviceToDevice, s));
             }
-            if (launch_linear_rows(ctx, cfg.text_emb_dim, u->tp_w0, u->tp_b0, tf0, td, B, cfg.text_emb_dim, td, 0, 2, ts))
+            if (launch_linear_rows(ctx, cfg.text_emb_dim, u->tp_w0, u->tp_b0, tf0, td, B, cfg.text_emb_dim, td, 0, 2, s))
                 return 1;
-            if (launch_linear_rows(tf0, td, u->tp_w2, u->tp_b2, cat + td, 2 * td, B, td, td, 0, 0, ts)) return 1;
-            if (launch_linear_rows(cat, 2 * td, u->tc_w, u->tc_b, t2, td, B, 2 * td, td, 0, 0, ts)) return 1;
+            if (launch_linear_rows(tf0, td, u->tp_w2, u->tp_b2, cat + td, 2 * td, B, td, td, 0, 0, s)) return 1;
+            if (launch_linear_rows(cat, 2 * td, u->tc_w, u->tc_b, t2, td, B, 2 * td, td, 0, 0, s)) return 1;
         }
         tfinal = t2;
     }
     if (!A.dry) {
         // every ResnetBlock.mlp (SiLU -> Linear) in one launch
-        if (launch_linear_rows(tfinal, td, u->ss_w, u->ss_b, ss, u->ss_total, Bt, td, u->ss_total, 1, 0, ts)) return 1;
+        if (launch_linear_rows(tfinal, td, u->ss_w, u->ss_b, ss, u->ss_total, Bt, td, u->ss_total, 1, 0, s)) return 1;
     }
     c.ss = A.dry ? reinterpret_cast<const float*>(16) : ss;  // non-null marker in dry mode
     c.ss_stride = Bt == 1 ? 0 : u->ss_total;
@@ -1278,7 +1211,6 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
     const int n_st = cfg.n_stages;
     float* x = A.alloc((size_t)B * H * W * u->init_dim);
     if (run_conv(c, u->init_conv, x_nchw, nullptr, H, W, x, 0, nullptr, nullptr, nullptr, /*in_nchw=*/true)) return 1;
-    if (c.par && join_side(c)) return 1;
     if (cat) A.release(cat);
     if (tf0) A.release(tf0);
     if (tfinal != temb) A.release(tfinal);
@@ -1482,8 +1414,6 @@ void dm_unet_destroy(dm_unet* u) {
     if (u->train) free_train(u);
     u->drop_graph();
     if (u->cap_stream) (void)hipStreamDestroy(u->cap_stream);
-    if (u->side) (void)hipStreamDestroy(u->side);
-    for (hipEvent_t e : u->ev_pool) (void)hipEventDestroy(e);
     if (u->done_ev) (void)hipEventDestroy(u->done_ev);
     if (u->ws) (void)hipFree(u->ws);
     if (u->state_dev) (void)hipFree(u->state_dev);

@@ -12,11 +12,15 @@
 
 namespace dm {
 
-// integer tuning knob from the environment (read once by the callers: they keep the value in a function-local static)
+// The environment is read here only.  Each DM_* variable has one reading site, which keeps the value in a function-local
+// static (read once per process); a switch more than one dispatcher consults is a function of its own (winograd_off()).
+// integer tuning knob
 inline int env_int(const char* name, int dflt) {
     const char* e = std::getenv(name);
     return e ? std::atoi(e) : dflt;
 }
+// on / off switch: set to any value = on
+inline bool env_flag(const char* name) { return std::getenv(name) != nullptr; }
 
 
 void set_error(const std::string& msg);
@@ -143,8 +147,9 @@ int conv_launch(const ConvParams& p, hipStream_t s);
 // ---------------------------------------------------------------------------------------
 // Winograd F(2x2, 3x3) convolution on the f32 MFMA (winograd_mfma.hip): 3x3 / stride 1 / pad 1, NHWC,
 // C0 % 8 == 0, C1 % 8 == 0, Cout % 64 == 0, even output size.  Same ConvParams / epilogue contract as
-// conv_launch; ConvGeom is reused with TW/TH/NB counted in 2x2-pixel Winograd tiles (64 per workgroup).
+// conv_launch; ConvGeom is reused with TW/TH/NB counted in 2x2-pixel Winograd tiles (32 per workgroup).
 // ---------------------------------------------------------------------------------------
+bool winograd_off();  // DM_NO_WINOGRAD: no Winograd form at all (F(2x2), F(4x4), the folded upsample, the weight gradient)
 bool wino_eligible(int Cout, int C0, int C1, int KH, int KW, int stride, int pad, bool up);
 size_t wino_packed_floats(int Cout, int C0, int C1);
 // OIHW (Cout, C0+C1, 3, 3) -> U = G g G^T in kernel layout [chunk of 8 cin][16 xi][Cout][8]
@@ -287,11 +292,10 @@ int launch_broadcast_rows(const float* src, float* dst, int rows, int n, int ld,
 // Attention cores (attention.hip); qkv is NHWC (B, n, 3*heads*dh) = [q | k | v] per pixel
 // ---------------------------------------------------------------------------------------
 // LinearAttention core: out (B, n, heads*dh); dh is 32 or 64
-bool linattn_keeps_kstats();
 int launch_linear_attention_core(const float* qkv, const float* mem_kv, float* ctx_ws, float* out, int B, int n,
                                  int heads, int dh, hipStream_t s, float* kstats = nullptr);
-// kstats (optional, B * heads * 2 * dh floats): per (image, head) the column max and the column sum of exp(k - max) the
-// context kernel formed; launch_linear_attention_core_bwd starts from them instead of two more passes over the keys.
+// kstats (B * heads * 2 * dh floats; null for inference): per (image, head) the column max and the column sum of exp(k - max)
+// the context kernel formed; launch_linear_attention_core_bwd starts from them.
 // softmax(q k^T * scale) v with `n_mem` learned key/value rows prepended.
 //   q: rows of length ldq per query token (head h at column h*dh), k/v likewise with ldk
 //   mem_k/mem_v: (heads, n_mem, dh) or nullptr
@@ -425,6 +429,7 @@ int launch_offset_noise(float* noise, const float* offset, float strength, int B
 int launch_cdist(const float* x, const float* y, float* out, int n, int m, int64_t D, hipStream_t s);
 size_t linear_dgrad_ws_floats(int R, int I, int O);
 // small_gemm.hip: the batch-row Linear layers of the training step as MFMA GEMMs
+bool small_gemm_off();  // DM_NO_SMALL_GEMM: every batch-row Linear layer on the VALU kernels instead
 bool rows_gemm_nt_ok(int R, int I, int O, int ldx);
 int launch_rows_gemm_nt(const float* x, int ldx, const float* W, const float* bias, float* y, int ldy, int R, int I, int O,
                         hipStream_t s);
@@ -478,7 +483,7 @@ int launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, co
 size_t linattn_bwd_ws_floats(int B, int n, int heads, int dh);
 int launch_linear_attention_core_bwd(const float* qkv, const float* mem_kv, const float* ctx, const float* dout, float* ws,
                                      float* dqkv, float* dmem_part, int B, int n, int heads, int dh, hipStream_t s,
-                                     const float* kstats = nullptr);
+                                     const float* kstats);
 // ws: attn_bwd_ws_floats() floats (row statistics of the tiled form; 0 floats when the sequence fits LDS)
 size_t attn_bwd_ws_floats(int B, int nq, int nk, int n_mem, int heads, int dh);
 int launch_attention_core_bwd(const float* qkv, const float* mem_kv, const float* dout, float* dqkv, float* dmem_part, float* ws,

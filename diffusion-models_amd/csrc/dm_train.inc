@@ -281,6 +281,12 @@ struct Tape {
     int hm = 0, wm = 0;
 };
 
+// DM_TRAIN_NO_LANDING_FUSE: every K-split convolution of the training step lands its partial tiles in a pass of its own
+static bool train_landing_fuse_off() {
+    static const bool off = env_flag("DM_TRAIN_NO_LANDING_FUSE");
+    return off;
+}
+
 struct TCtx {
     dm_unet* u;
     Arena* A;
@@ -332,7 +338,7 @@ static int t_block(TCtx& t, const ConvLayer& L, const float* x0, const float* x1
     const int block_index = t.n_blocks++;
     bt.drop_stream = p > 0.f ? ((t.u->train->drop_call << 16) | (uint64_t)(block_index + 1)) : 0;
     Ctx c = t.conv();
-    static const bool no_fuse = std::getenv("DM_TRAIN_NO_LANDING_FUSE") != nullptr;  // A/B: landing pass, then the norm pass
+    const bool no_fuse = train_landing_fuse_off();  // A/B: landing pass, then the norm pass
     PlannedConv P;
     if (plan_conv(c, L, x1 != nullptr, H, W, 0, false, false, P)) return 1;
     const int flags = EPI_NORM | EPI_SILU | (scale ? EPI_SCALE_SHIFT : 0);
@@ -394,7 +400,7 @@ static int t_attn(TCtx& t, const AttnLayer& At, const float* x, int H, int W, At
         return run_conv(c, At.out, at.o, nullptr, H, W, at.y, EPI_RESIDUAL, nullptr, nullptr, x);
     }
     at.ctx = t.A->alloc((size_t)t.B * heads * u->dh * u->dh);
-    at.kst = linattn_keeps_kstats() ? t.A->alloc((size_t)t.B * heads * 2 * u->dh) : nullptr;
+    at.kst = t.A->alloc((size_t)t.B * heads * 2 * u->dh);  // the key statistics the backward pass starts from
     at.y0 = t.A->alloc(rows * At.dim);
     if (!t.dry() && launch_linear_attention_core(at.qkv, At.mem_kv, at.ctx, at.o, t.B, n, heads, u->dh, t.s, at.kst))
         return 1;
@@ -590,7 +596,7 @@ static int conv_wgrad(TCtx& t, const ConvLayer& L, const ConvBwd& Bw, const floa
         return launch_colsum(dy, rows, L.Cout, L.Cout, 1, cw, t.grad(bname), t.acc, t.s, t.cdefer());
     }
     // 3x3 on even image sizes: Winograd-domain weight gradient (mode 3, 16 instead of 36 products per 2x2 tile)
-    static const bool no_wino = std::getenv("DM_WGRAD_NO_WINO") != nullptr || std::getenv("DM_NO_WINOGRAD") != nullptr;
+    static const bool no_wino = env_flag("DM_WGRAD_NO_WINO") || winograd_off();
     const int mode = Bw.kind == 0 ? ((!no_wino && Ho % 2 == 0 && Wo % 2 == 0) ? 3 : 0) : (Bw.kind == 1 ? 1 : 2);
     const int T = mode == 0 ? 9 : (mode == 1 ? 1 : (mode == 2 ? 4 : 16));
     const int cin_w = mode == 2 ? L.C0 : Cin;
@@ -649,7 +655,7 @@ struct DyParts {
 };
 // input gradient of a single-input, stride-1 convolution for a consumer that can sum partial tiles itself
 static int conv_dgrad_parts(TCtx& t, const ConvLayer& L, const ConvBwd& Bw, const float* dy, int H, int W, DyParts* out) {
-    static const bool no_fuse = std::getenv("DM_TRAIN_NO_LANDING_FUSE") != nullptr;
+    const bool no_fuse = train_landing_fuse_off();
     Ctx c{t.u, t.A, t.s, t.B, nullptr, 0};
     PlannedConv P;
     const bool plain = (Bw.kind == 0 || Bw.kind == 1) && !L.up && !Bw.has1 && !no_fuse;
@@ -714,7 +720,7 @@ static int t_resnet_bwd(TCtx& t, const ResBlock& R, const ResTape& rt, const flo
     // d(x) = dgrad_c1(du1) + dgrad_res(dout), per concat half.  Where block1's input gradient leaves K-split partial tiles for a
     // landing pass anyway, res_conv's input gradient stays partial tiles too and that ONE landing sums both (what run_resnet
     // does for block2 + res_conv in the forward pass): two launches per half instead of four.
-    static const bool no_merge = std::getenv("DM_TRAIN_NO_RES_MERGE") != nullptr || std::getenv("DM_TRAIN_NO_LANDING_FUSE") != nullptr;
+    const bool no_merge = train_landing_fuse_off();
     Ctx c{t.u, t.A, t.s, t.B, nullptr, 0};
     auto half = [&](const ConvLayer& Lc, const ConvLayer& Lr, int C, float** dx, bool* done) -> int {
         *done = false;
@@ -832,8 +838,7 @@ static int upload_table(const std::vector<E>& host, std::vector<E>& cached, E*& 
 
 static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, const float* dout_nchw, int B, int H, int W,
                                     hipStream_t s, Tape& tp, int accumulate, std::vector<WgradJob>* jobs,
-                                    std::vector<WgradDesc>* wbatch, bool defer_reductions,
-                                    const std::function<int(int)>& phase_done = nullptr) {
+                                    std::vector<WgradDesc>* wbatch, const std::function<int(int)>& phase_done) {
     const dm_unet_cfg& cfg = u->cfg;
     const int td = u->time_dim, n_st = cfg.n_stages;
     TCtx t{u, &A, s, B, A.dry ? reinterpret_cast<const float*>(16) : tp.ss, u->ss_total};
@@ -843,10 +848,8 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     t.phase_done = phase_done;
     std::vector<RowgradJob> rjobs;
     std::vector<ColsumJob> cjobs;
-    if (defer_reductions) {
-        t.rjobs = &rjobs;
-        t.cjobs = &cjobs;
-    }
+    t.rjobs = &rjobs;
+    t.cjobs = &cjobs;
     float* dss = A.alloc((size_t)B * u->ss_total);
     // final_conv (NCHW gradient, 64 -> out_dim)
     int h = H, w = W;
@@ -854,7 +857,7 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     {
         const ConvLayer& L = u->final_conv;
         DM_REQUIRE(L.wraw != nullptr, "training: final_conv must be the thin pointwise layer (out_dim <= 4)");
-        static const bool no_fuse = std::getenv("DM_TRAIN_NO_FINAL_FUSE") != nullptr;
+        static const bool no_fuse = env_flag("DM_TRAIN_NO_FINAL_FUSE");
         if (!no_fuse && thin_out_bwd_ok(L.Cout, h * w)) {  // dw, db and dx in one pass over the block's output
             float* ws = A.alloc(thin_out_bwd_ws_floats(B, h, w, L.Cout, L.C0));
             if (!A.dry) {
@@ -1034,8 +1037,6 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
 // write 38 MB of partial sums -- followed by ONE launch that sums the remaining split-K partial tiles of every layer.
 static int unet_train_backward(dm_unet* u, Arena& A, const float* x_nchw, const float* dout_nchw, int B, int H, int W,
                                hipStream_t s, Tape& tp, int accumulate) {
-    static const bool no_defer = std::getenv("DM_WGRAD_NO_DEFER") != nullptr;  // A/B: one reduce launch per layer
-    static const bool no_group = no_defer || std::getenv("DM_WGRAD_NO_GROUP") != nullptr;  // A/B: one launch per layer
     std::vector<WgradJob> jobs;
     std::vector<WgradDesc> batch[4];
     TrainState& T = *u->train;
@@ -1046,7 +1047,7 @@ static int unet_train_backward(dm_unet* u, Arena& A, const float* x_nchw, const 
         const int fi = n_flush++;
         if ((int)T.flush.size() <= fi) T.flush.resize(fi + 1);
         TrainState::FlushTables& F = T.flush[fi];
-        for (int mode = 0; mode < 4 && !no_group; ++mode) {
+        for (int mode = 0; mode < 4; ++mode) {
             if (batch[mode].empty()) continue;
             std::vector<int> splits;
             std::vector<size_t> wsf;
@@ -1077,7 +1078,7 @@ static int unet_train_backward(dm_unet* u, Arena& A, const float* x_nchw, const 
         return 0;
     };
     std::function<int(int)> phase_done;
-    if (T.bucketed && !no_defer && !no_group)
+    if (T.bucketed)
         phase_done = [&](int phase) -> int {  // data-parallel bucketing: a bucket's last phase has just been left
             for (TrainState::Bucket& bk : T.buckets) {
                 if (bk.last_phase != phase || &bk == &T.buckets.back()) continue;
@@ -1086,9 +1087,7 @@ static int unet_train_backward(dm_unet* u, Arena& A, const float* x_nchw, const 
             }
             return 0;
         };
-    if (unet_train_backward_impl(u, A, x_nchw, dout_nchw, B, H, W, s, tp, accumulate, no_defer ? nullptr : &jobs,
-                                 no_group ? nullptr : batch, !no_defer, phase_done))
-        return 1;
+    if (unet_train_backward_impl(u, A, x_nchw, dout_nchw, B, H, W, s, tp, accumulate, &jobs, batch, phase_done)) return 1;
     if (flush()) return 1;
     if (!A.dry && T.bucketed && !T.buckets.empty()) DM_CHECK_HIP(hipEventRecord(T.buckets.back().ready, s));
     return 0;
@@ -1214,7 +1213,7 @@ static bool pack_jobs_of(TrainState& T, const PackOp& op, float* tmp, size_t* tm
     if (it == T.off.end()) return false;
     const float* w = T.param + it->second;
     *tmp_floats = 0;
-    static const bool rot_tmp = std::getenv("DM_REPACK_ROT_TMP") != nullptr;  // A/B: materialise the rotated weights first
+    static const bool rot_tmp = env_flag("DM_REPACK_ROT_TMP");  // A/B: materialise the rotated weights first
     int rs = 0, rc = 0;
     if (op.src.kind == 1 && !rot_tmp &&
         (((kind == PJ_WINO || kind == PJ_WINO4 || kind == PJ_UPWINO) && op.src.sK == 3) ||
@@ -1245,7 +1244,7 @@ static bool pack_jobs_of(TrainState& T, const PackOp& op, float* tmp, size_t* tm
 
 // rebuild every used buffer of a known layout in two grouped launches
 static int batched_repack(dm_unet* u, hipStream_t s) {
-    static const bool off = std::getenv("DM_NO_BATCH_REPACK") != nullptr;  // A/B: everything on the lazy path
+    static const bool off = env_flag("DM_NO_BATCH_REPACK");  // A/B: everything on the lazy path
     TrainState& T = *u->train;
     if (off) return 0;
     if (T.jobs_version != T.used_version) {
@@ -1579,11 +1578,7 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a) {
             Arena dry;
             dry.dry = true;
             Tape tp;
-            const auto t0 = std::chrono::steady_clock::now();
             if (run(dry, tp)) return 1;
-            if (std::getenv("DM_TRAIN_TIME_DRY"))  // the host logic of one call without its launches
-                fprintf(stderr, "dm_unet_loss_backward: dry run (host logic, no launches) %.3f ms\n",
-                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
             known = T.ws_need.emplace(key, dry.off).first;
         }
         if (ensure_train_ws(T, known->second)) return 1;

@@ -21,7 +21,7 @@ static constexpr int I7_WR = 22, I7_WS = 24;  // window rows, padded row stride 
 static constexpr int I7_TS = 68;              // row stride of the epilogue staging tile
 
 bool init7_eligible(int Cout, int C0, int C1, int KH, int KW, int stride, int pad, bool up) {
-    static const bool off = std::getenv("DM_NO_INIT7") != nullptr;
+    static const bool off = env_flag("DM_NO_INIT7");
     return !off && KH == 7 && KW == 7 && stride == 1 && pad == 3 && !up && C1 == 0 && C0 >= 1 && C0 <= 8 && Cout == 64;
 }
 

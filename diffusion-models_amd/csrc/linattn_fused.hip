@@ -40,7 +40,7 @@ static constexpr int LA_TOK2 = 64;                    // tokens per workgroup, k
 __host__ __device__ static inline int la_row_of(int e, int half) { return (e & 3) + 8 * (e >> 2) + 4 * half; }
 
 bool linattn_fused_eligible(int C, int heads, int dh) {
-    static const bool off = std::getenv("DM_NO_FUSED_LINATTN") != nullptr;
+    static const bool off = env_flag("DM_NO_FUSED_LINATTN");
     return !off && heads == LA_HEADS && dh == LA_DH && (C == 64 || C == 128);
 }
 

@@ -30,9 +30,14 @@ static constexpr int PWTS = 68;  // row stride (floats) of the epilogue staging 
 static constexpr int PWD = 3;    // chunks in flight per wave
 
 
+// DM_NO_PW: neither pointwise form
+static bool pw_off() {
+    static const bool off = env_flag("DM_NO_PW");
+    return off;
+}
+
 bool pw_eligible(int Cout, int C0, int C1, int KH, int KW, int stride, int pad, bool up) {
-    static const bool off = std::getenv("DM_NO_PW") != nullptr;
-    return !off && KH == 1 && KW == 1 && stride == 1 && pad == 0 && !up && C0 > 0 && C0 % PWCK == 0 && C1 % PWCK == 0 &&
+    return !pw_off() && KH == 1 && KW == 1 && stride == 1 && pad == 0 && !up && C0 > 0 && C0 % PWCK == 0 && C1 % PWCK == 0 &&
            Cout % 64 == 0;
 }
 
@@ -59,9 +64,8 @@ void pw_pack_weights_s2d(const float* oihw, float* packed, int Cout, int C0) {
 }
 
 bool pw_s2d_eligible(int Cout, int C0, int C1, int KH, int KW, int stride, int pad, bool up) {
-    static const bool off = std::getenv("DM_NO_PW") != nullptr;
     const int cps = C0 / PWCK;
-    return !off && KH == 2 && KW == 2 && stride == 2 && pad == 0 && !up && C1 == 0 && C0 > 0 && C0 % PWCK == 0 &&
+    return !pw_off() && KH == 2 && KW == 2 && stride == 2 && pad == 0 && !up && C1 == 0 && C0 > 0 && C0 % PWCK == 0 &&
            (cps & (cps - 1)) == 0 && Cout % 64 == 0;
 }
 
@@ -293,8 +297,8 @@ int pw_launch(const ConvParams& pin, hipStream_t s) {
                "pointwise: K split does not cover the chunks");
     DM_REQUIRE(g.lds_bytes >= 4 * 32 * PWTS * 4, "pointwise: LDS size");
     const int blocks = g.n_tiles_n * g.tiles_x;
-    static const bool xcd_order = env_int("DM_NO_XCD_ORDER", 0) == 0;
-    p.geo.xcd_groups = (xcd_order && blocks % 8 == 0 && 8 % g.n_tiles_n == 0) ? 8 / g.n_tiles_n : 0;
+    // XCD-aware block order (conv_device.h: block_to_tile)
+    p.geo.xcd_groups = (blocks % 8 == 0 && 8 % g.n_tiles_n == 0) ? 8 / g.n_tiles_n : 0;
     const bool timed = prof::enabled();
     if (timed) {
         const double pix = (double)M, cin = p.s2d ? 4.0 * p.C0 : p.C0 + p.C1;

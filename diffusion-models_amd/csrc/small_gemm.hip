@@ -72,6 +72,11 @@ __global__ __launch_bounds__(256) void rows_gemm_nt_kernel(const float* __restri
         if (r < R) y[(size_t)r * ldy + o] = sum[e] + bv;
     }
 }
+bool small_gemm_off() {
+    static const bool off = env_flag("DM_NO_SMALL_GEMM");
+    return off;
+}
+
 bool rows_gemm_nt_ok(int R, int I, int O, int ldx) { return R >= 16 && I % 16 == 0 && O % 16 == 0 && ldx % 4 == 0; }
 int launch_rows_gemm_nt(const float* x, int ldx, const float* W, const float* bias, float* y, int ldy, int R, int I, int O,
                         hipStream_t s) {

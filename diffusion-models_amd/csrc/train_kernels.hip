@@ -824,8 +824,7 @@ __global__ void linear_wgrad_kernel(const float* __restrict__ dy, int ldy, const
 }
 int launch_linear_wgrad(const float* dy, int ldy, const float* x, int ldx, float* dw, int R, int I, int O, int act_in,
                         int accumulate, hipStream_t s) {
-    static const bool no_mfma = std::getenv("DM_NO_SMALL_GEMM") != nullptr;
-    if (!no_mfma && act_in == 0 && rows_gemm_tn_ok(R, I, O, ldy, ldx))
+    if (!small_gemm_off() && act_in == 0 && rows_gemm_tn_ok(R, I, O, ldy, ldx))
         return launch_rows_gemm_tn(dy, ldy, x, ldx, nullptr, nullptr, dw, I, nullptr, R, I, O, accumulate, s);
     hipLaunchKernelGGL(linear_wgrad_kernel, dim3((I + 63) / 64, O), dim3(64), 0, s, dy, ldy, x, ldx, dw, R, I, O, act_in,
                        accumulate);
@@ -882,8 +881,7 @@ __global__ __launch_bounds__(64) void mlp_rows_wgrad_kernel(const float* __restr
 }
 int launch_mlp_rows_wgrad(const float* dy, int ldy, const float* x, int ldx, float* const* dw_rows, float* const* db_rows,
                           int R, int I, int O, int accumulate, hipStream_t s, const float* x_act) {
-    static const bool no_mfma = std::getenv("DM_NO_SMALL_GEMM") != nullptr;
-    if (!no_mfma && x_act && rows_gemm_tn_ok(R, I, O, ldy, ldx))  // x_act = SiLU(x), formed once by the forward pass
+    if (!small_gemm_off() && x_act && rows_gemm_tn_ok(R, I, O, ldy, ldx))  // x_act = SiLU(x), formed once by the forward pass
         return launch_rows_gemm_tn(dy, ldy, x_act, ldx, dw_rows, db_rows, nullptr, 0, nullptr, R, I, O, accumulate, s);
     hipLaunchKernelGGL(mlp_rows_wgrad_kernel, dim3((I + 63) / 64, (O + MLP_ROWS - 1) / MLP_ROWS), dim3(64), 0, s, dy, ldy, x, ldx,
                        dw_rows, db_rows, R, I, O, accumulate);
@@ -949,8 +947,7 @@ size_t linear_dgrad_ws_floats(int R, int I, int O) {
 // ws: linear_dgrad_ws_floats(R, I, O) floats (may be nullptr when that is 0, or to force the one-pass form)
 int launch_linear_dgrad(const float* dy, int ldy, const float* W, float* dx, int ldx, int R, int I, int O, float* ws,
                         hipStream_t s) {
-    static const bool no_mfma = std::getenv("DM_NO_SMALL_GEMM") != nullptr;  // A/B: the VALU kernels below
-    if (!no_mfma && rows_gemm_nn_ok(R, I, O, ldy, ldx)) {  // batch rows as an MFMA GEMM (small_gemm.hip)
+    if (!small_gemm_off() && rows_gemm_nn_ok(R, I, O, ldy, ldx)) {  // batch rows as an MFMA GEMM (small_gemm.hip)
         const int nsh = rows_gemm_nn_shares(O);
         if (nsh == 1) return launch_rows_gemm_nn(dy, ldy, W, dx, ldx, R, I, O, s);
         if (ws && ldx == I) {

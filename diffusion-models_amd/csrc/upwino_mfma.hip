@@ -49,7 +49,7 @@ struct UWGeo {
 
 
 bool upwino_eligible(int Cout, int C0, int C1, int KH, int KW, int stride, int pad, bool up) {
-    static const bool off = std::getenv("DM_NO_UPWINO") != nullptr || std::getenv("DM_NO_WINOGRAD") != nullptr;
+    static const bool off = env_flag("DM_NO_UPWINO") || winograd_off();
     return !off && up && KH == 3 && KW == 3 && stride == 1 && pad == 1 && C0 > 0 && C0 % UWCK == 0 && C1 == 0 &&
            Cout % 64 == 0;
 }
@@ -409,8 +409,8 @@ int upwino_launch(const ConvParams& pin, hipStream_t s) {
     DM_REQUIRE(g.splits * g.chunks_per_split >= p.n_chunks && (g.splits - 1) * g.chunks_per_split < p.n_chunks,
                "upwino: K split does not cover the chunks");
     const int blocks = g.n_tiles_n * g.tiles_x * g.tiles_y * g.groups;
-    static const bool xcd_order = env_int("DM_NO_XCD_ORDER", 0) == 0;
-    p.geo.xcd_groups = (xcd_order && blocks % 8 == 0 && 8 % g.n_tiles_n == 0) ? 8 / g.n_tiles_n : 0;
+    // XCD-aware block order (conv_device.h: block_to_tile)
+    p.geo.xcd_groups = (blocks % 8 == 0 && 8 % g.n_tiles_n == 0) ? 8 / g.n_tiles_n : 0;
     const bool timed = prof::enabled();
     if (timed) {
         // priced as the reference's op: 2*9*Cin*Cout FLOP per OUTPUT pixel; the kernel executes 9/36 of

@@ -982,7 +982,7 @@ int launch_wgrad_naive(const float* x, int x_nchw, const float* dy, int dy_nchw,
     (void)wgrad_naive_ws_floats(B, H, Cout, Cin, KH, KW, &splits);
     p.rows_per_split = (B * H + splits - 1) / splits;
     const int n_out = Cout * Cin * KH * KW;
-    static const bool no_init_mfma = std::getenv("DM_WGRAD_INIT_VALU") != nullptr;
+    static const bool no_init_mfma = env_flag("DM_WGRAD_INIT_VALU");
     const int ntw = (x_nchw && !dy_nchw && KW == 7 && KH == 7 && pad == 3 && !no_init_mfma) ? wgrad_init_mfma_ntw(Cin, W) : 0;
     if (ntw) {
         const int ns = W <= 32 ? 16 : 32;

@@ -65,7 +65,7 @@ __host__ __device__ constexpr int w4_nbcode(int ltw, int nb) {
 }
 
 bool wino4_eligible(int Cout, int C0, int C1, int KH, int KW, int stride, int pad, bool up) {
-    static const bool off = std::getenv("DM_NO_WINO4") != nullptr || std::getenv("DM_NO_WINOGRAD") != nullptr;
+    static const bool off = env_flag("DM_NO_WINO4") || winograd_off();
     return !off && KH == 3 && KW == 3 && stride == 1 && pad == 1 && !up && C0 > 0 && C0 % W4CK == 0 &&
            C1 % W4CK == 0 && Cout % 64 == 0;
 }
@@ -617,9 +617,8 @@ int wino4_launch(const ConvParams& pin, hipStream_t s) {
     DM_REQUIRE(g.lds_bytes <= 160 * 1024, "winograd4: tile does not fit LDS");
     DM_REQUIRE(p.chunks0 == p.C0 / W4CK && p.n_chunks == (p.C0 + p.C1) / W4CK, "winograd4: chunk counts");
     const int blocks = g.n_tiles_n * g.tiles_x * g.tiles_y * g.groups;
-    // XCD-aware block order (conv_device.h: block_to_tile); DM_NO_XCD_ORDER=1 keeps the raw order for A/B runs
-    static const bool xcd_order = env_int("DM_NO_XCD_ORDER", 0) == 0;
-    p.geo.xcd_groups = (xcd_order && blocks % 8 == 0 && 8 % g.n_tiles_n == 0) ? 8 / g.n_tiles_n : 0;
+    // XCD-aware block order (conv_device.h: block_to_tile)
+    p.geo.xcd_groups = (blocks % 8 == 0 && 8 % g.n_tiles_n == 0) ? 8 / g.n_tiles_n : 0;
     const bool timed = prof::enabled();
     if (timed) {
         // priced as the reference's op: 2*9*Cin*Cout*pixels FLOP; the kernel executes 36/144 of the

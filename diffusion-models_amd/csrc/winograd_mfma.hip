@@ -8,18 +8,18 @@
 // For each of the 16 positions xi = (i, j) of the transformed patch the reduction over cin is an independent GEMM
 //     M[xi][tile][cout] = sum_c V[xi][tile][c] * U[xi][cout][c],   V = B^T d B,   U = G g G^T (host, once)
 //
-// Mapping (one workgroup = 4 waves = 64 Winograd tiles (128..256 output pixels) x 64 couts; one workgroup per CU):
-//   wave i owns row i of the transformed patch: xi = (i, 0..3).  Its accumulators are 4 xi x (64 tiles x 64
-//   couts = 2x2 MFMA tiles) = 256 registers.  Nothing but the raw input window is shared between waves:
+// Mapping (one workgroup = 4 waves = 32 Winograd tiles (64..128 output pixels) x 32 Q couts, Q = 2 or 1; two workgroups
+//   per CU): wave i owns row i of the transformed patch: xi = (i, 0..3).  Its accumulators are 4 xi x (32 tiles x 32 Q
+//   couts = Q MFMA tiles) = 64 Q registers.  Nothing but the raw input window is shared between waves:
 //   * B operand: U[xi][cout][c] is packed on the host as [chunk of 8 cin][xi][cout][8], so lane (cout = lane&31,
 //     half = lane>>5) loads its 4 channels of a chunk as ONE 16-byte global load straight into the MFMA operand
 //     registers (a wave reads 1 KiB contiguous).  Weights never touch LDS.
 //   * A operand: the raw input window of the tile (NB images x (2TH+2) x (2TW+2) pixels x 8 channels) is staged in
-//     LDS (double buffered, one barrier per chunk).  Lane (tile = lane&31 [+32], half) reads the two patch rows
+//     LDS (double buffered, one barrier per chunk).  Lane (tile = lane&31, half) reads the two patch rows
 //     that row i of B^T combines (8 ds_read_b128 per tile), forms T = d[ra] +- d[rb] and V[i][0..3] from it -- and
 //     those 4 values ARE its MFMA A operands for the chunk.  The transformed input never touches LDS either.
 //   * All of that (global loads of the next weights / next-but-one window, LDS reads and the ~64 VALU ops of the
-//     next chunk's transform) is issued from hooks between the 64 MFMAs of the current chunk.
+//     next chunk's transform) is issued from hooks between the 16 Q MFMAs of the current chunk.
 //   Epilogue: each wave reduces its 4 columns with A (R_i[b], 2 values), the four R_i go through LDS in the
 //   row layout of conv_mfma.hip, Y[a][b] = sum_i A^T[a][i] R_i[b], then the shared Block epilogue
 //   (bias / RMSNorm / scale-shift / SiLU / residual, or raw K-split partial sums).
@@ -50,9 +50,12 @@ static inline int w_ilog2(int v) {
     while ((1 << l) < v) ++l;
     return l;
 }
+bool winograd_off() {
+    static const bool off = env_flag("DM_NO_WINOGRAD");
+    return off;
+}
 bool wino_eligible(int Cout, int C0, int C1, int KH, int KW, int stride, int pad, bool up) {
-    static const bool off = std::getenv("DM_NO_WINOGRAD") != nullptr;
-    return !off && KH == 3 && KW == 3 && stride == 1 && pad == 1 && !up && C0 > 0 && C0 % WCK == 0 &&
+    return !winograd_off() && KH == 3 && KW == 3 && stride == 1 && pad == 1 && !up && C0 > 0 && C0 % WCK == 0 &&
            C1 % WCK == 0 && Cout % 64 == 0;
 }
 
@@ -77,12 +80,10 @@ void wino_pack_weights(const float* oihw, float* packed, int Cout, int C0, int C
 }
 
 ConvGeom wino_plan(int B, int Ho, int Wo, int Cout, int C0, int C1, bool allow_split, bool want_norm) {
-    // R = Winograd tiles per lane: 2 -> 64 tiles per workgroup, 256 accumulator registers, one workgroup per CU;
-    //                              1 -> 32 tiles per workgroup, 128 accumulator registers, two workgroups per CU
-    static const int R = env_int("DM_WINO_R", 1) == 2 ? 2 : 1;
-    const int tiles = 32 * R;
+    // 32 Winograd tiles per workgroup (one per lane and 32-lane half), two workgroups per CU
+    const int tiles = 32;
     ConvGeom g{};
-    g.WM = R;
+    g.WM = 1;
     g.WN = 1;
     g.CK = WCK;
     const int twi = (Wo + 1) / 2, thi = (Ho + 1) / 2;  // tiles per image
@@ -108,7 +109,7 @@ ConvGeom wino_plan(int B, int Ho, int Wo, int Cout, int C0, int C1, bool allow_s
     if (allow_split) {
         static const int target = env_int("DM_WINO_TARGET_WGS", 256);
         static const int min_chunks = env_int("DM_WINO_MIN_CHUNKS", 8);
-        while (wgs * splits < target * (3 - R) && splits < 8 && n_chunks / (splits * 2) >= min_chunks) splits *= 2;
+        while (wgs * splits < target * 2 && splits < 8 && n_chunks / (splits * 2) >= min_chunks) splits *= 2;
     }
     g.chunks_per_split = (n_chunks + splits - 1) / splits;
     g.splits = (n_chunks + g.chunks_per_split - 1) / g.chunks_per_split;
@@ -120,7 +121,7 @@ ConvGeom wino_plan(int B, int Ho, int Wo, int Cout, int C0, int C1, bool allow_s
     static const int q_target = env_int("DM_WINO_Q_TARGET_WGS", 512);
     // (want_norm = false: the caller has no norm to fuse -- the training step's convolutions, whose norms are separate passes
     // over the tape -- so a single 64-cout tile is no reason to keep it)
-    if (R == 1 && !(g.fused_norm && want_norm) && wgs * g.splits < q_target) {
+    if (!(g.fused_norm && want_norm) && wgs * g.splits < q_target) {
         g.NQ = 1;
         g.n_tiles_n = Cout / 32;
         g.fused_norm = 0;
@@ -137,15 +138,15 @@ bool wino_shape_ok(int B, int Ho, int Wo, int Cout, int C0, int C1) {
     if ((Ho | Wo) & 1) return false;
     const ConvGeom g = wino_plan(B, Ho, Wo, Cout, C0, C1, true);
     // the window of one tile block must fit the staging registers (very small images pack too many per block)
-    return g.NB * g.IH * g.IW * 2 <= 256 * (g.WM == 2 ? 5 : 3) && g.lds_bytes <= 160 * 1024 &&
+    return g.NB * g.IH * g.IW * 2 <= 256 * 3 && g.lds_bytes <= 160 * 1024 &&
            (size_t)B * Ho * Wo < (1u << 24) && (size_t)B * Ho * Wo * std::max(C0, C1) < (1ull << 30);
 }
 
-template <int R, int Q>
-__global__ __launch_bounds__(256, 3 - R) void wino_mfma_kernel(const ConvParams p) {
-    constexpr int TILES = 32 * R;         // Winograd tiles per workgroup
+template <int Q>
+__global__ __launch_bounds__(256, 2) void wino_mfma_kernel(const ConvParams p) {
+    constexpr int TILES = 32;             // Winograd tiles per workgroup
     constexpr int NC = 32 * Q;            // couts per workgroup
-    constexpr int HR = R == 2 ? 5 : 3;    // window staging registers (16 B each) per thread
+    constexpr int HR = 3;                 // window staging registers (16 B each) per thread
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const ConvGeom& g = p.geo;
     const int tid = threadIdx.x;
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(256, 3 - R) void wino_mfma_kernel(const ConvParams 
     }
     {
         // output pixel of (tile, a, b), or -1: thread = tile * 4 + (2a + b)
-        constexpr int NRT = 8 * R;
+        constexpr int NRT = 8;
         int* ptab = reinterpret_cast<int*>(smem + g.ptab_off);
         if (tid < 4 * TILES) {
             const int t = tid >> 2, ab = tid & 3;
@@ -233,14 +234,12 @@ __global__ __launch_bounds__(256, 3 - R) void wino_mfma_kernel(const ConvParams 
     };
     auto store_window = [&](float* raw, int i) { *reinterpret_cast<f32x4*>(raw + hoff[i]) = hreg[i]; };
 
-    // ---- input transform of this lane: tiles l31 (and 32 + l31), channel quad lh, row `wave` of B^T d
-    int rbase[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int t = 32 * r + l31;
-        const int ty = (t >> g.lTW) & (g.TH - 1);
-        const int nb = t >> (g.lTW + g.lTH);
-        rbase[r] = (nb * g.IH + 2 * ty) * RS;
+    // ---- input transform of this lane: tile l31, channel quad lh, row `wave` of B^T d
+    int rbase;
+    {
+        const int ty = (l31 >> g.lTW) & (g.TH - 1);
+        const int nb = l31 >> (g.lTW + g.lTH);
+        rbase = (nb * g.IH + 2 * ty) * RS;
     }
     // B^T row i = d[ra] + sgn * d[rb]:  i=0: d0 - d2;  i=1: d1 + d2;  i=2: d2 - d1;  i=3: d1 - d3
     const int ra = wave == 0 ? 0 : (wave == 2 ? 2 : 1);
@@ -253,28 +252,26 @@ __global__ __launch_bounds__(256, 3 - R) void wino_mfma_kernel(const ConvParams 
 #pragma unroll
         for (int b = 0; b < 4; ++b) colq[b] = (2 * tx + b) * WCK + 4 * (lh ^ (((2 * tx + b) >> 3) & 1));
     }
-    auto rd = [&](const float* raw, int r, int ab, int b) {  // patch row ra (ab = 0) or rb (1), column b, of tile r
-        return *reinterpret_cast<const f32x4*>(raw + rbase[r] + (ab ? offb : offa) + colq[b]);
+    auto rd = [&](const float* raw, int ab, int b) {  // patch row ra (ab = 0) or rb (1), column b
+        return *reinterpret_cast<const f32x4*>(raw + rbase + (ab ? offb : offa) + colq[b]);
     };
     // the same addresses precomputed per LDS buffer: in the main loop (which is unrolled over the two buffers) every
     // LDS access is then a register base + an immediate offset
-    const float* rdp[2][R][2][4];  // [buffer][tile r][row a / row b][column]
+    const float* rdp[2][2][4];     // [buffer][row a / row b][column]
     float* stp[2][HR];             // [buffer][window item]
 #pragma unroll
     for (int bf = 0; bf < 2; ++bf) {
         float* base = bf ? raw1 : raw0;
 #pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                rdp[bf][r][0][b] = base + rbase[r] + offa + colq[b];
-                rdp[bf][r][1][b] = base + rbase[r] + offb + colq[b];
-            }
+        for (int b = 0; b < 4; ++b) {
+            rdp[bf][0][b] = base + rbase + offa + colq[b];
+            rdp[bf][1][b] = base + rbase + offb + colq[b];
+        }
 #pragma unroll
         for (int i = 0; i < HR; ++i) stp[bf][i] = base + hoff[i];
     }
 
-    f32x4 A[4][R];  // V[wave][j] of tile r: channels 4*lh .. 4*lh+3 of the chunk
+    f32x4 A[4];     // V[wave][j]: channels 4*lh .. 4*lh+3 of the chunk
     f32x4 U[4][Q];  // U[wave*4 + j][cout 32*q + l31][channels 4*lh ..]
     const size_t u_chunk = (size_t)16 * p.Cout * WCK;
     const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w, (size_t)p.n_chunks * u_chunk * 4);
@@ -287,7 +284,7 @@ __global__ __launch_bounds__(256, 3 - R) void wino_mfma_kernel(const ConvParams 
         if constexpr (Q == 2) U[j][1] = bufload4(rs_w, uvo, so + 32 * WCK * 4);
     };
 
-    f32x16 acc[4][R][Q];  // first written by the first chunk's MFMAs (C = 0)
+    f32x16 acc[4][Q];  // first written by the first chunk's MFMAs (C = 0)
 
     DM_STAMP_ADD(4)
     // ---- prologue: chunks cb and cb + 1 -> LDS (both loads in flight together), operands of chunk cb -> registers
@@ -312,15 +309,14 @@ __global__ __launch_bounds__(256, 3 - R) void wino_mfma_kernel(const ConvParams 
     }
     DM_STAMP_ADD(5)
     __syncthreads();
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
+    {
         f32x4 T[4];
 #pragma unroll
-        for (int b = 0; b < 4; ++b) T[b] = rd(raw0, r, 0, b) + sgn * rd(raw0, r, 1, b);
-        A[0][r] = sub4(T[0], T[2]);
-        A[1][r] = add4(T[1], T[2]);
-        A[2][r] = sub4(T[2], T[1]);
-        A[3][r] = sub4(T[1], T[3]);
+        for (int b = 0; b < 4; ++b) T[b] = rd(raw0, 0, b) + sgn * rd(raw0, 1, b);
+        A[0] = sub4(T[0], T[2]);
+        A[1] = add4(T[1], T[2]);
+        A[2] = sub4(T[2], T[1]);
+        A[3] = sub4(T[1], T[3]);
     }
     __syncthreads();  // raw0 is overwritten with chunk cb + 2 by the first iteration
     DM_STAMP_ADD(0)
@@ -347,88 +343,47 @@ __global__ __launch_bounds__(256, 3 - R) void wino_mfma_kernel(const ConvParams 
             window_offsets(p.C1);
             asm volatile("" ::: "memory");  // keep this a branch: if-converted it costs a select per offset and chunk
         }
-        auto rdn = [&](int r, int ab, int b) { return *reinterpret_cast<const f32x4*>(rdp[BN][r][ab][b]); };
-        f32x4 T[R][4];
-        if constexpr (R == 2) {
-            static_assert(R == 1 || Q == 2, "the 64-tile form keeps 64 couts");
-            f32x4 d[8];
+        auto rdn = [&](int ab, int b) { return *reinterpret_cast<const f32x4*>(rdp[BN][ab][b]); };
+        f32x4 T[4];
+        f32x4 d[4];
+        // the hooks of the 32-MFMA stream (Q == 2: one per MFMA slot; Q == 1: two per slot of its 16 MFMAs -- "the MFMAs
+        // of j are issued" holds at the same hook index either way, MFMA (j, s, q) sitting at index ((4 j + s) 2 + q 2 / Q))
+        auto hook = [&](int m) {
+            if (m < HR) hreg[m] = window_value(cw, m);
+            if (m >= 3 && m < 7) d[m - 3] = rdn((m - 3) & 1, (m - 3) >> 1);  // columns 0, 1
+            if (m == 8) load_u(unext, 0);  // j = 0 done at m = 7
+            if (m == 11) T[0] = fma4(d[1], sgn2, d[0]);
+            if (m == 12) T[1] = fma4(d[3], sgn2, d[2]);
+            if (m >= 13 && m < 17) d[m - 13] = rdn((m - 13) & 1, 2 + ((m - 13) >> 1));  // columns 2, 3
+            if (m == 17) load_u(unext, 1);  // j = 1 done at m = 15
+            if (m == 21) T[2] = fma4(d[1], sgn2, d[0]);
+            if (m == 22) {
+                T[3] = fma4(d[3], sgn2, d[2]);
+                A[0] = sub4(T[0], T[2]);
+            }
+            if (m == 23) A[1] = add4(T[1], T[2]);
+            if (m == 24) load_u(unext, 2);  // j = 2 done at m = 23
+            if (m == 25) A[2] = sub4(T[2], T[1]);
+            if (m >= 27 && m < 27 + HR) *reinterpret_cast<f32x4*>(stp[BS][m - 27]) = hreg[m - 27];
+        };
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int s = 0; s < 4; ++s)
+            for (int s = 0; s < 4; ++s)
 #pragma unroll
-                    for (int r = 0; r < 2; ++r)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) {
-                            const int m = ((j * 4 + s) * 2 + r) * 2 + q;  // 0..63
-                            acc[j][r][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(
-                                A[j][r][s], U[j][q][s], (FIRST && s == 0) ? zero16 : acc[j][r][q], 0, 0, 0);
-                            if (m < HR) hreg[m] = window_value(cw, m);
-                            if (m >= 6 && m < 14) d[m - 6] = rdn(0, (m - 6) >> 2, (m - 6) & 3);
-                            if (m >= 14 && m < 18) T[0][m - 14] = fma4(d[4 + m - 14], sgn2, d[m - 14]);
-                            if (m == 16) load_u(unext, 0);  // the MFMAs of j = 0 were issued by m = 15
-                            if (m >= 18 && m < 26) d[m - 18] = rdn(1, (m - 18) >> 2, (m - 18) & 3);
-                            if (m >= 26 && m < 30) T[1][m - 26] = fma4(d[4 + m - 26], sgn2, d[m - 26]);
-                            if (m == 30) {
-                                A[0][0] = sub4(T[0][0], T[0][2]);
-                                A[0][1] = sub4(T[1][0], T[1][2]);
-                            }
-                            if (m == 32) {  // j = 1 done at m = 31
-                                A[1][0] = add4(T[0][1], T[0][2]);
-                                A[1][1] = add4(T[1][1], T[1][2]);
-                            }
-                            if (m == 33) load_u(unext, 1);
-                            if (m == 48) {  // j = 2 done at m = 47
-                                A[2][0] = sub4(T[0][2], T[0][1]);
-                                A[2][1] = sub4(T[1][2], T[1][1]);
-                            }
-                            if (m == 49) load_u(unext, 2);
-                            if (m >= 56 && m < 56 + HR) *reinterpret_cast<f32x4*>(stp[BS][m - 56]) = hreg[m - 56];
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-            A[3][0] = sub4(T[0][1], T[0][3]);
-            A[3][1] = sub4(T[1][1], T[1][3]);
-        } else {
-            f32x4 d[4];
-            // the hooks of the 32-MFMA stream (Q == 2: one per MFMA slot; Q == 1: two per slot of its 16 MFMAs -- "the MFMAs
-            // of j are issued" holds at the same hook index either way, MFMA (j, s, q) sitting at index ((4 j + s) 2 + q 2 / Q))
-            auto hook = [&](int m) {
-                if (m < HR) hreg[m] = window_value(cw, m);
-                if (m >= 3 && m < 7) d[m - 3] = rdn(0, (m - 3) & 1, (m - 3) >> 1);  // columns 0, 1
-                if (m == 8) load_u(unext, 0);  // j = 0 done at m = 7
-                if (m == 11) T[0][0] = fma4(d[1], sgn2, d[0]);
-                if (m == 12) T[0][1] = fma4(d[3], sgn2, d[2]);
-                if (m >= 13 && m < 17) d[m - 13] = rdn(0, (m - 13) & 1, 2 + ((m - 13) >> 1));  // columns 2, 3
-                if (m == 17) load_u(unext, 1);  // j = 1 done at m = 15
-                if (m == 21) T[0][2] = fma4(d[1], sgn2, d[0]);
-                if (m == 22) {
-                    T[0][3] = fma4(d[3], sgn2, d[2]);
-                    A[0][0] = sub4(T[0][0], T[0][2]);
-                }
-                if (m == 23) A[1][0] = add4(T[0][1], T[0][2]);
-                if (m == 24) load_u(unext, 2);  // j = 2 done at m = 23
-                if (m == 25) A[2][0] = sub4(T[0][2], T[0][1]);
-                if (m >= 27 && m < 27 + HR) *reinterpret_cast<f32x4*>(stp[BS][m - 27]) = hreg[m - 27];
-            };
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) {
-                        const int m = (j * 4 + s) * Q + q;  // 0 .. 16 Q - 1
-                        acc[j][0][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(
-                            A[j][0][s], U[j][q][s], (FIRST && s == 0) ? zero16 : acc[j][0][q], 0, 0, 0);
-                        if constexpr (Q == 2) {
-                            hook(m);
-                        } else {
-                            hook(2 * m);
-                            hook(2 * m + 1);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
+                for (int q = 0; q < Q; ++q) {
+                    const int m = (j * 4 + s) * Q + q;  // 0 .. 16 Q - 1
+                    acc[j][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(
+                        A[j][s], U[j][q][s], (FIRST && s == 0) ? zero16 : acc[j][q], 0, 0, 0);
+                    if constexpr (Q == 2) {
+                        hook(m);
+                    } else {
+                        hook(2 * m);
+                        hook(2 * m + 1);
                     }
-            A[3][0] = sub4(T[0][1], T[0][3]);
-        }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+        A[3] = sub4(T[1], T[3]);
         load_u(unext, 3);
         __syncthreads();
     };
@@ -448,7 +403,7 @@ __global__ __launch_bounds__(256, 3 - R) void wino_mfma_kernel(const ConvParams 
     // ---- epilogue: R_i[b] = sum_j M[i][j] A[j][b] per wave, then Y[a][b] = sum_i A^T[a][i] R_i[b] through LDS.
     // Wave w finishes tiles [NR*w, NR*w + NR): lane group rsub = 2a + b owns pixel (a, b) of each tile.  What
     // the epilogue needs from global memory is requested first.
-    constexpr int NR = 8 * R;
+    constexpr int NR = 8;
     const int rsub = lane >> 4;
     const int oa = rsub >> 1, ob = rsub & 1;
     const int c4 = (lane & 15) * 4;
@@ -482,22 +437,20 @@ __global__ __launch_bounds__(256, 3 - R) void wino_mfma_kernel(const ConvParams 
 
     float* Tb = smem + wave * (2 * TILES * WTS);  // [b][tile][WTS]
 #pragma unroll
-    for (int r = 0; r < R; ++r)
+    for (int q = 0; q < Q; ++q) {
 #pragma unroll
-        for (int q = 0; q < Q; ++q) {
-#pragma unroll
-            for (int e = 0; e < 16; e += 2) {  // two accumulator registers per packed instruction
-                const f32x2 a0 = {acc[0][r][q][e], acc[0][r][q][e + 1]}, a1 = {acc[1][r][q][e], acc[1][r][q][e + 1]};
-                const f32x2 a2 = {acc[2][r][q][e], acc[2][r][q][e + 1]}, a3 = {acc[3][r][q][e], acc[3][r][q][e + 1]};
-                const f32x2 r0 = pk_add(pk_add(a0, a1), a2);
-                const f32x2 r1 = pk_sub(pk_sub(a1, a2), a3);
-                const int row = r * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-                Tb[row * WTS + q * 32 + l31] = r0.x;
-                Tb[(row + 1) * WTS + q * 32 + l31] = r0.y;
-                Tb[(TILES + row) * WTS + q * 32 + l31] = r1.x;
-                Tb[(TILES + row + 1) * WTS + q * 32 + l31] = r1.y;
-            }
+        for (int e = 0; e < 16; e += 2) {  // two accumulator registers per packed instruction
+            const f32x2 a0 = {acc[0][q][e], acc[0][q][e + 1]}, a1 = {acc[1][q][e], acc[1][q][e + 1]};
+            const f32x2 a2 = {acc[2][q][e], acc[2][q][e + 1]}, a3 = {acc[3][q][e], acc[3][q][e + 1]};
+            const f32x2 r0 = pk_add(pk_add(a0, a1), a2);
+            const f32x2 r1 = pk_sub(pk_sub(a1, a2), a3);
+            const int row = (e & 3) + 8 * (e >> 2) + 4 * lh;
+            Tb[row * WTS + q * 32 + l31] = r0.x;
+            Tb[(row + 1) * WTS + q * 32 + l31] = r0.y;
+            Tb[(TILES + row) * WTS + q * 32 + l31] = r1.x;
+            Tb[(TILES + row + 1) * WTS + q * 32 + l31] = r1.y;
         }
+    }
     __syncthreads();
     DM_STAMP_ADD(2)
     const float ysgn = oa ? -1.0f : 1.0f;  // Y[0] = R0 + R1 + R2,  Y[1] = R1 - R2 - R3
@@ -516,10 +469,10 @@ __global__ __launch_bounds__(256, 3 - R) void wino_mfma_kernel(const ConvParams 
     DM_STAMP_FLUSH
 }
 
-template <int R, int Q>
-static int wino_launch_r(const ConvParams& p, int blocks, hipStream_t s) {
+template <int Q>
+static int wino_launch_q(const ConvParams& p, int blocks, hipStream_t s) {
     static LdsOptIn lds_flag;
-    if (lds_opt_in(lds_flag, reinterpret_cast<const void*>(wino_mfma_kernel<R, Q>), 1)) return 1;
+    if (lds_opt_in(lds_flag, reinterpret_cast<const void*>(wino_mfma_kernel<Q>), 1)) return 1;
 #ifdef DM_STAMPS
     // diagnostic build: run the launch synchronously with a stamp buffer and print the phase averages
     {
@@ -529,7 +482,7 @@ static int wino_launch_r(const ConvParams& p, int blocks, hipStream_t s) {
         DM_CHECK_HIP(hipMemsetAsync(dbuf, 0, nblk * 8 * sizeof(unsigned long long), s));
         ConvParams ps = p;
         ps.stamps = dbuf;
-        hipLaunchKernelGGL((wino_mfma_kernel<R, Q>), dim3(blocks, p.geo.splits, 1), dim3(256), p.geo.lds_bytes, s, ps);
+        hipLaunchKernelGGL((wino_mfma_kernel<Q>), dim3(blocks, p.geo.splits, 1), dim3(256), p.geo.lds_bytes, s, ps);
         DM_CHECK_HIP(hipStreamSynchronize(s));
         std::vector<unsigned long long> h(nblk * 8);
         DM_CHECK_HIP(hipMemcpy(h.data(), dbuf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
@@ -539,12 +492,12 @@ static int wino_launch_r(const ConvParams& p, int blocks, hipStream_t s) {
             for (int k = 0; k < 8; ++k) avg[k] += (double)h[b * 8 + k] / nblk;
         fprintf(stderr, "STAMPS wino<%d> %d+%d->%d @%dx%d e%d k%d chunks %d: wgs=%zu | setup %.0f load+store %.0f "
                         "transform %.0f loop %.0f (%.0f/chunk) reduce %.0f epilogue %.0f\n",
-                R, p.C0, p.C1, p.Cout, p.Ho, p.Wo, p.epi, p.geo.splits, p.geo.chunks_per_split, nblk, avg[4], avg[5],
+                Q, p.C0, p.C1, p.Cout, p.Ho, p.Wo, p.epi, p.geo.splits, p.geo.chunks_per_split, nblk, avg[4], avg[5],
                 avg[0], avg[1], avg[1] / p.geo.chunks_per_split, avg[2], avg[3]);
         return 0;
     }
 #endif
-    hipLaunchKernelGGL((wino_mfma_kernel<R, Q>), dim3(blocks, p.geo.splits, 1), dim3(256), p.geo.lds_bytes, s, p);
+    hipLaunchKernelGGL((wino_mfma_kernel<Q>), dim3(blocks, p.geo.splits, 1), dim3(256), p.geo.lds_bytes, s, p);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -557,11 +510,9 @@ int wino_launch(const ConvParams& pin, hipStream_t s) {
     DM_REQUIRE(!p.in_nchw && !p.out_nchw, "winograd: NHWC only");
     DM_REQUIRE(p.C0 % WCK == 0 && p.C1 % WCK == 0 && p.Cout % 64 == 0, "winograd: channel counts");
     DM_REQUIRE(p.Hin == p.Ho && p.Win == p.Wo, "winograd: same-size convolution");
-    const int R = g.WM;
-    DM_REQUIRE(R == 1 || R == 2, "winograd: tiles per lane");
-    DM_REQUIRE((g.NQ == 2 || (g.NQ == 1 && R == 1)) && g.n_tiles_n == p.Cout / (32 * g.NQ), "winograd: cout tile");
-    DM_REQUIRE(g.TW * g.TH * g.NB == 32 * R, "winograd: 32 R tiles per workgroup");
-    DM_REQUIRE(g.NB * g.IH * g.IW * 2 <= 256 * (R == 2 ? 5 : 3), "winograd: window exceeds staging registers");
+    DM_REQUIRE((g.NQ == 1 || g.NQ == 2) && g.n_tiles_n == p.Cout / (32 * g.NQ), "winograd: cout tile");
+    DM_REQUIRE(g.TW * g.TH * g.NB == 32, "winograd: 32 tiles per workgroup");
+    DM_REQUIRE(g.NB * g.IH * g.IW * 2 <= 256 * 3, "winograd: window exceeds staging registers");
     DM_REQUIRE((size_t)p.B * p.Ho * p.Wo < (1u << 24) && p.C0 < (1 << 24) && p.C1 < (1 << 24) &&
                    (size_t)p.B * p.Ho * p.Wo * std::max(p.C0, p.C1) < (1ull << 30),
                "winograd: tensor too large for 24-bit pixel indices");
@@ -570,9 +521,8 @@ int wino_launch(const ConvParams& pin, hipStream_t s) {
     DM_REQUIRE(g.lds_bytes <= 160 * 1024, "winograd: tile does not fit LDS");
     DM_REQUIRE(p.chunks0 == p.C0 / WCK && p.n_chunks == (p.C0 + p.C1) / WCK, "winograd: chunk counts");
     const int blocks = g.n_tiles_n * g.tiles_x * g.tiles_y * g.groups;
-    // XCD-aware block order (conv_device.h: block_to_tile); DM_NO_XCD_ORDER=1 keeps the raw order for A/B runs
-    static const bool xcd_order = env_int("DM_NO_XCD_ORDER", 0) == 0;
-    p.geo.xcd_groups = (xcd_order && blocks % 8 == 0 && 8 % g.n_tiles_n == 0) ? 8 / g.n_tiles_n : 0;
+    // XCD-aware block order (conv_device.h: block_to_tile)
+    p.geo.xcd_groups = (blocks % 8 == 0 && 8 % g.n_tiles_n == 0) ? 8 / g.n_tiles_n : 0;
     const bool timed = prof::enabled();
     if (timed) {
         // priced as the reference's op: 2*9*Cin*Cout*pixels FLOP; the kernel executes 16/36 of
@@ -584,14 +534,13 @@ int wino_launch(const ConvParams& pin, hipStream_t s) {
         const double bytes = 4.0 * (cin * pix + (1.0 + res_rows) * p.Cout * pix + 9.0 * cin * p.Cout);
         char name[64];
         if (prof::detail())
-            snprintf(name, sizeof(name), "wino<%d> 3x3 s1 %d+%d->%d @%dx%d e%d k%d g%d q%d", R, p.C0, p.C1, p.Cout, p.Ho,
-                     p.Wo, p.epi, g.splits, blocks * g.splits, g.NQ);
+            snprintf(name, sizeof(name), "wino 3x3 s1 %d+%d->%d @%dx%d e%d k%d g%d q%d", p.C0, p.C1, p.Cout, p.Ho, p.Wo,
+                     p.epi, g.splits, blocks * g.splits, g.NQ);
         else
-            snprintf(name, sizeof(name), "wino_mfma_kernel<%d, %d>", R, g.NQ);  // the symbol rocprofv3 reports
+            snprintf(name, sizeof(name), "wino_mfma_kernel<%d>", g.NQ);  // the symbol rocprofv3 reports
         if (prof::begin(name, flops, bytes, s)) return 1;
     }
-    if (R == 2 ? wino_launch_r<2, 2>(p, blocks, s) : (g.NQ == 1 ? wino_launch_r<1, 1>(p, blocks, s) : wino_launch_r<1, 2>(p, blocks, s)))
-        return 1;
+    if (g.NQ == 1 ? wino_launch_q<1>(p, blocks, s) : wino_launch_q<2>(p, blocks, s)) return 1;
     if (timed && prof::end(s)) return 1;
     return 0;
 }

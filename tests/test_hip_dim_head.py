@@ -275,10 +275,8 @@ def test_refusals():
 
 SWITCH_SETS = [
     dict(DM_NO_FUSED_LINATTN="1", DM_NO_ATTN16="1", DM_ATTN_TILED="1"),
-    dict(DM_LINATTN_VALU="1", DM_LINATTN_BWD_VALU="1"),
-    dict(DM_LINATTN_NO_KSTATS="1", DM_ATTN_BWD_TILED="1"),
+    dict(DM_ATTN_BWD_TILED="1"),
     dict(DM_ATTN_BWD_NO_CACHE="1"),
-    dict(DM_ATTN_BWD_NO_PAIRS="1"),
 ]
 
 
