@@ -14,20 +14,20 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DM_LIB") or os.path.join(_HERE, "libdm_hip.so")
 DM_MAX_STAGES = 8
 DM_COEFS = 8
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # every symbol include/dm_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
     "dm_last_error", "dm_abi_version",
     "dm_unet_create", "dm_unet_destroy", "dm_unet_set_param", "dm_unet_missing_params", "dm_unet_get_param_host", "dm_unet_finalize",
     "dm_unet_update_param", "dm_unet_refresh", "dm_unet_graph_captures", "dm_unet_workspace_bytes",
-    "dm_unet_forward", "dm_sample", "dm_sample_cond", "dm_sample_ex", "dm_randn",
+    "dm_unet_forward", "dm_unet_forward_masked", "dm_sample", "dm_sample_cond", "dm_sample_ex", "dm_randn",
     "dm_decoder_create", "dm_decoder_destroy", "dm_decoder_set_param", "dm_decoder_missing_params",
     "dm_decoder_finalize", "dm_decoder_forward",
     "dm_encoder_create", "dm_encoder_destroy", "dm_encoder_set_param", "dm_encoder_missing_params",
     "dm_encoder_finalize", "dm_encoder_forward",
     "dm_op_conv2d", "dm_op_downsample", "dm_op_rmsnorm", "dm_op_block", "dm_op_linear_attention",
-    "dm_op_attention", "dm_op_sampler_update",
+    "dm_op_attention", "dm_op_sampler_update", "dm_op_cfg_combine",
     "dm_conv_create", "dm_conv_destroy", "dm_conv_forward", "dm_op_pool2d", "dm_op_resize_bilinear",
     "dm_op_copy_channels_nhwc", "dm_op_global_avgpool", "dm_op_linear",
     "dm_unet_train_enable", "dm_unet_grad_floats", "dm_unet_grads_flat", "dm_unet_train_buckets", "dm_unet_train_bucket", "dm_unet_get_grad", "dm_unet_loss_backward", "dm_unet_loss_backward_ex", "dm_op_q_sample", "dm_op_linear_bwd",
@@ -79,6 +79,8 @@ class SampleArgs(C.Structure):
         ("out", C.c_void_p), ("all_steps", C.c_void_p),
         ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("unnormalize", C.c_int32), ("use_graph", C.c_int32),
         ("reserved_", C.c_int32), ("stream", C.c_void_p),
+        ("cfg", C.c_int32), ("cfg_scale", C.c_float), ("cfg_rescaled_phi", C.c_float),
+        ("cfg_keep_parallel_frac", C.c_float), ("cfg_remove_parallel", C.c_int32), ("cfg_reserved_", C.c_int32),
     ]
 
 
@@ -106,6 +108,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_unet_finalize.argtypes = [vp]
     lib.dm_unet_get_param_host.argtypes = [vp, C.c_char_p, vp, i64]
     lib.dm_unet_forward.argtypes = [vp, fp, vp, fp, i32, fp, i32, i32, i32, vp]
+    lib.dm_unet_forward_masked.argtypes = [vp, fp, vp, fp, i32, vp, fp, i32, i32, i32, vp]
     lib.dm_unet_update_param.argtypes = [vp, C.c_char_p, fp, C.POINTER(i64), i32]
     lib.dm_unet_refresh.argtypes = [vp]
     lib.dm_unet_graph_captures.argtypes = [vp]
@@ -138,6 +141,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_linear_attention.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
     lib.dm_op_attention.argtypes = [fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
     lib.dm_op_sampler_update.argtypes = [i32, i32, fp, fp, fp, C.POINTER(C.c_float), fp, fp, i64, vp]
+    lib.dm_op_cfg_combine.argtypes = [fp, fp, fp, i32, i64, C.c_float, C.c_float, i32, C.c_float, vp]
     lib.dm_conv_create.argtypes = [fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
     lib.dm_conv_destroy.argtypes = [vp]
     lib.dm_conv_destroy.restype = None

@@ -314,11 +314,11 @@ struct dm_unet {
     std::vector<std::pair<std::string, ResBlock*>> resnets;  // in ss_off order
     // the instantiated graph of one denoise step, reused while the key (shape, kind, every captured pointer) holds
     struct GraphKey {
-        int kind = -1, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0;
+        int kind = -1, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
         const void *noise = nullptr, *all_steps = nullptr, *ws = nullptr, *times = nullptr, *coefs = nullptr;
         bool operator==(const GraphKey& o) const {
             return kind == o.kind && B == o.B && H == o.H && W == o.W && ctx_tokens == o.ctx_tokens &&
-                   cond_channels == o.cond_channels && objective == o.objective && self_cond == o.self_cond && noise == o.noise && all_steps == o.all_steps && ws == o.ws &&
+                   cond_channels == o.cond_channels && objective == o.objective && self_cond == o.self_cond && guided == o.guided && noise == o.noise && all_steps == o.all_steps && ws == o.ws &&
                    times == o.times && coefs == o.coefs;
         }
     } gkey;
@@ -1104,7 +1104,13 @@ static bool cross1_off() {
 
 // CrossAttention.forward (DD/denoising_diffusion_text_conditional.py:54-78); the result REPLACES x (:173-177)
 static int run_cross(Ctx& c, const CrossLayer& Cr, const float* x, int H, int W, const float* ctx, int m,
-                     float** out) {
+                     float** out, const int32_t* tmask = nullptr) {
+    // tmask (classifier-free guidance's batched forward): the layers are skipped for images with tmask == 0
+    // (DD/denoising_diffusion_text_conditional.py:173,183,194 when text_emb is None), so those rows keep x
+    auto keep_null_rows = [&](float* y) -> int {
+        if (!tmask || c.dry()) return 0;
+        return launch_select_rows(y, x, (int64_t)H * W * Cr.out.Cout, tmask, c.B, (int64_t)H * W * Cr.out.Cout, c.s);
+    };
     dm_unet* u = c.u;
     const int n = H * W, inner = 4 * u->dh, dim = Cr.out.Cout, E = u->cfg.text_emb_dim;
     const size_t rows = (size_t)c.B * n;
@@ -1124,6 +1130,7 @@ static int run_cross(Ctx& c, const CrossLayer& Cr, const float* x, int H, int W,
                 return 1;
             if (launch_broadcast_rows(zb, y, (int)rows, dim, dim, c.s, n)) return 1;
         }
+        if (keep_null_rows(y)) return 1;
         c.A->release(v);
         c.A->release(yb);
         c.A->release(zb);
@@ -1144,6 +1151,7 @@ static int run_cross(Ctx& c, const CrossLayer& Cr, const float* x, int H, int W,
             return 1;
     }
     if (run_conv(c, Cr.out, o, nullptr, H, W, y, EPI_NORM, Cr.g, nullptr, nullptr)) return 1;
+    if (keep_null_rows(y)) return 1;
     c.A->release(q);
     c.A->release(k);
     c.A->release(v);
@@ -1155,15 +1163,20 @@ static int run_cross(Ctx& c, const CrossLayer& Cr, const float* x, int H, int W,
 // Unet.forward (DD/denoising_diffusion.py:349-390; text hooks DD/denoising_diffusion_text_conditional.py:131-214)
 static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const int64_t* t_dev,
                              const int64_t* step_times, const SamplerState* step_dev, const float* ctx, int ctx_tokens,
-                             float* out_nchw, int B, int H, int W, hipStream_t s) {
+                             float* out_nchw, int B, int H, int W, hipStream_t s, const int32_t* tmask = nullptr) {
+    // tmask: per-image text mask (device int32, B entries, or nullptr = every image as `ctx` says).  Image b is
+    // conditioned iff tmask[b] != 0; the others take the model's null path (text_emb = None).  Every row of ctx is
+    // read, the masked-out ones included, and their values do not reach the output.
     const dm_unet_cfg& cfg = u->cfg;
+    DM_REQUIRE(!tmask || (ctx && cfg.text_mode != DM_TEXT_NONE), "a text mask needs a text-conditional U-Net and a context");
     Ctx c{u, &A, s, B, nullptr, 0};
     const int td = u->time_dim;
     const bool text_concat = cfg.text_mode == DM_TEXT_CONCAT && ctx != nullptr;
     const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && ctx != nullptr;
     // one context token: the three CrossAttention layers ignore their image input (run_cross), which makes everything
     // between the last skip connection and cross_attn_up dead code (DM_NO_CROSS1 computes it anyway)
-    const bool dead_bottleneck = text_cross && ctx_tokens == 1 && !cross1_off();
+    // (not with a text mask: the null rows need the bottleneck)
+    const bool dead_bottleneck = text_cross && ctx_tokens == 1 && !cross1_off() && !tmask;
     // the time embedding is one row when the whole batch shares t (samplers), else one row per sample
     const int Bt = (step_times && !text_concat) ? 1 : B;
     const int Rt = step_times ? 1 : B;  // rows of the sinusoid / time_mlp
@@ -1198,6 +1211,8 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
                 return 1;
             if (launch_linear_rows(tf0, td, u->tp_w2, u->tp_b2, cat + td, 2 * td, B, td, td, 0, 0, s)) return 1;
             if (launch_linear_rows(cat, 2 * td, u->tc_w, u->tc_b, t2, td, B, 2 * td, td, 0, 0, s)) return 1;
+            // null rows: the raw time embedding (:146-152 skipped when text_emb is None)
+            if (tmask && launch_select_rows(t2, temb, Rt == 1 ? 0 : td, tmask, B, td, s)) return 1;
         }
         tfinal = t2;
     }
@@ -1252,12 +1267,12 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
         if (run_cross(c, u->cross_up, nullptr, h, w, ctx, ctx_tokens, &t0)) return 1;
         cur = t0;
     } else {
-        if (text_cross) { if (run_cross(c, u->cross_down, cur, h, w, ctx, ctx_tokens, &t0)) return 1; rel(cur); cur = t0; }
+        if (text_cross) { if (run_cross(c, u->cross_down, cur, h, w, ctx, ctx_tokens, &t0, tmask)) return 1; rel(cur); cur = t0; }
         if (run_resnet(c, u->mid1, cur, nullptr, h, w, &t0)) return 1; rel(cur); cur = t0;
-        if (text_cross) { if (run_cross(c, u->cross_mid, cur, h, w, ctx, ctx_tokens, &t0)) return 1; rel(cur); cur = t0; }
+        if (text_cross) { if (run_cross(c, u->cross_mid, cur, h, w, ctx, ctx_tokens, &t0, tmask)) return 1; rel(cur); cur = t0; }
         if (run_attn(c, u->mid_attn, cur, h, w, &t0)) return 1; rel(cur); cur = t0;
         if (run_resnet(c, u->mid2, cur, nullptr, h, w, &t0)) return 1; rel(cur); cur = t0;
-        if (text_cross) { if (run_cross(c, u->cross_up, cur, h, w, ctx, ctx_tokens, &t0)) return 1; rel(cur); cur = t0; }
+        if (text_cross) { if (run_cross(c, u->cross_up, cur, h, w, ctx, ctx_tokens, &t0, tmask)) return 1; rel(cur); cur = t0; }
     }
     for (int j = 0; j < n_st; ++j) {
         Stage& S = u->ups[j];
@@ -1323,7 +1338,7 @@ static int check_hw(dm_unet* u, int H, int W) {
 extern "C" {
 
 const char* dm_last_error(void) { return g_err.c_str(); }
-int dm_abi_version(void) { return 5; }
+int dm_abi_version(void) { return 6; }
 
 int dm_unet_create(const dm_unet_cfg* cfg, int device, dm_unet** out) {
     DM_REQUIRE(cfg && out, "null argument");
@@ -1564,6 +1579,30 @@ int dm_unet_forward(dm_unet* u, const float* x, const int64_t* time, const float
     return u->mark_done(s);
 }
 
+int dm_unet_forward_masked(dm_unet* u, const float* x, const int64_t* time, const float* ctx, int ctx_tokens,
+                           const int32_t* text_mask, float* out, int B, int H, int W, void* stream) {
+    DM_REQUIRE(u && x && time && ctx && text_mask && out, "null argument");
+    DM_REQUIRE(u->cfg.text_mode != DM_TEXT_NONE, "dm_unet_forward_masked needs a text-conditional U-Net");
+    DM_REQUIRE(u->finalized, "dm_unet_finalize has not been called");
+    DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
+    DM_REQUIRE(!u->infer_stale, "parameters were updated on the device (dm_unet_optimizer_step): call dm_unet_train_sync "
+                                "before sampling from this handle");
+    DM_REQUIRE(B > 0 && ctx_tokens > 0, "empty batch or context");
+    if (check_hw(u, H, W)) return 1;
+    DM_CHECK_HIP(hipSetDevice(u->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Arena dry;
+    dry.dry = true;
+    if (unet_forward_impl(u, dry, x, time, nullptr, nullptr, ctx, ctx_tokens, out, B, H, W, s, text_mask)) return 1;
+    if (ensure_workspace(u, dry.off)) return 1;
+    Arena A;
+    A.base = u->ws;
+    A.cap = u->ws_cap;
+    if (u->order_after_previous(s)) return 1;
+    if (unet_forward_impl(u, A, x, time, nullptr, nullptr, ctx, ctx_tokens, out, B, H, W, s, text_mask)) return 1;
+    return u->mark_done(s);
+}
+
 }  // extern "C"
 
 // The sampling loop behind dm_sample / dm_sample_cond.  cond (B, cond_channels, H, W) is the image condition of
@@ -1579,7 +1618,7 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
                        const float* x_T, const float* noise, uint64_t seed, uint64_t sample_offset, const float* ctx,
                        int ctx_tokens, const float* cond, int cond_channels, float* out, float* all_steps, int B, int H,
                        int W, int unnormalize, int use_graph, void* stream, int objective = DM_OBJ_PRED_NOISE,
-                       int self_cond = 0) {
+                       int self_cond = 0, const CfgParams* guide = nullptr) {
     DM_REQUIRE(u && times_host && coefs_host && x_T && out, "null argument");
     DM_REQUIRE(u->finalized, "dm_unet_finalize has not been called");
     DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
@@ -1594,6 +1633,16 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
     DM_REQUIRE(u->cfg.input_channels == u->cfg.channels * (self_cond ? 2 : 1) + cond_channels,
                "U-Net input channels != channels [* 2 with self-conditioning] + cond_channels");
     DM_REQUIRE((ctx == nullptr) == (ctx_tokens == 0), "ctx and ctx_tokens come together");
+    // classifier-free guidance: every step runs the U-Net on [x | x] with the text mask [1.. | 0..] (B conditioned and
+    // B null images in one forward) and combines the two halves into the model output the update reads
+    const bool guided = guide != nullptr;
+    if (guided) {
+        DM_REQUIRE(u->cfg.text_mode != DM_TEXT_NONE, "classifier-free guidance (cfg_scale != 1) needs a text-conditional U-Net");
+        DM_REQUIRE(ctx != nullptr, "classifier-free guidance needs a text context");
+        DM_REQUIRE(!self_cond, "classifier-free guidance is not combined with self-conditioning");
+        DM_REQUIRE(cond == nullptr, "classifier-free guidance is not combined with an image condition");
+    }
+    const int Bf = guided ? 2 * B : B;  // batch of the U-Net forward
     if (check_hw(u, H, W)) return 1;
     DM_CHECK_HIP(hipSetDevice(u->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1628,16 +1677,25 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
         DM_CHECK_HIP(hipStreamSynchronize(nullptr));
         s = u->cap_stream;
     }
-    // workspace: [x | eps | [x | cond] | ctx | forward arena]
+    // workspace: [x | eps | [x | cond] | ctx | forward arena]; guided: [x | x copy | eps | 2B model output | ctx | ctx copy |
+    // text mask | guidance parameters | forward arena]
+    const int64_t n_ws = guided ? 2 * n : n;
     Arena dry;
     dry.dry = true;
+    dry.alloc(n_ws);
     dry.alloc(n);
-    dry.alloc(n);
+    if (guided) dry.alloc(2 * n);
     if (wide) dry.alloc(n_in);
     if (self_cond) dry.alloc(n);
-    if (ctx) dry.alloc(n_ctx);
+    if (ctx) dry.alloc(guided ? 2 * n_ctx : n_ctx);
+    if (guided) {
+        dry.alloc(2 * B);
+        dry.alloc(4);
+    }
     const float* ctx_marker = ctx ? reinterpret_cast<const float*>(16) : nullptr;
-    if (unet_forward_impl(u, dry, nullptr, nullptr, u->times_dev, u->state_dev, ctx_marker, ctx_tokens, nullptr, B, H, W, s))
+    const int32_t* mask_marker = guided ? reinterpret_cast<const int32_t*>(16) : nullptr;
+    if (unet_forward_impl(u, dry, nullptr, nullptr, u->times_dev, u->state_dev, ctx_marker, ctx_tokens, nullptr, Bf, H, W, s,
+                          mask_marker))
         return 1;
     if (ensure_workspace(u, dry.off)) return 1;
 
@@ -1652,19 +1710,33 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
     DM_CHECK_HIP(hipMemcpyAsync(u->coefs_dev, coefs_host, (size_t)n_steps * DM_COEFS * sizeof(float),
                                 hipMemcpyHostToDevice, s));
     DM_CHECK_HIP(hipMemcpyAsync(u->state_dev, &st_host, sizeof(st_host), hipMemcpyHostToDevice, s));
-    DM_CHECK_HIP(hipStreamSynchronize(s));  // the host tables and st_host may go away when this function returns
 
     Arena A;
     A.base = u->ws;
     A.cap = u->ws_cap;
-    float* xbuf = A.alloc(n);
+    float* xbuf = A.alloc(n_ws);  // guided: [x | x], the U-Net input of both halves
     float* eps = A.alloc(n);
+    float* eps2 = guided ? A.alloc(2 * n) : nullptr;  // model output of the conditioned and the null half
     float* xin = wide ? A.alloc(n_in) : nullptr;  // [x | cond] or [x_start | x] per image, what init_conv reads
     float* xstart = self_cond ? A.alloc(n) : nullptr;  // clamped x_0 estimate of the previous step
-    float* ctxbuf = ctx ? A.alloc(n_ctx) : nullptr;
+    float* ctxbuf = ctx ? A.alloc(guided ? 2 * n_ctx : n_ctx) : nullptr;
+    int32_t* tmask = guided ? reinterpret_cast<int32_t*>(A.alloc(2 * B)) : nullptr;
+    float* gpar = guided ? A.alloc(4) : nullptr;  // CfgParams: device data, so a captured step serves any guidance scale
+    std::vector<int32_t> tmask_host;
+    if (guided) {
+        tmask_host.assign(2 * B, 0);
+        std::fill(tmask_host.begin(), tmask_host.begin() + B, 1);
+        DM_CHECK_HIP(hipMemcpyAsync(tmask, tmask_host.data(), 2 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        DM_CHECK_HIP(hipMemcpyAsync(gpar, guide, sizeof(CfgParams), hipMemcpyHostToDevice, s));
+    }
+    DM_CHECK_HIP(hipStreamSynchronize(s));  // the host tables and st_host may go away when this function returns
     const std::vector<Arena::Blk> arena_mark = A.blks;  // allocator state in front of a denoise step
     DM_CHECK_HIP(hipMemcpyAsync(xbuf, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (ctx) DM_CHECK_HIP(hipMemcpyAsync(ctxbuf, ctx, n_ctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (guided) {  // the null half reads the same x and (unused) context rows
+        DM_CHECK_HIP(hipMemcpyAsync(xbuf + n, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        DM_CHECK_HIP(hipMemcpyAsync(ctxbuf + n_ctx, ctx, n_ctx * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
     if (cond && launch_copy_channels(cond, xin, B, cond_channels, C + cond_channels, C, H * W, s)) return 1;
     if (self_cond) DM_CHECK_HIP(hipMemsetAsync(xstart, 0, n * sizeof(float), s));  // x_self_cond = zeros_like(x) (:353)
     if (all_steps) DM_CHECK_HIP(hipMemcpyAsync(all_steps, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1675,11 +1747,18 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
         if (self_cond && (launch_copy_channels(xstart, xin, B, C, Cin, 0, H * W, st) ||
                           launch_copy_channels(xbuf, xin, B, C, Cin, C, H * W, st)))
             return 1;
-        if (unet_forward_impl(u, A, wide ? xin : xbuf, nullptr, u->times_dev, u->state_dev, ctxbuf, ctx_tokens, eps, B, H,
-                              W, st))
+        if (guided) {
+            if (unet_forward_impl(u, A, xbuf, nullptr, u->times_dev, u->state_dev, ctxbuf, ctx_tokens, eps2, Bf, H, W, st,
+                                  tmask))
+                return 1;
+            if (launch_cfg_combine(eps2, eps2 + n, eps, B, n / B, gpar, CfgParams{}, st)) return 1;
+        } else if (unet_forward_impl(u, A, wide ? xin : xbuf, nullptr, u->times_dev, u->state_dev, ctxbuf, ctx_tokens, eps,
+                                     B, H, W, st)) {
             return 1;
+        }
+        // guided: x_{t-1} goes to both halves of the next step's input
         if (launch_sampler_update(kind, xbuf, eps, noise, u->coefs_dev, u->state_dev, n, xbuf, all_steps, nullptr, n, st,
-                                  objective, xstart))
+                                  objective, xstart, guided ? xbuf + n : nullptr))
             return 1;
         return launch_step_advance(u->state_dev, st);
     };
@@ -1699,7 +1778,7 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
     }
     dm_unet::GraphKey key;
     key.kind = kind; key.B = B; key.H = H; key.W = W; key.ctx_tokens = ctx_tokens; key.cond_channels = cond_channels;
-    key.objective = objective; key.self_cond = self_cond;
+    key.objective = objective; key.self_cond = self_cond; key.guided = guided;
     key.noise = noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.coefs = u->coefs_dev;
     if (!u->gexec || !(u->gkey == key)) {
         u->drop_graph();
@@ -1749,9 +1828,11 @@ int dm_sample_cond(dm_unet* u, int kind, int n_steps, const int64_t* times_host,
 
 int dm_sample_ex(dm_unet* u, const dm_sample_args* a) {
     DM_REQUIRE(u && a, "null argument");
+    DM_REQUIRE(a->cfg_remove_parallel == 0 || a->cfg_remove_parallel == 1, "cfg_remove_parallel is 0 or 1");
+    const CfgParams g{a->cfg_scale, a->cfg_rescaled_phi, a->cfg_keep_parallel_frac, (float)a->cfg_remove_parallel};
     return sample_impl(u, a->kind, a->n_steps, a->times_host, a->coefs_host, a->x_T, a->noise, a->seed, a->sample_offset,
                        a->ctx, a->ctx_tokens, a->cond, a->cond_channels, a->out, a->all_steps, a->B, a->H, a->W,
-                       a->unnormalize, a->use_graph, a->stream, a->objective, a->self_condition);
+                       a->unnormalize, a->use_graph, a->stream, a->objective, a->self_condition, a->cfg ? &g : nullptr);
 }
 
 int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t element_offset, void* stream) {

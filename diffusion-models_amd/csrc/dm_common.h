@@ -280,13 +280,27 @@ int launch_pointwise_small(const float* x, const float* w_oc, const float* bias,
 // state_dev == nullptr: one stand-alone update (step 0 of 1, no Philox noise, no unnormalize)
 int launch_sampler_update(int kind, const float* x, const float* eps, const float* noise, const float* coefs_dev,
                           const SamplerState* state_dev, int64_t noise_step_stride, float* out, float* all_steps,
-                          float* final_out, int64_t n, hipStream_t s, int objective = 0, float* xstart_out = nullptr);
+                          float* final_out, int64_t n, hipStream_t s, int objective = 0, float* xstart_out = nullptr,
+                          float* dup_out = nullptr);
+// (dup_out: a second copy of `out`, the null half of a guided step's 2B input)
 // element e of the tensor uses Philox counter ((element_offset + e) / 4, draw); element_offset % 4 == 0
 int launch_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t element_offset, hipStream_t s);
 int launch_step_advance(SamplerState* state_dev, hipStream_t s);
 int launch_finalize(const float* x, float* out, int64_t n, int unnormalize, hipStream_t s);
 int launch_broadcast_rows(const float* src, float* dst, int rows, int n, int ld, hipStream_t s, int group = 0);
 // (group > 0: source row r / group feeds destination row r; 0: one source row for all)
+
+// Classifier-free guidance (cfg.hip).  The parameters of Unet.forward_with_cond_scale (DD/classifier_free_guidance.py:339-345);
+// remove_parallel is 0 or 1, a float so that the four sit together in one device table of the sampler.
+struct CfgParams {
+    float cond_scale, rescaled_phi, keep_parallel_frac, remove_parallel;
+};
+// out[b] = the guided output of image b from cond[b] and null_out[b], rows of `per` floats; params_dev (4 floats in the
+// order of CfgParams) overrides `p` when it is set
+int launch_cfg_combine(const float* cond, const float* null_out, float* out, int B, int64_t per, const float* params_dev,
+                       CfgParams p, hipStream_t s);
+// y[b][0..per) = x[b * x_ld ..] where mask[b] == 0 (device int32 mask; x_ld = 0: one x row for every image)
+int launch_select_rows(float* y, const float* x, int64_t x_ld, const int32_t* mask, int B, int64_t per, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
 // Attention cores (attention.hip); qkv is NHWC (B, n, 3*heads*dh) = [q | k | v] per pixel

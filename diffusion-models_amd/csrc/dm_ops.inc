@@ -278,4 +278,14 @@ int dm_op_sampler_update(int kind, int objective, const float* x, const float* e
     return rc;
 }
 
+int dm_op_cfg_combine(const float* cond, const float* null_out, float* out, int B, int64_t per_sample, float cond_scale,
+                      float rescaled_phi, int remove_parallel_component, float keep_parallel_frac, void* stream) {
+    DM_REQUIRE(cond && null_out && out, "null argument");
+    DM_REQUIRE(B > 0 && per_sample > 1, "dm_op_cfg_combine needs B > 0 and more than one value per sample");
+    DM_REQUIRE(out != cond && out != null_out, "dm_op_cfg_combine does not run in place");
+    DM_REQUIRE(remove_parallel_component == 0 || remove_parallel_component == 1, "remove_parallel_component is 0 or 1");
+    const CfgParams p{cond_scale, rescaled_phi, keep_parallel_frac, (float)remove_parallel_component};
+    return launch_cfg_combine(cond, null_out, out, B, per_sample, nullptr, p, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

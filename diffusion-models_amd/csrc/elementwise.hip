@@ -570,7 +570,7 @@ __global__ void sampler_update_kernel(int kind, int objective, const float* __re
                                       const float* __restrict__ coefs, const SamplerState* __restrict__ st,
                                       int64_t noise_step_stride, float* __restrict__ out,
                                       float* __restrict__ all_steps, float* __restrict__ final_out,
-                                      float* __restrict__ xstart_out, int64_t n) {
+                                      float* __restrict__ xstart_out, float* __restrict__ dup_out, int64_t n) {
     // everything that changes between two sample() calls of one shape is read from the device-side state, so a
     // captured step graph stays valid across calls (seed, Philox offset, step count, unnormalize)
     const int step = st ? st->step : 0;
@@ -614,6 +614,7 @@ __global__ void sampler_update_kernel(int kind, int objective, const float* __re
             r = flag ? (x0 * c2 + c3 * e2) + c4 * z[j] : x0;
         }
         out[i] = r;
+        if (dup_out) dup_out[i] = r;
         if (all_steps) all_steps[(size_t)(step + 1) * n + i] = r;
         if (final_out && step == n_steps - 1) final_out[i] = unnormalize ? (r + 1.0f) * 0.5f : r;
     }
@@ -635,10 +636,11 @@ int launch_finalize(const float* x, float* out, int64_t n, int unnormalize, hipS
 
 int launch_sampler_update(int kind, const float* x, const float* eps, const float* noise, const float* coefs_dev,
                           const SamplerState* state_dev, int64_t noise_step_stride, float* out, float* all_steps,
-                          float* final_out, int64_t n, hipStream_t s, int objective, float* xstart_out) {
+                          float* final_out, int64_t n, hipStream_t s, int objective, float* xstart_out,
+                          float* dup_out) {
     int64_t n4 = (n + 3) / 4;
     hipLaunchKernelGGL(sampler_update_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, kind, objective, x, eps, noise,
-                       coefs_dev, state_dev, noise_step_stride, out, all_steps, final_out, xstart_out, n);
+                       coefs_dev, state_dev, noise_step_stride, out, all_steps, final_out, xstart_out, dup_out, n);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -36,6 +36,7 @@ import torch
 
 from . import _lib
 from .spec import SCHEDULE_BUFFERS, ddim_step_table, ddpm_step_table, make_schedule
+from .unet import check_guidance
 
 DDPM, DDIM = 0, 1
 
@@ -181,7 +182,9 @@ class DenoisingDiffusion:
         return out
 
     def _run(self, kind, shape, times, coefs, takes_noise: Sequence[bool], return_all_timesteps, noise, seed,
-             text_emb=None, max_steps=None, cond=None, sample_offset=0, x_init=None, unnormalize=None):
+             text_emb=None, max_steps=None, cond=None, sample_offset=0, x_init=None, unnormalize=None, guidance=None):
+        """guidance: None, or (cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac) of classifier-free
+        guidance (TextConditionalDenoisingDiffusion), which the library applies to the model output of every step."""
         shape = tuple(int(v) for v in shape)
         B, Cc, H, W = shape
         assert Cc == self.channels, f"shape has {Cc} channels, the model {self.channels}"
@@ -233,6 +236,11 @@ class DenoisingDiffusion:
         a.B, a.H, a.W = B, H, W
         a.unnormalize = self._unnormalize_flag if unnormalize is None else int(bool(unnormalize))
         a.use_graph, a.stream = 1 if self.use_graph else 0, stream
+        if guidance is not None:
+            assert ctx is not None, "classifier-free guidance needs text_emb"
+            a.cfg = 1
+            a.cfg_scale, a.cfg_rescaled_phi, a.cfg_remove_parallel, a.cfg_keep_parallel_frac = (
+                float(guidance[0]), float(guidance[1]), int(bool(guidance[2])), float(guidance[3]))
         _lib.check(self._lib.dm_sample_ex(self.model._handle, C.byref(a)))
         if not return_all_timesteps:
             return out
@@ -396,21 +404,21 @@ class DenoisingDiffusion:
 
     @torch.inference_mode()
     def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, text_emb=None,
-                      sample_offset=0):
+                      sample_offset=0, _guidance=None):
         times, coefs = self._ddpm_tables()
         takes = [t > 0 for t in times]
         return self._run(DDPM, shape, times, coefs, takes, return_all_timesteps, noise, seed, text_emb, max_steps,
-                         sample_offset=sample_offset)
+                         sample_offset=sample_offset, guidance=_guidance)
 
     @torch.inference_mode()
     def ddim_sample(self, shape, sampling_timesteps=None, return_all_timesteps=False, *, noise=None, seed=None,
-                    max_steps=None, text_emb=None, sample_offset=0):
+                    max_steps=None, text_emb=None, sample_offset=0, _guidance=None):
         if sampling_timesteps is None:
             sampling_timesteps = self.sampling_timesteps
         times, coefs = self._ddim_tables(sampling_timesteps)
         takes = [bool(c[5] != 0) for c in coefs]
         return self._run(DDIM, shape, times, coefs, takes, return_all_timesteps, noise, seed, text_emb, max_steps,
-                         sample_offset=sample_offset)
+                         sample_offset=sample_offset, guidance=_guidance)
 
     @torch.inference_mode()
     def sample(self, batch_size=16, return_all_timesteps=False, **kw):
@@ -656,23 +664,36 @@ class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
                         f.write(t + "\n")
         return text_emb
 
+    # -- classifier-free guidance (classifier_free_guidance.py:339-369): the keywords of Unet.forward_with_cond_scale.
+    # cond_scale == 1 is the unguided code path; otherwise every step's model output is the guided one.
+    def _guidance(self, cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac):
+        if not check_guidance(self.model, cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac):
+            return None
+        return (float(cond_scale), float(rescaled_phi), bool(remove_parallel_component), float(keep_parallel_frac))
+
     @torch.inference_mode()
-    def p_sample_loop(self, shape, save_path_for_text=None, return_all_timesteps=False, *, text_emb=None, **kw):
+    def p_sample_loop(self, shape, save_path_for_text=None, return_all_timesteps=False, *, text_emb=None, cond_scale=1.0,
+                      rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, **kw):
+        g = self._guidance(cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
         text_emb = self._text(shape[0], save_path_for_text, text_emb)
-        return super().p_sample_loop(shape, return_all_timesteps, text_emb=text_emb, **kw)
+        return super().p_sample_loop(shape, return_all_timesteps, text_emb=text_emb, _guidance=g, **kw)
 
     @torch.inference_mode()
     def ddim_sample(self, shape, save_path_for_text=None, sampling_timesteps=None, return_all_timesteps=False, *,
-                    text_emb=None, **kw):
+                    text_emb=None, cond_scale=1.0, rescaled_phi=0.0, remove_parallel_component=True,
+                    keep_parallel_frac=0.0, **kw):
+        g = self._guidance(cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
         text_emb = self._text(shape[0], save_path_for_text, text_emb)
-        return super().ddim_sample(shape, sampling_timesteps, return_all_timesteps, text_emb=text_emb, **kw)
+        return super().ddim_sample(shape, sampling_timesteps, return_all_timesteps, text_emb=text_emb, _guidance=g, **kw)
 
     @torch.inference_mode()
-    def sample(self, batch_size=16, save_path_for_text=None, return_all_timesteps=False, **kw):
+    def sample(self, batch_size=16, save_path_for_text=None, return_all_timesteps=False, *, cond_scale=1.0,
+               rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, **kw):
         (h, w), channels = self.image_size, self.channels
         sample_fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
         return sample_fn((batch_size, channels, h, w), save_path_for_text, return_all_timesteps=return_all_timesteps,
-                         **kw)
+                         cond_scale=cond_scale, rescaled_phi=rescaled_phi,
+                         remove_parallel_component=remove_parallel_component, keep_parallel_frac=keep_parallel_frac, **kw)
 
     def p_losses(self, x_start, t, text_emb=None, noise=None, offset_noise_strength=None, **kw):
         """denoising_diffusion_text_conditional.py:476-542 (the reference's positional order: x_start, t, text_emb, noise)."""
@@ -692,22 +713,48 @@ class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
         """denoising_diffusion_text_conditional.py:456-473 (positional order: x1, x2, t, text_emb, lam)."""
         return self._interpolate(x1, x2, t, lam, noise, seed, text_emb=text_emb)
 
-    @torch.inference_mode()
-    def model_predictions(self, x, t, text_emb=None, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False):
-        """denoising_diffusion_text_conditional.py:274-297 (positional order: x, t, text_emb, x_self_cond)."""
+    def _cond_kw(self, text_emb, cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac):
         kw = {"text_emb": text_emb} if text_emb is not None else {}
+        g = self._guidance(cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
+        if g is not None:
+            if text_emb is None:
+                raise ValueError("classifier-free guidance (cond_scale != 1) needs text_emb")
+            kw["_guidance"] = g
+        return kw
+
+    def _eps(self, x, bt, _guidance=None, **cond_kw):
+        if _guidance is None:
+            return super()._eps(x, bt, **cond_kw)
+        scale, phi, remove, keep = _guidance
+        return self.model.forward_with_cond_scale(x, bt, cond_kw["text_emb"], cond_scale=scale, rescaled_phi=phi,
+                                                  remove_parallel_component=remove, keep_parallel_frac=keep)[0]
+
+    @torch.inference_mode()
+    def model_predictions(self, x, t, text_emb=None, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False, *,
+                          cond_scale=1.0, rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0):
+        """denoising_diffusion_text_conditional.py:274-297 (positional order: x, t, text_emb, x_self_cond); with
+        cond_scale != 1 the model output is the guided one of Unet.forward_with_cond_scale."""
+        kw = self._cond_kw(text_emb, cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
         return super().model_predictions(x, t, x_self_cond, clip_x_start, rederive_pred_noise, **kw)
 
     @torch.inference_mode()
-    def p_mean_variance(self, x, t, text_emb=None, x_self_cond=None, clip_denoised=True):
+    def p_mean_variance(self, x, t, text_emb=None, x_self_cond=None, clip_denoised=True, *, cond_scale=1.0,
+                        rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0):
         """:299-307."""
-        kw = {"text_emb": text_emb} if text_emb is not None else {}
-        return super().p_mean_variance(x, t, x_self_cond, clip_denoised, **kw)
+        x = x.to(self.device, torch.float32).contiguous()
+        x_start = self.model_predictions(x, t, text_emb, x_self_cond, clip_x_start=bool(clip_denoised),
+                                         cond_scale=cond_scale, rescaled_phi=rescaled_phi,
+                                         remove_parallel_component=remove_parallel_component,
+                                         keep_parallel_frac=keep_parallel_frac).pred_x_start
+        mean, var, logvar = self.q_posterior(x_start, x, t)
+        return mean, var, logvar, x_start
 
     @torch.inference_mode()
-    def p_sample(self, x, t: int, text_emb=None, x_self_cond=None, *, noise=None):
+    def p_sample(self, x, t: int, text_emb=None, x_self_cond=None, *, noise=None, cond_scale=1.0, rescaled_phi=0.0,
+                 remove_parallel_component=True, keep_parallel_frac=0.0):
         """denoising_diffusion_text_conditional.py:310-317 (the reference's positional order: x, t, text_emb)."""
-        return self._p_sample(x, t, noise, {"text_emb": text_emb} if text_emb is not None else {}, x_self_cond)
+        kw = self._cond_kw(text_emb, cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
+        return self._p_sample(x, t, noise, kw, x_self_cond)
 
 
 class ImageConditionalDenoisingDiffusion(DenoisingDiffusion):
@@ -866,11 +913,14 @@ class TextConditionalLatentDiffusion(TextConditionalDenoisingDiffusion):
     __call__ = forward
 
     @torch.inference_mode()
-    def sample(self, batch_size=16, save_path_for_text=None, return_all_timesteps=False, **kw):
+    def sample(self, batch_size=16, save_path_for_text=None, return_all_timesteps=False, *, cond_scale=1.0,
+               rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, **kw):
         (h, w), channels = self.image_size, self.channels
         sample_fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
         latents = sample_fn((batch_size, channels, h, w), save_path_for_text,
-                            return_all_timesteps=return_all_timesteps, **kw)
+                            return_all_timesteps=return_all_timesteps, cond_scale=cond_scale, rescaled_phi=rescaled_phi,
+                            remove_parallel_component=remove_parallel_component, keep_parallel_frac=keep_parallel_frac,
+                            **kw)
         return self.decode(latents)
 
 

@@ -437,3 +437,71 @@ class Unet:
         return out
 
     __call__ = forward
+
+    def forward_with_cond_scale(self, x, time, text_emb, *, cond_scale=1.0, rescaled_phi=0.0,
+                                remove_parallel_component=True, keep_parallel_frac=0.0):
+        """Classifier-free guidance (classifier_free_guidance.py:339-369) on the text-conditional U-Net: ``logits`` is the
+        output with ``text_emb``, ``null_logits`` the output with ``text_emb=None``.  Returns ``logits`` when
+        ``cond_scale == 1`` (one plain forward), else ``(guided, null_logits)``.  Both predictions come from ONE U-Net
+        forward on 2B images (dm_unet_forward_masked) and the combine runs in cfg_combine_kernel."""
+        check_guidance(self, cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
+        if cond_scale == 1:
+            return self.forward(x, time, text_emb=text_emb)
+        if text_emb is None:
+            raise ValueError("forward_with_cond_scale needs text_emb")
+        if not self._loaded:
+            raise RuntimeError("load_state_dict() must be called before forward()")
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        B, Cin, H, W = x.shape
+        f = self.downsample_factor
+        assert H % f == 0 and W % f == 0, f"your input dimensions {(H, W)} need to be divisible by {f}, given the unet"
+        if Cin != self.cfg.input_channels:
+            raise RuntimeError(f"expected {self.cfg.input_channels} input channels, got {Cin}")
+        t = time.to(device=self.device, dtype=torch.int64).reshape(-1)
+        if t.numel() == 1 and B > 1:
+            t = t.expand(B)
+        if t.numel() != B:
+            raise RuntimeError(f"time has {t.numel()} entries for a batch of {B}")
+        ctx, m = self._ctx(text_emb, B)
+        x2, t2, ctx2 = (torch.cat((v, v), dim=0).contiguous() for v in (x, t, ctx))
+        mask = torch.cat((torch.ones(B, dtype=torch.int32), torch.zeros(B, dtype=torch.int32))).to(self.device)
+        out2 = torch.empty((2 * B, self.out_dim, H, W), device=self.device, dtype=torch.float32)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        _lib.check(self._lib.dm_unet_forward_masked(self._handle, _lib.ptr(x2), _lib.ptr(t2), _lib.ptr(ctx2), m,
+                                                    _lib.ptr(mask), _lib.ptr(out2), 2 * B, H, W, stream))
+        return cfg_combine(out2[:B], out2[B:], cond_scale, rescaled_phi, remove_parallel_component,
+                           keep_parallel_frac), out2[B:]
+
+
+def check_guidance(model, cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac):
+    """The refusals of classifier-free guidance; returns True when guidance is on (cond_scale != 1)."""
+    for name, v in (("cond_scale", cond_scale), ("rescaled_phi", rescaled_phi), ("keep_parallel_frac", keep_parallel_frac)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v:
+            raise TypeError(f"{name} must be a real number, got {v!r}")
+    if not isinstance(remove_parallel_component, bool):
+        raise TypeError(f"remove_parallel_component must be a bool, got {remove_parallel_component!r}")
+    if cond_scale == 1:
+        return False
+    if not getattr(model, "text_condition", False):
+        raise ValueError("classifier-free guidance (cond_scale != 1) needs a text-conditional Unet: other models have no "
+                         "null prediction")
+    if getattr(model, "self_condition", False):
+        raise NotImplementedError("classifier-free guidance (cond_scale != 1) is not combined with self_condition=True: "
+                                  "the reference formula does not define the null half's x_self_cond")
+    return True
+
+
+def cfg_combine(cond, null, cond_scale, rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0):
+    """The guided output from the conditioned and the null prediction, per image (classifier_free_guidance.py:355-369;
+    the projection and the statistics accumulate in fp64): dm_op_cfg_combine."""
+    cond = cond.to(torch.float32).contiguous()
+    null = null.to(cond.device, torch.float32).contiguous()
+    if cond.shape != null.shape or cond.dim() < 2:
+        raise ValueError(f"cond {tuple(cond.shape)} and null {tuple(null.shape)} must be equal (B, ...) shapes")
+    out = torch.empty_like(cond)
+    stream = torch.cuda.current_stream(cond.device).cuda_stream
+    lib = _lib.load()
+    _lib.check(lib.dm_op_cfg_combine(_lib.ptr(cond), _lib.ptr(null), _lib.ptr(out), cond.shape[0], cond[0].numel(),
+                                     float(cond_scale), float(rescaled_phi), int(bool(remove_parallel_component)),
+                                     float(keep_parallel_frac), stream))
+    return out

@@ -104,6 +104,16 @@ int64_t dm_unet_workspace_bytes(dm_unet* u);
 int dm_unet_forward(dm_unet* u, const float* x, const int64_t* time, const float* ctx, int ctx_tokens,
                     float* out, int B, int H, int W, void* stream);
 
+/* The text-conditional forward with a per-image text mask: image i is conditioned on ctx row i iff text_mask[i] != 0,
+ * and takes the null path of forward(x, time, text_emb=None) otherwise (DD/denoising_diffusion_text_conditional.py:
+ * 146-152 concat, :173/:183/:194 cross).  One batch holds both kinds, so classifier-free guidance runs its conditioned
+ * and null predictions as one forward (DD/classifier_free_guidance.py:350-354).
+ *   text_mask  (B,) int32 device   ctx (B, ctx_tokens, text_emb_dim), every row initialised (the masked-out rows are
+ *              read, their values do not reach the output)
+ * Needs a handle with text_mode != DM_TEXT_NONE. */
+int dm_unet_forward_masked(dm_unet* u, const float* x, const int64_t* time, const float* ctx, int ctx_tokens,
+                           const int32_t* text_mask, float* out, int B, int H, int W, void* stream);
+
 /* ---- samplers (replace DenoisingDiffusion.p_sample_loop / ddim_sample,
  *      DD/denoising_diffusion.py:647-664 and :666-708) ------------------------------------
  *
@@ -180,6 +190,20 @@ typedef struct dm_sample_args {
     int32_t use_graph;
     int32_t reserved_;
     void* stream;
+    /* classifier-free guidance (Unet.forward_with_cond_scale, DD/classifier_free_guidance.py:339-369); cfg == 0 (the
+     * zero-initialised struct): no guidance, the other cfg_* fields are ignored.  cfg != 0: every step runs the U-Net
+     * once on 2B images, B conditioned on ctx and B null ones, and the update reads the guided output
+     *   scaled = cond + update * (cfg_scale - 1),  update = cond - null, its component parallel to cond removed (per
+     *   image, in fp64) and cfg_keep_parallel_frac of it added back when cfg_remove_parallel == 1;
+     *   rescaled_phi != 0: out = phi * scaled * std(cond) / std(scaled) + (1 - phi) * scaled (unbiased std per image).
+     * Needs a text-conditional handle and ctx; not combined with self_condition or cond.  The four values are device
+     * data of the captured step graph: a new cfg_scale reuses the graph of the same shape. */
+    int32_t cfg;
+    float cfg_scale;
+    float cfg_rescaled_phi;
+    float cfg_keep_parallel_frac;
+    int32_t cfg_remove_parallel;
+    int32_t cfg_reserved_;
 } dm_sample_args;
 int dm_sample_ex(dm_unet* u, const dm_sample_args* args);
 
@@ -272,6 +296,11 @@ int dm_op_attention(const float* x, const float* norm_g, const float* mem_kv, co
  * floats (host); x_start (optional) receives the clamped x_0 estimate of the step (pred_x_start of model_predictions) */
 int dm_op_sampler_update(int kind, int objective, const float* x, const float* eps, const float* noise,
                          const float* c_host, float* out, float* x_start, int64_t n, void* stream);
+/* The guidance combine of dm_sample_args.cfg on its own: out[b] = guided(cond[b], null_out[b]) for B rows of
+ * per_sample floats (DD/classifier_free_guidance.py:355-369 with project :49-60).  Device pointers, out distinct from
+ * both inputs. */
+int dm_op_cfg_combine(const float* cond, const float* null_out, float* out, int B, int64_t per_sample, float cond_scale,
+                      float rescaled_phi, int remove_parallel_component, float keep_parallel_frac, void* stream);
 
 /* ---- sample consumer: the InceptionV3 feature extractor behind the reference's FID and
  *      Inception-score evaluators (DD/fid_evaluation.py:41-51 -> pytorch_fid.inception.InceptionV3;
