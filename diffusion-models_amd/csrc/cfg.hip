@@ -113,6 +113,26 @@ __global__ void select_rows_kernel(float* __restrict__ y, const float* __restric
     if (mask[b] == 0) y[i] = x[b * x_ld + j];
 }
 
+// Training: the backward of that select (y = mask ? branch(x) : x), four floats per thread.  Row b of `dst` becomes row b
+// of `kept` where mask[b] != 0 and row b of `dropped` (zeros when `dropped` is null) elsewhere; rows are 4 * per4 floats long
+// and dst_ld / kept_ld / dropped_ld floats apart, all multiples of 4.
+//   split: kept = dy, dropped = null                  -> what the text branch receives: exact zeros for the rows that bypassed it
+//   merge: dst = kept = the branch's dx, dropped = dy -> the gradient of the select's input, written in place
+__global__ void route_rows_kernel(float* dst, int64_t dst_ld, const float* kept, int64_t kept_ld, const float* dropped,
+                                  int64_t dropped_ld, const int32_t* __restrict__ mask, int64_t per4, int64_t n4) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const int64_t b = i / per4, j = 4 * (i - b * per4);
+    float4 v{0.f, 0.f, 0.f, 0.f};
+    if (mask[b] != 0) {
+        if (kept == dst) return;  // in place: the row is already there
+        v = *reinterpret_cast<const float4*>(kept + b * kept_ld + j);
+    } else if (dropped) {
+        v = *reinterpret_cast<const float4*>(dropped + b * dropped_ld + j);
+    }
+    *reinterpret_cast<float4*>(dst + b * dst_ld + j) = v;
+}
+
 }  // namespace
 
 int launch_cfg_combine(const float* cond, const float* null_out, float* out, int B, int64_t per, const float* params_dev,
@@ -132,6 +152,22 @@ int launch_select_rows(float* y, const float* x, int64_t x_ld, const int32_t* ma
     if (n == 0) return 0;
     hipLaunchKernelGGL(select_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, s, y, x, x_ld, mask, per, n);
     DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_route_rows(float* dst, int64_t dst_ld, const float* kept, int64_t kept_ld, const float* dropped,
+                      int64_t dropped_ld, const int32_t* mask, int B, int64_t per, hipStream_t s) {
+    DM_REQUIRE(dst && kept && mask && B > 0 && per > 0, "route_rows: null argument");
+    DM_REQUIRE(per % 4 == 0 && dst_ld % 4 == 0 && kept_ld % 4 == 0 && dropped_ld % 4 == 0 && dst_ld >= per && kept_ld >= per &&
+                   (!dropped || dropped_ld >= per),
+               "route_rows: rows are multiples of 4 floats, at least `per` apart");
+    const int64_t n4 = (int64_t)B * (per / 4);
+    const bool timed = prof::enabled();
+    if (timed && prof::begin("route_rows_kernel", 0.0, 4.0 * 2.0 * B * per, s)) return 1;  // at most one read and one write
+    hipLaunchKernelGGL(route_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dst, dst_ld, kept, kept_ld,
+                       dropped, dropped_ld, mask, per / 4, n4);
+    DM_CHECK_HIP(hipGetLastError());
+    if (timed && prof::end(s)) return 1;
     return 0;
 }
 

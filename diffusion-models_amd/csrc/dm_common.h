@@ -301,6 +301,10 @@ int launch_cfg_combine(const float* cond, const float* null_out, float* out, int
                        CfgParams p, hipStream_t s);
 // y[b][0..per) = x[b * x_ld ..] where mask[b] == 0 (device int32 mask; x_ld = 0: one x row for every image)
 int launch_select_rows(float* y, const float* x, int64_t x_ld, const int32_t* mask, int B, int64_t per, hipStream_t s);
+// the backward of that select in training: dst[b][0..per) = mask[b] ? kept[b] : (dropped ? dropped[b] : 0); rows are
+// dst_ld / kept_ld / dropped_ld floats apart (multiples of 4, as is per); dst may be kept (those rows then stay)
+int launch_route_rows(float* dst, int64_t dst_ld, const float* kept, int64_t kept_ld, const float* dropped,
+                      int64_t dropped_ld, const int32_t* mask, int B, int64_t per, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
 // Attention cores (attention.hip); qkv is NHWC (B, n, 3*heads*dh) = [q | k | v] per pixel

@@ -107,6 +107,7 @@ struct TrainState {
     size_t ws_cap = 0;
     float* coef_dev = nullptr;  // [B][4]
     int64_t* t_dev = nullptr;
+    int32_t* mask_dev = nullptr;  // [B]: the per-image text mask of a masked call (dm_unet_loss_backward_masked)
     int cap_B = 0;
     float* loss_dev = nullptr;
     std::vector<float> coef_stage;  // the call's coefficient rows, DM_TRAIN_COEFS floats each
@@ -127,6 +128,7 @@ struct TrainState {
         if (ws) (void)hipFree(ws);
         if (coef_dev) (void)hipFree(coef_dev);
         if (t_dev) (void)hipFree(t_dev);
+        if (mask_dev) (void)hipFree(mask_dev);
         if (loss_dev) (void)hipFree(loss_dev);
     }
 };
@@ -273,6 +275,7 @@ struct Tape {
     const float* tfinal = nullptr;  // what the ResnetBlock.mlp layers see (temb, or the text-concat projection)
     const float* ctx = nullptr;
     int ctx_tokens = 0;
+    const int32_t* mask = nullptr;  // per-image caption dropout: rows with mask 0 took the text_emb = None path
     CrossTape cdown, cmid, cup;
     float* x0 = nullptr;
     std::vector<StageTape> downs, ups;
@@ -416,8 +419,10 @@ static int conv_dgrad(TCtx& t, const ConvLayer& L, const ConvBwd& Bw, const floa
                       const float* add1, float** dx0, float** dx1);
 
 // CrossAttention.forward (DD/denoising_diffusion_text_conditional.py:54-78) in tape mode, general path (m context tokens);
-// the result REPLACES x (:173-177): no residual
-static int t_cross(TCtx& t, const CrossLayer& Cr, const float* x, int H, int W, const float* ctx, int m, CrossTape& ct) {
+// the result REPLACES x (:173-177): no residual.  mask (per-image caption dropout): the layer is skipped for rows with
+// mask 0 (text_emb is None, :173/:183/:194), so those rows of the result are x -- the select of dm_unet_forward_masked
+static int t_cross(TCtx& t, const CrossLayer& Cr, const float* x, int H, int W, const float* ctx, int m, CrossTape& ct,
+                   const int32_t* mask) {
     dm_unet* u = t.u;
     const int n = H * W, inner = 4 * u->dh, dim = Cr.out.Cout, E = u->cfg.text_emb_dim;
     const size_t rows = (size_t)t.B * n;
@@ -439,15 +444,26 @@ static int t_cross(TCtx& t, const CrossLayer& Cr, const float* x, int H, int W, 
     }
     if (run_conv(c, Cr.out, ct.o, nullptr, H, W, ct.y0, 0, nullptr, nullptr, nullptr)) return 1;
     if (t.dry()) return 0;
-    return launch_norm_act(ct.y0, 1, 0, nullptr, Cr.g, nullptr, 0, n, nullptr, ct.y, (int64_t)rows, dim, EPI_NORM, t.s);
+    if (launch_norm_act(ct.y0, 1, 0, nullptr, Cr.g, nullptr, 0, n, nullptr, ct.y, (int64_t)rows, dim, EPI_NORM, t.s)) return 1;
+    return mask ? launch_select_rows(ct.y, x, (int64_t)n * dim, mask, t.B, (int64_t)n * dim, t.s) : 0;
 }
 
-static int t_cross_bwd(TCtx& t, const CrossLayer& Cr, const CrossTape& ct, const float* dy, int H, int W, const float* ctx, int m,
-                       const std::string& p, float** dx_out) {
+// mask (per-image caption dropout): rows with mask 0 kept the layer's input, so their gradient bypasses the layer -- the
+// layer receives exact zeros for them (every parameter gradient is linear in it) and *dx_out is dy for those rows
+static int t_cross_bwd(TCtx& t, const CrossLayer& Cr, const CrossTape& ct, const float* dy_in, int H, int W, const float* ctx, int m,
+                       const std::string& p, float** dx_out, const int32_t* mask) {
     dm_unet* u = t.u;
     TrainState& T = *u->train;
     const int n = H * W, inner = 4 * u->dh, dim = Cr.out.Cout, E = u->cfg.text_emb_dim;
     const size_t rows = (size_t)t.B * n;
+    const int64_t per = (int64_t)n * dim;
+    const float* dy = dy_in;
+    if (mask) {
+        DM_REQUIRE(Cr.q.C0 == dim, "CrossAttention replaces x: its input and output widths are equal");
+        float* kept = t.A->alloc(rows * dim);
+        if (!t.dry() && launch_route_rows(kept, per, dy_in, per, nullptr, 0, mask, t.B, per, t.s)) return 1;
+        dy = kept;
+    }
     float* dy0 = t.A->alloc(rows * dim);
     float* ws = t.A->alloc(norm_act_bwd_ws_floats(t.B, n, dim));
     if (!t.dry() && launch_norm_act_bwd(dy, ct.y0, Cr.g, nullptr, 0, n, dy0, ws, t.grad(p + ".to_out.1.g"),
@@ -466,18 +482,22 @@ static int t_cross_bwd(TCtx& t, const CrossLayer& Cr, const CrossTape& ct, const
         if (launch_linear_wgrad(dv, inner, ctx, E, t.grad(p + ".to_v.weight"), t.B * m, E, inner, 0, t.acc, t.s)) return 1;
     }
     if (conv_wgrad(t, Cr.q, T.conv.at(&Cr.q), ct.x, nullptr, dq, H, W, p + ".to_q.weight", "", false)) return 1;
-    return conv_dgrad(t, Cr.q, T.conv.at(&Cr.q), dq, H, W, nullptr, nullptr, dx_out, &none);
+    if (conv_dgrad(t, Cr.q, T.conv.at(&Cr.q), dq, H, W, nullptr, nullptr, dx_out, &none)) return 1;
+    if (mask && !t.dry()) return launch_route_rows(*dx_out, per, *dx_out, per, dy_in, per, mask, t.B, per, t.s);
+    return 0;
 }
 
 // Unet.forward (DD/denoising_diffusion.py:349-390) with per-sample times and everything kept for the backward pass
 static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const int64_t* t_dev, float* out_nchw, int B, int H,
-                              int W, hipStream_t s, Tape& tp, const float* ctx = nullptr, int ctx_tokens = 0) {
+                              int W, hipStream_t s, Tape& tp, const float* ctx = nullptr, int ctx_tokens = 0,
+                              const int32_t* mask = nullptr) {
     const dm_unet_cfg& cfg = u->cfg;
     const int td = u->time_dim, n_st = cfg.n_stages;
     const bool text_concat = cfg.text_mode == DM_TEXT_CONCAT && ctx != nullptr;
     const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && ctx != nullptr;
     tp.ctx = ctx;
     tp.ctx_tokens = ctx_tokens;
+    tp.mask = ctx ? mask : nullptr;
     TCtx t{u, &A, s, B, nullptr, 0};
     tp.e0 = A.alloc((size_t)B * cfg.dim);
     tp.h1pre = A.alloc((size_t)B * td);
@@ -506,6 +526,8 @@ static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const i
             if (launch_act_fwd(tp.te0pre, tp.te0, (int64_t)B * td, 2, s)) return 1;
             if (launch_linear_rows(tp.te0, td, u->tp_w2, u->tp_b2, tp.cat + td, 2 * td, B, td, td, 0, 0, s)) return 1;
             if (launch_linear_rows(tp.cat, 2 * td, u->tc_w, u->tc_b, t2, td, B, 2 * td, td, 0, 0, s)) return 1;
+            // per-image caption dropout: rows with mask 0 keep the raw time embedding (text_emb is None, :146)
+            if (mask && launch_select_rows(t2, tp.temb, td, mask, B, td, s)) return 1;
         }
         tp.tfinal = t2;
     }
@@ -542,20 +564,20 @@ static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const i
     tp.hm = h; tp.wm = w;
     // text hooks around the bottleneck (DD/denoising_diffusion_text_conditional.py:173-203): each CrossAttention REPLACES x
     if (text_cross) {
-        if (t_cross(t, u->cross_down, cur, h, w, ctx, ctx_tokens, tp.cdown)) return 1;
+        if (t_cross(t, u->cross_down, cur, h, w, ctx, ctx_tokens, tp.cdown, mask)) return 1;
         cur = tp.cdown.y;
     }
     if (t_resnet(t, u->mid1, cur, nullptr, h, w, tp.mid1)) return 1;
     cur = tp.mid1.out;
     if (text_cross) {
-        if (t_cross(t, u->cross_mid, cur, h, w, ctx, ctx_tokens, tp.cmid)) return 1;
+        if (t_cross(t, u->cross_mid, cur, h, w, ctx, ctx_tokens, tp.cmid, mask)) return 1;
         cur = tp.cmid.y;
     }
     if (t_attn(t, u->mid_attn, cur, h, w, tp.mid_attn)) return 1;
     if (t_resnet(t, u->mid2, tp.mid_attn.y, nullptr, h, w, tp.mid2)) return 1;
     cur = tp.mid2.out;
     if (text_cross) {
-        if (t_cross(t, u->cross_up, cur, h, w, ctx, ctx_tokens, tp.cup)) return 1;
+        if (t_cross(t, u->cross_up, cur, h, w, ctx, ctx_tokens, tp.cup, mask)) return 1;
         cur = tp.cup.y;
     }
     for (int j = 0; j < n_st; ++j) {
@@ -910,19 +932,20 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
         const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && tp.ctx != nullptr;
         float *d2 = nullptr, *da = nullptr, *d1 = nullptr, *none = nullptr, *dx = nullptr;
         if (text_cross) {
-            if (t_cross_bwd(t, u->cross_up, tp.cup, dcur, h, w, tp.ctx, tp.ctx_tokens, "cross_attn_up", &dx)) return 1;
+            if (t_cross_bwd(t, u->cross_up, tp.cup, dcur, h, w, tp.ctx, tp.ctx_tokens, "cross_attn_up", &dx, tp.mask)) return 1;
             dcur = dx;
         }
         if (t_resnet_bwd(t, u->mid2, tp.mid2, dcur, h, w, dss, "mid_block2", nullptr, &d2, &none)) return 1;
         if (t_attn_bwd(t, u->mid_attn, tp.mid_attn, d2, h, w, "mid_attn", &da)) return 1;
         if (text_cross) {
-            if (t_cross_bwd(t, u->cross_mid, tp.cmid, da, h, w, tp.ctx, tp.ctx_tokens, "cross_attn", &dx)) return 1;
+            if (t_cross_bwd(t, u->cross_mid, tp.cmid, da, h, w, tp.ctx, tp.ctx_tokens, "cross_attn", &dx, tp.mask)) return 1;
             da = dx;
         }
         if (t_resnet_bwd(t, u->mid1, tp.mid1, da, h, w, dss, "mid_block1", nullptr, &d1, &none)) return 1;
         dcur = d1;
         if (text_cross) {
-            if (t_cross_bwd(t, u->cross_down, tp.cdown, dcur, h, w, tp.ctx, tp.ctx_tokens, "cross_attn_down", &dx)) return 1;
+            if (t_cross_bwd(t, u->cross_down, tp.cdown, dcur, h, w, tp.ctx, tp.ctx_tokens, "cross_attn_down", &dx, tp.mask))
+                return 1;
             dcur = dx;
         }
         if (left_phase(n_st + 1)) return 1;
@@ -960,6 +983,7 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     float* dcat = text_concat ? A.alloc((size_t)B * 2 * td) : nullptr;
     float* dte0 = text_concat ? A.alloc((size_t)B * td) : nullptr;
     float* dte0pre = text_concat ? A.alloc((size_t)B * td) : nullptr;
+    float* dtc_kept = text_concat && tp.mask ? A.alloc((size_t)B * td) : nullptr;
     float* dh1 = A.alloc((size_t)B * td);
     float* dh1pre = A.alloc((size_t)B * td);
     float* cw = A.alloc(colsum_ws_floats(B, std::max(u->ss_total, 2 * td)));
@@ -1009,9 +1033,17 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     int ldt = td;
     if (text_concat) {
         const int E = cfg.text_emb_dim;
-        if (launch_linear_wgrad(dtf, td, tp.cat, 2 * td, t.grad("text_concat_proj.weight"), B, 2 * td, td, 0, t.acc, s)) return 1;
-        if (launch_colsum(dtf, B, td, td, 1, cw, t.grad("text_concat_proj.bias"), t.acc, s)) return 1;
-        if (launch_linear_dgrad(dtf, td, u->tc_w, dcat, 2 * td, B, 2 * td, td, nullptr, s)) return 1;
+        const float* dtc = dtf;  // what text_concat_proj's output receives
+        if (tp.mask) {
+            // per-image caption dropout: rows with mask 0 took the raw time embedding, so their gradient bypasses the text
+            // branch -- the branch receives exact zeros for them, and below they take dtf itself as time_mlp's gradient
+            if (launch_route_rows(dtc_kept, td, dtf, td, nullptr, 0, tp.mask, B, td, s)) return 1;
+            dtc = dtc_kept;
+        }
+        if (launch_linear_wgrad(dtc, td, tp.cat, 2 * td, t.grad("text_concat_proj.weight"), B, 2 * td, td, 0, t.acc, s)) return 1;
+        if (launch_colsum(dtc, B, td, td, 1, cw, t.grad("text_concat_proj.bias"), t.acc, s)) return 1;
+        if (launch_linear_dgrad(dtc, td, u->tc_w, dcat, 2 * td, B, 2 * td, td, nullptr, s)) return 1;
+        if (tp.mask && launch_route_rows(dcat, 2 * td, dcat, 2 * td, dtf, td, tp.mask, B, td, s)) return 1;  // the left half
         const float* dte = dcat + td;  // right half: text_proj's output
         if (launch_linear_wgrad(dte, 2 * td, tp.te0, td, t.grad("text_proj.2.weight"), B, td, td, 0, t.acc, s)) return 1;
         if (launch_colsum(dte, B, td, 2 * td, 1, cw, t.grad("text_proj.2.bias"), t.acc, s)) return 1;
@@ -1481,7 +1513,7 @@ int dm_unet_get_grad(dm_unet* u, const char* name, float* out_dev, void* stream)
     return 0;
 }
 
-static int loss_backward_impl(dm_unet* u, const dm_train_args& a) {
+static int loss_backward_impl(dm_unet* u, const dm_train_args& a, const int32_t* text_mask = nullptr) {
     const float *x_start = a.x_start, *coef_host = a.coef_host, *noise = a.noise, *noise_q = a.noise_q, *cond = a.cond,
                 *ctx = a.ctx;
     const int64_t* t_host = a.t_host;
@@ -1502,6 +1534,7 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a) {
     DM_REQUIRE(self_cond >= 0 && self_cond <= 2 && !(self_cond && cond), "self_cond: 0 off, 1 zeros, 2 predicted x_start; not with cond");
     DM_REQUIRE((ctx == nullptr) == (ctx_tokens == 0) && ctx_tokens >= 0, "ctx and ctx_tokens come together");
     DM_REQUIRE(!ctx || u->cfg.text_mode != DM_TEXT_NONE, "the U-Net was built without text conditioning");
+    DM_REQUIRE(!text_mask || ctx, "text_mask needs ctx: without captions there is nothing to drop");
     DM_REQUIRE(u->cfg.input_channels == u->cfg.channels * (self_cond ? 2 : 1) + cond_channels && u->out_dim == u->cfg.channels,
                "training path: U-Net input channels != channels [* 2 with self-conditioning] + cond_channels");
     if (check_hw(u, H, W)) return 1;
@@ -1512,14 +1545,17 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a) {
         DM_CHECK_HIP(hipDeviceSynchronize());
         if (T.coef_dev) (void)hipFree(T.coef_dev);
         if (T.t_dev) (void)hipFree(T.t_dev);
-        T.coef_dev = nullptr; T.t_dev = nullptr; T.cap_B = 0;
+        if (T.mask_dev) (void)hipFree(T.mask_dev);
+        T.coef_dev = nullptr; T.t_dev = nullptr; T.mask_dev = nullptr; T.cap_B = 0;
         DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.coef_dev), (size_t)B * DM_TRAIN_COEFS * sizeof(float)));
         DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.t_dev), (size_t)B * sizeof(int64_t)));
+        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.mask_dev), (size_t)B * sizeof(int32_t)));
         T.cap_B = B;
     }
     const int C = u->cfg.channels;
     const int per = C * H * W;
     const size_t n = (size_t)B * per;
+    const int32_t* mask = text_mask ? T.mask_dev : nullptr;  // the same mask in every forward pass of the call
     auto run = [&](Arena& A, Tape& tp) -> int {
         float* x = A.alloc(n);
         float* out = A.alloc(n);
@@ -1544,7 +1580,7 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a) {
                 TrainState& TT = *u->train;
                 const uint64_t call = TT.drop_call;
                 TT.drop_call = call | (1ull << 40);  // the gradient-free pass draws its own dropout masks
-                const int rc = unet_train_forward(u, A, xin, T.t_dev, out0, B, H, W, s, tp0, ctx, ctx_tokens);
+                const int rc = unet_train_forward(u, A, xin, T.t_dev, out0, B, H, W, s, tp0, ctx, ctx_tokens, mask);
                 TT.drop_call = call;
                 if (rc) return 1;
                 if (!A.dry && (launch_pred_x_start(x, out0, T.coef_dev, xs, B, per, objective, s) ||
@@ -1560,7 +1596,7 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a) {
                 return 1;
             x = xin;
         }
-        if (unet_train_forward(u, A, x, T.t_dev, out, B, H, W, s, tp, ctx, ctx_tokens)) return 1;
+        if (unet_train_forward(u, A, x, T.t_dev, out, B, H, W, s, tp, ctx, ctx_tokens, mask)) return 1;
         if (!A.dry) {
             if (launch_mse_loss(out, x_start, noise, T.coef_dev, dout, part, T.loss_dev, B, per, objective, loss_scale, s, terms,
                                 xq, klpart, a.kl_scale))
@@ -1572,7 +1608,7 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a) {
     try {
         // workspace a call of this shape needs: a dry run of the same allocation sequence, once per shape
         const std::array<long long, 8> key{B, H, W, self_cond, cond_channels, ctx_tokens, ctx ? 1 : 0,
-                                            (model_out ? 1 : 0) | (T.bucketed ? 2 : 0)};
+                                            (model_out ? 1 : 0) | (T.bucketed ? 2 : 0) | (text_mask ? 4 : 0)};
         auto known = T.ws_need.find(key);
         if (known == T.ws_need.end()) {
             Arena dry;
@@ -1599,6 +1635,9 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a) {
         DM_CHECK_HIP(hipMemcpyAsync(T.coef_dev, T.coef_stage.data(), (size_t)B * DM_TRAIN_COEFS * sizeof(float),
                                     hipMemcpyHostToDevice, s));
         DM_CHECK_HIP(hipMemcpyAsync(T.t_dev, t_host, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        if (text_mask) {
+            DM_CHECK_HIP(hipMemcpyAsync(T.mask_dev, text_mask, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
         Arena A;
         A.base = T.ws;
         A.cap = T.ws_cap;
@@ -1632,6 +1671,11 @@ int dm_unet_loss_backward(dm_unet* u, const float* x_start, const int64_t* t_hos
 int dm_unet_loss_backward_ex(dm_unet* u, const dm_train_args* a) {
     DM_REQUIRE(u && a, "null argument");
     return loss_backward_impl(u, *a);
+}
+
+int dm_unet_loss_backward_masked(dm_unet* u, const dm_train_args* a, const int32_t* text_mask) {
+    DM_REQUIRE(u && a && text_mask, "null argument");
+    return loss_backward_impl(u, *a, text_mask);
 }
 
 /* The scalars of the training loop without a host round trip: which = 0 the loss of the last dm_unet_loss_backward, 1 the

@@ -53,6 +53,22 @@ def _default_seed() -> int:
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])  # :33
 
 
+def prob_mask_like(shape, prob) -> torch.Tensor:
+    """classifier_free_guidance.py:41-47: a bool mask that is True with probability ``prob`` (1: all True, 0: all False),
+    drawn from torch's global CPU generator (reproducible under ``torch.manual_seed``, like the timesteps)."""
+    if prob == 1:
+        return torch.ones(shape, dtype=torch.bool)
+    if prob == 0:
+        return torch.zeros(shape, dtype=torch.bool)
+    return torch.zeros(shape).float().uniform_(0, 1) < prob
+
+
+def _drop_prob(p) -> float:
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 <= p <= 1.0:
+        raise ValueError(f"cond_drop_prob must be a probability in [0, 1], got {p!r}")
+    return float(p)
+
+
 class DenoisingDiffusion:
     def __init__(
         self,
@@ -303,7 +319,8 @@ class DenoisingDiffusion:
         return out
 
     def p_losses(self, x_start, t, noise=None, offset_noise_strength=None, cond=None, *, return_model_out=False,
-                 loss_scale=1.0, accumulate=False, self_cond=None, text_emb=None, offset_noise=None, sync=True):
+                 loss_scale=1.0, accumulate=False, self_cond=None, text_emb=None, offset_noise=None, sync=True,
+                 text_mask=None):
         """:823-889: returns the loss (0-dim CPU tensor); the parameter gradients stay on the model
         (``self.model.grad(name)`` / ``.grads()``) -- loss and backward are one call of the library, there is no autograd
         graph to keep.  ``loss_scale`` / ``accumulate`` are the micro-batch loop of ``Trainer.train`` (:1164-1176):
@@ -352,6 +369,15 @@ class DenoisingDiffusion:
             assert cond.shape[0] == b and tuple(cond.shape[2:]) == (h, w), "batch / size mismatch between x and cond"
             cc = int(cond.shape[1])
         ctx, m = self.model._ctx(text_emb, b) if text_emb is not None else (None, 0)
+        mask_arr = None
+        if text_mask is not None:
+            # per-image caption dropout (TextConditionalDenoisingDiffusion.p_losses): 1 = the image keeps its caption
+            if ctx is None:
+                raise ValueError("text_mask needs text_emb on a text-conditional model: without captions there is nothing to drop")
+            keep = torch.as_tensor(text_mask).detach().to("cpu").reshape(-1)
+            if keep.numel() != b:
+                raise RuntimeError(f"text_mask has {keep.numel()} entries for a batch of {b}")
+            mask_arr = (C.c_int32 * b)(*[int(bool(v)) for v in keep.tolist()])
         loss = C.c_float(0.0)
         out = torch.empty_like(x_start) if return_model_out else None
         t_arr = (C.c_int64 * b)(*[int(v) for v in t_cpu.tolist()])
@@ -364,6 +390,11 @@ class DenoisingDiffusion:
         a.loss_out_host = C.pointer(loss) if sync else None
         a.model_out, a.B, a.H, a.W, a.stream = _lib.ptr(out), b, h, w, stream
         a.loss_terms = 1
+        def backward():  # an unmasked call is the entry point it always was; the KL term's second call passes the same mask
+            if mask_arr is None:
+                return self._lib.dm_unet_loss_backward_ex(self.model._handle, C.byref(a))
+            return self._lib.dm_unet_loss_backward_masked(self.model._handle, C.byref(a), mask_arr)
+
         if self.hybrid_loss:
             if cond is not None:
                 # the reference's image-conditional p_losses calls p_mean_variance WITHOUT cond (denoising_diffusion_image_
@@ -373,7 +404,7 @@ class DenoisingDiffusion:
             mask_sum = (t_cpu > 0).float().sum()  # fp32, as the reference forms kl / (mask.sum() + 1e-8), :893-895
             a.kl_scale = float(torch.tensor(0.001, dtype=torch.float32) / (mask_sum + 1e-8))
             a.loss_terms = 3 if float(getattr(self.model, "dropout", 0.0) or 0.0) == 0.0 else 1
-        _lib.check(self._lib.dm_unet_loss_backward_ex(self.model._handle, C.byref(a)))
+        _lib.check(backward())
         if self.hybrid_loss and a.loss_terms == 1:
             # dropout: p_mean_variance's forward pass draws its own masks -- a second, accumulating call for the KL term
             mse = C.c_float(loss.value)
@@ -381,7 +412,7 @@ class DenoisingDiffusion:
                 mse_dev = torch.empty((), device=self.device, dtype=torch.float32)
                 _lib.check(self._lib.dm_unet_train_scalar(self.model._handle, 0, _lib.ptr(mse_dev), stream))
             a.loss_terms, a.accumulate, a.model_out = 2, 1, None
-            _lib.check(self._lib.dm_unet_loss_backward_ex(self.model._handle, C.byref(a)))
+            _lib.check(backward())
             if sync:
                 loss = C.c_float(mse.value + loss.value)
         if sync:
@@ -632,8 +663,10 @@ class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
     """Pipes ``text_emb`` through the U-Net at every step
     (denoising_diffusion_text_conditional.py:264-453)."""
 
-    def __init__(self, *, model, embedding_file=None, **kwargs):
+    def __init__(self, *, model, embedding_file=None, cond_drop_prob=0.0, **kwargs):
         super().__init__(model, **kwargs)
+        # the probability with which p_losses drops an image's caption (classifier_free_guidance.py:376-392); 0: never
+        self.cond_drop_prob = _drop_prob(cond_drop_prob)
         if embedding_file is not None:
             assert os.path.exists(embedding_file), "Pre-computed caption embeddings file not found."
         self.embedding_file = Path(embedding_file) if embedding_file is not None else None
@@ -695,9 +728,24 @@ class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
                          cond_scale=cond_scale, rescaled_phi=rescaled_phi,
                          remove_parallel_component=remove_parallel_component, keep_parallel_frac=keep_parallel_frac, **kw)
 
-    def p_losses(self, x_start, t, text_emb=None, noise=None, offset_noise_strength=None, **kw):
-        """denoising_diffusion_text_conditional.py:476-542 (the reference's positional order: x_start, t, text_emb, noise)."""
-        return super().p_losses(x_start, t, noise, offset_noise_strength, text_emb=text_emb, **kw)
+    def p_losses(self, x_start, t, text_emb=None, noise=None, offset_noise_strength=None, *, text_mask=None,
+                 cond_drop_prob=None, **kw):
+        """denoising_diffusion_text_conditional.py:476-542 (the reference's positional order: x_start, t, text_emb, noise).
+        Per-image caption dropout, the training half of classifier-free guidance (classifier_free_guidance.py:376-392):
+        ``text_mask`` is a (B,) bool / int tensor, 1 = the image keeps its caption, 0 = it is trained as if ``text_emb``
+        were None.  Without it, and with a drop probability > 0 (``cond_drop_prob``, default: the constructor's), the mask
+        is ``prob_mask_like((B,), 1 - cond_drop_prob)`` drawn from torch's global CPU generator."""
+        if text_mask is None and text_emb is not None:
+            p = self.cond_drop_prob if cond_drop_prob is None else _drop_prob(cond_drop_prob)
+            if p > 0:
+                text_mask = prob_mask_like((x_start.shape[0],), 1.0 - p)
+        if text_mask is not None:
+            if not getattr(self.model, "text_condition", False):
+                raise ValueError("text_mask (per-image caption dropout) needs a text-conditional Unet: other models have no "
+                                 "null prediction")
+            if text_emb is None:
+                raise ValueError("text_mask needs text_emb: without captions there is nothing to drop")
+        return super().p_losses(x_start, t, noise, offset_noise_strength, text_emb=text_emb, text_mask=text_mask, **kw)
 
     def forward(self, img, text_emb=None, *args, **kwargs):
         """denoising_diffusion_text_conditional.py:544-550: the training loss with the caption embeddings."""

@@ -154,9 +154,11 @@ def load_checkpoint(path, diffusion, *, ema: Optional[EMA] = None):
 
 def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, betas=(0.9, 0.99), eps=1e-8,
                max_grad_norm=1.0, ema: Optional[EMA] = None, t=None, noise=None, group=None, sync=True,
-               timing: Optional[dict] = None, bucketed: Optional[bool] = None):
+               timing: Optional[dict] = None, bucketed: Optional[bool] = None, text_mask=None):
     """One iteration of ``Trainer.train`` (:1164-1190).  ``micro_batches``: the ``gradient_accumulate_every`` image batches
-    (in [0, 1]) of the iteration.  ``t`` / ``noise`` (lists, one per micro-batch) inject the random draws for tests.
+    (in [0, 1]) of the iteration; for a text-conditional model a micro-batch may be a pair ``(images, text_emb)``, whose
+    captions ``p_losses`` then drops per image with the model's ``cond_drop_prob``.  ``t`` / ``noise`` / ``text_mask``
+    (lists, one entry per micro-batch) inject the random draws for tests.
     Under ``torch.distributed`` (one process per GPU, as ``accelerate`` runs the reference's Trainer under DDP) every rank
     computes the gradients of ITS micro-batches and the flat gradient buffer is averaged over the ranks in place (RCCL over
     xGMI) before the optimiser step; every rank then takes the same step.  With more than one rank (``bucketed=True`` forces
@@ -180,11 +182,23 @@ def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, bet
         bucketed or (dist.get_world_size(group) > 1 and dist.get_backend(group) == "nccl"))
     if overlap != getattr(unet, "_bucketed", False) and hasattr(unet, "grad_buckets"):
         unet.grad_buckets(enable=overlap)
+    if text_mask is not None and len(text_mask) != k:
+        raise ValueError(f"text_mask has {len(text_mask)} entries for {k} micro-batches")
     for i, data in enumerate(batches):
+        text = {}  # only a micro-batch with captions asks the diffusion object for anything new
+        if isinstance(data, (tuple, list)):
+            if len(data) != 2:
+                raise ValueError("a micro-batch is an image tensor or a pair (images, text_emb)")
+            data, emb = data
+            text = {"text_emb": emb}
+        if text_mask is not None and text_mask[i] is not None:
+            if not text:
+                raise ValueError(f"text_mask[{i}] given for a micro-batch without text_emb")
+            text["text_mask"] = text_mask[i]
         x = diffusion.normalize(data.to(diffusion.device, torch.float32))
         ti = t[i] if t is not None else torch.randint(0, diffusion.num_timesteps, (x.shape[0],)).long()
         ni = noise[i] if noise is not None else None
-        loss = diffusion.p_losses(x, ti, noise=ni, loss_scale=1.0 / k, accumulate=i > 0, **lazy)
+        loss = diffusion.p_losses(x, ti, noise=ni, loss_scale=1.0 / k, accumulate=i > 0, **text, **lazy)
         total = (total + float(loss)) if sync else (loss if i == 0 else total + loss)
     if parallel:
         # DDP averages the gradients over the ranks.  The buffer is the library's own (a zero-copy view); no host

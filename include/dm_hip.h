@@ -412,6 +412,13 @@ typedef struct dm_train_args {
     float kl_scale;
 } dm_train_args;
 int dm_unet_loss_backward_ex(dm_unet* u, const dm_train_args* a);
+/* The same call with a per-image text mask (per-image caption dropout, what DD/classifier_free_guidance.py does with
+ * cond_drop_prob / prob_mask_like, :41-47, :376-392).  text_mask: B HOST int32 values, copied to the device as t_host is.
+ * Image b keeps its caption iff text_mask[b] != 0; the others are trained as if text_emb were None.  The mask holds in
+ * every forward pass of the call: the gradient-free self-conditioning pass and the KL term's pass see the same one.  It
+ * needs a->ctx; masked-out rows of ctx are read (they must be initialised), their values reach neither the loss nor any
+ * gradient.  dm_train_args is unchanged, so dm_unet_loss_backward_ex issues the launches it always did. */
+int dm_unet_loss_backward_masked(dm_unet* u, const dm_train_args* a, const int32_t* text_mask);
 /* The rest of one Trainer.train iteration (:1178-1190) on device-resident state: the master parameters, the Adam moments and
  * the EMA copy live in flat device buffers in the reference layouts; after the update every packed weight buffer the
  * kernels read is rebuilt on the device (pack_kernels.hip, bit-identical to the host packers).
