@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DM_LIB") or os.path.join(_HERE, "libdm_hip.so")
 DM_MAX_STAGES = 8
 DM_COEFS = 8
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 # every symbol include/dm_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -28,6 +28,7 @@ EXPORTS = (
     "dm_encoder_finalize", "dm_encoder_forward",
     "dm_op_conv2d", "dm_op_downsample", "dm_op_rmsnorm", "dm_op_block", "dm_op_linear_attention",
     "dm_op_attention", "dm_op_sampler_update", "dm_op_cfg_combine",
+    "dm_op_group_norm", "dm_op_vae_attention", "dm_op_vq_nearest",
     "dm_conv_create", "dm_conv_destroy", "dm_conv_forward", "dm_op_pool2d", "dm_op_resize_bilinear",
     "dm_op_copy_channels_nhwc", "dm_op_global_avgpool", "dm_op_linear",
     "dm_unet_train_enable", "dm_unet_grad_floats", "dm_unet_grads_flat", "dm_unet_train_buckets", "dm_unet_train_bucket", "dm_unet_get_grad", "dm_unet_loss_backward", "dm_unet_loss_backward_ex", "dm_unet_loss_backward_masked", "dm_op_q_sample", "dm_op_linear_bwd",
@@ -142,6 +143,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_attention.argtypes = [fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
     lib.dm_op_sampler_update.argtypes = [i32, i32, fp, fp, fp, C.POINTER(C.c_float), fp, fp, i64, vp]
     lib.dm_op_cfg_combine.argtypes = [fp, fp, fp, i32, i64, C.c_float, C.c_float, i32, C.c_float, vp]
+    lib.dm_op_group_norm.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, C.c_float, i32, vp]
+    lib.dm_op_vae_attention.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, vp]
+    lib.dm_op_vq_nearest.argtypes = [fp, fp, fp, vp, i64, i32, i32, i32, vp]
     lib.dm_conv_create.argtypes = [fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
     lib.dm_conv_destroy.argtypes = [vp]
     lib.dm_conv_destroy.restype = None

@@ -82,6 +82,16 @@ static int launch_attention_rows(const float* q, const float* k, const float* v,
     return 0;
 }
 
+// The one place that picks the attention kernel (vrun_attn and dm_op_vae_attention): the MFMA kernel where it applies,
+// else one row per wavefront; force_rows runs the row kernel at any shape it can take.
+static int launch_vae_attention(const float* q, const float* k, const float* v, float* out, int B, int n, int C,
+                                bool force_rows, hipStream_t s) {
+    DM_REQUIRE(B > 0 && n > 0 && C > 0, "VAE attention: empty input");
+    DM_REQUIRE(B <= 65535, "VAE attention: the batch is the grid's y dimension");
+    if (!force_rows && vae_attn_mfma_ok(n, C)) return launch_vae_attn_mfma(q, k, v, out, B, n, C, s);
+    return launch_attention_rows(q, k, v, out, B, n, C, s);
+}
+
 }  // namespace dm
 
 struct dm_decoder {
@@ -181,9 +191,7 @@ static int vrun_attn(Ctx& c, const VaeAttn& At, const float* x, int H, int W, fl
     if (run_conv(c, At.k, hn, nullptr, H, W, k, 0, nullptr, nullptr, nullptr)) return 1;
     if (run_conv(c, At.v, hn, nullptr, H, W, v, 0, nullptr, nullptr, nullptr)) return 1;
     if (!c.dry()) {
-        if (vae_attn_mfma_ok(n, At.c) ? launch_vae_attn_mfma(q, k, v, o, c.B, n, At.c, c.s)
-                                      : launch_attention_rows(q, k, v, o, c.B, n, At.c, c.s))
-            return 1;
+        if (launch_vae_attention(q, k, v, o, c.B, n, At.c, /*force_rows=*/false, c.s)) return 1;
     }
     if (run_conv(c, At.proj, o, nullptr, H, W, y, EPI_RESIDUAL, nullptr, nullptr, x)) return 1;
     *out = y;
@@ -396,6 +404,28 @@ __global__ __launch_bounds__(256) void vq_nearest_kernel(const float* __restrict
     if (idx && lane == 0) idx[pix] = bi;
 }
 
+static int launch_vq_nearest(const float* z, const float* e, const float* e2, float* zq_nchw, int* idx, int64_t pixels,
+                             int E, int n_embed, int hw, hipStream_t s) {
+    DM_REQUIRE(pixels > 0 && E > 0 && n_embed > 0 && hw > 0, "VQ: empty input");
+    DM_REQUIRE(pixels % hw == 0, "VQ: pixels is a whole number of images of hw pixels");
+    DM_REQUIRE((pixels + 3) / 4 <= 0x7fffffff, "VQ: too many pixels for one launch");
+    hipLaunchKernelGGL(vq_nearest_kernel, dim3((unsigned)((pixels + 3) / 4)), dim3(256), 0, s, z, e, e2, zq_nchw, idx,
+                       pixels, E, n_embed, hw);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// |e_j|^2 of every codebook row: fp32, summed in channel order like torch.sum(embedding.weight ** 2, dim=1)
+static std::vector<float> code_sq_host(const float* cb, int n_embed, int E) {
+    std::vector<float> sq((size_t)n_embed);
+    for (int j = 0; j < n_embed; ++j) {
+        float s2 = 0.f;
+        for (int c = 0; c < E; ++c) s2 += cb[(size_t)j * E + c] * cb[(size_t)j * E + c];
+        sq[j] = s2;
+    }
+    return sq;
+}
+
 }  // namespace dm
 
 struct dm_encoder {
@@ -447,10 +477,9 @@ static int encoder_forward_impl(dm_encoder* d, Arena& A, const float* x, float* 
     if (A.dry) return 0;
     if (pre_quant && launch_nhwc_to_nchw(pq, pre_quant, B, cfg.embed_dim, h * w, s)) return 1;
     if (zq) {
-        const int64_t pixels = (int64_t)B * h * w;
-        hipLaunchKernelGGL(vq_nearest_kernel, dim3((pixels + 3) / 4), dim3(256), 0, s, pq, d->codebook, d->code_sq, zq,
-                           indices, pixels, cfg.embed_dim, cfg.n_embed, h * w);
-        DM_CHECK_HIP(hipGetLastError());
+        if (launch_vq_nearest(pq, d->codebook, d->code_sq, zq, indices, (int64_t)B * h * w, cfg.embed_dim, cfg.n_embed,
+                              h * w, s))
+            return 1;
     }
     return 0;
 }
@@ -566,12 +595,7 @@ int dm_encoder_finalize(dm_encoder* d) {
     if (vconv(u, d->conv_out, "encoder.conv_out", zc, block_in, 3, 1, false)) return 1;
     if (vconv(u, d->quant_conv, "quant_conv", cfg.embed_dim, zc, 1, 0, false)) return 1;
     const HostTensor& cb = P(u, "quantize.embedding.weight");
-    std::vector<float> sq((size_t)cfg.n_embed);
-    for (int j = 0; j < cfg.n_embed; ++j) {
-        float s2 = 0.f;  // fp32, summed in channel order like torch.sum(embedding.weight ** 2, dim=1)
-        for (int c = 0; c < cfg.embed_dim; ++c) s2 += cb.data[(size_t)j * cfg.embed_dim + c] * cb.data[(size_t)j * cfg.embed_dim + c];
-        sq[j] = s2;
-    }
+    const std::vector<float> sq = code_sq_host(cb.data.data(), cfg.n_embed, cfg.embed_dim);
     if (u->own.upload(cb.data.data(), cb.data.size(), &d->codebook) || u->own.upload(sq.data(), sq.size(), &d->code_sq))
         return 1;
     for (auto& kv : u->params) std::vector<float>().swap(kv.second.data);
@@ -600,3 +624,65 @@ int dm_encoder_forward(dm_encoder* d, const float* x, float* zq, float* pre_quan
 
 }  // extern "C"
 
+// =====================================================================================================
+// The three kernels groups above on their own (dm_op_*): the same launch functions, workspaces owned by the call.
+// =====================================================================================================
+namespace dm {
+
+// wait for the stream, release the call's scratch buffers, report an execution error
+static int finish_vae_op(int rc, hipStream_t s, void* buf0, void* buf1 = nullptr) {
+    hipError_t e = hipStreamSynchronize(s);
+    if (buf0) (void)hipFree(buf0);
+    if (buf1) (void)hipFree(buf1);
+    if (!rc && e != hipSuccess) {
+        set_error(std::string("kernel execution failed: ") + hipGetErrorString(e));
+        rc = 1;
+    }
+    return rc;
+}
+
+}  // namespace dm
+
+extern "C" {
+
+int dm_op_group_norm(const float* x_nhwc, const float* weight, const float* bias, float* y_nhwc, int B, int HW, int C,
+                     int groups, float eps, int swish, void* stream) {
+    DM_REQUIRE(x_nhwc && weight && bias && y_nhwc, "null argument");
+    DM_REQUIRE(B > 0 && HW > 0 && C > 0 && groups > 0, "empty input");
+    DM_REQUIRE(B <= 65535 && C % groups == 0, "GroupNorm: B <= 65535 and C % groups == 0");  // before the workspace is sized
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* ws = nullptr;
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ws), group_stats_ws_floats(B, groups) * sizeof(float)));
+    int rc = launch_group_norm(x_nhwc, weight, bias, y_nhwc, ws, B, HW, C, groups, eps, swish, s);
+    return finish_vae_op(rc, s, ws);
+}
+
+int dm_op_vae_attention(const float* q, const float* k, const float* v, float* out, int B, int n, int C, int kernel,
+                        void* stream) {
+    DM_REQUIRE(q && k && v && out, "null argument");
+    DM_REQUIRE(kernel == 0 || kernel == 1, "kernel: 0 (as the model dispatches) or 1 (row kernel)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = launch_vae_attention(q, k, v, out, B, n, C, kernel == 1, s);
+    return finish_vae_op(rc, s, nullptr);
+}
+
+int dm_op_vq_nearest(const float* z_rows, const float* codebook, float* zq_nchw, int32_t* indices, int64_t pixels, int E,
+                     int n_embed, int hw, void* stream) {
+    DM_REQUIRE(z_rows && codebook && zq_nchw, "null argument");
+    DM_REQUIRE(pixels > 0 && E > 0 && n_embed > 0 && hw > 0, "empty input");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<float> cb;
+    if (d2h(codebook, (size_t)n_embed * E, cb)) return 1;
+    const std::vector<float> sq = code_sq_host(cb.data(), n_embed, E);
+    float* e2 = nullptr;
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&e2), sq.size() * sizeof(float)));
+    hipError_t e = hipMemcpy(e2, sq.data(), sq.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(e2);
+        DM_CHECK_HIP(e);
+    }
+    int rc = launch_vq_nearest(z_rows, codebook, e2, zq_nchw, indices, pixels, E, n_embed, hw, s);
+    return finish_vae_op(rc, s, e2);
+}
+
+}  // extern "C"

@@ -341,39 +341,43 @@ int launch_sinusoid(const int64_t* t, const int64_t* step_times, const SamplerSt
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void group_stats_kernel(const float* __restrict__ x, float* __restrict__ stats,
                                                           int HW, int C, int groups, float eps) {
+    // two passes, both summed in double: a constant group gets its own value back as the mean (no residue of an fp32 sum
+    // for rstd = eps^-1/2 to blow up), and the mean of an off-centre group is good to the last bit of its fp32 store
     const int b = blockIdx.y, grp = blockIdx.x;
     const int cg = C / groups;
     const int64_t n = (int64_t)HW * cg;
     const float* xb = x + (size_t)b * HW * C + grp * cg;
-    __shared__ float red[4];
-    __shared__ float mean_s;
-    float sum = 0.f;
+    __shared__ double red[4];
+    __shared__ double mean_s;
+    double sum = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 256) {
         int64_t p = i / cg;
         int j = i - p * cg;
-        sum += xb[p * C + j];
+        sum += (double)xb[p * C + j];
     }
-    sum = wave_sum(sum);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
     __syncthreads();
-    if (threadIdx.x == 0) mean_s = (red[0] + red[1] + red[2] + red[3]) / (float)n;
+    if (threadIdx.x == 0) mean_s = (red[0] + red[1] + red[2] + red[3]) / (double)n;
     __syncthreads();
-    const float mean = mean_s;
-    float var = 0.f;
+    const double mean = mean_s;
+    double var = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += 256) {
         int64_t p = i / cg;
         int j = i - p * cg;
-        float d = xb[p * C + j] - mean;
+        const double d = (double)xb[p * C + j] - mean;
         var += d * d;
     }
-    var = wave_sum(var);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) var += __shfl_xor(var, m);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = var;
     __syncthreads();
     if (threadIdx.x == 0) {
-        float v = (red[0] + red[1] + red[2] + red[3]) / (float)n;
-        stats[((size_t)b * groups + grp) * 2 + 0] = mean;
-        stats[((size_t)b * groups + grp) * 2 + 1] = 1.0f / sqrtf(v + eps);
+        const double v = (red[0] + red[1] + red[2] + red[3]) / (double)n;
+        stats[((size_t)b * groups + grp) * 2 + 0] = (float)mean;
+        stats[((size_t)b * groups + grp) * 2 + 1] = (float)(1.0 / sqrt(v + (double)eps));
     }
 }
 __global__ void group_apply_kernel(const float* __restrict__ x, const float* __restrict__ stats,
@@ -392,6 +396,8 @@ __global__ void group_apply_kernel(const float* __restrict__ x, const float* __r
 int launch_group_norm(const float* x, const float* w, const float* b, float* y, float* stats_ws, int B, int HW,
                       int C, int groups, float eps, int swish, hipStream_t s) {
     // stats_ws: group_stats_ws_floats(B, groups) = B*groups*2 floats (mean, rstd), then the per-block partial sums (doubles)
+    DM_REQUIRE(groups > 0 && C % groups == 0, "GroupNorm: C % groups == 0");
+    DM_REQUIRE(B <= 65535, "GroupNorm: the batch is the grid's y dimension");
     if (group_sums_ok(C, groups)) {
         double* acc = reinterpret_cast<double*>(stats_ws + (size_t)B * groups * 2);
         if (launch_group_stats_fast(x, stats_ws, acc, B, HW, C, groups, eps, s)) return 1;

@@ -174,7 +174,9 @@ int launch_vae_attn_mfma(const float* q, const float* k, const float* v, float* 
 
 // ---------------------------------------------------------------------------------------
 // GroupNorm statistics, NHWC, deterministic.  Stage 1: one block per (image, slab of pixel rows) reads whole pixel rows
-// (16 bytes per lane, coalesced), keeps per-lane channel sums in fp32 over its rows, folds a lane's quad in double, combines
+// (16 bytes per lane, coalesced), keeps per-lane channel sums in DOUBLE over its rows (x * x is exact there, so that
+// E[x^2] - mean^2 keeps ten digits where the mean is a thousand times the spread; fp32 sums lost the variance at
+// mean / std of a few hundred, tests/test_hip_vae_ops.py), folds a lane's quad, combines
 // the lanes of one group with wavefront shuffles (a group's channels are adjacent lanes of one pixel row: a fixed butterfly),
 // the row slots of the block through LDS in a fixed order, and writes its (sum, sum of squares) per group to
 // part[b][block][2 * groups].  Stage 2: one thread per (image, group) adds the blocks in order -> (mean, rstd).  No atomics:
@@ -191,22 +193,25 @@ __global__ __launch_bounds__(256) void group_sums_kernel(const float* __restrict
     const int c4 = threadIdx.x % tpr, sub = threadIdx.x / tpr;
     const int r0 = blockIdx.x * rows_per_block;
     const int r1 = min(r0 + rows_per_block, HW);
-    f32x4 s = make_f32x4(0.f, 0.f, 0.f, 0.f), ss = make_f32x4(0.f, 0.f, 0.f, 0.f);
+    double sv[4] = {0.0, 0.0, 0.0, 0.0}, qv[4] = {0.0, 0.0, 0.0, 0.0};
     if (sub < rpp)
         for (int r = r0 + sub; r < r1; r += rpp) {
             const f32x4 vx = *reinterpret_cast<const f32x4*>(x + ((size_t)b * HW + r) * C + 4 * c4);
-            s += vx;
-            ss += vx * vx;
+            const double xe[4] = {(double)vx.x, (double)vx.y, (double)vx.z, (double)vx.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                sv[e] += xe[e];
+                qv[e] += xe[e] * xe[e];
+            }
         }
     const int cg = C / groups;  // channels per group (>= 1)
     if (cg % 4 != 0) {
         // a quad straddles groups (2 channels per group at C = 64, 6 at C = 192): per-element sums through LDS, each group
         // added up channel by channel and row slot by row slot, in order
-        const float sv[4] = {s.x, s.y, s.z, s.w}, qv[4] = {ss.x, ss.y, ss.z, ss.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            red[threadIdx.x][2 * e] = (double)sv[e];
-            red[threadIdx.x][2 * e + 1] = (double)qv[e];
+            red[threadIdx.x][2 * e] = sv[e];
+            red[threadIdx.x][2 * e + 1] = qv[e];
         }
         __syncthreads();
         if ((int)threadIdx.x < 2 * groups) {
@@ -219,8 +224,8 @@ __global__ __launch_bounds__(256) void group_sums_kernel(const float* __restrict
         return;
     }
     const int lpg = cg / 4;  // a group = lpg adjacent lanes of a pixel row
-    double ds = ((double)s.x + (double)s.y) + ((double)s.z + (double)s.w);
-    double dq = ((double)ss.x + (double)ss.y) + ((double)ss.z + (double)ss.w);
+    double ds = (sv[0] + sv[1]) + (sv[2] + sv[3]);
+    double dq = (qv[0] + qv[1]) + (qv[2] + qv[3]);
     if ((lpg & (lpg - 1)) == 0 && lpg <= 64) {
         // power-of-two group width: butterfly over the group's lanes (tpr is a multiple of lpg and divides 256, so a group
         // never straddles a wavefront); idle row slots (sub >= rpp) hold zeros and take part harmlessly

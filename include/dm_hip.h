@@ -301,6 +301,20 @@ int dm_op_sampler_update(int kind, int objective, const float* x, const float* e
  * both inputs. */
 int dm_op_cfg_combine(const float* cond, const float* null_out, float* out, int B, int64_t per_sample, float cond_scale,
                       float rescaled_phi, int remove_parallel_component, float keep_parallel_frac, void* stream);
+/* The VAE's non-convolution kernels on their own, in the kernels' own layouts (pixel rows, NHWC), through the same
+ * launch functions as the decoder / encoder forward.  Workspaces are allocated inside the call; every call synchronises.
+ * GroupNorm(groups, eps) with affine weight / bias (C), then x * sigmoid(x) when swish != 0
+ * (LD/modules/diffusionmodules/model.py:50-56).  x, y: (B, HW, C). */
+int dm_op_group_norm(const float* x_nhwc, const float* weight, const float* bias, float* y_nhwc, int B, int HW, int C,
+                     int groups, float eps, int swish, void* stream);
+/* The core of AttnBlock (model.py:203-215): out[b][i] = softmax_j(q[b][i] . k[b][j] * C^-1/2) v[b][j]; q, k, v, out
+ * (B, n, C) rows.  kernel 0: the kernel the model dispatches for (n, C); 1: the one-row-per-wavefront kernel. */
+int dm_op_vae_attention(const float* q, const float* k, const float* v, float* out, int B, int n, int C, int kernel,
+                        void* stream);
+/* The codebook search of VQModel.encode: z_rows (pixels, E), codebook (n_embed, E) -> zq_nchw (pixels / hw, E, hw) =
+ * z + (nearest code - z) and indices (pixels, may be NULL); ties go to the lower index. */
+int dm_op_vq_nearest(const float* z_rows, const float* codebook, float* zq_nchw, int32_t* indices, int64_t pixels, int E,
+                     int n_embed, int hw, void* stream);
 
 /* ---- sample consumer: the InceptionV3 feature extractor behind the reference's FID and
  *      Inception-score evaluators (DD/fid_evaluation.py:41-51 -> pytorch_fid.inception.InceptionV3;

@@ -101,12 +101,12 @@ def test_guidance_keywords(cls, methods):
 
 
 def test_sample_args_guidance_fields():
-    """dm_sample_args (ABI 6) ends with the guidance fields; the zero-initialised struct means no guidance."""
+    """dm_sample_args (since ABI 6) ends with the guidance fields; the zero-initialised struct means no guidance."""
     names = [f[0] for f in _lib.SampleArgs._fields_]
     assert names[-6:] == ["cfg", "cfg_scale", "cfg_rescaled_phi", "cfg_keep_parallel_frac", "cfg_remove_parallel",
                           "cfg_reserved_"]
     a = _lib.SampleArgs()
     assert a.cfg == 0 and a.cfg_scale == 0.0
     assert ctypes.sizeof(_lib.SampleArgs) % 8 == 0
-    assert _lib.ABI_VERSION == 6
+    assert _lib.ABI_VERSION == 7
     assert {"dm_unet_forward_masked", "dm_op_cfg_combine"} <= set(_lib.EXPORTS)

@@ -231,6 +231,48 @@ def test_attention(shape):
     assert rel_l2(out.cpu(), ref) < TOL
 
 
+def _hard_limit(fn, sd, x):
+    """Inputs that are not unit-scale randn: the oracle in fp64 is the reference, and the limit is the error of the same
+    oracle in fp32 against it, times 4 for another summation order, never below TOL."""
+    ref = fn({k: v.double() for k, v in sd.items()}, "a", x.double(), 4, 32)
+    return ref, max(TOL, 4 * rel_l2(fn(sd, "a", x, 4, 32), ref))
+
+
+# x scaled by 8 (the pre-norm makes the operator invariant to it in exact arithmetic), mem_kv by 4: softmax inputs far from
+# unit scale, the memory slots dominate.  One shape per kernel: fused C = 64, fused C = 128, unfused chain
+@pytest.mark.parametrize("shape", [(2, 64, 16, 16), (3, 128, 8, 8), (1, 256, 8, 8)])
+def test_linear_attention_hard_inputs(shape):
+    B, Cc, H, W = shape
+    x = seeded(shape, 1, 8.0)
+    sd = _attn_sd(Cc, full=False)
+    sd["a.mem_kv"] = sd["a.mem_kv"] * 4
+    ref, lim = _hard_limit(uo.linear_attention, sd, x)
+    out = torch.empty(shape, device=DEV)
+    a = [dev(t) for t in (x, sd["a.norm.g"], sd["a.mem_kv"], sd["a.to_qkv.weight"], sd["a.to_out.0.weight"],
+                          sd["a.to_out.0.bias"], sd["a.to_out.1.g"])]
+    _lib.check(_lib.load().dm_op_linear_attention(*[_lib.ptr(t) for t in a], _lib.ptr(out), B, Cc, H, W, 4, 32, None))
+    err = rel_l2(out.cpu(), ref)
+    print(f"linear_attention hard {shape}: kernel {err:.3g}  limit {lim:.3g}")
+    assert err <= lim
+
+
+# one shape per kernel: fused 4x4 (attn16_fused.hip), unfused chain, tiled core
+@pytest.mark.parametrize("shape", [(2, 256, 4, 4), (1, 128, 16, 16), (1, 64, 32, 32)])
+def test_attention_hard_inputs(shape):
+    B, Cc, H, W = shape
+    x = seeded(shape, 1, 8.0)
+    sd = _attn_sd(Cc, full=True)
+    sd["a.mem_kv"] = sd["a.mem_kv"] * 4
+    ref, lim = _hard_limit(uo.full_attention, sd, x)
+    out = torch.empty(shape, device=DEV)
+    a = [dev(t) for t in (x, sd["a.norm.g"], sd["a.mem_kv"], sd["a.to_qkv.weight"], sd["a.to_out.weight"],
+                          sd["a.to_out.bias"])]
+    _lib.check(_lib.load().dm_op_attention(*[_lib.ptr(t) for t in a], _lib.ptr(out), B, Cc, H, W, 4, 32, None))
+    err = rel_l2(out.cpu(), ref)
+    print(f"attention hard {shape}: kernel {err:.3g}  limit {lim:.3g}")
+    assert err <= lim
+
+
 def test_sampler_update_bit_exact():
     """The update is elementwise fp32 with contraction off: it must equal the reference's
     expression tree bit for bit (clamp included), for every objective (pred_noise / pred_x0 / pred_v,
