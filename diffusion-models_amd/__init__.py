@@ -23,6 +23,7 @@ from .diffusion import (  # noqa: F401
     TextConditionalDenoisingDiffusion,
     TextConditionalLatentDiffusion,
 )
+from .elucidated import ElucidatedDiffusion, edm_dpmpp_table, edm_heun_table, edm_sigmas  # noqa: F401
 from .vae import VQDecoder, VQEncoder, VQModel  # noqa: F401
 from .dist import gather_shards, sample_global, sample_sharded, shard_bounds, shared_seed  # noqa: F401
 from .checkpoint import load_trainer_checkpoint, load_vae_checkpoint  # noqa: F401
@@ -38,6 +39,7 @@ __all__ = [
     "ImageConditionalLatentDiffusion",
     "LatentDiffusion",
     "TextConditionalLatentDiffusion",
+    "ElucidatedDiffusion",
     "VQDecoder",
     "VQEncoder",
     "VQModel",
@@ -54,6 +56,9 @@ __all__ = [
     "decoder_param_spec",
     "make_schedule",
     "ddim_time_pairs",
+    "edm_sigmas",
+    "edm_heun_table",
+    "edm_dpmpp_table",
     "synth_state_dict",
     "synth_tensor",
 ]

@@ -14,6 +14,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DM_LIB") or os.path.join(_HERE, "libdm_hip.so")
 DM_MAX_STAGES = 8
 DM_COEFS = 8
+DM_EDM_COEFS = 16
+EDM_HEUN, EDM_DPMPP = 0, 1
 ABI_VERSION = 7
 
 # every symbol include/dm_hip.h declares (tests check the library exports all of them)
@@ -39,6 +41,8 @@ EXPORTS = (
     "dm_op_conv2d_bwd", "dm_op_downsample_bwd", "dm_op_block_bwd", "dm_op_rmsnorm_bwd", "dm_op_linear_attention_bwd",
     "dm_op_attention_bwd",
     "dm_profile_enable", "dm_profile_read",
+    "dm_unet_forward_ft", "dm_sample_edm",
+    "dm_op_edm_churn_in", "dm_op_edm_euler", "dm_op_edm_heun", "dm_op_edm_dpmpp", "dm_op_edm_finalize",
 )
 
 
@@ -82,6 +86,16 @@ class SampleArgs(C.Structure):
         ("reserved_", C.c_int32), ("stream", C.c_void_p),
         ("cfg", C.c_int32), ("cfg_scale", C.c_float), ("cfg_rescaled_phi", C.c_float),
         ("cfg_keep_parallel_frac", C.c_float), ("cfg_remove_parallel", C.c_int32), ("cfg_reserved_", C.c_int32),
+    ]
+
+
+class EdmArgs(C.Structure):
+    """dm_edm_args (include/dm_hip.h)."""
+    _fields_ = [
+        ("kind", C.c_int32), ("n_steps", C.c_int32), ("table_host", C.POINTER(C.c_float)),
+        ("x_init", C.c_void_p), ("noise", C.c_void_p), ("seed", C.c_uint64), ("sample_offset", C.c_uint64),
+        ("out", C.c_void_p), ("sigma_init", C.c_float), ("clamp", C.c_int32),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("use_graph", C.c_int32), ("stream", C.c_void_p),
     ]
 
 
@@ -191,6 +205,13 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_linear_attention_bwd.argtypes = [fp] * 15 + [i32] * 6 + [vp]
     lib.dm_op_attention_bwd.argtypes = [fp] * 13 + [i32] * 6 + [vp]
     lib.dm_profile_enable.argtypes = [i32]
+    lib.dm_unet_forward_ft.argtypes = [vp, fp, fp, fp, i32, fp, i32, i32, i32, vp]
+    lib.dm_sample_edm.argtypes = [vp, C.POINTER(EdmArgs)]
+    lib.dm_op_edm_churn_in.argtypes = [fp, fp, C.POINTER(C.c_float), i32, u64, u64, u64, fp, fp, i32, i64, vp]
+    lib.dm_op_edm_euler.argtypes = [fp, fp, C.POINTER(C.c_float), i32, i32, fp, fp, fp, fp, i32, i64, vp]
+    lib.dm_op_edm_heun.argtypes = [fp, fp, fp, fp, C.POINTER(C.c_float), i32, i32, fp, i32, i64, vp]
+    lib.dm_op_edm_dpmpp.argtypes = [fp, fp, fp, C.POINTER(C.c_float), i32, fp, i32, i64, vp]
+    lib.dm_op_edm_finalize.argtypes = [fp, fp, i64, vp]
     lib.dm_profile_read.argtypes = [C.POINTER(ProfileRow), i32, C.POINTER(i32)]
 
 

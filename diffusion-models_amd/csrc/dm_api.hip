@@ -4,6 +4,7 @@
 // sequence, so one denoise step can be captured into a hipGraph and replayed.
 #include "../../include/dm_hip.h"
 #include "dm_common.h"
+#include "edm.h"
 
 #include <array>
 #include <cmath>
@@ -315,10 +316,11 @@ struct dm_unet {
     // the instantiated graph of one denoise step, reused while the key (shape, kind, every captured pointer) holds
     struct GraphKey {
         int kind = -1, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
+        int edm_clamp = 0;  // ElucidatedDiffusion: the clamp flag, a kernel argument of the captured Heun step
         const void *noise = nullptr, *all_steps = nullptr, *ws = nullptr, *times = nullptr, *coefs = nullptr;
         bool operator==(const GraphKey& o) const {
             return kind == o.kind && B == o.B && H == o.H && W == o.W && ctx_tokens == o.ctx_tokens &&
-                   cond_channels == o.cond_channels && objective == o.objective && self_cond == o.self_cond && guided == o.guided && noise == o.noise && all_steps == o.all_steps && ws == o.ws &&
+                   cond_channels == o.cond_channels && objective == o.objective && self_cond == o.self_cond && guided == o.guided && edm_clamp == o.edm_clamp && noise == o.noise && all_steps == o.all_steps && ws == o.ws &&
                    times == o.times && coefs == o.coefs;
         }
     } gkey;
@@ -338,11 +340,21 @@ struct dm_unet {
         done_recorded = true;
         return 0;
     }
+    // ElucidatedDiffusion (dm_edm.inc): device step table and the graph of the last Heun step (sigma_next == 0: one
+    // forward); the graph of a full step is `graph` / `gexec` above, keyed by kind = DM_EDM_* + 2
+    float* edm_tab_dev = nullptr;
+    int edm_cap = 0;
+    hipGraph_t edm_last_graph = nullptr;
+    hipGraphExec_t edm_last_gexec = nullptr;
     hipStream_t cap_stream = nullptr;  // capture / replay stream when the caller passes the legacy default stream
     int graph_captures = 0;            // diagnostics (dm_unet_graph_captures)
     void drop_graph() {
         if (gexec) (void)hipGraphExecDestroy(gexec);
         if (graph) (void)hipGraphDestroy(graph);
+        if (edm_last_gexec) (void)hipGraphExecDestroy(edm_last_gexec);
+        if (edm_last_graph) (void)hipGraphDestroy(edm_last_graph);
+        edm_last_gexec = nullptr;
+        edm_last_graph = nullptr;
         gexec = nullptr;
         graph = nullptr;
         gkey = GraphKey{};
@@ -1163,7 +1175,10 @@ static int run_cross(Ctx& c, const CrossLayer& Cr, const float* x, int H, int W,
 // Unet.forward (DD/denoising_diffusion.py:349-390; text hooks DD/denoising_diffusion_text_conditional.py:131-214)
 static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const int64_t* t_dev,
                              const int64_t* step_times, const SamplerState* step_dev, const float* ctx, int ctx_tokens,
-                             float* out_nchw, int B, int H, int W, hipStream_t s, const int32_t* tmask = nullptr) {
+                             float* out_nchw, int B, int H, int W, hipStream_t s, const int32_t* tmask = nullptr,
+                             const float* tf = nullptr, int tf_stride = 0) {
+    // tf: a REAL-valued time instead of t_dev / step_times (ElucidatedDiffusion's c_noise(sigma)): one value per image, or
+    // with step_dev the value tf[step * tf_stride] of the EDM step table for the whole batch
     // tmask: per-image text mask (device int32, B entries, or nullptr = every image as `ctx` says).  Image b is
     // conditioned iff tmask[b] != 0; the others take the model's null path (text_emb = None).  Every row of ctx is
     // read, the masked-out ones included, and their values do not reach the output.
@@ -1178,8 +1193,9 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
     // (not with a text mask: the null rows need the bottleneck)
     const bool dead_bottleneck = text_cross && ctx_tokens == 1 && !cross1_off() && !tmask;
     // the time embedding is one row when the whole batch shares t (samplers), else one row per sample
-    const int Bt = (step_times && !text_concat) ? 1 : B;
-    const int Rt = step_times ? 1 : B;  // rows of the sinusoid / time_mlp
+    const bool shared_t = step_times || (tf && step_dev);
+    const int Bt = (shared_t && !text_concat) ? 1 : B;
+    const int Rt = shared_t ? 1 : B;  // rows of the sinusoid / time_mlp
     const int lsd = cfg.learned_sinusoidal_dim;  // > 0: cat(t, sin(t w 2 pi), cos(t w 2 pi)) of width lsd + 1 (:96-101)
     const int fdim = lsd > 0 ? lsd + 1 : cfg.dim;
     float* e0 = A.alloc((size_t)Rt * fdim);
@@ -1187,7 +1203,11 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
     float* temb = A.alloc((size_t)B * td);
     float* ss = A.alloc((size_t)Bt * u->ss_total);
     if (!A.dry) {
-        if (launch_sinusoid(t_dev, step_times, step_dev, u->freqs, e0, Rt, (lsd > 0 ? lsd : cfg.dim) / 2, s, lsd > 0)) return 1;
+        if (tf) {
+            if (launch_sinusoid_ft(tf, tf_stride, step_dev, u->freqs, e0, Rt, (lsd > 0 ? lsd : cfg.dim) / 2, s, lsd > 0)) return 1;
+        } else if (launch_sinusoid(t_dev, step_times, step_dev, u->freqs, e0, Rt, (lsd > 0 ? lsd : cfg.dim) / 2, s, lsd > 0)) {
+            return 1;
+        }
         if (launch_linear_rows(e0, fdim, u->tw1, u->tb1, e1, td, Rt, fdim, td, 0, 2, s)) return 1;
         if (launch_linear_rows(e1, td, u->tw2, u->tb2, temb, td, Rt, td, td, 0, 0, s)) return 1;
     }
@@ -1434,6 +1454,7 @@ void dm_unet_destroy(dm_unet* u) {
     if (u->state_dev) (void)hipFree(u->state_dev);
     if (u->times_dev) (void)hipFree(u->times_dev);
     if (u->coefs_dev) (void)hipFree(u->coefs_dev);
+    if (u->edm_tab_dev) (void)hipFree(u->edm_tab_dev);
     delete u;
 }
 
@@ -1848,3 +1869,4 @@ int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t eleme
 #include "dm_consumer.inc"
 #include "dm_train.inc"
 #include "dm_train_ops.inc"
+#include "dm_edm.inc"

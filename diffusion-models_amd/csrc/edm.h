@@ -1,0 +1,63 @@
+// ElucidatedDiffusion (Karras et al. "EDM") sampling: launchers of edm.hip.
+// Reference: DD/elucidated_diffusion.py:76-110 (preconditioning), :129-187 (Heun), :189-224 (DPM-Solver++(2M)).
+#pragma once
+
+#include "dm_common.h"
+
+namespace dm {
+
+// Columns of one row of the step table (DM_EDM_COEFS floats, include/dm_hip.h).  Every value is computed by the host
+// the way the reference computes it; the kernels only multiply, add and divide.
+enum EdmCol : int {
+    EDM_CHURN = 0,     // sqrt(sigma_hat^2 - sigma^2), 0 when gamma == 0
+    EDM_S_NOISE = 1,
+    EDM_C_IN = 2,      // preconditioning at sigma_hat (Heun) / sigma (DPM++)
+    EDM_C_NOISE = 3,
+    EDM_C_SKIP = 4,
+    EDM_C_OUT = 5,
+    EDM_SIGMA = 6,     // sigma_hat
+    EDM_DT = 7,        // sigma_next - sigma_hat
+    EDM_C_IN2 = 8,     // preconditioning at sigma_next (Heun); DPM++: a = sigma_fn(t_next) / sigma_fn(t)
+    EDM_C_NOISE2 = 9,  //                                      DPM++: b = expm1(-h)
+    EDM_C_SKIP2 = 10,  //                                      DPM++: g (gamma of the multistep blend)
+    EDM_C_OUT2 = 11,   //                                      DPM++: 1 - g
+    EDM_SIGMA2 = 12,   // sigma_next
+    EDM_HALF_DT = 13,  // 0.5 * (sigma_next - sigma_hat)
+    EDM_NCOLS = 16,
+};
+enum : int { EDM_A = EDM_C_IN2, EDM_B = EDM_C_NOISE2, EDM_G = EDM_C_SKIP2, EDM_OMG = EDM_C_OUT2 };
+
+// Which table row an element reads.  EDM_ROW_STEP: row st->step (sampling loops; st == nullptr: row 0); EDM_ROW_IMAGE: row
+// b of image b (B rows; preconditioned_network_forward on a (B,) sigma); EDM_ROW_FIRST: row 0 whatever st->step says (a
+// stand-alone pass whose state only selects the Philox draw).  n = B * per, per % 4 == 0, 16-byte pointers.
+enum EdmRowMode : int { EDM_ROW_STEP = 0, EDM_ROW_IMAGE = 1, EDM_ROW_FIRST = 2 };
+struct EdmRows {
+    const float* tab;
+    const SamplerState* st;
+    int mode;
+    int64_t per;
+};
+
+// e[r] = [t | sin(t w 2 pi) | cos(t w 2 pi)] (learned) or [sin(t f) | cos(t f)] for a REAL-valued time.
+// st == nullptr: row r reads t[r]; else one row (R == 1) reads t[st->step * t_stride]
+int launch_sinusoid_ft(const float* t, int t_stride, const SamplerState* st, const float* freqs, float* e, int R, int half,
+                       hipStream_t s, bool learned);
+// xhat = x + churn * (S_noise * eps), xin = c_in * xhat.  eps: row `step` of noise (stride noise_step_stride), or the
+// Philox draw step + 1 under st->seed when noise == nullptr; not read at all when churn == 0.  xhat may be nullptr.
+int launch_edm_churn_in(const float* x, const float* noise, int64_t noise_step_stride, EdmRows r, float* xhat, float* xin,
+                        int64_t n, hipStream_t s);
+// D = c_skip xhat + c_out F [clamped]; d = (xhat - D) / sigma_hat; xnext = xhat + dt d; xin2 = c_in' xnext.
+// Every output may be nullptr.
+int launch_edm_euler(const float* xhat, const float* F, EdmRows r, int clamp, float* D_out, float* d_out, float* xnext,
+                     float* xin2, int64_t n, hipStream_t s);
+// D' = c_skip' xnext + c_out' F2 [clamped]; d' = (xnext - D') / sigma_next; out = xhat + half_dt (d + d').  out may be xnext.
+int launch_edm_heun(const float* xhat, const float* d, const float* xnext, const float* F2, EdmRows r, int clamp, float* out,
+                    int64_t n, hipStream_t s);
+// D = c_skip x + c_out F; out = a x - b ((1 - g) D + g d_old); d_old = D.  out may be x.
+int launch_edm_dpmpp(const float* x, const float* F, float* d_old, EdmRows r, float* out, int64_t n, hipStream_t s);
+// out = (clamp(x, -1, 1) + 1) / 2
+int launch_edm_finalize(const float* x, float* out, int64_t n, hipStream_t s);
+// out = scale * x
+int launch_edm_scale(const float* x, float scale, float* out, int64_t n, hipStream_t s);
+
+}  // namespace dm

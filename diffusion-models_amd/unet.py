@@ -423,7 +423,10 @@ class Unet:
         B, Cin, H, W = x.shape
         if Cin != self.cfg.input_channels:
             raise RuntimeError(f"expected {self.cfg.input_channels} input channels, got {Cin}")
-        t = time.to(device=self.device, dtype=torch.int64).reshape(-1)
+        # a real-valued time (ElucidatedDiffusion's c_noise(sigma)) on a learned / random sinusoidal U-Net keeps its
+        # fraction: dm_unet_forward_ft.  Every other call takes the int64 entry it always took.
+        float_time = self.random_or_learned_sinusoidal_cond and torch.is_tensor(time) and time.is_floating_point()
+        t = time.to(device=self.device, dtype=torch.float32 if float_time else torch.int64).reshape(-1)
         if t.numel() == 1 and B > 1:
             t = t.expand(B)  # the reference broadcasts a single time embedding over the batch
         if t.numel() != B:
@@ -432,8 +435,8 @@ class Unet:
         ctx, m = self._ctx(text_emb, B)
         out = torch.empty((B, self.out_dim, H, W), device=self.device, dtype=torch.float32)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.dm_unet_forward(self._handle, _lib.ptr(x), _lib.ptr(t), _lib.ptr(ctx), m,
-                                             _lib.ptr(out), B, H, W, stream))
+        fwd = self._lib.dm_unet_forward_ft if float_time else self._lib.dm_unet_forward
+        _lib.check(fwd(self._handle, _lib.ptr(x), _lib.ptr(t), _lib.ptr(ctx), m, _lib.ptr(out), B, H, W, stream))
         return out
 
     __call__ = forward

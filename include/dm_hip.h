@@ -536,6 +536,70 @@ typedef struct dm_profile_row {
 int dm_profile_enable(int on);
 int dm_profile_read(dm_profile_row* rows, int max_rows, int* n_rows);
 
+/* ---- ElucidatedDiffusion sampling (DD/elucidated_diffusion.py; Karras et al. "EDM") --------------------------------
+ * Unet.forward with a REAL-valued time, one float per image (c_noise(sigma) = 0.25 ln sigma): the handle must have
+ * learned_sinusoidal_dim > 0, the only U-Net ElucidatedDiffusion accepts (:42).  dm_unet_forward keeps its int64 time. */
+int dm_unet_forward_ft(dm_unet* u, const float* x, const float* time, const float* ctx, int ctx_tokens, float* out, int B,
+                       int H, int W, void* stream);
+
+/* ElucidatedDiffusion.sample (Heun, :129-187) and .sample_using_dpmpp (DPM-Solver++(2M), :189-224).  As for dm_sample,
+ * the HOST computes every per-step scalar exactly as the reference does -- the preconditioning terms in fp32 tensor
+ * arithmetic, sigma_hat / sqrt(sigma_hat^2 - sigma^2) / sigma_next - sigma_hat as doubles rounded to fp32 once -- and passes
+ * n_steps rows of DM_EDM_COEFS floats:
+ *   Heun step i:   c[0]=sqrt(sigma_hat^2 - sigma^2) (0 when gamma == 0)   c[1]=S_noise
+ *                  c[2..5]=c_in, c_noise, c_skip, c_out at sigma_hat       c[6]=sigma_hat   c[7]=sigma_next - sigma_hat
+ *                  c[8..11]=c_in, c_noise, c_skip, c_out at sigma_next     c[12]=sigma_next c[13]=0.5*(sigma_next - sigma_hat)
+ *                  c[12] == 0 marks the step that runs one forward only (the reference's last step, :176)
+ *   DPM++ step i:  c[2..5] at sigma_i   c[8]=sigma_fn(t_next)/sigma_fn(t)   c[9]=expm1(-h)   c[10]=gamma   c[11]=1 - gamma
+ *                  (gamma = 0 at the first step and when sigma_next == 0: denoised_d = denoised, :212-213)
+ *   unused entries are 0.
+ *   x_init     (B,C,H,W) N(0,1) noise, draw 0 of the reference; the loop starts from sigma_init * x_init (:151, :201)
+ *   noise      Heun only.  NULL -> device Philox noise (draw i + 1 at step i); else (n_steps, B,C,H,W), row i read by step
+ *              i.  A step whose c[0] == 0 reads neither.  sample_offset as in dm_sample.
+ *   clamp      Heun: clamp every denoised image to [-1, 1] (:107-108); DPM-Solver++ never clamps per step.
+ *   out        (clamp(x, -1, 1) + 1) / 2   (:186-187, :223-224)
+ *   use_graph  a Heun step (two forwards) and the final single-forward step are captured as one hipGraph each, a DPM++
+ *              step as one; cached on the handle per (kind, B, H, W, clamp, noise pointer) like dm_sample's graph. */
+#define DM_EDM_COEFS 16
+#define DM_EDM_HEUN 0
+#define DM_EDM_DPMPP 1
+typedef struct dm_edm_args {
+    int32_t kind;       /* DM_EDM_* */
+    int32_t n_steps;
+    const float* table_host;
+    const float* x_init;
+    const float* noise;
+    uint64_t seed;
+    uint64_t sample_offset;
+    float* out;
+    float sigma_init;
+    int32_t clamp;
+    int32_t B, H, W;
+    int32_t use_graph;
+    void* stream;
+} dm_edm_args;
+int dm_sample_edm(dm_unet* u, const dm_edm_args* args);
+
+/* The elementwise passes of the two loops on their own (tests).  c_host: `rows` table rows in the layout above, rows == 1
+ * (every image) or rows == B (row b for image b: preconditioned_network_forward on a (B,) sigma).  Tensors are B * per
+ * floats, per % 4 == 0, 16-byte aligned.  The table-driven ones wait for the result.
+ *   churn_in:  xhat = x + c[0] * (c[1] * eps); xin = c[2] * xhat.  eps NULL: Philox draw `draw` (>= 1) under `seed`.
+ *              xhat may be NULL.
+ *   euler:     D = c[4] xhat + c[5] F [clamped]; d = (xhat - D) / c[6]; xnext = xhat + c[7] d; xin_next = c[8] xnext.
+ *              Each of the four outputs may be NULL.
+ *   heun:      D' = c[10] xnext + c[11] F2 [clamped]; d' = (xnext - D') / c[12]; out = xhat + c[13] (d + d').
+ *   dpmpp:     D = c[4] x + c[5] F; out = c[8] x - c[9] (c[11] D + c[10] d_old)  (D itself when c[10] == 0); d_old = D.
+ *   finalize:  out = (clamp(x, -1, 1) + 1) / 2 on n floats. */
+int dm_op_edm_churn_in(const float* x, const float* eps, const float* c_host, int rows, uint64_t seed, uint64_t draw,
+                       uint64_t element_offset, float* xhat, float* xin, int B, int64_t per, void* stream);
+int dm_op_edm_euler(const float* xhat, const float* F, const float* c_host, int rows, int clamp, float* D_out, float* d_out,
+                    float* xnext, float* xin_next, int B, int64_t per, void* stream);
+int dm_op_edm_heun(const float* xhat, const float* d, const float* xnext, const float* F2, const float* c_host, int rows,
+                   int clamp, float* out, int B, int64_t per, void* stream);
+int dm_op_edm_dpmpp(const float* x, const float* F, float* d_old, const float* c_host, int rows, float* out, int B,
+                    int64_t per, void* stream);
+int dm_op_edm_finalize(const float* x, float* out, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
