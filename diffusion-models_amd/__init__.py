@@ -23,7 +23,8 @@ from .diffusion import (  # noqa: F401
     TextConditionalDenoisingDiffusion,
     TextConditionalLatentDiffusion,
 )
-from .elucidated import ElucidatedDiffusion, edm_dpmpp_table, edm_heun_table, edm_sigmas  # noqa: F401
+from .elucidated import (ElucidatedDiffusion, edm_dpmpp_table, edm_heun_table, edm_sigmas,  # noqa: F401
+                         edm_train_table)
 from .vae import VQDecoder, VQEncoder, VQModel  # noqa: F401
 from .dist import gather_shards, sample_global, sample_sharded, shard_bounds, shared_seed  # noqa: F401
 from .checkpoint import load_trainer_checkpoint, load_vae_checkpoint  # noqa: F401
@@ -59,6 +60,7 @@ __all__ = [
     "edm_sigmas",
     "edm_heun_table",
     "edm_dpmpp_table",
+    "edm_train_table",
     "synth_state_dict",
     "synth_tensor",
 ]

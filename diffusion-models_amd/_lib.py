@@ -43,6 +43,8 @@ EXPORTS = (
     "dm_profile_enable", "dm_profile_read",
     "dm_unet_forward_ft", "dm_sample_edm",
     "dm_op_edm_churn_in", "dm_op_edm_euler", "dm_op_edm_heun", "dm_op_edm_dpmpp", "dm_op_edm_finalize",
+    "dm_unet_train_enable_ft", "dm_unet_loss_backward_edm",
+    "dm_op_edm_noise_in", "dm_op_edm_loss", "dm_op_sinusoid_ft_bwd",
 )
 
 
@@ -96,6 +98,15 @@ class EdmArgs(C.Structure):
         ("x_init", C.c_void_p), ("noise", C.c_void_p), ("seed", C.c_uint64), ("sample_offset", C.c_uint64),
         ("out", C.c_void_p), ("sigma_init", C.c_float), ("clamp", C.c_int32),
         ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("use_graph", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
+class EdmTrainArgs(C.Structure):
+    """dm_edm_train_args (include/dm_hip.h)."""
+    _fields_ = [
+        ("images", C.c_void_p), ("noise", C.c_void_p), ("coef_host", C.POINTER(C.c_float)), ("coef_stride", C.c_int32),
+        ("loss_scale", C.c_float), ("accumulate", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("loss_out_host", C.POINTER(C.c_float)), ("denoised_out", C.c_void_p), ("stream", C.c_void_p),
     ]
 
 
@@ -212,6 +223,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_edm_heun.argtypes = [fp, fp, fp, fp, C.POINTER(C.c_float), i32, i32, fp, i32, i64, vp]
     lib.dm_op_edm_dpmpp.argtypes = [fp, fp, fp, C.POINTER(C.c_float), i32, fp, i32, i64, vp]
     lib.dm_op_edm_finalize.argtypes = [fp, fp, i64, vp]
+    lib.dm_unet_train_enable_ft.argtypes = [vp, i32]
+    lib.dm_unet_loss_backward_edm.argtypes = [vp, C.POINTER(EdmTrainArgs)]
+    lib.dm_op_edm_noise_in.argtypes = [fp, fp, C.POINTER(C.c_float), i32, fp, fp, fp, i32, i64, vp]
+    lib.dm_op_edm_loss.argtypes = [fp, fp, fp, C.POINTER(C.c_float), C.c_float, fp, fp, C.POINTER(C.c_float), i32, i64, vp]
+    lib.dm_op_sinusoid_ft_bwd.argtypes = [fp, fp, fp, i32, i32, i32, i32, vp]
     lib.dm_profile_read.argtypes = [C.POINTER(ProfileRow), i32, C.POINTER(i32)]
 
 

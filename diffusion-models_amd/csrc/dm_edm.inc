@@ -1,5 +1,5 @@
-// ElucidatedDiffusion on the C ABI: the float-time forward, the two sampling loops and the single-pass entry points
-// (dm_op_edm_*).  Included by dm_api.hip; kernels in edm.hip.
+// ElucidatedDiffusion on the C ABI: the float-time forward, the two sampling loops, the training loss + backward and the
+// single-pass entry points (dm_op_edm_*).  Included by dm_api.hip; kernels in edm.hip.
 
 namespace dm {
 
@@ -206,6 +206,90 @@ static int edm_rows(const float* tab, int rows, int B, int64_t per, EdmRows* out
     return 0;
 }
 
+// ElucidatedDiffusion.forward (DD/elucidated_diffusion.py:234-264) + backward on a handle armed by dm_unet_train_enable_ft:
+// the noise-in pass, the tape forward with c_noise(sigma) as a float time, the weighted loss with its gradient, then the
+// backward pass of the p_losses path, which goes on through time_mlp.1 into the embedding's weights.  Workspace, arena and
+// stream ordering follow loss_backward_impl.
+static int loss_backward_edm_impl(dm_unet* u, const dm_edm_train_args& a) {
+    DM_REQUIRE(a.images && a.noise && a.coef_host, "null argument");
+    DM_REQUIRE(u->train && u->train->ft, "dm_unet_train_enable_ft has not been called");
+    DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
+    const int cstride = a.coef_stride ? a.coef_stride : DM_EDM_COEFS;
+    DM_REQUIRE(a.B > 0 && cstride > EDM_LOSS_W, "coef_host rows hold at least 15 floats (loss_weight is column 14)");
+    DM_REQUIRE(u->cfg.text_mode == DM_TEXT_NONE && u->out_dim == u->cfg.channels && u->cfg.input_channels == u->cfg.channels,
+               "ElucidatedDiffusion needs a U-Net with out_dim == input channels == channels and no text conditioning");
+    const int B = a.B, H = a.H, W = a.W, accumulate = a.accumulate ? 1 : 0;
+    if (check_hw(u, H, W)) return 1;
+    DM_CHECK_HIP(hipSetDevice(u->device));
+    hipStream_t s = static_cast<hipStream_t>(a.stream);
+    TrainState& T = *u->train;
+    if (B > T.edm_cap_B) {
+        DM_CHECK_HIP(hipDeviceSynchronize());
+        if (T.edm_coef_dev) (void)hipFree(T.edm_coef_dev);
+        if (T.tf_dev) (void)hipFree(T.tf_dev);
+        T.edm_coef_dev = nullptr; T.tf_dev = nullptr; T.edm_cap_B = 0;
+        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.edm_coef_dev), (size_t)B * DM_EDM_COEFS * sizeof(float)));
+        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.tf_dev), (size_t)B * sizeof(float)));
+        T.edm_cap_B = B;
+    }
+    const int64_t per = (int64_t)u->cfg.channels * H * W, n = (int64_t)B * per;
+    DM_REQUIRE(per % 4 == 0, "C * H * W must be a multiple of 4");
+    const EdmRows rows{T.edm_coef_dev, nullptr, B > 1 ? EDM_ROW_IMAGE : EDM_ROW_FIRST, per};
+    auto run = [&](Arena& A, Tape& tp) -> int {
+        float* x0 = A.alloc(n);
+        float* noised = A.alloc(n);
+        float* xin = A.alloc(n);
+        float* F = A.alloc(n);
+        float* dF = A.alloc(n);
+        float* part = A.alloc(B);
+        if (!A.dry && launch_edm_noise_in(a.images, a.noise, rows, x0, noised, xin, n, s)) return 1;
+        if (unet_train_forward(u, A, xin, nullptr, F, B, H, W, s, tp, nullptr, 0, nullptr, T.tf_dev)) return 1;
+        if (!A.dry && launch_edm_loss(noised, F, x0, T.edm_coef_dev, dF, a.denoised_out, part, T.loss_dev, B, per, a.loss_scale, s))
+            return 1;
+        return unet_train_backward(u, A, xin, dF, B, H, W, s, tp, accumulate);
+    };
+    try {
+        // (the fourth entry is self_cond on the integer-time path, never negative there)
+        const std::array<long long, 8> key{B, H, W, -1, 0, 0, 0, (a.denoised_out ? 1 : 0) | (T.bucketed ? 2 : 0)};
+        auto known = T.ws_need.find(key);
+        if (known == T.ws_need.end()) {
+            Arena dry;
+            dry.dry = true;
+            Tape tp;
+            if (run(dry, tp)) return 1;
+            known = T.ws_need.emplace(key, dry.off).first;
+        }
+        if (ensure_train_ws(T, known->second)) return 1;
+        if (u->order_after_previous(s)) return 1;
+        // rows as the kernels index them (DM_EDM_COEFS floats), then the B float times the embedding reads
+        T.coef_stage.assign((size_t)B * DM_EDM_COEFS + B, 0.f);
+        const int ncopy = cstride < DM_EDM_COEFS ? cstride : DM_EDM_COEFS;
+        for (int b = 0; b < B; ++b) {
+            std::memcpy(&T.coef_stage[(size_t)b * DM_EDM_COEFS], a.coef_host + (size_t)b * cstride, ncopy * sizeof(float));
+            T.coef_stage[(size_t)B * DM_EDM_COEFS + b] = a.coef_host[(size_t)b * cstride + EDM_C_NOISE];
+        }
+        DM_CHECK_HIP(hipMemcpyAsync(T.edm_coef_dev, T.coef_stage.data(), (size_t)B * DM_EDM_COEFS * sizeof(float),
+                                    hipMemcpyHostToDevice, s));
+        DM_CHECK_HIP(hipMemcpyAsync(T.tf_dev, T.coef_stage.data() + (size_t)B * DM_EDM_COEFS, (size_t)B * sizeof(float),
+                                    hipMemcpyHostToDevice, s));
+        Arena A;
+        A.base = T.ws;
+        A.cap = T.ws_cap;
+        Tape tp;
+        if (run(A, tp)) return 1;
+        T.drop_call += 1;
+        DM_REQUIRE(A.off <= T.ws_cap, "training workspace overrun: the dry run and the real run allocated differently");
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return 1;
+    }
+    if (u->mark_done(s)) return 1;
+    if (!a.loss_out_host) return 0;  // asynchronous form: the loss stays on the device (dm_unet_train_scalar)
+    DM_CHECK_HIP(hipMemcpyAsync(a.loss_out_host, T.loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+    DM_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
 }  // namespace dm
 
 extern "C" {
@@ -298,6 +382,56 @@ int dm_op_edm_dpmpp(const float* x, const float* F, float* d_old, const float* c
 int dm_op_edm_finalize(const float* x, float* out, int64_t n, void* stream) {
     DM_REQUIRE(x && out, "null argument");
     return launch_edm_finalize(x, out, n, static_cast<hipStream_t>(stream));
+}
+
+int dm_unet_train_enable_ft(dm_unet* u, int time_weights_frozen) {
+    DM_REQUIRE(u && u->finalized, "dm_unet_train_enable_ft needs a finalized handle");
+    DM_REQUIRE(u->cfg.learned_sinusoidal_dim > 0,
+               "float-time training is for the learned / random sinusoidal U-Net ElucidatedDiffusion asserts: every other U-Net "
+               "trains through dm_unet_train_enable");
+    DM_REQUIRE(u->cfg.text_mode == DM_TEXT_NONE && u->out_dim == u->cfg.channels && u->cfg.input_channels == u->cfg.channels,
+               "ElucidatedDiffusion needs a U-Net with out_dim == input channels == channels and no text conditioning");
+    if (train_enable_impl(u, true)) return 1;
+    // the handle's configuration does not say which of the two embeddings it holds: the caller does, at the one call that arms it
+    u->train->freqs_frozen = time_weights_frozen != 0;
+    return 0;
+}
+
+int dm_unet_loss_backward_edm(dm_unet* u, const dm_edm_train_args* a) {
+    DM_REQUIRE(u && a, "null argument");
+    return loss_backward_edm_impl(u, *a);
+}
+
+int dm_op_edm_noise_in(const float* images, const float* eps, const float* c_host, int rows, float* x0, float* noised,
+                       float* xin, int B, int64_t per, void* stream) {
+    DM_REQUIRE(images && eps && x0 && noised && xin, "null argument");
+    return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
+        EdmRows r;
+        if (edm_rows(cd, rows, B, per, &r)) return 1;
+        return launch_edm_noise_in(images, eps, r, x0, noised, xin, (int64_t)B * per, s);
+    });
+}
+
+int dm_op_edm_loss(const float* noised, const float* F, const float* x0, const float* c_host, float loss_scale, float* dF,
+                   float* D_out, float* loss_out_host, int B, int64_t per, void* stream) {
+    DM_REQUIRE(noised && F && x0 && dF && loss_out_host && B > 0, "null argument");
+    float* scratch = nullptr;  // [B] per-image partials, then the loss
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&scratch), ((size_t)B + 1) * sizeof(float)));
+    int rc = edm_op(c_host, B, stream, [&](const float* cd, hipStream_t s) {
+        return launch_edm_loss(noised, F, x0, cd, dF, D_out, scratch, scratch + B, B, per, loss_scale, s);
+    });
+    if (!rc && hipMemcpy(loss_out_host, scratch + B, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+        set_error("dm_op_edm_loss: reading the loss back failed");
+        rc = 1;
+    }
+    (void)hipFree(scratch);
+    return rc;
+}
+
+int dm_op_sinusoid_ft_bwd(const float* de0, const float* e0, float* dw, int B, int half, int learned, int accumulate,
+                          void* stream) {
+    DM_REQUIRE(de0 && e0 && dw && B > 0 && half > 0, "bad argument");
+    return launch_sinusoid_ft_bwd(de0, e0, dw, B, half, learned != 0, accumulate, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -110,6 +110,12 @@ struct TrainState {
     int32_t* mask_dev = nullptr;  // [B]: the per-image text mask of a masked call (dm_unet_loss_backward_masked)
     int cap_B = 0;
     float* loss_dev = nullptr;
+    // float-time training (dm_unet_train_enable_ft: ElucidatedDiffusion): the U-Net's time is a float per image and the
+    // embedding's `weights` take a gradient (exact zeros when frozen: random_fourier_features has requires_grad = False)
+    bool ft = false, freqs_frozen = false;
+    float* tf_dev = nullptr;        // [B] c_noise(sigma_b)
+    float* edm_coef_dev = nullptr;  // [B][DM_EDM_COEFS]
+    int edm_cap_B = 0;
     std::vector<float> coef_stage;  // the call's coefficient rows, DM_TRAIN_COEFS floats each
     std::map<std::array<long long, 8>, size_t> ws_need;  // workspace bytes per call shape (measured by a dry run, once)
     ~TrainState() {
@@ -130,6 +136,8 @@ struct TrainState {
         if (t_dev) (void)hipFree(t_dev);
         if (mask_dev) (void)hipFree(mask_dev);
         if (loss_dev) (void)hipFree(loss_dev);
+        if (tf_dev) (void)hipFree(tf_dev);
+        if (edm_coef_dev) (void)hipFree(edm_coef_dev);
     }
 };
 
@@ -270,6 +278,7 @@ struct CrossTape {
 struct Tape {
     float *e0 = nullptr, *h1pre = nullptr, *h1 = nullptr, *temb = nullptr, *ss = nullptr;
     float* tact = nullptr;  // SiLU(tfinal): the input of every ResnetBlock.mlp Linear
+    int e0_dim = 0;         // row width of e0: dim (fixed sinusoid of an integer time) or learned_sinusoidal_dim + 1 (float time)
     // text conditioning: concat variant (text_proj -> cat(t, .) -> text_concat_proj) and the three CrossAttention layers
     float *te0pre = nullptr, *te0 = nullptr, *cat = nullptr;
     const float* tfinal = nullptr;  // what the ResnetBlock.mlp layers see (temb, or the text-concat projection)
@@ -490,7 +499,7 @@ static int t_cross_bwd(TCtx& t, const CrossLayer& Cr, const CrossTape& ct, const
 // Unet.forward (DD/denoising_diffusion.py:349-390) with per-sample times and everything kept for the backward pass
 static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const int64_t* t_dev, float* out_nchw, int B, int H,
                               int W, hipStream_t s, Tape& tp, const float* ctx = nullptr, int ctx_tokens = 0,
-                              const int32_t* mask = nullptr) {
+                              const int32_t* mask = nullptr, const float* tf_dev = nullptr) {
     const dm_unet_cfg& cfg = u->cfg;
     const int td = u->time_dim, n_st = cfg.n_stages;
     const bool text_concat = cfg.text_mode == DM_TEXT_CONCAT && ctx != nullptr;
@@ -499,14 +508,20 @@ static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const i
     tp.ctx_tokens = ctx_tokens;
     tp.mask = ctx ? mask : nullptr;
     TCtx t{u, &A, s, B, nullptr, 0};
-    tp.e0 = A.alloc((size_t)B * cfg.dim);
+    // tf_dev: a float time per image (ElucidatedDiffusion's c_noise(sigma)) through cat(t, sin(t w 2 pi), cos(t w 2 pi))
+    const int fdim = tp.e0_dim = tf_dev ? cfg.learned_sinusoidal_dim + 1 : cfg.dim;
+    tp.e0 = A.alloc((size_t)B * fdim);
     tp.h1pre = A.alloc((size_t)B * td);
     tp.h1 = A.alloc((size_t)B * td);
     tp.temb = A.alloc((size_t)B * td);
     tp.ss = A.alloc((size_t)B * u->ss_total);
     if (!A.dry) {
-        if (launch_sinusoid(t_dev, nullptr, nullptr, u->freqs, tp.e0, B, cfg.dim / 2, s)) return 1;
-        if (launch_linear_rows(tp.e0, cfg.dim, u->tw1, u->tb1, tp.h1pre, td, B, cfg.dim, td, 0, 0, s)) return 1;
+        if (tf_dev) {
+            if (launch_sinusoid_ft(tf_dev, 0, nullptr, u->freqs, tp.e0, B, cfg.learned_sinusoidal_dim / 2, s, true)) return 1;
+        } else if (launch_sinusoid(t_dev, nullptr, nullptr, u->freqs, tp.e0, B, cfg.dim / 2, s)) {
+            return 1;
+        }
+        if (launch_linear_rows(tp.e0, fdim, u->tw1, u->tb1, tp.h1pre, td, B, fdim, td, 0, 0, s)) return 1;
         if (launch_act_fwd(tp.h1pre, tp.h1, (int64_t)B * td, 2, s)) return 1;
         if (launch_linear_rows(tp.h1, td, u->tw2, u->tb2, tp.temb, td, B, td, td, 0, 0, s)) return 1;
     }
@@ -988,6 +1003,8 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     float* dh1pre = A.alloc((size_t)B * td);
     float* cw = A.alloc(colsum_ws_floats(B, std::max(u->ss_total, 2 * td)));
     float* dgw = A.alloc(linear_dgrad_ws_floats(B, td, u->ss_total));
+    const bool ft = u->train->ft;  // the embedding has a parameter: the pass goes on through time_mlp.1 into e0
+    float* de0 = ft ? A.alloc((size_t)B * tp.e0_dim) : nullptr;
     if (A.dry) return 0;
     {   // the per-image / per-channel reductions behind every norm_act_bwd_kernel (dss is complete after them) and every
         // bias / mem_kv column sum of the pass: two launches each
@@ -1058,8 +1075,16 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     if (launch_colsum(dtemb, B, td, ldt, 1, cw, t.grad("time_mlp.3.bias"), t.acc, s)) return 1;
     if (launch_linear_dgrad(dtemb, ldt, u->tw2, dh1, td, B, td, td, nullptr, s)) return 1;
     if (launch_act_bwd(dh1, tp.h1pre, dh1pre, (int64_t)B * td, 2, s)) return 1;
-    if (launch_linear_wgrad(dh1pre, td, tp.e0, cfg.dim, t.grad("time_mlp.1.weight"), B, cfg.dim, td, 0, t.acc, s)) return 1;
+    const int fdim = tp.e0_dim;
+    if (launch_linear_wgrad(dh1pre, td, tp.e0, fdim, t.grad("time_mlp.1.weight"), B, fdim, td, 0, t.acc, s)) return 1;
     if (launch_colsum(dh1pre, B, td, td, 1, cw, t.grad("time_mlp.1.bias"), t.acc, s)) return 1;
+    if (ft) {
+        // fdim = learned_sinusoidal_dim + 1 is odd: launch_linear_dgrad takes its scalar kernel (rows_gemm_nn_ok wants I % 64 == 0)
+        if (launch_linear_dgrad(dh1pre, td, u->tw1, de0, fdim, B, fdim, td, nullptr, s)) return 1;
+        if (launch_sinusoid_ft_bwd(de0, tp.e0, t.grad("time_mlp.0.weights"), B, cfg.learned_sinusoidal_dim / 2,
+                                   !u->train->freqs_frozen, t.acc, s))
+            return 1;
+    }
     return 0;
 }
 
@@ -1406,14 +1431,17 @@ static int grad_phase(const dm_unet* u, const std::string& name) {
     return 2 * n + 2;
 }
 
-int dm_unet_train_enable(dm_unet* u) {
-    DM_REQUIRE(u && u->finalized, "dm_unet_train_enable needs a finalized handle");
-    DM_REQUIRE(u->cfg.learned_sinusoidal_dim == 0,
-               "the random / learned sinusoidal embedding is forward-only: DenoisingDiffusion (hence p_losses) refuses such a U-Net");
+// ft: the handle is armed for float-time training (dm_unet_train_enable_ft) instead of the integer-time p_losses path
+static int train_enable_impl(dm_unet* u, bool ft) {
     DM_CHECK_HIP(hipSetDevice(u->device));
-    if (u->train) return 0;
+    if (u->train) {
+        DM_REQUIRE(u->train->ft == ft, "the handle is already in training mode through the other entry "
+                                       "(dm_unet_train_enable / dm_unet_train_enable_ft)");
+        return 0;
+    }
     u->train = new TrainState();
     TrainState& T = *u->train;
+    T.ft = ft;
     if (build_train(u)) {  // also collects T.conv_weights
         free_train(u);
         return 1;
@@ -1463,6 +1491,13 @@ int dm_unet_train_enable(dm_unet* u) {
     DM_CHECK_HIP(hipMemset(T.grad, 0, off * sizeof(float)));
     DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.loss_dev), 256));
     return 0;
+}
+
+int dm_unet_train_enable(dm_unet* u) {
+    DM_REQUIRE(u && u->finalized, "dm_unet_train_enable needs a finalized handle");
+    DM_REQUIRE(u->cfg.learned_sinusoidal_dim == 0,
+               "the random / learned sinusoidal embedding is forward-only: DenoisingDiffusion (hence p_losses) refuses such a U-Net");
+    return train_enable_impl(u, false);
 }
 
 /* Data-parallel gradient buckets (torch DDP's bucketed all-reduce, DD/denoising_diffusion.py:971-974 via accelerate): with
@@ -1526,6 +1561,8 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a, const int32_t*
     const int cstride = a.coef_stride ? a.coef_stride : 8;
     DM_REQUIRE(u && x_start && t_host && coef_host && noise, "null argument");
     DM_REQUIRE(u->train, "dm_unet_train_enable has not been called");
+    DM_REQUIRE(!u->train->ft, "the handle is armed for float-time training (dm_unet_train_enable_ft): an integer timestep would "
+                              "truncate c_noise(sigma) -- use dm_unet_loss_backward_edm");
     DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
     DM_REQUIRE(B > 0 && objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "bad argument");
     DM_REQUIRE(terms >= 1 && terms <= 3 && cstride >= 8 && cstride <= DM_TRAIN_COEFS && (!(terms & 2) || cstride == DM_TRAIN_COEFS),

@@ -1,4 +1,4 @@
-// ElucidatedDiffusion (Karras et al. "EDM") sampling: launchers of edm.hip.
+// ElucidatedDiffusion (Karras et al. "EDM") sampling and training: launchers of edm.hip.
 // Reference: DD/elucidated_diffusion.py:76-110 (preconditioning), :129-187 (Heun), :189-224 (DPM-Solver++(2M)).
 #pragma once
 
@@ -23,6 +23,7 @@ enum EdmCol : int {
     EDM_C_OUT2 = 11,   //                                      DPM++: 1 - g
     EDM_SIGMA2 = 12,   // sigma_next
     EDM_HALF_DT = 13,  // 0.5 * (sigma_next - sigma_hat)
+    EDM_LOSS_W = 14,   // training rows only: loss_weight(sigma) (:228-229)
     EDM_NCOLS = 16,
 };
 enum : int { EDM_A = EDM_C_IN2, EDM_B = EDM_C_NOISE2, EDM_G = EDM_C_SKIP2, EDM_OMG = EDM_C_OUT2 };
@@ -59,5 +60,18 @@ int launch_edm_dpmpp(const float* x, const float* F, float* d_old, EdmRows r, fl
 int launch_edm_finalize(const float* x, float* out, int64_t n, hipStream_t s);
 // out = scale * x
 int launch_edm_scale(const float* x, float scale, float* out, int64_t n, hipStream_t s);
+
+// Training rows (one per image, EDM_ROW_IMAGE): c_in, c_noise, c_skip, c_out, sigma in their sampling columns, EDM_LOSS_W.
+// x0 = 2 img - 1; noised = x0 + sigma eps; xin = c_in noised
+int launch_edm_noise_in(const float* img, const float* eps, EdmRows r, float* x0, float* noised, float* xin, int64_t n,
+                        hipStream_t s);
+// D = c_skip noised + c_out F; *loss = loss_scale * mean_b(loss_weight_b * mean((D - x0)^2)); dF = d(loss) / dF.
+// tab: B device rows; part: B floats of workspace; D_out may be nullptr.
+int launch_edm_loss(const float* noised, const float* F, const float* x0, const float* tab, float* dF, float* D_out, float* part,
+                    float* loss, int B, int64_t per, float loss_scale, hipStream_t s);
+// dW[k] (+)= sum_b 2 pi t_b (de_sin[b][k] cos[b][k] - de_cos[b][k] sin[b][k]) from the taped e0 = [t | sin | cos] rows of
+// width 2 half + 1; learned == false writes zeros (random_fourier_features)
+int launch_sinusoid_ft_bwd(const float* de0, const float* e0, float* dw, int B, int half, bool learned, int accumulate,
+                           hipStream_t s);
 
 }  // namespace dm

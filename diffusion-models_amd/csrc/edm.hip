@@ -1,5 +1,6 @@
-// ElucidatedDiffusion sampling kernels (gfx950): the elementwise passes of the Heun and DPM-Solver++(2M) loops of
-// DD/elucidated_diffusion.py:129-224 and the real-valued time embedding their U-Net reads.
+// ElucidatedDiffusion kernels (gfx950): the elementwise passes of the Heun and DPM-Solver++(2M) loops of
+// DD/elucidated_diffusion.py:129-224, the real-valued time embedding their U-Net reads, and the training passes of :234-264
+// (noise-in, weighted loss + its gradient, the backward of the learned embedding).
 //
 // The passes are bandwidth-bound: each thread moves 16 bytes per tensor (one dwordx4 load / store), reads every input
 // once and holds no schedule logic -- every per-step scalar comes from the host-built step table (edm.h), rounded to
@@ -154,6 +155,95 @@ __global__ __launch_bounds__(256) void edm_scale_kernel(const float* __restrict_
     st4(out, i, make_float4(scale * v.x, scale * v.y, scale * v.z, scale * v.w));
 }
 
+// ---- training (DD/elucidated_diffusion.py:234-264) ----------------------------------------------------------------
+// :240 (normalize_to_neg_one_to_one), :247 (noised = images + sigma * noise) and the input scaling of :100, per-image rows
+__global__ __launch_bounds__(256) void edm_noise_in_kernel(const float* __restrict__ img, const float* __restrict__ eps,
+                                                           EdmRows r, float* __restrict__ x0, float* __restrict__ noised,
+                                                           float* __restrict__ xin, int64_t n) {
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float* c = edm_row(r, i);
+    const float sigma = c[EDM_SIGMA], c_in = c[EDM_C_IN];
+    const float4 im4 = ld4(img, i), e4 = ld4(eps, i);
+    const float im[4] = {im4.x, im4.y, im4.z, im4.w}, e[4] = {e4.x, e4.y, e4.z, e4.w};
+    float a[4], nz[4], xi[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        a[j] = im[j] * 2.0f - 1.0f;
+        nz[j] = a[j] + sigma * e[j];
+        xi[j] = c_in * nz[j];
+    }
+    st4(x0, i, make_float4(a[0], a[1], a[2], a[3]));
+    st4(noised, i, make_float4(nz[0], nz[1], nz[2], nz[3]));
+    st4(xin, i, make_float4(xi[0], xi[1], xi[2], xi[3]));
+}
+
+// :105 (D = c_skip noised + c_out F) and :259-262: one workgroup per image, part[b] = loss_weight_b * mean((D - x0)^2) with the
+// squares summed in double in a fixed order (no float atomics, as mse_loss_kernel);  dF = d(loss) / dF in the same pass:
+// loss_scale * loss_weight_b * c_out_b * 2 (D - x0) / (B * per)
+__global__ __launch_bounds__(256) void edm_loss_kernel(const float* __restrict__ noised, const float* __restrict__ F,
+                                                       const float* __restrict__ x0, const float* __restrict__ tab,
+                                                       float* __restrict__ dF, float* __restrict__ D_out,
+                                                       float* __restrict__ part, int per, int B, float loss_scale) {
+    __shared__ double red[256];
+    const int b = blockIdx.x;
+    const float* c = tab + (size_t)b * EDM_NCOLS;
+    const float c_skip = c[EDM_C_SKIP], c_out = c[EDM_C_OUT], lw = c[EDM_LOSS_W];
+    const float gscale = (loss_scale * 2.0f * lw / ((float)per * (float)B)) * c_out;
+    const int64_t base = (int64_t)b * per;
+    double s = 0.0;
+    for (int i = threadIdx.x * 4; i < per; i += 256 * 4) {
+        const float4 n4 = ld4(noised, base + i), f4 = ld4(F, base + i), a4 = ld4(x0, base + i);
+        const float nz[4] = {n4.x, n4.y, n4.z, n4.w}, f[4] = {f4.x, f4.y, f4.z, f4.w}, a[4] = {a4.x, a4.y, a4.z, a4.w};
+        float D[4], g[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            D[j] = c_skip * nz[j] + c_out * f[j];
+            const float d = D[j] - a[j];
+            s += (double)d * d;
+            g[j] = d * gscale;
+        }
+        st4(dF, base + i, make_float4(g[0], g[1], g[2], g[3]));
+        if (D_out) st4(D_out, base + i, make_float4(D[0], D[1], D[2], D[3]));
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int m = 128; m > 0; m >>= 1) {
+        if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[b] = (float)(red[0] / per) * lw;
+}
+// :264 (losses.mean()) times loss_scale; image order
+__global__ void edm_loss_mean_kernel(const float* __restrict__ part, int B, float* __restrict__ loss, float loss_scale) {
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) s += part[b];
+    *loss = (float)(s / B) * loss_scale;
+}
+
+// Backward of RandomOrLearnedSinusoidalPosEmb (DD/denoising_diffusion.py:96-101) with respect to its `weights`, from the
+// taped rows e0[b] = [t_b | sin_b | cos_b] -- no trigonometric function is evaluated again:
+//   dW[k] (+)= sum_b (de_sin[b][k] cos[b][k] - de_cos[b][k] sin[b][k]) * 2 pi * t_b,   b in order (one thread per k).
+// learned == 0 (random_fourier_features: requires_grad = False): the slot is exact zeros.
+__global__ void sinusoid_ft_bwd_kernel(const float* __restrict__ de0, const float* __restrict__ e0, float* __restrict__ dw, int B,
+                                       int half, int learned, int accumulate) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= half) return;
+    if (!learned) {
+        dw[k] = 0.0f;
+        return;
+    }
+    const int wdt = 2 * half + 1;
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) {
+        const float* e = e0 + (size_t)b * wdt;
+        const float* d = de0 + (size_t)b * wdt;
+        const float da = d[1 + k] * e[1 + half + k] - d[1 + half + k] * e[1 + k];
+        s += (double)((da * 6.283185307179586f) * e[0]);
+    }
+    dw[k] = accumulate ? dw[k] + (float)s : (float)s;
+}
+
 #pragma clang fp contract(fast)
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -225,6 +315,37 @@ int launch_edm_finalize(const float* x, float* out, int64_t n, hipStream_t s) {
 int launch_edm_scale(const float* x, float scale, float* out, int64_t n, hipStream_t s) {
     EDM_VEC_OK(n, x, out);
     hipLaunchKernelGGL(edm_scale_kernel, grid4(n), dim3(256), 0, s, x, scale, out, n);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_edm_noise_in(const float* img, const float* eps, EdmRows r, float* x0, float* noised, float* xin, int64_t n,
+                        hipStream_t s) {
+    DM_REQUIRE(img && eps && x0 && noised && xin, "edm_noise_in: null tensor");
+    EDM_VEC_OK(n, img, eps, x0, noised, xin);
+    if (rows_ok(r, n)) return 1;
+    hipLaunchKernelGGL(edm_noise_in_kernel, grid4(n), dim3(256), 0, s, img, eps, r, x0, noised, xin, n);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_edm_loss(const float* noised, const float* F, const float* x0, const float* tab, float* dF, float* D_out, float* part,
+                    float* loss, int B, int64_t per, float loss_scale, hipStream_t s) {
+    DM_REQUIRE(noised && F && x0 && tab && dF && part && loss && B > 0, "edm_loss: null tensor");
+    DM_REQUIRE(per > 0 && per % 4 == 0 && per < (int64_t(1) << 30), "edm_loss: C*H*W must be a multiple of 4");
+    EDM_VEC_OK((int64_t)B * per, noised, F, x0, dF, D_out);
+    hipLaunchKernelGGL(edm_loss_kernel, dim3(B), dim3(256), 0, s, noised, F, x0, tab, dF, D_out, part, (int)per, B, loss_scale);
+    DM_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(edm_loss_mean_kernel, dim3(1), dim3(1), 0, s, part, B, loss, loss_scale);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_sinusoid_ft_bwd(const float* de0, const float* e0, float* dw, int B, int half, bool learned, int accumulate,
+                           hipStream_t s) {
+    DM_REQUIRE(de0 && e0 && dw && B > 0 && half > 0, "sinusoid_ft_bwd: bad argument");
+    hipLaunchKernelGGL(sinusoid_ft_bwd_kernel, dim3((half + 63) / 64), dim3(64), 0, s, de0, e0, dw, B, half, learned ? 1 : 0,
+                       accumulate ? 1 : 0);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -3,15 +3,23 @@ Diffusion-Based Generative Models") in front of ``dm_sample_edm`` in libdm_hip.s
 
 Same constructor arguments, method names and ``state_dict`` keys as
   denoising-diffusion-pytorch/denoising_diffusion/elucidated_diffusion.py:22-264
-for sampling: the Heun loop (``sample``) and DPM-Solver++(2M) (``sample_using_dpmpp``).  The per-step scalars are
-computed here the way the reference computes them -- preconditioning terms as fp32 tensor arithmetic, the churn terms as
-Python doubles rounded to fp32 once -- and handed to the library as a step table; the kernels hold no schedule logic.
+for sampling -- the Heun loop (``sample``) and DPM-Solver++(2M) (``sample_using_dpmpp``) -- and for training (``forward``,
+the weighted denoising loss of :228-264 with its backward pass).  The per-step and per-image scalars are computed here
+the way the reference computes them -- preconditioning terms as fp32 tensor arithmetic, the churn terms as Python doubles
+rounded to fp32 once -- and handed to the library as a table; the kernels hold no schedule logic.
 
 Extensions (keyword-only, as on the other samplers): ``noise`` injects a source of N(0,1) draws called in the
 reference's order (the start image, then one draw per Heun step); ``seed`` / ``sample_offset`` select the device Philox
 stream and the index of the call's first sample in a global batch.
 
-Training (``forward``) is not on the HIP path: the library refuses to train a learned-sinusoidal U-Net.
+Training: ``train()`` arms the U-Net through ``dm_unet_train_enable_ft`` (``Unet.train()`` keeps refusing a learned /
+random sinusoidal U-Net: it arms the integer-time ``p_losses`` path, which would truncate ``c_noise(sigma)``);
+``forward(images)`` is then one ``dm_unet_loss_backward_edm`` call -- loss and every parameter gradient, no autograd graph.
+Its keyword-only extensions: ``sigmas`` / ``noise`` inject the two draws (without them sigma comes from torch's global CPU
+generator, drawn first as in the reference, and the noise from the device Philox stream), ``loss_scale`` / ``accumulate``
+are the micro-batch loop of ``Trainer.train``, ``sync=False`` leaves the loss on the device, ``return_denoised`` also
+returns the denoised images.  ``train_step`` / ``EMA`` / ``save_checkpoint`` of train.py take the object as they take a
+``DenoisingDiffusion``.
 """
 from __future__ import annotations
 
@@ -26,6 +34,7 @@ from . import _lib
 COLS = _lib.DM_EDM_COEFS
 # columns of a step-table row (csrc/edm.h)
 CHURN, S_NOISE, C_IN, C_NOISE, C_SKIP, C_OUT, SIGMA, DT, C_IN2, C_NOISE2, C_SKIP2, C_OUT2, SIGMA2, HALF_DT = range(14)
+LOSS_W = 14  # training rows only
 A, B_, G, OMG = C_IN2, C_NOISE2, C_SKIP2, C_OUT2  # DPM-Solver++ reuses the second preconditioning block
 
 
@@ -106,6 +115,23 @@ def edm_dpmpp_table(num_sample_steps, sigma_min=0.002, sigma_max=80, sigma_data=
     return tab
 
 
+def edm_loss_weight(sigma: torch.Tensor, sigma_data=0.5) -> torch.Tensor:
+    """``loss_weight`` (:228-229) of an fp32 sigma tensor."""
+    return (sigma ** 2 + sigma_data ** 2) * (sigma * sigma_data) ** -2
+
+
+def edm_train_table(sigmas: torch.Tensor, sigma_data=0.5) -> torch.Tensor:
+    """(B, DM_EDM_COEFS) fp32 rows of ``forward`` (:234-264), one per image: the preconditioning terms and sigma in their
+    step-table columns, ``loss_weight(sigma)`` in column 14 -- fp32 tensor expressions on the (B,) sigma tensor, as
+    ``preconditioned_network_forward`` and ``loss_weight`` evaluate them."""
+    sig = sigmas.detach().to("cpu", torch.float32).reshape(-1)
+    tab = torch.zeros((sig.numel(), COLS), dtype=torch.float32)
+    tab[:, C_IN], tab[:, C_NOISE], tab[:, C_SKIP], tab[:, C_OUT] = edm_precond(sig, sigma_data)
+    tab[:, SIGMA] = sig
+    tab[:, LOSS_W] = edm_loss_weight(sig, sigma_data)
+    return tab
+
+
 def _default_seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
 
@@ -115,7 +141,7 @@ def _fptr(t: torch.Tensor):
 
 
 class ElucidatedDiffusion:
-    """``ElucidatedDiffusion(net, image_size=...)`` -- drop-in for the reference class, sampling only."""
+    """``ElucidatedDiffusion(net, image_size=...)`` -- drop-in for the reference class: training loss and samplers."""
 
     def __init__(
         self,
@@ -203,11 +229,14 @@ class ElucidatedDiffusion:
         return torch.log(sigma.clamp(min=1e-20)) * 0.25
 
     def loss_weight(self, sigma):
-        return (sigma ** 2 + self.sigma_data ** 2) * (sigma * self.sigma_data) ** -2
+        return edm_loss_weight(sigma, self.sigma_data)
+
+    def _draw_sigmas(self, batch_size):
+        return (self.P_mean + self.P_std * torch.randn((batch_size,))).exp()
 
     def noise_distribution(self, batch_size):
         """:231-232; the (batch_size,) draw comes from torch's global CPU generator."""
-        return (self.P_mean + self.P_std * torch.randn((batch_size,))).exp().to(self.device)
+        return self._draw_sigmas(batch_size).to(self.device)
 
     def sample_schedule(self, num_sample_steps=None):
         n = self.num_sample_steps if num_sample_steps is None else num_sample_steps
@@ -292,9 +321,65 @@ class ElucidatedDiffusion:
         return self._run(_lib.EDM_DPMPP, table, sigma_init, batch_size, False, noise, 0, seed, sample_offset)
 
     # -- training ----------------------------------------------------------------------------------
-    def forward(self, images):
-        raise NotImplementedError("ElucidatedDiffusion.forward is the training loss: the library refuses to train a "
-                                  "learned / random sinusoidal U-Net (Unet.train() raises), so EDM training is not on the "
-                                  "HIP path")
+    def _trainable_net(self):
+        """The library ``Unet`` behind ``net``; anything else (no handle, or a library without the float-time training
+        entry) cannot be trained.  Touches neither a tensor nor the device."""
+        from .unet import Unet
+
+        net = self.net
+        if not isinstance(net, Unet) or getattr(net, "_handle", None) is None or not hasattr(self._lib, "dm_unet_loss_backward_edm"):
+            raise NotImplementedError("ElucidatedDiffusion can train a library Unet only (dm_unet_train_enable_ft arms its "
+                                      f"handle for the float-time training loss); got {type(net).__name__}")
+        return net
+
+    def train(self, mode: bool = True):
+        """``model.train()``: arm the U-Net for float-time training (gradient buffers, input-gradient convolutions; once)."""
+        if mode:
+            net = self._trainable_net()
+            if not net._loaded:
+                raise RuntimeError("load_state_dict() must be called before train()")
+            # random_fourier_features: the reference builds time_mlp.0.weights with requires_grad = False
+            _lib.check(self._lib.dm_unet_train_enable_ft(net._handle, int(bool(net.cfg.random_fourier_features))))
+            if not getattr(net, "_training", False):
+                net.set_dropout_seed(int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
+            net._training = True
+        return self
+
+    def forward(self, images, *, sigmas=None, noise=None, loss_scale=1.0, accumulate=False, sync=True,
+                return_denoised=False):
+        """:234-264: the loss (0-dim CPU tensor; ``sync=False``: a 0-dim device tensor, nothing waited for); the parameter
+        gradients stay on the U-Net (``self.net.grad(name)`` / ``.grads()``).  ``images`` in [0, 1]."""
+        net = self._trainable_net()
+        b, c, h, w = images.shape
+        assert h == self.image_size and w == self.image_size, f"height and width of image must be {self.image_size}"
+        assert c == self.channels, "mismatch of image channels"
+        if not getattr(net, "_training", False):
+            self.train()
+        # the reference's order of draws: sigma (:242), then the noise (:245)
+        sig = self._draw_sigmas(b) if sigmas is None else sigmas.detach().to("cpu", torch.float32).reshape(-1)
+        if sig.numel() != b:
+            raise RuntimeError(f"sigmas has {sig.numel()} entries for a batch of {b}")
+        images = images.to(self.device, torch.float32).contiguous()
+        noise = (noise.to(self.device, torch.float32).contiguous() if noise is not None
+                 else self._randn(images.shape, _default_seed(), 0, 0))
+        if noise.shape != images.shape:
+            raise RuntimeError(f"noise {tuple(noise.shape)} does not match images {tuple(images.shape)}")
+        tab = edm_train_table(sig, self.sigma_data).contiguous()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        loss = C.c_float(0.0)
+        den = torch.empty_like(images) if return_denoised else None
+        a = _lib.EdmTrainArgs()
+        a.images, a.noise, a.coef_host, a.coef_stride = _lib.ptr(images), _lib.ptr(noise), _fptr(tab), COLS
+        a.loss_scale, a.accumulate = float(loss_scale), int(bool(accumulate))
+        a.B, a.H, a.W = b, h, w
+        a.loss_out_host = C.pointer(loss) if sync else None
+        a.denoised_out, a.stream = _lib.ptr(den), stream
+        _lib.check(self._lib.dm_unet_loss_backward_edm(net._handle, C.byref(a)))
+        if sync:
+            val = torch.tensor(loss.value, dtype=torch.float32)
+        else:
+            val = torch.empty((), device=self.device, dtype=torch.float32)
+            _lib.check(self._lib.dm_unet_train_scalar(net._handle, 0, _lib.ptr(val), stream))
+        return (val, den) if return_denoised else val
 
     __call__ = forward

@@ -18,6 +18,14 @@ from typing import Iterable, Optional
 import torch
 
 
+def _unet_of(diffusion):
+    """The U-Net of a diffusion object and its state-dict prefix: ``model`` (DenoisingDiffusion and its variants) or
+    ``net`` (ElucidatedDiffusion)."""
+    if hasattr(diffusion, "model"):
+        return diffusion.model, "model"
+    return diffusion.net, "net"
+
+
 class EMA:
     """``ema = EMA(diffusion, beta=0.995, update_every=10); ema.update(); ema.ema_model.sample(...)``."""
 
@@ -43,7 +51,7 @@ class EMA:
         self.step += 1
         if step % self.update_every != 0:
             return
-        unet = self.online_model.model
+        unet = _unet_of(self.online_model)[0]
         if step <= self.update_after_step or not self.initted:
             unet.ema_update(0.0, copy=True)
             self.initted = self.initted or step > self.update_after_step
@@ -70,16 +78,17 @@ class EMA:
         ``ema_model``, which is then ready to sample."""
         self.initted = bool(sd["initted"]) if "initted" in sd else True
         self.step = int(sd["step"]) if "step" in sd else 1
-        pre = "ema_model.model."
+        online, attr = _unet_of(self.online_model)
+        pre = f"ema_model.{attr}."
         averaged = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
         if not averaged:
             raise KeyError(f"state dict has no '{pre}*' entries")
-        if getattr(self.online_model.model, "_training", False):
+        if getattr(online, "_training", False):
             if self.step > 0:
-                self.online_model.model.load_ema_state_dict(averaged)
+                online.load_ema_state_dict(averaged)
             self._ema_model_step = -1
         else:
-            self._make_ema_model().model.load_state_dict(averaged)
+            _unet_of(self._make_ema_model())[0].load_state_dict(averaged)
             self._ema_model_step = self.step
         return self
 
@@ -92,14 +101,17 @@ class EMA:
 
         d = self.online_model
         if self._ema_model is None:
-            cfg = d.model.cfg
+            online, attr = _unet_of(d)
+            cfg = online.cfg
             unet = Unet(dim=cfg.dim, init_dim=cfg.init_dim, out_dim=cfg.out_dim, dim_mults=cfg.dim_mults, channels=cfg.channels,
                         self_condition=cfg.self_condition, sinusoidal_pos_emb_theta=cfg.sinusoidal_pos_emb_theta,
                         attn_dim_head=cfg.attn_dim_head, attn_heads=cfg.attn_heads, full_attn=cfg.full_attn,
                         text_condition=cfg.text_condition, text_emb_dim=cfg.text_emb_dim, use_cross_attn=cfg.use_cross_attn,
-                        cond_channels=cfg.cond_channels, device=d.device)
+                        cond_channels=cfg.cond_channels, learned_sinusoidal_cond=cfg.learned_sinusoidal_cond,
+                        random_fourier_features=cfg.random_fourier_features,
+                        learned_sinusoidal_dim=cfg.learned_sinusoidal_dim, device=d.device)
             self._ema_model = copy.copy(d)
-            self._ema_model.model = unet
+            setattr(self._ema_model, attr, unet)
         return self._ema_model
 
     @property
@@ -110,17 +122,19 @@ class EMA:
         if self._ema_model_step != self.step:
             if self.step == 0:
                 raise RuntimeError("EMA.update() has not run yet")
-            self._ema_model.model.load_state_dict(d.model.state_dict(ema=True))
+            _unet_of(self._ema_model)[0].load_state_dict(_unet_of(d)[0].state_dict(ema=True))
             self._ema_model_step = self.step
         return self._ema_model
 
 
 def diffusion_state_dict(diffusion, ema: bool = False):
     """``DenoisingDiffusion.state_dict()`` of the reference module: the 13 schedule buffers + ``model.*`` (the online
-    parameters of the device-resident training state, or its EMA copy)."""
+    parameters of the device-resident training state, or its EMA copy).  ``ElucidatedDiffusion.state_dict()`` has no
+    buffers and the prefix ``net.``."""
     out = {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in diffusion.state_dict().items()}
     if ema:
-        out.update({"model." + k: v.cpu() for k, v in diffusion.model.state_dict(ema=True).items()})
+        unet, attr = _unet_of(diffusion)
+        out.update({f"{attr}." + k: v.cpu() for k, v in unet.state_dict(ema=True).items()})
     return out
 
 
@@ -130,7 +144,7 @@ def save_checkpoint(path, diffusion, *, step: int, ema: Optional[EMA] = None, lr
     (``model``: ``DenoisingDiffusion.state_dict()``; ``opt``: ``torch.optim.Adam.state_dict()``; ``ema``:
     ``ema_pytorch.EMA.state_dict()``), so that the reference's ``Trainer.load`` / sampling scripts -- and
     ``load_checkpoint`` below -- read it back.  Tensors are written on the CPU."""
-    opt = diffusion.model.optimizer_state_dict(lr=lr, betas=betas, eps=eps)
+    opt = _unet_of(diffusion)[0].optimizer_state_dict(lr=lr, betas=betas, eps=eps)
     for st in opt["state"].values():
         st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].cpu(), st["exp_avg_sq"].cpu()
     data = {"step": int(step), "model": diffusion_state_dict(diffusion), "opt": opt,
@@ -146,7 +160,7 @@ def load_checkpoint(path, diffusion, *, ema: Optional[EMA] = None):
     data = torch.load(str(path), map_location="cpu", weights_only=True)
     diffusion.load_state_dict(data["model"])
     diffusion.train()
-    hyper = diffusion.model.load_optimizer_state_dict(data["opt"])
+    hyper = _unet_of(diffusion)[0].load_optimizer_state_dict(data["opt"])
     if ema is not None and data.get("ema") is not None:
         ema.load_state_dict(data["ema"])
     return int(data["step"]), hyper
@@ -154,11 +168,12 @@ def load_checkpoint(path, diffusion, *, ema: Optional[EMA] = None):
 
 def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, betas=(0.9, 0.99), eps=1e-8,
                max_grad_norm=1.0, ema: Optional[EMA] = None, t=None, noise=None, group=None, sync=True,
-               timing: Optional[dict] = None, bucketed: Optional[bool] = None, text_mask=None):
+               timing: Optional[dict] = None, bucketed: Optional[bool] = None, text_mask=None, sigmas=None):
     """One iteration of ``Trainer.train`` (:1164-1190).  ``micro_batches``: the ``gradient_accumulate_every`` image batches
     (in [0, 1]) of the iteration; for a text-conditional model a micro-batch may be a pair ``(images, text_emb)``, whose
     captions ``p_losses`` then drops per image with the model's ``cond_drop_prob``.  ``t`` / ``noise`` / ``text_mask``
-    (lists, one entry per micro-batch) inject the random draws for tests.
+    (lists, one entry per micro-batch) inject the random draws for tests.  An ``ElucidatedDiffusion`` takes the same
+    iteration through its ``forward``; its injection lists are ``sigmas`` / ``noise``.
     Under ``torch.distributed`` (one process per GPU, as ``accelerate`` runs the reference's Trainer under DDP) every rank
     computes the gradients of ITS micro-batches and the flat gradient buffer is averaged over the ranks in place (RCCL over
     xGMI) before the optimiser step; every rank then takes the same step.  With more than one rank (``bucketed=True`` forces
@@ -176,7 +191,12 @@ def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, bet
     total = 0.0
     lazy = {} if sync else {"sync": False}  # only the asynchronous form asks the diffusion object for anything new
     parallel = dist.is_available() and dist.is_initialized()  # also at world size 1: the collectives are the same code path
-    unet = diffusion.model
+    unet = _unet_of(diffusion)[0]
+    edm = not hasattr(diffusion, "p_losses")  # ElucidatedDiffusion: the loss is forward(images), the draws sigma and noise
+    if edm and (t is not None or text_mask is not None):
+        raise ValueError("an ElucidatedDiffusion has no timesteps or captions: inject sigmas= / noise=")
+    if sigmas is not None and not edm:
+        raise ValueError("sigmas= is the draw of an ElucidatedDiffusion; this object takes t=")
     # by default on RCCL with more than one rank (gloo stages every collective through pinned host memory: nothing to overlap)
     overlap = parallel and bucketed is not False and hasattr(unet, "grad_buckets") and (
         bucketed or (dist.get_world_size(group) > 1 and dist.get_backend(group) == "nccl"))
@@ -185,6 +205,11 @@ def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, bet
     if text_mask is not None and len(text_mask) != k:
         raise ValueError(f"text_mask has {len(text_mask)} entries for {k} micro-batches")
     for i, data in enumerate(batches):
+        if edm:
+            loss = diffusion(data, sigmas=sigmas[i] if sigmas is not None else None,
+                             noise=noise[i] if noise is not None else None, loss_scale=1.0 / k, accumulate=i > 0, **lazy)
+            total = (total + float(loss)) if sync else (loss if i == 0 else total + loss)
+            continue
         text = {}  # only a micro-batch with captions asks the diffusion object for anything new
         if isinstance(data, (tuple, list)):
             if len(data) != 2:
@@ -229,7 +254,7 @@ def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, bet
         if ev is not None:
             ev[1].record()
             timing.setdefault("allreduce_events", []).append(ev)
-    norm = diffusion.model.optimizer_step(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, **lazy)
+    norm = unet.optimizer_step(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, **lazy)
     if ema is not None:
         ema.update()
     return total, norm

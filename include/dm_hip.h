@@ -536,7 +536,7 @@ typedef struct dm_profile_row {
 int dm_profile_enable(int on);
 int dm_profile_read(dm_profile_row* rows, int max_rows, int* n_rows);
 
-/* ---- ElucidatedDiffusion sampling (DD/elucidated_diffusion.py; Karras et al. "EDM") --------------------------------
+/* ---- ElucidatedDiffusion (DD/elucidated_diffusion.py; Karras et al. "EDM"): sampling, then training ----------------
  * Unet.forward with a REAL-valued time, one float per image (c_noise(sigma) = 0.25 ln sigma): the handle must have
  * learned_sinusoidal_dim > 0, the only U-Net ElucidatedDiffusion accepts (:42).  dm_unet_forward keeps its int64 time. */
 int dm_unet_forward_ft(dm_unet* u, const float* x, const float* time, const float* ctx, int ctx_tokens, float* out, int B,
@@ -599,6 +599,54 @@ int dm_op_edm_heun(const float* xhat, const float* d, const float* xnext, const 
 int dm_op_edm_dpmpp(const float* x, const float* F, float* d_old, const float* c_host, int rows, float* out, int B,
                     int64_t per, void* stream);
 int dm_op_edm_finalize(const float* x, float* out, int64_t n, void* stream);
+
+/* ---- ElucidatedDiffusion training (DD/elucidated_diffusion.py:228-264) ------------------------------------------------
+ * dm_unet_train_enable_ft arms a learned / random sinusoidal U-Net (learned_sinusoidal_dim > 0, no text conditioning,
+ * out_dim == channels) for training with a REAL-valued time: the same gradient buffers, optimiser state and buckets as
+ * dm_unet_train_enable, which keeps refusing such a U-Net -- what it arms is the integer-time p_losses path, and an int64
+ * time would truncate c_noise(sigma).  A handle armed this way is refused by dm_unet_loss_backward*; every other training
+ * entry (dm_unet_optimizer_step, dm_unet_ema_update, dm_unet_get_grad, dm_unet_train_sync, dm_unet_grads_flat, the buckets,
+ * dm_unet_train_scalar) works on it unchanged.  The embedding's parameter time_mlp.0.weights takes a gradient; with
+ * time_weights_frozen != 0 that gradient is exact zeros instead (random_fourier_features: the reference builds the
+ * parameter with requires_grad = False -- the handle's configuration does not say which embedding it holds, so the call
+ * that arms it does), and Adam leaves the parameter bit for bit where it is.  A repeated call updates the flag. */
+int dm_unet_train_enable_ft(dm_unet* u, int time_weights_frozen);
+
+/* One ElucidatedDiffusion.forward (:234-264) + backward:
+ *   x0 = 2 images - 1;  noised = x0 + sigma_b noise;  F = Unet(c_in_b noised, c_noise_b);  D = c_skip_b noised + c_out_b F;
+ *   loss = loss_scale * mean_b( loss_weight_b * mean((D - x0)^2) );  every parameter gradient.
+ * images (in [0, 1]) and noise: (B, C, H, W) device.  coef_host: B rows of coef_stride floats (0: DM_EDM_COEFS) in the
+ * layout of the step table above -- c[2..5] = c_in, c_noise, c_skip, c_out at sigma_b, c[6] = sigma_b -- plus
+ * c[14] = loss_weight(sigma_b); the host computes them in fp32 tensor arithmetic as the reference does.  loss_scale,
+ * accumulate, loss_out_host (NULL: the call only enqueues, see dm_unet_train_scalar) as in dm_unet_loss_backward;
+ * denoised_out (optional, device): D. */
+typedef struct dm_edm_train_args {
+    const float* images;
+    const float* noise;
+    const float* coef_host;
+    int32_t coef_stride;
+    float loss_scale;
+    int32_t accumulate;
+    int32_t B, H, W;
+    float* loss_out_host;
+    float* denoised_out;
+    void* stream;
+} dm_edm_train_args;
+int dm_unet_loss_backward_edm(dm_unet* u, const dm_edm_train_args* args);
+
+/* The three training passes on their own (tests); tensors as for the sampling passes above.
+ *   noise_in:        x0 = 2 images - 1; noised = x0 + c[6] eps; xin = c[2] noised.  rows == 1 or rows == B.
+ *   loss:            c_host holds B rows.  D = c[4] noised + c[5] F;  *loss_out_host = loss_scale * mean_b(c[14] mean((D - x0)^2));
+ *                    dF = loss_scale * c[14] * c[5] * 2 (D - x0) / (B * per);  D_out (optional) = D.
+ *   sinusoid_ft_bwd: e0, de0: (B, 2 half + 1) rows [t | sin | cos] of the float-time embedding and their gradient;
+ *                    dw[k] (+)= sum_b 2 pi t_b (de_sin[b][k] cos[b][k] - de_cos[b][k] sin[b][k]), k < half, from the taped
+ *                    values; learned == 0 writes zeros.  Enqueues only. */
+int dm_op_edm_noise_in(const float* images, const float* eps, const float* c_host, int rows, float* x0, float* noised,
+                       float* xin, int B, int64_t per, void* stream);
+int dm_op_edm_loss(const float* noised, const float* F, const float* x0, const float* c_host, float loss_scale, float* dF,
+                   float* D_out, float* loss_out_host, int B, int64_t per, void* stream);
+int dm_op_sinusoid_ft_bwd(const float* de0, const float* e0, float* dw, int B, int half, int learned, int accumulate,
+                          void* stream);
 
 #ifdef __cplusplus
 }
