@@ -7,6 +7,9 @@
 
 namespace dm {
 
+// max that keeps a NaN, as F.max_pool2d does (fmaxf would drop it)
+__device__ __forceinline__ float pool_max(float acc, float v) { return (v > acc || v != v) ? v : acc; }
+
 // k x k pooling, NHWC.  mode 0: max (padding never wins); 1: average over k*k (count_include_pad = True, the
 // F.avg_pool2d default of torchvision's InceptionA/C/E); 2: average over the valid pixels (count_include_pad = False,
 // pytorch_fid's FIDInceptionA/C/E_1)
@@ -32,10 +35,10 @@ __global__ void pool2d_nhwc_kernel(const float* __restrict__ in, float* __restri
             if (x < 0 || x >= W) continue;
             const f4 v = *reinterpret_cast<const f4*>(in + ((b * H + y) * W + x) * C + 4 * c4);
             if (mode == 0) {
-                acc.x = fmaxf(acc.x, v.x);
-                acc.y = fmaxf(acc.y, v.y);
-                acc.z = fmaxf(acc.z, v.z);
-                acc.w = fmaxf(acc.w, v.w);
+                acc.x = pool_max(acc.x, v.x);
+                acc.y = pool_max(acc.y, v.y);
+                acc.z = pool_max(acc.z, v.z);
+                acc.w = pool_max(acc.w, v.w);
             } else {
                 acc += v;
             }

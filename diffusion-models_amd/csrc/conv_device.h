@@ -291,7 +291,7 @@ __device__ __forceinline__ void rows_epilogue(const ConvParams& p, const RowsEpi
     if (epi & EPI_RELU) {
 #pragma unroll
         for (int j = 0; j < NR; ++j)
-            v[j] = make_f32x4(fmaxf(v[j].x, 0.f), fmaxf(v[j].y, 0.f), fmaxf(v[j].z, 0.f), fmaxf(v[j].w, 0.f));
+            v[j] = make_f32x4(relu_f(v[j].x), relu_f(v[j].y), relu_f(v[j].z), relu_f(v[j].w));
     }
     const gfloat_mptr op = (gfloat_mptr)p.out;
 #pragma unroll

@@ -831,7 +831,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
                     }
                 }
                 if (epi & EPI_SILU) v = v * fast_rcp(1.0f + __expf(-v));
-                if (epi & EPI_RELU) v = fmaxf(v, 0.0f);
+                if (epi & EPI_RELU) v = relu_f(v);
                 if (epi & EPI_RESIDUAL) v += p.residual[pix * p.Cout + co[q]];
                 if (p.out_nchw) {
                     const int b = pixi / HoWo;

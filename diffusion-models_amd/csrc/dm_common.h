@@ -22,6 +22,9 @@ inline int env_int(const char* name, int dflt) {
 // on / off switch: set to any value = on
 inline bool env_flag(const char* name) { return std::getenv(name) != nullptr; }
 
+// ReLU of every epilogue, as a select: fmaxf returns the other operand for a NaN and would turn a NaN activation into 0
+// (torch's relu keeps it)
+__device__ __forceinline__ float relu_f(float v) { return v < 0.0f ? 0.0f : v; }
 
 void set_error(const std::string& msg);
 

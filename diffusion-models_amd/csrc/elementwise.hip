@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void norm_act_kernel(const float* __restrict__
         if (flags & EPI_NORM) v = v * rn * g[c];
         if (flags & EPI_SCALE_SHIFT) v = v * (sp[c] + 1.0f) + sp[C + c];
         if (flags & EPI_SILU) v = silu_f(v);
-        if (flags & EPI_RELU) v = fmaxf(v, 0.0f);
+        if (flags & EPI_RELU) v = relu_f(v);
         if (flags & EPI_RESIDUAL) {
             float r = residual[row * C + c];
             for (int sp2 = 1; sp2 < res_nsplit; ++sp2) r += residual[(size_t)sp2 * res_stride + row * C + c];
@@ -172,10 +172,10 @@ __global__ __launch_bounds__(256) void norm_act_vec_kernel(const float* __restri
             t.w = silu_f(t.w);
         }
         if (flags & EPI_RELU) {
-            t.x = fmaxf(t.x, 0.f);
-            t.y = fmaxf(t.y, 0.f);
-            t.z = fmaxf(t.z, 0.f);
-            t.w = fmaxf(t.w, 0.f);
+            t.x = relu_f(t.x);
+            t.y = relu_f(t.y);
+            t.z = relu_f(t.z);
+            t.w = relu_f(t.w);
         }
         if (flags & EPI_RESIDUAL) {
             const float* rp = residual + row * C + c;

@@ -197,31 +197,38 @@ class InceptionV3:
                                                    _lib.ptr(sh), self._stream()))
         return y
 
-    def _trunk(self, x, want: Sequence[int]):
-        """x NHWC (B, 299, 299, 3) -> {block index: NHWC feature map}."""
+    def _trunk(self, x, want: Sequence[int], taps: Optional[Dict[str, torch.Tensor]] = None):
+        """x NHWC (B, 299, 299, 3) -> {block index: NHWC feature map}.  ``taps`` (tests): a dict that receives the NHWC
+        map after each stem pool (``pool1``, ``pool2``) and after every ``Mixed_*`` block."""
         fid = self.variant == "fid"
         outs = {}
+
+        def tap(name, t):
+            if taps is not None:
+                taps[name] = t
+            return t
+
         x = self._conv("Conv2d_1a_3x3", x)
         x = self._conv("Conv2d_2a_3x3", x)
         x = self._conv("Conv2d_2b_3x3", x)
-        x = self._pool(x, 3, 2, 0, POOL_MAX)
+        x = tap("pool1", self._pool(x, 3, 2, 0, POOL_MAX))
         outs[0] = x
         if max(want) >= 1:
             x = self._conv("Conv2d_3b_1x1", x)
             x = self._conv("Conv2d_4a_3x3", x)
-            x = self._pool(x, 3, 2, 0, POOL_MAX)
+            x = tap("pool2", self._pool(x, 3, 2, 0, POOL_MAX))
             outs[1] = x
         if max(want) >= 2:
             for name in ("Mixed_5b", "Mixed_5c", "Mixed_5d"):
-                x = self._a(name, x)
-            x = self._b("Mixed_6a", x)
+                x = tap(name, self._a(name, x))
+            x = tap("Mixed_6a", self._b("Mixed_6a", x))
             for name in ("Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e"):
-                x = self._c(name, x)
+                x = tap(name, self._c(name, x))
             outs[2] = x
         if max(want) >= 3:
-            x = self._d("Mixed_7a", x)
-            x = self._e("Mixed_7b", x, POOL_AVG_VALID if fid else POOL_AVG)
-            x = self._e("Mixed_7c", x, POOL_MAX if fid else POOL_AVG)
+            x = tap("Mixed_7a", self._d("Mixed_7a", x))
+            x = tap("Mixed_7b", self._e("Mixed_7b", x, POOL_AVG_VALID if fid else POOL_AVG))
+            x = tap("Mixed_7c", self._e("Mixed_7c", x, POOL_MAX if fid else POOL_AVG))
             outs[3] = x
         return outs
 

@@ -18,7 +18,7 @@ models/inception.py; pytorch-fid 0.3.0 inception.py / fid_score.py) independentl
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -92,26 +92,36 @@ def _e(sd, p, x, pool: str):
     return torch.cat([b1, b3, bd, bp], 1)
 
 
-def trunk(sd: SD, x: torch.Tensor, fid: bool) -> torch.Tensor:
-    """x: (B, 3, 299, 299) already normalised -> (B, 2048, 8, 8)."""
+TAPS = ("pool1", "pool2", "Mixed_5b", "Mixed_5c", "Mixed_5d", "Mixed_6a", "Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e",
+        "Mixed_7a", "Mixed_7b", "Mixed_7c")
+
+
+def trunk(sd: SD, x: torch.Tensor, fid: bool, taps: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+    """x: (B, 3, 299, 299) already normalised -> (B, 2048, 8, 8).  Runs in the dtype of ``sd`` and ``x`` (fp64 when both
+    are).  ``taps``: a dict that receives the tensor after each stem pool and after every Mixed_* block (keys: TAPS)."""
+    def tap(name, t):
+        if taps is not None:
+            taps[name] = t
+        return t
+
     x = _bc(sd, "Conv2d_1a_3x3", x, stride=2)
     x = _bc(sd, "Conv2d_2a_3x3", x)
     x = _bc(sd, "Conv2d_2b_3x3", x, padding=1)
-    x = F.max_pool2d(x, kernel_size=3, stride=2)
+    x = tap("pool1", F.max_pool2d(x, kernel_size=3, stride=2))
     x = _bc(sd, "Conv2d_3b_1x1", x)
     x = _bc(sd, "Conv2d_4a_3x3", x)
-    x = F.max_pool2d(x, kernel_size=3, stride=2)
-    x = _a(sd, "Mixed_5b", x, fid)
-    x = _a(sd, "Mixed_5c", x, fid)
-    x = _a(sd, "Mixed_5d", x, fid)
-    x = _b(sd, "Mixed_6a", x)
-    x = _c(sd, "Mixed_6b", x, fid)
-    x = _c(sd, "Mixed_6c", x, fid)
-    x = _c(sd, "Mixed_6d", x, fid)
-    x = _c(sd, "Mixed_6e", x, fid)
-    x = _d(sd, "Mixed_7a", x)
-    x = _e(sd, "Mixed_7b", x, "avg_valid" if fid else "avg")
-    x = _e(sd, "Mixed_7c", x, "max" if fid else "avg")
+    x = tap("pool2", F.max_pool2d(x, kernel_size=3, stride=2))
+    x = tap("Mixed_5b", _a(sd, "Mixed_5b", x, fid))
+    x = tap("Mixed_5c", _a(sd, "Mixed_5c", x, fid))
+    x = tap("Mixed_5d", _a(sd, "Mixed_5d", x, fid))
+    x = tap("Mixed_6a", _b(sd, "Mixed_6a", x))
+    x = tap("Mixed_6b", _c(sd, "Mixed_6b", x, fid))
+    x = tap("Mixed_6c", _c(sd, "Mixed_6c", x, fid))
+    x = tap("Mixed_6d", _c(sd, "Mixed_6d", x, fid))
+    x = tap("Mixed_6e", _c(sd, "Mixed_6e", x, fid))
+    x = tap("Mixed_7a", _d(sd, "Mixed_7a", x))
+    x = tap("Mixed_7b", _e(sd, "Mixed_7b", x, "avg_valid" if fid else "avg"))
+    x = tap("Mixed_7c", _e(sd, "Mixed_7c", x, "max" if fid else "avg"))
     return x
 
 
