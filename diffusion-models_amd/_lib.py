@@ -16,7 +16,7 @@ DM_MAX_STAGES = 8
 DM_COEFS = 8
 DM_EDM_COEFS = 16
 EDM_HEUN, EDM_DPMPP = 0, 1
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 # every symbol include/dm_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -39,7 +39,7 @@ EXPORTS = (
     "dm_unet_train_sync", "dm_unet_check_device_pack",
     "dm_unet_train_dropout", "dm_op_dropout_mask",
     "dm_op_conv2d_bwd", "dm_op_downsample_bwd", "dm_op_block_bwd", "dm_op_rmsnorm_bwd", "dm_op_linear_attention_bwd",
-    "dm_op_attention_bwd",
+    "dm_op_attention_bwd", "dm_op_cross_attention", "dm_op_cross_attention_bwd",
     "dm_profile_enable", "dm_profile_read",
     "dm_unet_forward_ft", "dm_sample_edm",
     "dm_op_edm_churn_in", "dm_op_edm_euler", "dm_op_edm_heun", "dm_op_edm_dpmpp", "dm_op_edm_finalize",
@@ -215,6 +215,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_rmsnorm_bwd.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i32, vp]
     lib.dm_op_linear_attention_bwd.argtypes = [fp] * 15 + [i32] * 6 + [vp]
     lib.dm_op_attention_bwd.argtypes = [fp] * 13 + [i32] * 6 + [vp]
+    lib.dm_op_cross_attention.argtypes = [fp] * 8 + [vp, fp] + [i32] * 7 + [vp]
+    lib.dm_op_cross_attention_bwd.argtypes = [fp] * 8 + [vp] + [fp] * 9 + [i32] * 7 + [vp]
     lib.dm_profile_enable.argtypes = [i32]
     lib.dm_unet_forward_ft.argtypes = [vp, fp, fp, fp, i32, fp, i32, i32, i32, vp]
     lib.dm_sample_edm.argtypes = [vp, C.POINTER(EdmArgs)]

@@ -368,6 +368,16 @@ int launch_linear_attention_core_bwd(const float* qkv, const float* mem_kv, cons
 // Self-attention (Attention :215-229): q, k, v are column blocks of one qkv tensor and 4 learned memory rows come first;
 // cross-attention (DD/denoising_diffusion_text_conditional.py:54-78): k, v are projections of the text context, no memory.
 // ---------------------------------------------------------------------------------------
+// Phase 1 (thread = query) leaves the row statistics m_i, 1 / l_i, D_i; phase 2 (thread = key) forms the same scores and dP
+// again and meets them.  Both must round alike, or P_ij is exp() of a difference that is not the one the statistics were
+// taken over and dP_ij - D_i does not cancel where it should (one key: P = 1, dS = 0 exactly).  Left to the compiler the
+// query side became an fma chain and the key side packed multiplies and adds, and `sc * scale - m` an fma on one side only.
+// So: the dot products are explicit fma chains in d, and the softmax argument is the ROUNDED product minus the maximum.
+__device__ __forceinline__ float score_minus(float sc, float scale, float m) {
+#pragma clang fp contract(off)
+    return sc * scale - m;
+}
+
 struct AttnBwdParams {
     const float *q, *k, *v;      // rows of ldq / ldk floats per token, head h at column h * dh
     const float *mem_k, *mem_v;  // (heads, n_mem, dh) or nullptr
@@ -427,17 +437,17 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
         for (int j = 0; j < nkt; ++j) {
             float sc = 0.f;
 #pragma unroll
-            for (int d = 0; d < DH; ++d) sc += q[d] * Ks[j * (DH + 1) + d];
+            for (int d = 0; d < DH; ++d) sc = fmaf(q[d], Ks[j * (DH + 1) + d], sc);
             m = fmaxf(m, sc * scale);
         }
         for (int j = 0; j < nkt; ++j) {
             float sc = 0.f, dp = 0.f;
 #pragma unroll
             for (int d = 0; d < DH; ++d) {
-                sc += q[d] * Ks[j * (DH + 1) + d];
-                dp += dov[d] * Vs[j * (DH + 1) + d];
+                sc = fmaf(q[d], Ks[j * (DH + 1) + d], sc);
+                dp = fmaf(dov[d], Vs[j * (DH + 1) + d], dp);
             }
-            const float e = __expf(sc * scale - m);
+            const float e = __expf(score_minus(sc, scale, m));
             l += e;
             D += e * dp;
         }
@@ -447,10 +457,10 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
             float sc = 0.f, dp = 0.f;
 #pragma unroll
             for (int d = 0; d < DH; ++d) {
-                sc += q[d] * Ks[j * (DH + 1) + d];
-                dp += dov[d] * Vs[j * (DH + 1) + d];
+                sc = fmaf(q[d], Ks[j * (DH + 1) + d], sc);
+                dp = fmaf(dov[d], Vs[j * (DH + 1) + d], dp);
             }
-            const float dS = __expf(sc * scale - m) * linv * (dp - D);
+            const float dS = __expf(score_minus(sc, scale, m)) * linv * (dp - D);
 #pragma unroll
             for (int d = 0; d < DH; ++d) dq[d] += dS * Ks[j * (DH + 1) + d];
         }
@@ -475,10 +485,10 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
             float sc = 0.f, dp = 0.f;
 #pragma unroll
             for (int d = 0; d < DH; ++d) {
-                sc += Qs[i * (DH + 1) + d] * kk[d];
-                dp += Ds[i * (DH + 1) + d] * vv[d];
+                sc = fmaf(Qs[i * (DH + 1) + d], kk[d], sc);
+                dp = fmaf(Ds[i * (DH + 1) + d], vv[d], dp);
             }
-            const float P = __expf(sc * scale - rm[i]) * rl[i];
+            const float P = __expf(score_minus(sc, scale, rm[i])) * rl[i];
             const float dS = P * (dp - rD[i]);
 #pragma unroll
             for (int d = 0; d < DH; ++d) {
@@ -657,17 +667,17 @@ __global__ __launch_bounds__(64) void attn_bwd_q_tiled_kernel(const AttnBwdParam
                 float sc = 0.f, dp = 0.f;
 #pragma unroll
                 for (int d = 0; d < DH; ++d) {
-                    sc += q[d] * Ks[jj * ATS + d];
-                    dp += dov[d] * Vs[jj * ATS + d];
+                    sc = fmaf(q[d], Ks[jj * ATS + d], sc);
+                    dp = fmaf(dov[d], Vs[jj * ATS + d], dp);
                 }
                 if (pass == 0) {
                     m = fmaxf(m, sc * scale);
                 } else if (pass == 1) {
-                    const float e = __expf(sc * scale - m);
+                    const float e = __expf(score_minus(sc, scale, m));
                     l += e;
                     D += e * dp;
                 } else {
-                    const float dS = __expf(sc * scale - m) * linv * (dp - D);
+                    const float dS = __expf(score_minus(sc, scale, m)) * linv * (dp - D);
 #pragma unroll
                     for (int d = 0; d < DH; ++d) dq[d] += dS * Ks[jj * ATS + d];
                 }
@@ -716,10 +726,10 @@ __global__ __launch_bounds__(64) void attn_bwd_kv_tiled_kernel(const AttnBwdPara
             float sc = 0.f, dp = 0.f;
 #pragma unroll
             for (int d = 0; d < DH; ++d) {
-                sc += Qs[ii * ATS + d] * kk[d];
-                dp += Ds[ii * ATS + d] * vv[d];
+                sc = fmaf(Qs[ii * ATS + d], kk[d], sc);
+                dp = fmaf(Ds[ii * ATS + d], vv[d], dp);
             }
-            const float P = __expf(sc * scale - St[3 * ii]) * St[3 * ii + 1];
+            const float P = __expf(score_minus(sc, scale, St[3 * ii])) * St[3 * ii + 1];
             const float dS = P * (dp - St[3 * ii + 2]);
 #pragma unroll
             for (int d = 0; d < DH; ++d) {

@@ -48,6 +48,27 @@ static int from_nhwc(Arena& A, const float* nhwc, float* nchw, int B, int C, int
     return launch_nhwc_to_nchw(nhwc, nchw, B, C, HW, s);
 }
 
+// one CrossAttention layer "c" on a throw-away handle, packed by build_cross_body as the text-conditional U-Net packs its
+// three; train: gradient slots and the input-gradient layers of to_q / to_out as build_train makes them
+static int cross_op_layer(OpTrain& op, CrossLayer& Cr, const float* w_q, const float* w_k, const float* w_v, const float* w_out,
+                          const float* b_out, const float* out_g, int C, int E, int dim_head, bool train) {
+    const int inner = 4 * dim_head;
+    op.u.cfg.text_emb_dim = E;  // run_cross / t_cross take the context width from the handle
+    if (op.param("c.to_q.weight", w_q, {inner, C}) || op.param("c.to_k.weight", w_k, {inner, E}) ||
+        op.param("c.to_v.weight", w_v, {inner, E}) || op.param("c.to_out.0.weight", w_out, {C, inner}) ||
+        op.param("c.to_out.0.bias", b_out, {C}) || op.param("c.to_out.1.g", out_g, {1, C}))
+        return 1;
+    if (build_cross_body(&op.u, Cr, "c", C)) return 1;
+    if (!train) return 0;
+    if (op.alloc_grads()) return 1;
+    return build_conv_bwd(&op.u, *op.u.train, Cr.q, "c.to_q.weight", 1) ||
+           build_conv_bwd(&op.u, *op.u.train, Cr.out, "c.to_out.0.weight", 1);
+}
+
+static bool cross_op_args_ok(int B, int C, int H, int W, int m, int E, int dim_head) {
+    return B > 0 && C > 0 && H > 0 && W > 0 && m > 0 && E > 0 && (dim_head == 32 || dim_head == 64);
+}
+
 }  // namespace dm
 
 extern "C" {
@@ -269,6 +290,65 @@ int dm_op_attention_bwd(const float* x, const float* norm_g, const float* mem_kv
                         float* d_w_out, float* d_b_out, int B, int C, int H, int W, int heads, int dim_head, void* stream) {
     return attn_bwd_op(true, x, norm_g, mem_kv, w_qkv, w_out, b_out, nullptr, dy, dx, d_norm_g, d_mem_kv, d_w_qkv, d_w_out,
                        d_b_out, nullptr, B, C, H, W, heads, dim_head, stream);
+}
+
+/* CrossAttention (DD/denoising_diffusion_text_conditional.py:54-78) as the text-conditional U-Net runs it: the forward is
+ * run_cross (one-token algebra included), the backward t_cross then t_cross_bwd (always the general path; y_out is its
+ * forward result).  The forward sits here, next to its backward, because both build the layer on an OpTrain handle. */
+int dm_op_cross_attention(const float* x, const float* ctx, const float* w_q, const float* w_k, const float* w_v,
+                          const float* w_out, const float* b_out, const float* out_g, const int32_t* text_mask, float* out,
+                          int B, int C, int H, int W, int m, int E, int dim_head, void* stream) {
+    DM_REQUIRE(x && ctx && w_q && w_k && w_v && w_out && b_out && out_g && out, "null argument");
+    DM_REQUIRE(cross_op_args_ok(B, C, H, W, m, E, dim_head), "cross_attention: positive sizes, dim_head 32 or 64");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&]() -> int {
+        OpTrain op(4, dim_head);
+        CrossLayer Cr;
+        if (cross_op_layer(op, Cr, w_q, w_k, w_v, w_out, b_out, out_g, C, E, dim_head, false)) return 1;
+        return run_op(s, [&](Arena& A) -> int {
+            int e = 0;
+            Ctx c{&op.u, &A, s, B, nullptr, 0};
+            float* a = to_nhwc(A, x, B, C, H * W, s, &e);
+            if (e) return 1;
+            float* y = nullptr;
+            if (run_cross(c, Cr, a, H, W, ctx, m, &y, text_mask)) return 1;
+            return from_nhwc(A, y, out, B, C, H * W, s);
+        });
+    });
+}
+
+int dm_op_cross_attention_bwd(const float* x, const float* ctx, const float* w_q, const float* w_k, const float* w_v,
+                              const float* w_out, const float* b_out, const float* out_g, const int32_t* text_mask,
+                              const float* dy, float* y_out, float* dx, float* d_w_q, float* d_w_k, float* d_w_v,
+                              float* d_w_out, float* d_b_out, float* d_out_g, int B, int C, int H, int W, int m, int E,
+                              int dim_head, void* stream) {
+    DM_REQUIRE(x && ctx && w_q && w_k && w_v && w_out && b_out && out_g && dy && dx, "null argument");
+    DM_REQUIRE(cross_op_args_ok(B, C, H, W, m, E, dim_head), "cross_attention_bwd: positive sizes, dim_head 32 or 64");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&]() -> int {
+        OpTrain op(4, dim_head);
+        CrossLayer Cr;
+        if (cross_op_layer(op, Cr, w_q, w_k, w_v, w_out, b_out, out_g, C, E, dim_head, true)) return 1;
+        return run_op(s, [&](Arena& A) -> int {
+            int e = 0;
+            TCtx t{&op.u, &A, s, B, nullptr, 0};
+            float* a = to_nhwc(A, x, B, C, H * W, s, &e);
+            float* gy = to_nhwc(A, dy, B, C, H * W, s, &e);
+            if (e) return 1;
+            CrossTape ct;
+            if (t_cross(t, Cr, a, H, W, ctx, m, ct, text_mask)) return 1;
+            if (from_nhwc(A, ct.y, y_out, B, C, H * W, s)) return 1;
+            float* d = nullptr;
+            if (t_cross_bwd(t, Cr, ct, gy, H, W, ctx, m, "c", &d, text_mask)) return 1;
+            if (from_nhwc(A, d, dx, B, C, H * W, s)) return 1;
+            if (A.dry) return 0;
+            if (op.out("c.to_q.weight", d_w_q, s) || op.out("c.to_k.weight", d_w_k, s) || op.out("c.to_v.weight", d_w_v, s) ||
+                op.out("c.to_out.0.weight", d_w_out, s) || op.out("c.to_out.0.bias", d_b_out, s) ||
+                op.out("c.to_out.1.g", d_out_g, s))
+                return 1;
+            return 0;
+        });
+    });
 }
 
 }  // extern "C"

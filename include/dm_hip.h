@@ -517,6 +517,20 @@ int dm_op_linear_attention_bwd(const float* x, const float* norm_g, const float*
 int dm_op_attention_bwd(const float* x, const float* norm_g, const float* mem_kv, const float* w_qkv, const float* w_out,
                         const float* b_out, const float* dy, float* dx, float* d_norm_g, float* d_mem_kv, float* d_w_qkv,
                         float* d_w_out, float* d_b_out, int B, int C, int H, int W, int heads, int dim_head, void* stream);
+/* CrossAttention of the text-conditional U-Net (DD/denoising_diffusion_text_conditional.py:54-78), forward and backward,
+ * through the code the models run (4 heads, as there).  x, dy, out, y_out, dx (B, C, H, W); ctx (B, m, E); weights in the
+ * reference layout: w_q (4*dim_head, C), w_k / w_v (4*dim_head, E), w_out (C, 4*dim_head), b_out (C), out_g (C).
+ * text_mask: B device int32 or NULL; image b with text_mask[b] == 0 skips the layer (out = x, dx = dy, no contribution to
+ * any parameter gradient).  The forward takes the one-token algebra at m == 1; the backward call always runs the general
+ * path and returns that path's forward result in y_out (optional).  There is no gradient for ctx. */
+int dm_op_cross_attention(const float* x, const float* ctx, const float* w_q, const float* w_k, const float* w_v,
+                          const float* w_out, const float* b_out, const float* out_g, const int32_t* text_mask, float* out,
+                          int B, int C, int H, int W, int m, int E, int dim_head, void* stream);
+int dm_op_cross_attention_bwd(const float* x, const float* ctx, const float* w_q, const float* w_k, const float* w_v,
+                              const float* w_out, const float* b_out, const float* out_g, const int32_t* text_mask,
+                              const float* dy, float* y_out, float* dx, float* d_w_q, float* d_w_k, float* d_w_v,
+                              float* d_w_out, float* d_b_out, float* d_out_g, int B, int C, int H, int W, int m, int E,
+                              int dim_head, void* stream);
 
 /* ---- measurement (bench.py's roofline leg; not part of the reference surface) -------------
  * While enabled, every convolution / fused-attention launch is bracketed by two HIP events recorded on

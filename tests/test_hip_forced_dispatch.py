@@ -110,6 +110,20 @@ def test_attention_backward_tiled_form_on_every_shape():
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
 
 
+def test_cross_attention_operator_on_the_other_forms():
+    """Every case of test_hip_cross_attention.py, at its own tolerances, on the forms its shapes do not take by default: the
+    tiled attention core and the tiled backward pair on every shape; the thread-per-query backward kernel where the score
+    cache would be used; the general path for one context token (the exact zeros and out == y_out must still hold), the
+    VALU kernels for the context projections and their weight gradients, and no 1x1 GEMM kernel for to_q / to_out."""
+    for extra in (dict(DM_ATTN_TILED="1", DM_ATTN_BWD_TILED="1"), dict(DM_ATTN_BWD_NO_CACHE="1"),
+                  dict(DM_NO_CROSS1="1", DM_NO_SMALL_GEMM="1", DM_NO_PW="1")):
+        env = dict(os.environ, **extra)
+        r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_hip_cross_attention.py"), "-q",
+                            "-x", "-m", "gpu", "-p", "no:cacheprovider"],
+                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (extra, r.stdout[-4000:] + r.stderr[-2000:])
+
+
 def test_training_goldens_grouped_without_winograd():
     """... and the grouped launches with the direct (row-split) 3x3 weight gradient."""
     _run_training(dict(DM_WGRAD_NO_WINO="1"))
