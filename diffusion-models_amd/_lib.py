@@ -16,7 +16,7 @@ DM_MAX_STAGES = 8
 DM_COEFS = 8
 DM_EDM_COEFS = 16
 EDM_HEUN, EDM_DPMPP = 0, 1
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # every symbol include/dm_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -35,6 +35,7 @@ EXPORTS = (
     "dm_op_copy_channels_nhwc", "dm_op_global_avgpool", "dm_op_linear",
     "dm_unet_train_enable", "dm_unet_grad_floats", "dm_unet_grads_flat", "dm_unet_train_buckets", "dm_unet_train_bucket", "dm_unet_get_grad", "dm_unet_loss_backward", "dm_unet_loss_backward_ex", "dm_unet_loss_backward_masked", "dm_op_q_sample", "dm_op_linear_bwd",
     "dm_op_offset_noise", "dm_op_cdist", "dm_op_gather_rows", "dm_op_lincomb", "dm_op_mask_mix",
+    "dm_op_mse_loss", "dm_op_adam_step", "dm_op_ema_lerp",
     "dm_unet_optimizer_step", "dm_unet_train_scalar", "dm_unet_ema_update", "dm_unet_get_param", "dm_unet_set_train_tensor", "dm_unet_adam_step",
     "dm_unet_train_sync", "dm_unet_check_device_pack",
     "dm_unet_train_dropout", "dm_op_dropout_mask",
@@ -191,9 +192,9 @@ def _declare(lib: C.CDLL) -> None:
                                           C.c_float, i32, C.POINTER(C.c_float), fp, i32, i32, i32, vp]
     lib.dm_unet_loss_backward_ex.argtypes = [vp, C.POINTER(TrainArgs)]
     lib.dm_unet_loss_backward_masked.argtypes = [vp, C.POINTER(TrainArgs), C.POINTER(C.c_int32)]
-    lib.dm_unet_optimizer_step.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), vp]
+    lib.dm_unet_optimizer_step.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.POINTER(C.c_float), vp]
     lib.dm_unet_train_scalar.argtypes = [vp, i32, fp, vp]
-    lib.dm_unet_ema_update.argtypes = [vp, C.c_float, i32, vp]
+    lib.dm_unet_ema_update.argtypes = [vp, C.c_double, i32, vp]
     lib.dm_unet_get_param.argtypes = [vp, C.c_char_p, i32, fp, vp]
     lib.dm_unet_set_train_tensor.argtypes = [vp, C.c_char_p, i32, fp, vp]
     lib.dm_unet_adam_step.argtypes = [vp, C.c_longlong]
@@ -208,6 +209,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_mask_mix.argtypes = [fp, fp, fp, fp, i64, vp]
     lib.dm_op_cdist.argtypes = [fp, fp, fp, i32, i32, i64, vp]
     lib.dm_op_gather_rows.argtypes = [fp, C.POINTER(i64), fp, i32, i64, vp]
+    lib.dm_op_mse_loss.argtypes = [fp, fp, fp, fp, C.POINTER(C.c_float), i32, i32, C.c_float, C.c_float, fp, C.POINTER(C.c_float),
+                                   fp, fp, i32, i32, vp]
+    lib.dm_op_adam_step.argtypes = [fp, fp, fp, fp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i32, C.c_float,
+                                    C.POINTER(C.c_float), vp]
+    lib.dm_op_ema_lerp.argtypes = [fp, fp, i64, C.c_double, vp]
     lib.dm_op_linear_bwd.argtypes = [fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, vp]
     lib.dm_op_conv2d_bwd.argtypes = [fp, i32, fp, i32, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.dm_op_downsample_bwd.argtypes = [fp, i32, fp, fp, fp, fp, fp, i32, i32, i32, i32, vp]

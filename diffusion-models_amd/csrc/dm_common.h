@@ -474,7 +474,7 @@ int launch_q_sample(const float* x_start, const float* noise, const float* coef_
 int launch_mse_loss(const float* out, const float* x_start, const float* noise, const float* coef_dev, float* dout,
                     float* part, float* loss, int B, int per_sample, int objective, float loss_scale, hipStream_t s,
                     int terms = 1, const float* xq = nullptr, float* klpart = nullptr, float kl_scale = 0.f);
-int launch_lerp(float* ema, const float* p, int64_t n, float decay, hipStream_t s);
+int launch_lerp(float* ema, const float* p, int64_t n, double decay, hipStream_t s);
 // device mirrors of the host weight packers (pack_kernels.hip)
 int launch_pack_direct(const float* oihw, float* packed, int Cout, int C0, int C1, int KH, int KW, hipStream_t s);
 int launch_fold_taps(const float* oihw, float* w2, int Cout, int Cin, int py, int px, hipStream_t s);
@@ -499,8 +499,8 @@ int launch_s2d_transpose(const float* w, float* out, int Cout, int C, hipStream_
 // table_dev: device array of {long long src_off; float* dst; long long n;}: dst[i] = param[src_off + i]
 int launch_scatter_copy(const float* param, const void* table_dev, int n_entries, long long max_n, hipStream_t s);
 int launch_grad_norm(const float* grads, int64_t n, double* part_ws, float max_norm, float* out2, hipStream_t s);
-int launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, const float* clip2, int64_t n, float lr,
-                    float b1, float b2, float eps, int step, float ema_decay, hipStream_t s);
+int launch_adam(float* p, const float* g, float* m, float* v, const double* coef, int64_t n, double lr, double b1, double b2,
+                double eps, int step, hipStream_t s);
 size_t linattn_bwd_ws_floats(int B, int n, int heads, int dh);
 int launch_linear_attention_core_bwd(const float* qkv, const float* mem_kv, const float* ctx, const float* dout, float* ws,
                                      float* dqkv, float* dmem_part, int B, int n, int heads, int dh, hipStream_t s,

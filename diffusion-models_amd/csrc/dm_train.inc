@@ -1732,7 +1732,7 @@ int dm_unet_train_scalar(dm_unet* u, int which, float* out_dev, void* stream) {
 /* The optimiser step of Trainer.train (DD/denoising_diffusion.py:1006, :1178-1183): clip_grad_norm_(max_grad_norm), Adam
  * on the device-resident master parameters, then every packed weight buffer is rebuilt on the device. */
 static int ensure_adam_state(TrainState& T);
-int dm_unet_optimizer_step(dm_unet* u, float lr, float beta1, float beta2, float eps, float max_grad_norm,
+int dm_unet_optimizer_step(dm_unet* u, double lr, double beta1, double beta2, double eps, float max_grad_norm,
                            float* grad_norm_out_host, void* stream) {
     DM_REQUIRE(u && u->train, "dm_unet_train_enable has not been called");
     DM_CHECK_HIP(hipSetDevice(u->device));
@@ -1744,8 +1744,8 @@ int dm_unet_optimizer_step(dm_unet* u, float lr, float beta1, float beta2, float
         if (u->order_after_previous(s)) return 1;  // the previous call on this handle may have used another stream
         if (launch_grad_norm(T.grad, (int64_t)T.grad_floats, T.norm_ws, max_grad_norm, T.clip2, s)) return 1;
         T.adam_step += 1;
-        if (launch_adam_ema(T.param, T.grad, T.adam_m, T.adam_v, nullptr, T.clip2, (int64_t)T.grad_floats, lr, beta1, beta2, eps,
-                            T.adam_step, 0.f, s))
+        if (launch_adam(T.param, T.grad, T.adam_m, T.adam_v, T.norm_ws, (int64_t)T.grad_floats, lr, beta1, beta2, eps,
+                        (int)T.adam_step, s))
             return 1;
         if (device_repack(u, s)) return 1;
         u->infer_stale = true;  // the fused inference-only packs (attn16, fused LinearAttention) still hold the old values
@@ -1760,9 +1760,9 @@ int dm_unet_optimizer_step(dm_unet* u, float lr, float beta1, float beta2, float
 }
 
 /* ema.update() of ema_pytorch as Trainer uses it (:1190): copy != 0 copies the online parameters into the EMA buffer,
- * else ema = ema * decay + param * (1 - decay).  The decay schedule (update_after_step, update_every, warm-up) is host
- * logic in the Python mirror. */
-int dm_unet_ema_update(dm_unet* u, float decay, int copy, void* stream) {
+ * else ema.lerp_(param, 1 - decay) with the weight formed in double.  The decay schedule (update_after_step, update_every,
+ * warm-up) is host logic in the Python mirror. */
+int dm_unet_ema_update(dm_unet* u, double decay, int copy, void* stream) {
     DM_REQUIRE(u && u->train, "dm_unet_train_enable has not been called");
     DM_CHECK_HIP(hipSetDevice(u->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1978,16 +1978,17 @@ int dm_op_dropout_mask(float* out, int64_t n, float p, uint64_t seed, uint64_t c
 // Per-call coefficient tables of the stand-alone elementwise ops: one grow-only device buffer per (host thread, device), on
 // the device the data lives on (the ops take no handle: the device comes from the data pointer).  The caller synchronises
 // the stream before it returns, so the buffer is free again for the thread's next call.
-static int stage_coefs(const void* data_dev, const float* host, size_t n, hipStream_t s, float** out) {
+// `extra`: floats of device scratch behind the table (per-sample partial sums, a scalar result)
+static int stage_coefs(const void* data_dev, const float* host, size_t n, hipStream_t s, float** out, size_t extra = 0) {
     hipPointerAttribute_t at{};
     DM_CHECK_HIP(hipPointerGetAttributes(&at, data_dev));
     DM_CHECK_HIP(hipSetDevice(at.device));
     thread_local std::map<int, std::pair<float*, size_t>> scratch;
     auto& sc = scratch[at.device];
-    if (sc.second < n) {
+    if (sc.second < n + extra) {
         if (sc.first) (void)hipFree(sc.first);
         sc = {nullptr, 0};
-        const size_t cap = std::max<size_t>(n, 4096);
+        const size_t cap = std::max<size_t>(n + extra, 4096);
         DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&sc.first), cap * sizeof(float)));
         sc.second = cap;
     }
@@ -2046,6 +2047,77 @@ int dm_op_gather_rows(const float* src, const int64_t* idx_host, float* dst, int
                                     hipMemcpyDeviceToDevice, s));
     }
     return 0;
+}
+
+/* The DDPM loss kernel on its own (p_losses :864-897 after the U-Net): the weighted MSE (terms & 1) and / or the hybrid KL
+ * term (terms & 2), the gradient with respect to the model output, and the per-sample parts.  The factor of the KL term is
+ * kl_weight / (n_pos + 1e-8) in fp32, n_pos = the number of rows with t > 0 (coef[b][3]), as the reference forms
+ * kl / (mask.sum() + 1e-8).  The training call does not form it: dm_train_args.kl_scale arrives from the caller, which is
+ * hybrid_kl_scale() in diffusion.py.  The two must stay the same fp32 expression;
+ * test_mse_loss_kl_factor_is_the_one_training_passes compares them bit for bit. */
+static float hybrid_kl_scale(float kl_weight, const float* coef_host, int B) {
+    float n_pos = 0.f;
+    for (int b = 0; b < B; ++b) n_pos += coef_host[(size_t)b * DM_TRAIN_COEFS + 3];
+    return kl_weight / (n_pos + 1e-8f);
+}
+int dm_op_mse_loss(const float* out, const float* x_start, const float* noise, const float* xq, const float* coef_host,
+                   int objective, int terms, float loss_scale, float kl_weight, float* dout, float* loss_out_host,
+                   float* part_out, float* klpart_out, int B, int per_sample, void* stream) {
+    DM_REQUIRE(out && x_start && noise && coef_host && dout && loss_out_host && B > 0 && per_sample > 0, "bad argument");
+    DM_REQUIRE(objective >= 0 && objective <= 2 && terms >= 1 && terms <= 3 && (!(terms & 2) || xq), "mse_loss: objective / terms");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&]() -> int {
+        const size_t nc = (size_t)B * DM_TRAIN_COEFS;
+        float* cd = nullptr;
+        if (stage_coefs(dout, coef_host, nc, s, &cd, 2 * (size_t)B + 1)) return 1;
+        float *part = cd + nc, *klpart = part + B, *loss = klpart + B;
+        const float kl_scale = (terms & 2) ? hybrid_kl_scale(kl_weight, coef_host, B) : 0.f;
+        int rc = launch_mse_loss(out, x_start, noise, cd, dout, part, loss, B, per_sample, objective, loss_scale, s, terms, xq,
+                                 klpart, kl_scale);
+        // from here on the stream may hold work on the scratch: every path goes through finish_op, which synchronises
+        auto copy = [&](void* dst, const float* src, size_t floats, hipMemcpyKind kind) {
+            const hipError_t e = rc ? hipSuccess : hipMemcpyAsync(dst, src, floats * sizeof(float), kind, s);
+            if (e != hipSuccess) {
+                set_error(std::string("mse_loss: copying a result failed: ") + hipGetErrorString(e));
+                rc = 1;
+            }
+        };
+        copy(loss_out_host, loss, 1, hipMemcpyDeviceToHost);
+        if (part_out) copy(part_out, part, (size_t)B, hipMemcpyDeviceToDevice);
+        if (klpart_out && (terms & 2)) copy(klpart_out, klpart, (size_t)B, hipMemcpyDeviceToDevice);
+        return finish_op(rc, s);
+    });
+}
+
+/* clip_grad_norm_(max_grad_norm) + one torch.optim.Adam step (the `step`-th) on flat device buffers: what
+ * dm_unet_optimizer_step runs on the handle's parameters.  norm_coef_out_host (optional): the total gradient norm before
+ * clipping and the clip coefficient. */
+int dm_op_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                    int step, float max_grad_norm, float* norm_coef_out_host, void* stream) {
+    DM_REQUIRE(p && g && m && v && n > 0 && step >= 1, "bad argument");
+    DM_REQUIRE((reinterpret_cast<uintptr_t>(g) & 15) == 0, "adam_step: the gradient buffer must be 16-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&]() -> int {
+        double* ws = nullptr;  // 1024 partial sums, then (norm, coefficient)
+        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ws), 1024 * sizeof(double) + 2 * sizeof(float)));
+        float* clip2 = reinterpret_cast<float*>(ws + 1024);
+        int rc = launch_grad_norm(g, n, ws, max_grad_norm, clip2, s) ||
+                 launch_adam(p, g, m, v, ws, n, lr, beta1, beta2, eps, step, s);
+        if (!rc && norm_coef_out_host &&
+            hipMemcpyAsync(norm_coef_out_host, clip2, 2 * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess) {
+            set_error("adam_step: copying the norm failed");
+            rc = 1;
+        }
+        rc = finish_op(rc, s);
+        (void)hipFree(ws);
+        return rc;
+    });
+}
+
+/* ema.lerp_(online, 1 - decay) on flat device buffers (what dm_unet_ema_update runs) */
+int dm_op_ema_lerp(float* ema, const float* p, int64_t n, double decay, void* stream) {
+    DM_REQUIRE(ema && p && n > 0, "bad argument");
+    return guarded([&]() -> int { return launch_lerp(ema, p, n, decay, static_cast<hipStream_t>(stream)); });
 }
 
 }  // extern "C"

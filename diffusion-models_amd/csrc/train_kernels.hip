@@ -5,6 +5,7 @@
 #include "conv_device.h"
 
 #include <algorithm>
+#include <cmath>
 
 namespace dm {
 
@@ -1099,7 +1100,7 @@ int launch_pred_x_start(const float* x, const float* out, const float* coef_dev,
 //   kl = 0.5 (plv - mlv + (exp(mlv) + (model_mean - posterior_mean)^2) / posterior_variance - 1), mlv = plv =
 //   posterior_log_variance_clipped[t];  klpart[b] = mean(kl) * [t_b > 0];  loss += kl_weight * sum_b klpart[b] / (n_pos + 1e-8)
 // -- including the division by posterior_variance[t] = 0 at t = 0 that the mask multiplies afterwards (inf * 0): a batch that
-// holds a t = 0 sample has a NaN loss and NaN gradients in the reference, and here.
+// holds a t = 0 sample has a NaN loss and, inside the clamp, NaN gradients in the reference, and here.
 // coef[b]: [8] posterior_mean_coef1, [9] posterior_mean_coef2, [10] posterior_variance, [11] posterior_log_variance_clipped,
 // [3] 1 if t_b > 0 else 0.  xq: the q_sample output the U-Net saw (its first C channels).
 __global__ void mse_loss_kernel(const float* __restrict__ out, const float* __restrict__ x_start, const float* __restrict__ noise,
@@ -1139,9 +1140,10 @@ __global__ void mse_loss_kernel(const float* __restrict__ out, const float* __re
             const float diff = mm - pm;
             const float kl = 0.5f * ((c[11] - c[11]) + (emlv + diff * diff) / c[10] - 1.0f);
             sk += (double)kl;
-            // 0.5 * 2 diff / pv * coef1 * [inside] * dx0, then the chain of means; formed in the reference's order so that
-            // t = 0 (pv = 0, mask 0) yields 0 * inf = NaN as autograd does
-            const float gk = kscale * (diff / c[10]) * (inside ? c[8] * dx0 : 0.0f);
+            // 0.5 * 2 diff / pv * coef1 * dx0 inside the clamp, then the chain of means; formed in the reference's order so
+            // that t = 0 (pv = 0, mask 0) yields 0 * inf = NaN as autograd does.  Outside the clamp the gradient is 0 even
+            // then: clamp's backward selects (where), it does not multiply
+            const float gk = inside ? kscale * (diff / c[10]) * (c[8] * dx0) : 0.0f;
             g = (terms & 1) ? g + gk : gk;
         }
         dout[k] = g;
@@ -1189,8 +1191,14 @@ int launch_mse_loss(const float* out, const float* x_start, const float* noise, 
 // ---------------------------------------------------------------------------------------
 // Optimiser step of the caller of record (Trainer: Adam(lr, betas = (0.9, 0.99)) after clip_grad_norm_(1.0), then
 // ema.update(), DD/denoising_diffusion.py:1006,1180-1190).  One fused pass over a flat parameter tensor:
-//   g = grad * clip;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= lr * (m / bc1) / (sqrt(v / bc2) + eps)
-//   ema = ema * decay + p * (1 - decay)   (when ema != nullptr)
+//   g = grad * clip;  m = m + (1-b1) (g - m);  v = v b2 + (1-b2) g g;  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+// The state is fp32; the step itself is evaluated in double -- the host scalars (1-b, the bias corrections bc = 1 - b^step,
+// lr / bc1, sqrt(bc2), formed from the caller's double hyper-parameters as torch forms them from Python floats), the clip
+// coefficient, and the element arithmetic -- and m, v, p are rounded to float once each.  Every stored value is then the
+// float nearest to what torch.optim.Adam gives in fp64 on the same fp32 state, so no fp32 evaluation order is closer, on
+// any element.  (In float, 1.0f - 0.999f is 1.0000467e-3 and powf(0.999f, 1000) is 1.3e-5 off: far above the rounding of
+// the step.)  The fp32 kernel it replaces already divided and took the root with IEEE rounding: 109 instructions then, 104
+// now, about 50 of them fp64.  Its time against that kernel has not been measured.
 // ---------------------------------------------------------------------------------------
 __global__ void sumsq_partial_kernel(const float* __restrict__ x, int64_t n, double* __restrict__ part) {
     __shared__ double red[256];
@@ -1212,7 +1220,9 @@ __global__ void sumsq_partial_kernel(const float* __restrict__ x, int64_t n, dou
 // total_norm = sqrt(sum); clip coefficient = min(1, max_norm / (total_norm + 1e-6))  (torch.nn.utils.clip_grad_norm_)
 // One wave: lane l adds the partial sums l, l + 64, ... in order, the 64 lane sums meet in a fixed tree (a single thread
 // walking 1024 dependent loads took 53 us).
-__global__ __launch_bounds__(64) void clip_coef_kernel(const double* __restrict__ part, int nparts, float max_norm,
+// out2 = (norm, coefficient) as floats for the caller; part[0] receives the coefficient in double for adam_kernel (every
+// partial sum has been read by then).
+__global__ __launch_bounds__(64) void clip_coef_kernel(double* __restrict__ part, int nparts, float max_norm,
                                                        float* __restrict__ out2) {
     __shared__ double red[64];
     double s = 0.0;
@@ -1224,9 +1234,14 @@ __global__ __launch_bounds__(64) void clip_coef_kernel(const double* __restrict_
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const float norm = (float)sqrt(red[0]);
-        out2[0] = norm;
-        out2[1] = max_norm > 0.f ? fminf(1.0f, max_norm / (norm + 1e-6f)) : 1.0f;
+        const double norm = sqrt(red[0]);
+        // clamp(max_norm / (norm + 1e-6), max = 1.0) keeps a NaN norm (fmin alone would return 1): one NaN gradient makes
+        // every clipped gradient NaN, as clip_grad_norm_ does
+        const double c = (double)max_norm / (norm + 1e-6);
+        const double coef = max_norm > 0.f ? (c != c ? c : fmin(1.0, c)) : 1.0;
+        out2[0] = (float)norm;
+        out2[1] = (float)coef;
+        part[0] = coef;
     }
 }
 int launch_grad_norm(const float* grads, int64_t n, double* part_ws /* 1024 doubles */, float max_norm, float* out2,
@@ -1238,37 +1253,44 @@ int launch_grad_norm(const float* grads, int64_t n, double* part_ws /* 1024 doub
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
-__global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                float* __restrict__ ema, const float* __restrict__ clip2, int64_t n, float lr, float b1, float b2,
-                                float eps, float bc1, float bc2, float ema_decay) {
+// Tensor.lerp_ as torch evaluates it: one fused multiply-add on start + w (end - start), or on end - (1 - w) (end - start)
+// from |w| >= 0.5 on.  w is the weight the host formed in double and rounded to float.
+__device__ __forceinline__ float lerp_torch(float start, float end, float w) {
+#pragma clang fp contract(off)
+    const bool small = fabsf(w) < 0.5f;
+    return fmaf(small ? w : w - 1.0f, end - start, small ? start : end);
+}
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                            const double* __restrict__ coef, int64_t n, double w1, double b2, double w2, double step_size,
+                            double bc2_sqrt, double eps) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float gi = g[i] * (clip2 ? clip2[1] : 1.0f);
-    const float mi = b1 * m[i] + (1.0f - b1) * gi;
-    const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    const float pi = p[i] - lr * (mi / bc1) / (sqrtf(vi / bc2) + eps);
-    p[i] = pi;
-    if (ema) ema[i] = ema[i] * ema_decay + pi * (1.0f - ema_decay);
+    const double gi = (double)g[i] * (coef ? coef[0] : 1.0);
+    const double m0 = m[i];
+    const double mi = m0 + w1 * (gi - m0);
+    const double vi = (double)v[i] * b2 + w2 * gi * gi;
+    m[i] = (float)mi;
+    v[i] = (float)vi;
+    p[i] = (float)((double)p[i] - step_size * mi / (sqrt(vi) / bc2_sqrt + eps));
 }
-// ema = ema * decay + p * (1 - decay)   (ema_pytorch: ema.lerp_(online, 1 - decay))
-__global__ void lerp_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n, float decay) {
+// ema.lerp_(online, 1 - decay) of ema_pytorch; weight = float(1 - decay), the difference taken in double by the caller
+// (1.0f - 0.9999f is 1.00017e-4: 1.7e-4 of every increment)
+__global__ void lerp_kernel(float* __restrict__ ema, const float* __restrict__ p, int64_t n, float weight) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float e = ema[i];
-    ema[i] = e + (p[i] - e) * (1.0f - decay);
+    ema[i] = lerp_torch(ema[i], p[i], weight);
 }
-int launch_lerp(float* ema, const float* p, int64_t n, float decay, hipStream_t s) {
-    hipLaunchKernelGGL(lerp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ema, p, n, decay);
+int launch_lerp(float* ema, const float* p, int64_t n, double decay, hipStream_t s) {
+    hipLaunchKernelGGL(lerp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ema, p, n, (float)(1.0 - decay));
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
-int launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, const float* clip2, int64_t n, float lr,
-                    float b1, float b2, float eps, int step, float ema_decay, hipStream_t s) {
-    const float bc1 = 1.0f - powf(b1, (float)step), bc2 = 1.0f - powf(b2, (float)step);
-    hipLaunchKernelGGL(adam_ema_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, ema, clip2, n, lr, b1,
-                       b2, eps, bc1, bc2, ema_decay);
+// coef: the double clip coefficient launch_grad_norm left in part_ws[0]; nullptr: no clipping
+int launch_adam(float* p, const float* g, float* m, float* v, const double* coef, int64_t n, double lr, double b1, double b2,
+                double eps, int step, hipStream_t s) {
+    const double bc1 = 1.0 - std::pow(b1, (double)step), bc2 = 1.0 - std::pow(b2, (double)step);
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, coef, n, 1.0 - b1, b2,
+                       1.0 - b2, lr / bc1, std::sqrt(bc2), eps);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }

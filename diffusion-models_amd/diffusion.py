@@ -69,6 +69,14 @@ def _drop_prob(p) -> float:
     return float(p)
 
 
+def hybrid_kl_scale(t_cpu: torch.Tensor, kl_weight: float = 0.001) -> float:
+    """The factor of the hybrid loss's KL term, ``kl_weight / (mask.sum() + 1e-8)`` with ``mask = t > 0``, in fp32 as the
+    reference forms it (:893-895).  ``dm_unet_loss_backward`` receives it as ``kl_scale``; ``dm_op_mse_loss`` forms the same
+    expression in C (``hybrid_kl_scale`` in csrc/dm_train.inc) -- keep the two alike, a test compares them bit for bit."""
+    mask_sum = (t_cpu > 0).float().sum()
+    return float(torch.tensor(kl_weight, dtype=torch.float32) / (mask_sum + 1e-8))
+
+
 class DenoisingDiffusion:
     def __init__(
         self,
@@ -401,8 +409,7 @@ class DenoisingDiffusion:
                 # conditional.py:295): its 6-channel U-Net then receives 3 channels and raises
                 raise NotImplementedError("hybrid_loss with an image condition fails in the reference (p_mean_variance is "
                                           "called without cond); not reproduced")
-            mask_sum = (t_cpu > 0).float().sum()  # fp32, as the reference forms kl / (mask.sum() + 1e-8), :893-895
-            a.kl_scale = float(torch.tensor(0.001, dtype=torch.float32) / (mask_sum + 1e-8))
+            a.kl_scale = hybrid_kl_scale(t_cpu)
             a.loss_terms = 3 if float(getattr(self.model, "dropout", 0.0) or 0.0) == 0.0 else 1
         _lib.check(backward())
         if self.hybrid_loss and a.loss_terms == 1:

@@ -270,7 +270,8 @@ class Unet:
         return out
 
     def ema_update(self, decay: float, copy: bool = False):
-        """``ema = ema * decay + online * (1 - decay)`` (or a copy) on the device-resident EMA parameters."""
+        """``ema.lerp_(online, 1 - decay)`` (or a copy) on the device-resident EMA parameters; the weight ``1 - decay`` is
+        formed in double, as ema_pytorch's Python float is."""
         stream = torch.cuda.current_stream(self.device).cuda_stream
         _lib.check(self._lib.dm_unet_ema_update(self._handle, float(decay), int(bool(copy)), stream))
 

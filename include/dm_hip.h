@@ -438,7 +438,10 @@ int dm_unet_loss_backward_masked(dm_unet* u, const dm_train_args* a, const int32
  * kernels read is rebuilt on the device (pack_kernels.hip, bit-identical to the host packers).
  *   dm_unet_optimizer_step: clip_grad_norm_(max_grad_norm; <= 0: off), Adam(lr, (beta1, beta2), eps) step; the total
  *                           gradient norm (before clipping) goes to grad_norm_out_host when given.
- *   dm_unet_ema_update:     copy != 0: ema <- online;  else ema <- ema * decay + online * (1 - decay)
+ *                           lr, the betas and eps are doubles, as torch's Python floats are; the step is evaluated in
+ *                           double on the fp32 state and m, v, p are rounded to float once each.  A NaN
+ *                           gradient makes the norm, the coefficient and with max_grad_norm > 0 every parameter NaN.
+ *   dm_unet_ema_update:     copy != 0: ema <- online;  else ema.lerp_(online, 1 - decay), the weight formed in double
  *   dm_unet_get_param:      one tensor of the online parameters (which = 0), the EMA copy (1) or Adam's exp_avg (2) /
  *                           exp_avg_sq (3) into a device buffer -- what Trainer.save (:1100-1113) writes as 'model' / 'ema' /
  *                           'opt'
@@ -448,14 +451,14 @@ int dm_unet_loss_backward_masked(dm_unet* u, const dm_train_args* a, const int32
  *   dm_unet_train_sync:     device -> host copies + dm_unet_refresh, after which the handle samples with the trained weights
  *                           (the sampling entry points refuse to run on stale fused packs until then)
  *   dm_unet_check_device_pack: self-check, number of packed buffers whose device packer differs from the host packer */
-int dm_unet_optimizer_step(dm_unet* u, float lr, float beta1, float beta2, float eps, float max_grad_norm,
+int dm_unet_optimizer_step(dm_unet* u, double lr, double beta1, double beta2, double eps, float max_grad_norm,
                            float* grad_norm_out_host, void* stream);
 /* The loop's scalars without a host round trip (the reference's loss is a device tensor until Trainer calls loss.item(),
  * DD/denoising_diffusion.py:1173): with loss_out_host == NULL dm_unet_loss_backward, and with grad_norm_out_host == NULL
  * dm_unet_optimizer_step, return as soon as their kernels are enqueued; dm_unet_train_scalar copies the loss of the last
  * loss / backward call (which = 0) or the total gradient norm of the last optimiser step (which = 1) to a DEVICE float. */
 int dm_unet_train_scalar(dm_unet* u, int which, float* out_dev, void* stream);
-int dm_unet_ema_update(dm_unet* u, float decay, int copy, void* stream);
+int dm_unet_ema_update(dm_unet* u, double decay, int copy, void* stream);
 int dm_unet_get_param(dm_unet* u, const char* name, int which, float* out_dev, void* stream);
 int dm_unet_set_train_tensor(dm_unet* u, const char* name, int which, const float* src_dev, void* stream);
 long long dm_unet_adam_step(dm_unet* u, long long set_to);
@@ -487,6 +490,20 @@ int dm_op_offset_noise(float* noise, const float* offset, float strength, int BC
  * gather dst[i] = src[idx[i]] (idx: n host indices) */
 int dm_op_cdist(const float* x, const float* y, float* out, int n, int m, int64_t D, void* stream);
 int dm_op_gather_rows(const float* src, const int64_t* idx_host, float* dst, int n, int64_t D, void* stream);
+/* The loss kernel of dm_unet_loss_backward on its own: out (the model output), x_start, noise, xq (the q_sample output, needed
+ * with terms & 2) and dout (B, per_sample) device floats; coef_host (B, 12) rows as in dm_train_args; objective 0 / 1 / 2;
+ * terms as loss_terms there; kl_weight: the reference's 0.001 -- the KL factor is kl_weight / (n_pos + 1e-8) in fp32 with
+ * n_pos the number of rows whose [3] is 1.  *loss_out_host = loss_scale * (mean_b part[b] + factor * sum_b klpart[b]);
+ * part_out / klpart_out (optional, B device floats): loss_weight[t_b] * mean((out - target)^2) and mean(kl) * [t_b > 0]. */
+int dm_op_mse_loss(const float* out, const float* x_start, const float* noise, const float* xq, const float* coef_host,
+                   int objective, int terms, float loss_scale, float kl_weight, float* dout, float* loss_out_host,
+                   float* part_out, float* klpart_out, int B, int per_sample, void* stream);
+/* What dm_unet_optimizer_step / dm_unet_ema_update run, on flat device buffers of n floats (g 16-byte aligned):
+ * clip_grad_norm_(max_grad_norm; <= 0: off) + the step-th torch.optim.Adam step, p / m / v updated in place,
+ * norm_coef_out_host (optional) = {total norm before clipping, clip coefficient};  ema.lerp_(p, 1 - decay) in place. */
+int dm_op_adam_step(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                    int step, float max_grad_norm, float* norm_coef_out_host, void* stream);
+int dm_op_ema_lerp(float* ema, const float* p, int64_t n, double decay, void* stream);
 
 /* Backward of the single operators above (what autograd computes for the reference module), for parity tests of each
  * piece of the training step.  All tensors NCHW fp32 device pointers; gradient outputs have the shape of the tensor they

@@ -108,5 +108,5 @@ def test_sample_args_guidance_fields():
     a = _lib.SampleArgs()
     assert a.cfg == 0 and a.cfg_scale == 0.0
     assert ctypes.sizeof(_lib.SampleArgs) % 8 == 0
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
     assert {"dm_unet_forward_masked", "dm_op_cfg_combine"} <= set(_lib.EXPORTS)

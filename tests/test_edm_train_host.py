@@ -154,7 +154,7 @@ def test_train_args_binding_matches_the_header():
     assert E.LOSS_W == 14 < _lib.DM_EDM_COEFS
     assert {"dm_unet_train_enable_ft", "dm_unet_loss_backward_edm", "dm_op_edm_noise_in", "dm_op_edm_loss",
             "dm_op_sinusoid_ft_bwd"} <= set(_lib.EXPORTS)
-    assert _lib.ABI_VERSION == 8
+    assert _lib.ABI_VERSION == 9
 
 
 def test_surface_and_refusals():
