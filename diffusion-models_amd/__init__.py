@@ -25,6 +25,8 @@ from .diffusion import (  # noqa: F401
 )
 from .elucidated import (ElucidatedDiffusion, edm_dpmpp_table, edm_heun_table, edm_sigmas,  # noqa: F401
                          edm_train_table)
+from .continuous import (ContinuousTimeGaussianDiffusion, VParamContinuousTimeGaussianDiffusion,  # noqa: F401
+                         alpha_cosine_log_snr, beta_linear_log_snr, ct_step_table, ct_train_table)
 from .vae import VQDecoder, VQEncoder, VQModel  # noqa: F401
 from .dist import gather_shards, sample_global, sample_sharded, shard_bounds, shared_seed  # noqa: F401
 from .checkpoint import load_trainer_checkpoint, load_vae_checkpoint  # noqa: F401
@@ -41,6 +43,8 @@ __all__ = [
     "LatentDiffusion",
     "TextConditionalLatentDiffusion",
     "ElucidatedDiffusion",
+    "ContinuousTimeGaussianDiffusion",
+    "VParamContinuousTimeGaussianDiffusion",
     "VQDecoder",
     "VQEncoder",
     "VQModel",
@@ -61,6 +65,10 @@ __all__ = [
     "edm_heun_table",
     "edm_dpmpp_table",
     "edm_train_table",
+    "beta_linear_log_snr",
+    "alpha_cosine_log_snr",
+    "ct_step_table",
+    "ct_train_table",
     "synth_state_dict",
     "synth_tensor",
 ]

@@ -1,0 +1,398 @@
+"""Host-side mirrors of the reference's two continuous-time classes in front of ``dm_sample_ct`` /
+``dm_unet_loss_backward_ct`` in libdm_hip.so:
+
+  ``ContinuousTimeGaussianDiffusion``        denoising-diffusion-pytorch/denoising_diffusion/continuous_time_gaussian_diffusion.py:97-259
+  ``VParamContinuousTimeGaussianDiffusion``  denoising-diffusion-pytorch/denoising_diffusion/v_param_continuous_time_gaussian_diffusion.py:32-170
+
+Same constructor arguments, method names and ``state_dict`` keys.  The U-Net's time is ``log_snr(t)``, a float, so both
+need the learned / random sinusoidal U-Net (the reference asserts it).  ``num_sample_steps`` is a sampling-time choice: no
+table is tied to training.
+
+The per-step and per-image scalars are computed HERE, as the same fp32 torch expressions in the same order as the
+reference (0-dim tensors for a sampling step, (B,) tensors for a training batch), and handed to the library as a table;
+the kernels hold no schedule logic.  This is deliberate: the cosine schedule's own samples move by 4e-3 .. 2e-2 (rel-L2)
+when the same expressions are evaluated in fp64 -- at t = 1, ``cos(pi / 2) ** -2`` makes log-SNR ~ -33.9 a pure fp32
+rounding artefact -- so parity is with the reference's fp32 scalars, never with a cleaner formula.
+
+``noise_schedule='learned'`` (a trainable MLP whose gradient flows into the U-Net's time input) is not built.
+
+Extensions (keyword-only): ``noise`` injects a source of N(0,1) draws called in the reference's order (the start image,
+then one draw per step except the last); ``seed`` / ``sample_offset`` select the device Philox stream and the index of the
+call's first sample in a global batch.  Training: ``train()`` arms the U-Net through ``dm_unet_train_enable_ft``;
+``p_losses`` / ``forward`` are one ``dm_unet_loss_backward_ct`` call -- loss and every parameter gradient; ``times`` /
+``noise`` inject the two draws, ``loss_scale`` / ``accumulate`` / ``sync`` are as on ``ElucidatedDiffusion.forward``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import torch
+from torch import sqrt
+from torch.special import expm1
+
+from . import _lib
+
+COLS = _lib.DM_CT_COEFS
+# columns of a table row (csrc/ct.h)
+LOG_SNR, ALPHA, SIGMA, ALPHA_NEXT, C_, ONE_M_C, SQRT_VAR, AN_OVER_A, C_SIGMA, LOSS_W = range(10)
+
+
+def _log(t, eps=1e-20):
+    return torch.log(t.clamp(min=eps))
+
+
+def beta_linear_log_snr(t):
+    """log(snr) that approximates the original linear schedule (continuous_time_gaussian_diffusion.py:51-52)."""
+    return -_log(expm1(1e-4 + 10 * (t ** 2)))
+
+
+def alpha_cosine_log_snr(t, s=0.008):
+    """:54-55 (and the v class, :29-30)."""
+    return -_log((torch.cos((t + s) / (1 + s) * math.pi * 0.5) ** -2) - 1, eps=1e-5)
+
+
+SCHEDULES = {"linear": beta_linear_log_snr, "cosine": alpha_cosine_log_snr}
+
+
+def _schedule(schedule):
+    if callable(schedule):
+        return schedule
+    if schedule == "learned":
+        raise NotImplementedError("noise_schedule='learned' (a trainable monotonic MLP whose gradient reaches the U-Net's "
+                                  "time input) is not built on the HIP path")
+    if schedule not in SCHEDULES:
+        raise ValueError(f"unknown noise schedule {schedule}")
+    return SCHEDULES[schedule]
+
+
+def ct_step_row(schedule, time: torch.Tensor, time_next: torch.Tensor) -> torch.Tensor:
+    """One DM_CT_COEFS row of ``p_mean_variance`` (:155-183) + ``p_sample`` (:188-197) for 0-dim fp32 ``time`` /
+    ``time_next``: every entry is the reference's own 0-dim tensor expression."""
+    f = _schedule(schedule)
+    log_snr = f(time)
+    log_snr_next = f(time_next)
+    c = -expm1(log_snr - log_snr_next)
+    squared_alpha, squared_alpha_next = log_snr.sigmoid(), log_snr_next.sigmoid()
+    squared_sigma, squared_sigma_next = (-log_snr).sigmoid(), (-log_snr_next).sigmoid()
+    alpha, sigma, alpha_next = map(sqrt, (squared_alpha, squared_sigma, squared_alpha_next))
+    posterior_variance = squared_sigma_next * c
+    row = torch.zeros(COLS, dtype=torch.float32)
+    row[LOG_SNR], row[ALPHA], row[SIGMA], row[ALPHA_NEXT] = log_snr, alpha, sigma, alpha_next
+    row[C_], row[ONE_M_C] = c, 1 - c
+    row[SQRT_VAR] = 0.0 if time_next == 0 else sqrt(posterior_variance)  # p_sample returns the mean when time_next == 0
+    row[AN_OVER_A], row[C_SIGMA] = alpha_next / alpha, c * sigma
+    return row
+
+
+def ct_step_table(num_sample_steps, schedule="linear") -> torch.Tensor:
+    """(N, DM_CT_COEFS) fp32 step table of ``p_sample_loop`` (:200-213): ``steps = linspace(1, 0, N + 1)``, row i from
+    the 0-dim ``steps[i]`` / ``steps[i + 1]``; the layout is documented in include/dm_hip.h."""
+    n = int(num_sample_steps)
+    steps = torch.linspace(1., 0., n + 1)
+    return torch.stack([ct_step_row(schedule, steps[i], steps[i + 1]) for i in range(n)])
+
+
+def ct_train_table(times: torch.Tensor, schedule="linear", min_snr_loss_weight=False, min_snr_gamma=5) -> torch.Tensor:
+    """(B, DM_CT_COEFS) fp32 rows of ``q_sample`` / ``p_losses`` (:222-251), one per image: log_snr, alpha, sigma as
+    tensor expressions on the (B,) ``times``; column 9 the loss weight (1, or ``snr.clamp(min = gamma) / snr``)."""
+    f = _schedule(schedule)
+    t = times.detach().to("cpu", torch.float32).reshape(-1)
+    log_snr = f(t)
+    tab = torch.zeros((t.numel(), COLS), dtype=torch.float32)
+    tab[:, LOG_SNR] = log_snr
+    tab[:, ALPHA], tab[:, SIGMA] = sqrt(log_snr.sigmoid()), sqrt((-log_snr).sigmoid())
+    if min_snr_loss_weight:
+        snr = log_snr.exp()
+        tab[:, LOSS_W] = snr.clamp(min=min_snr_gamma) / snr
+    else:
+        tab[:, LOSS_W] = 1.0
+    return tab
+
+
+def _default_seed() -> int:
+    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+
+
+def _fptr(t: torch.Tensor):
+    return C.cast(t.data_ptr(), C.POINTER(C.c_float))
+
+
+class _ContinuousTimeBase:
+    """What the two classes share; ``_objective`` and the schedule tell them apart."""
+
+    _objective = _lib.CT_PRED_NOISE
+    min_snr_loss_weight = False
+    min_snr_gamma = 5
+
+    def _init(self, model, image_size, channels, schedule, num_sample_steps, clip_sample_denoised, use_graph):
+        assert model.random_or_learned_sinusoidal_cond
+        assert not model.self_condition, 'not supported yet'
+        name = type(self).__name__
+        if getattr(model, "text_condition", False) or getattr(getattr(model, "cfg", None), "cond_channels", 0):
+            raise NotImplementedError(f"{name} calls model(x, log_snr) only: a text-conditional or image-conditional "
+                                      "U-Net has no place for its condition")
+        if model.out_dim != channels or model.channels != channels:
+            raise ValueError(f"the U-Net maps {model.channels} to {model.out_dim} channels, the sampler needs {channels} -> "
+                             f"{channels} (no learned variance)")
+        self.log_snr = _schedule(schedule)
+        self.model = model
+        self.channels = channels
+        self.image_size = image_size
+        self.num_sample_steps = num_sample_steps
+        self.clip_sample_denoised = clip_sample_denoised
+        self.use_graph = use_graph
+        self._lib = _lib.load()
+
+    # -- module-ish surface ------------------------------------------------------------------------
+    @property
+    def device(self):
+        return self.model.device
+
+    def eval(self):
+        return self
+
+    def parameters(self):
+        return self.model.parameters()
+
+    def sample_shape(self):
+        """(C, H, W) of one sample (``dist.sample_global`` builds empty shards from it)."""
+        return (self.channels, self.image_size, self.image_size)
+
+    def state_dict(self):
+        """The reference modules have no buffers: ``model.`` + the U-Net's keys."""
+        return {"model." + k: v for k, v in self.model.state_dict().items()}
+
+    def load_state_dict(self, state_dict, strict=True):
+        other = [k for k in state_dict if not k.startswith("model.")]
+        if strict and other:
+            raise RuntimeError(f"Error(s) in loading state_dict: unexpected {other[:5]}")
+        self.model.load_state_dict({k[len("model."):]: v for k, v in state_dict.items() if k.startswith("model.")},
+                                   strict=strict)
+        return self
+
+    # -- sampling ----------------------------------------------------------------------------------
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _randn(self, shape, seed, draw, sample_offset):
+        out = torch.empty(tuple(shape), device=self.device, dtype=torch.float32)
+        per = out.numel() // max(int(shape[0]), 1)
+        _lib.check(self._lib.dm_randn(_lib.ptr(out), out.numel(), C.c_uint64(seed), C.c_uint64(draw),
+                                      C.c_uint64(int(sample_offset) * per), self._stream()))
+        return out
+
+    def _step_op(self, x, row, eps, want_x_start=False):
+        """``dm_op_ct_step`` on one table row: the U-Net at log_snr, then the elementwise step."""
+        x = x.to(self.device, torch.float32).contiguous()
+        b, per = x.shape[0], x[0].numel()
+        row = row.reshape(1, COLS).contiguous()
+        F = self.model(x, row[0, LOG_SNR].expand(b).contiguous().to(self.device))
+        out = torch.empty_like(x)
+        x_start = torch.empty_like(x) if want_x_start else None
+        if eps is not None:
+            eps = eps.to(self.device, torch.float32).contiguous()
+            assert eps.shape == x.shape, "noise must have the shape of x"
+        _lib.check(self._lib.dm_op_ct_step(_lib.ptr(x), _lib.ptr(F), _lib.ptr(eps), _fptr(row), 1, self._objective,
+                                           int(bool(self.clip_sample_denoised)), 0, 1, 0, _lib.ptr(out), _lib.ptr(x_start),
+                                           b, per, self._stream()))
+        return out, x_start
+
+    @staticmethod
+    def _t0(v):
+        return torch.as_tensor(v, dtype=torch.float32).detach().cpu().reshape(())
+
+    def p_mean_variance(self, x, time, time_next):
+        """:155-183: (model_mean, posterior_variance) for 0-dim ``time`` / ``time_next``."""
+        time, time_next = self._t0(time), self._t0(time_next)
+        row = ct_step_row(self.log_snr, time, time_next)
+        row[SQRT_VAR] = 0.0
+        mean, _ = self._step_op(x, row, None)
+        log_snr, log_snr_next = self.log_snr(time), self.log_snr(time_next)
+        return mean, ((-log_snr_next).sigmoid() * -expm1(log_snr - log_snr_next)).to(self.device)
+
+    def p_sample(self, x, time, time_next, *, noise=None):
+        """:188-197.  ``noise``: the step's N(0,1) tensor (default: a device Philox draw); unused when time_next == 0."""
+        time, time_next = self._t0(time), self._t0(time_next)
+        row = ct_step_row(self.log_snr, time, time_next)
+        if float(row[SQRT_VAR]) != 0.0 and noise is None:
+            noise = self._randn(x.shape, _default_seed(), 0, 0)
+        return self._step_op(x, row, noise if float(row[SQRT_VAR]) != 0.0 else None)[0]
+
+    def p_sample_loop(self, shape, *, noise=None, seed=None, sample_offset=0):
+        """:200-213.  An injected ``noise`` callable is called once for the start image and once per step except the
+        last, the reference's order of draws."""
+        shape = tuple(int(v) for v in shape)
+        f = self.model.downsample_factor
+        assert shape[0] > 0 and shape[2] % f == 0 and shape[3] % f == 0, f"shape {shape}: the sides must be divisible by {f}"
+        if seed is None:
+            seed = _default_seed()
+        table = ct_step_table(self.num_sample_steps, self.log_snr).contiguous()
+        n_steps = table.shape[0]
+        if noise is not None:
+            x_init = noise(shape).to(self.device, torch.float32).contiguous()
+            rows = [noise(shape).to(torch.float32) for _ in range(n_steps - 1)]
+            # (a one-step loop draws nothing after the start image: its only row has c[6] == 0)
+            noise_dev = torch.stack(rows, dim=0).to(self.device).contiguous() if rows else None
+        else:
+            x_init = self._randn(shape, seed, 0, sample_offset)
+            noise_dev = None
+        assert tuple(x_init.shape) == shape, "noise() must return tensors of the sampled shape"
+        out = torch.empty(shape, device=self.device, dtype=torch.float32)
+        a = _lib.CtArgs()
+        a.objective, a.clip, a.n_steps, a.table_host = self._objective, int(bool(self.clip_sample_denoised)), n_steps, _fptr(table)
+        a.x_init, a.noise, a.seed, a.sample_offset = _lib.ptr(x_init), _lib.ptr(noise_dev), seed, int(sample_offset)
+        a.out = _lib.ptr(out)
+        a.B, a.H, a.W = shape[0], shape[2], shape[3]
+        a.use_graph, a.stream = 1 if self.use_graph else 0, self._stream()
+        _lib.check(self._lib.dm_sample_ct(self.model._handle, C.byref(a)))
+        return out
+
+    def sample(self, batch_size=16, *, noise=None, seed=None, sample_offset=0):
+        """:216-217."""
+        return self.p_sample_loop((batch_size, self.channels, self.image_size, self.image_size), noise=noise, seed=seed,
+                                  sample_offset=sample_offset)
+
+    # -- training ----------------------------------------------------------------------------------
+    def _q_sample(self, x_start, times, noise):
+        x_start = x_start.to(self.device, torch.float32).contiguous()
+        noise = (noise.to(self.device, torch.float32).contiguous() if noise is not None
+                 else self._randn(x_start.shape, _default_seed(), 0, 0))
+        tab = ct_train_table(times, self.log_snr)
+        b = x_start.shape[0]
+        if tab.shape[0] != b:
+            raise RuntimeError(f"times has {tab.shape[0]} entries for a batch of {b}")
+        coef = tab[:, [ALPHA, SIGMA]].contiguous()
+        out = torch.empty_like(x_start)
+        _lib.check(self._lib.dm_op_lincomb(_lib.ptr(x_start), _lib.ptr(noise), _fptr(coef), _lib.ptr(out), b,
+                                           x_start[0].numel(), 0, 0, self._stream()))
+        pad = (b,) + (1,) * (x_start.dim() - 1)
+        return out, tab[:, LOG_SNR].to(self.device), tab[:, ALPHA].reshape(pad).to(self.device), tab[:, SIGMA].reshape(pad).to(self.device)
+
+    def _draw_times(self, batch_size):
+        return torch.zeros((batch_size,)).float().uniform_(0, 1)
+
+    def random_times(self, batch_size):
+        """:233-235: uniform on [0, 1); the (batch_size,) draw comes from torch's global CPU generator."""
+        return self._draw_times(batch_size).to(self.device)
+
+    def _trainable_model(self):
+        from .unet import Unet
+
+        model = self.model
+        if not isinstance(model, Unet) or getattr(model, "_handle", None) is None or not hasattr(self._lib, "dm_unet_loss_backward_ct"):
+            raise NotImplementedError(f"{type(self).__name__} can train a library Unet only (dm_unet_train_enable_ft arms its "
+                                      f"handle for the float-time training loss); got {type(model).__name__}")
+        return model
+
+    def train(self, mode: bool = True):
+        """``model.train()``: arm the U-Net for float-time training (gradient buffers, input-gradient convolutions; once)."""
+        if mode:
+            model = self._trainable_model()
+            if not model._loaded:
+                raise RuntimeError("load_state_dict() must be called before train()")
+            # random_fourier_features: the reference builds time_mlp.0.weights with requires_grad = False
+            _lib.check(self._lib.dm_unet_train_enable_ft(model._handle, int(bool(model.cfg.random_fourier_features))))
+            if not getattr(model, "_training", False):
+                model.set_dropout_seed(int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
+            model._training = True
+        return self
+
+    def _loss(self, images, times, noise, normalize, loss_scale, accumulate, sync):
+        model = self._trainable_model()
+        b, c, h, w = images.shape
+        assert c == self.channels, "mismatch of image channels"
+        if not getattr(model, "_training", False):
+            self.train()
+        tab = ct_train_table(times, self.log_snr, self.min_snr_loss_weight, self.min_snr_gamma).contiguous()
+        if tab.shape[0] != b:
+            raise RuntimeError(f"times has {tab.shape[0]} entries for a batch of {b}")
+        images = images.to(self.device, torch.float32).contiguous()
+        noise = (noise.to(self.device, torch.float32).contiguous() if noise is not None
+                 else self._randn(images.shape, _default_seed(), 0, 0))
+        if noise.shape != images.shape:
+            raise RuntimeError(f"noise {tuple(noise.shape)} does not match images {tuple(images.shape)}")
+        stream = self._stream()
+        loss = C.c_float(0.0)
+        a = _lib.CtTrainArgs()
+        a.images, a.noise, a.coef_host, a.coef_stride = _lib.ptr(images), _lib.ptr(noise), _fptr(tab), COLS
+        a.objective, a.loss_scale, a.accumulate = self._objective, float(loss_scale), int(bool(accumulate))
+        a.B, a.H, a.W, a.normalize = b, h, w, int(bool(normalize))
+        a.loss_out_host = C.pointer(loss) if sync else None
+        a.stream = stream
+        _lib.check(self._lib.dm_unet_loss_backward_ct(model._handle, C.byref(a)))
+        if sync:
+            return torch.tensor(loss.value, dtype=torch.float32)
+        val = torch.empty((), device=self.device, dtype=torch.float32)
+        _lib.check(self._lib.dm_unet_train_scalar(model._handle, 0, _lib.ptr(val), stream))
+        return val
+
+    def p_losses(self, x_start, times, noise=None, *, loss_scale=1.0, accumulate=False, sync=True):
+        """:237-251 (v: :152-162) on ``x_start`` in [-1, 1]: the loss (0-dim CPU tensor; ``sync=False``: a 0-dim device
+        tensor, nothing waited for); the parameter gradients stay on the U-Net (``self.model.grad(name)`` / ``.grads()``)."""
+        return self._loss(x_start, times, noise, False, loss_scale, accumulate, sync)
+
+    def forward(self, img, *, times=None, noise=None, loss_scale=1.0, accumulate=False, sync=True):
+        """:253-259 on ``img`` in [0, 1]: the draw of ``times`` comes first, as in the reference, then the noise."""
+        self._trainable_model()
+        b, c, h, w = img.shape
+        assert h == self.image_size and w == self.image_size, f'height and width of image must be {self.image_size}'
+        times = self._draw_times(b) if times is None else times
+        return self._loss(img, times, noise, True, loss_scale, accumulate, sync)
+
+    __call__ = forward
+
+
+class ContinuousTimeGaussianDiffusion(_ContinuousTimeBase):
+    """``ContinuousTimeGaussianDiffusion(model, image_size=...)`` -- drop-in for the reference class (noise prediction,
+    linear or cosine log-SNR schedule, optional min-SNR loss weight)."""
+
+    _objective = _lib.CT_PRED_NOISE
+
+    def __init__(
+        self,
+        model,
+        *,
+        image_size,
+        channels=3,
+        noise_schedule='linear',
+        num_sample_steps=500,
+        clip_sample_denoised=True,
+        learned_schedule_net_hidden_dim=1024,
+        learned_noise_schedule_frac_gradient=1.,
+        min_snr_loss_weight=False,
+        min_snr_gamma=5,
+        use_graph=True,
+    ):
+        if not isinstance(noise_schedule, str):
+            raise ValueError(f'unknown noise schedule {noise_schedule}')
+        self._init(model, image_size, channels, noise_schedule, num_sample_steps, clip_sample_denoised, use_graph)
+        self.min_snr_loss_weight = min_snr_loss_weight
+        self.min_snr_gamma = min_snr_gamma
+
+    def q_sample(self, x_start, times, noise=None):
+        """:222-231: (x_noised, log_snr)."""
+        return self._q_sample(x_start, times, noise)[:2]
+
+
+class VParamContinuousTimeGaussianDiffusion(_ContinuousTimeBase):
+    """``VParamContinuousTimeGaussianDiffusion(model, image_size=...)`` -- drop-in for the reference class (v prediction,
+    cosine log-SNR schedule)."""
+
+    _objective = _lib.CT_PRED_V
+
+    def __init__(
+        self,
+        model,
+        *,
+        image_size,
+        channels=3,
+        num_sample_steps=500,
+        clip_sample_denoised=True,
+        use_graph=True,
+    ):
+        self._init(model, image_size, channels, "cosine", num_sample_steps, clip_sample_denoised, use_graph)
+
+    def q_sample(self, x_start, times, noise=None):
+        """:138-147: (x_noised, log_snr, alpha, sigma), the last two padded to ``x_start``'s rank."""
+        return self._q_sample(x_start, times, noise)

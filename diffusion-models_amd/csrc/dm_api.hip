@@ -5,6 +5,7 @@
 #include "../../include/dm_hip.h"
 #include "dm_common.h"
 #include "edm.h"
+#include "ct.h"
 
 #include <array>
 #include <cmath>
@@ -1870,3 +1871,4 @@ int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t eleme
 #include "dm_train.inc"
 #include "dm_train_ops.inc"
 #include "dm_edm.inc"
+#include "dm_ct.inc"

@@ -19,8 +19,8 @@ import torch
 
 
 def _unet_of(diffusion):
-    """The U-Net of a diffusion object and its state-dict prefix: ``model`` (DenoisingDiffusion and its variants) or
-    ``net`` (ElucidatedDiffusion)."""
+    """The U-Net of a diffusion object and its state-dict prefix: ``model`` (DenoisingDiffusion and its variants, the
+    continuous-time classes) or ``net`` (ElucidatedDiffusion)."""
     if hasattr(diffusion, "model"):
         return diffusion.model, "model"
     return diffusion.net, "net"
@@ -168,12 +168,14 @@ def load_checkpoint(path, diffusion, *, ema: Optional[EMA] = None):
 
 def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, betas=(0.9, 0.99), eps=1e-8,
                max_grad_norm=1.0, ema: Optional[EMA] = None, t=None, noise=None, group=None, sync=True,
-               timing: Optional[dict] = None, bucketed: Optional[bool] = None, text_mask=None, sigmas=None):
+               timing: Optional[dict] = None, bucketed: Optional[bool] = None, text_mask=None, sigmas=None, times=None):
     """One iteration of ``Trainer.train`` (:1164-1190).  ``micro_batches``: the ``gradient_accumulate_every`` image batches
     (in [0, 1]) of the iteration; for a text-conditional model a micro-batch may be a pair ``(images, text_emb)``, whose
     captions ``p_losses`` then drops per image with the model's ``cond_drop_prob``.  ``t`` / ``noise`` / ``text_mask``
     (lists, one entry per micro-batch) inject the random draws for tests.  An ``ElucidatedDiffusion`` takes the same
-    iteration through its ``forward``; its injection lists are ``sigmas`` / ``noise``.
+    iteration through its ``forward``; its injection lists are ``sigmas`` / ``noise``.  So does a continuous-time object
+    (``ContinuousTimeGaussianDiffusion`` / ``VParamContinuousTimeGaussianDiffusion``, told by ``random_times``); its lists
+    are ``times`` / ``noise``.
     Under ``torch.distributed`` (one process per GPU, as ``accelerate`` runs the reference's Trainer under DDP) every rank
     computes the gradients of ITS micro-batches and the flat gradient buffer is averaged over the ranks in place (RCCL over
     xGMI) before the optimiser step; every rank then takes the same step.  With more than one rank (``bucketed=True`` forces
@@ -193,6 +195,11 @@ def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, bet
     parallel = dist.is_available() and dist.is_initialized()  # also at world size 1: the collectives are the same code path
     unet = _unet_of(diffusion)[0]
     edm = not hasattr(diffusion, "p_losses")  # ElucidatedDiffusion: the loss is forward(images), the draws sigma and noise
+    ct = hasattr(diffusion, "random_times")  # continuous time: the loss is forward(images), the draws times and noise
+    if ct and (t is not None or sigmas is not None or text_mask is not None):
+        raise ValueError("a continuous-time diffusion has real-valued times and no captions: inject times= / noise=")
+    if times is not None and not ct:
+        raise ValueError("times= is the draw of a continuous-time diffusion; this object takes t= or sigmas=")
     if edm and (t is not None or text_mask is not None):
         raise ValueError("an ElucidatedDiffusion has no timesteps or captions: inject sigmas= / noise=")
     if sigmas is not None and not edm:
@@ -205,6 +212,11 @@ def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, bet
     if text_mask is not None and len(text_mask) != k:
         raise ValueError(f"text_mask has {len(text_mask)} entries for {k} micro-batches")
     for i, data in enumerate(batches):
+        if ct:
+            loss = diffusion(data, times=times[i] if times is not None else None,
+                             noise=noise[i] if noise is not None else None, loss_scale=1.0 / k, accumulate=i > 0, **lazy)
+            total = (total + float(loss)) if sync else (loss if i == 0 else total + loss)
+            continue
         if edm:
             loss = diffusion(data, sigmas=sigmas[i] if sigmas is not None else None,
                              noise=noise[i] if noise is not None else None, loss_scale=1.0 / k, accumulate=i > 0, **lazy)

@@ -679,6 +679,85 @@ int dm_op_edm_loss(const float* noised, const float* F, const float* x0, const f
 int dm_op_sinusoid_ft_bwd(const float* de0, const float* e0, float* dw, int B, int half, int learned, int accumulate,
                           void* stream);
 
+/* ---- Continuous-time Gaussian diffusion (DD/continuous_time_gaussian_diffusion.py: noise prediction;
+ * DD/v_param_continuous_time_gaussian_diffusion.py: v prediction) -- the U-Net's time is log_snr(t), a float, so the handle
+ * must have learned_sinusoidal_dim > 0 (both classes assert it), no text conditioning and out_dim == channels.
+ *
+ * Sampling (p_sample_loop of both classes).  The HOST evaluates every per-step scalar as the reference's own 0-dim fp32
+ * tensor expression and passes n_steps rows of DM_CT_COEFS floats; step i runs Unet(x, c[0]) and one elementwise pass:
+ *   c[0]=log_snr(t_i)                  c[1]=alpha=sqrt(sigmoid(c[0]))          c[2]=sigma=sqrt(sigmoid(-c[0]))
+ *   c[3]=alpha_next                    c[4]=c=-expm1(log_snr - log_snr_next)   c[5]=1 - c
+ *   c[6]=sqrt(sigmoid(-log_snr_next) * c), 0 on the step with time_next == 0 (p_sample returns the mean there)
+ *   c[7]=alpha_next / alpha            c[8]=c * sigma                          (noise prediction without clipping)
+ *   c[9]=loss weight (training rows only); unused entries are 0.
+ *   objective  DM_CT_PRED_NOISE / DM_CT_PRED_V;   clip: clamp x_start to [-1, 1] (clip_sample_denoised)
+ *     v:               x_start = c[1] x - c[2] F [clamped];       mean = c[3] (x c[5] / c[1] + c[4] x_start)
+ *     noise, clip:     x_start = (x - c[2] F) / c[1], clamped;    the same mean
+ *     noise, no clip:  mean = c[7] (x - c[8] F)
+ *     x <- mean + c[6] eps
+ *   x_init     (B,C,H,W) N(0,1) noise, the loop's start image (unscaled)
+ *   noise      NULL -> device Philox noise (draw i + 1 at step i); else (n_steps - 1, B,C,H,W), row i read by step i.  A
+ *              step whose c[6] == 0 reads neither; with a noise tensor the last row's c[6] must be 0.
+ *   out        (clamp(x, -1, 1) + 1) / 2
+ *   use_graph  one step is captured as a hipGraph, cached on the handle per (objective, clip, B, H, W, noise pointer) in
+ *              the slot dm_sample / dm_sample_edm use. */
+#define DM_CT_COEFS 16
+#define DM_CT_PRED_NOISE 0
+#define DM_CT_PRED_V 1
+typedef struct dm_ct_args {
+    int32_t objective;  /* DM_CT_PRED_* */
+    int32_t clip;
+    int32_t n_steps;
+    const float* table_host;
+    const float* x_init;
+    const float* noise;
+    uint64_t seed;
+    uint64_t sample_offset;
+    float* out;
+    int32_t B, H, W;
+    int32_t use_graph;
+    void* stream;
+} dm_ct_args;
+int dm_sample_ct(dm_unet* u, const dm_ct_args* args);
+
+/* One p_losses (+ the normalisation of forward) and its backward pass on a handle armed by dm_unet_train_enable_ft:
+ *   x0 = 2 images - 1 (normalize != 0: forward on images in [0, 1]) or images (normalize == 0: p_losses on x_start);
+ *   x = x0 alpha_b + noise sigma_b;  F = Unet(x, log_snr_b);
+ *   target = noise (DM_CT_PRED_NOISE) or alpha_b noise - sigma_b x0 (DM_CT_PRED_V);
+ *   loss = loss_scale * mean_b( w_b * mean((F - target)^2) );  every parameter gradient.
+ * coef_host: B rows of coef_stride floats (0: DM_CT_COEFS) with c[0] = log_snr_b, c[1] = alpha_b, c[2] = sigma_b and
+ * c[9] = w_b (1, or min-SNR: clamp(snr_b, min = gamma) / snr_b).  loss_scale, accumulate and loss_out_host as in
+ * dm_unet_loss_backward_edm. */
+typedef struct dm_ct_train_args {
+    const float* images;
+    const float* noise;
+    const float* coef_host;
+    int32_t coef_stride;
+    int32_t objective;
+    float loss_scale;
+    int32_t accumulate;
+    int32_t B, H, W;
+    int32_t normalize;
+    float* loss_out_host;
+    void* stream;
+} dm_ct_train_args;
+int dm_unet_loss_backward_ct(dm_unet* u, const dm_ct_train_args* args);
+
+/* The three passes on their own (tests).  c_host: rows == 1 (every image) or rows == B (row b for image b) in the layout
+ * above; tensors are B * per floats, per % 4 == 0, 16-byte aligned; each call waits for its result.
+ *   step:      as above on (x, F).  eps NULL: Philox draw `draw` (>= 1) under `seed`; a row with c[6] == 0 reads neither.
+ *              x_start_out (optional) = x_start; it must be NULL for noise prediction without clipping.
+ *   noise_in:  x0 = 2 images - 1 (normalize != 0) or images;  x = x0 c[1] + eps c[2];  target as above.
+ *   loss:      c_host holds B rows.  *loss_out_host = loss_scale * mean_b(c[9] mean((F - target)^2));
+ *              dF = loss_scale * c[9] * 2 (F - target) / (B * per). */
+int dm_op_ct_step(const float* x, const float* F, const float* eps, const float* c_host, int rows, int objective, int clip,
+                  uint64_t seed, uint64_t draw, uint64_t element_offset, float* out, float* x_start_out, int B, int64_t per,
+                  void* stream);
+int dm_op_ct_noise_in(const float* images, const float* eps, const float* c_host, int rows, int objective, int normalize,
+                      float* x, float* target, int B, int64_t per, void* stream);
+int dm_op_ct_loss(const float* F, const float* target, const float* c_host, float loss_scale, float* dF,
+                  float* loss_out_host, int B, int64_t per, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
