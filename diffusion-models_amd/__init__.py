@@ -27,6 +27,7 @@ from .elucidated import (ElucidatedDiffusion, edm_dpmpp_table, edm_heun_table, e
                          edm_train_table)
 from .continuous import (ContinuousTimeGaussianDiffusion, VParamContinuousTimeGaussianDiffusion,  # noqa: F401
                          alpha_cosine_log_snr, beta_linear_log_snr, ct_step_table, ct_train_table)
+from .repaint import GaussianDiffusion as RePaintGaussianDiffusion, RepaintTable, repaint_step_table  # noqa: F401
 from .vae import VQDecoder, VQEncoder, VQModel  # noqa: F401
 from .dist import gather_shards, sample_global, sample_sharded, shard_bounds, shared_seed  # noqa: F401
 from .checkpoint import load_trainer_checkpoint, load_vae_checkpoint  # noqa: F401
@@ -45,6 +46,7 @@ __all__ = [
     "ElucidatedDiffusion",
     "ContinuousTimeGaussianDiffusion",
     "VParamContinuousTimeGaussianDiffusion",
+    "RePaintGaussianDiffusion",
     "VQDecoder",
     "VQEncoder",
     "VQModel",
@@ -69,6 +71,8 @@ __all__ = [
     "alpha_cosine_log_snr",
     "ct_step_table",
     "ct_train_table",
+    "repaint_step_table",
+    "RepaintTable",
     "synth_state_dict",
     "synth_tensor",
 ]

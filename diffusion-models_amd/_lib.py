@@ -18,6 +18,7 @@ DM_EDM_COEFS = 16
 EDM_HEUN, EDM_DPMPP = 0, 1
 DM_CT_COEFS = 16
 CT_PRED_NOISE, CT_PRED_V = 0, 1
+DM_REPAINT_COEFS = 16
 ABI_VERSION = 9
 
 # every symbol include/dm_hip.h declares (tests check the library exports all of them)
@@ -49,6 +50,7 @@ EXPORTS = (
     "dm_unet_train_enable_ft", "dm_unet_loss_backward_edm",
     "dm_op_edm_noise_in", "dm_op_edm_loss", "dm_op_sinusoid_ft_bwd",
     "dm_sample_ct", "dm_unet_loss_backward_ct", "dm_op_ct_step", "dm_op_ct_noise_in", "dm_op_ct_loss",
+    "dm_sample_repaint", "dm_op_repaint_step",
 )
 
 
@@ -130,6 +132,17 @@ class CtTrainArgs(C.Structure):
         ("images", C.c_void_p), ("noise", C.c_void_p), ("coef_host", C.POINTER(C.c_float)), ("coef_stride", C.c_int32),
         ("objective", C.c_int32), ("loss_scale", C.c_float), ("accumulate", C.c_int32), ("B", C.c_int32), ("H", C.c_int32),
         ("W", C.c_int32), ("normalize", C.c_int32), ("loss_out_host", C.POINTER(C.c_float)), ("stream", C.c_void_p),
+    ]
+
+
+class RepaintArgs(C.Structure):
+    """dm_repaint_args (include/dm_hip.h)."""
+    _fields_ = [
+        ("objective", C.c_int32), ("n_rows", C.c_int32), ("times_host", C.POINTER(C.c_int64)),
+        ("table_host", C.POINTER(C.c_float)), ("x_T", C.c_void_p), ("noise", C.c_void_p), ("seed", C.c_uint64),
+        ("sample_offset", C.c_uint64), ("gt", C.c_void_p), ("mask", C.c_void_p), ("mask_channels", C.c_int32),
+        ("unnormalize", C.c_int32), ("out", C.c_void_p), ("all_steps", C.c_void_p), ("n_frames", C.c_int32),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("use_graph", C.c_int32), ("stream", C.c_void_p),
     ]
 
 
@@ -263,6 +276,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_ct_step.argtypes = [fp, fp, fp, C.POINTER(C.c_float), i32, i32, i32, u64, u64, u64, fp, fp, i32, i64, vp]
     lib.dm_op_ct_noise_in.argtypes = [fp, fp, C.POINTER(C.c_float), i32, i32, i32, fp, fp, i32, i64, vp]
     lib.dm_op_ct_loss.argtypes = [fp, fp, C.POINTER(C.c_float), C.c_float, fp, C.POINTER(C.c_float), i32, i64, vp]
+    lib.dm_sample_repaint.argtypes = [vp, C.POINTER(RepaintArgs)]
+    lib.dm_op_repaint_step.argtypes = [i32, i32, fp, fp, fp, fp, i32, fp, fp, fp, C.POINTER(C.c_float), i32, u64, u64, u64, fp, fp,
+                                       i32, i32, i32, vp]
     lib.dm_profile_read.argtypes = [C.POINTER(ProfileRow), i32, C.POINTER(i32)]
 
 

@@ -6,6 +6,7 @@
 #include "dm_common.h"
 #include "edm.h"
 #include "ct.h"
+#include "repaint.h"
 
 #include <array>
 #include <cmath>
@@ -1872,3 +1873,4 @@ int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t eleme
 #include "dm_train_ops.inc"
 #include "dm_edm.inc"
 #include "dm_ct.inc"
+#include "dm_repaint.inc"

@@ -758,6 +758,75 @@ int dm_op_ct_noise_in(const float* images, const float* eps, const float* c_host
 int dm_op_ct_loss(const float* F, const float* target, const float* c_host, float loss_scale, float* dF,
                   float* loss_out_host, int B, int64_t per, void* stream);
 
+/* ---- RePaint inpainting (arXiv 2201.09865 as DD/repaint.py:614-681 has it): the DDPM loop over a trained U-Net with the
+ * pixels where mask == 1 taken from a ground-truth image and the rest generated, and with "resampling" jumps back up the
+ * chain.  The HOST unrolls the loop into n_rows rows, one U-Net evaluation each, and evaluates every scalar as the
+ * reference's own 0-dim fp32 tensor expression; row r is DM_REPAINT_COEFS floats:
+ *   c[0..7]  the DDPM row of dm_sample at the row's time t_r (DM_COEFS floats, same layout)
+ *   c[8]=sqrt(alphas_cumprod[t_r])   c[9]=sqrt(1 - alphas_cumprod[t_r])         (the known region, noised to t_r)
+ *   c[10]=sqrt(1 - betas[j])  c[11]=sqrt(betas[j])  c[12]=1 on a row that opens a resample iteration (j = resample_jump),
+ *   else 1, 0, 0              c[13]=frame of all_steps the row's result goes to, or -1;  c[14], c[15] = 0
+ * With g = 2 gt - 1 (applied whatever the caller's auto_normalize is, as the reference does) row r runs
+ *   [x <- c[10] x + c[11] z_jump]                        when c[12] != 0
+ *   x <- mask (c[8] g + c[9] z_known) + (1 - mask) x
+ *   x <- the DDPM update of dm_sample (objective as there) on Unet(x, t_r), with z_step when c[5] != 0
+ * and the last row ends with x <- mask g + (1 - mask) x.  The update of row r and the jump and blend of row r + 1 are one
+ * kernel launch (the blend of row 0 is a launch of its own in front of the loop).
+ *   times_host  n_rows int64 times;  table_host  n_rows x DM_REPAINT_COEFS floats
+ *   x_T         (B,C,H,W) N(0,1) start image;  gt (B,C,H,W) in [0, 1];  mask (B,mask_channels,H,W), mask_channels 1 or C,
+ *               any values (1 = known); all device pointers
+ *   noise       NULL -> device Philox noise under `seed`: draw 0 is x_T (the caller's), row r draws 3r + 1 (jump), 3r + 2
+ *               (known) and 3r + 3 (step); counters are global element indices as in dm_sample_ex (sample_offset).
+ *               Else (n_rows, 3, B,C,H,W) with [r][0] = z_jump, [r][1] = z_known, [r][2] = z_step; unread entries are
+ *               never touched.
+ *   out         the result, (x + 1) / 2 when unnormalize != 0
+ *   all_steps   NULL or (n_frames, B,C,H,W): frame 0 = x_T, frame c[13] = the row's result before the next row's jump
+ *               and blend (never unnormalised)
+ *   use_graph   one row is captured as a hipGraph, cached on the handle per (objective, mask_channels, B, H, W, noise and
+ *               all_steps pointers) in the slot dm_sample uses; seed, offset, tables, row count, unnormalize, gt and mask
+ *               values are device data and do not re-capture. */
+#define DM_REPAINT_COEFS 16
+#define DM_REPAINT_AUTO 0
+#define DM_REPAINT_BLEND 1
+#define DM_REPAINT_STEP 2
+#define DM_REPAINT_STEP_NEXT 3
+#define DM_REPAINT_LAST 4
+typedef struct dm_repaint_args {
+    int32_t objective;  /* DM_OBJ_* */
+    int32_t n_rows;
+    const int64_t* times_host;
+    const float* table_host;
+    const float* x_T;
+    const float* noise;
+    uint64_t seed;
+    uint64_t sample_offset;
+    const float* gt;
+    const float* mask;
+    int32_t mask_channels;
+    int32_t unnormalize;
+    float* out;
+    float* all_steps;
+    int32_t n_frames;
+    int32_t B, H, W;
+    int32_t use_graph;
+    void* stream;
+} dm_repaint_args;
+int dm_sample_repaint(dm_unet* u, const dm_repaint_args* args);
+
+/* The fused kernel on plain buffers for one row (tests, p_sample); tensors are (B,C,HW) floats, the mask (B,mask_channels,HW);
+ * the call waits for its result.  c_host is the row's table row, followed by the next row's for DM_REPAINT_STEP_NEXT.
+ *   DM_REPAINT_BLEND      out = mask (c[8] g + c[9] z_known) + (1 - mask) x               (eps may be NULL)
+ *   DM_REPAINT_STEP       out = the DDPM update of (x, eps) with c[0..7] and z_step      (gt and mask may be NULL)
+ *   DM_REPAINT_STEP_NEXT  that update, then the next row's jump and blend with c[16 + 8 .. 16 + 12]
+ *   DM_REPAINT_LAST       that update, then out = mask g + (1 - mask) out, (out + 1) / 2 when unnormalize != 0
+ * z_jump, z_known, z_step all NULL: the Philox draws of row `row` (of row + 1 for the jump and blend of STEP_NEXT) under
+ * `seed`, element counters starting at element_offset (a multiple of 4).  Else the draws the row reads must be given.
+ * x_start_out (optional) = the clamped x_start of the update.  out may be x. */
+int dm_op_repaint_step(int mode, int objective, const float* x, const float* eps, const float* gt, const float* mask,
+                       int mask_channels, const float* z_jump, const float* z_known, const float* z_step, const float* c_host,
+                       int unnormalize, uint64_t seed, uint64_t row, uint64_t element_offset, float* out, float* x_start_out,
+                       int B, int C, int HW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
