@@ -315,15 +315,22 @@ struct dm_unet {
     // weight groups: parameter-name prefix -> [first upload, count) in `own` (dm_unet_refresh skips clean groups)
     std::map<std::string, std::pair<size_t, size_t>> groups;
     std::vector<std::pair<std::string, ResBlock*>> resnets;  // in ss_off order
-    // the instantiated graph of one denoise step, reused while the key (shape, kind, every captured pointer) holds
+    // the instantiated graph of one denoise step, reused while the key (shape, kind, every captured pointer) holds.  The
+    // slot serves every sampling loop of the handle (dm_sampler.inc: run_steps); the kind says whose graph it holds.
+    enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT };
     struct GraphKey {
-        int kind = -1, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
-        int edm_clamp = 0;  // ElucidatedDiffusion: the clamp flag, a kernel argument of the captured Heun step
+        int kind = GK_NONE, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
+        int edm_clamp = 0;      // ElucidatedDiffusion: the clamp flag, a kernel argument of the captured Heun step
+        int ct_clip = 0;        // continuous time: the clip flag of the captured ct_step
+        int mask_channels = 0;  // RePaint: 1 or C
         const void *noise = nullptr, *all_steps = nullptr, *ws = nullptr, *times = nullptr, *coefs = nullptr;
+        const void* tab = nullptr;  // the 16-float-row table (edm_tab_dev) of the EDM, continuous-time and RePaint steps
         bool operator==(const GraphKey& o) const {
             return kind == o.kind && B == o.B && H == o.H && W == o.W && ctx_tokens == o.ctx_tokens &&
-                   cond_channels == o.cond_channels && objective == o.objective && self_cond == o.self_cond && guided == o.guided && edm_clamp == o.edm_clamp && noise == o.noise && all_steps == o.all_steps && ws == o.ws &&
-                   times == o.times && coefs == o.coefs;
+                   cond_channels == o.cond_channels && objective == o.objective && self_cond == o.self_cond &&
+                   guided == o.guided && edm_clamp == o.edm_clamp && ct_clip == o.ct_clip && mask_channels == o.mask_channels &&
+                   noise == o.noise && all_steps == o.all_steps && ws == o.ws && times == o.times && coefs == o.coefs &&
+                   tab == o.tab;
         }
     } gkey;
     hipGraph_t graph = nullptr;
@@ -342,8 +349,8 @@ struct dm_unet {
         done_recorded = true;
         return 0;
     }
-    // ElucidatedDiffusion (dm_edm.inc): device step table and the graph of the last Heun step (sigma_next == 0: one
-    // forward); the graph of a full step is `graph` / `gexec` above, keyed by kind = DM_EDM_* + 2
+    // ElucidatedDiffusion (dm_edm.inc): device step table (continuous time and RePaint keep theirs in it too) and the graph
+    // of the last Heun step (sigma_next == 0: one forward); the graph of a full step is `graph` / `gexec` above
     float* edm_tab_dev = nullptr;
     int edm_cap = 0;
     hipGraph_t edm_last_graph = nullptr;
@@ -1626,238 +1633,6 @@ int dm_unet_forward_masked(dm_unet* u, const float* x, const int64_t* time, cons
     return u->mark_done(s);
 }
 
-}  // extern "C"
-
-// The sampling loop behind dm_sample / dm_sample_cond.  cond (B, cond_channels, H, W) is the image condition of
-// DD/denoising_diffusion_image_conditional.py:51-55,156-180: constant over the loop, concatenated behind x in front of
-// init_conv at every step.
-//
-// One denoise step (U-Net forward + update + step counter) touches only handle-owned memory: x, eps, the [x | cond]
-// input, the text context and the final image live at fixed offsets of the workspace, and everything that differs
-// between two calls of one shape (seed, Philox offset, step tables) is device DATA, not a kernel argument.  The step is
-// therefore captured into a hipGraph once per (shape, sampler kind) and the instantiated graph is replayed by every
-// later call; it is re-captured only when the shape, an injected-noise / all-steps pointer or the workspace changes.
-static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_host, const float* coefs_host,
-                       const float* x_T, const float* noise, uint64_t seed, uint64_t sample_offset, const float* ctx,
-                       int ctx_tokens, const float* cond, int cond_channels, float* out, float* all_steps, int B, int H,
-                       int W, int unnormalize, int use_graph, void* stream, int objective = DM_OBJ_PRED_NOISE,
-                       int self_cond = 0, const CfgParams* guide = nullptr) {
-    DM_REQUIRE(u && times_host && coefs_host && x_T && out, "null argument");
-    DM_REQUIRE(u->finalized, "dm_unet_finalize has not been called");
-    DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
-    DM_REQUIRE(!u->infer_stale, "parameters were updated on the device (dm_unet_optimizer_step): call dm_unet_train_sync "
-                                "before sampling from this handle");
-    DM_REQUIRE(kind == DM_SAMPLER_DDPM || kind == DM_SAMPLER_DDIM, "unknown sampler kind");
-    DM_REQUIRE(n_steps > 0 && B > 0, "empty run");
-    DM_REQUIRE(u->out_dim == u->cfg.channels, "sampler needs out_dim == channels (DD/denoising_diffusion.py:456)");
-    DM_REQUIRE((cond == nullptr) == (cond_channels == 0) && cond_channels >= 0, "cond and cond_channels come together");
-    DM_REQUIRE(objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "unknown objective");
-    DM_REQUIRE(!self_cond || cond_channels == 0, "self-conditioning and an image condition are not combined");
-    DM_REQUIRE(u->cfg.input_channels == u->cfg.channels * (self_cond ? 2 : 1) + cond_channels,
-               "U-Net input channels != channels [* 2 with self-conditioning] + cond_channels");
-    DM_REQUIRE((ctx == nullptr) == (ctx_tokens == 0), "ctx and ctx_tokens come together");
-    // classifier-free guidance: every step runs the U-Net on [x | x] with the text mask [1.. | 0..] (B conditioned and
-    // B null images in one forward) and combines the two halves into the model output the update reads
-    const bool guided = guide != nullptr;
-    if (guided) {
-        DM_REQUIRE(u->cfg.text_mode != DM_TEXT_NONE, "classifier-free guidance (cfg_scale != 1) needs a text-conditional U-Net");
-        DM_REQUIRE(ctx != nullptr, "classifier-free guidance needs a text context");
-        DM_REQUIRE(!self_cond, "classifier-free guidance is not combined with self-conditioning");
-        DM_REQUIRE(cond == nullptr, "classifier-free guidance is not combined with an image condition");
-    }
-    const int Bf = guided ? 2 * B : B;  // batch of the U-Net forward
-    if (check_hw(u, H, W)) return 1;
-    DM_CHECK_HIP(hipSetDevice(u->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int C = u->cfg.channels;
-    const int64_t n = (int64_t)B * C * H * W;
-    // the U-Net input when it is wider than x: [x | cond] (image condition) or [x_start | x] (self-conditioning)
-    const int Cin = self_cond ? 2 * C : C + cond_channels;
-    const bool wide = Cin != C;
-    const int64_t n_in = (int64_t)B * Cin * H * W;
-    const int64_t n_ctx = ctx ? (int64_t)B * ctx_tokens * u->cfg.text_emb_dim : 0;
-    const uint64_t elem_off = sample_offset * (uint64_t)C * H * W;  // global element index of this shard's first value
-    DM_REQUIRE(elem_off % 4 == 0, "sample_offset * C * H * W must be a multiple of 4");
-
-    if (!u->state_dev) DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&u->state_dev), 256));
-    if (n_steps > u->sampler_cap) {
-        DM_CHECK_HIP(hipDeviceSynchronize());
-        u->drop_graph();
-        if (u->times_dev) (void)hipFree(u->times_dev);
-        if (u->coefs_dev) (void)hipFree(u->coefs_dev);
-        u->times_dev = nullptr;
-        u->coefs_dev = nullptr;
-        u->sampler_cap = 0;
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&u->times_dev), n_steps * sizeof(int64_t)));
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&u->coefs_dev), (size_t)n_steps * DM_COEFS * sizeof(float)));
-        u->sampler_cap = n_steps;
-    }
-    // graph mode on the legacy default stream: that stream cannot be captured, so the whole call runs on a stream of
-    // the handle, ordered after the caller's work by a synchronisation here and finished before return
-    const bool own_stream = use_graph && s == nullptr;
-    if (own_stream) {
-        if (!u->cap_stream) DM_CHECK_HIP(hipStreamCreateWithFlags(&u->cap_stream, hipStreamNonBlocking));
-        DM_CHECK_HIP(hipStreamSynchronize(nullptr));
-        s = u->cap_stream;
-    }
-    // workspace: [x | eps | [x | cond] | ctx | forward arena]; guided: [x | x copy | eps | 2B model output | ctx | ctx copy |
-    // text mask | guidance parameters | forward arena]
-    const int64_t n_ws = guided ? 2 * n : n;
-    Arena dry;
-    dry.dry = true;
-    dry.alloc(n_ws);
-    dry.alloc(n);
-    if (guided) dry.alloc(2 * n);
-    if (wide) dry.alloc(n_in);
-    if (self_cond) dry.alloc(n);
-    if (ctx) dry.alloc(guided ? 2 * n_ctx : n_ctx);
-    if (guided) {
-        dry.alloc(2 * B);
-        dry.alloc(4);
-    }
-    const float* ctx_marker = ctx ? reinterpret_cast<const float*>(16) : nullptr;
-    const int32_t* mask_marker = guided ? reinterpret_cast<const int32_t*>(16) : nullptr;
-    if (unet_forward_impl(u, dry, nullptr, nullptr, u->times_dev, u->state_dev, ctx_marker, ctx_tokens, nullptr, Bf, H, W, s,
-                          mask_marker))
-        return 1;
-    if (ensure_workspace(u, dry.off)) return 1;
-
-    if (u->order_after_previous(s)) return 1;
-    SamplerState st_host{};
-    st_host.step = 0;
-    st_host.n_steps = n_steps;
-    st_host.unnormalize = unnormalize;
-    st_host.seed = seed;
-    st_host.off4 = elem_off / 4;
-    DM_CHECK_HIP(hipMemcpyAsync(u->times_dev, times_host, n_steps * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    DM_CHECK_HIP(hipMemcpyAsync(u->coefs_dev, coefs_host, (size_t)n_steps * DM_COEFS * sizeof(float),
-                                hipMemcpyHostToDevice, s));
-    DM_CHECK_HIP(hipMemcpyAsync(u->state_dev, &st_host, sizeof(st_host), hipMemcpyHostToDevice, s));
-
-    Arena A;
-    A.base = u->ws;
-    A.cap = u->ws_cap;
-    float* xbuf = A.alloc(n_ws);  // guided: [x | x], the U-Net input of both halves
-    float* eps = A.alloc(n);
-    float* eps2 = guided ? A.alloc(2 * n) : nullptr;  // model output of the conditioned and the null half
-    float* xin = wide ? A.alloc(n_in) : nullptr;  // [x | cond] or [x_start | x] per image, what init_conv reads
-    float* xstart = self_cond ? A.alloc(n) : nullptr;  // clamped x_0 estimate of the previous step
-    float* ctxbuf = ctx ? A.alloc(guided ? 2 * n_ctx : n_ctx) : nullptr;
-    int32_t* tmask = guided ? reinterpret_cast<int32_t*>(A.alloc(2 * B)) : nullptr;
-    float* gpar = guided ? A.alloc(4) : nullptr;  // CfgParams: device data, so a captured step serves any guidance scale
-    std::vector<int32_t> tmask_host;
-    if (guided) {
-        tmask_host.assign(2 * B, 0);
-        std::fill(tmask_host.begin(), tmask_host.begin() + B, 1);
-        DM_CHECK_HIP(hipMemcpyAsync(tmask, tmask_host.data(), 2 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        DM_CHECK_HIP(hipMemcpyAsync(gpar, guide, sizeof(CfgParams), hipMemcpyHostToDevice, s));
-    }
-    DM_CHECK_HIP(hipStreamSynchronize(s));  // the host tables and st_host may go away when this function returns
-    const std::vector<Arena::Blk> arena_mark = A.blks;  // allocator state in front of a denoise step
-    DM_CHECK_HIP(hipMemcpyAsync(xbuf, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (ctx) DM_CHECK_HIP(hipMemcpyAsync(ctxbuf, ctx, n_ctx * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (guided) {  // the null half reads the same x and (unused) context rows
-        DM_CHECK_HIP(hipMemcpyAsync(xbuf + n, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        DM_CHECK_HIP(hipMemcpyAsync(ctxbuf + n_ctx, ctx, n_ctx * sizeof(float), hipMemcpyDeviceToDevice, s));
-    }
-    if (cond && launch_copy_channels(cond, xin, B, cond_channels, C + cond_channels, C, H * W, s)) return 1;
-    if (self_cond) DM_CHECK_HIP(hipMemsetAsync(xstart, 0, n * sizeof(float), s));  // x_self_cond = zeros_like(x) (:353)
-    if (all_steps) DM_CHECK_HIP(hipMemcpyAsync(all_steps, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-
-    auto one_step = [&](hipStream_t st) -> int {
-        A.blks = arena_mark;
-        if (cond && launch_copy_channels(xbuf, xin, B, C, Cin, 0, H * W, st)) return 1;
-        if (self_cond && (launch_copy_channels(xstart, xin, B, C, Cin, 0, H * W, st) ||
-                          launch_copy_channels(xbuf, xin, B, C, Cin, C, H * W, st)))
-            return 1;
-        if (guided) {
-            if (unet_forward_impl(u, A, xbuf, nullptr, u->times_dev, u->state_dev, ctxbuf, ctx_tokens, eps2, Bf, H, W, st,
-                                  tmask))
-                return 1;
-            if (launch_cfg_combine(eps2, eps2 + n, eps, B, n / B, gpar, CfgParams{}, st)) return 1;
-        } else if (unet_forward_impl(u, A, wide ? xin : xbuf, nullptr, u->times_dev, u->state_dev, ctxbuf, ctx_tokens, eps,
-                                     B, H, W, st)) {
-            return 1;
-        }
-        // guided: x_{t-1} goes to both halves of the next step's input
-        if (launch_sampler_update(kind, xbuf, eps, noise, u->coefs_dev, u->state_dev, n, xbuf, all_steps, nullptr, n, st,
-                                  objective, xstart, guided ? xbuf + n : nullptr))
-            return 1;
-        return launch_step_advance(u->state_dev, st);
-    };
-    auto finish = [&]() -> int {  // out = x_0 [ (x + 1) / 2 ]
-        if (launch_finalize(xbuf, out, n, unnormalize, s)) return 1;
-        if (u->mark_done(s)) return 1;
-        if (own_stream) DM_CHECK_HIP(hipStreamSynchronize(s));
-        return 0;
-    };
-
-    if (!use_graph) {
-        // profiling leg: park the GPU while the host enqueues, so that event intervals are kernel times (<= 8 steps)
-        if (prof::enabled() && n_steps <= 8 && launch_spin(8.0 * n_steps, s)) return 1;
-        for (int i = 0; i < n_steps; ++i)
-            if (one_step(s)) return 1;
-        return finish();
-    }
-    dm_unet::GraphKey key;
-    key.kind = kind; key.B = B; key.H = H; key.W = W; key.ctx_tokens = ctx_tokens; key.cond_channels = cond_channels;
-    key.objective = objective; key.self_cond = self_cond; key.guided = guided;
-    key.noise = noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.coefs = u->coefs_dev;
-    if (!u->gexec || !(u->gkey == key)) {
-        u->drop_graph();
-        DM_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        int rc = one_step(s);
-        hipGraph_t graph = nullptr;
-        hipError_t ce = hipStreamEndCapture(s, &graph);
-        if (rc || ce != hipSuccess) {
-            if (graph) (void)hipGraphDestroy(graph);
-            if (!rc) set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-            return 1;
-        }
-        hipGraphExec_t exec = nullptr;
-        hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) {
-            (void)hipGraphDestroy(graph);
-            set_error(std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
-            return 1;
-        }
-        u->graph = graph;
-        u->gexec = exec;
-        u->gkey = key;
-        u->graph_captures += 1;
-    }
-    for (int i = 0; i < n_steps; ++i) DM_CHECK_HIP(hipGraphLaunch(u->gexec, s));
-    return finish();
-}
-
-extern "C" {
-
-int dm_sample(dm_unet* u, int kind, int n_steps, const int64_t* times_host, const float* coefs_host,
-              const float* x_T, const float* noise, uint64_t seed, uint64_t sample_offset, const float* ctx,
-              int ctx_tokens, float* out, float* all_steps, int B, int H, int W, int unnormalize, int use_graph,
-              void* stream) {
-    return sample_impl(u, kind, n_steps, times_host, coefs_host, x_T, noise, seed, sample_offset, ctx, ctx_tokens,
-                       nullptr, 0, out, all_steps, B, H, W, unnormalize, use_graph, stream);
-}
-
-int dm_sample_cond(dm_unet* u, int kind, int n_steps, const int64_t* times_host, const float* coefs_host,
-                   const float* x_T, const float* noise, uint64_t seed, uint64_t sample_offset, const float* ctx,
-                   int ctx_tokens, const float* cond, int cond_channels, float* out, float* all_steps, int B, int H,
-                   int W, int unnormalize, int use_graph, void* stream) {
-    DM_REQUIRE(cond && cond_channels > 0, "dm_sample_cond needs a condition image");
-    return sample_impl(u, kind, n_steps, times_host, coefs_host, x_T, noise, seed, sample_offset, ctx, ctx_tokens, cond,
-                       cond_channels, out, all_steps, B, H, W, unnormalize, use_graph, stream);
-}
-
-int dm_sample_ex(dm_unet* u, const dm_sample_args* a) {
-    DM_REQUIRE(u && a, "null argument");
-    DM_REQUIRE(a->cfg_remove_parallel == 0 || a->cfg_remove_parallel == 1, "cfg_remove_parallel is 0 or 1");
-    const CfgParams g{a->cfg_scale, a->cfg_rescaled_phi, a->cfg_keep_parallel_frac, (float)a->cfg_remove_parallel};
-    return sample_impl(u, a->kind, a->n_steps, a->times_host, a->coefs_host, a->x_T, a->noise, a->seed, a->sample_offset,
-                       a->ctx, a->ctx_tokens, a->cond, a->cond_channels, a->out, a->all_steps, a->B, a->H, a->W,
-                       a->unnormalize, a->use_graph, a->stream, a->objective, a->self_condition, a->cfg ? &g : nullptr);
-}
-
 int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t element_offset, void* stream) {
     DM_REQUIRE(out && n >= 0, "bad argument");
     return launch_randn(out, n, seed, draw, element_offset, static_cast<hipStream_t>(stream));
@@ -1871,6 +1646,7 @@ int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t eleme
 #include "dm_consumer.inc"
 #include "dm_train.inc"
 #include "dm_train_ops.inc"
+#include "dm_sampler.inc"
 #include "dm_edm.inc"
 #include "dm_ct.inc"
 #include "dm_repaint.inc"

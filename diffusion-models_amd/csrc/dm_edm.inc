@@ -1,40 +1,13 @@
-// ElucidatedDiffusion on the C ABI: the float-time forward, the two sampling loops, the training loss + backward and the
-// single-pass entry points (dm_op_edm_*).  Included by dm_api.hip; kernels in edm.hip.
+// ElucidatedDiffusion on the C ABI: the float-time forward, the two sampling loops, the float-time training driver (which
+// continuous time shares) with the EDM loss + backward, and the single-pass entry points (dm_op_edm_*).  Included by
+// dm_api.hip after dm_sampler.inc, whose loop scaffolding it runs on; kernels in edm.hip.
 
 namespace dm {
 
 static int edm_handle_ok(dm_unet* u) {
-    DM_REQUIRE(u->finalized, "dm_unet_finalize has not been called");
-    DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
-    DM_REQUIRE(!u->infer_stale, "parameters were updated on the device (dm_unet_optimizer_step): call dm_unet_train_sync "
-                                "before sampling from this handle");
+    if (handle_ready(u)) return 1;
     DM_REQUIRE(u->cfg.learned_sinusoidal_dim > 0,
                "a real-valued time needs a learned / random sinusoidal U-Net (ElucidatedDiffusion asserts it)");
-    return 0;
-}
-
-// capture fn(s) into an instantiated graph
-static int edm_capture(dm_unet* u, hipStream_t s, const std::function<int(hipStream_t)>& fn, hipGraph_t* g_out,
-                       hipGraphExec_t* e_out) {
-    DM_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    int rc = fn(s);
-    hipGraph_t graph = nullptr;
-    hipError_t ce = hipStreamEndCapture(s, &graph);
-    if (rc || ce != hipSuccess) {
-        if (graph) (void)hipGraphDestroy(graph);
-        if (!rc) set_error(std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        return 1;
-    }
-    hipGraphExec_t exec = nullptr;
-    hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    if (ie != hipSuccess) {
-        (void)hipGraphDestroy(graph);
-        set_error(std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
-        return 1;
-    }
-    *g_out = graph;
-    *e_out = exec;
-    u->graph_captures += 1;
     return 0;
 }
 
@@ -47,68 +20,40 @@ static int sample_edm_impl(dm_unet* u, const dm_edm_args* a) {
     DM_REQUIRE(a->table_host && a->x_init && a->out, "null argument");
     DM_REQUIRE(a->n_steps > 0 && a->B > 0, "empty run");
     if (edm_handle_ok(u)) return 1;
-    DM_REQUIRE(u->cfg.text_mode == DM_TEXT_NONE, "ElucidatedDiffusion calls net(x, t, self_cond) only: no text-conditional U-Net");
-    DM_REQUIRE(u->out_dim == u->cfg.channels && u->cfg.input_channels == u->cfg.channels,
-               "ElucidatedDiffusion needs a U-Net with out_dim == input channels == channels (no self-conditioning, no image "
-               "condition, no learned variance)");
+    if (plain_unet_ok(u,
+                      "ElucidatedDiffusion needs a U-Net with out_dim == input channels == channels (no self-conditioning, no image "
+                      "condition, no learned variance)",
+                      "ElucidatedDiffusion calls net(x, t, self_cond) only: no text-conditional U-Net"))
+        return 1;
     const int B = a->B, H = a->H, W = a->W, n_steps = a->n_steps, clamp = a->clamp ? 1 : 0;
     const bool heun = a->kind == DM_EDM_HEUN;
     if (check_hw(u, H, W)) return 1;
     DM_CHECK_HIP(hipSetDevice(u->device));
-    hipStream_t s = static_cast<hipStream_t>(a->stream);
     const int C = u->cfg.channels;
     const int64_t per = (int64_t)C * H * W, n = (int64_t)B * per;
     DM_REQUIRE(per % 4 == 0, "C * H * W must be a multiple of 4");
     const float* noise = a->noise;
     const float* tab_host = a->table_host;
 
-    if (!u->state_dev) DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&u->state_dev), 256));
-    if (n_steps > u->edm_cap) {
-        DM_CHECK_HIP(hipDeviceSynchronize());
-        u->drop_graph();
-        if (u->edm_tab_dev) (void)hipFree(u->edm_tab_dev);
-        u->edm_tab_dev = nullptr;
-        u->edm_cap = 0;
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&u->edm_tab_dev), (size_t)n_steps * DM_EDM_COEFS * sizeof(float)));
-        u->edm_cap = n_steps;
-    }
-    const bool own_stream = a->use_graph && s == nullptr;
-    if (own_stream) {
-        if (!u->cap_stream) DM_CHECK_HIP(hipStreamCreateWithFlags(&u->cap_stream, hipStreamNonBlocking));
-        DM_CHECK_HIP(hipStreamSynchronize(nullptr));
-        s = u->cap_stream;
-    }
+    SamplerRun r;
+    if (grow_tables(u, TAB_FLOAT, n_steps, 1) || run_begin(r, u, a->stream, a->use_graph)) return 1;
+    hipStream_t s = r.s;
     // workspace: Heun [x | xhat | xin | F | d | forward arena], DPM++ [x | xin | F | d_old | forward arena]
-    const int n_bufs = heun ? 5 : 4;
-    Arena dry;
-    dry.dry = true;
-    for (int i = 0; i < n_bufs; ++i) dry.alloc(n);
+    float *x, *xhat, *xin, *F, *d;
+    auto layout = [&](Arena& A) {
+        x = A.alloc(n);
+        xhat = heun ? A.alloc(n) : nullptr;
+        xin = A.alloc(n);
+        F = A.alloc(n);
+        d = A.alloc(n);  // Heun: d of the Euler step; DPM++: the previous step's denoised image
+    };
     const float* tf_marker = reinterpret_cast<const float*>(16);
-    if (unet_forward_impl(u, dry, nullptr, nullptr, nullptr, u->state_dev, nullptr, 0, nullptr, B, H, W, s, nullptr, tf_marker,
-                          DM_EDM_COEFS))
+    if (run_workspace(r, layout, [&](Arena& dry) {
+            return unet_forward_impl(u, dry, nullptr, nullptr, nullptr, u->state_dev, nullptr, 0, nullptr, B, H, W, s, nullptr,
+                                     tf_marker, DM_EDM_COEFS);
+        }))
         return 1;
-    if (ensure_workspace(u, dry.off)) return 1;
-
-    if (u->order_after_previous(s)) return 1;
-    SamplerState st_host{};
-    st_host.step = 0;
-    st_host.n_steps = n_steps;
-    st_host.seed = a->seed;
-    const uint64_t elem_off = a->sample_offset * (uint64_t)per;
-    st_host.off4 = elem_off / 4;
-    DM_CHECK_HIP(hipMemcpyAsync(u->edm_tab_dev, tab_host, (size_t)n_steps * DM_EDM_COEFS * sizeof(float), hipMemcpyHostToDevice, s));
-    DM_CHECK_HIP(hipMemcpyAsync(u->state_dev, &st_host, sizeof(st_host), hipMemcpyHostToDevice, s));
-    DM_CHECK_HIP(hipStreamSynchronize(s));  // st_host may go away when this function returns
-
-    Arena A;
-    A.base = u->ws;
-    A.cap = u->ws_cap;
-    float* x = A.alloc(n);
-    float* xhat = heun ? A.alloc(n) : nullptr;
-    float* xin = A.alloc(n);
-    float* F = A.alloc(n);
-    float* d = A.alloc(n);  // Heun: d of the Euler step; DPM++: the previous step's denoised image
-    const std::vector<Arena::Blk> arena_mark = A.blks;
+    if (run_upload(r, n_steps, nullptr, nullptr, tab_host, 0, a->seed, a->sample_offset * (uint64_t)per)) return 1;
     const float* tab = u->edm_tab_dev;
     const EdmRows rows{tab, u->state_dev, EDM_ROW_STEP, per};
 
@@ -116,8 +61,8 @@ static int sample_edm_impl(dm_unet* u, const dm_edm_args* a) {
     if (!heun) DM_CHECK_HIP(hipMemsetAsync(d, 0, n * sizeof(float), s));
 
     auto forward = [&](hipStream_t st, int col) -> int {
-        A.blks = arena_mark;
-        return unet_forward_impl(u, A, xin, nullptr, nullptr, u->state_dev, nullptr, 0, F, B, H, W, st, nullptr, tab + col,
+        r.rewind();
+        return unet_forward_impl(u, r.A, xin, nullptr, nullptr, u->state_dev, nullptr, 0, F, B, H, W, st, nullptr, tab + col,
                                  DM_EDM_COEFS);
     };
     // second == false: the loop's last step, images = images_next of the Euler step (:176)
@@ -137,46 +82,21 @@ static int sample_edm_impl(dm_unet* u, const dm_edm_args* a) {
         if (launch_edm_dpmpp(x, F, d, rows, x, n, st)) return 1;
         return launch_step_advance(u->state_dev, st);
     };
-    auto is_full = [&](int i) { return heun && tab_host[(size_t)i * DM_EDM_COEFS + EDM_SIGMA2] != 0.0f; };
-    auto finish = [&]() -> int {
-        if (launch_edm_finalize(x, a->out, n, s)) return 1;
-        if (u->mark_done(s)) return 1;
-        if (own_stream) DM_CHECK_HIP(hipStreamSynchronize(s));
-        return 0;
-    };
-
-    if (!a->use_graph) {
-        for (int i = 0; i < n_steps; ++i)
-            if (heun ? heun_step(s, is_full(i)) : dpmpp_step(s)) return 1;
-        return finish();
-    }
     dm_unet::GraphKey key;
-    // the handle's graph slot is shared with DDPM / DDIM: EDM kinds follow the DM_SAMPLER_* values
-    constexpr int kEdmKindBase = 2;
-    static_assert(DM_SAMPLER_DDPM < kEdmKindBase && DM_SAMPLER_DDIM < kEdmKindBase && DM_EDM_HEUN >= 0 && DM_EDM_DPMPP >= 0,
-                  "EDM graph kinds must not collide with DM_SAMPLER_*");
-    key.kind = kEdmKindBase + a->kind;
+    key.kind = heun ? dm_unet::GK_EDM_HEUN : dm_unet::GK_EDM_DPMPP;
     key.B = B; key.H = H; key.W = W;
     key.edm_clamp = clamp;
-    key.noise = noise; key.ws = u->ws; key.coefs = u->edm_tab_dev;
-    if (!(u->gkey == key)) {
-        u->drop_graph();
-        u->gkey = key;
+    key.noise = noise; key.ws = u->ws; key.tab = u->edm_tab_dev;
+    if (heun) {
+        if (run_steps(r, key, n_steps, [&](hipStream_t st) { return heun_step(st, true); },
+                      [&](hipStream_t st) { return heun_step(st, false); },
+                      [&](int i) { return tab_host[(size_t)i * DM_EDM_COEFS + EDM_SIGMA2] != 0.0f; }))
+            return 1;
+    } else if (run_steps(r, key, n_steps, dpmpp_step)) {
+        return 1;
     }
-    for (int i = 0; i < n_steps; ++i) {
-        const bool full = heun ? is_full(i) : true;
-        hipGraph_t* g = full ? &u->graph : &u->edm_last_graph;
-        hipGraphExec_t* e = full ? &u->gexec : &u->edm_last_gexec;
-        if (!*e) {
-            const std::function<int(hipStream_t)> fn = [&](hipStream_t st) { return heun ? heun_step(st, full) : dpmpp_step(st); };
-            if (edm_capture(u, s, fn, g, e)) {
-                u->drop_graph();
-                return 1;
-            }
-        }
-        DM_CHECK_HIP(hipGraphLaunch(*e, s));
-    }
-    return finish();
+    if (launch_edm_finalize(x, a->out, n, s)) return 1;
+    return run_finish(r);
 }
 
 // one stand-alone pass: upload `rows` table rows, run fn, wait
@@ -206,22 +126,39 @@ static int edm_rows(const float* tab, int rows, int B, int64_t per, EdmRows* out
     return 0;
 }
 
-// ElucidatedDiffusion.forward (DD/elucidated_diffusion.py:234-264) + backward on a handle armed by dm_unet_train_enable_ft:
-// the noise-in pass, the tape forward with c_noise(sigma) as a float time, the weighted loss with its gradient, then the
-// backward pass of the p_losses path, which goes on through time_mlp.1 into the embedding's weights.  Workspace, arena and
-// stream ordering follow loss_backward_impl.
-static int loss_backward_edm_impl(dm_unet* u, const dm_edm_train_args& a) {
-    DM_REQUIRE(a.images && a.noise && a.coef_host, "null argument");
-    DM_REQUIRE(u->train && u->train->ft, "dm_unet_train_enable_ft has not been called");
-    DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
-    const int cstride = a.coef_stride ? a.coef_stride : DM_EDM_COEFS;
-    DM_REQUIRE(a.B > 0 && cstride > EDM_LOSS_W, "coef_host rows hold at least 15 floats (loss_weight is column 14)");
-    DM_REQUIRE(u->cfg.text_mode == DM_TEXT_NONE && u->out_dim == u->cfg.channels && u->cfg.input_channels == u->cfg.channels,
-               "ElucidatedDiffusion needs a U-Net with out_dim == input channels == channels and no text conditioning");
-    const int B = a.B, H = a.H, W = a.W, accumulate = a.accumulate ? 1 : 0;
-    if (check_hw(u, H, W)) return 1;
+// One SamplerState for a stand-alone pass next to its table rows (edm_op): upload, run fn, wait, free.
+static int state_op(const SamplerState& st_host, const float* c_host, int rows, void* stream,
+                    const std::function<int(const SamplerState*, const float*, hipStream_t)>& fn) {
+    SamplerState* st_dev = nullptr;
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&st_dev), sizeof(SamplerState)));
+    hipError_t e = hipMemcpy(st_dev, &st_host, sizeof(st_host), hipMemcpyHostToDevice);
+    int rc = 1;
+    if (e == hipSuccess) rc = edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) { return fn(st_dev, cd, s); });
+    else set_error(std::string("hipMemcpy: ") + hipGetErrorString(e));
+    (void)hipFree(st_dev);
+    return rc;
+}
+// The kernels draw `step + 1`: a state with step = draw - 1 selects the draw (with injected noise: none).
+static SamplerState draw_state(bool injected, uint64_t seed, uint64_t draw, uint64_t element_offset) {
+    SamplerState st{};
+    st.step = injected ? 0 : (int)(draw - 1);
+    st.n_steps = st.step + 1;
+    st.seed = seed;
+    st.off4 = element_offset / 4;
+    return st;
+}
+
+// Loss + backward at a real-valued time on a handle armed by dm_unet_train_enable_ft, for ElucidatedDiffusion and
+// continuous time: the per-image coefficient rows (DM_EDM_COEFS floats on the device, `cstride` on the host) and column
+// `tf_col` of them as the float times the embedding reads, then run(arena, tape) -- the caller's noise-in pass, tape
+// forward, loss with its gradient and backward pass, which goes on through time_mlp.1 into the embedding's weights.
+// run is called twice: on a dry arena to size the workspace (once per key_tag, shape and key_flags), then for real.
+// Workspace, arena and stream ordering follow loss_backward_impl.
+static int loss_backward_ft(dm_unet* u, int B, int H, int W, const float* coef_host, int cstride, int tf_col, long long key_tag,
+                            long long key_flags, float* loss_out_host, void* stream,
+                            const std::function<int(Arena&, Tape&)>& run) {
     DM_CHECK_HIP(hipSetDevice(u->device));
-    hipStream_t s = static_cast<hipStream_t>(a.stream);
+    hipStream_t s = static_cast<hipStream_t>(stream);
     TrainState& T = *u->train;
     if (B > T.edm_cap_B) {
         DM_CHECK_HIP(hipDeviceSynchronize());
@@ -232,25 +169,10 @@ static int loss_backward_edm_impl(dm_unet* u, const dm_edm_train_args& a) {
         DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.tf_dev), (size_t)B * sizeof(float)));
         T.edm_cap_B = B;
     }
-    const int64_t per = (int64_t)u->cfg.channels * H * W, n = (int64_t)B * per;
-    DM_REQUIRE(per % 4 == 0, "C * H * W must be a multiple of 4");
-    const EdmRows rows{T.edm_coef_dev, nullptr, B > 1 ? EDM_ROW_IMAGE : EDM_ROW_FIRST, per};
-    auto run = [&](Arena& A, Tape& tp) -> int {
-        float* x0 = A.alloc(n);
-        float* noised = A.alloc(n);
-        float* xin = A.alloc(n);
-        float* F = A.alloc(n);
-        float* dF = A.alloc(n);
-        float* part = A.alloc(B);
-        if (!A.dry && launch_edm_noise_in(a.images, a.noise, rows, x0, noised, xin, n, s)) return 1;
-        if (unet_train_forward(u, A, xin, nullptr, F, B, H, W, s, tp, nullptr, 0, nullptr, T.tf_dev)) return 1;
-        if (!A.dry && launch_edm_loss(noised, F, x0, T.edm_coef_dev, dF, a.denoised_out, part, T.loss_dev, B, per, a.loss_scale, s))
-            return 1;
-        return unet_train_backward(u, A, xin, dF, B, H, W, s, tp, accumulate);
-    };
+    DM_REQUIRE((int64_t)u->cfg.channels * H * W % 4 == 0, "C * H * W must be a multiple of 4");
     try {
         // (the fourth entry is self_cond on the integer-time path, never negative there)
-        const std::array<long long, 8> key{B, H, W, -1, 0, 0, 0, (a.denoised_out ? 1 : 0) | (T.bucketed ? 2 : 0)};
+        const std::array<long long, 8> key{B, H, W, key_tag, 0, 0, 0, key_flags | (T.bucketed ? 2 : 0)};
         auto known = T.ws_need.find(key);
         if (known == T.ws_need.end()) {
             Arena dry;
@@ -265,8 +187,8 @@ static int loss_backward_edm_impl(dm_unet* u, const dm_edm_train_args& a) {
         T.coef_stage.assign((size_t)B * DM_EDM_COEFS + B, 0.f);
         const int ncopy = cstride < DM_EDM_COEFS ? cstride : DM_EDM_COEFS;
         for (int b = 0; b < B; ++b) {
-            std::memcpy(&T.coef_stage[(size_t)b * DM_EDM_COEFS], a.coef_host + (size_t)b * cstride, ncopy * sizeof(float));
-            T.coef_stage[(size_t)B * DM_EDM_COEFS + b] = a.coef_host[(size_t)b * cstride + EDM_C_NOISE];
+            std::memcpy(&T.coef_stage[(size_t)b * DM_EDM_COEFS], coef_host + (size_t)b * cstride, ncopy * sizeof(float));
+            T.coef_stage[(size_t)B * DM_EDM_COEFS + b] = coef_host[(size_t)b * cstride + tf_col];
         }
         DM_CHECK_HIP(hipMemcpyAsync(T.edm_coef_dev, T.coef_stage.data(), (size_t)B * DM_EDM_COEFS * sizeof(float),
                                     hipMemcpyHostToDevice, s));
@@ -284,10 +206,44 @@ static int loss_backward_edm_impl(dm_unet* u, const dm_edm_train_args& a) {
         return 1;
     }
     if (u->mark_done(s)) return 1;
-    if (!a.loss_out_host) return 0;  // asynchronous form: the loss stays on the device (dm_unet_train_scalar)
-    DM_CHECK_HIP(hipMemcpyAsync(a.loss_out_host, T.loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+    if (!loss_out_host) return 0;  // asynchronous form: the loss stays on the device (dm_unet_train_scalar)
+    DM_CHECK_HIP(hipMemcpyAsync(loss_out_host, T.loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
     DM_CHECK_HIP(hipStreamSynchronize(s));
     return 0;
+}
+
+static const char* const kEdmTrainUnet =
+    "ElucidatedDiffusion needs a U-Net with out_dim == input channels == channels and no text conditioning";
+
+// ElucidatedDiffusion.forward (DD/elucidated_diffusion.py:234-264) + backward: the noise-in pass, the tape forward with
+// c_noise(sigma) as the float time, the weighted loss with its gradient, the backward pass.
+static int loss_backward_edm_impl(dm_unet* u, const dm_edm_train_args& a) {
+    DM_REQUIRE(a.images && a.noise && a.coef_host, "null argument");
+    DM_REQUIRE(u->train && u->train->ft, "dm_unet_train_enable_ft has not been called");
+    DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
+    const int cstride = a.coef_stride ? a.coef_stride : DM_EDM_COEFS;
+    DM_REQUIRE(a.B > 0 && cstride > EDM_LOSS_W, "coef_host rows hold at least 15 floats (loss_weight is column 14)");
+    if (plain_unet_ok(u, kEdmTrainUnet)) return 1;
+    const int B = a.B, H = a.H, W = a.W, accumulate = a.accumulate ? 1 : 0;
+    if (check_hw(u, H, W)) return 1;
+    hipStream_t s = static_cast<hipStream_t>(a.stream);
+    TrainState& T = *u->train;
+    const int64_t per = (int64_t)u->cfg.channels * H * W, n = (int64_t)B * per;
+    auto run = [&](Arena& A, Tape& tp) -> int {
+        const EdmRows rows{T.edm_coef_dev, nullptr, B > 1 ? EDM_ROW_IMAGE : EDM_ROW_FIRST, per};
+        float* x0 = A.alloc(n);
+        float* noised = A.alloc(n);
+        float* xin = A.alloc(n);
+        float* F = A.alloc(n);
+        float* dF = A.alloc(n);
+        float* part = A.alloc(B);
+        if (!A.dry && launch_edm_noise_in(a.images, a.noise, rows, x0, noised, xin, n, s)) return 1;
+        if (unet_train_forward(u, A, xin, nullptr, F, B, H, W, s, tp, nullptr, 0, nullptr, T.tf_dev)) return 1;
+        if (!A.dry && launch_edm_loss(noised, F, x0, T.edm_coef_dev, dF, a.denoised_out, part, T.loss_dev, B, per, a.loss_scale, s))
+            return 1;
+        return unet_train_backward(u, A, xin, dF, B, H, W, s, tp, accumulate);
+    };
+    return loss_backward_ft(u, B, H, W, a.coef_host, cstride, EDM_C_NOISE, -1, a.denoised_out ? 1 : 0, a.loss_out_host, a.stream, run);
 }
 
 }  // namespace dm
@@ -325,28 +281,13 @@ int dm_op_edm_churn_in(const float* x, const float* eps, const float* c_host, in
     DM_REQUIRE(x && xin, "null argument");
     DM_REQUIRE(element_offset % 4 == 0, "Philox element offset must be a multiple of 4 (one counter serves 4 elements)");
     DM_REQUIRE(eps || draw >= 1, "Philox draw 0 is the initial noise: a step's draw is its index + 1");
-    // the kernel draws `step + 1`: a state with step = draw - 1 selects the draw; the table row is 0 or the image's
-    SamplerState st_host{};
-    st_host.step = eps ? 0 : (int)(draw - 1);
-    st_host.n_steps = st_host.step + 1;
-    st_host.seed = seed;
-    st_host.off4 = element_offset / 4;
-    SamplerState* st_dev = nullptr;
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&st_dev), sizeof(SamplerState)));
-    hipError_t e = hipMemcpy(st_dev, &st_host, sizeof(st_host), hipMemcpyHostToDevice);
-    int rc = 1;
-    if (e == hipSuccess) {
-        rc = edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
-            EdmRows r;
-            if (edm_rows(cd, rows, B, per, &r)) return 1;
-            r.st = st_dev;
-            return launch_edm_churn_in(x, eps, 0, r, xhat, xin, (int64_t)B * per, s);
-        });
-    } else {
-        set_error(std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(st_dev);
-    return rc;
+    return state_op(draw_state(eps != nullptr, seed, draw, element_offset), c_host, rows, stream,
+                    [&](const SamplerState* st, const float* cd, hipStream_t s) {
+                        EdmRows r;
+                        if (edm_rows(cd, rows, B, per, &r)) return 1;
+                        r.st = st;
+                        return launch_edm_churn_in(x, eps, 0, r, xhat, xin, (int64_t)B * per, s);
+                    });
 }
 
 int dm_op_edm_euler(const float* xhat, const float* F, const float* c_host, int rows, int clamp, float* D_out, float* d_out,
@@ -389,8 +330,7 @@ int dm_unet_train_enable_ft(dm_unet* u, int time_weights_frozen) {
     DM_REQUIRE(u->cfg.learned_sinusoidal_dim > 0,
                "float-time training is for the learned / random sinusoidal U-Net ElucidatedDiffusion asserts: every other U-Net "
                "trains through dm_unet_train_enable");
-    DM_REQUIRE(u->cfg.text_mode == DM_TEXT_NONE && u->out_dim == u->cfg.channels && u->cfg.input_channels == u->cfg.channels,
-               "ElucidatedDiffusion needs a U-Net with out_dim == input channels == channels and no text conditioning");
+    if (plain_unet_ok(u, kEdmTrainUnet)) return 1;
     if (train_enable_impl(u, true)) return 1;
     // the handle's configuration does not say which of the two embeddings it holds: the caller does, at the one call that arms it
     u->train->freqs_frozen = time_weights_frozen != 0;

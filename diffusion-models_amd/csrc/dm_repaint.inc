@@ -1,5 +1,6 @@
 // RePaint inpainting on the C ABI: the flattened sampling loop and the single-row entry point (dm_op_repaint_step).
-// Included by dm_api.hip after dm_ct.inc (whose capture helper it shares); kernel in repaint.hip.
+// Included by dm_api.hip after dm_sampler.inc (the loop scaffolding) and dm_edm.inc (the state helper of the dm_op_*
+// passes); kernel in repaint.hip.
 
 namespace dm {
 
@@ -27,14 +28,12 @@ static int sample_repaint_impl(dm_unet* u, const dm_repaint_args* a) {
     DM_REQUIRE(a->times_host && a->table_host && a->x_T && a->gt && a->mask && a->out, "null argument");
     DM_REQUIRE(a->n_rows > 0 && a->B > 0, "empty run");
     DM_REQUIRE(a->objective >= DM_OBJ_PRED_NOISE && a->objective <= DM_OBJ_PRED_V, "unknown objective");
-    DM_REQUIRE(u->finalized, "dm_unet_finalize has not been called");
-    DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
-    DM_REQUIRE(!u->infer_stale, "parameters were updated on the device (dm_unet_optimizer_step): call dm_unet_train_sync "
-                                "before sampling from this handle");
-    DM_REQUIRE(u->cfg.text_mode == DM_TEXT_NONE && u->cfg.learned_sinusoidal_dim == 0,
-               "RePaint calls model(x, t) with an integer time: no text-conditional or float-time U-Net");
-    DM_REQUIRE(u->out_dim == u->cfg.channels && u->cfg.input_channels == u->cfg.channels,
-               "RePaint needs a U-Net with out_dim == input channels == channels (no self-conditioning, no image condition)");
+    if (handle_ready(u)) return 1;
+    const char* const time_msg = "RePaint calls model(x, t) with an integer time: no text-conditional or float-time U-Net";
+    DM_REQUIRE(u->cfg.learned_sinusoidal_dim == 0, time_msg);
+    if (plain_unet_ok(u, "RePaint needs a U-Net with out_dim == input channels == channels (no self-conditioning, no image condition)",
+                      time_msg))
+        return 1;
     const int B = a->B, H = a->H, W = a->W, n_rows = a->n_rows, objective = a->objective;
     const int C = u->cfg.channels, Cm = a->mask_channels, HW = H * W;
     DM_REQUIRE(Cm == 1 || Cm == C, "the mask has 1 or C channels");
@@ -42,71 +41,29 @@ static int sample_repaint_impl(dm_unet* u, const dm_repaint_args* a) {
     if (check_hw(u, H, W)) return 1;
     if (repaint_table_ok(a->table_host, n_rows, a->n_frames, a->all_steps != nullptr)) return 1;
     DM_CHECK_HIP(hipSetDevice(u->device));
-    hipStream_t s = static_cast<hipStream_t>(a->stream);
     const int64_t per = (int64_t)C * HW, n = (int64_t)B * per, n_mask = (int64_t)B * Cm * HW;
     const uint64_t elem_off = a->sample_offset * (uint64_t)per;
     DM_REQUIRE(elem_off % 4 == 0, "sample_offset * C * H * W must be a multiple of 4");
 
-    if (!u->state_dev) DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&u->state_dev), 256));
     // The default loop has about 3000 rows against the 1000 steps of a DDPM run.  The buffers grow in units of 4096 rows,
     // so that a change of the resampling settings keeps their addresses, and with them the captured graph.
-    const int want_cap = (n_rows + 4095) / 4096 * 4096;
-    if (n_rows > u->sampler_cap) {
-        DM_CHECK_HIP(hipDeviceSynchronize());
-        u->drop_graph();
-        if (u->times_dev) (void)hipFree(u->times_dev);
-        if (u->coefs_dev) (void)hipFree(u->coefs_dev);
-        u->times_dev = nullptr;
-        u->coefs_dev = nullptr;
-        u->sampler_cap = 0;
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&u->times_dev), (size_t)want_cap * sizeof(int64_t)));
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&u->coefs_dev), (size_t)want_cap * DM_COEFS * sizeof(float)));
-        u->sampler_cap = want_cap;
-    }
-    if (n_rows > u->edm_cap) {
-        DM_CHECK_HIP(hipDeviceSynchronize());
-        u->drop_graph();
-        if (u->edm_tab_dev) (void)hipFree(u->edm_tab_dev);
-        u->edm_tab_dev = nullptr;
-        u->edm_cap = 0;
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&u->edm_tab_dev), (size_t)want_cap * RP_NCOLS * sizeof(float)));
-        u->edm_cap = want_cap;
-    }
-    const bool own_stream = a->use_graph && s == nullptr;
-    if (own_stream) {
-        if (!u->cap_stream) DM_CHECK_HIP(hipStreamCreateWithFlags(&u->cap_stream, hipStreamNonBlocking));
-        DM_CHECK_HIP(hipStreamSynchronize(nullptr));
-        s = u->cap_stream;
-    }
+    SamplerRun r;
+    if (grow_tables(u, TAB_INT | TAB_FLOAT, n_rows, 4096) || run_begin(r, u, a->stream, a->use_graph)) return 1;
+    hipStream_t s = r.s;
     // workspace: [x | eps | gt | result | mask | forward arena]
-    Arena dry;
-    dry.dry = true;
-    for (int i = 0; i < 4; ++i) dry.alloc(n);
-    dry.alloc(n_mask);
-    if (unet_forward_impl(u, dry, nullptr, nullptr, u->times_dev, u->state_dev, nullptr, 0, nullptr, B, H, W, s)) return 1;
-    if (ensure_workspace(u, dry.off)) return 1;
-
-    if (u->order_after_previous(s)) return 1;
-    SamplerState st_host{};
-    st_host.step = 0;
-    st_host.n_steps = n_rows;
-    st_host.unnormalize = a->unnormalize ? 1 : 0;
-    st_host.seed = a->seed;
-    st_host.off4 = elem_off / 4;
-    DM_CHECK_HIP(hipMemcpyAsync(u->times_dev, a->times_host, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    DM_CHECK_HIP(hipMemcpyAsync(u->edm_tab_dev, a->table_host, (size_t)n_rows * RP_NCOLS * sizeof(float), hipMemcpyHostToDevice, s));
-    DM_CHECK_HIP(hipMemcpyAsync(u->state_dev, &st_host, sizeof(st_host), hipMemcpyHostToDevice, s));
-    DM_CHECK_HIP(hipStreamSynchronize(s));  // the host tables and st_host may go away when this function returns
-
-    Arena A;
-    A.base = u->ws;
-    A.cap = u->ws_cap;
-    float* xbuf = A.alloc(n);
-    float* eps = A.alloc(n);
-    float* gt = A.alloc(n);
-    float* fin = A.alloc(n);  // what the last row leaves for `out`: the caller's pointer stays out of the captured graph
-    float* mask = A.alloc(n_mask);
-    const std::vector<Arena::Blk> arena_mark = A.blks;
+    float *xbuf, *eps, *gt, *fin, *mask;
+    auto layout = [&](Arena& A) {
+        xbuf = A.alloc(n);
+        eps = A.alloc(n);
+        gt = A.alloc(n);
+        fin = A.alloc(n);  // what the last row leaves for `out`: the caller's pointer stays out of the captured graph
+        mask = A.alloc(n_mask);
+    };
+    if (run_workspace(r, layout, [&](Arena& dry) {
+            return unet_forward_impl(u, dry, nullptr, nullptr, u->times_dev, u->state_dev, nullptr, 0, nullptr, B, H, W, s);
+        }))
+        return 1;
+    if (run_upload(r, n_rows, a->times_host, nullptr, a->table_host, a->unnormalize ? 1 : 0, a->seed, elem_off)) return 1;
     const float* tab = u->edm_tab_dev;
     RepaintNoise z;
     if (a->noise) z = RepaintNoise{a->noise, a->noise + n, a->noise + 2 * n, 3 * n};
@@ -122,46 +79,22 @@ static int sample_repaint_impl(dm_unet* u, const dm_repaint_args* a) {
         return 1;
 
     auto row = [&](hipStream_t st) -> int {
-        A.blks = arena_mark;
-        if (unet_forward_impl(u, A, xbuf, nullptr, u->times_dev, u->state_dev, nullptr, 0, eps, B, H, W, st)) return 1;
+        r.rewind();
+        if (unet_forward_impl(u, r.A, xbuf, nullptr, u->times_dev, u->state_dev, nullptr, 0, eps, B, H, W, st)) return 1;
         if (launch_repaint_step(RP_AUTO, objective, xbuf, eps, z, tab, 0, u->state_dev, gt, mask, Cm, per, HW, xbuf, all_steps,
                                 fin, nullptr, n, st))
             return 1;
         return launch_step_advance(u->state_dev, st);
     };
-    auto finish = [&]() -> int {
-        DM_CHECK_HIP(hipMemcpyAsync(a->out, fin, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (u->mark_done(s)) return 1;
-        if (own_stream) DM_CHECK_HIP(hipStreamSynchronize(s));
-        return 0;
-    };
-
-    if (!a->use_graph) {
-        for (int i = 0; i < n_rows; ++i)
-            if (row(s)) return 1;
-        return finish();
-    }
     dm_unet::GraphKey key;
-    // the handle's graph slot is shared with DDPM / DDIM (DM_SAMPLER_*), EDM (2 + DM_EDM_*) and continuous time (4)
-    constexpr int kRepaintKind = 5;
-    key.kind = kRepaintKind;
+    key.kind = dm_unet::GK_REPAINT;
     key.B = B; key.H = H; key.W = W;
     key.objective = objective;
-    key.cond_channels = Cm;  // (no image condition on this path: the field keys the mask's channel count)
-    key.noise = a->noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.coefs = u->edm_tab_dev;
-    if (!(u->gkey == key)) {
-        u->drop_graph();
-        u->gkey = key;
-    }
-    if (!u->gexec) {
-        const std::function<int(hipStream_t)> fn = row;
-        if (edm_capture(u, s, fn, &u->graph, &u->gexec)) {
-            u->drop_graph();
-            return 1;
-        }
-    }
-    for (int i = 0; i < n_rows; ++i) DM_CHECK_HIP(hipGraphLaunch(u->gexec, s));
-    return finish();
+    key.mask_channels = Cm;
+    key.noise = a->noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.tab = u->edm_tab_dev;
+    if (run_steps(r, key, n_rows, row)) return 1;
+    DM_CHECK_HIP(hipMemcpyAsync(a->out, fin, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return run_finish(r);
 }
 
 }  // namespace dm
@@ -202,27 +135,10 @@ int dm_op_repaint_step(int mode, int objective, const float* x, const float* eps
     st_host.unnormalize = unnormalize ? 1 : 0;
     st_host.seed = seed;
     st_host.off4 = element_offset / 4;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char* dev = nullptr;  // [state | table rows]
-    const size_t tab_bytes = (size_t)n_tab * RP_NCOLS * sizeof(float);
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&dev), 256 + tab_bytes));
-    int rc = 1;
-    hipError_t e = hipMemcpy(dev, &st_host, sizeof(st_host), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dev + 256, c_host, tab_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = launch_repaint_step(mode, objective, x, eps, z, reinterpret_cast<const float*>(dev + 256), (int)row,
-                                 reinterpret_cast<const SamplerState*>(dev), gt, mask, mask_channels, per, HW, out, nullptr,
-                                 nullptr, x_start_out, (int64_t)B * per, s);
-        e = hipStreamSynchronize(s);
-        if (!rc && e != hipSuccess) {
-            set_error(std::string("kernel execution failed: ") + hipGetErrorString(e));
-            rc = 1;
-        }
-    } else {
-        set_error(std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(dev);
-    return rc;
+    return state_op(st_host, c_host, n_tab, stream, [&](const SamplerState* st, const float* cd, hipStream_t s) {
+        return launch_repaint_step(mode, objective, x, eps, z, cd, (int)row, st, gt, mask, mask_channels, per, HW, out, nullptr,
+                                   nullptr, x_start_out, (int64_t)B * per, s);
+    });
 }
 
 }  // extern "C"

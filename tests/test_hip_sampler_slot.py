@@ -1,0 +1,163 @@
+"""The four sampling loops on ONE handle: DDPM / DDIM, ElucidatedDiffusion (Heun, DPM-Solver++), continuous time and
+RePaint share the handle's workspace, step tables, sampler state and its single graph slot.
+
+What is pinned here, and nowhere else: a loop that runs after another loop on the same handle gives the bits it gives on
+a fresh handle, captures exactly the graphs of its own kind (Heun two, every other loop one), and captures nothing when
+it is simply called again; tables that grow after a capture do not leave a stale graph behind; and the eager leg is the
+graph leg bit for bit and leaves the slot alone.
+
+Networks and schedules are the tiny ones of the EDM / continuous-time and RePaint golden fixtures (dim 32, mults (1, 2),
+16 x 16, cosine betas), B = 2, at most 4 steps (RePaint: at most 12 rows).
+"""
+import pytest
+import torch
+
+import diffusion_models_amd as dm
+from diffusion_models_amd.spec import UnetConfig
+
+from conftest import load_golden
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+B, SIZE, SEED = 2, 16, 5
+SHAPE = (B, 3, SIZE, SIZE)
+
+
+def _net(ukw, salt):
+    cfg = UnetConfig(channels=3, **ukw)
+    u = dm.Unet(channels=3, device=DEV, **ukw)
+    u.load_state_dict(dm.synth_state_dict(dm.unet_param_spec(cfg), salt=salt))
+    return u
+
+
+def _float_net():
+    c = load_golden("edm.pt")["cases"]["d32_n32"]
+    return _net(c["unet_kw"], c["salt"])
+
+
+def _int_net():
+    g = load_golden("repaint.pt")
+    return _net(g["unet_kw"], g["salt"])
+
+
+def _inpaint_inputs():
+    g = torch.Generator().manual_seed(11)
+    gt = torch.rand(SHAPE, generator=g)
+    mask = (torch.rand(SHAPE, generator=g) > 0.5).float()
+    return gt, mask, mask[:, :1].contiguous()
+
+
+# name -> (run(net, use_graph) -> image, graphs the loop captures when it takes over the slot)
+def _float_calls():
+    def edm(net, use_graph):
+        return dm.ElucidatedDiffusion(net, image_size=SIZE, num_sample_steps=4, use_graph=use_graph)
+
+    def ct(net, use_graph, clip):
+        return dm.VParamContinuousTimeGaussianDiffusion(net, image_size=SIZE, num_sample_steps=4, clip_sample_denoised=clip,
+                                                        use_graph=use_graph)
+
+    return {
+        "heun": (lambda net, g=True: edm(net, g).sample(batch_size=B, seed=SEED), 2),
+        "dpmpp": (lambda net, g=True: edm(net, g).sample_using_dpmpp(batch_size=B, seed=SEED), 1),
+        "ct": (lambda net, g=True: ct(net, g, True).sample(batch_size=B, seed=SEED), 1),
+        "ct_noclip": (lambda net, g=True: ct(net, g, False).sample(batch_size=B, seed=SEED), 1),
+    }
+
+
+def _int_calls():
+    gt, mask_c, mask_1 = _inpaint_inputs()
+    kw = dict(image_size=SIZE, timesteps=8, objective="pred_noise", beta_schedule="cosine")
+
+    def ddpm(net, use_graph, steps=4):
+        return dm.DenoisingDiffusion(net, use_graph=use_graph, **kw).p_sample_loop(SHAPE, seed=SEED, max_steps=steps)
+
+    def ddim(net, use_graph):
+        return dm.DenoisingDiffusion(net, use_graph=use_graph, **kw).ddim_sample(SHAPE, sampling_timesteps=4, seed=SEED)
+
+    def repaint(net, use_graph, mask, resample_iter=1):  # 8 + resample_iter * 2 rows
+        d = dm.RePaintGaussianDiffusion(net, use_graph=use_graph, **kw)
+        return d.sample(gt=gt, mask=mask, seed=SEED, resample_iter=resample_iter, resample_jump=2)
+
+    return {
+        "ddpm": (lambda net, g=True: ddpm(net, g), 1),
+        "ddpm2": (lambda net, g=True: ddpm(net, g, 2), 1),
+        "ddim": (lambda net, g=True: ddim(net, g), 1),
+        "repaint": (lambda net, g=True: repaint(net, g, mask_c), 1),
+        "repaint_1ch": (lambda net, g=True: repaint(net, g, mask_1), 1),
+        "repaint_12rows": (lambda net, g=True: repaint(net, g, mask_c, 2), 1),
+    }
+
+
+@pytest.fixture(scope="module")
+def float_calls():
+    return _float_calls()
+
+
+@pytest.fixture(scope="module")
+def int_calls():
+    return _int_calls()
+
+
+@pytest.fixture(scope="module")
+def fresh(float_calls, int_calls):
+    """Every call on a handle of its own: computed once, never changed."""
+    out = {}
+    for calls, make in ((float_calls, _float_net), (int_calls, _int_net)):
+        for name, (run, captures) in calls.items():
+            net = make()
+            out[name] = run(net).clone()
+            assert net.graph_captures == captures, name
+            assert bool(torch.isfinite(out[name]).all()) and float(out[name].std()) > 0.01, name
+    return out
+
+
+def _shared_sequence(net, calls, fresh, order):
+    assert net.graph_captures == 0
+    for name in order:
+        run, captures = calls[name]
+        before = net.graph_captures
+        got = run(net)
+        assert torch.equal(got, fresh[name]), name
+        assert net.graph_captures == before + captures, (name, before, net.graph_captures)
+        again = run(net)  # immediately repeated: the slot is this loop's
+        assert torch.equal(again, fresh[name]), name
+        assert net.graph_captures == before + captures, (name, "repeated")
+
+
+def test_float_time_loops_share_one_handle(float_calls, fresh):
+    _shared_sequence(_float_net(), float_calls, fresh, ["heun", "ct", "dpmpp", "ct_noclip", "heun"])
+
+
+def test_integer_time_loops_share_one_handle(int_calls, fresh):
+    _shared_sequence(_int_net(), int_calls, fresh, ["ddpm", "repaint", "ddim", "repaint_1ch", "ddpm"])
+
+
+def test_tables_grow_after_a_capture(int_calls, fresh):
+    net = _int_net()
+    assert torch.equal(int_calls["ddpm2"][0](net), fresh["ddpm2"])
+    assert net.graph_captures == 1
+    # more steps than the tables hold: they are reallocated, and the graph that read the old ones goes with them
+    assert torch.equal(int_calls["ddpm"][0](net), fresh["ddpm"])
+    assert net.graph_captures == 2
+    # RePaint's tables grow in granules of 4096 rows: another row count below that keeps the addresses and the graph
+    assert torch.equal(int_calls["repaint"][0](net), fresh["repaint"])
+    n = net.graph_captures
+    assert n == 3
+    assert torch.equal(int_calls["repaint_12rows"][0](net), fresh["repaint_12rows"])
+    assert net.graph_captures == n
+    assert torch.equal(int_calls["repaint"][0](net), fresh["repaint"])
+    assert net.graph_captures == n
+
+
+@pytest.mark.parametrize("family", ["float", "int"])
+def test_eager_is_the_graph_and_leaves_the_slot_alone(family, float_calls, int_calls, fresh):
+    calls, net = (float_calls, _float_net()) if family == "float" else (int_calls, _int_net())
+    names = ["heun", "dpmpp", "ct"] if family == "float" else ["ddpm", "ddim", "repaint"]
+    for name in names:
+        run = calls[name][0]
+        graph = run(net)
+        n = net.graph_captures
+        eager = run(net, False)
+        assert torch.equal(eager, graph) and torch.equal(graph, fresh[name]), name
+        assert net.graph_captures == n, name
+        assert torch.equal(run(net), graph) and net.graph_captures == n, name  # the eager call did not disturb the slot
