@@ -311,8 +311,9 @@ def load() -> C.CDLL:
     return lib
 
 
-def profile_enable(on: bool) -> None:
-    check(load().dm_profile_enable(1 if on else 0))
+def profile_enable(on: bool, detail: bool = False) -> None:
+    """detail: one row per layer shape (the row names its shape, epilogue and K split) instead of one per kernel instance."""
+    check(load().dm_profile_enable((2 if detail else 1) if on else 0))
 
 
 def profile_read():

@@ -19,8 +19,14 @@ static int run_op(hipStream_t s, F body) {
     Arena A;
     A.base = static_cast<char*>(buf);
     A.cap = dry.off + 256;
-    int rc = body(A);
-    hipError_t e = hipStreamSynchronize(s);
+    // Every float of the workspace starts as a NaN: a kernel that reads a partial-sum slot, a ragged tile or a masked row
+    // nobody wrote shows up in the result instead of reading the zeros of fresh device memory.
+    hipError_t e = hipMemsetAsync(buf, 0xFF, A.cap, s);
+    int rc = 0;
+    if (e == hipSuccess) {
+        rc = body(A);
+        e = hipStreamSynchronize(s);
+    }
     (void)hipFree(buf);
     if (!rc && e != hipSuccess) {
         set_error(std::string("kernel execution failed: ") + hipGetErrorString(e));

@@ -23,7 +23,7 @@ struct OpTrain {
         u.order.push_back(name);
         return 0;
     }
-    int alloc_grads() {
+    int alloc_grads(bool poison = false) {  // poison: NaN instead of 0 (operators that overwrite every slot they return)
         TrainState& T = *u.train;
         size_t off = 0;
         for (const std::string& n : u.order) {
@@ -32,7 +32,7 @@ struct OpTrain {
         }
         T.grad_floats = off;
         DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.grad), std::max<size_t>(off, 4) * sizeof(float)));
-        DM_CHECK_HIP(hipMemset(T.grad, 0, std::max<size_t>(off, 4) * sizeof(float)));
+        DM_CHECK_HIP(hipMemset(T.grad, poison ? 0xFF : 0, std::max<size_t>(off, 4) * sizeof(float)));
         return 0;
     }
     int out(const std::string& name, float* dst, hipStream_t s) {  // gradient slot -> caller's device buffer
@@ -83,7 +83,7 @@ int dm_op_conv2d_bwd(const float* in0, int C0, const float* in1, int C1, const f
     return guarded([&]() -> int {
         OpTrain op(4, 32);
         const int C1e = in1 ? C1 : 0;
-        if (op.param("w", weight, {Cout, C0 + C1e, ksize, ksize}) || op.param("b", nullptr, {Cout}) || op.alloc_grads()) return 1;
+        if (op.param("w", weight, {Cout, C0 + C1e, ksize, ksize}) || op.param("b", nullptr, {Cout}) || op.alloc_grads(true)) return 1;
         ConvLayer L;
         if (make_conv(op.u.own, L, op.u.params["w"].data.data(), nullptr, Cout, C0, C1e, ksize, ksize, 1, pad, up2 != 0)) return 1;
         if (build_conv_bwd(&op.u, *op.u.train, L, "w", ksize == 3 ? 0 : 1)) return 1;
@@ -115,7 +115,7 @@ int dm_op_downsample_bwd(const float* in, int C, const float* weight, const floa
     hipStream_t s = static_cast<hipStream_t>(stream);
     return guarded([&]() -> int {
         OpTrain op(4, 32);
-        if (op.param("w", weight, {Cout, 4 * C, 1, 1}) || op.param("b", nullptr, {Cout}) || op.alloc_grads()) return 1;
+        if (op.param("w", weight, {Cout, 4 * C, 1, 1}) || op.param("b", nullptr, {Cout}) || op.alloc_grads(true)) return 1;
         ConvLayer L;
         if (make_conv(op.u.own, L, op.u.params["w"].data.data(), nullptr, Cout, C, 0, 2, 2, 2, 0, false)) return 1;
         if (build_conv_bwd(&op.u, *op.u.train, L, "w", 2)) return 1;
@@ -143,7 +143,7 @@ int dm_op_block_bwd(const float* x, int Cin, const float* weight, const float* b
     return guarded([&]() -> int {
         OpTrain op(4, 32);
         if (op.param("blk.proj.weight", weight, {Cout, Cin, 3, 3}) || op.param("blk.proj.bias", bias, {Cout}) ||
-            op.param("blk.norm.g", g, {1, Cout, 1, 1}) || op.alloc_grads())
+            op.param("blk.norm.g", g, {1, Cout, 1, 1}) || op.alloc_grads(true))
             return 1;
         ConvLayer L;
         if (make_conv(op.u.own, L, op.u.params["blk.proj.weight"].data.data(), op.u.params["blk.proj.bias"].data.data(), Cout,

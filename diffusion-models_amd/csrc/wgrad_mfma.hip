@@ -560,9 +560,16 @@ int launch_wgrad(const float* in0, int C0, const float* in1, int C1, const float
     const size_t lds = wgrad_lds_bytes(p, mode);
     const dim3 grid(p.n_ct * p.n_kt, splits, wgrad_zdim(mode));
     const bool timed = prof::enabled();
-    if (timed && prof::begin("wgrad_mfma_kernel", 2.0 * T * p.Cin * Cout * (double)B * Ho * Wo,
-                             4.0 * ((double)B * Ho * Wo * (p.Cin * (mode == 2 ? 4 : 1) + Cout) + (double)T * p.Cin * Cout), s))
-        return 1;
+    if (timed) {
+        char name[64];
+        if (prof::detail())  // m: 0 direct 3x3, 1 1x1, 2 space-to-depth (Downsample), 3 Winograd domain
+            snprintf(name, sizeof(name), "wgrad m%d %d+%d->%d @%dx%d%s k%d", mode, C0, C1, Cout, Ho, Wo, up ? " up" : "", splits);
+        else
+            snprintf(name, sizeof(name), "wgrad_mfma_kernel");
+        if (prof::begin(name, 2.0 * T * p.Cin * Cout * (double)B * Ho * Wo,
+                        4.0 * ((double)B * Ho * Wo * (p.Cin * (mode == 2 ? 4 : 1) + Cout) + (double)T * p.Cin * Cout), s))
+            return 1;
+    }
     static LdsOptIn f0, f1, f2, f3;
     if (mode == 0) {
         if (lds_opt_in(f0, reinterpret_cast<const void*>(wgrad_mfma_kernel<0, false>), 1)) return 1;

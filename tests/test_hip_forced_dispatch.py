@@ -127,3 +127,17 @@ def test_cross_attention_operator_on_the_other_forms():
 def test_training_goldens_grouped_without_winograd():
     """... and the grouped launches with the direct (row-split) 3x3 weight gradient."""
     _run_training(dict(DM_WGRAD_NO_WINO="1"))
+
+
+def test_conv_families_on_the_forced_and_the_alternative_forms():
+    """tests/test_hip_conv_families.py once more, with its asserted dispatch, fp64 limits and poisoned workspace, in two
+    children: F(4x4) and the upsample kernel on the small shapes (forced), and the 64-cout F(2x2) workgroups, the 64-pixel
+    wave tiles of the 1x1 GEMM and the direct 3x3 weight gradient (alt); the expected kernel of every case under each set of
+    switches stands in that file's tables."""
+    for extra in (dict(DM_WINO4_MIN_WGS="1", DM_WINO4_MIN_K="1", DM_UPWINO_MIN_WGS="1", DM_UPWINO_MIN_K="1"),
+                  dict(DM_WINO_Q_TARGET_WGS="1", DM_PW_RT_TARGET_WGS="1", DM_WGRAD_NO_WINO="1")):
+        env = dict(os.environ, **extra)
+        r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_hip_conv_families.py"), "-q",
+                            "-x", "-m", "gpu", "-p", "no:cacheprovider"],
+                           cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (extra, r.stdout[-4000:] + r.stderr[-2000:])

@@ -64,8 +64,10 @@ CONV_CASES = [
     (2, 16, 0, 24, 24, 16, 3, 1, False, True, False),     # non power-of-two image (masked tile)
     (2, 48, 16, 12, 12, 48, 3, 1, False, True, False),    # odd sizes, concat
     (1, 6, 0, 8, 8, 8, 3, 1, False, True, False),         # channels not a multiple of 4
-    # Winograd F(2x2,3x3) path (3x3, C % 8 == 0, Cout % 64 == 0, even size); the cases above with those
-    # properties take it too
+    # Winograd F(2x2,3x3) kernel (winograd_mfma.hip: 3x3, C % 8 == 0, Cout % 64 == 0, even size); the cases above with
+    # those properties take it too.  The 4x4-map cases of this group are F(4x4) cases (wino4_mfma.hip) in the forced child of
+    # tests/test_hip_forced_dispatch.py; 12x20 and 6x2 are in no F(4x4) class (4x4, 8x8, multiples of 16) and stay F(2x2) there.
+    # (Which kernel a shape reaches is ASSERTED in tests/test_hip_conv_families.py; the comments here only describe.)
     (3, 72, 8, 12, 20, 64, 3, 1, False, True, True),      # non power-of-two even image, masked tiles, concat 72+8
     (37, 64, 0, 4, 4, 128, 3, 1, False, False, False),    # 8 images per workgroup, ragged batch, no bias
     (2, 8, 0, 6, 2, 64, 3, 1, False, True, False),        # single K chunk, image narrower than a tile row
@@ -82,16 +84,20 @@ CONV_CASES = [
     (2, 512, 0, 4, 4, 64, 3, 1, True, True, False),       # K split (partial sums + finalize)
     (1, 16, 0, 8, 24, 64, 3, 1, True, False, False),      # non-square source, two chunks, no bias
     (40, 128, 0, 16, 16, 64, 3, 1, True, True, False),    # 160 workgroups of 16 chunks: production dispatch
-    # 1x1 GEMM kernel (pw_mfma.hip; C % 8 == 0, Cout % 64 == 0): res_conv / attention projections
+    # 1x1 GEMM kernel (pw_mfma.hip; C0 % 16 == 0, C1 % 16 == 0, Cout % 64 == 0): res_conv / attention projections.  The two
+    # cases with 8 and 72 + 8 channels are off its 16-channel chunks and reach the direct kernel (conv_mfma.hip, CK = 4) that
+    # the first group already covers
     (3, 64, 64, 10, 6, 64, 1, 0, False, True, True),      # two sources + residual, 180 pixels (ragged last rows)
     (2, 512, 256, 4, 4, 512, 1, 0, False, True, True),    # res_conv of the deepest stage: 96 chunks, K split, 4 cout blocks
     (5, 256, 0, 8, 8, 384, 1, 0, False, False, False),    # to_qkv: three 128-cout blocks, no bias
-    (1, 8, 0, 2, 2, 64, 1, 0, False, True, False),        # one chunk, four pixels
-    (7, 72, 8, 16, 16, 128, 1, 0, False, True, False),    # chunk boundary of the concat inside the prefetch ring
+    (1, 8, 0, 2, 2, 64, 1, 0, False, True, False),        # direct kernel: 8 channels, four pixels
+    (7, 72, 8, 16, 16, 128, 1, 0, False, True, False),    # direct kernel: concat 72 + 8 in chunks of 4
     (2, 64, 0, 8, 8, 192, 1, 0, False, True, False),      # 192 couts: three 64-cout blocks (InceptionV3 branches)
-    # even images >= 16x16 with C % 16 == 0, Cout % 64 == 0: masked / ragged pixel blocks of the Winograd kernels
-    (2, 32, 16, 24, 40, 128, 3, 1, False, True, True),    # masked 16x16 blocks, concat 32+16, two cout tiles, residual
-    (1, 16, 0, 18, 34, 64, 3, 1, False, False, False),    # single chunk, no bias, ragged blocks in both directions
+    # even images >= 16x16 with C % 16 == 0, Cout % 64 == 0: masked / ragged tile blocks of the F(2x2) kernel only.  24x40
+    # and 18x34 are no multiples of 16, so neither is in an F(4x4) class and the forced child runs F(2x2) again: the same
+    # kernel as the F(2x2) group above, at larger masked blocks
+    (2, 32, 16, 24, 40, 128, 3, 1, False, True, True),    # masked 8x4-tile blocks, concat 32+16, two cout tiles, residual
+    (1, 16, 0, 18, 34, 64, 3, 1, False, False, False),    # two chunks, no bias, ragged blocks in both directions
     # the direct 3x3 kernel behind it (odd sizes are not Winograd-eligible)
     (2, 64, 64, 7, 9, 64, 3, 1, False, True, True),
     (3, 256, 0, 5, 5, 256, 3, 1, False, True, False),
