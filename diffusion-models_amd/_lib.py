@@ -9,6 +9,8 @@ import ctypes as C
 import os
 from typing import Optional
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DM_LIB selects another build of the same ABI (tools/conv_stamps.py loads the stamped diagnostic build)
 LIB_PATH = os.environ.get("DM_LIB") or os.path.join(_HERE, "libdm_hip.so")
@@ -338,3 +340,23 @@ def ptr(t) -> Optional[int]:
         return None
     assert t.is_contiguous(), "tensor must be contiguous at the C ABI"
     return t.data_ptr()
+
+
+def fptr(t):
+    """``const float*`` of a contiguous fp32 host tensor (the step and coefficient tables)."""
+    return C.cast(t.data_ptr(), C.POINTER(C.c_float))
+
+
+def default_seed() -> int:
+    """A Philox key from torch's global CPU generator (reproducible under torch.manual_seed)."""
+    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+
+
+def randn(lib, device, shape, seed, draw, sample_offset=0):
+    """``dm_randn``: draw ``draw`` of the Philox stream ``seed`` as a ``shape`` tensor on ``device``; ``sample_offset`` is the
+    index of the first sample in a global batch."""
+    out = torch.empty(tuple(shape), device=device, dtype=torch.float32)
+    per_sample = out.numel() // max(int(shape[0]), 1)
+    check(lib.dm_randn(ptr(out), out.numel(), C.c_uint64(seed), C.c_uint64(draw),
+                       C.c_uint64(int(sample_offset) * per_sample), torch.cuda.current_stream(device).cuda_stream))
+    return out

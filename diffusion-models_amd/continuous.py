@@ -32,6 +32,8 @@ from torch import sqrt
 from torch.special import expm1
 
 from . import _lib
+from ._floattime import FloatTimeDiffusion
+from ._lib import default_seed as _default_seed, fptr as _fptr
 
 COLS = _lib.DM_CT_COEFS
 # columns of a table row (csrc/ct.h)
@@ -110,78 +112,26 @@ def ct_train_table(times: torch.Tensor, schedule="linear", min_snr_loss_weight=F
     return tab
 
 
-def _default_seed() -> int:
-    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-
-
-def _fptr(t: torch.Tensor):
-    return C.cast(t.data_ptr(), C.POINTER(C.c_float))
-
-
-class _ContinuousTimeBase:
+class _ContinuousTimeBase(FloatTimeDiffusion):
     """What the two classes share; ``_objective`` and the schedule tell them apart."""
 
+    _unet_attr = "model"
+    _train_entry = "dm_unet_loss_backward_ct"
     _objective = _lib.CT_PRED_NOISE
     min_snr_loss_weight = False
     min_snr_gamma = 5
 
     def _init(self, model, image_size, channels, schedule, num_sample_steps, clip_sample_denoised, use_graph):
-        assert model.random_or_learned_sinusoidal_cond
-        assert not model.self_condition, 'not supported yet'
-        name = type(self).__name__
-        if getattr(model, "text_condition", False) or getattr(getattr(model, "cfg", None), "cond_channels", 0):
-            raise NotImplementedError(f"{name} calls model(x, log_snr) only: a text-conditional or image-conditional "
-                                      "U-Net has no place for its condition")
-        if model.out_dim != channels or model.channels != channels:
-            raise ValueError(f"the U-Net maps {model.channels} to {model.out_dim} channels, the sampler needs {channels} -> "
-                             f"{channels} (no learned variance)")
+        self._init_unet(model, image_size, channels, use_graph, f"{type(self).__name__} calls model(x, log_snr) only")
         self.log_snr = _schedule(schedule)
-        self.model = model
-        self.channels = channels
-        self.image_size = image_size
         self.num_sample_steps = num_sample_steps
         self.clip_sample_denoised = clip_sample_denoised
-        self.use_graph = use_graph
-        self._lib = _lib.load()
 
-    # -- module-ish surface ------------------------------------------------------------------------
-    @property
-    def device(self):
-        return self.model.device
-
-    def eval(self):
-        return self
-
-    def parameters(self):
-        return self.model.parameters()
-
-    def sample_shape(self):
-        """(C, H, W) of one sample (``dist.sample_global`` builds empty shards from it)."""
-        return (self.channels, self.image_size, self.image_size)
-
-    def state_dict(self):
-        """The reference modules have no buffers: ``model.`` + the U-Net's keys."""
-        return {"model." + k: v for k, v in self.model.state_dict().items()}
-
-    def load_state_dict(self, state_dict, strict=True):
-        other = [k for k in state_dict if not k.startswith("model.")]
-        if strict and other:
-            raise RuntimeError(f"Error(s) in loading state_dict: unexpected {other[:5]}")
-        self.model.load_state_dict({k[len("model."):]: v for k, v in state_dict.items() if k.startswith("model.")},
-                                   strict=strict)
-        return self
+    @staticmethod
+    def _refuse_self_condition(model):
+        assert not model.self_condition, 'not supported yet'
 
     # -- sampling ----------------------------------------------------------------------------------
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _randn(self, shape, seed, draw, sample_offset):
-        out = torch.empty(tuple(shape), device=self.device, dtype=torch.float32)
-        per = out.numel() // max(int(shape[0]), 1)
-        _lib.check(self._lib.dm_randn(_lib.ptr(out), out.numel(), C.c_uint64(seed), C.c_uint64(draw),
-                                      C.c_uint64(int(sample_offset) * per), self._stream()))
-        return out
-
     def _step_op(self, x, row, eps, want_x_start=False):
         """``dm_op_ct_step`` on one table row: the U-Net at log_snr, then the elementwise step."""
         x = x.to(self.device, torch.float32).contiguous()
@@ -225,19 +175,10 @@ class _ContinuousTimeBase:
         shape = tuple(int(v) for v in shape)
         f = self.model.downsample_factor
         assert shape[0] > 0 and shape[2] % f == 0 and shape[3] % f == 0, f"shape {shape}: the sides must be divisible by {f}"
-        if seed is None:
-            seed = _default_seed()
         table = ct_step_table(self.num_sample_steps, self.log_snr).contiguous()
         n_steps = table.shape[0]
-        if noise is not None:
-            x_init = noise(shape).to(self.device, torch.float32).contiguous()
-            rows = [noise(shape).to(torch.float32) for _ in range(n_steps - 1)]
-            # (a one-step loop draws nothing after the start image: its only row has c[6] == 0)
-            noise_dev = torch.stack(rows, dim=0).to(self.device).contiguous() if rows else None
-        else:
-            x_init = self._randn(shape, seed, 0, sample_offset)
-            noise_dev = None
-        assert tuple(x_init.shape) == shape, "noise() must return tensors of the sampled shape"
+        # (a one-step loop draws nothing after the start image: its only row has c[6] == 0)
+        seed, x_init, noise_dev = self._start(shape, noise, n_steps - 1, seed, sample_offset)
         out = torch.empty(shape, device=self.device, dtype=torch.float32)
         a = _lib.CtArgs()
         a.objective, a.clip, a.n_steps, a.table_host = self._objective, int(bool(self.clip_sample_denoised)), n_steps, _fptr(table)
@@ -276,30 +217,8 @@ class _ContinuousTimeBase:
         """:233-235: uniform on [0, 1); the (batch_size,) draw comes from torch's global CPU generator."""
         return self._draw_times(batch_size).to(self.device)
 
-    def _trainable_model(self):
-        from .unet import Unet
-
-        model = self.model
-        if not isinstance(model, Unet) or getattr(model, "_handle", None) is None or not hasattr(self._lib, "dm_unet_loss_backward_ct"):
-            raise NotImplementedError(f"{type(self).__name__} can train a library Unet only (dm_unet_train_enable_ft arms its "
-                                      f"handle for the float-time training loss); got {type(model).__name__}")
-        return model
-
-    def train(self, mode: bool = True):
-        """``model.train()``: arm the U-Net for float-time training (gradient buffers, input-gradient convolutions; once)."""
-        if mode:
-            model = self._trainable_model()
-            if not model._loaded:
-                raise RuntimeError("load_state_dict() must be called before train()")
-            # random_fourier_features: the reference builds time_mlp.0.weights with requires_grad = False
-            _lib.check(self._lib.dm_unet_train_enable_ft(model._handle, int(bool(model.cfg.random_fourier_features))))
-            if not getattr(model, "_training", False):
-                model.set_dropout_seed(int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
-            model._training = True
-        return self
-
     def _loss(self, images, times, noise, normalize, loss_scale, accumulate, sync):
-        model = self._trainable_model()
+        model = self._trainable()
         b, c, h, w = images.shape
         assert c == self.channels, "mismatch of image channels"
         if not getattr(model, "_training", False):
@@ -307,25 +226,12 @@ class _ContinuousTimeBase:
         tab = ct_train_table(times, self.log_snr, self.min_snr_loss_weight, self.min_snr_gamma).contiguous()
         if tab.shape[0] != b:
             raise RuntimeError(f"times has {tab.shape[0]} entries for a batch of {b}")
-        images = images.to(self.device, torch.float32).contiguous()
-        noise = (noise.to(self.device, torch.float32).contiguous() if noise is not None
-                 else self._randn(images.shape, _default_seed(), 0, 0))
-        if noise.shape != images.shape:
-            raise RuntimeError(f"noise {tuple(noise.shape)} does not match images {tuple(images.shape)}")
-        stream = self._stream()
-        loss = C.c_float(0.0)
+        images, noise = self._loss_inputs(images, noise)
         a = _lib.CtTrainArgs()
         a.images, a.noise, a.coef_host, a.coef_stride = _lib.ptr(images), _lib.ptr(noise), _fptr(tab), COLS
         a.objective, a.loss_scale, a.accumulate = self._objective, float(loss_scale), int(bool(accumulate))
         a.B, a.H, a.W, a.normalize = b, h, w, int(bool(normalize))
-        a.loss_out_host = C.pointer(loss) if sync else None
-        a.stream = stream
-        _lib.check(self._lib.dm_unet_loss_backward_ct(model._handle, C.byref(a)))
-        if sync:
-            return torch.tensor(loss.value, dtype=torch.float32)
-        val = torch.empty((), device=self.device, dtype=torch.float32)
-        _lib.check(self._lib.dm_unet_train_scalar(model._handle, 0, _lib.ptr(val), stream))
-        return val
+        return self._loss_call(a, sync)
 
     def p_losses(self, x_start, times, noise=None, *, loss_scale=1.0, accumulate=False, sync=True):
         """:237-251 (v: :152-162) on ``x_start`` in [-1, 1]: the loss (0-dim CPU tensor; ``sync=False``: a 0-dim device
@@ -334,7 +240,7 @@ class _ContinuousTimeBase:
 
     def forward(self, img, *, times=None, noise=None, loss_scale=1.0, accumulate=False, sync=True):
         """:253-259 on ``img`` in [0, 1]: the draw of ``times`` comes first, as in the reference, then the noise."""
-        self._trainable_model()
+        self._trainable()
         b, c, h, w = img.shape
         assert h == self.image_size and w == self.image_size, f'height and width of image must be {self.image_size}'
         times = self._draw_times(b) if times is None else times

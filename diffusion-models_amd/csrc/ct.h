@@ -23,18 +23,18 @@ enum CtCol : int {
 };
 enum CtObjective : int { CT_PRED_NOISE = 0, CT_PRED_V = 1 };
 
-// Rows are selected as in edm.h (EdmRows: step / image / first); n = B * per, per % 4 == 0, 16-byte pointers.
+// Rows are selected by a StepRows (step_device.h: step / image / first); n = B * per, per % 4 == 0, 16-byte pointers.
 // One reverse step, p_mean_variance + p_sample of both classes:
 //   v:               x_start = alpha x - sigma F [clamped];        mean = alpha_next (x (1 - c) / alpha + c x_start)
 //   noise, clip:     x_start = (x - sigma F) / alpha, clamped;     the same mean
 //   noise, no clip:  mean = (alpha_next / alpha) (x - (c sigma) F)   (x_start_out must be nullptr)
 //   out = mean + sqrt_var * eps;  eps: row `step` of noise (stride noise_step_stride), or the Philox draw step + 1 under
 //   st->seed when noise == nullptr; a row with sqrt_var == 0 reads and draws nothing.  out may be x.
-int launch_ct_step(const float* x, const float* F, const float* noise, int64_t noise_step_stride, EdmRows r, int objective,
+int launch_ct_step(const float* x, const float* F, const float* noise, int64_t noise_step_stride, StepRows r, int objective,
                    int clip, float* out, float* x_start_out, int64_t n, hipStream_t s);
 // q_sample + regression target: x0 = 2 img - 1 (normalize != 0) or img; x = x0 alpha_b + eps sigma_b;
 // target = eps (noise) or alpha_b eps - sigma_b x0 (v)
-int launch_ct_noise_in(const float* img, const float* eps, EdmRows r, int objective, int normalize, float* x, float* target,
+int launch_ct_noise_in(const float* img, const float* eps, StepRows r, int objective, int normalize, float* x, float* target,
                        int64_t n, hipStream_t s);
 // *loss = loss_scale * mean_b(w_b * mean((F - target)^2)); dF = loss_scale * w_b * 2 (F - target) / (B * per).
 // tab: B device rows (w_b = column CT_LOSS_W); part: B floats of workspace

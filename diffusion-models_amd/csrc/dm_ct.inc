@@ -54,7 +54,7 @@ static int sample_ct_impl(dm_unet* u, const dm_ct_args* a) {
         return 1;
     if (run_upload(r, n_steps, nullptr, nullptr, tab_host, 0, a->seed, a->sample_offset * (uint64_t)per)) return 1;
     const float* tab = u->edm_tab_dev;
-    const EdmRows rows{tab, u->state_dev, EDM_ROW_STEP, per};
+    const StepRows rows{tab, u->state_dev, STEP_ROW_STEP, per};
 
     DM_CHECK_HIP(hipMemcpyAsync(x, a->x_init, n * sizeof(float), hipMemcpyDeviceToDevice, s));  // img = randn(shape)
 
@@ -94,7 +94,7 @@ static int loss_backward_ct_impl(dm_unet* u, const dm_ct_train_args& a) {
     TrainState& T = *u->train;
     const int64_t per = (int64_t)u->cfg.channels * H * W, n = (int64_t)B * per;
     auto run = [&](Arena& A, Tape& tp) -> int {
-        const EdmRows rows{T.edm_coef_dev, nullptr, B > 1 ? EDM_ROW_IMAGE : EDM_ROW_FIRST, per};
+        const StepRows rows{T.edm_coef_dev, nullptr, B > 1 ? STEP_ROW_IMAGE : STEP_ROW_FIRST, per};
         float* x = A.alloc(n);
         float* target = A.alloc(n);
         float* F = A.alloc(n);
@@ -130,7 +130,7 @@ int dm_op_ct_step(const float* x, const float* F, const float* eps, const float*
     DM_REQUIRE(eps || draw >= 1, "Philox draw 0 is the initial noise: a step's draw is its index + 1");
     return state_op(draw_state(eps != nullptr, seed, draw, element_offset), c_host, rows, stream,
                     [&](const SamplerState* st, const float* cd, hipStream_t s) {
-                        EdmRows r;
+                        StepRows r;
                         if (edm_rows(cd, rows, B, per, &r)) return 1;
                         r.st = st;
                         return launch_ct_step(x, F, eps, 0, r, objective, clip ? 1 : 0, out, x_start_out, (int64_t)B * per, s);
@@ -141,7 +141,7 @@ int dm_op_ct_noise_in(const float* images, const float* eps, const float* c_host
                       float* x, float* target, int B, int64_t per, void* stream) {
     DM_REQUIRE(images && eps && x && target, "null argument");
     return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
-        EdmRows r;
+        StepRows r;
         if (edm_rows(cd, rows, B, per, &r)) return 1;
         return launch_ct_noise_in(images, eps, r, objective, normalize, x, target, (int64_t)B * per, s);
     });

@@ -55,7 +55,7 @@ static int sample_edm_impl(dm_unet* u, const dm_edm_args* a) {
         return 1;
     if (run_upload(r, n_steps, nullptr, nullptr, tab_host, 0, a->seed, a->sample_offset * (uint64_t)per)) return 1;
     const float* tab = u->edm_tab_dev;
-    const EdmRows rows{tab, u->state_dev, EDM_ROW_STEP, per};
+    const StepRows rows{tab, u->state_dev, STEP_ROW_STEP, per};
 
     if (launch_edm_scale(a->x_init, a->sigma_init, x, n, s)) return 1;  // images = sigmas[0] * randn (:151, :201)
     if (!heun) DM_CHECK_HIP(hipMemsetAsync(d, 0, n * sizeof(float), s));
@@ -119,10 +119,10 @@ static int edm_op(const float* c_host, int rows, void* stream, const std::functi
     return rc;
 }
 // rows == 1: one row for every image; rows == B: row b for image b
-static int edm_rows(const float* tab, int rows, int B, int64_t per, EdmRows* out) {
+static int edm_rows(const float* tab, int rows, int B, int64_t per, StepRows* out) {
     DM_REQUIRE(B > 0 && per > 0, "empty tensor");
     DM_REQUIRE(rows == 1 || rows == B, "the step table has one row, or one row per image");
-    *out = EdmRows{tab, nullptr, rows == B && B > 1 ? EDM_ROW_IMAGE : EDM_ROW_FIRST, per};
+    *out = StepRows{tab, nullptr, rows == B && B > 1 ? STEP_ROW_IMAGE : STEP_ROW_FIRST, per};
     return 0;
 }
 
@@ -230,7 +230,7 @@ static int loss_backward_edm_impl(dm_unet* u, const dm_edm_train_args& a) {
     TrainState& T = *u->train;
     const int64_t per = (int64_t)u->cfg.channels * H * W, n = (int64_t)B * per;
     auto run = [&](Arena& A, Tape& tp) -> int {
-        const EdmRows rows{T.edm_coef_dev, nullptr, B > 1 ? EDM_ROW_IMAGE : EDM_ROW_FIRST, per};
+        const StepRows rows{T.edm_coef_dev, nullptr, B > 1 ? STEP_ROW_IMAGE : STEP_ROW_FIRST, per};
         float* x0 = A.alloc(n);
         float* noised = A.alloc(n);
         float* xin = A.alloc(n);
@@ -283,7 +283,7 @@ int dm_op_edm_churn_in(const float* x, const float* eps, const float* c_host, in
     DM_REQUIRE(eps || draw >= 1, "Philox draw 0 is the initial noise: a step's draw is its index + 1");
     return state_op(draw_state(eps != nullptr, seed, draw, element_offset), c_host, rows, stream,
                     [&](const SamplerState* st, const float* cd, hipStream_t s) {
-                        EdmRows r;
+                        StepRows r;
                         if (edm_rows(cd, rows, B, per, &r)) return 1;
                         r.st = st;
                         return launch_edm_churn_in(x, eps, 0, r, xhat, xin, (int64_t)B * per, s);
@@ -294,7 +294,7 @@ int dm_op_edm_euler(const float* xhat, const float* F, const float* c_host, int 
                     float* xnext, float* xin_next, int B, int64_t per, void* stream) {
     DM_REQUIRE(xhat && F, "null argument");
     return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
-        EdmRows r;
+        StepRows r;
         if (edm_rows(cd, rows, B, per, &r)) return 1;
         return launch_edm_euler(xhat, F, r, clamp ? 1 : 0, D_out, d_out, xnext, xin_next, (int64_t)B * per, s);
     });
@@ -304,7 +304,7 @@ int dm_op_edm_heun(const float* xhat, const float* d, const float* xnext, const 
                    int clamp, float* out, int B, int64_t per, void* stream) {
     DM_REQUIRE(xhat && d && xnext && F2 && out, "null argument");
     return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
-        EdmRows r;
+        StepRows r;
         if (edm_rows(cd, rows, B, per, &r)) return 1;
         return launch_edm_heun(xhat, d, xnext, F2, r, clamp ? 1 : 0, out, (int64_t)B * per, s);
     });
@@ -314,7 +314,7 @@ int dm_op_edm_dpmpp(const float* x, const float* F, float* d_old, const float* c
                     int64_t per, void* stream) {
     DM_REQUIRE(x && F && d_old && out, "null argument");
     return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
-        EdmRows r;
+        StepRows r;
         if (edm_rows(cd, rows, B, per, &r)) return 1;
         return launch_edm_dpmpp(x, F, d_old, r, out, (int64_t)B * per, s);
     });
@@ -346,7 +346,7 @@ int dm_op_edm_noise_in(const float* images, const float* eps, const float* c_hos
                        float* xin, int B, int64_t per, void* stream) {
     DM_REQUIRE(images && eps && x0 && noised && xin, "null argument");
     return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
-        EdmRows r;
+        StepRows r;
         if (edm_rows(cd, rows, B, per, &r)) return 1;
         return launch_edm_noise_in(images, eps, r, x0, noised, xin, (int64_t)B * per, s);
     });

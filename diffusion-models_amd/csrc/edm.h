@@ -2,7 +2,7 @@
 // Reference: DD/elucidated_diffusion.py:76-110 (preconditioning), :129-187 (Heun), :189-224 (DPM-Solver++(2M)).
 #pragma once
 
-#include "dm_common.h"
+#include "step_device.h"
 
 namespace dm {
 
@@ -28,42 +28,33 @@ enum EdmCol : int {
 };
 enum : int { EDM_A = EDM_C_IN2, EDM_B = EDM_C_NOISE2, EDM_G = EDM_C_SKIP2, EDM_OMG = EDM_C_OUT2 };
 
-// Which table row an element reads.  EDM_ROW_STEP: row st->step (sampling loops; st == nullptr: row 0); EDM_ROW_IMAGE: row
-// b of image b (B rows; preconditioned_network_forward on a (B,) sigma); EDM_ROW_FIRST: row 0 whatever st->step says (a
-// stand-alone pass whose state only selects the Philox draw).  n = B * per, per % 4 == 0, 16-byte pointers.
-enum EdmRowMode : int { EDM_ROW_STEP = 0, EDM_ROW_IMAGE = 1, EDM_ROW_FIRST = 2 };
-struct EdmRows {
-    const float* tab;
-    const SamplerState* st;
-    int mode;
-    int64_t per;
-};
-
+// Rows are selected by a StepRows (step_device.h: step / image / first; STEP_ROW_IMAGE is preconditioned_network_forward
+// on a (B,) sigma); n = B * per, per % 4 == 0, 16-byte pointers.
 // e[r] = [t | sin(t w 2 pi) | cos(t w 2 pi)] (learned) or [sin(t f) | cos(t f)] for a REAL-valued time.
 // st == nullptr: row r reads t[r]; else one row (R == 1) reads t[st->step * t_stride]
 int launch_sinusoid_ft(const float* t, int t_stride, const SamplerState* st, const float* freqs, float* e, int R, int half,
                        hipStream_t s, bool learned);
 // xhat = x + churn * (S_noise * eps), xin = c_in * xhat.  eps: row `step` of noise (stride noise_step_stride), or the
 // Philox draw step + 1 under st->seed when noise == nullptr; not read at all when churn == 0.  xhat may be nullptr.
-int launch_edm_churn_in(const float* x, const float* noise, int64_t noise_step_stride, EdmRows r, float* xhat, float* xin,
+int launch_edm_churn_in(const float* x, const float* noise, int64_t noise_step_stride, StepRows r, float* xhat, float* xin,
                         int64_t n, hipStream_t s);
 // D = c_skip xhat + c_out F [clamped]; d = (xhat - D) / sigma_hat; xnext = xhat + dt d; xin2 = c_in' xnext.
 // Every output may be nullptr.
-int launch_edm_euler(const float* xhat, const float* F, EdmRows r, int clamp, float* D_out, float* d_out, float* xnext,
+int launch_edm_euler(const float* xhat, const float* F, StepRows r, int clamp, float* D_out, float* d_out, float* xnext,
                      float* xin2, int64_t n, hipStream_t s);
 // D' = c_skip' xnext + c_out' F2 [clamped]; d' = (xnext - D') / sigma_next; out = xhat + half_dt (d + d').  out may be xnext.
-int launch_edm_heun(const float* xhat, const float* d, const float* xnext, const float* F2, EdmRows r, int clamp, float* out,
+int launch_edm_heun(const float* xhat, const float* d, const float* xnext, const float* F2, StepRows r, int clamp, float* out,
                     int64_t n, hipStream_t s);
 // D = c_skip x + c_out F; out = a x - b ((1 - g) D + g d_old); d_old = D.  out may be x.
-int launch_edm_dpmpp(const float* x, const float* F, float* d_old, EdmRows r, float* out, int64_t n, hipStream_t s);
+int launch_edm_dpmpp(const float* x, const float* F, float* d_old, StepRows r, float* out, int64_t n, hipStream_t s);
 // out = (clamp(x, -1, 1) + 1) / 2
 int launch_edm_finalize(const float* x, float* out, int64_t n, hipStream_t s);
 // out = scale * x
 int launch_edm_scale(const float* x, float scale, float* out, int64_t n, hipStream_t s);
 
-// Training rows (one per image, EDM_ROW_IMAGE): c_in, c_noise, c_skip, c_out, sigma in their sampling columns, EDM_LOSS_W.
+// Training rows (one per image, STEP_ROW_IMAGE): c_in, c_noise, c_skip, c_out, sigma in their sampling columns, EDM_LOSS_W.
 // x0 = 2 img - 1; noised = x0 + sigma eps; xin = c_in noised
-int launch_edm_noise_in(const float* img, const float* eps, EdmRows r, float* x0, float* noised, float* xin, int64_t n,
+int launch_edm_noise_in(const float* img, const float* eps, StepRows r, float* x0, float* noised, float* xin, int64_t n,
                         hipStream_t s);
 // D = c_skip noised + c_out F; *loss = loss_scale * mean_b(loss_weight_b * mean((D - x0)^2)); dF = d(loss) / dF.
 // tab: B device rows; part: B floats of workspace; D_out may be nullptr.

@@ -5,22 +5,12 @@
 // The passes are bandwidth-bound: each thread moves 16 bytes per tensor (one dwordx4 load / store), reads every input
 // once and holds no schedule logic -- every per-step scalar comes from the host-built step table (edm.h), rounded to
 // fp32 where the reference rounds it.  Contraction is off so the expression trees round like the reference's tensor ops.
+// Row lookup, 16-byte access, noise fetch, block reduction and the launch checks are those of step_device.h.
 #include "edm.h"
-#include "philox.h"
-
-#include <initializer_list>
 
 namespace dm {
 
 #pragma clang fp contract(off)
-
-__device__ __forceinline__ const float* edm_row(const EdmRows& r, int64_t i) {
-    const int row = r.mode == EDM_ROW_IMAGE ? (int)(i / r.per) : (r.mode == EDM_ROW_STEP && r.st ? r.st->step : 0);
-    return r.tab + (size_t)row * EDM_NCOLS;
-}
-__device__ __forceinline__ float4 ld4(const float* p, int64_t i) { return *reinterpret_cast<const float4*>(p + i); }
-__device__ __forceinline__ void st4(float* p, int64_t i, float4 v) { *reinterpret_cast<float4*>(p + i) = v; }
-__device__ __forceinline__ float clamp1(float v) { return fminf(fmaxf(v, -1.0f), 1.0f); }
 
 // RandomOrLearnedSinusoidalPosEmb / SinusoidalPosEmb on a float time (DD/denoising_diffusion.py:77-101)
 __global__ void sinusoid_ft_kernel(const float* __restrict__ t, int t_stride, const SamplerState* __restrict__ st,
@@ -44,23 +34,17 @@ __global__ void sinusoid_ft_kernel(const float* __restrict__ t, int t_stride, co
 
 // :162-165 and the input scaling of :100
 __global__ __launch_bounds__(256) void edm_churn_in_kernel(const float* __restrict__ x, const float* __restrict__ noise,
-                                                           int64_t noise_step_stride, EdmRows r, float* __restrict__ xhat,
+                                                           int64_t noise_step_stride, StepRows r, float* __restrict__ xhat,
                                                            float* __restrict__ xin, int64_t n) {
     const int64_t i4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t i = i4 * 4;
     if (i >= n) return;
-    const float* c = edm_row(r, i);
+    const float* c = step_row<EDM_NCOLS>(r, i);
     const float churn = c[EDM_CHURN], s_noise = c[EDM_S_NOISE], c_in = c[EDM_C_IN];
     float4 xv = ld4(x, i);
     if (churn != 0.0f) {
-        const int step = r.st ? r.st->step : 0;
         float z[4];
-        if (noise) {
-            const float4 zv = ld4(noise + (size_t)step * noise_step_stride, i);
-            z[0] = zv.x; z[1] = zv.y; z[2] = zv.z; z[3] = zv.w;
-        } else {
-            philox_normal4(r.st ? r.st->seed : 0, (uint64_t)step + 1, (r.st ? r.st->off4 : 0) + (uint64_t)i4, z);
-        }
+        step_noise4(r, noise, noise_step_stride, i4, z);
         xv.x = xv.x + churn * (s_noise * z[0]);
         xv.y = xv.y + churn * (s_noise * z[1]);
         xv.z = xv.z + churn * (s_noise * z[2]);
@@ -71,12 +55,12 @@ __global__ __launch_bounds__(256) void edm_churn_in_kernel(const float* __restri
 }
 
 // :105-108 (preconditioned output), :170-172 (Euler step) and the input scaling of the second forward
-__global__ __launch_bounds__(256) void edm_euler_kernel(const float* __restrict__ xhat, const float* __restrict__ F, EdmRows r,
+__global__ __launch_bounds__(256) void edm_euler_kernel(const float* __restrict__ xhat, const float* __restrict__ F, StepRows r,
                                                         int clamp, float* __restrict__ D_out, float* __restrict__ d_out,
                                                         float* __restrict__ xnext, float* __restrict__ xin2, int64_t n) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
-    const float* c = edm_row(r, i);
+    const float* c = step_row<EDM_NCOLS>(r, i);
     const float c_skip = c[EDM_C_SKIP], c_out = c[EDM_C_OUT], sigma = c[EDM_SIGMA], dt = c[EDM_DT], c_in2 = c[EDM_C_IN2];
     const float4 xh4 = ld4(xhat, i), f4 = ld4(F, i);
     const float xh[4] = {xh4.x, xh4.y, xh4.z, xh4.w}, f[4] = {f4.x, f4.y, f4.z, f4.w};
@@ -97,11 +81,11 @@ __global__ __launch_bounds__(256) void edm_euler_kernel(const float* __restrict_
 
 // :179-181 (second-order correction); out may alias xnext (each thread reads its 4 values before it writes them)
 __global__ __launch_bounds__(256) void edm_heun_kernel(const float* __restrict__ xhat, const float* __restrict__ d,
-                                                       const float* xnext, const float* __restrict__ F2, EdmRows r, int clamp,
+                                                       const float* xnext, const float* __restrict__ F2, StepRows r, int clamp,
                                                        float* out, int64_t n) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
-    const float* c = edm_row(r, i);
+    const float* c = step_row<EDM_NCOLS>(r, i);
     const float c_skip = c[EDM_C_SKIP2], c_out = c[EDM_C_OUT2], sigma = c[EDM_SIGMA2], half_dt = c[EDM_HALF_DT];
     const float4 xh4 = ld4(xhat, i), d4 = ld4(d, i), xn4 = ld4(xnext, i), f4 = ld4(F2, i);
     const float xh[4] = {xh4.x, xh4.y, xh4.z, xh4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
@@ -119,10 +103,10 @@ __global__ __launch_bounds__(256) void edm_heun_kernel(const float* __restrict__
 
 // :208-221; out may alias x
 __global__ __launch_bounds__(256) void edm_dpmpp_kernel(const float* x, const float* __restrict__ F, float* __restrict__ d_old,
-                                                        EdmRows r, float* out, int64_t n) {
+                                                        StepRows r, float* out, int64_t n) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
-    const float* c = edm_row(r, i);
+    const float* c = step_row<EDM_NCOLS>(r, i);
     const float c_skip = c[EDM_C_SKIP], c_out = c[EDM_C_OUT], a = c[EDM_A], b = c[EDM_B], g = c[EDM_G], omg = c[EDM_OMG];
     const float4 x4 = ld4(x, i), f4 = ld4(F, i), o4 = ld4(d_old, i);
     const float xv[4] = {x4.x, x4.y, x4.z, x4.w}, f[4] = {f4.x, f4.y, f4.z, f4.w}, od[4] = {o4.x, o4.y, o4.z, o4.w};
@@ -158,11 +142,11 @@ __global__ __launch_bounds__(256) void edm_scale_kernel(const float* __restrict_
 // ---- training (DD/elucidated_diffusion.py:234-264) ----------------------------------------------------------------
 // :240 (normalize_to_neg_one_to_one), :247 (noised = images + sigma * noise) and the input scaling of :100, per-image rows
 __global__ __launch_bounds__(256) void edm_noise_in_kernel(const float* __restrict__ img, const float* __restrict__ eps,
-                                                           EdmRows r, float* __restrict__ x0, float* __restrict__ noised,
+                                                           StepRows r, float* __restrict__ x0, float* __restrict__ noised,
                                                            float* __restrict__ xin, int64_t n) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i >= n) return;
-    const float* c = edm_row(r, i);
+    const float* c = step_row<EDM_NCOLS>(r, i);
     const float sigma = c[EDM_SIGMA], c_in = c[EDM_C_IN];
     const float4 im4 = ld4(img, i), e4 = ld4(eps, i);
     const float im[4] = {im4.x, im4.y, im4.z, im4.w}, e[4] = {e4.x, e4.y, e4.z, e4.w};
@@ -179,7 +163,7 @@ __global__ __launch_bounds__(256) void edm_noise_in_kernel(const float* __restri
 }
 
 // :105 (D = c_skip noised + c_out F) and :259-262: one workgroup per image, part[b] = loss_weight_b * mean((D - x0)^2) with the
-// squares summed in double in a fixed order (no float atomics, as mse_loss_kernel);  dF = d(loss) / dF in the same pass:
+// squares summed in double in a fixed order (no float atomics: block_sum256, as mse_loss_kernel);  dF = d(loss) / dF in the same pass:
 // loss_scale * loss_weight_b * c_out_b * 2 (D - x0) / (B * per)
 __global__ __launch_bounds__(256) void edm_loss_kernel(const float* __restrict__ noised, const float* __restrict__ F,
                                                        const float* __restrict__ x0, const float* __restrict__ tab,
@@ -206,19 +190,8 @@ __global__ __launch_bounds__(256) void edm_loss_kernel(const float* __restrict__
         st4(dF, base + i, make_float4(g[0], g[1], g[2], g[3]));
         if (D_out) st4(D_out, base + i, make_float4(D[0], D[1], D[2], D[3]));
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int m = 128; m > 0; m >>= 1) {
-        if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[b] = (float)(red[0] / per) * lw;
-}
-// :264 (losses.mean()) times loss_scale; image order
-__global__ void edm_loss_mean_kernel(const float* __restrict__ part, int B, float* __restrict__ loss, float loss_scale) {
-    double s = 0.0;
-    for (int b = 0; b < B; ++b) s += part[b];
-    *loss = (float)(s / B) * loss_scale;
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) part[b] = (float)(s / per) * lw;
 }
 
 // Backward of RandomOrLearnedSinusoidalPosEmb (DD/denoising_diffusion.py:96-101) with respect to its `weights`, from the
@@ -246,20 +219,6 @@ __global__ void sinusoid_ft_bwd_kernel(const float* __restrict__ de0, const floa
 
 #pragma clang fp contract(fast)
 
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-#define EDM_VEC_OK(n, ...)                                                                                      \
-    do {                                                                                                        \
-        DM_REQUIRE((n) > 0 && (n) % 4 == 0, "EDM passes move 4 floats per thread: the element count must be a multiple of 4"); \
-        for (const void* p_ : std::initializer_list<const void*>{__VA_ARGS__}) DM_REQUIRE(aligned16(p_), "EDM passes need 16-byte aligned tensors"); \
-    } while (0)
-static int rows_ok(const EdmRows& r, int64_t n) {
-    DM_REQUIRE(r.tab != nullptr, "null step table");
-    DM_REQUIRE(r.mode != EDM_ROW_IMAGE || (r.per > 0 && r.per % 4 == 0 && n % r.per == 0),
-               "per-image coefficients need C*H*W to be a multiple of 4 that divides the element count");
-    return 0;
-}
-static dim3 grid4(int64_t n) { return dim3((unsigned)((n / 4 + 255) / 256)); }
-
 int launch_sinusoid_ft(const float* t, int t_stride, const SamplerState* st, const float* freqs, float* e, int R, int half,
                        hipStream_t s, bool learned) {
     const int n = R * half;
@@ -269,61 +228,61 @@ int launch_sinusoid_ft(const float* t, int t_stride, const SamplerState* st, con
     return 0;
 }
 
-int launch_edm_churn_in(const float* x, const float* noise, int64_t noise_step_stride, EdmRows r, float* xhat, float* xin,
+int launch_edm_churn_in(const float* x, const float* noise, int64_t noise_step_stride, StepRows r, float* xhat, float* xin,
                         int64_t n, hipStream_t s) {
-    EDM_VEC_OK(n, x, noise, xhat, xin);
+    if (vec4_ok("EDM", n, {x, noise, xhat, xin})) return 1;
     DM_REQUIRE(noise_step_stride % 4 == 0, "noise rows must keep 16-byte alignment");
-    if (rows_ok(r, n)) return 1;
+    if (rows_ok(r, n, "null step table")) return 1;
     hipLaunchKernelGGL(edm_churn_in_kernel, grid4(n), dim3(256), 0, s, x, noise, noise_step_stride, r, xhat, xin, n);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_edm_euler(const float* xhat, const float* F, EdmRows r, int clamp, float* D_out, float* d_out, float* xnext,
+int launch_edm_euler(const float* xhat, const float* F, StepRows r, int clamp, float* D_out, float* d_out, float* xnext,
                      float* xin2, int64_t n, hipStream_t s) {
-    EDM_VEC_OK(n, xhat, F, D_out, d_out, xnext, xin2);
-    if (rows_ok(r, n)) return 1;
+    if (vec4_ok("EDM", n, {xhat, F, D_out, d_out, xnext, xin2})) return 1;
+    if (rows_ok(r, n, "null step table")) return 1;
     hipLaunchKernelGGL(edm_euler_kernel, grid4(n), dim3(256), 0, s, xhat, F, r, clamp, D_out, d_out, xnext, xin2, n);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_edm_heun(const float* xhat, const float* d, const float* xnext, const float* F2, EdmRows r, int clamp, float* out,
+int launch_edm_heun(const float* xhat, const float* d, const float* xnext, const float* F2, StepRows r, int clamp, float* out,
                     int64_t n, hipStream_t s) {
-    EDM_VEC_OK(n, xhat, d, xnext, F2, out);
-    if (rows_ok(r, n)) return 1;
+    if (vec4_ok("EDM", n, {xhat, d, xnext, F2, out})) return 1;
+    if (rows_ok(r, n, "null step table")) return 1;
     hipLaunchKernelGGL(edm_heun_kernel, grid4(n), dim3(256), 0, s, xhat, d, xnext, F2, r, clamp, out, n);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_edm_dpmpp(const float* x, const float* F, float* d_old, EdmRows r, float* out, int64_t n, hipStream_t s) {
-    EDM_VEC_OK(n, x, F, d_old, out);
-    if (rows_ok(r, n)) return 1;
+int launch_edm_dpmpp(const float* x, const float* F, float* d_old, StepRows r, float* out, int64_t n, hipStream_t s) {
+    if (vec4_ok("EDM", n, {x, F, d_old, out})) return 1;
+    if (rows_ok(r, n, "null step table")) return 1;
     hipLaunchKernelGGL(edm_dpmpp_kernel, grid4(n), dim3(256), 0, s, x, F, d_old, r, out, n);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_edm_finalize(const float* x, float* out, int64_t n, hipStream_t s) {
-    EDM_VEC_OK(n, x, out);
+    if (vec4_ok("EDM", n, {x, out})) return 1;
     hipLaunchKernelGGL(edm_finalize_kernel, grid4(n), dim3(256), 0, s, x, out, n);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_edm_scale(const float* x, float scale, float* out, int64_t n, hipStream_t s) {
-    EDM_VEC_OK(n, x, out);
+    if (vec4_ok("EDM", n, {x, out})) return 1;
     hipLaunchKernelGGL(edm_scale_kernel, grid4(n), dim3(256), 0, s, x, scale, out, n);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_edm_noise_in(const float* img, const float* eps, EdmRows r, float* x0, float* noised, float* xin, int64_t n,
+int launch_edm_noise_in(const float* img, const float* eps, StepRows r, float* x0, float* noised, float* xin, int64_t n,
                         hipStream_t s) {
     DM_REQUIRE(img && eps && x0 && noised && xin, "edm_noise_in: null tensor");
-    EDM_VEC_OK(n, img, eps, x0, noised, xin);
-    if (rows_ok(r, n)) return 1;
+    if (vec4_ok("EDM", n, {img, eps, x0, noised, xin})) return 1;
+    if (rows_ok(r, n, "null step table")) return 1;
     hipLaunchKernelGGL(edm_noise_in_kernel, grid4(n), dim3(256), 0, s, img, eps, r, x0, noised, xin, n);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
@@ -333,12 +292,10 @@ int launch_edm_loss(const float* noised, const float* F, const float* x0, const 
                     float* loss, int B, int64_t per, float loss_scale, hipStream_t s) {
     DM_REQUIRE(noised && F && x0 && tab && dF && part && loss && B > 0, "edm_loss: null tensor");
     DM_REQUIRE(per > 0 && per % 4 == 0 && per < (int64_t(1) << 30), "edm_loss: C*H*W must be a multiple of 4");
-    EDM_VEC_OK((int64_t)B * per, noised, F, x0, dF, D_out);
+    if (vec4_ok("EDM", (int64_t)B * per, {noised, F, x0, dF, D_out})) return 1;
     hipLaunchKernelGGL(edm_loss_kernel, dim3(B), dim3(256), 0, s, noised, F, x0, tab, dF, D_out, part, (int)per, B, loss_scale);
     DM_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(edm_loss_mean_kernel, dim3(1), dim3(1), 0, s, part, B, loss, loss_scale);
-    DM_CHECK_HIP(hipGetLastError());
-    return 0;
+    return launch_loss_mean(part, B, loss, loss_scale, s);  // :264 (losses.mean())
 }
 
 int launch_sinusoid_ft_bwd(const float* de0, const float* e0, float* dw, int B, int half, bool learned, int accumulate,

@@ -1,8 +1,7 @@
 // Bandwidth-bound kernels of the sampling path (gfx950): layout changes at the NCHW boundary,
 // RMSNorm / GroupNorm, the small Linear layers of the time embedding, the DDPM/DDIM update and
 // the Philox noise generator.  One wavefront = 64 lanes throughout.
-#include "dm_common.h"
-#include "philox.h"
+#include "step_device.h"
 
 namespace dm {
 
@@ -517,7 +516,7 @@ int launch_pointwise_small(const float* x, const float* w_oc, const float* bias,
 // ---------------------------------------------------------------------------------------
 // Philox4x32-10 + Box-Muller
 // ---------------------------------------------------------------------------------------
-// philox4x32_10 / philox_normal4: philox.h (shared with edm.hip)
+// philox4x32_10 / philox_normal4: philox.h (shared by every kernel that draws noise in place)
 __global__ void randn_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint64_t draw, uint64_t off4) {
     int64_t i4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i4 * 4 >= n) return;
@@ -538,7 +537,7 @@ int launch_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t e
 
 // ---------------------------------------------------------------------------------------
 // One sampler update (elementwise, layout-agnostic).  Restates, for objective pred_noise:
-//   DDPM  DD/denoising_diffusion.py:570-574 (x0), :633 (clamp), :594-598 (posterior mean), :643-644
+//   DDPM  DD/denoising_diffusion.py:570-574 (x0), :633 (clamp), :594-598 (posterior mean), :643-644 (ddpm_update, step_device.h)
 //   DDIM  DD/denoising_diffusion.py:607-613 (x0, clamp, re-derived eps), :686-701
 // Contraction is off so that the expression tree rounds exactly like the reference's tensor ops.
 // ---------------------------------------------------------------------------------------
@@ -559,7 +558,7 @@ __global__ void sampler_update_kernel(int kind, int objective, const float* __re
     const uint64_t seed = st ? st->seed : 0;
     const uint64_t off4 = st ? st->off4 : 0;
     const float* c = coefs + (size_t)step * 8;
-    const float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], c4 = c[4], c6 = c[6], c7 = c[7];
+    const DdpmCoefs dc = ddpm_coefs(c);
     const bool flag = c[5] != 0.0f;
     int64_t i4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i4 * 4 >= n) return;
@@ -570,7 +569,7 @@ __global__ void sampler_update_kernel(int kind, int objective, const float* __re
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (i4 * 4 + j < n) z[j] = np[i4 * 4 + j];
-        } else if (c4 != 0.0f) {
+        } else if (dc.c4 != 0.0f) {
             philox_normal4(seed, (uint64_t)step + 1, off4 + (uint64_t)i4, z);
         }
     }
@@ -579,19 +578,14 @@ __global__ void sampler_update_kernel(int kind, int objective, const float* __re
         int64_t i = i4 * 4 + j;
         if (i >= n) break;
         float xv = x[i], ev = eps[i];
-        float x0;
-        if (objective == 0) x0 = c0 * xv - c1 * ev;       // predict_start_from_noise :570-574
-        else if (objective == 1) x0 = ev;                  // the model predicts x_0 :614-617
-        else x0 = c6 * xv - c7 * ev;                       // predict_start_from_v :588-592
-        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        const float x0 = ddpm_x_start(dc, objective, xv, ev);
         if (xstart_out) xstart_out[i] = x0;
         float r;
         if (kind == 0) {
-            float mean = c2 * x0 + c3 * xv;
-            r = flag ? mean + c4 * z[j] : mean + c4 * 0.0f;
+            r = ddpm_update(dc, x0, xv, flag, z[j]);
         } else {
-            float e2 = (c0 * xv - x0) / c1;
-            r = flag ? (x0 * c2 + c3 * e2) + c4 * z[j] : x0;
+            float e2 = (dc.c0 * xv - x0) / dc.c1;
+            r = flag ? (x0 * dc.c2 + dc.c3 * e2) + dc.c4 * z[j] : x0;
         }
         out[i] = r;
         if (dup_out) dup_out[i] = r;

@@ -4,10 +4,10 @@
 // (:619-628), the DDPM update behind it (:630-636), the forward jump that opens a resample iteration (:672-674) and the
 // ground-truth paste at t == 0 (:638-640) -- is elementwise, so the update of row r and the jump and blend in front of row
 // r + 1 are one pass over the image: a masked row costs the launches of a plain DDPM step and adds the reads of gt and mask.
-// Bandwidth-bound like sampler_update_kernel, whose update it restates; 4 elements per thread share one Philox counter.
-// Contraction is off so the expression trees round like the reference's tensor ops.
+// Bandwidth-bound like sampler_update_kernel, whose update it shares (ddpm_update, step_device.h); 4 elements per thread
+// share one Philox counter.  Contraction is off so the expression trees round like the reference's tensor ops.
 #include "repaint.h"
-#include "philox.h"
+#include "step_device.h"
 
 namespace dm {
 
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void repaint_step_kernel(int mode, int objecti
     const int brow = mode == RP_BLEND ? row : row + 1;  // the row whose model call the blend prepares
     const float* c = tab + (size_t)(row - tab_base) * RP_NCOLS;
     const float* cb = tab + (size_t)(do_blend ? brow - tab_base : row - tab_base) * RP_NCOLS;
-    const float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], c4 = c[4], c6 = c[6], c7 = c[7];
+    const DdpmCoefs dc = ddpm_coefs(c);
     const bool step_noise = do_step && c[5] != 0.0f;
     const int slot = (int)c[RP_SLOT];
     const float kg = cb[RP_KNOWN_GT], kz = cb[RP_KNOWN_Z], jx = cb[RP_JUMP_X], jz = cb[RP_JUMP_Z];
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void repaint_step_kernel(int mode, int objecti
     if (i4 * 4 >= n) return;
     float zs[4] = {0.f, 0.f, 0.f, 0.f}, zj[4] = {0.f, 0.f, 0.f, 0.f}, zk[4] = {0.f, 0.f, 0.f, 0.f};
     if (philox) {
-        if (step_noise && c4 != 0.0f) philox_normal4(seed, repaint_draw_step((uint64_t)row), off4 + (uint64_t)i4, zs);
+        if (step_noise && dc.c4 != 0.0f) philox_normal4(seed, repaint_draw_step((uint64_t)row), off4 + (uint64_t)i4, zs);
         if (do_jump) philox_normal4(seed, repaint_draw_jump((uint64_t)brow), off4 + (uint64_t)i4, zj);
         if (do_blend) philox_normal4(seed, repaint_draw_known((uint64_t)brow), off4 + (uint64_t)i4, zk);
     } else {
@@ -82,15 +82,10 @@ __global__ __launch_bounds__(256) void repaint_step_kernel(int mode, int objecti
         if (i >= n) break;
         float v = x[i];
         if (do_step) {
-            const float xv = v, ev = eps[i];
-            float x0;
-            if (objective == 0) x0 = c0 * xv - c1 * ev;   // predict_start_from_noise :546-550
-            else if (objective == 1) x0 = ev;              // the model predicts x_0 :591-593
-            else x0 = c6 * xv - c7 * ev;                   // predict_start_from_v :564-568
-            x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+            // :630-636: model_predictions :546-568 / :591-593, q_posterior :570-574, noise = 0. at t == 0
+            const float x0 = ddpm_x_start(dc, objective, v, eps[i]);
             if (xstart_out) xstart_out[i] = x0;
-            const float mean = c2 * x0 + c3 * xv;          // q_posterior :570-574
-            v = step_noise ? mean + c4 * zs[j] : mean + c4 * 0.0f;  // :635-636 (noise = 0. at t == 0)
+            v = ddpm_update(dc, x0, v, step_noise, zs[j]);
         }
         if (mode == RP_STEP) {
             out[i] = v;

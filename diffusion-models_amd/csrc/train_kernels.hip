@@ -3,6 +3,7 @@
 // Downsample / Upsample rearrangements :48-58, final_conv, q_sample :813-821 and the weighted MSE :874-878).
 // All activations NHWC fp32 (rows = pixels, C contiguous) unless the name says nchw.  HBM-bound.
 #include "conv_device.h"
+#include "step_device.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1134,7 +1135,7 @@ __global__ void mse_loss_kernel(const float* __restrict__ out, const float* __re
             else if (objective == 1) { x0 = o; dx0 = 1.0f; }
             else { x0 = c[0] * x - c[1] * o; dx0 = -c[1]; }
             const bool inside = x0 >= -1.0f && x0 <= 1.0f;
-            const float x0c = fminf(fmaxf(x0, -1.0f), 1.0f);
+            const float x0c = clamp1(x0);
             const float mm = c[8] * x0c + c[9] * x;
             const float pm = c[8] * x_start[k] + c[9] * x;
             const float diff = mm - pm;
@@ -1148,20 +1149,23 @@ __global__ void mse_loss_kernel(const float* __restrict__ out, const float* __re
         }
         dout[k] = g;
     }
-    red[threadIdx.x] = s;
-    red2[threadIdx.x] = sk;
-    __syncthreads();
-    for (int m = 128; m > 0; m >>= 1) {
-        if ((int)threadIdx.x < m) {
-            red[threadIdx.x] += red[threadIdx.x + m];
-            red2[threadIdx.x] += red2[threadIdx.x + m];
-        }
-        __syncthreads();
-    }
+    s = block_sum256(s, red);
+    if (terms & 2) sk = block_sum256(sk, red2);  // a second tree only where the KL term is on (terms is uniform)
     if (threadIdx.x == 0) {
-        part[b] = (terms & 1) ? (float)(red[0] / per_sample) * c[2] : 0.f;
-        if (terms & 2) klpart[b] = (float)(red2[0] / per_sample) * c[3];  // kl * mask, as the reference multiplies
+        part[b] = (terms & 1) ? (float)(s / per_sample) * c[2] : 0.f;
+        if (terms & 2) klpart[b] = (float)(sk / per_sample) * c[3];  // kl * mask, as the reference multiplies
     }
+}
+// *loss = loss_scale * mean_b(part[b]), image order: the tail of the EDM and continuous-time losses (losses.mean())
+__global__ void loss_mean_kernel(const float* __restrict__ part, int B, float* __restrict__ loss, float loss_scale) {
+    double s = 0.0;
+    for (int b = 0; b < B; ++b) s += part[b];
+    *loss = (float)(s / B) * loss_scale;
+}
+int launch_loss_mean(const float* part, int B, float* loss, float loss_scale, hipStream_t s) {
+    hipLaunchKernelGGL(loss_mean_kernel, dim3(1), dim3(1), 0, s, part, B, loss, loss_scale);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 __global__ void mean_kernel(const float* __restrict__ part, const float* __restrict__ klpart, int B, float* __restrict__ loss,
                             float loss_scale, float kl_scale) {
@@ -1209,13 +1213,8 @@ __global__ void sumsq_partial_kernel(const float* __restrict__ x, int64_t n, dou
         s += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) s += (double)x[4 * n4 + threadIdx.x] * x[4 * n4 + threadIdx.x];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int m = 128; m > 0; m >>= 1) {
-        if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 // total_norm = sqrt(sum); clip coefficient = min(1, max_norm / (total_norm + 1e-6))  (torch.nn.utils.clip_grad_norm_)
 // One wave: lane l adds the partial sums l, l + 64, ... in order, the 64 lane sums meet in a fixed tree (a single thread

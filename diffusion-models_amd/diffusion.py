@@ -45,11 +45,6 @@ def _identity(t, *a, **k):
     return t
 
 
-def _default_seed() -> int:
-    """A Philox key from torch's global CPU generator (reproducible under torch.manual_seed)."""
-    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-
-
 ModelPrediction = namedtuple("ModelPrediction", ["pred_noise", "pred_x_start"])  # :33
 
 
@@ -198,12 +193,7 @@ class DenoisingDiffusion:
 
     # -- the loop --------------------------------------------------------------------------------------
     def _randn(self, shape, seed: int, draw: int, sample_offset: int = 0) -> torch.Tensor:
-        out = torch.empty(tuple(shape), device=self.device, dtype=torch.float32)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        per_sample = out.numel() // max(int(shape[0]), 1)
-        _lib.check(self._lib.dm_randn(_lib.ptr(out), out.numel(), C.c_uint64(seed), C.c_uint64(draw),
-                                      C.c_uint64(int(sample_offset) * per_sample), stream))
-        return out
+        return _lib.randn(self._lib, self.device, shape, seed, draw, sample_offset)
 
     def _run(self, kind, shape, times, coefs, takes_noise: Sequence[bool], return_all_timesteps, noise, seed,
              text_emb=None, max_steps=None, cond=None, sample_offset=0, x_init=None, unnormalize=None, guidance=None):
@@ -216,7 +206,7 @@ class DenoisingDiffusion:
         assert B > 0 and H % f == 0 and W % f == 0, f"shape {shape}: the sides must be divisible by {f}"
         n_steps = len(times)
         if seed is None:
-            seed = _default_seed()
+            seed = _lib.default_seed()
         sample_offset = int(sample_offset)
         if noise is not None:
             x_T = (noise(shape) if x_init is None else x_init).to(self.device, torch.float32).contiguous()
@@ -245,7 +235,7 @@ class DenoisingDiffusion:
                      if return_all_timesteps else None)
         times_arr = (C.c_int64 * n_steps)(*[int(t) for t in times[:n_steps]])
         coefs = coefs[:n_steps].contiguous()
-        coefs_ptr = C.cast(coefs.data_ptr(), C.POINTER(C.c_float))
+        coefs_ptr = _lib.fptr(coefs)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         a = _lib.SampleArgs()
         a.kind, a.objective, a.self_condition, a.n_steps = kind, self._objective_id, int(bool(self.self_condition)), n_steps
@@ -316,13 +306,13 @@ class DenoisingDiffusion:
         """:813-821, with the immiscible noise assignment of :815-817 when the object was built with ``immiscible=True``."""
         x_start = x_start.to(self.device, torch.float32).contiguous()
         noise = (noise.to(self.device, torch.float32).contiguous() if noise is not None
-                 else self._randn(x_start.shape, _default_seed(), 0))
+                 else self._randn(x_start.shape, _lib.default_seed(), 0))
         if self.immiscible:
             noise = self._assigned(x_start, noise)
         coef = self._tcoef(t)
         out = torch.empty_like(x_start)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.dm_op_q_sample(_lib.ptr(x_start), _lib.ptr(noise), C.cast(coef.data_ptr(), C.POINTER(C.c_float)),
+        _lib.check(self._lib.dm_op_q_sample(_lib.ptr(x_start), _lib.ptr(noise), _lib.fptr(coef),
                                             _lib.ptr(out), x_start.shape[0], x_start[0].numel(), stream))
         return out
 
@@ -357,13 +347,13 @@ class DenoisingDiffusion:
         if c != self.channels or h % f or w % f:
             raise RuntimeError(f"x_start {tuple(x_start.shape)}: expected {self.channels} channels and sides divisible by {f}")
         noise = (noise.to(self.device, torch.float32).contiguous() if noise is not None
-                 else self._randn(x_start.shape, _default_seed(), 0))
+                 else self._randn(x_start.shape, _lib.default_seed(), 0))
         if noise.shape != x_start.shape or t.numel() != b:
             raise RuntimeError(f"noise {tuple(noise.shape)} / t ({t.numel()} entries) do not match x_start {tuple(x_start.shape)}")
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if offset_noise_strength and offset_noise_strength > 0.0:
             offs = (offset_noise.to(self.device, torch.float32).contiguous() if offset_noise is not None
-                    else self._randn((b, c), _default_seed(), 3))
+                    else self._randn((b, c), _lib.default_seed(), 3))
             assert tuple(offs.shape) == (b, c)
             noise = noise.clone()  # the caller's tensor stays as it was
             _lib.check(self._lib.dm_op_offset_noise(_lib.ptr(noise), _lib.ptr(offs), float(offset_noise_strength), b * c, h * w,
@@ -392,7 +382,7 @@ class DenoisingDiffusion:
         a = _lib.TrainArgs()
         a.x_start, a.noise, a.noise_q, a.cond, a.ctx = (_lib.ptr(v) for v in (x_start, noise, noise_q, cond, ctx))
         a.t_host = C.cast(t_arr, C.POINTER(C.c_int64))
-        a.coef_host, a.coef_stride = C.cast(coef.data_ptr(), C.POINTER(C.c_float)), int(coef.shape[1])
+        a.coef_host, a.coef_stride = _lib.fptr(coef), int(coef.shape[1])
         a.cond_channels, a.ctx_tokens, a.self_cond, a.objective = cc, m, sc_mode, self._objective_id
         a.loss_scale, a.accumulate = float(loss_scale), int(bool(accumulate))
         a.loss_out_host = C.pointer(loss) if sync else None
@@ -477,7 +467,7 @@ class DenoisingDiffusion:
         t = self.num_timesteps - 1 if t is None else int(t)
         tb = torch.full((b,), t, dtype=torch.long)
         if seed is None:
-            seed = _default_seed()
+            seed = _lib.default_seed()
         n1 = noise(tuple(x1.shape)) if noise is not None else self._randn(x1.shape, seed, 1 << 20)
         n2 = noise(tuple(x1.shape)) if noise is not None else self._randn(x1.shape, seed, (1 << 20) + 1)
         xt1, xt2 = self.q_sample(x1, tb, n1), self.q_sample(x2, tb, n2)
@@ -508,7 +498,7 @@ class DenoisingDiffusion:
         coef = torch.stack([c0, -c1 if neg1 else c1], dim=1).to(torch.float32).contiguous()
         out = torch.empty_like(x)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.dm_op_lincomb(_lib.ptr(x), _lib.ptr(y), C.cast(coef.data_ptr(), C.POINTER(C.c_float)), _lib.ptr(out),
+        _lib.check(self._lib.dm_op_lincomb(_lib.ptr(x), _lib.ptr(y), _lib.fptr(coef), _lib.ptr(out),
                                            x.shape[0], x[0].numel(), mode, int(bool(clamp)), stream))
         return out
 
@@ -583,7 +573,7 @@ class DenoisingDiffusion:
         shape = tuple(int(v) for v in shape)
         b = shape[0]
         if seed is None:
-            seed = _default_seed()
+            seed = _lib.default_seed()
         draws = [0]
 
         def draw():
@@ -614,7 +604,7 @@ class DenoisingDiffusion:
             def comb(x, y, c0, c1):
                 coef = torch.tensor([[float(c0), float(c1)]] * b, dtype=torch.float32).contiguous()
                 out = torch.empty_like(x)
-                _lib.check(self._lib.dm_op_lincomb(_lib.ptr(x), _lib.ptr(y), C.cast(coef.data_ptr(), C.POINTER(C.c_float)),
+                _lib.check(self._lib.dm_op_lincomb(_lib.ptr(x), _lib.ptr(y), _lib.fptr(coef),
                                                    _lib.ptr(out), b, x[0].numel(), 0, 0, stream))
                 return out
 
@@ -653,7 +643,7 @@ class DenoisingDiffusion:
         z = None
         if t > 0:
             z = (noise(x.shape).to(self.device, torch.float32).contiguous() if noise is not None
-                 else self._randn(x.shape, _default_seed(), 1))
+                 else self._randn(x.shape, _lib.default_seed(), 1))
         out = torch.empty_like(x)
         x_start = torch.empty_like(x)
         _lib.check(self._lib.dm_op_sampler_update(DDPM, self._objective_id, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(z), coef,

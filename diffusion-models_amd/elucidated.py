@@ -30,6 +30,8 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._floattime import FloatTimeDiffusion
+from ._lib import fptr as _fptr
 
 COLS = _lib.DM_EDM_COEFS
 # columns of a step-table row (csrc/edm.h)
@@ -132,16 +134,11 @@ def edm_train_table(sigmas: torch.Tensor, sigma_data=0.5) -> torch.Tensor:
     return tab
 
 
-def _default_seed() -> int:
-    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-
-
-def _fptr(t: torch.Tensor):
-    return C.cast(t.data_ptr(), C.POINTER(C.c_float))
-
-
-class ElucidatedDiffusion:
+class ElucidatedDiffusion(FloatTimeDiffusion):
     """``ElucidatedDiffusion(net, image_size=...)`` -- drop-in for the reference class: training loss and samplers."""
+
+    _unet_attr = "net"
+    _train_entry = "dm_unet_loss_backward_edm"
 
     def __init__(
         self,
@@ -162,19 +159,8 @@ class ElucidatedDiffusion:
         S_noise=1.003,
         use_graph=True,
     ):
-        assert net.random_or_learned_sinusoidal_cond
-        if getattr(net, "self_condition", False):
-            raise NotImplementedError("ElucidatedDiffusion with a self_condition U-Net is not built on the HIP path")
-        if getattr(net, "text_condition", False) or getattr(getattr(net, "cfg", None), "cond_channels", 0):
-            raise NotImplementedError("ElucidatedDiffusion calls net(x, t, self_cond) only: a text-conditional or "
-                                      "image-conditional U-Net has no place for its condition")
-        if net.out_dim != channels or net.channels != channels:
-            raise ValueError(f"the U-Net maps {net.channels} to {net.out_dim} channels, the sampler needs {channels} -> "
-                             f"{channels} (no learned variance)")
+        self._init_unet(net, image_size, channels, use_graph, "ElucidatedDiffusion calls net(x, t, self_cond) only")
         self.self_condition = net.self_condition
-        self.net = net
-        self.channels = channels
-        self.image_size = image_size
         self.sigma_min = sigma_min
         self.sigma_max = sigma_max
         self.sigma_data = sigma_data
@@ -186,34 +172,11 @@ class ElucidatedDiffusion:
         self.S_tmin = S_tmin
         self.S_tmax = S_tmax
         self.S_noise = S_noise
-        self.use_graph = use_graph
-        self._lib = _lib.load()
 
-    # -- module-ish surface ------------------------------------------------------------------------
-    @property
-    def device(self):
-        return self.net.device
-
-    def eval(self):
-        return self
-
-    def parameters(self):
-        return self.net.parameters()
-
-    def sample_shape(self):
-        """(C, H, W) of one sample (``dist.sample_global`` builds empty shards from it)."""
-        return (self.channels, self.image_size, self.image_size)
-
-    def state_dict(self):
-        """The reference module has no buffers: ``net.`` + the U-Net's keys."""
-        return {"net." + k: v for k, v in self.net.state_dict().items()}
-
-    def load_state_dict(self, state_dict, strict=True):
-        other = [k for k in state_dict if not k.startswith("net.")]
-        if strict and other:
-            raise RuntimeError(f"Error(s) in loading state_dict: unexpected {other[:5]}")
-        self.net.load_state_dict({k[len("net."):]: v for k, v in state_dict.items() if k.startswith("net.")}, strict=strict)
-        return self
+    @staticmethod
+    def _refuse_self_condition(net):
+        if getattr(net, "self_condition", False):
+            raise NotImplementedError("ElucidatedDiffusion with a self_condition U-Net is not built on the HIP path")
 
     # -- Table 1 -----------------------------------------------------------------------------------
     def c_skip(self, sigma):
@@ -260,7 +223,7 @@ class ElucidatedDiffusion:
         tab = torch.zeros((rows, COLS), dtype=torch.float32)
         tab[:, C_IN], tab[:, C_NOISE], tab[:, C_SKIP], tab[:, C_OUT] = edm_precond(sig, self.sigma_data)
         tab[:, SIGMA] = sig
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         xin = torch.empty_like(x)
         _lib.check(self._lib.dm_op_edm_churn_in(_lib.ptr(x), None, _fptr(tab), rows, 0, 1, 0, None, _lib.ptr(xin), b, per,
                                                 stream))
@@ -271,36 +234,19 @@ class ElucidatedDiffusion:
         return out
 
     # -- sampling ----------------------------------------------------------------------------------
-    def _randn(self, shape, seed, draw, sample_offset):
-        out = torch.empty(tuple(shape), device=self.device, dtype=torch.float32)
-        per = out.numel() // max(int(shape[0]), 1)
-        _lib.check(self._lib.dm_randn(_lib.ptr(out), out.numel(), C.c_uint64(seed), C.c_uint64(draw),
-                                      C.c_uint64(int(sample_offset) * per), torch.cuda.current_stream(self.device).cuda_stream))
-        return out
-
     def _run(self, kind, table, sigma_init, batch_size, clamp, noise, noise_rows, seed, sample_offset):
         shape = (int(batch_size), self.channels, self.image_size, self.image_size)
         f = self.net.downsample_factor
         assert shape[0] > 0 and self.image_size % f == 0, f"shape {shape}: the sides must be divisible by {f}"
-        if seed is None:
-            seed = _default_seed()
-        n_steps = table.shape[0]
-        if noise is not None:
-            x_init = noise(shape).to(self.device, torch.float32).contiguous()
-            noise_dev = (torch.stack([noise(shape).to(torch.float32) for _ in range(noise_rows)], dim=0)
-                         .to(self.device).contiguous() if noise_rows else None)
-        else:
-            x_init = self._randn(shape, seed, 0, sample_offset)
-            noise_dev = None
-        assert tuple(x_init.shape) == shape, "noise() must return tensors of the sampled shape"
+        seed, x_init, noise_dev = self._start(shape, noise, noise_rows, seed, sample_offset)
         table = table.contiguous()
         out = torch.empty(shape, device=self.device, dtype=torch.float32)
         a = _lib.EdmArgs()
-        a.kind, a.n_steps, a.table_host = kind, n_steps, _fptr(table)
+        a.kind, a.n_steps, a.table_host = kind, table.shape[0], _fptr(table)
         a.x_init, a.noise, a.seed, a.sample_offset = _lib.ptr(x_init), _lib.ptr(noise_dev), seed, int(sample_offset)
         a.out, a.sigma_init, a.clamp = _lib.ptr(out), float(sigma_init), int(bool(clamp))
         a.B, a.H, a.W = shape[0], shape[2], shape[3]
-        a.use_graph, a.stream = 1 if self.use_graph else 0, torch.cuda.current_stream(self.device).cuda_stream
+        a.use_graph, a.stream = 1 if self.use_graph else 0, self._stream()
         _lib.check(self._lib.dm_sample_edm(self.net._handle, C.byref(a)))
         return out
 
@@ -321,35 +267,11 @@ class ElucidatedDiffusion:
         return self._run(_lib.EDM_DPMPP, table, sigma_init, batch_size, False, noise, 0, seed, sample_offset)
 
     # -- training ----------------------------------------------------------------------------------
-    def _trainable_net(self):
-        """The library ``Unet`` behind ``net``; anything else (no handle, or a library without the float-time training
-        entry) cannot be trained.  Touches neither a tensor nor the device."""
-        from .unet import Unet
-
-        net = self.net
-        if not isinstance(net, Unet) or getattr(net, "_handle", None) is None or not hasattr(self._lib, "dm_unet_loss_backward_edm"):
-            raise NotImplementedError("ElucidatedDiffusion can train a library Unet only (dm_unet_train_enable_ft arms its "
-                                      f"handle for the float-time training loss); got {type(net).__name__}")
-        return net
-
-    def train(self, mode: bool = True):
-        """``model.train()``: arm the U-Net for float-time training (gradient buffers, input-gradient convolutions; once)."""
-        if mode:
-            net = self._trainable_net()
-            if not net._loaded:
-                raise RuntimeError("load_state_dict() must be called before train()")
-            # random_fourier_features: the reference builds time_mlp.0.weights with requires_grad = False
-            _lib.check(self._lib.dm_unet_train_enable_ft(net._handle, int(bool(net.cfg.random_fourier_features))))
-            if not getattr(net, "_training", False):
-                net.set_dropout_seed(int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
-            net._training = True
-        return self
-
     def forward(self, images, *, sigmas=None, noise=None, loss_scale=1.0, accumulate=False, sync=True,
                 return_denoised=False):
         """:234-264: the loss (0-dim CPU tensor; ``sync=False``: a 0-dim device tensor, nothing waited for); the parameter
         gradients stay on the U-Net (``self.net.grad(name)`` / ``.grads()``).  ``images`` in [0, 1]."""
-        net = self._trainable_net()
+        net = self._trainable()
         b, c, h, w = images.shape
         assert h == self.image_size and w == self.image_size, f"height and width of image must be {self.image_size}"
         assert c == self.channels, "mismatch of image channels"
@@ -359,27 +281,15 @@ class ElucidatedDiffusion:
         sig = self._draw_sigmas(b) if sigmas is None else sigmas.detach().to("cpu", torch.float32).reshape(-1)
         if sig.numel() != b:
             raise RuntimeError(f"sigmas has {sig.numel()} entries for a batch of {b}")
-        images = images.to(self.device, torch.float32).contiguous()
-        noise = (noise.to(self.device, torch.float32).contiguous() if noise is not None
-                 else self._randn(images.shape, _default_seed(), 0, 0))
-        if noise.shape != images.shape:
-            raise RuntimeError(f"noise {tuple(noise.shape)} does not match images {tuple(images.shape)}")
+        images, noise = self._loss_inputs(images, noise)
         tab = edm_train_table(sig, self.sigma_data).contiguous()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        loss = C.c_float(0.0)
         den = torch.empty_like(images) if return_denoised else None
         a = _lib.EdmTrainArgs()
         a.images, a.noise, a.coef_host, a.coef_stride = _lib.ptr(images), _lib.ptr(noise), _fptr(tab), COLS
         a.loss_scale, a.accumulate = float(loss_scale), int(bool(accumulate))
         a.B, a.H, a.W = b, h, w
-        a.loss_out_host = C.pointer(loss) if sync else None
-        a.denoised_out, a.stream = _lib.ptr(den), stream
-        _lib.check(self._lib.dm_unet_loss_backward_edm(net._handle, C.byref(a)))
-        if sync:
-            val = torch.tensor(loss.value, dtype=torch.float32)
-        else:
-            val = torch.empty((), device=self.device, dtype=torch.float32)
-            _lib.check(self._lib.dm_unet_train_scalar(net._handle, 0, _lib.ptr(val), stream))
+        a.denoised_out = _lib.ptr(den)
+        val = self._loss_call(a, sync)
         return (val, den) if return_denoised else val
 
     __call__ = forward

@@ -23,7 +23,7 @@ from typing import Dict, List, NamedTuple
 import torch
 
 from . import _lib
-from .diffusion import DenoisingDiffusion, _default_seed
+from .diffusion import DenoisingDiffusion
 from .spec import ddpm_step_table
 
 COLS = _lib.DM_REPAINT_COEFS
@@ -157,7 +157,7 @@ class GaussianDiffusion(DenoisingDiffusion):
         tab = repaint_step_table(self._sched, resample, resample_iter, resample_jump, resample_every)
         n_rows = len(tab.times)
         if seed is None:
-            seed = _default_seed()
+            seed = _lib.default_seed()
         sample_offset = int(sample_offset)
         if noise is not None:
             x_T = noise(shape).to(self.device, torch.float32).contiguous()
@@ -180,7 +180,7 @@ class GaussianDiffusion(DenoisingDiffusion):
         a = _lib.RepaintArgs()
         a.objective, a.n_rows = self._objective_id, n_rows
         a.times_host = C.cast(times_arr, C.POINTER(C.c_int64))
-        a.table_host = C.cast(coefs.data_ptr(), C.POINTER(C.c_float))
+        a.table_host = _lib.fptr(coefs)
         a.x_T, a.noise, a.seed, a.sample_offset = _lib.ptr(x_T), _lib.ptr(noise_dev), seed, sample_offset
         a.gt, a.mask, a.mask_channels = _lib.ptr(gt), _lib.ptr(mask), int(mask.shape[1])
         a.unnormalize = 0 if return_all_timesteps else self._unnormalize_flag  # the frames are unnormalised together below
@@ -219,14 +219,14 @@ class GaussianDiffusion(DenoisingDiffusion):
         row[:8] = ddpm_step_table(s)[1][self.num_timesteps - 1 - t]
         row[KNOWN_GT], row[KNOWN_Z] = torch.sqrt(s["alphas_cumprod"][t]), torch.sqrt(1 - s["alphas_cumprod"][t])
         row[JUMP_X], row[SLOT] = 1.0, -1.0
-        coef = C.cast(row.data_ptr(), C.POINTER(C.c_float))
+        coef = _lib.fptr(row)
         if noise is not None:
             z_known = noise(shape).to(self.device, torch.float32).contiguous()
             z_step = noise(shape).to(self.device, torch.float32).contiguous() if t > 0 else None
             seed = 0
         else:
             z_known = z_step = None
-            seed = _default_seed()
+            seed = _lib.default_seed()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         mc = int(mask.shape[1])
 

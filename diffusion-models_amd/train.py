@@ -21,9 +21,8 @@ import torch
 def _unet_of(diffusion):
     """The U-Net of a diffusion object and its state-dict prefix: ``model`` (DenoisingDiffusion and its variants, the
     continuous-time classes) or ``net`` (ElucidatedDiffusion)."""
-    if hasattr(diffusion, "model"):
-        return diffusion.model, "model"
-    return diffusion.net, "net"
+    attr = getattr(diffusion, "_unet_attr", "model")
+    return getattr(diffusion, attr), attr
 
 
 class EMA:

@@ -197,7 +197,7 @@ class Unet:
                                           "whenever x_self_cond is not given (zeros_like of the concatenated input)")
             _lib.check(self._lib.dm_unet_train_enable(self._handle))
             if not getattr(self, "_training", False):
-                self.set_dropout_seed(int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()))
+                self.set_dropout_seed(_lib.default_seed())
             self._training = True
         return self
 
