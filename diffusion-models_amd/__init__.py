@@ -28,6 +28,7 @@ from .elucidated import (ElucidatedDiffusion, edm_dpmpp_table, edm_heun_table, e
 from .continuous import (ContinuousTimeGaussianDiffusion, VParamContinuousTimeGaussianDiffusion,  # noqa: F401
                          alpha_cosine_log_snr, beta_linear_log_snr, ct_step_table, ct_train_table)
 from .repaint import GaussianDiffusion as RePaintGaussianDiffusion, RepaintTable, repaint_step_table  # noqa: F401
+from .learned import LearnedGaussianDiffusion, lv_step_table, lv_train_table  # noqa: F401
 from .vae import VQDecoder, VQEncoder, VQModel  # noqa: F401
 from .dist import gather_shards, sample_global, sample_sharded, shard_bounds, shared_seed  # noqa: F401
 from .checkpoint import load_trainer_checkpoint, load_vae_checkpoint  # noqa: F401
@@ -47,6 +48,7 @@ __all__ = [
     "ContinuousTimeGaussianDiffusion",
     "VParamContinuousTimeGaussianDiffusion",
     "RePaintGaussianDiffusion",
+    "LearnedGaussianDiffusion",
     "VQDecoder",
     "VQEncoder",
     "VQModel",
@@ -73,6 +75,8 @@ __all__ = [
     "ct_train_table",
     "repaint_step_table",
     "RepaintTable",
+    "lv_step_table",
+    "lv_train_table",
     "synth_state_dict",
     "synth_tensor",
 ]

@@ -21,6 +21,8 @@ EDM_HEUN, EDM_DPMPP = 0, 1
 DM_CT_COEFS = 16
 CT_PRED_NOISE, CT_PRED_V = 0, 1
 DM_REPAINT_COEFS = 16
+DM_LV_COEFS = 16
+DM_LV_TRAIN_COEFS = 12
 ABI_VERSION = 9
 
 # every symbol include/dm_hip.h declares (tests check the library exports all of them)
@@ -53,6 +55,7 @@ EXPORTS = (
     "dm_op_edm_noise_in", "dm_op_edm_loss", "dm_op_sinusoid_ft_bwd",
     "dm_sample_ct", "dm_unet_loss_backward_ct", "dm_op_ct_step", "dm_op_ct_noise_in", "dm_op_ct_loss",
     "dm_sample_repaint", "dm_op_repaint_step",
+    "dm_sample_lv", "dm_unet_loss_backward_lv", "dm_op_lv_step", "dm_op_lv_loss",
 )
 
 
@@ -145,6 +148,26 @@ class RepaintArgs(C.Structure):
         ("sample_offset", C.c_uint64), ("gt", C.c_void_p), ("mask", C.c_void_p), ("mask_channels", C.c_int32),
         ("unnormalize", C.c_int32), ("out", C.c_void_p), ("all_steps", C.c_void_p), ("n_frames", C.c_int32),
         ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("use_graph", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
+class LvArgs(C.Structure):
+    """dm_lv_args (include/dm_hip.h)."""
+    _fields_ = [
+        ("n_steps", C.c_int32), ("times_host", C.POINTER(C.c_int64)), ("table_host", C.POINTER(C.c_float)),
+        ("x_T", C.c_void_p), ("noise", C.c_void_p), ("seed", C.c_uint64), ("sample_offset", C.c_uint64),
+        ("out", C.c_void_p), ("all_steps", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("unnormalize", C.c_int32), ("use_graph", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
+class LvTrainArgs(C.Structure):
+    """dm_lv_train_args (include/dm_hip.h)."""
+    _fields_ = [
+        ("x_start", C.c_void_p), ("t_host", C.POINTER(C.c_int64)), ("coef_host", C.POINTER(C.c_float)),
+        ("coef_stride", C.c_int32), ("noise", C.c_void_p), ("vb_loss_weight", C.c_float), ("clip_denoised", C.c_int32),
+        ("loss_scale", C.c_float), ("accumulate", C.c_int32), ("loss_out_host", C.POINTER(C.c_float)),
+        ("model_out", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("stream", C.c_void_p),
     ]
 
 
@@ -281,6 +304,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_sample_repaint.argtypes = [vp, C.POINTER(RepaintArgs)]
     lib.dm_op_repaint_step.argtypes = [i32, i32, fp, fp, fp, fp, i32, fp, fp, fp, C.POINTER(C.c_float), i32, u64, u64, u64, fp, fp,
                                        i32, i32, i32, vp]
+    lib.dm_sample_lv.argtypes = [vp, C.POINTER(LvArgs)]
+    lib.dm_unet_loss_backward_lv.argtypes = [vp, C.POINTER(LvTrainArgs)]
+    lib.dm_op_lv_step.argtypes = [fp, fp, fp, C.POINTER(C.c_float), u64, u64, u64, fp, fp, fp, fp, i32, i64, vp]
+    lib.dm_op_lv_loss.argtypes = [fp, fp, fp, fp, C.POINTER(C.c_float), C.c_float, i32, C.c_float, fp, C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i64, vp]
     lib.dm_profile_read.argtypes = [C.POINTER(ProfileRow), i32, C.POINTER(i32)]
 
 

@@ -7,6 +7,7 @@
 #include "edm.h"
 #include "ct.h"
 #include "repaint.h"
+#include "learned.h"
 
 #include <array>
 #include <cmath>
@@ -241,7 +242,7 @@ struct ConvLayer {
     float* wwu = nullptr;  // transformed weights of the upsample + 3x3 algorithm (upwino_mfma.hip)
     float* wpw = nullptr;  // lane-ordered weights of the 1x1 GEMM kernel (pw_mfma.hip)
     float* wi7 = nullptr;  // weights of the 7x7 first-conv kernel (init7_mfma.hip)
-    float* wraw = nullptr;  // (Cout, Cin) weights of a 1x1 conv with Cout <= 4 (pointwise_small_kernel)
+    float* wraw = nullptr;  // (Cout, Cin) weights of a 1x1 conv with Cout <= 8 (pointwise_small_kernel)
     float* bias = nullptr;
 };
 
@@ -317,7 +318,7 @@ struct dm_unet {
     std::vector<std::pair<std::string, ResBlock*>> resnets;  // in ss_off order
     // the instantiated graph of one denoise step, reused while the key (shape, kind, every captured pointer) holds.  The
     // slot serves every sampling loop of the handle (dm_sampler.inc: run_steps); the kind says whose graph it holds.
-    enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT };
+    enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT, GK_LV };
     struct GraphKey {
         int kind = GK_NONE, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
         int edm_clamp = 0;      // ElucidatedDiffusion: the clamp flag, a kernel argument of the captured Heun step
@@ -516,7 +517,7 @@ static int make_conv(DeviceOwner& own, ConvLayer& L, const float* oihw, const fl
         own.record(PK_INIT7, L.wi7, wp.size(), Cout, C0, C1, KH, KW);
     }
     L.wraw = nullptr;
-    if (KH == 1 && KW == 1 && stride == 1 && pad == 0 && !up && Cout <= 4 && C1 == 0 && C0 % 4 == 0) {
+    if (KH == 1 && KW == 1 && stride == 1 && pad == 0 && !up && Cout <= 8 && C1 == 0 && C0 % 4 == 0) {
         if (own.upload(oihw, (size_t)Cout * C0, &L.wraw)) return 1;
         own.record(PK_RAW_W, L.wraw, (size_t)Cout * C0, Cout, C0, C1, KH, KW);
     }
@@ -1650,3 +1651,4 @@ int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t eleme
 #include "dm_edm.inc"
 #include "dm_ct.inc"
 #include "dm_repaint.inc"
+#include "dm_learned.inc"

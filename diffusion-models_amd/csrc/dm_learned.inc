@@ -1,0 +1,207 @@
+// LearnedGaussianDiffusion on the C ABI: the sampling loop, the hybrid loss + backward and the single-pass entry points
+// (dm_op_lv_*).  Included by dm_api.hip after dm_train.inc (the tape forward / backward), dm_sampler.inc (the loop
+// scaffolding) and dm_edm.inc (the state helper of the dm_op_* passes); kernels in learned.hip.
+
+namespace dm {
+
+static_assert(DM_LV_COEFS == LV_NCOLS && DM_LV_COEFS == DM_EDM_COEFS,
+              "the learned-variance step table lives in the handle's EDM table buffer: the row widths must agree");
+static_assert(DM_LV_TRAIN_COEFS == LVT_NCOLS && DM_LV_TRAIN_COEFS == DM_TRAIN_COEFS,
+              "the learned-variance training rows live in the training state's coefficient buffer (q_sample reads columns 0, 1)");
+
+static int lv_unet_ok(dm_unet* u) {
+    DM_REQUIRE(u->cfg.text_mode == DM_TEXT_NONE, "LearnedGaussianDiffusion calls model(x, t) only: no text-conditional U-Net");
+    DM_REQUIRE(u->cfg.learned_sinusoidal_dim == 0, "LearnedGaussianDiffusion calls model(x, t) with an integer time");
+    DM_REQUIRE(u->out_dim == 2 * u->cfg.channels && u->cfg.input_channels == u->cfg.channels,
+               "LearnedGaussianDiffusion needs a U-Net with out_dim == 2 * channels == 2 * input channels "
+               "(DD/learned_gaussian_diffusion.py:70-71: learned_variance=True, no self-conditioning)");
+    return 0;
+}
+
+// p_sample_loop of the base class (DD/denoising_diffusion.py:647-664) with the subclass's p_mean_variance.  One step -- the
+// forward into the 2n buffer, lv_step_kernel, the step counter -- is one linear chain that reads everything that differs
+// between two calls of one shape (tables, step counter and count, seed, Philox offset, unnormalise) as device data: it is
+// captured once per shape.
+static int sample_lv_impl(dm_unet* u, const dm_lv_args* a) {
+    DM_REQUIRE(a->times_host && a->table_host && a->x_T && a->out, "null argument");
+    DM_REQUIRE(a->n_steps > 0 && a->B > 0, "empty run");
+    if (handle_ready(u)) return 1;
+    if (lv_unet_ok(u)) return 1;
+    const int B = a->B, H = a->H, W = a->W, n_steps = a->n_steps;
+    if (check_hw(u, H, W)) return 1;
+    DM_CHECK_HIP(hipSetDevice(u->device));
+    const int C = u->cfg.channels;
+    const int64_t per = (int64_t)C * H * W, n = (int64_t)B * per;
+    DM_REQUIRE(per % 4 == 0, "C * H * W must be a multiple of 4");
+    const float* noise = a->noise;
+    float* all_steps = a->all_steps;
+
+    SamplerRun r;
+    if (grow_tables(u, TAB_INT | TAB_FLOAT, n_steps, 1) || run_begin(r, u, a->stream, a->use_graph)) return 1;
+    hipStream_t s = r.s;
+    // workspace: [x | model output (2n) | result | forward arena]
+    float *xbuf, *eps2, *fin;
+    auto layout = [&](Arena& A) {
+        xbuf = A.alloc(n);
+        eps2 = A.alloc(2 * n);
+        fin = A.alloc(n);  // what the last step leaves for `out`: the caller's pointer stays out of the captured graph
+    };
+    if (run_workspace(r, layout, [&](Arena& dry) {
+            return unet_forward_impl(u, dry, nullptr, nullptr, u->times_dev, u->state_dev, nullptr, 0, nullptr, B, H, W, s);
+        }))
+        return 1;
+    if (run_upload(r, n_steps, a->times_host, nullptr, a->table_host, a->unnormalize ? 1 : 0, a->seed,
+                   a->sample_offset * (uint64_t)per))
+        return 1;
+    const float* tab = u->edm_tab_dev;
+
+    DM_CHECK_HIP(hipMemcpyAsync(xbuf, a->x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));  // img = randn(shape)
+    if (all_steps) DM_CHECK_HIP(hipMemcpyAsync(all_steps, a->x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+
+    auto step = [&](hipStream_t st) -> int {
+        r.rewind();
+        if (unet_forward_impl(u, r.A, xbuf, nullptr, u->times_dev, u->state_dev, nullptr, 0, eps2, B, H, W, st)) return 1;
+        if (launch_lv_step(xbuf, eps2, noise, n, tab, u->state_dev, STEP_ROW_STEP, per, xbuf, all_steps, fin, nullptr, nullptr, nullptr, n, st))
+            return 1;
+        return launch_step_advance(u->state_dev, st);
+    };
+    dm_unet::GraphKey key;
+    key.kind = dm_unet::GK_LV;
+    key.B = B; key.H = H; key.W = W;
+    key.noise = noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.tab = u->edm_tab_dev;
+    if (run_steps(r, key, n_steps, step)) return 1;
+    DM_CHECK_HIP(hipMemcpyAsync(a->out, fin, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return run_finish(r);
+}
+
+// p_losses (DD/learned_gaussian_diffusion.py:113-146) and the backward pass: the body of loss_backward_impl without
+// self-conditioning, condition image and text -- q_sample, the tape forward into a 2n buffer, the loss with its gradient,
+// the backward pass.
+static int loss_backward_lv_impl(dm_unet* u, const dm_lv_train_args& a) {
+    DM_REQUIRE(a.x_start && a.t_host && a.coef_host && a.noise, "null argument");
+    DM_REQUIRE(u->train, "dm_unet_train_enable has not been called");
+    DM_REQUIRE(!u->train->ft, "the handle is armed for float-time training (dm_unet_train_enable_ft)");
+    DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
+    const int cstride = a.coef_stride ? a.coef_stride : DM_LV_TRAIN_COEFS;
+    DM_REQUIRE(a.B > 0 && cstride > LVT_T0 && cstride <= DM_LV_TRAIN_COEFS, "coef_host rows hold 10 to 12 floats (the t == 0 flag is column 9)");
+    if (lv_unet_ok(u)) return 1;
+    const int B = a.B, H = a.H, W = a.W, accumulate = a.accumulate ? 1 : 0;
+    if (check_hw(u, H, W)) return 1;
+    DM_CHECK_HIP(hipSetDevice(u->device));
+    hipStream_t s = static_cast<hipStream_t>(a.stream);
+    TrainState& T = *u->train;
+    if (grow_train_rows(T, B)) return 1;
+    const int64_t per = (int64_t)u->cfg.channels * H * W, n = (int64_t)B * per;
+    DM_REQUIRE(per % 4 == 0 && per < (int64_t(1) << 30), "C * H * W must be a multiple of 4");
+    auto run = [&](Arena& A, Tape& tp) -> int {
+        float* x = A.alloc(n);
+        float* out = A.alloc(2 * n);
+        float* dout = A.alloc(2 * n);
+        float* part = A.alloc(3 * (size_t)B);  // [loss | mse | vb] per image
+        if (!A.dry && launch_q_sample(a.x_start, a.noise, T.coef_dev, x, B, (int)per, s)) return 1;
+        if (unet_train_forward(u, A, x, T.t_dev, out, B, H, W, s, tp, nullptr, 0, nullptr)) return 1;
+        if (!A.dry) {
+            if (launch_lv_loss(out, a.x_start, a.noise, x, T.coef_dev, a.vb_loss_weight, a.clip_denoised, dout, part, part + B,
+                               part + 2 * B, T.loss_dev, B, per, a.loss_scale, s))
+                return 1;
+            if (a.model_out) DM_CHECK_HIP(hipMemcpyAsync(a.model_out, out, 2 * n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+        return unet_train_backward(u, A, x, dout, B, H, W, s, tp, accumulate);
+    };
+    try {
+        // (the fourth entry is self_cond on the plain path and -1 / -2 on the float-time paths)
+        const std::array<long long, 8> key{B, H, W, -3, 0, 0, 0, (a.model_out ? 1 : 0) | (T.bucketed ? 2 : 0)};
+        auto known = T.ws_need.find(key);
+        if (known == T.ws_need.end()) {
+            Arena dry;
+            dry.dry = true;
+            Tape tp;
+            if (run(dry, tp)) return 1;
+            known = T.ws_need.emplace(key, dry.off).first;
+        }
+        if (ensure_train_ws(T, known->second)) return 1;
+        if (u->order_after_previous(s)) return 1;
+        T.coef_stage.assign((size_t)B * DM_LV_TRAIN_COEFS, 0.f);
+        for (int b = 0; b < B; ++b)
+            std::memcpy(&T.coef_stage[(size_t)b * DM_LV_TRAIN_COEFS], a.coef_host + (size_t)b * cstride, cstride * sizeof(float));
+        DM_CHECK_HIP(hipMemcpyAsync(T.coef_dev, T.coef_stage.data(), (size_t)B * DM_LV_TRAIN_COEFS * sizeof(float),
+                                    hipMemcpyHostToDevice, s));
+        DM_CHECK_HIP(hipMemcpyAsync(T.t_dev, a.t_host, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        Arena A;
+        A.base = T.ws;
+        A.cap = T.ws_cap;
+        Tape tp;
+        if (run(A, tp)) return 1;
+        T.drop_call += 1;
+        DM_REQUIRE(A.off <= T.ws_cap, "training workspace overrun: the dry run and the real run allocated differently");
+    } catch (const std::exception& e) {
+        set_error(e.what());
+        return 1;
+    }
+    if (u->mark_done(s)) return 1;
+    if (!a.loss_out_host) return 0;  // asynchronous form: the loss stays on the device (dm_unet_train_scalar)
+    DM_CHECK_HIP(hipMemcpyAsync(a.loss_out_host, T.loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+    DM_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+}  // namespace dm
+
+extern "C" {
+
+int dm_sample_lv(dm_unet* u, const dm_lv_args* a) {
+    DM_REQUIRE(u && a, "null argument");
+    return sample_lv_impl(u, a);
+}
+
+int dm_unet_loss_backward_lv(dm_unet* u, const dm_lv_train_args* a) {
+    DM_REQUIRE(u && a, "null argument");
+    return loss_backward_lv_impl(u, *a);
+}
+
+int dm_op_lv_step(const float* x, const float* model_out, const float* z, const float* c_host, uint64_t seed, uint64_t draw,
+                  uint64_t element_offset, float* out, float* mean_out, float* logvar_out, float* x_start_out, int B,
+                  int64_t per, void* stream) {
+    DM_REQUIRE(x && model_out && c_host && out, "null argument");
+    DM_REQUIRE(B > 0 && per > 0, "empty tensor");
+    DM_REQUIRE(element_offset % 4 == 0, "Philox element offset must be a multiple of 4 (one counter serves 4 elements)");
+    DM_REQUIRE(z || draw >= 1, "Philox draw 0 is the initial noise: a step's draw is its index + 1");
+    DM_REQUIRE(draw < (uint64_t(1) << 30), "draw index out of range");
+    return state_op(draw_state(z != nullptr, seed, draw, element_offset), c_host, 1, stream,
+                    [&](const SamplerState* st, const float* cd, hipStream_t s) {
+                        return launch_lv_step(x, model_out, z, 0, cd, st, STEP_ROW_FIRST, per, out, nullptr, nullptr, mean_out,
+                                              logvar_out, x_start_out, (int64_t)B * per, s);
+                    });
+}
+
+int dm_op_lv_loss(const float* model_out, const float* x_start, const float* noise, const float* x_t, const float* c_host,
+                  float vb_loss_weight, int clip_denoised, float loss_scale, float* dout, float* loss_out_host,
+                  float* mse_part_out_host, float* vb_part_out_host, int B, int64_t per, void* stream) {
+    DM_REQUIRE(model_out && x_start && noise && x_t && c_host && dout && loss_out_host && B > 0, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n_tab = (size_t)B * LVT_NCOLS;
+    float* scratch = nullptr;  // [B rows of the table | 3 B per-image parts | the loss]
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&scratch), (n_tab + 3 * (size_t)B + 1) * sizeof(float)));
+    float *part = scratch + n_tab, *loss = part + 3 * (size_t)B;
+    std::vector<float> host(3 * (size_t)B + 1);
+    int rc = 0;
+    hipError_t e = hipMemcpy(scratch, c_host, n_tab * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = launch_lv_loss(model_out, x_start, noise, x_t, scratch, vb_loss_weight, clip_denoised, dout, part, part + B,
+                            part + 2 * B, loss, B, per, loss_scale, s);
+        e = hipStreamSynchronize(s);
+    }
+    if (!rc && e == hipSuccess) e = hipMemcpy(host.data(), part, host.size() * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(scratch);
+    if (!rc && e != hipSuccess) {
+        set_error(std::string("dm_op_lv_loss: ") + hipGetErrorString(e));
+        rc = 1;
+    }
+    if (rc) return rc;
+    *loss_out_host = host[3 * (size_t)B];
+    if (mse_part_out_host) std::memcpy(mse_part_out_host, host.data() + B, B * sizeof(float));
+    if (vb_part_out_host) std::memcpy(vb_part_out_host, host.data() + 2 * B, B * sizeof(float));
+    return 0;
+}
+
+}  // extern "C"

@@ -893,7 +893,7 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     float* dfr = A.alloc((size_t)B * h * w * u->init_dim);
     {
         const ConvLayer& L = u->final_conv;
-        DM_REQUIRE(L.wraw != nullptr, "training: final_conv must be the thin pointwise layer (out_dim <= 4)");
+        DM_REQUIRE(L.wraw != nullptr, "training: final_conv must be the thin pointwise layer (out_dim <= 8)");
         static const bool no_fuse = env_flag("DM_TRAIN_NO_FINAL_FUSE");
         if (!no_fuse && thin_out_bwd_ok(L.Cout, h * w)) {  // dw, db and dx in one pass over the block's output
             float* ws = A.alloc(thin_out_bwd_ws_floats(B, h, w, L.Cout, L.C0));
@@ -1548,6 +1548,21 @@ int dm_unet_get_grad(dm_unet* u, const char* name, float* out_dev, void* stream)
     return 0;
 }
 
+// the per-image device rows of an integer-time call (coefficients, timesteps, text mask) hold B images
+static int grow_train_rows(TrainState& T, int B) {
+    if (B <= T.cap_B) return 0;
+    DM_CHECK_HIP(hipDeviceSynchronize());
+    if (T.coef_dev) (void)hipFree(T.coef_dev);
+    if (T.t_dev) (void)hipFree(T.t_dev);
+    if (T.mask_dev) (void)hipFree(T.mask_dev);
+    T.coef_dev = nullptr; T.t_dev = nullptr; T.mask_dev = nullptr; T.cap_B = 0;
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.coef_dev), (size_t)B * DM_TRAIN_COEFS * sizeof(float)));
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.t_dev), (size_t)B * sizeof(int64_t)));
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.mask_dev), (size_t)B * sizeof(int32_t)));
+    T.cap_B = B;
+    return 0;
+}
+
 static int loss_backward_impl(dm_unet* u, const dm_train_args& a, const int32_t* text_mask = nullptr) {
     const float *x_start = a.x_start, *coef_host = a.coef_host, *noise = a.noise, *noise_q = a.noise_q, *cond = a.cond,
                 *ctx = a.ctx;
@@ -1564,6 +1579,8 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a, const int32_t*
     DM_REQUIRE(!u->train->ft, "the handle is armed for float-time training (dm_unet_train_enable_ft): an integer timestep would "
                               "truncate c_noise(sigma) -- use dm_unet_loss_backward_edm");
     DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
+    DM_REQUIRE(u->out_dim != 2 * u->cfg.channels, "the U-Net predicts a learned variance (out_dim == 2 * channels): its loss is "
+                                                  "dm_unet_loss_backward_lv");
     DM_REQUIRE(B > 0 && objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "bad argument");
     DM_REQUIRE(terms >= 1 && terms <= 3 && cstride >= 8 && cstride <= DM_TRAIN_COEFS && (!(terms & 2) || cstride == DM_TRAIN_COEFS),
                "loss_terms is 1 (MSE), 2 (KL) or 3 (both); the KL term needs coef rows of 12 floats");
@@ -1578,17 +1595,7 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a, const int32_t*
     DM_CHECK_HIP(hipSetDevice(u->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     TrainState& T = *u->train;
-    if (B > T.cap_B) {
-        DM_CHECK_HIP(hipDeviceSynchronize());
-        if (T.coef_dev) (void)hipFree(T.coef_dev);
-        if (T.t_dev) (void)hipFree(T.t_dev);
-        if (T.mask_dev) (void)hipFree(T.mask_dev);
-        T.coef_dev = nullptr; T.t_dev = nullptr; T.mask_dev = nullptr; T.cap_B = 0;
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.coef_dev), (size_t)B * DM_TRAIN_COEFS * sizeof(float)));
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.t_dev), (size_t)B * sizeof(int64_t)));
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.mask_dev), (size_t)B * sizeof(int32_t)));
-        T.cap_B = B;
-    }
+    if (grow_train_rows(T, B)) return 1;
     const int C = u->cfg.channels;
     const int per = C * H * W;
     const size_t n = (size_t)B * per;

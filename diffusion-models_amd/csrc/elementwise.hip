@@ -471,7 +471,8 @@ int launch_add(const float* a, const float* b, float* y, int64_t n, hipStream_t 
 // ---------------------------------------------------------------------------------------
 // 1x1 convolution to a few output channels, NHWC in -> NCHW out (final_conv, DD/denoising_diffusion.py:319: 64 -> 3).
 // One pixel per thread: the MFMA tile would spend 61 of 64 columns on padding; this is a 256-byte read and three
-// coalesced dword stores per pixel, HBM bound.  Weights (Cout x C) and bias sit in LDS.
+// coalesced dword stores per pixel, HBM bound.  Weights (Cout x C) and bias sit in LDS.  1 to 8 outputs: 5 to 8 are the
+// learned-variance models (out_dim = 2 * channels).
 // ---------------------------------------------------------------------------------------
 template <int COUT>
 __global__ __launch_bounds__(256) void pointwise_small_kernel(const float* __restrict__ x, const float* __restrict__ w,
@@ -500,14 +501,19 @@ __global__ __launch_bounds__(256) void pointwise_small_kernel(const float* __res
 }
 int launch_pointwise_small(const float* x, const float* w_oc, const float* bias, float* y_nchw, int64_t pixels, int C,
                            int Cout, int HW, hipStream_t s) {
-    DM_REQUIRE(Cout >= 1 && Cout <= 4 && C % 4 == 0, "pointwise_small: 1..4 output channels, C % 4 == 0");
+    DM_REQUIRE(Cout >= 1 && Cout <= 8 && C % 4 == 0, "pointwise_small: 1..8 output channels, C % 4 == 0");
     const dim3 grid((pixels + 255) / 256), block(256);
     const size_t lds = (size_t)Cout * C * sizeof(float);
     switch (Cout) {
         case 1: hipLaunchKernelGGL(pointwise_small_kernel<1>, grid, block, lds, s, x, w_oc, bias, y_nchw, pixels, C, HW); break;
         case 2: hipLaunchKernelGGL(pointwise_small_kernel<2>, grid, block, lds, s, x, w_oc, bias, y_nchw, pixels, C, HW); break;
         case 3: hipLaunchKernelGGL(pointwise_small_kernel<3>, grid, block, lds, s, x, w_oc, bias, y_nchw, pixels, C, HW); break;
-        default: hipLaunchKernelGGL(pointwise_small_kernel<4>, grid, block, lds, s, x, w_oc, bias, y_nchw, pixels, C, HW); break;
+        case 4: hipLaunchKernelGGL(pointwise_small_kernel<4>, grid, block, lds, s, x, w_oc, bias, y_nchw, pixels, C, HW); break;
+        // 5..8: the learned-variance models (out_dim = 2 * channels, DD/learned_gaussian_diffusion.py:70)
+        case 5: hipLaunchKernelGGL(pointwise_small_kernel<5>, grid, block, lds, s, x, w_oc, bias, y_nchw, pixels, C, HW); break;
+        case 6: hipLaunchKernelGGL(pointwise_small_kernel<6>, grid, block, lds, s, x, w_oc, bias, y_nchw, pixels, C, HW); break;
+        case 7: hipLaunchKernelGGL(pointwise_small_kernel<7>, grid, block, lds, s, x, w_oc, bias, y_nchw, pixels, C, HW); break;
+        default: hipLaunchKernelGGL(pointwise_small_kernel<8>, grid, block, lds, s, x, w_oc, bias, y_nchw, pixels, C, HW); break;
     }
     DM_CHECK_HIP(hipGetLastError());
     return 0;

@@ -835,23 +835,27 @@ static int wgrad_init_mfma_ntw(int Cin, int W) {
 }
 
 // final_conv (:343): 1x1 with a handful of outputs, x NHWC, dy NCHW.  256 threads = 64 input channels x 4 pixel lanes.
+// OB bounds the outputs: 4 (every model whose out_dim is channels) or 8 (learned variance, out_dim = 2 * channels).
+template <int OB>
 __global__ __launch_bounds__(256) void wgrad_thin_out_kernel(const WgradNaive p) {
-    __shared__ float red[4][4][64];
+    __shared__ float red[OB][4][64];
     const int li = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + li;
     const int64_t HW = (int64_t)p.H * p.W;
     const int64_t px0 = (int64_t)blockIdx.y * p.rows_per_split * p.W, px1 = min(px0 + (int64_t)p.rows_per_split * p.W, p.B * HW);
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    float acc[OB];
+#pragma unroll
+    for (int o = 0; o < OB; ++o) acc[o] = 0.f;
     if (c < p.Cin)
         for (int64_t px = px0 + q; px < px1; px += 4) {
             const float xv = p.x[px * p.Cin + c];
             const int64_t b = px / HW, r = px - b * HW;
 #pragma unroll
-            for (int o = 0; o < 4; ++o)
+            for (int o = 0; o < OB; ++o)
                 if (o < p.Cout) acc[o] += xv * p.dy[(b * p.Cout + o) * HW + r];
         }
 #pragma unroll
-    for (int o = 0; o < 4; ++o) red[o][q][li] = acc[o];
+    for (int o = 0; o < OB; ++o) red[o][q][li] = acc[o];
     __syncthreads();
     if (q == 0 && c < p.Cin)
         for (int o = 0; o < p.Cout; ++o)
@@ -860,32 +864,39 @@ __global__ __launch_bounds__(256) void wgrad_thin_out_kernel(const WgradNaive p)
 }
 
 // final_conv (:343) backward in one pass over its input: weight gradient, bias gradient and input gradient of a 1x1 convolution
-// with at most 4 outputs, x NHWC, dy NCHW (the loss gradient).  256 threads = 64 input channels x 4 pixel lanes; a thread keeps 16
-// pixels in flight (x and the Cout dy values of each), and the pixel's dx row -- sum_o w[o][c] dy[o][px] -- leaves with the same
+// with at most OB outputs, x NHWC, dy NCHW (the loss gradient).  256 threads = 64 input channels x 4 pixel lanes; a thread keeps NP
+// pixels in flight (x and the OB dy values of each), and the pixel's dx row -- sum_o w[o][c] dy[o][px] -- leaves with the same
 // registers.  Split partials: [split][Cout * Cin] then [split][Cout] (bias), summed by the reduce jobs in split order.
+// <4, 16>: every model whose out_dim is channels.  <8, 8>: learned variance (out_dim = 2 * channels, 5 to 8 outputs) -- dv alone
+// would be 128 registers at 16 pixels, so it keeps 8 in flight.
 struct ThinOutBwd {
     const float *x, *dy, *w;  // x (B, H, W, Cin), dy (B, Cout, H, W), w (Cout, Cin)
     float *dx, *part_w, *part_b;
     int Cin, Cout, HW, px_per_split;
     long long pixels;
 };
+template <int OB, int NP_>
 __global__ __launch_bounds__(256) void thin_out_bwd_kernel(const ThinOutBwd p) {
-    __shared__ float red[4][4][64];
-    __shared__ float redb[4][4];
+    __shared__ float red[OB][4][64];
+    __shared__ float redb[OB][4];
     const int li = threadIdx.x & 63, q = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + li;
     const bool cok = c < p.Cin;
     const long long px0 = (long long)blockIdx.y * p.px_per_split, px1 = min(px0 + (long long)p.px_per_split, p.pixels);
-    float wv[4], acc[4] = {0.f, 0.f, 0.f, 0.f}, bs[4] = {0.f, 0.f, 0.f, 0.f};
+    float wv[OB], acc[OB], bs[OB];
 #pragma unroll
-    for (int o = 0; o < 4; ++o) wv[o] = (cok && o < p.Cout) ? p.w[o * p.Cin + c] : 0.f;
+    for (int o = 0; o < OB; ++o) {
+        wv[o] = (cok && o < p.Cout) ? p.w[o * p.Cin + c] : 0.f;
+        acc[o] = 0.f;
+        bs[o] = 0.f;
+    }
     long long px = px0 + q;
     long long b = px / p.HW;
     int r = (int)(px - b * p.HW);
     const int cc = cok ? c : 0;
     while (px < px1) {  // branch-free body: clamped addresses, masked values (HW >= 4: one wrap per step at most)
-        constexpr int NP = 16;  // pixels in flight per thread
-        float xv[NP], dv[NP][4];
+        constexpr int NP = NP_;  // pixels in flight per thread
+        float xv[NP], dv[NP][OB];
         long long pxs[NP];
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
@@ -896,7 +907,7 @@ __global__ __launch_bounds__(256) void thin_out_bwd_kernel(const ThinOutBwd p) {
             pxs[k] = ok ? px : -1;
             xv[k] = p.x[pc * p.Cin + cc];
 #pragma unroll
-            for (int o = 0; o < 4; ++o) dv[k][o] = p.dy[(bc * p.Cout + min(o, p.Cout - 1)) * p.HW + rc];
+            for (int o = 0; o < OB; ++o) dv[k][o] = p.dy[(bc * p.Cout + min(o, p.Cout - 1)) * p.HW + rc];
             px += 4;
             r += 4;
             const bool wrap = r >= p.HW;
@@ -908,7 +919,7 @@ __global__ __launch_bounds__(256) void thin_out_bwd_kernel(const ThinOutBwd p) {
             const float m = pxs[k] >= 0 ? 1.f : 0.f;
             float d = 0.f;
 #pragma unroll
-            for (int o = 0; o < 4; ++o) {
+            for (int o = 0; o < OB; ++o) {
                 const float dvm = dv[k][o] * m;
                 acc[o] += xv[k] * dvm;
                 bs[o] += dvm;
@@ -918,10 +929,10 @@ __global__ __launch_bounds__(256) void thin_out_bwd_kernel(const ThinOutBwd p) {
         }
     }
 #pragma unroll
-    for (int o = 0; o < 4; ++o) red[o][q][li] = acc[o];
+    for (int o = 0; o < OB; ++o) red[o][q][li] = acc[o];
     if (li == 0)
 #pragma unroll
-        for (int o = 0; o < 4; ++o) redb[o][q] = bs[o];
+        for (int o = 0; o < OB; ++o) redb[o][q] = bs[o];
     __syncthreads();
     if (q == 0 && cok)
         for (int o = 0; o < p.Cout; ++o)
@@ -936,12 +947,12 @@ static int thin_out_bwd_splits(long long pixels) { return (int)std::min<long lon
 size_t thin_out_bwd_ws_floats(int B, int H, int W, int Cout, int Cin) {
     return (size_t)thin_out_bwd_splits((long long)B * H * W) * ((size_t)Cout * Cin + Cout);
 }
-bool thin_out_bwd_ok(int Cout, int HW) { return Cout >= 1 && Cout <= 4 && HW >= 4; }
+bool thin_out_bwd_ok(int Cout, int HW) { return Cout >= 1 && Cout <= 8 && HW >= 4; }
 // defer_w / defer_b: both set (the training step's grouped split sums) or both null (summed here)
 int launch_thin_out_bwd(const float* x, const float* dy_nchw, const float* w_oc, float* dx, float* ws, float* dw, float* db,
                         int B, int H, int W, int Cin, int Cout, int accumulate, hipStream_t s, WgradJob* defer_w,
                         WgradJob* defer_b) {
-    DM_REQUIRE(thin_out_bwd_ok(Cout, H * W), "thin_out_bwd: 1 to 4 outputs");
+    DM_REQUIRE(thin_out_bwd_ok(Cout, H * W), "thin_out_bwd: 1 to 8 outputs");
     ThinOutBwd p{};
     p.pixels = (long long)B * H * W;
     const int splits0 = thin_out_bwd_splits(p.pixels);
@@ -950,7 +961,8 @@ int launch_thin_out_bwd(const float* x, const float* dy_nchw, const float* w_oc,
     p.x = x; p.dy = dy_nchw; p.w = w_oc; p.dx = dx;
     p.part_w = ws; p.part_b = ws + (size_t)splits * Cout * Cin;
     p.Cin = Cin; p.Cout = Cout; p.HW = H * W;
-    hipLaunchKernelGGL(thin_out_bwd_kernel, dim3((Cin + 63) / 64, splits), dim3(256), 0, s, p);
+    if (Cout <= 4) hipLaunchKernelGGL((thin_out_bwd_kernel<4, 16>), dim3((Cin + 63) / 64, splits), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((thin_out_bwd_kernel<8, 8>), dim3((Cin + 63) / 64, splits), dim3(256), 0, s, p);
     DM_CHECK_HIP(hipGetLastError());
     const WgradJob jw{p.part_w, dw, (long long)Cout * Cin, splits, 1, accumulate, 0};
     const WgradJob jb{p.part_b, db, (long long)Cout, splits, 1, accumulate, 0};
@@ -1003,7 +1015,9 @@ int launch_wgrad_naive(const float* x, int x_nchw, const float* dy, int dy_nchw,
         hipLaunchKernelGGL((wgrad_init_kernel<7, 7>), dim3(Cin, splits, (Cout + 63) / 64), dim3(64), 7 * (W + 6) * sizeof(float), s,
                            p);
     else if (!x_nchw && dy_nchw && KH == 1 && KW == 1 && Cout <= 4)
-        hipLaunchKernelGGL(wgrad_thin_out_kernel, dim3((Cin + 63) / 64, splits), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(wgrad_thin_out_kernel<4>, dim3((Cin + 63) / 64, splits), dim3(256), 0, s, p);
+    else if (!x_nchw && dy_nchw && KH == 1 && KW == 1 && Cout <= 8)
+        hipLaunchKernelGGL(wgrad_thin_out_kernel<8>, dim3((Cin + 63) / 64, splits), dim3(256), 0, s, p);
     else
         hipLaunchKernelGGL(wgrad_naive_kernel, dim3((n_out + 127) / 128, splits), dim3(128), 0, s, p);
     DM_CHECK_HIP(hipGetLastError());

@@ -102,7 +102,7 @@ class EMA:
         if self._ema_model is None:
             online, attr = _unet_of(d)
             cfg = online.cfg
-            unet = Unet(dim=cfg.dim, init_dim=cfg.init_dim, out_dim=cfg.out_dim, dim_mults=cfg.dim_mults, channels=cfg.channels,
+            unet = Unet(dim=cfg.dim, init_dim=cfg.init_dim, out_dim=cfg.out_dim_, dim_mults=cfg.dim_mults, channels=cfg.channels,
                         self_condition=cfg.self_condition, sinusoidal_pos_emb_theta=cfg.sinusoidal_pos_emb_theta,
                         attn_dim_head=cfg.attn_dim_head, attn_heads=cfg.attn_heads, full_attn=cfg.full_attn,
                         text_condition=cfg.text_condition, text_emb_dim=cfg.text_emb_dim, use_cross_attn=cfg.use_cross_attn,

@@ -827,6 +827,94 @@ int dm_op_repaint_step(int mode, int objective, const float* x, const float* eps
                        int unnormalize, uint64_t seed, uint64_t row, uint64_t element_offset, float* out, float* x_start_out,
                        int B, int C, int HW, void* stream);
 
+/* ---- LearnedGaussianDiffusion (Improved DDPM, arXiv 2102.09672, as DD/learned_gaussian_diffusion.py:61-146 has it): the
+ * U-Net predicts 2 * channels maps per image (out_dim == 2 * channels, :70) -- the noise, then a per-pixel weight v that
+ * interpolates between the two extreme posterior log-variances.  The handle has no text conditioning, an integer time and
+ * input channels == channels (no self-conditioning, :71).
+ *
+ * Sampling (the base class's p_sample_loop, DD/denoising_diffusion.py:647-664, over p_mean_variance :93-111).  The HOST
+ * gathers every per-step scalar in fp32 as `extract` does; row i is DM_LV_COEFS floats at the step's time t_i:
+ *   c[0]=sqrt_recip_alphas_cumprod   c[1]=sqrt_recipm1_alphas_cumprod   c[2]=posterior_mean_coef1   c[3]=posterior_mean_coef2
+ *   c[4]=min_log=posterior_log_variance_clipped   c[5]=1 if t_i > 0 else 0   c[6]=max_log=log(betas);  the rest 0.
+ * Step i runs (eps | v) = Unet(x, t_i) and one elementwise pass:
+ *   logvar = (v + 1) / 2 * c[6] + (1 - (v + 1) / 2) * c[4];   x_start = clamp(c[0] x - c[1] eps, -1, 1)
+ *   x <- c[2] x_start + c[3] x + exp(0.5 logvar) * z          (z = 0 where c[5] == 0)
+ * The first half is read as noise whatever the object's `objective` says, as in the reference.
+ *   times_host  n_steps int64 times;  table_host  n_steps x DM_LV_COEFS floats
+ *   x_T         (B,C,H,W) N(0,1) start image (device)
+ *   noise       NULL -> device Philox noise under `seed` (draw 0 is x_T, the caller's; step i draws i + 1; counters are
+ *               global element indices as in dm_sample_ex: sample_offset).  Else (n_steps, B,C,H,W), row i read by step i
+ *               when its c[5] != 0.
+ *   out         the result, (x + 1) / 2 when unnormalize != 0 (written by the last step's pass)
+ *   all_steps   NULL or (n_steps + 1, B,C,H,W): frame 0 = x_T, frame i + 1 = x after step i (never unnormalised)
+ *   use_graph   one step is captured as a hipGraph, cached on the handle per (B, H, W, noise and all_steps pointers) in
+ *               the slot dm_sample uses, under a kind of its own; seed, offset, tables, step count and unnormalize are
+ *               device data and do not re-capture. */
+#define DM_LV_COEFS 16
+typedef struct dm_lv_args {
+    int32_t n_steps;
+    const int64_t* times_host;
+    const float* table_host;
+    const float* x_T;
+    const float* noise;
+    uint64_t seed;
+    uint64_t sample_offset;
+    float* out;
+    float* all_steps;
+    int32_t B, H, W;
+    int32_t unnormalize;
+    int32_t use_graph;
+    void* stream;
+} dm_lv_args;
+int dm_sample_lv(dm_unet* u, const dm_lv_args* args);
+
+/* One p_losses (:113-146) and its backward pass on a handle armed by dm_unet_train_enable (which accepts
+ * out_dim == 2 * channels; dm_unet_loss_backward* refuse such a handle and name this call):
+ *   x_t = c[0] x_start + c[1] noise;  (pred | v) = Unet(x_t, t_b);  logvar as above from c[6] (min_log), c[8] (max_log);
+ *   model_mean = c[4] x0 + c[5] x_t, x0 = c[2] x_t - c[3] pred [clamped when clip_denoised];  true_mean = c[4] x_start + c[5] x_t
+ *   vb_b = meanflat(c[9] ? -discretized_gaussian_log_likelihood(x_start, model_mean, 0.5 logvar)
+ *                        : normal_kl(true_mean, c[7], model_mean, logvar)) / ln 2           (an image runs its own branch only)
+ *   loss = loss_scale * (mean((pred - noise)^2) + vb_loss_weight * mean_b(vb_b));  every parameter gradient.
+ * The model mean is detached (:128): the vb term's gradient reaches only the variance half of the output, the MSE's only
+ * the noise half.  coef_host: B rows of coef_stride floats (0: DM_LV_TRAIN_COEFS; 10 to 12):
+ *   c[0]=sqrt_alphas_cumprod[t_b]  c[1]=sqrt_one_minus_alphas_cumprod[t_b]  c[2]=sqrt_recip_alphas_cumprod[t_b]
+ *   c[3]=sqrt_recipm1_alphas_cumprod[t_b]  c[4]=posterior_mean_coef1[t_b]  c[5]=posterior_mean_coef2[t_b]
+ *   c[6]=c[7]=posterior_log_variance_clipped[t_b] (min_log; the true log variance)  c[8]=log(betas)[t_b]  c[9]=1 if t_b == 0
+ * loss_scale, accumulate, loss_out_host (NULL: the loss stays on the device, dm_unet_train_scalar) as in
+ * dm_unet_loss_backward_ex; model_out (optional, device) receives the (B, 2C, H, W) model output. */
+#define DM_LV_TRAIN_COEFS 12
+typedef struct dm_lv_train_args {
+    const float* x_start;
+    const int64_t* t_host;
+    const float* coef_host;
+    int32_t coef_stride;
+    const float* noise;
+    float vb_loss_weight;
+    int32_t clip_denoised;
+    float loss_scale;
+    int32_t accumulate;
+    float* loss_out_host;
+    float* model_out;
+    int32_t B, H, W;
+    void* stream;
+} dm_lv_train_args;
+int dm_unet_loss_backward_lv(dm_unet* u, const dm_lv_train_args* args);
+
+/* The two kernels on their own (tests, p_sample, p_mean_variance).  Tensors are on the device, B * per floats (model_out and
+ * dout 2 * B * per: image b's noise half, then its variance half), per % 4 == 0, 16-byte aligned; tables are on the host;
+ * each call waits for its result.
+ *   step:  one row of DM_LV_COEFS floats.  z NULL: Philox draw `draw` (>= 1) under `seed`, counters from element_offset;
+ *          a row with c[5] == 0 reads neither.  out may be x.  mean_out, logvar_out, x_start_out (optional) are
+ *          p_mean_variance's model_mean, model_log_variance and clamped x_start.
+ *   loss:  B rows of DM_LV_TRAIN_COEFS floats.  *loss_out_host = the loss above; mse_part_out_host / vb_part_out_host
+ *          (optional, B floats on the host) = mean((pred_b - noise_b)^2) and vb_b;  dout = d loss / d model_out. */
+int dm_op_lv_step(const float* x, const float* model_out, const float* z, const float* c_host, uint64_t seed, uint64_t draw,
+                  uint64_t element_offset, float* out, float* mean_out, float* logvar_out, float* x_start_out, int B,
+                  int64_t per, void* stream);
+int dm_op_lv_loss(const float* model_out, const float* x_start, const float* noise, const float* x_t, const float* c_host,
+                  float vb_loss_weight, int clip_denoised, float loss_scale, float* dout, float* loss_out_host,
+                  float* mse_part_out_host, float* vb_part_out_host, int B, int64_t per, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
