@@ -29,6 +29,7 @@ from .continuous import (ContinuousTimeGaussianDiffusion, VParamContinuousTimeGa
                          alpha_cosine_log_snr, beta_linear_log_snr, ct_step_table, ct_train_table)
 from .repaint import GaussianDiffusion as RePaintGaussianDiffusion, RepaintTable, repaint_step_table  # noqa: F401
 from .learned import LearnedGaussianDiffusion, lv_step_table, lv_train_table  # noqa: F401
+from .classifier_guidance import ClassifierGuidedGaussianDiffusion, cg_step_table  # noqa: F401
 from .vae import VQDecoder, VQEncoder, VQModel  # noqa: F401
 from .dist import gather_shards, sample_global, sample_sharded, shard_bounds, shared_seed  # noqa: F401
 from .checkpoint import load_trainer_checkpoint, load_vae_checkpoint  # noqa: F401
@@ -49,6 +50,7 @@ __all__ = [
     "VParamContinuousTimeGaussianDiffusion",
     "RePaintGaussianDiffusion",
     "LearnedGaussianDiffusion",
+    "ClassifierGuidedGaussianDiffusion",
     "VQDecoder",
     "VQEncoder",
     "VQModel",

@@ -8,6 +8,7 @@
 #include "ct.h"
 #include "repaint.h"
 #include "learned.h"
+#include "cguide.h"
 
 #include <array>
 #include <cmath>
@@ -318,7 +319,7 @@ struct dm_unet {
     std::vector<std::pair<std::string, ResBlock*>> resnets;  // in ss_off order
     // the instantiated graph of one denoise step, reused while the key (shape, kind, every captured pointer) holds.  The
     // slot serves every sampling loop of the handle (dm_sampler.inc: run_steps); the kind says whose graph it holds.
-    enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT, GK_LV };
+    enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT, GK_LV, GK_CG };
     struct GraphKey {
         int kind = GK_NONE, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
         int edm_clamp = 0;      // ElucidatedDiffusion: the clamp flag, a kernel argument of the captured Heun step
@@ -326,12 +327,13 @@ struct dm_unet {
         int mask_channels = 0;  // RePaint: 1 or C
         const void *noise = nullptr, *all_steps = nullptr, *ws = nullptr, *times = nullptr, *coefs = nullptr;
         const void* tab = nullptr;  // the 16-float-row table (edm_tab_dev) of the EDM, continuous-time and RePaint steps
+        const void *cg_mean = nullptr, *cg_grad = nullptr;  // classifier guidance: the caller's tensors the two halves touch
         bool operator==(const GraphKey& o) const {
             return kind == o.kind && B == o.B && H == o.H && W == o.W && ctx_tokens == o.ctx_tokens &&
                    cond_channels == o.cond_channels && objective == o.objective && self_cond == o.self_cond &&
                    guided == o.guided && edm_clamp == o.edm_clamp && ct_clip == o.ct_clip && mask_channels == o.mask_channels &&
                    noise == o.noise && all_steps == o.all_steps && ws == o.ws && times == o.times && coefs == o.coefs &&
-                   tab == o.tab;
+                   tab == o.tab && cg_mean == o.cg_mean && cg_grad == o.cg_grad;
         }
     } gkey;
     hipGraph_t graph = nullptr;
@@ -1652,3 +1654,4 @@ int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t eleme
 #include "dm_ct.inc"
 #include "dm_repaint.inc"
 #include "dm_learned.inc"
+#include "dm_cguide.inc"

@@ -144,27 +144,42 @@ static int capture_graph(dm_unet* u, hipStream_t s, const std::function<int(hipS
 // The loop: n times `step`, eagerly or as replays of the handle's graph.  The slot is this loop's while `key` (shape,
 // kind, every pointer and flag that is a kernel argument of the step) holds; otherwise what it held is dropped and the
 // step is captured again.  ElucidatedDiffusion's Heun loop has two steps: `step` where is_full(i), else `last` (graph in
-// edm_last_graph); each is captured when the loop first needs it.
+// edm_last_graph); each is captured when the loop first needs it.  With `between` (classifier guidance) every iteration
+// is `step`, then between(i) on the host, then `last`: the two halves of one step, a graph slot each; a non-zero
+// between(i) ends the loop and nothing more is launched.
 static int run_steps(SamplerRun& r, const dm_unet::GraphKey& key, int n, const std::function<int(hipStream_t)>& step,
-                     const std::function<int(hipStream_t)>& last = nullptr, const std::function<bool(int)>& is_full = nullptr) {
+                     const std::function<int(hipStream_t)>& last = nullptr, const std::function<bool(int)>& is_full = nullptr,
+                     const std::function<int(int)>& between = nullptr) {
     dm_unet* u = r.u;
     if (!r.use_graph) {
-        for (int i = 0; i < n; ++i)
-            if ((!is_full || is_full(i) ? step : last)(r.s)) return 1;
+        for (int i = 0; i < n; ++i) {
+            if (between) {
+                if (step(r.s) || between(i) || last(r.s)) return 1;
+            } else if ((!is_full || is_full(i) ? step : last)(r.s)) {
+                return 1;
+            }
+        }
         return 0;
     }
     if (!(u->gkey == key)) {
         u->drop_graph();
         u->gkey = key;
     }
-    for (int i = 0; i < n; ++i) {
-        const bool full = !is_full || is_full(i);
+    auto replay = [&](bool full) -> int {
         hipGraphExec_t* e = full ? &u->gexec : &u->edm_last_gexec;
         if (!*e && capture_graph(u, r.s, full ? step : last, full ? &u->graph : &u->edm_last_graph, e)) {
             u->drop_graph();
             return 1;
         }
         DM_CHECK_HIP(hipGraphLaunch(*e, r.s));
+        return 0;
+    };
+    for (int i = 0; i < n; ++i) {
+        if (between) {
+            if (replay(true) || between(i) || replay(false)) return 1;
+        } else if (replay(!is_full || is_full(i))) {
+            return 1;
+        }
     }
     return 0;
 }

@@ -915,6 +915,69 @@ int dm_op_lv_loss(const float* model_out, const float* x_start, const float* noi
                   float vb_loss_weight, int clip_denoised, float loss_scale, float* dout, float* loss_out_host,
                   float* mse_part_out_host, float* vb_part_out_host, int B, int64_t per, void* stream);
 
+/* ---- Classifier-guided DDPM sampling (Sohl-Dickstein et al. 2015; Dhariwal & Nichol 2021; as DD/guided_diffusion.py:553-603
+ * has it): after the U-Net has produced the posterior mean, the caller's cond_fn returns grad log p(y | x) AT THAT MEAN, the
+ * mean is shifted by posterior_variance[t] * gradient, and the noise is added after that.  The handle has no text
+ * conditioning, no image condition, an integer time and out_dim == channels; self-conditioning and the three objectives
+ * are served.  Text, image condition and classifier-free guidance are refused with a message.
+ *
+ * The HOST gathers every per-step scalar; row i is DM_CG_COEFS floats: columns 0..7 are the DDPM row of dm_sample as it is
+ * (c[4] = exp(0.5 posterior_log_variance_clipped), c[5] = 1 if t_i > 0 else 0), c[8] = posterior_variance[t_i] (unclipped:
+ * 0 at t == 0, where the gradient has no effect), the rest 0.  Step i is two device halves with the host in between:
+ *   front  [self-conditioning input]  model_out = Unet(x, t_i [, x_start]);  x_start = clamp(x_0 by objective, -1, 1);
+ *          mean = c[2] x_start + c[3] x                                             (cg_mean_kernel writes `mean`)
+ *   host   the run's stream is synchronised, then cond_cb(user, i, t_i) is called on the calling thread.  It reads `mean`,
+ *          writes `grad`, and returns 0 only when `grad` is complete on the device (it synchronises whatever stream it used).
+ *          A non-zero return ends the loop: the call fails with a message and launches nothing more; the handle stays usable.
+ *   back   x <- (mean + c[8] grad) + c[4] z   (z = 0 where c[5] == 0)                (cg_finish_kernel)
+ * The x_start that self-conditioning feeds to the next step is the unguided one.  With a zero gradient the result equals
+ * dm_sample's DDPM loop bit for bit (same Philox draws: step i draws i + 1).
+ *   objective, self_condition   as in dm_sample_args
+ *   times_host  n_steps int64 times;  table_host  n_steps x DM_CG_COEFS floats
+ *   x_T, noise, seed, sample_offset, out, all_steps, unnormalize   as in dm_lv_args
+ *   mean, grad  caller-owned (B,C,H,W) device tensors, 16-byte aligned, distinct; they live until the call returns
+ *   cond_cb     the callback above;  user  passed through to it
+ *   stream      the stream of the call; with use_graph and the legacy default stream (NULL) the call runs on a stream of the
+ *               handle, as dm_sample does.  Either way `mean` is complete when cond_cb is entered.
+ *   use_graph   the two halves are captured once each into the handle's two graph slots, cached per (B, H, W, objective,
+ *               self_condition, mean, grad, noise and all_steps pointers) under a kind of their own; seed, offset, tables,
+ *               step count and unnormalize are device data and do not re-capture. */
+#define DM_CG_COEFS 16
+typedef struct dm_cguide_args {
+    int32_t objective;
+    int32_t self_condition;
+    int32_t n_steps;
+    int32_t reserved_;
+    const int64_t* times_host;
+    const float* table_host;
+    const float* x_T;
+    const float* noise;
+    uint64_t seed;
+    uint64_t sample_offset;
+    float* mean;
+    float* grad;
+    int (*cond_cb)(void* user, int step, int64_t t);
+    void* user;
+    float* out;
+    float* all_steps;
+    int32_t B, H, W;
+    int32_t unnormalize;
+    int32_t use_graph;
+    int32_t reserved2_;
+    void* stream;
+} dm_cguide_args;
+int dm_sample_classifier_guided(dm_unet* u, const dm_cguide_args* args);
+
+/* The two kernels on their own (tests, p_sample, condition_mean).  Tensors are on the device, B * per floats, per % 4 == 0,
+ * 16-byte aligned; c_host is one row of DM_CG_COEFS floats on the host; each call waits for its result.
+ *   mean:    mean = c[2] x_start + c[3] x with x_start as above; x_start_out (optional).  The outputs alias nothing.
+ *   finish:  out = (mean + c[8] grad) + c[4] z.  z NULL: Philox draw `draw` (>= 1) under `seed`, counters from
+ *            element_offset; a row with c[5] == 0 reads neither.  out may be mean.  guided_out (optional) = mean + c[8] grad. */
+int dm_op_cg_mean(const float* x, const float* model_out, const float* c_host, int objective, float* mean, float* x_start_out,
+                  int B, int64_t per, void* stream);
+int dm_op_cg_finish(const float* mean, const float* grad, const float* z, const float* c_host, uint64_t seed, uint64_t draw,
+                    uint64_t element_offset, float* out, float* guided_out, int B, int64_t per, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
