@@ -1644,6 +1644,7 @@ int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t eleme
 }  // extern "C"
 
 // single-operator entry points (dm_op_*) and the VAE decoder share the helpers above
+#include "dm_op_scaffold.inc"
 #include "dm_ops.inc"
 #include "dm_vae.inc"
 #include "dm_consumer.inc"

@@ -110,7 +110,7 @@ int dm_op_cg_mean(const float* x, const float* model_out, const float* c_host, i
                   int B, int64_t per, void* stream) {
     DM_REQUIRE(x && model_out && c_host && mean, "null argument");
     DM_REQUIRE(B > 0 && per > 0, "empty tensor");
-    return edm_op(c_host, 1, stream, [&](const float* cd, hipStream_t s) {
+    return table_op(c_host, 1, stream, [&](const float* cd, hipStream_t s) {
         return launch_cg_mean(x, model_out, cd, nullptr, STEP_ROW_FIRST, per, objective, mean, x_start_out, (int64_t)B * per, s);
     });
 }

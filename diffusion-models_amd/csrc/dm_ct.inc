@@ -78,8 +78,7 @@ static int sample_ct_impl(dm_unet* u, const dm_ct_args* a) {
 }
 
 // p_losses of both classes (+ forward's normalisation) and the backward pass: q_sample with the target, the tape forward
-// with log_snr_b as the float time, the weighted loss with its gradient, the backward pass.  The per-image rows and times
-// use the EDM path's device buffers (the row widths agree).
+// with log_snr_b as the float time, the weighted loss with its gradient, the backward pass (an entry of run_train).
 static int loss_backward_ct_impl(dm_unet* u, const dm_ct_train_args& a) {
     DM_REQUIRE(a.images && a.noise && a.coef_host, "null argument");
     DM_REQUIRE(a.objective == DM_CT_PRED_NOISE || a.objective == DM_CT_PRED_V, "unknown continuous-time objective");
@@ -93,8 +92,9 @@ static int loss_backward_ct_impl(dm_unet* u, const dm_ct_train_args& a) {
     hipStream_t s = static_cast<hipStream_t>(a.stream);
     TrainState& T = *u->train;
     const int64_t per = (int64_t)u->cfg.channels * H * W, n = (int64_t)B * per;
+    DM_REQUIRE(per % 4 == 0, "C * H * W must be a multiple of 4");
     auto run = [&](Arena& A, Tape& tp) -> int {
-        const StepRows rows{T.edm_coef_dev, nullptr, B > 1 ? STEP_ROW_IMAGE : STEP_ROW_FIRST, per};
+        const StepRows rows{T.coef_dev, nullptr, B > 1 ? STEP_ROW_IMAGE : STEP_ROW_FIRST, per};
         float* x = A.alloc(n);
         float* target = A.alloc(n);
         float* F = A.alloc(n);
@@ -102,10 +102,14 @@ static int loss_backward_ct_impl(dm_unet* u, const dm_ct_train_args& a) {
         float* part = A.alloc(B);
         if (!A.dry && launch_ct_noise_in(a.images, a.noise, rows, objective, a.normalize, x, target, n, s)) return 1;
         if (unet_train_forward(u, A, x, nullptr, F, B, H, W, s, tp, nullptr, 0, nullptr, T.tf_dev)) return 1;
-        if (!A.dry && launch_ct_loss(F, target, T.edm_coef_dev, dF, part, T.loss_dev, B, per, a.loss_scale, s)) return 1;
+        if (!A.dry && launch_ct_loss(F, target, T.coef_dev, dF, part, T.loss_dev, B, per, a.loss_scale, s)) return 1;
         return unet_train_backward(u, A, x, dF, B, H, W, s, tp, accumulate);
     };
-    return loss_backward_ft(u, B, H, W, a.coef_host, cstride, CT_LOG_SNR, -2, 0, a.loss_out_host, a.stream, run);
+    TrainRun r;
+    r.entry = TRAIN_CT;
+    r.B = B; r.H = H; r.W = W; r.stream = a.stream; r.loss_out_host = a.loss_out_host;
+    r.coef_host = a.coef_host; r.cstride = cstride; r.width = DM_CT_COEFS; r.tf_col = CT_LOG_SNR;
+    return run_train(u, r, run);
 }
 
 }  // namespace dm
@@ -140,7 +144,7 @@ int dm_op_ct_step(const float* x, const float* F, const float* eps, const float*
 int dm_op_ct_noise_in(const float* images, const float* eps, const float* c_host, int rows, int objective, int normalize,
                       float* x, float* target, int B, int64_t per, void* stream) {
     DM_REQUIRE(images && eps && x && target, "null argument");
-    return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
+    return table_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
         StepRows r;
         if (edm_rows(cd, rows, B, per, &r)) return 1;
         return launch_ct_noise_in(images, eps, r, objective, normalize, x, target, (int64_t)B * per, s);
@@ -150,17 +154,11 @@ int dm_op_ct_noise_in(const float* images, const float* eps, const float* c_host
 int dm_op_ct_loss(const float* F, const float* target, const float* c_host, float loss_scale, float* dF, float* loss_out_host,
                   int B, int64_t per, void* stream) {
     DM_REQUIRE(F && target && dF && loss_out_host && B > 0, "null argument");
-    float* scratch = nullptr;  // [B] per-image partials, then the loss
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&scratch), ((size_t)B + 1) * sizeof(float)));
-    int rc = edm_op(c_host, B, stream, [&](const float* cd, hipStream_t s) {
-        return launch_ct_loss(F, target, cd, dF, scratch, scratch + B, B, per, loss_scale, s);
-    });
-    if (!rc && hipMemcpy(loss_out_host, scratch + B, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error("dm_op_ct_loss: reading the loss back failed");
-        rc = 1;
-    }
-    (void)hipFree(scratch);
-    return rc;
+    // scratch: [B] per-image partials, then the loss
+    return table_op(c_host, B, stream, [&](float* cd, hipStream_t s) {
+        float* part = cd + (size_t)B * DM_CT_COEFS;
+        return launch_ct_loss(F, target, cd, dF, part, part + B, B, per, loss_scale, s);
+    }, DM_CT_COEFS, (size_t)B + 1, {{loss_out_host, (size_t)B, 1}});
 }
 
 }  // extern "C"

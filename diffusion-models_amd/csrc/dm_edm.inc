@@ -1,6 +1,6 @@
-// ElucidatedDiffusion on the C ABI: the float-time forward, the two sampling loops, the float-time training driver (which
-// continuous time shares) with the EDM loss + backward, and the single-pass entry points (dm_op_edm_*).  Included by
-// dm_api.hip after dm_sampler.inc, whose loop scaffolding it runs on; kernels in edm.hip.
+// ElucidatedDiffusion on the C ABI: the float-time forward, the two sampling loops, the EDM loss + backward (an entry of
+// run_train, dm_train.inc) and the single-pass entry points (dm_op_edm_*).  Included by dm_api.hip after dm_sampler.inc,
+// whose loop scaffolding it runs on; kernels in edm.hip.
 
 namespace dm {
 
@@ -99,119 +99,6 @@ static int sample_edm_impl(dm_unet* u, const dm_edm_args* a) {
     return run_finish(r);
 }
 
-// one stand-alone pass: upload `rows` table rows, run fn, wait
-static int edm_op(const float* c_host, int rows, void* stream, const std::function<int(const float*, hipStream_t)>& fn) {
-    DM_REQUIRE(c_host && rows > 0, "null step table");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float* cd = nullptr;
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&cd), (size_t)rows * DM_EDM_COEFS * sizeof(float)));
-    hipError_t e = hipMemcpy(cd, c_host, (size_t)rows * DM_EDM_COEFS * sizeof(float), hipMemcpyHostToDevice);
-    int rc = 0;
-    if (e == hipSuccess) {
-        rc = fn(cd, s);
-        e = hipStreamSynchronize(s);
-    }
-    (void)hipFree(cd);
-    if (!rc && e != hipSuccess) {
-        set_error(std::string("kernel execution failed: ") + hipGetErrorString(e));
-        rc = 1;
-    }
-    return rc;
-}
-// rows == 1: one row for every image; rows == B: row b for image b
-static int edm_rows(const float* tab, int rows, int B, int64_t per, StepRows* out) {
-    DM_REQUIRE(B > 0 && per > 0, "empty tensor");
-    DM_REQUIRE(rows == 1 || rows == B, "the step table has one row, or one row per image");
-    *out = StepRows{tab, nullptr, rows == B && B > 1 ? STEP_ROW_IMAGE : STEP_ROW_FIRST, per};
-    return 0;
-}
-
-// One SamplerState for a stand-alone pass next to its table rows (edm_op): upload, run fn, wait, free.
-static int state_op(const SamplerState& st_host, const float* c_host, int rows, void* stream,
-                    const std::function<int(const SamplerState*, const float*, hipStream_t)>& fn) {
-    SamplerState* st_dev = nullptr;
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&st_dev), sizeof(SamplerState)));
-    hipError_t e = hipMemcpy(st_dev, &st_host, sizeof(st_host), hipMemcpyHostToDevice);
-    int rc = 1;
-    if (e == hipSuccess) rc = edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) { return fn(st_dev, cd, s); });
-    else set_error(std::string("hipMemcpy: ") + hipGetErrorString(e));
-    (void)hipFree(st_dev);
-    return rc;
-}
-// The kernels draw `step + 1`: a state with step = draw - 1 selects the draw (with injected noise: none).
-static SamplerState draw_state(bool injected, uint64_t seed, uint64_t draw, uint64_t element_offset) {
-    SamplerState st{};
-    st.step = injected ? 0 : (int)(draw - 1);
-    st.n_steps = st.step + 1;
-    st.seed = seed;
-    st.off4 = element_offset / 4;
-    return st;
-}
-
-// Loss + backward at a real-valued time on a handle armed by dm_unet_train_enable_ft, for ElucidatedDiffusion and
-// continuous time: the per-image coefficient rows (DM_EDM_COEFS floats on the device, `cstride` on the host) and column
-// `tf_col` of them as the float times the embedding reads, then run(arena, tape) -- the caller's noise-in pass, tape
-// forward, loss with its gradient and backward pass, which goes on through time_mlp.1 into the embedding's weights.
-// run is called twice: on a dry arena to size the workspace (once per key_tag, shape and key_flags), then for real.
-// Workspace, arena and stream ordering follow loss_backward_impl.
-static int loss_backward_ft(dm_unet* u, int B, int H, int W, const float* coef_host, int cstride, int tf_col, long long key_tag,
-                            long long key_flags, float* loss_out_host, void* stream,
-                            const std::function<int(Arena&, Tape&)>& run) {
-    DM_CHECK_HIP(hipSetDevice(u->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    TrainState& T = *u->train;
-    if (B > T.edm_cap_B) {
-        DM_CHECK_HIP(hipDeviceSynchronize());
-        if (T.edm_coef_dev) (void)hipFree(T.edm_coef_dev);
-        if (T.tf_dev) (void)hipFree(T.tf_dev);
-        T.edm_coef_dev = nullptr; T.tf_dev = nullptr; T.edm_cap_B = 0;
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.edm_coef_dev), (size_t)B * DM_EDM_COEFS * sizeof(float)));
-        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.tf_dev), (size_t)B * sizeof(float)));
-        T.edm_cap_B = B;
-    }
-    DM_REQUIRE((int64_t)u->cfg.channels * H * W % 4 == 0, "C * H * W must be a multiple of 4");
-    try {
-        // (the fourth entry is self_cond on the integer-time path, never negative there)
-        const std::array<long long, 8> key{B, H, W, key_tag, 0, 0, 0, key_flags | (T.bucketed ? 2 : 0)};
-        auto known = T.ws_need.find(key);
-        if (known == T.ws_need.end()) {
-            Arena dry;
-            dry.dry = true;
-            Tape tp;
-            if (run(dry, tp)) return 1;
-            known = T.ws_need.emplace(key, dry.off).first;
-        }
-        if (ensure_train_ws(T, known->second)) return 1;
-        if (u->order_after_previous(s)) return 1;
-        // rows as the kernels index them (DM_EDM_COEFS floats), then the B float times the embedding reads
-        T.coef_stage.assign((size_t)B * DM_EDM_COEFS + B, 0.f);
-        const int ncopy = cstride < DM_EDM_COEFS ? cstride : DM_EDM_COEFS;
-        for (int b = 0; b < B; ++b) {
-            std::memcpy(&T.coef_stage[(size_t)b * DM_EDM_COEFS], coef_host + (size_t)b * cstride, ncopy * sizeof(float));
-            T.coef_stage[(size_t)B * DM_EDM_COEFS + b] = coef_host[(size_t)b * cstride + tf_col];
-        }
-        DM_CHECK_HIP(hipMemcpyAsync(T.edm_coef_dev, T.coef_stage.data(), (size_t)B * DM_EDM_COEFS * sizeof(float),
-                                    hipMemcpyHostToDevice, s));
-        DM_CHECK_HIP(hipMemcpyAsync(T.tf_dev, T.coef_stage.data() + (size_t)B * DM_EDM_COEFS, (size_t)B * sizeof(float),
-                                    hipMemcpyHostToDevice, s));
-        Arena A;
-        A.base = T.ws;
-        A.cap = T.ws_cap;
-        Tape tp;
-        if (run(A, tp)) return 1;
-        T.drop_call += 1;
-        DM_REQUIRE(A.off <= T.ws_cap, "training workspace overrun: the dry run and the real run allocated differently");
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return 1;
-    }
-    if (u->mark_done(s)) return 1;
-    if (!loss_out_host) return 0;  // asynchronous form: the loss stays on the device (dm_unet_train_scalar)
-    DM_CHECK_HIP(hipMemcpyAsync(loss_out_host, T.loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
-    DM_CHECK_HIP(hipStreamSynchronize(s));
-    return 0;
-}
-
 static const char* const kEdmTrainUnet =
     "ElucidatedDiffusion needs a U-Net with out_dim == input channels == channels and no text conditioning";
 
@@ -229,8 +116,9 @@ static int loss_backward_edm_impl(dm_unet* u, const dm_edm_train_args& a) {
     hipStream_t s = static_cast<hipStream_t>(a.stream);
     TrainState& T = *u->train;
     const int64_t per = (int64_t)u->cfg.channels * H * W, n = (int64_t)B * per;
+    DM_REQUIRE(per % 4 == 0, "C * H * W must be a multiple of 4");
     auto run = [&](Arena& A, Tape& tp) -> int {
-        const StepRows rows{T.edm_coef_dev, nullptr, B > 1 ? STEP_ROW_IMAGE : STEP_ROW_FIRST, per};
+        const StepRows rows{T.coef_dev, nullptr, B > 1 ? STEP_ROW_IMAGE : STEP_ROW_FIRST, per};
         float* x0 = A.alloc(n);
         float* noised = A.alloc(n);
         float* xin = A.alloc(n);
@@ -239,11 +127,16 @@ static int loss_backward_edm_impl(dm_unet* u, const dm_edm_train_args& a) {
         float* part = A.alloc(B);
         if (!A.dry && launch_edm_noise_in(a.images, a.noise, rows, x0, noised, xin, n, s)) return 1;
         if (unet_train_forward(u, A, xin, nullptr, F, B, H, W, s, tp, nullptr, 0, nullptr, T.tf_dev)) return 1;
-        if (!A.dry && launch_edm_loss(noised, F, x0, T.edm_coef_dev, dF, a.denoised_out, part, T.loss_dev, B, per, a.loss_scale, s))
+        if (!A.dry && launch_edm_loss(noised, F, x0, T.coef_dev, dF, a.denoised_out, part, T.loss_dev, B, per, a.loss_scale, s))
             return 1;
         return unet_train_backward(u, A, xin, dF, B, H, W, s, tp, accumulate);
     };
-    return loss_backward_ft(u, B, H, W, a.coef_host, cstride, EDM_C_NOISE, -1, a.denoised_out ? 1 : 0, a.loss_out_host, a.stream, run);
+    TrainRun r;
+    r.entry = TRAIN_EDM;
+    r.sel = {a.denoised_out ? 1 : 0};
+    r.B = B; r.H = H; r.W = W; r.stream = a.stream; r.loss_out_host = a.loss_out_host;
+    r.coef_host = a.coef_host; r.cstride = cstride; r.width = DM_EDM_COEFS; r.tf_col = EDM_C_NOISE;
+    return run_train(u, r, run);
 }
 
 }  // namespace dm
@@ -293,7 +186,7 @@ int dm_op_edm_churn_in(const float* x, const float* eps, const float* c_host, in
 int dm_op_edm_euler(const float* xhat, const float* F, const float* c_host, int rows, int clamp, float* D_out, float* d_out,
                     float* xnext, float* xin_next, int B, int64_t per, void* stream) {
     DM_REQUIRE(xhat && F, "null argument");
-    return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
+    return table_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
         StepRows r;
         if (edm_rows(cd, rows, B, per, &r)) return 1;
         return launch_edm_euler(xhat, F, r, clamp ? 1 : 0, D_out, d_out, xnext, xin_next, (int64_t)B * per, s);
@@ -303,7 +196,7 @@ int dm_op_edm_euler(const float* xhat, const float* F, const float* c_host, int 
 int dm_op_edm_heun(const float* xhat, const float* d, const float* xnext, const float* F2, const float* c_host, int rows,
                    int clamp, float* out, int B, int64_t per, void* stream) {
     DM_REQUIRE(xhat && d && xnext && F2 && out, "null argument");
-    return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
+    return table_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
         StepRows r;
         if (edm_rows(cd, rows, B, per, &r)) return 1;
         return launch_edm_heun(xhat, d, xnext, F2, r, clamp ? 1 : 0, out, (int64_t)B * per, s);
@@ -313,7 +206,7 @@ int dm_op_edm_heun(const float* xhat, const float* d, const float* xnext, const 
 int dm_op_edm_dpmpp(const float* x, const float* F, float* d_old, const float* c_host, int rows, float* out, int B,
                     int64_t per, void* stream) {
     DM_REQUIRE(x && F && d_old && out, "null argument");
-    return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
+    return table_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
         StepRows r;
         if (edm_rows(cd, rows, B, per, &r)) return 1;
         return launch_edm_dpmpp(x, F, d_old, r, out, (int64_t)B * per, s);
@@ -345,7 +238,7 @@ int dm_unet_loss_backward_edm(dm_unet* u, const dm_edm_train_args* a) {
 int dm_op_edm_noise_in(const float* images, const float* eps, const float* c_host, int rows, float* x0, float* noised,
                        float* xin, int B, int64_t per, void* stream) {
     DM_REQUIRE(images && eps && x0 && noised && xin, "null argument");
-    return edm_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
+    return table_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
         StepRows r;
         if (edm_rows(cd, rows, B, per, &r)) return 1;
         return launch_edm_noise_in(images, eps, r, x0, noised, xin, (int64_t)B * per, s);
@@ -355,17 +248,11 @@ int dm_op_edm_noise_in(const float* images, const float* eps, const float* c_hos
 int dm_op_edm_loss(const float* noised, const float* F, const float* x0, const float* c_host, float loss_scale, float* dF,
                    float* D_out, float* loss_out_host, int B, int64_t per, void* stream) {
     DM_REQUIRE(noised && F && x0 && dF && loss_out_host && B > 0, "null argument");
-    float* scratch = nullptr;  // [B] per-image partials, then the loss
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&scratch), ((size_t)B + 1) * sizeof(float)));
-    int rc = edm_op(c_host, B, stream, [&](const float* cd, hipStream_t s) {
-        return launch_edm_loss(noised, F, x0, cd, dF, D_out, scratch, scratch + B, B, per, loss_scale, s);
-    });
-    if (!rc && hipMemcpy(loss_out_host, scratch + B, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error("dm_op_edm_loss: reading the loss back failed");
-        rc = 1;
-    }
-    (void)hipFree(scratch);
-    return rc;
+    // scratch: [B] per-image partials, then the loss
+    return table_op(c_host, B, stream, [&](float* cd, hipStream_t s) {
+        float* part = cd + (size_t)B * DM_EDM_COEFS;
+        return launch_edm_loss(noised, F, x0, cd, dF, D_out, part, part + B, B, per, loss_scale, s);
+    }, DM_EDM_COEFS, (size_t)B + 1, {{loss_out_host, (size_t)B, 1}});
 }
 
 int dm_op_sinusoid_ft_bwd(const float* de0, const float* e0, float* dw, int B, int half, int learned, int accumulate,

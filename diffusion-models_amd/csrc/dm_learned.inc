@@ -1,13 +1,13 @@
 // LearnedGaussianDiffusion on the C ABI: the sampling loop, the hybrid loss + backward and the single-pass entry points
 // (dm_op_lv_*).  Included by dm_api.hip after dm_train.inc (the tape forward / backward), dm_sampler.inc (the loop
-// scaffolding) and dm_edm.inc (the state helper of the dm_op_* passes); kernels in learned.hip.
+// scaffolding); kernels in learned.hip.
 
 namespace dm {
 
 static_assert(DM_LV_COEFS == LV_NCOLS && DM_LV_COEFS == DM_EDM_COEFS,
               "the learned-variance step table lives in the handle's EDM table buffer: the row widths must agree");
 static_assert(DM_LV_TRAIN_COEFS == LVT_NCOLS && DM_LV_TRAIN_COEFS == DM_TRAIN_COEFS,
-              "the learned-variance training rows live in the training state's coefficient buffer (q_sample reads columns 0, 1)");
+              "q_sample_kernel reads columns 0, 1 of the learned-variance training rows at its own row width");
 
 static int lv_unet_ok(dm_unet* u) {
     DM_REQUIRE(u->cfg.text_mode == DM_TEXT_NONE, "LearnedGaussianDiffusion calls model(x, t) only: no text-conditional U-Net");
@@ -74,9 +74,8 @@ static int sample_lv_impl(dm_unet* u, const dm_lv_args* a) {
     return run_finish(r);
 }
 
-// p_losses (DD/learned_gaussian_diffusion.py:113-146) and the backward pass: the body of loss_backward_impl without
-// self-conditioning, condition image and text -- q_sample, the tape forward into a 2n buffer, the loss with its gradient,
-// the backward pass.
+// p_losses (DD/learned_gaussian_diffusion.py:113-146) and the backward pass, an entry of run_train: q_sample, the tape
+// forward into a 2n buffer, the loss with its gradient, the backward pass.
 static int loss_backward_lv_impl(dm_unet* u, const dm_lv_train_args& a) {
     DM_REQUIRE(a.x_start && a.t_host && a.coef_host && a.noise, "null argument");
     DM_REQUIRE(u->train, "dm_unet_train_enable has not been called");
@@ -87,10 +86,8 @@ static int loss_backward_lv_impl(dm_unet* u, const dm_lv_train_args& a) {
     if (lv_unet_ok(u)) return 1;
     const int B = a.B, H = a.H, W = a.W, accumulate = a.accumulate ? 1 : 0;
     if (check_hw(u, H, W)) return 1;
-    DM_CHECK_HIP(hipSetDevice(u->device));
     hipStream_t s = static_cast<hipStream_t>(a.stream);
     TrainState& T = *u->train;
-    if (grow_train_rows(T, B)) return 1;
     const int64_t per = (int64_t)u->cfg.channels * H * W, n = (int64_t)B * per;
     DM_REQUIRE(per % 4 == 0 && per < (int64_t(1) << 30), "C * H * W must be a multiple of 4");
     auto run = [&](Arena& A, Tape& tp) -> int {
@@ -108,41 +105,13 @@ static int loss_backward_lv_impl(dm_unet* u, const dm_lv_train_args& a) {
         }
         return unet_train_backward(u, A, x, dout, B, H, W, s, tp, accumulate);
     };
-    try {
-        // (the fourth entry is self_cond on the plain path and -1 / -2 on the float-time paths)
-        const std::array<long long, 8> key{B, H, W, -3, 0, 0, 0, (a.model_out ? 1 : 0) | (T.bucketed ? 2 : 0)};
-        auto known = T.ws_need.find(key);
-        if (known == T.ws_need.end()) {
-            Arena dry;
-            dry.dry = true;
-            Tape tp;
-            if (run(dry, tp)) return 1;
-            known = T.ws_need.emplace(key, dry.off).first;
-        }
-        if (ensure_train_ws(T, known->second)) return 1;
-        if (u->order_after_previous(s)) return 1;
-        T.coef_stage.assign((size_t)B * DM_LV_TRAIN_COEFS, 0.f);
-        for (int b = 0; b < B; ++b)
-            std::memcpy(&T.coef_stage[(size_t)b * DM_LV_TRAIN_COEFS], a.coef_host + (size_t)b * cstride, cstride * sizeof(float));
-        DM_CHECK_HIP(hipMemcpyAsync(T.coef_dev, T.coef_stage.data(), (size_t)B * DM_LV_TRAIN_COEFS * sizeof(float),
-                                    hipMemcpyHostToDevice, s));
-        DM_CHECK_HIP(hipMemcpyAsync(T.t_dev, a.t_host, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        Arena A;
-        A.base = T.ws;
-        A.cap = T.ws_cap;
-        Tape tp;
-        if (run(A, tp)) return 1;
-        T.drop_call += 1;
-        DM_REQUIRE(A.off <= T.ws_cap, "training workspace overrun: the dry run and the real run allocated differently");
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return 1;
-    }
-    if (u->mark_done(s)) return 1;
-    if (!a.loss_out_host) return 0;  // asynchronous form: the loss stays on the device (dm_unet_train_scalar)
-    DM_CHECK_HIP(hipMemcpyAsync(a.loss_out_host, T.loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
-    DM_CHECK_HIP(hipStreamSynchronize(s));
-    return 0;
+    TrainRun r;
+    r.entry = TRAIN_LV;
+    r.sel = {a.model_out ? 1 : 0};
+    r.B = B; r.H = H; r.W = W; r.stream = a.stream; r.loss_out_host = a.loss_out_host;
+    r.coef_host = a.coef_host; r.cstride = cstride; r.width = DM_LV_TRAIN_COEFS;
+    r.t_host = a.t_host;
+    return run_train(u, r, run);
 }
 
 }  // namespace dm
@@ -178,30 +147,13 @@ int dm_op_lv_loss(const float* model_out, const float* x_start, const float* noi
                   float vb_loss_weight, int clip_denoised, float loss_scale, float* dout, float* loss_out_host,
                   float* mse_part_out_host, float* vb_part_out_host, int B, int64_t per, void* stream) {
     DM_REQUIRE(model_out && x_start && noise && x_t && c_host && dout && loss_out_host && B > 0, "null argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t n_tab = (size_t)B * LVT_NCOLS;
-    float* scratch = nullptr;  // [B rows of the table | 3 B per-image parts | the loss]
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&scratch), (n_tab + 3 * (size_t)B + 1) * sizeof(float)));
-    float *part = scratch + n_tab, *loss = part + 3 * (size_t)B;
-    std::vector<float> host(3 * (size_t)B + 1);
-    int rc = 0;
-    hipError_t e = hipMemcpy(scratch, c_host, n_tab * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = launch_lv_loss(model_out, x_start, noise, x_t, scratch, vb_loss_weight, clip_denoised, dout, part, part + B,
-                            part + 2 * B, loss, B, per, loss_scale, s);
-        e = hipStreamSynchronize(s);
-    }
-    if (!rc && e == hipSuccess) e = hipMemcpy(host.data(), part, host.size() * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(scratch);
-    if (!rc && e != hipSuccess) {
-        set_error(std::string("dm_op_lv_loss: ") + hipGetErrorString(e));
-        rc = 1;
-    }
-    if (rc) return rc;
-    *loss_out_host = host[3 * (size_t)B];
-    if (mse_part_out_host) std::memcpy(mse_part_out_host, host.data() + B, B * sizeof(float));
-    if (vb_part_out_host) std::memcpy(vb_part_out_host, host.data() + 2 * B, B * sizeof(float));
-    return 0;
+    // scratch: [3 B per-image parts: loss | mse | vb] [the loss]
+    const size_t nb = (size_t)B;
+    return table_op(c_host, B, stream, [&](float* cd, hipStream_t s) {
+        float* part = cd + nb * LVT_NCOLS;
+        return launch_lv_loss(model_out, x_start, noise, x_t, cd, vb_loss_weight, clip_denoised, dout, part, part + B,
+                              part + 2 * B, part + 3 * nb, B, per, loss_scale, s);
+    }, LVT_NCOLS, 3 * nb + 1, {{loss_out_host, 3 * nb, 1}, {mse_part_out_host, nb, nb}, {vb_part_out_host, 2 * nb, nb}});
 }
 
 }  // extern "C"

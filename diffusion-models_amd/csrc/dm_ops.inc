@@ -270,18 +270,9 @@ int dm_op_sampler_update(int kind, int objective, const float* x, const float* e
                          const float* c_host, float* out, float* x_start, int64_t n, void* stream) {
     DM_REQUIRE(x && eps && c_host && out, "null argument");
     DM_REQUIRE(objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "unknown objective");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    float* cd = nullptr;
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&cd), DM_COEFS * sizeof(float)));
-    DM_CHECK_HIP(hipMemcpy(cd, c_host, DM_COEFS * sizeof(float), hipMemcpyHostToDevice));
-    int rc = launch_sampler_update(kind, x, eps, noise, cd, nullptr, 0, out, nullptr, nullptr, n, s, objective, x_start);
-    hipError_t e = hipStreamSynchronize(s);
-    (void)hipFree(cd);
-    if (!rc && e != hipSuccess) {
-        set_error(std::string("kernel execution failed: ") + hipGetErrorString(e));
-        rc = 1;
-    }
-    return rc;
+    return table_op(c_host, 1, stream, [&](const float* cd, hipStream_t s) {
+        return launch_sampler_update(kind, x, eps, noise, cd, nullptr, 0, out, nullptr, nullptr, n, s, objective, x_start);
+    }, DM_COEFS);
 }
 
 int dm_op_cfg_combine(const float* cond, const float* null_out, float* out, int B, int64_t per_sample, float cond_scale,

@@ -105,19 +105,21 @@ struct TrainState {
     long long max_copy = 0;
     char* ws = nullptr;
     size_t ws_cap = 0;
-    float* coef_dev = nullptr;  // [B][4]
-    int64_t* t_dev = nullptr;
+    // per-image device rows of a loss / backward call, grown together (grow_train_rows) to cap_B images.  A handle is armed
+    // for integer or float time, never both: a call writes t_dev or tf_dev, and the coefficient rows at the width its own
+    // kernels index them with (DM_TRAIN_COEFS, or DM_EDM_COEFS on the float-time paths)
+    float* coef_dev = nullptr;    // [B][up to DM_EDM_COEFS]
+    int64_t* t_dev = nullptr;     // [B] integer timesteps
+    float* tf_dev = nullptr;      // [B] float times: c_noise(sigma_b), log_snr_b
     int32_t* mask_dev = nullptr;  // [B]: the per-image text mask of a masked call (dm_unet_loss_backward_masked)
     int cap_B = 0;
     float* loss_dev = nullptr;
     // float-time training (dm_unet_train_enable_ft: ElucidatedDiffusion): the U-Net's time is a float per image and the
     // embedding's `weights` take a gradient (exact zeros when frozen: random_fourier_features has requires_grad = False)
     bool ft = false, freqs_frozen = false;
-    float* tf_dev = nullptr;        // [B] c_noise(sigma_b)
-    float* edm_coef_dev = nullptr;  // [B][DM_EDM_COEFS]
-    int edm_cap_B = 0;
-    std::vector<float> coef_stage;  // the call's coefficient rows, DM_TRAIN_COEFS floats each
-    std::map<std::array<long long, 8>, size_t> ws_need;  // workspace bytes per call shape (measured by a dry run, once)
+    std::vector<float> coef_stage;  // the call's coefficient rows at the device width, then its float times
+    // workspace bytes per call (measured by a dry run, once): entry, B, H, W, bucketed, the entry's own TrainRun::sel
+    std::map<std::array<long long, 9>, size_t> ws_need;
     ~TrainState() {
         for (void* q : {(void*)param, (void*)adam_m, (void*)adam_v, (void*)ema, (void*)norm_ws, (void*)clip2, (void*)pack_tmp,
                         (void*)copy_table, (void*)mlp_rows, (void*)rjobs_dev, (void*)cjobs_dev, (void*)pk_dev[0], (void*)pk_dev[1],
@@ -137,7 +139,6 @@ struct TrainState {
         if (mask_dev) (void)hipFree(mask_dev);
         if (loss_dev) (void)hipFree(loss_dev);
         if (tf_dev) (void)hipFree(tf_dev);
-        if (edm_coef_dev) (void)hipFree(edm_coef_dev);
     }
 };
 
@@ -1414,6 +1415,96 @@ static int ensure_train_ws(TrainState& T, size_t bytes) {
     return 0;
 }
 
+// the per-image device rows (coefficients at the widest row, integer and float times, text mask) hold B images
+static int grow_train_rows(TrainState& T, int B) {
+    if (B <= T.cap_B) return 0;
+    DM_CHECK_HIP(hipDeviceSynchronize());
+    for (void** q : {(void**)&T.coef_dev, (void**)&T.t_dev, (void**)&T.tf_dev, (void**)&T.mask_dev}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    T.cap_B = 0;
+    static_assert(DM_EDM_COEFS >= DM_TRAIN_COEFS, "the rows are sized for the widest entry");
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.coef_dev), (size_t)B * DM_EDM_COEFS * sizeof(float)));
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.t_dev), (size_t)B * sizeof(int64_t)));
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.tf_dev), (size_t)B * sizeof(float)));
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.mask_dev), (size_t)B * sizeof(int32_t)));
+    T.cap_B = B;
+    return 0;
+}
+
+// ---- one loss + backward call -------------------------------------------------------------------------------------------
+// What every training entry (DDPM, learned variance, ElucidatedDiffusion, continuous time) hands run_train once its own
+// argument checks have passed.  An entry keeps what is its own: those checks and run(arena, tape) -- its noise-in pass, tape
+// forward, loss kernel and backward pass, reading T.coef_dev / t_dev / tf_dev / mask_dev.
+enum TrainEntry : long long { TRAIN_DDPM, TRAIN_EDM, TRAIN_CT, TRAIN_LV };
+namespace {
+struct TrainRun {
+    TrainEntry entry = TRAIN_DDPM;
+    std::array<long long, 4> sel{};  // whatever else selects the entry's allocation sequence (workspace key, below)
+    int B = 0, H = 0, W = 0;
+    void* stream = nullptr;
+    float* loss_out_host = nullptr;  // nullptr: the loss stays on the device (dm_unet_train_scalar)
+    const float* coef_host = nullptr;  // B rows of `cstride` floats; on the device a row is `width` floats, zero-extended
+    int cstride = 0, width = 0;
+    int tf_col = -1;                   // >= 0: this column of every row is also the image's float time (tf_dev)
+    const int64_t* t_host = nullptr;   // integer timesteps (t_dev)
+    const int32_t* text_mask = nullptr;  // per-image text mask (mask_dev)
+};
+}  // namespace
+
+// The call itself: device, per-image rows, workspace (sized by a dry run of `run`, once per key: entry, shape, bucketing
+// and r.sel), ordering behind the handle's previous call, the uploads, the real run on an arena over the workspace, the
+// dropout call counter -- advanced by a call that succeeded, and only by that --, then the handle's done mark and the
+// optional loss read-back, which waits for the stream.
+static int run_train(dm_unet* u, const TrainRun& r, const std::function<int(Arena&, Tape&)>& run) {
+    DM_CHECK_HIP(hipSetDevice(u->device));
+    hipStream_t s = static_cast<hipStream_t>(r.stream);
+    TrainState& T = *u->train;
+    const int B = r.B;
+    const size_t n_coef = (size_t)B * r.width;
+    if (guarded([&]() -> int {
+            if (grow_train_rows(T, B)) return 1;
+            const std::array<long long, 9> key{r.entry, B, r.H, r.W, T.bucketed ? 1 : 0, r.sel[0], r.sel[1], r.sel[2], r.sel[3]};
+            auto known = T.ws_need.find(key);
+            if (known == T.ws_need.end()) {
+                Arena dry;
+                dry.dry = true;
+                Tape tp;
+                if (run(dry, tp)) return 1;
+                known = T.ws_need.emplace(key, dry.off).first;
+            }
+            if (ensure_train_ws(T, known->second)) return 1;
+            if (u->order_after_previous(s)) return 1;  // e.g. an optimiser step enqueued on another stream
+            T.coef_stage.assign(n_coef + (r.tf_col >= 0 ? B : 0), 0.f);
+            const int ncopy = std::min(r.cstride, r.width);
+            for (int b = 0; b < B; ++b) {
+                std::memcpy(&T.coef_stage[(size_t)b * r.width], r.coef_host + (size_t)b * r.cstride, ncopy * sizeof(float));
+                if (r.tf_col >= 0) T.coef_stage[n_coef + b] = r.coef_host[(size_t)b * r.cstride + r.tf_col];
+            }
+            DM_CHECK_HIP(hipMemcpyAsync(T.coef_dev, T.coef_stage.data(), n_coef * sizeof(float), hipMemcpyHostToDevice, s));
+            if (r.t_host) DM_CHECK_HIP(hipMemcpyAsync(T.t_dev, r.t_host, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            if (r.tf_col >= 0)
+                DM_CHECK_HIP(hipMemcpyAsync(T.tf_dev, T.coef_stage.data() + n_coef, (size_t)B * sizeof(float), hipMemcpyHostToDevice, s));
+            if (r.text_mask)
+                DM_CHECK_HIP(hipMemcpyAsync(T.mask_dev, r.text_mask, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            Arena A;
+            A.base = T.ws;
+            A.cap = T.ws_cap;
+            Tape tp;
+            if (run(A, tp)) return 1;
+            T.drop_call += 1;
+            DM_REQUIRE(A.off <= T.ws_cap, "training workspace overrun: the dry run and the real run allocated differently");
+            return 0;
+        }))
+        return 1;
+    if (u->mark_done(s)) return 1;
+    if (!r.loss_out_host) return 0;
+    DM_CHECK_HIP(hipMemcpyAsync(r.loss_out_host, T.loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+    DM_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
 }  // namespace dm
 
 extern "C" {
@@ -1548,21 +1639,6 @@ int dm_unet_get_grad(dm_unet* u, const char* name, float* out_dev, void* stream)
     return 0;
 }
 
-// the per-image device rows of an integer-time call (coefficients, timesteps, text mask) hold B images
-static int grow_train_rows(TrainState& T, int B) {
-    if (B <= T.cap_B) return 0;
-    DM_CHECK_HIP(hipDeviceSynchronize());
-    if (T.coef_dev) (void)hipFree(T.coef_dev);
-    if (T.t_dev) (void)hipFree(T.t_dev);
-    if (T.mask_dev) (void)hipFree(T.mask_dev);
-    T.coef_dev = nullptr; T.t_dev = nullptr; T.mask_dev = nullptr; T.cap_B = 0;
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.coef_dev), (size_t)B * DM_TRAIN_COEFS * sizeof(float)));
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.t_dev), (size_t)B * sizeof(int64_t)));
-    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.mask_dev), (size_t)B * sizeof(int32_t)));
-    T.cap_B = B;
-    return 0;
-}
-
 static int loss_backward_impl(dm_unet* u, const dm_train_args& a, const int32_t* text_mask = nullptr) {
     const float *x_start = a.x_start, *coef_host = a.coef_host, *noise = a.noise, *noise_q = a.noise_q, *cond = a.cond,
                 *ctx = a.ctx;
@@ -1592,15 +1668,21 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a, const int32_t*
     DM_REQUIRE(u->cfg.input_channels == u->cfg.channels * (self_cond ? 2 : 1) + cond_channels && u->out_dim == u->cfg.channels,
                "training path: U-Net input channels != channels [* 2 with self-conditioning] + cond_channels");
     if (check_hw(u, H, W)) return 1;
-    DM_CHECK_HIP(hipSetDevice(u->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     TrainState& T = *u->train;
-    if (grow_train_rows(T, B)) return 1;
     const int C = u->cfg.channels;
     const int per = C * H * W;
     const size_t n = (size_t)B * per;
-    const int32_t* mask = text_mask ? T.mask_dev : nullptr;  // the same mask in every forward pass of the call
     auto run = [&](Arena& A, Tape& tp) -> int {
+        if (!A.dry && !accumulate && !ctx && u->cfg.text_mode != DM_TEXT_NONE) {
+            // text_emb=None on a text-conditional U-Net (caption dropout): the pass visits no text parameter, and with
+            // accumulate == 0 every other gradient is overwritten -- torch leaves these .grad None, here they must not keep
+            // the values of an earlier call with captions
+            for (const std::string& name : u->order)
+                if (name.compare(0, 5, "text_") == 0 || name.compare(0, 10, "cross_attn") == 0)
+                    DM_CHECK_HIP(hipMemsetAsync(T.grad + T.off.at(name), 0, P(u, name).numel() * sizeof(float), s));
+        }
+        const int32_t* mask = text_mask ? T.mask_dev : nullptr;  // the same mask in every forward pass of the call
         float* x = A.alloc(n);
         float* out = A.alloc(n);
         float* dout = A.alloc(n);
@@ -1649,55 +1731,13 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a, const int32_t*
         }
         return unet_train_backward(u, A, x, dout, B, H, W, s, tp, accumulate);
     };
-    try {
-        // workspace a call of this shape needs: a dry run of the same allocation sequence, once per shape
-        const std::array<long long, 8> key{B, H, W, self_cond, cond_channels, ctx_tokens, ctx ? 1 : 0,
-                                            (model_out ? 1 : 0) | (T.bucketed ? 2 : 0) | (text_mask ? 4 : 0)};
-        auto known = T.ws_need.find(key);
-        if (known == T.ws_need.end()) {
-            Arena dry;
-            dry.dry = true;
-            Tape tp;
-            if (run(dry, tp)) return 1;
-            known = T.ws_need.emplace(key, dry.off).first;
-        }
-        if (ensure_train_ws(T, known->second)) return 1;
-        if (u->order_after_previous(s)) return 1;  // e.g. an optimiser step enqueued on another stream
-        if (!accumulate && !ctx && u->cfg.text_mode != DM_TEXT_NONE) {
-            // text_emb=None on a text-conditional U-Net (caption dropout): the pass visits no text parameter, and with
-            // accumulate == 0 every other gradient is overwritten -- torch leaves these .grad None, here they must not keep
-            // the values of an earlier call with captions
-            for (const std::string& name : u->order)
-                if (name.compare(0, 5, "text_") == 0 || name.compare(0, 10, "cross_attn") == 0)
-                    DM_CHECK_HIP(hipMemsetAsync(T.grad + T.off.at(name), 0, P(u, name).numel() * sizeof(float), s));
-        }
-        {   // coefficient rows as the kernels index them (DM_TRAIN_COEFS floats; a shorter caller row is zero-extended)
-            T.coef_stage.assign((size_t)B * DM_TRAIN_COEFS, 0.f);
-            for (int b = 0; b < B; ++b)
-                std::memcpy(&T.coef_stage[(size_t)b * DM_TRAIN_COEFS], coef_host + (size_t)b * cstride, cstride * sizeof(float));
-        }
-        DM_CHECK_HIP(hipMemcpyAsync(T.coef_dev, T.coef_stage.data(), (size_t)B * DM_TRAIN_COEFS * sizeof(float),
-                                    hipMemcpyHostToDevice, s));
-        DM_CHECK_HIP(hipMemcpyAsync(T.t_dev, t_host, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        if (text_mask) {
-            DM_CHECK_HIP(hipMemcpyAsync(T.mask_dev, text_mask, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        }
-        Arena A;
-        A.base = T.ws;
-        A.cap = T.ws_cap;
-        Tape tp;
-        if (run(A, tp)) return 1;
-        T.drop_call += 1;
-        DM_REQUIRE(A.off <= T.ws_cap, "training workspace overrun: the dry run and the real run allocated differently");
-    } catch (const std::exception& e) {
-        set_error(e.what());
-        return 1;
-    }
-    if (u->mark_done(s)) return 1;
-    if (!loss_out_host) return 0;  // asynchronous form: the loss stays on the device (dm_unet_train_scalar)
-    DM_CHECK_HIP(hipMemcpyAsync(loss_out_host, T.loss_dev, sizeof(float), hipMemcpyDeviceToHost, s));
-    DM_CHECK_HIP(hipStreamSynchronize(s));
-    return 0;
+    TrainRun r;
+    r.entry = TRAIN_DDPM;
+    r.sel = {self_cond, cond_channels, ctx_tokens, (ctx ? 1 : 0) | (model_out ? 2 : 0) | (text_mask ? 4 : 0)};
+    r.B = B; r.H = H; r.W = W; r.stream = stream; r.loss_out_host = loss_out_host;
+    r.coef_host = coef_host; r.cstride = cstride; r.width = DM_TRAIN_COEFS;
+    r.t_host = t_host; r.text_mask = text_mask;
+    return run_train(u, r, run);
 }
 
 int dm_unet_loss_backward(dm_unet* u, const float* x_start, const int64_t* t_host, const float* coef_host, const float* noise,
@@ -1984,7 +2024,11 @@ int dm_op_dropout_mask(float* out, int64_t n, float p, uint64_t seed, uint64_t c
 
 // Per-call coefficient tables of the stand-alone elementwise ops: one grow-only device buffer per (host thread, device), on
 // the device the data lives on (the ops take no handle: the device comes from the data pointer).  The caller synchronises
-// the stream before it returns, so the buffer is free again for the thread's next call.
+// the stream before it returns, so the buffer is free again for the thread's next call.  These ops keep this helper
+// beside table_op (dm_op_scaffold.inc), which allocates per call on the CURRENT device: they pick the device from the
+// data pointer, which a caller with tensors on several devices observes (q_sample and lincomb are product calls of the
+// Python classes, not test plumbing only), and dm_op_mse_loss copies its parts to DEVICE pointers.  Nothing is read that
+// the call did not write: the table is uploaded whole and the kernel writes every scratch float the entry copies out.
 // `extra`: floats of device scratch behind the table (per-sample partial sums, a scalar result)
 static int stage_coefs(const void* data_dev, const float* host, size_t n, hipStream_t s, float** out, size_t extra = 0) {
     hipPointerAttribute_t at{};

@@ -375,7 +375,7 @@ int dm_unet_get_grad(dm_unet* u, const char* name, float* out_dev, void* stream)
  *   x = q_sample(x_start, t, noise) (:813-821);  out = Unet(x, t);  target per `objective` (DM_OBJ_*, :864-872);
  *   loss = loss_scale * mean_b( loss_weight[t_b] * mean((out - target)^2) ) (:874-878, :889);  every parameter gradient.
  * x_start, noise: (B, C, H, W) device, x_start already normalised to [-1, 1];  t_host: (B) timesteps;
- * coef_host: (B, DM_TRAIN_COEFS = 8) = sqrt_alphas_cumprod[t_b], sqrt_one_minus_alphas_cumprod[t_b], loss_weight[t_b], 0,
+ * coef_host: (B, 8) = sqrt_alphas_cumprod[t_b], sqrt_one_minus_alphas_cumprod[t_b], loss_weight[t_b], 0,
  * sqrt_recip_alphas_cumprod[t_b], sqrt_recipm1_alphas_cumprod[t_b], 0, 0 -- the values `extract` gathers (:394-397).
  * self_cond (Unet(self_condition=True), :846-855): 0 off; 1 the U-Net sees [0 | x]; 2 it sees [x_start | x] with x_start
  * predicted (unclipped, without gradient) by a first forward pass on [0 | x] -- the caller flips the reference's coin.  loss_scale = 1 / gradient_accumulate_every and accumulate != 0 adds the gradients to
