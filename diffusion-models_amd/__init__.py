@@ -29,6 +29,7 @@ from .continuous import (ContinuousTimeGaussianDiffusion, VParamContinuousTimeGa
                          alpha_cosine_log_snr, beta_linear_log_snr, ct_step_table, ct_train_table)
 from .repaint import GaussianDiffusion as RePaintGaussianDiffusion, RepaintTable, repaint_step_table  # noqa: F401
 from .learned import LearnedGaussianDiffusion, lv_step_table, lv_train_table  # noqa: F401
+from .weighted import WeightedObjectiveGaussianDiffusion, wo_step_table, wo_train_table  # noqa: F401
 from .classifier_guidance import ClassifierGuidedGaussianDiffusion, cg_step_table  # noqa: F401
 from .vae import VQDecoder, VQEncoder, VQModel  # noqa: F401
 from .dist import gather_shards, sample_global, sample_sharded, shard_bounds, shared_seed  # noqa: F401
@@ -50,6 +51,7 @@ __all__ = [
     "VParamContinuousTimeGaussianDiffusion",
     "RePaintGaussianDiffusion",
     "LearnedGaussianDiffusion",
+    "WeightedObjectiveGaussianDiffusion",
     "ClassifierGuidedGaussianDiffusion",
     "VQDecoder",
     "VQEncoder",
@@ -79,6 +81,8 @@ __all__ = [
     "RepaintTable",
     "lv_step_table",
     "lv_train_table",
+    "wo_step_table",
+    "wo_train_table",
     "synth_state_dict",
     "synth_tensor",
 ]

@@ -23,6 +23,8 @@ CT_PRED_NOISE, CT_PRED_V = 0, 1
 DM_REPAINT_COEFS = 16
 DM_LV_COEFS = 16
 DM_LV_TRAIN_COEFS = 12
+DM_WO_COEFS = 16
+DM_WO_TRAIN_COEFS = 12
 DM_CG_COEFS = 16
 ABI_VERSION = 9
 
@@ -57,6 +59,7 @@ EXPORTS = (
     "dm_sample_ct", "dm_unet_loss_backward_ct", "dm_op_ct_step", "dm_op_ct_noise_in", "dm_op_ct_loss",
     "dm_sample_repaint", "dm_op_repaint_step",
     "dm_sample_lv", "dm_unet_loss_backward_lv", "dm_op_lv_step", "dm_op_lv_loss",
+    "dm_sample_wo", "dm_unet_loss_backward_wo", "dm_op_wo_step", "dm_op_wo_loss",
     "dm_sample_classifier_guided", "dm_op_cg_mean", "dm_op_cg_finish",
 )
 
@@ -186,6 +189,27 @@ class CguideArgs(C.Structure):
         ("mean", C.c_void_p), ("grad", C.c_void_p), ("cond_cb", CondCallback), ("user", C.c_void_p),
         ("out", C.c_void_p), ("all_steps", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
         ("unnormalize", C.c_int32), ("use_graph", C.c_int32), ("reserved2_", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
+class WoArgs(C.Structure):
+    """dm_wo_args (include/dm_hip.h)."""
+    _fields_ = [
+        ("n_steps", C.c_int32), ("times_host", C.POINTER(C.c_int64)), ("table_host", C.POINTER(C.c_float)),
+        ("x_T", C.c_void_p), ("noise", C.c_void_p), ("seed", C.c_uint64), ("sample_offset", C.c_uint64),
+        ("out", C.c_void_p), ("all_steps", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("unnormalize", C.c_int32), ("use_graph", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
+class WoTrainArgs(C.Structure):
+    """dm_wo_train_args (include/dm_hip.h)."""
+    _fields_ = [
+        ("x_start", C.c_void_p), ("t_host", C.POINTER(C.c_int64)), ("coef_host", C.POINTER(C.c_float)),
+        ("coef_stride", C.c_int32), ("noise", C.c_void_p), ("pred_noise_loss_weight", C.c_float),
+        ("pred_x_start_loss_weight", C.c_float), ("loss_scale", C.c_float), ("accumulate", C.c_int32),
+        ("loss_out_host", C.POINTER(C.c_float)), ("model_out", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32),
+        ("W", C.c_int32), ("stream", C.c_void_p),
     ]
 
 
@@ -330,6 +354,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_sample_classifier_guided.argtypes = [vp, C.POINTER(CguideArgs)]
     lib.dm_op_cg_mean.argtypes = [fp, fp, C.POINTER(C.c_float), i32, fp, fp, i32, i64, vp]
     lib.dm_op_cg_finish.argtypes = [fp, fp, fp, C.POINTER(C.c_float), u64, u64, u64, fp, fp, i32, i64, vp]
+    lib.dm_sample_wo.argtypes = [vp, C.POINTER(WoArgs)]
+    lib.dm_unet_loss_backward_wo.argtypes = [vp, C.POINTER(WoTrainArgs)]
+    lib.dm_op_wo_step.argtypes = [fp, fp, fp, C.POINTER(C.c_float), i32, u64, u64, u64, fp, fp, fp, i32, i32, i64, vp]
+    lib.dm_op_wo_loss.argtypes = [fp, fp, fp, fp, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, fp, C.POINTER(C.c_float),
+                                  C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, i64, vp]
     lib.dm_profile_read.argtypes = [C.POINTER(ProfileRow), i32, C.POINTER(i32)]
 
 

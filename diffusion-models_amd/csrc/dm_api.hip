@@ -8,6 +8,7 @@
 #include "ct.h"
 #include "repaint.h"
 #include "learned.h"
+#include "weighted.h"
 #include "cguide.h"
 
 #include <array>
@@ -319,7 +320,7 @@ struct dm_unet {
     std::vector<std::pair<std::string, ResBlock*>> resnets;  // in ss_off order
     // the instantiated graph of one denoise step, reused while the key (shape, kind, every captured pointer) holds.  The
     // slot serves every sampling loop of the handle (dm_sampler.inc: run_steps); the kind says whose graph it holds.
-    enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT, GK_LV, GK_CG };
+    enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT, GK_LV, GK_CG, GK_WO };
     struct GraphKey {
         int kind = GK_NONE, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
         int edm_clamp = 0;      // ElucidatedDiffusion: the clamp flag, a kernel argument of the captured Heun step
@@ -1655,4 +1656,5 @@ int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t eleme
 #include "dm_ct.inc"
 #include "dm_repaint.inc"
 #include "dm_learned.inc"
+#include "dm_weighted.inc"
 #include "dm_cguide.inc"

@@ -1434,10 +1434,10 @@ static int grow_train_rows(TrainState& T, int B) {
 }
 
 // ---- one loss + backward call -------------------------------------------------------------------------------------------
-// What every training entry (DDPM, learned variance, ElucidatedDiffusion, continuous time) hands run_train once its own
-// argument checks have passed.  An entry keeps what is its own: those checks and run(arena, tape) -- its noise-in pass, tape
-// forward, loss kernel and backward pass, reading T.coef_dev / t_dev / tf_dev / mask_dev.
-enum TrainEntry : long long { TRAIN_DDPM, TRAIN_EDM, TRAIN_CT, TRAIN_LV };
+// What every training entry (DDPM, learned variance, weighted objective, ElucidatedDiffusion, continuous time) hands
+// run_train once its own argument checks have passed.  An entry keeps what is its own: those checks and run(arena, tape)
+// -- its noise-in pass, tape forward, loss kernel and backward pass, reading T.coef_dev / t_dev / tf_dev / mask_dev.
+enum TrainEntry : long long { TRAIN_DDPM, TRAIN_EDM, TRAIN_CT, TRAIN_LV, TRAIN_WO };
 namespace {
 struct TrainRun {
     TrainEntry entry = TRAIN_DDPM;
@@ -1657,6 +1657,8 @@ static int loss_backward_impl(dm_unet* u, const dm_train_args& a, const int32_t*
     DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
     DM_REQUIRE(u->out_dim != 2 * u->cfg.channels, "the U-Net predicts a learned variance (out_dim == 2 * channels): its loss is "
                                                   "dm_unet_loss_backward_lv");
+    DM_REQUIRE(u->out_dim != 2 * u->cfg.channels + 2, "the U-Net predicts noise, x_start and two weight maps (out_dim == 2 * channels + 2): "
+                                                      "its loss is dm_unet_loss_backward_wo");
     DM_REQUIRE(B > 0 && objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "bad argument");
     DM_REQUIRE(terms >= 1 && terms <= 3 && cstride >= 8 && cstride <= DM_TRAIN_COEFS && (!(terms & 2) || cstride == DM_TRAIN_COEFS),
                "loss_terms is 1 (MSE), 2 (KL) or 3 (both); the KL term needs coef rows of 12 floats");

@@ -915,6 +915,89 @@ int dm_op_lv_loss(const float* model_out, const float* x_start, const float* noi
                   float vb_loss_weight, int clip_denoised, float loss_scale, float* dout, float* loss_out_host,
                   float* mse_part_out_host, float* vb_part_out_host, int B, int64_t per, void* stream);
 
+/* ---- WeightedObjectiveGaussianDiffusion (DD/weighted_objective_gaussian_diffusion.py:14-74): the U-Net predicts
+ * 2 * channels + 2 maps per image (out_dim == 2 * channels + 2, :25) -- the noise eps (C maps), x_start px (C maps) and two
+ * weight maps w0, w1.  The softmax over the pair, s0 = sigmoid(w0 - w1), s1 = 1 - s0, blends the x_start derived from the
+ * noise with the predicted one, pixel by pixel.  The handle has no text conditioning, an integer time, input channels ==
+ * channels (no self-conditioning, :26) and out_dim <= 8 (channels <= 3: the thin-output final_conv kernels stop there).
+ *
+ * Sampling (the base class's p_sample_loop, DD/denoising_diffusion.py:647-664, over p_mean_variance :33-49; the reference's
+ * own p_sample passes x_self_cond and unpacks four values, which this p_mean_variance does not take: the loop here calls it
+ * with (x, t, clip_denoised = True) and takes its three values).  The HOST gathers every per-step scalar in fp32 as
+ * `extract` does; row i is DM_WO_COEFS floats at the step's time t_i:
+ *   c[0]=sqrt_recip_alphas_cumprod   c[1]=sqrt_recipm1_alphas_cumprod   c[2]=posterior_mean_coef1   c[3]=posterior_mean_coef2
+ *   c[4]=posterior_log_variance_clipped   c[5]=1 if t_i > 0 else 0;  the rest 0.
+ * Step i runs (eps | px | w0 | w1) = Unet(x, t_i) and one elementwise pass:
+ *   x_start = clamp(s0 (c[0] x - c[1] eps) + s1 px, -1, 1);   x <- c[2] x_start + c[3] x + exp(0.5 c[4]) * z   (z = 0 where c[5] == 0)
+ * Every field is dm_lv_args': times_host, table_host (n_steps x DM_WO_COEFS), x_T, noise, seed, sample_offset, out,
+ * all_steps, unnormalize, use_graph (cached in the slot dm_sample uses, under a kind of its own), stream.  H * W % 4 == 0. */
+#define DM_WO_COEFS 16
+typedef struct dm_wo_args {
+    int32_t n_steps;
+    const int64_t* times_host;
+    const float* table_host;
+    const float* x_T;
+    const float* noise;
+    uint64_t seed;
+    uint64_t sample_offset;
+    float* out;
+    float* all_steps;
+    int32_t B, H, W;
+    int32_t unnormalize;
+    int32_t use_graph;
+    void* stream;
+} dm_wo_args;
+int dm_sample_wo(dm_unet* u, const dm_wo_args* args);
+
+/* One p_losses (:51-74) and its backward pass on a handle armed by dm_unet_train_enable (dm_unet_loss_backward* refuse such
+ * a handle and name this call).  With N = B C H W:
+ *   x_t = c[0] x_start + c[1] noise;  (pn | px | w0 | w1) = Unet(x_t, t_b);  xs = c[2] x_t - c[3] pn;  xc = clamp(xs, -2, 2)
+ *   wx = s0 xc + s1 px
+ *   loss = loss_scale * (mean((x_start - wx)^2) + pred_x_start_loss_weight * mean((x_start - px)^2)
+ *                        + pred_noise_loss_weight * mean((noise - pn)^2));  every parameter gradient, from
+ *   d pn = 2 / N [w_n (pn - noise) - (wx - x_start) s0 c[3] (-2 <= xs <= 2)]     (torch's clamp passes the gradient on the bounds)
+ *   d px = 2 / N [w_x (px - x_start) + (wx - x_start) s1]
+ *   d w0 = 2 / N sum_c (wx - x_start) (xc - px) s0 s1;   d w1 = -d w0
+ * coef_host: B rows of coef_stride floats (0: DM_WO_TRAIN_COEFS; 4 to 12):
+ *   c[0]=sqrt_alphas_cumprod[t_b]  c[1]=sqrt_one_minus_alphas_cumprod[t_b]  c[2]=sqrt_recip_alphas_cumprod[t_b]
+ *   c[3]=sqrt_recipm1_alphas_cumprod[t_b];  the rest 0.
+ * loss_scale, accumulate, loss_out_host (NULL: the loss stays on the device, dm_unet_train_scalar) as in
+ * dm_unet_loss_backward_ex; model_out (optional, device) receives the (B, 2C + 2, H, W) model output. */
+#define DM_WO_TRAIN_COEFS 12
+typedef struct dm_wo_train_args {
+    const float* x_start;
+    const int64_t* t_host;
+    const float* coef_host;
+    int32_t coef_stride;
+    const float* noise;
+    float pred_noise_loss_weight;
+    float pred_x_start_loss_weight;
+    float loss_scale;
+    int32_t accumulate;
+    float* loss_out_host;
+    float* model_out;
+    int32_t B, H, W;
+    void* stream;
+} dm_wo_train_args;
+int dm_unet_loss_backward_wo(dm_unet* u, const dm_wo_train_args* args);
+
+/* The two kernels on their own (tests, p_sample, p_mean_variance).  Tensors are on the device: x, z, out, mean_out,
+ * x_start_out, x_start, noise, x_t are (B, C, HW); model_out and dout (B, 2C + 2, HW); HW % 4 == 0, 16-byte aligned; tables
+ * are on the host; each call waits for its result.
+ *   step:  one row of DM_WO_COEFS floats.  clip_denoised != 0 clamps the weighted x_start to [-1, 1] (p_sample always
+ *          does).  z NULL: Philox draw `draw` (>= 1) under `seed`, the counter of element b C HW + c HW + p from
+ *          element_offset; a row with c[5] == 0 reads neither.  out may be x.  mean_out, x_start_out (optional) are
+ *          p_mean_variance's model_mean and the weighted x_start.
+ *   loss:  B rows of DM_WO_TRAIN_COEFS floats.  *loss_out_host = the loss above; weighted_part / x_start_part / noise_part
+ *          (optional, B floats on the host) = the three per-image means, unweighted;  dout = d loss / d model_out. */
+int dm_op_wo_step(const float* x, const float* model_out, const float* z, const float* c_host, int clip_denoised, uint64_t seed,
+                  uint64_t draw, uint64_t element_offset, float* out, float* mean_out, float* x_start_out, int B, int C,
+                  int64_t HW, void* stream);
+int dm_op_wo_loss(const float* model_out, const float* x_start, const float* noise, const float* x_t, const float* c_host,
+                  float pred_noise_loss_weight, float pred_x_start_loss_weight, float loss_scale, float* dout,
+                  float* loss_out_host, float* weighted_part_out_host, float* x_start_part_out_host,
+                  float* noise_part_out_host, int B, int C, int64_t HW, void* stream);
+
 /* ---- Classifier-guided DDPM sampling (Sohl-Dickstein et al. 2015; Dhariwal & Nichol 2021; as DD/guided_diffusion.py:553-603
  * has it): after the U-Net has produced the posterior mean, the caller's cond_fn returns grad log p(y | x) AT THAT MEAN, the
  * mean is shifted by posterior_variance[t] * gradient, and the noise is added after that.  The handle has no text
