@@ -631,6 +631,27 @@ static int build_scale_shift(dm_unet* u) {
     return 0;
 }
 
+// The fused form of a LinearAttention layer (linattn_fused.hip) from host copies of its weights.  A.out.bias and A.mem_kv
+// are already on the device.  has_fused stays false when the layer is not eligible or a softmax bound is too large for
+// the shift trick: such a layer keeps the unfused chain.
+static int fuse_linattn(DeviceOwner& own, AttnLayer& A, const float* w_qkv, const float* norm_g, const float* w_out,
+                        const float* mem_kv, const float* out_g, int dim, int heads, int dh) {
+    A.has_fused = false;
+    if (!linattn_fused_eligible(dim, heads, dh)) return 0;
+    std::vector<float> wq, wk, wv, wo, kb;
+    if (!linattn_fused_pack(w_qkv, norm_g, w_out, mem_kv, dim, wq, wk, wv, wo, kb)) return 0;
+    std::vector<float> ogs(out_g, out_g + dim);
+    for (float& v : ogs) v *= std::sqrt((float)dim);
+    float *dq, *dk, *dv, *dwo, *dkb, *dog;
+    if (own.upload(wq.data(), wq.size(), &dq) || own.upload(wk.data(), wk.size(), &dk) ||
+        own.upload(wv.data(), wv.size(), &dv) || own.upload(w_out, (size_t)dim * heads * dh, &dwo) ||
+        own.upload(kb.data(), kb.size(), &dkb) || own.upload(ogs.data(), ogs.size(), &dog))
+        return 1;
+    A.fused = LinAttnFused{dim, dq, dk, dv, dwo, A.out.bias, dog, dkb, A.mem_kv};
+    A.has_fused = true;
+    return 0;
+}
+
 static int build_attn_body(dm_unet* u, AttnLayer& A, const std::string& p, int dim, bool full, int heads) {
     A.full = full;
     A.dim = dim;
@@ -659,24 +680,10 @@ static int build_attn_body(dm_unet* u, AttnLayer& A, const std::string& p, int d
         if (make_conv(u->own, A.out, P(u, p + ".to_out.0.weight").data.data(), P(u, p + ".to_out.0.bias").data.data(),
                       dim, hidden, 0, 1, 1, 1, 0, false)) return 1;
         if (up1(u, p + ".to_out.1.g", &A.out_g)) return 1;
-        if (linattn_fused_eligible(dim, heads, u->dh)) {
-            std::vector<float> wq, wk, wv, wo, kb;
-            const HostTensor& og = P(u, p + ".to_out.1.g");
-            if (linattn_fused_pack(P(u, p + ".to_qkv.weight").data.data(), P(u, p + ".norm.g").data.data(),
-                                   P(u, p + ".to_out.0.weight").data.data(), P(u, p + ".mem_kv").data.data(), dim, wq,
-                                   wk, wv, wo, kb)) {
-                std::vector<float> ogs(og.data);
-                for (float& v : ogs) v *= std::sqrt((float)dim);
-                float *dq, *dk, *dv, *dwo, *dkb, *dog;
-                const HostTensor& wor = P(u, p + ".to_out.0.weight");
-                if (u->own.upload(wq.data(), wq.size(), &dq) || u->own.upload(wk.data(), wk.size(), &dk) ||
-                    u->own.upload(wv.data(), wv.size(), &dv) || u->own.upload(wor.data.data(), wor.data.size(), &dwo) ||
-                    u->own.upload(kb.data(), kb.size(), &dkb) || u->own.upload(ogs.data(), ogs.size(), &dog))
-                    return 1;
-                A.fused = LinAttnFused{dim, dq, dk, dv, dwo, A.out.bias, dog, dkb, A.mem_kv};
-                A.has_fused = true;
-            }
-        }
+        if (fuse_linattn(u->own, A, P(u, p + ".to_qkv.weight").data.data(), P(u, p + ".norm.g").data.data(),
+                         P(u, p + ".to_out.0.weight").data.data(), P(u, p + ".mem_kv").data.data(),
+                         P(u, p + ".to_out.1.g").data.data(), dim, heads, u->dh))
+            return 1;
     }
     return 0;
 }

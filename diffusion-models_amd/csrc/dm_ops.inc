@@ -182,6 +182,13 @@ static int attn_op(bool full, const float* x, const float* norm_g, const float* 
     At.out_g = const_cast<float*>(out_g);
     if (make_conv(dummy.own, At.qkv, wq.data(), nullptr, 3 * hidden, C, 0, 1, 1, 1, 0, false)) return 1;
     if (make_conv(dummy.own, At.out, wo.data(), bo.data(), C, hidden, 0, 1, 1, 1, 0, false)) return 1;
+    if (!full) {
+        // the layer as the U-Net builds it: the fused kernels where they are eligible
+        std::vector<float> ng, mk, og;
+        if (d2h(norm_g, C, ng) || d2h(mem_kv, (size_t)2 * hidden * 4, mk) || d2h(out_g, C, og)) return 1;
+        if (fuse_linattn(dummy.own, At, wq.data(), ng.data(), wo.data(), mk.data(), og.data(), C, heads, dim_head))
+            return 1;
+    }
     return run_op(s, [&](Arena& A) -> int {
         int rc = 0;
         Ctx c{&dummy, &A, s, B, nullptr, 0};

@@ -13,7 +13,12 @@
 //      normal float -- keep the unfused path.)
 //   (a tiny kernel sums the block partials, divides by the denominators and folds the context into to_out:
 //    z = W_out (ctx^T q) = (W_out ctx^T) q =: M q with M (C x 32) per image and head, packed in lane order)
-//   2. linattn_out_fused_kernel   (token block, image): q = W_q x^, softmax over dim_head, z = M q + b,
+//   1'. linattn_ctx_image_kernel  (image): the form of kernel 1 for batches that fill the chip (la_image_form).  One
+//      workgroup walks all tokens of its image through a double-buffered LDS window, so there are no partial sums and
+//      no reduce launch: it finishes the image itself and writes M.  It also folds W_v into the context the way W_out
+//      is folded on the output side: ctx = W'_v P with P[d][c] = sum_t a[d][t] rn_t x[t][c], so the token loop forms
+//      k and P only (C/2 + C/2 MFMAs per 32-token tile instead of C/2 + C/2 + 16) and W'_v is applied once per image.
+//   2. linattn_out_fused_kernel  (token block, image): q = W_q x^, softmax over dim_head, z = M q + b,
 //      RMSNorm(z) * g, + x, one store.
 //
 // MFMA bookkeeping (v_mfma_f32_32x32x2_f32, wave = head): the accumulator of one product is used DIRECTLY as an
@@ -36,6 +41,7 @@ static constexpr int LA_CTX = LA_DH * LA_DH + LA_DH;  // partial context + parti
 static constexpr int LA_TOK1 = 128;                   // tokens per workgroup, kernel 1 (C = 128; 256 for C = 64)
 __host__ __device__ constexpr int la_tok1(int C) { return C <= 64 ? 256 : LA_TOK1; }
 static constexpr int LA_TOK2 = 64;                    // tokens per workgroup, kernel 2
+static constexpr int LA_TOKI = 128;                   // tokens per LDS window, per-image form of kernel 1
 
 __host__ __device__ static inline int la_row_of(int e, int half) { return (e & 3) + 8 * (e >> 2) + 4 * half; }
 
@@ -241,6 +247,195 @@ __global__ __launch_bounds__(256) void linattn_ctx_reduce_kernel(const float* __
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// The per-image form of kernel 1: one workgroup of 8 waves walks ALL tokens of its image, wave = (head, token half).
+// ---------------------------------------------------------------------------------------
+// x rows [t0, t0 + LA_TOKI) of one image -> registers.  Rows past the image read the image's last row (always in
+// bounds) and are zeroed, so the LDS window never holds anything but finite numbers.
+template <int C>
+__device__ __forceinline__ void la_image_load(const float* __restrict__ xb, int t0, int n,
+                                              f32x4 (&pre)[LA_TOKI * (C / 4) / 512]) {
+    constexpr int Q = C / 4;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < LA_TOKI * Q / 512; ++i) {
+        const int it = tid + 512 * i;
+        const int row = it / Q, q = it - row * Q;
+        const int t = t0 + row;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (size_t)min(t, n - 1) * C + 4 * q);
+        pre[i] = t < n ? v : make_f32x4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// registers -> LDS window, rn[t] = 1 / max(||x_t||, 1e-12) (the Q lanes that hold one row are consecutive)
+template <int C>
+__device__ __forceinline__ void la_image_store(const f32x4 (&pre)[LA_TOKI * (C / 4) / 512], float* xs, float* rn) {
+    constexpr int XS = C + 4, Q = C / 4;
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < LA_TOKI * Q / 512; ++i) {
+        const int it = tid + 512 * i;
+        const int row = it / Q, q = it - row * Q;
+        const f32x4 v = pre[i];
+        *reinterpret_cast<f32x4*>(xs + row * XS + 4 * q) = v;
+        float ss = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+#pragma unroll
+        for (int o = 1; o < Q; o <<= 1) ss += __shfl_xor(ss, o);
+        if (q == 0) rn[row] = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+    }
+}
+
+// ctx[d][e] = sum_t a[d][t] v[e][t] is linear in v = W'_v (rn_t x_t), so the token loop accumulates
+//   P^T[c][d] = sum_t x[t][c] (a[d][t] rn_t)                      (C/32 column tiles of 32 x 32 per head)
+// and W'_v is applied once per image: ctx^T = W'_v P^T.  A tile costs C/2 MFMAs for k and C/2 for P^T instead of
+// C/2 + C/2 + 16, and no v is ever formed.  Operands: step e of P^T takes A = x[token row_of(e, half)][32 ct + l31]
+// (one ds_read_b32: each lane half reads 32 consecutive floats of one row, conflict-free) and B = a rn from k's
+// accumulator register e; P^T's accumulator register e (row c = 32 ct + row_of(e, half), column d) is the B operand of
+// step (ct, e) of ctx^T = W'_v P^T, whose A operand W'_v[head*32 + l31][8 g + 4 half + s], g = 4 ct + (e >> 2), s = e & 3,
+// is the projection packing as it stands; and ctx^T's accumulator register e (ctx[d = l31][e = row_of(e, half)]) is the
+// A operand of step e of M^T = ctx W_out[:, head]^T, which leaves M in the order kernel 2 reads.
+//
+// Token blocks of LA_TOKI rows go through two LDS windows: the rows of block i+1 are loaded into registers before the
+// products of block i and written to the other window after them, one barrier per block.  Inside a block wave
+// (head, half) takes the 32-token tiles half and half + 2.  The two halves are added through LDS in a fixed order, then
+// the half-0 wave of each head adds the memory tokens, divides by the denominators and writes M: the summation order
+// of an image depends on n alone, never on B or on where the image sits in the batch.
+template <int C>
+__global__ __launch_bounds__(512) void linattn_ctx_image_kernel(const float* __restrict__ x, const LinAttnFused w,
+                                                                float* __restrict__ mz, int n) {
+    constexpr int G = C / 8, XS = C + 4, CT = C / 32, TB = LA_TOKI, NP = TB * (C / 4) / 512;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* rnb = smem + 2 * TB * XS;  // [2][TB]
+    const int b = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int h = wid & 3, th = wid >> 2;  // the two halves of a head share a SIMD
+    const int l31 = lane & 31, lh = lane >> 5;
+    const float* xb = x + (size_t)b * n * C;
+    const int nb = (n + TB - 1) / TB;
+
+    f32x4 wk[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) wk[g] = *reinterpret_cast<const f32x4*>(w.wk + (((size_t)h * G + g) * 64 + lane) * 4);
+    const float kb = w.kbound[h * LA_DH + l31];
+
+    f32x4 pre[NP];
+    la_image_load<C>(xb, 0, n, pre);
+    la_image_store<C>(pre, smem, rnb);
+    __syncthreads();
+
+    f32x16 pacc[CT];
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) pacc[ct][e] = 0.f;
+    float ksum = 0.f;
+    for (int blk = 0; blk < nb; ++blk) {
+        const bool more = blk + 1 < nb;
+        if (more) la_image_load<C>(xb, (blk + 1) * TB, n, pre);
+        const float* xs = smem + (blk & 1) * TB * XS;
+        const float* rn = rnb + (blk & 1) * TB;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int tb = 32 * (th + 2 * j);  // first row of the tile inside the window
+            const int nt = n - blk * TB - tb;  // valid tokens from there on
+            if (nt <= 0) break;
+            // k^T (tokens x d) = x (tokens x C) W'_k^T: A = x row of token l31 from LDS, B = weights in registers
+            f32x16 kacc;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) kacc[e] = 0.f;
+            const float* xr = xs + (tb + l31) * XS + 4 * lh;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(xr + 8 * g);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) kacc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], wk[g][s], kacc, 0, 0, 0);
+            }
+            const float* xc = xs + (tb + 4 * lh) * XS + l31;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const f32x4 r4 = *reinterpret_cast<const f32x4*>(rn + tb + 8 * m + 4 * lh);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int e = 4 * m + i;
+                    const bool valid = 8 * m + 4 * lh + i < nt;
+                    const float a = valid ? __expf(kacc[e] * r4[i] - kb) : 0.f;
+                    ksum += a;
+                    const float ar = a * r4[i];
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct)
+                        pacc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(xc[(8 * m + i) * XS + 32 * ct], ar, pacc[ct], 0, 0, 0);
+                }
+            }
+        }
+        if (more) la_image_store<C>(pre, smem + ((blk + 1) & 1) * TB * XS, rnb + ((blk + 1) & 1) * TB);
+        __syncthreads();  // the next window is written; this one may be rewritten after the next block's products
+    }
+
+    // token half 1 -> LDS (the windows are free behind the loop's last barrier), [head][ct][e][lane]
+    float* cps = smem + (size_t)h * CT * 16 * 64 + lane;
+    float* cks = smem + LA_HEADS * CT * 16 * 64 + h * 64 + lane;
+    if (th == 1) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) cps[(ct * 16 + e) * 64] = pacc[ct][e];
+        *cks = ksum;
+    }
+    __syncthreads();
+    if (th == 1) return;
+
+    ksum += *cks;
+    f32x16 tacc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) tacc[e] = 0.f;
+    {
+        // the 4 learned memory tokens (mem_kv, :159/:182-183), once per image: token j + half per lane half
+        const float* mk = w.mem_kv + (size_t)h * LA_DH * 4;               // [d][j]
+        const float* mv = w.mem_kv + (size_t)(LA_HEADS + h) * LA_DH * 4;  // [e][j]
+#pragma unroll
+        for (int j = 0; j < 4; j += 2) {
+            const float a = __expf(mk[l31 * 4 + j + lh] - kb);
+            ksum += a;
+            tacc = __builtin_amdgcn_mfma_f32_32x32x2f32(mv[l31 * 4 + j + lh], a, tacc, 0, 0, 0);
+        }
+    }
+    // ctx^T (e x d) += W'_v (e x C) P^T (C x d)
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(w.wv + (((size_t)h * G + 4 * ct + q) * 64 + lane) * 4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = 4 * q + i;
+                tacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[i], pacc[ct][e] + cps[(ct * 16 + e) * 64], tacc, 0, 0, 0);
+            }
+        }
+    // softmax denominator of column d = l31 (k.softmax(dim=-1), :186)
+    ksum += __shfl_xor(ksum, 32);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) tacc[e] = tacc[e] / ksum;
+    // M^T (d x c) = ctx (d x e) W_out[:, head]^T (e x c), stored as linattn_ctx_reduce_kernel stores it
+#pragma unroll
+    for (int mt = 0; mt < CT; ++mt) {
+        const float* wr = w.wo_raw + (size_t)(32 * mt + l31) * LA_HID + h * LA_DH + 4 * lh;
+        f32x16 macc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) macc[e] = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4 wo = *reinterpret_cast<const f32x4*>(wr + 8 * q);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) macc = __builtin_amdgcn_mfma_f32_32x32x2f32(tacc[4 * q + i], wo[i], macc, 0, 0, 0);
+        }
+        float* op = mz + ((((size_t)b * LA_HEADS + h) * CT + mt) * 4) * 64 * 4 + lane * 4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            *reinterpret_cast<f32x4*>(op + q * 64 * 4) =
+                make_f32x4(macc[4 * q], macc[4 * q + 1], macc[4 * q + 2], macc[4 * q + 3]);
+    }
+}
+
 template <int C>
 __global__ __launch_bounds__(256) void linattn_out_fused_kernel(const float* __restrict__ x, const LinAttnFused w,
                                                                 const float* __restrict__ mz, float* __restrict__ y,
@@ -353,27 +548,69 @@ static int launch_ctx(const LinAttnFused& w, const float* x, float* ws, int B, i
     return 0;
 }
 
+// Which form of kernel 1 a layer takes.  The per-image form runs B workgroups of 8 waves, so it needs a batch that
+// fills the chip's 256 CUs; below that the (token block, image) grid of the blocked kernel plus the reduce launch win.
+// Context pass per launch in us on MI355X, blocked kernel + reduce | per-image kernel, event-timed through
+// tools/linattn_ctx_time.py (profiles/linattn_image_dispatch_table.json, two runs of each; the second run is within 0.7 us):
+//
+//   (C, tokens)   B = 32         B = 64         B = 128        B = 256
+//   (64, 1024)    16.6 | 80.2    29.5 | 80.4    57.0 | 82.6    106.3 | 86.7
+//   (64, 256)     14.4 | 23.2    15.1 | 23.6    17.9 | 24.6     32.5 | 27.1
+//   (128, 256)    26.5 | 45.3    27.5 | 45.9    31.8 | 48.0     56.9 | 51.4
+//   (128, 64)     13.7 | 19.8    14.8 | 20.2    17.5 | 21.6     24.1 | 23.9
+//
+// It wins at B = 256 wherever an image has more than one 32-token tile per wave; at (128, 64) the two forms tie (one
+// tile per wave, nothing to pipeline, and the C = 128 fold is the larger one), so that shape keeps the blocked kernel.
+// Batches between 128 and 256 and C = 64 maps of 64 tokens or fewer are not measured; the rule takes the per-image form
+// only from the batch at which it was seen to win.
+static bool la_image_form(int B, int n, int C) { return B >= 256 && (C == 64 || n > 64); }
+
+template <int C>
+static int launch_ctx_image(const LinAttnFused& w, const float* x, float* mz, int B, int n, hipStream_t s) {
+    const size_t lds = (size_t)(2 * LA_TOKI * (C + 4) + 2 * LA_TOKI) * 4;
+    static LdsOptIn lds_flag;
+    if (lds_opt_in(lds_flag, reinterpret_cast<const void*>(linattn_ctx_image_kernel<C>), 1)) return 1;
+    hipLaunchKernelGGL(linattn_ctx_image_kernel<C>, dim3(B), dim3(512), lds, s, x, w, mz, n);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 template <int C>
 static int launch_c(const LinAttnFused& w, const float* x, float* ws, float* y, int B, int n, bool add_x, hipStream_t s) {
+    const bool image = la_image_form(B, n, C);
     // 256-token blocks halve the partial-context traffic, but only when they still fill the chip
     const bool big = la_tok1(C) == 256 && (size_t)B * ((n + 255) / 256) >= 512;
     const int tok1 = big ? 256 : LA_TOK1;
-    const int nblk = (n + tok1 - 1) / tok1;
+    const int nblk = image ? 0 : (n + tok1 - 1) / tok1;
     const size_t lds2 = (size_t)(LA_TOK2 * (C + 4) + LA_TOK2 + LA_HEADS * 32 * (C + 4)) * 4;
     static LdsOptIn lds_flag;
     if (lds_opt_in(lds_flag, reinterpret_cast<const void*>(linattn_out_fused_kernel<C>), 1)) return 1;
     const bool timed = prof::enabled();
     const double tokens = (double)B * n;
-    if (timed && prof::begin("linattn_ctx_fused_kernel", 2.0 * tokens * (2.0 * LA_HID * C + LA_HID * LA_DH),
-                             4.0 * tokens * C, s))
-        return 1;
-    if (big ? launch_ctx<C, (C <= 64 ? 256 : LA_TOK1)>(w, x, ws, B, n, nblk, s)
-            : launch_ctx<C, LA_TOK1>(w, x, ws, B, n, nblk, s))
-        return 1;
-    if (timed && prof::end(s)) return 1;
     float* ctxn = ws + (size_t)B * nblk * LA_HEADS * LA_CTX;  // M = W_out ctx^T, lane-packed
-    hipLaunchKernelGGL(linattn_ctx_reduce_kernel<C>, dim3(LA_HEADS, B), dim3(256), 0, s, ws, w.wo_raw, ctxn, nblk);
-    DM_CHECK_HIP(hipGetLastError());
+    if (image) {
+        // k and P^T per token, then per image W'_v P^T and W_out ctx^T; one read of x
+        if (timed && prof::begin("linattn_ctx_image_kernel",
+                                 2.0 * tokens * (2.0 * LA_HID * C) + (double)B * 2.0 * (2.0 * LA_HID * LA_DH * C),
+                                 4.0 * tokens * C, s))
+            return 1;
+        if (launch_ctx_image<C>(w, x, ctxn, B, n, s)) return 1;
+        if (timed && prof::end(s)) return 1;
+    } else {
+        if (timed && prof::begin("linattn_ctx_fused_kernel", 2.0 * tokens * (2.0 * LA_HID * C + LA_HID * LA_DH),
+                                 4.0 * tokens * C, s))
+            return 1;
+        if (big ? launch_ctx<C, (C <= 64 ? 256 : LA_TOK1)>(w, x, ws, B, n, nblk, s)
+                : launch_ctx<C, LA_TOK1>(w, x, ws, B, n, nblk, s))
+            return 1;
+        if (timed && prof::end(s)) return 1;
+        if (timed && prof::begin("linattn_ctx_reduce_kernel", (double)B * 2.0 * LA_HID * LA_DH * C,
+                                 4.0 * B * ((double)nblk * LA_HEADS * LA_CTX + LA_HID * C + LA_HID * C), s))
+            return 1;
+        hipLaunchKernelGGL(linattn_ctx_reduce_kernel<C>, dim3(LA_HEADS, B), dim3(256), 0, s, ws, w.wo_raw, ctxn, nblk);
+        DM_CHECK_HIP(hipGetLastError());
+        if (timed && prof::end(s)) return 1;
+    }
     if (timed && prof::begin("linattn_out_fused_kernel", 2.0 * tokens * (2.0 * LA_HID * C + LA_HID * LA_DH),
                              8.0 * tokens * C, s))
         return 1;
