@@ -51,6 +51,7 @@ EXPORTS = (
     "dm_unet_train_dropout", "dm_op_dropout_mask",
     "dm_op_conv2d_bwd", "dm_op_downsample_bwd", "dm_op_block_bwd", "dm_op_rmsnorm_bwd", "dm_op_linear_attention_bwd",
     "dm_op_attention_bwd", "dm_op_cross_attention", "dm_op_cross_attention_bwd",
+    "dm_op_linear_attention_core_bwd", "dm_op_attention_core_bwd",
     "dm_profile_enable", "dm_profile_read",
     "dm_unet_forward_ft", "dm_sample_edm",
     "dm_op_edm_churn_in", "dm_op_edm_euler", "dm_op_edm_heun", "dm_op_edm_dpmpp", "dm_op_edm_finalize",
@@ -323,6 +324,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_rmsnorm_bwd.argtypes = [fp, fp, fp, fp, fp, i32, i32, i32, i32, vp]
     lib.dm_op_linear_attention_bwd.argtypes = [fp] * 15 + [i32] * 6 + [vp]
     lib.dm_op_attention_bwd.argtypes = [fp] * 13 + [i32] * 6 + [vp]
+    lib.dm_op_linear_attention_core_bwd.argtypes = [fp] * 9 + [i32] * 4 + [vp]
+    lib.dm_op_attention_core_bwd.argtypes = [fp] * 7 + [i32] * 4 + [vp]
     lib.dm_op_cross_attention.argtypes = [fp] * 8 + [vp, fp] + [i32] * 7 + [vp]
     lib.dm_op_cross_attention_bwd.argtypes = [fp] * 8 + [vp] + [fp] * 9 + [i32] * 7 + [vp]
     lib.dm_profile_enable.argtypes = [i32]

@@ -12,6 +12,7 @@
 
 #include <algorithm>
 
+#include <cstdio>
 #include <cstdlib>
 
 namespace dm {
@@ -326,6 +327,13 @@ static int linear_attention_core(const float* qkv, const float* mem_kv, float* c
                                  hipStream_t s, float* kstats) {
     // waves per (image, head) by the sequence length alone, so that a sample's result does not depend on its batch
     const int nw = n >= 1024 ? 16 : n >= 256 ? 8 : 4;
+    const bool timed = prof::enabled();
+    char name[64];
+    if (timed) {
+        // (n + 4) tokens x DH x DH multiply-adds per (image, head); k and v read once, the context written once
+        snprintf(name, sizeof(name), "linattn_ctx_mfma_kernel<%d,%d>", nw, DH);
+        if (prof::begin(name, 2.0 * B * heads * (n + 4.0) * DH * DH, 4.0 * B * heads * (2.0 * n * DH + DH * DH), s)) return 1;
+    }
     if (nw == 16)
         hipLaunchKernelGGL((linattn_ctx_mfma_kernel<16, DH>), dim3(heads, B), dim3(1024), 0, s, qkv, mem_kv, ctx_ws, kstats,
                            n, heads);
@@ -336,10 +344,16 @@ static int linear_attention_core(const float* qkv, const float* mem_kv, float* c
         hipLaunchKernelGGL((linattn_ctx_mfma_kernel<4, DH>), dim3(heads, B), dim3(256), 0, s, qkv, mem_kv, ctx_ws, kstats, n,
                            heads);
     DM_CHECK_HIP(hipGetLastError());
+    if (timed && prof::end(s)) return 1;
     DM_REQUIRE(B <= 65535, "LinearAttention: batch");
+    if (timed) {
+        snprintf(name, sizeof(name), "linattn_out_mfma_kernel<%d>", DH);
+        if (prof::begin(name, 2.0 * B * heads * (double)n * DH * DH, 4.0 * B * heads * (2.0 * n * DH + DH * DH), s)) return 1;
+    }
     hipLaunchKernelGGL(linattn_out_mfma_kernel<DH>, dim3((n + 63) / 64, heads, B), dim3(64), 0, s, qkv, ctx_ws, out, n, heads,
                        1.0f / sqrtf((float)DH));
     DM_CHECK_HIP(hipGetLastError());
+    if (timed && prof::end(s)) return 1;
     return 0;
 }
 
@@ -504,19 +518,33 @@ static int attention_core(const float* q, int ldq, const float* k, const float* 
     // beyond ~320 keys the tiled form is also the faster one (tools/attn_time.py: 512 tokens 1.29 vs 2.79 ms per layer at
     // B=64, equal at 256): the LDS-resident kernel re-stages all K / V of an (image, head) in every query block
     static const int tiled_min = env_int("DM_ATTN_TILED_MIN", 320);
+    const bool timed = prof::enabled();
+    // q k^T and P v: 2 x (nq x ntok x DH) multiply-adds per (image, head); q, k, v read once, out written once
+    const double flops = 4.0 * B * heads * (double)nq * ntok * DH, bytes = 4.0 * B * heads * (2.0 * nq + 2.0 * nk) * DH;
+    char name[64];
     if (lds > 160 * 1024 || ntok > tiled_min || force_tiled) {
         DM_REQUIRE(B <= 65535 && heads <= 65535 && ldo % 4 == 0, "attention: batch / row stride");
+        if (timed) {
+            snprintf(name, sizeof(name), "attention_core_tiled_kernel<%d>", DH);
+            if (prof::begin(name, flops, bytes, s)) return 1;
+        }
         hipLaunchKernelGGL(attention_core_tiled_kernel<DH>, dim3((nq + 63) / 64, heads, B), dim3(64), 0, s, q, ldq, k, v,
                            ldk, mem_k, mem_v, n_mem, out, ldo, nq, nk, scale);
         DM_CHECK_HIP(hipGetLastError());
+        if (timed && prof::end(s)) return 1;
         return 0;
     }
     static LdsOptIn lds_flag;
     if (lds_opt_in(lds_flag, reinterpret_cast<const void*>(attention_core_kernel<DH>), 1)) return 1;
     const int qblocks = std::max(1, std::min((nq + 3) / 4, (512 + heads * B - 1) / (heads * B)));
+    if (timed) {
+        snprintf(name, sizeof(name), "attention_core_kernel<%d>", DH);
+        if (prof::begin(name, flops, bytes, s)) return 1;
+    }
     hipLaunchKernelGGL(attention_core_kernel<DH>, dim3(heads, B, qblocks), dim3(256), lds, s, q, ldq, k, v, ldk, mem_k,
                        mem_v, n_mem, out, ldo, nq, nk, scale);
     DM_CHECK_HIP(hipGetLastError());
+    if (timed && prof::end(s)) return 1;
     return 0;
 }
 

@@ -14,6 +14,7 @@
 #include "dm_common.h"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 namespace dm {
@@ -336,15 +337,34 @@ static int linear_attention_core_bwd(const float* qkv, const float* mem_kv, cons
     const int nblk = (n + 63) / 64;
     const float scale = 1.0f / sqrtf((float)DH);
     float* stats = ws + (size_t)B * nblk * heads * DH * DH;
+    const bool timed = prof::enabled();
+    // per (image, head): a (tokens x DH) x (DH x DH) product is n * DH * DH multiply-adds
+    const double bh = (double)B * heads, mm = 2.0 * bh * n * DH * DH;
+    char name[64];
+    if (timed) {  // dqs and the dctx shares; q, dout read, dq and the shares written
+        snprintf(name, sizeof(name), "linattn_bwd_q_mfma_kernel<%d>", DH);
+        if (prof::begin(name, 2.0 * mm, 4.0 * bh * (3.0 * n * DH + (1.0 + nblk) * DH * DH), s)) return 1;
+    }
     hipLaunchKernelGGL(linattn_bwd_q_mfma_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ctx, dout, dqkv, ws, n, heads,
                        scale);
     DM_CHECK_HIP(hipGetLastError());
+    if (timed && prof::end(s)) return 1;
+    if (timed) {
+        snprintf(name, sizeof(name), "linattn_bwd_stats_kernel<%d>", DH);
+        if (prof::begin(name, bh * (nblk + 2.0 + 4.0 * NMEM) * DH * DH, 4.0 * bh * (nblk + 2.0) * DH * DH, s)) return 1;
+    }
     hipLaunchKernelGGL(linattn_bwd_stats_kernel<DH>, dim3(heads, B), dim3(256), 0, s, mem_kv, ctx, ws, nblk, stats, dmem_part,
                        kstats, heads);
     DM_CHECK_HIP(hipGetLastError());
+    if (timed && prof::end(s)) return 1;
+    if (timed) {  // dks and dv; k, v read, dk, dv written
+        snprintf(name, sizeof(name), "linattn_bwd_kv_mfma_kernel<%d>", DH);
+        if (prof::begin(name, 2.0 * mm, 4.0 * bh * (4.0 * n * DH + DH * DH), s)) return 1;
+    }
     hipLaunchKernelGGL(linattn_bwd_kv_mfma_kernel<DH>, dim3(nblk, heads, B), dim3(64), 0, s, qkv, ws, nblk, stats, dqkv, n,
                        heads);
     DM_CHECK_HIP(hipGetLastError());
+    if (timed && prof::end(s)) return 1;
     return 0;
 }
 
@@ -376,6 +396,18 @@ int launch_linear_attention_core_bwd(const float* qkv, const float* mem_kv, cons
 __device__ __forceinline__ float score_minus(float sc, float scale, float m) {
 #pragma clang fp contract(off)
     return sc * scale - m;
+}
+// The row statistics l_i = sum_j e_ij and D_i = sum_j e_ij dP_ij / l_i are compensated (Kahan) sums.  They were single fp32
+// accumulators over all keys, and their rounding does not stay small where dq_i and dk_j cancel: with dS_ij = P_ij (dP_ij - D_i)
+// the sum over j of dS_ij is D_i's and l_i's error, and it multiplies whatever the key rows share -- a common offset of k (k + 100
+// on every token: the worst dq row was 2.4e-4 of the RMS row norm where the same arithmetic with exact sums gives 3e-5), or
+// one key far larger than the others (4.8e-4 against 1.7e-5).  tests/test_hip_attn_cores.py holds both inputs.
+__device__ __forceinline__ void kahan_add(float& sum, float& comp, float x) {
+#pragma clang fp contract(off)
+    const float y = x - comp;
+    const float t = sum + y;
+    comp = (t - sum) - y;
+    sum = t;
 }
 
 struct AttnBwdParams {
@@ -430,7 +462,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
             q[d] = Qs[i * (DH + 1) + d];
             dov[d] = Ds[i * (DH + 1) + d];
         }
-        float m = -INFINITY, l = 0.f, D = 0.f, linv;
+        float m = -INFINITY, l = 0.f, D = 0.f, lc = 0.f, Dc = 0.f, linv;
         float dq[DH];
 #pragma unroll
         for (int d = 0; d < DH; ++d) dq[d] = 0.f;
@@ -448,8 +480,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const AttnBwdParams p) {
                 dp = fmaf(dov[d], Vs[j * (DH + 1) + d], dp);
             }
             const float e = __expf(score_minus(sc, scale, m));
-            l += e;
-            D += e * dp;
+            kahan_add(l, lc, e);
+            kahan_add(D, Dc, e * dp);
         }
         linv = 1.0f / l;
         D *= linv;
@@ -569,13 +601,13 @@ __global__ __launch_bounds__(256) void attn_bwd_pairs_kernel(const AttnBwdParams
     for (int i = tid; i < n; i += 256) {  // (2) row softmax, D_i, dS
         float* Pi = Pc + i * nkt;
         float* Si = Sc + i * nkt;
-        float m = -INFINITY, l = 0.f, D = 0.f;
+        float m = -INFINITY, l = 0.f, D = 0.f, lc = 0.f, Dc = 0.f;
         for (int j = 0; j < nkt; ++j) m = fmaxf(m, Pi[j]);
         for (int j = 0; j < nkt; ++j) {
             const float e = __expf(Pi[j] - m);
             Pi[j] = e;
-            l += e;
-            D += e * Si[j];
+            kahan_add(l, lc, e);
+            kahan_add(D, Dc, e * Si[j]);
         }
         const float linv = 1.0f / l;
         D *= linv;
@@ -643,7 +675,7 @@ __global__ __launch_bounds__(64) void attn_bwd_q_tiled_kernel(const AttnBwdParam
         q[d] = ok ? p.q[((size_t)b * n + i) * p.ldq + h * DH + d] : 0.f;
         dov[d] = ok ? p.dout[((size_t)b * n + i) * hid + h * DH + d] : 0.f;
     }
-    float m = -INFINITY, l = 0.f, D = 0.f, dq[DH];
+    float m = -INFINITY, l = 0.f, D = 0.f, lc = 0.f, Dc = 0.f, dq[DH];
 #pragma unroll
     for (int d = 0; d < DH; ++d) dq[d] = 0.f;
     for (int pass = 0; pass < 3; ++pass) {
@@ -674,8 +706,8 @@ __global__ __launch_bounds__(64) void attn_bwd_q_tiled_kernel(const AttnBwdParam
                     m = fmaxf(m, sc * scale);
                 } else if (pass == 1) {
                     const float e = __expf(score_minus(sc, scale, m));
-                    l += e;
-                    D += e * dp;
+                    kahan_add(l, lc, e);
+                    kahan_add(D, Dc, e * dp);
                 } else {
                     const float dS = __expf(score_minus(sc, scale, m)) * linv * (dp - D);
 #pragma unroll
@@ -776,26 +808,52 @@ size_t attn_bwd_ws_floats(int B, int nq, int nk, int n_mem, int heads, int dh) {
 template <int DH>
 static int launch_attn_bwd(const AttnBwdParams& p, int B, float* ws, hipStream_t s) {
     const size_t lds = attn_bwd_lds_bytes(p.nq, p.nk, p.n_mem, DH);
+    const bool timed = prof::enabled();
+    // scores, dP, dq, dk, dv: 5 x (nq x nkt x DH) multiply-adds per (image, head) (the query / key phases each form the first
+    // two); q, k, v, dout read and dq, dk, dv written once
+    const double bh = (double)B * p.heads, nkt = p.nk + p.n_mem;
+    const double mm = 2.0 * bh * p.nq * nkt * DH, bytes = 4.0 * bh * (3.0 * p.nq + 4.0 * p.nk) * DH;
+    char name[64];
     if (attn_bwd_tiled(p.nq, p.nk, p.n_mem, DH)) {
         DM_REQUIRE(ws != nullptr, "attention backward: the tiled form needs its statistics workspace (attn_bwd_ws_floats)");
         DM_REQUIRE(B <= 65535 && p.heads <= 65535, "attention backward: batch");
+        if (timed) {
+            snprintf(name, sizeof(name), "attn_bwd_q_tiled_kernel<%d>", DH);
+            if (prof::begin(name, 3.0 * mm, 0.5 * bytes, s)) return 1;
+        }
         hipLaunchKernelGGL(attn_bwd_q_tiled_kernel<DH>, dim3((p.nq + 63) / 64, p.heads, B), dim3(64), 0, s, p, ws);
         DM_CHECK_HIP(hipGetLastError());
+        if (timed && prof::end(s)) return 1;
+        if (timed) {
+            snprintf(name, sizeof(name), "attn_bwd_kv_tiled_kernel<%d>", DH);
+            if (prof::begin(name, 4.0 * mm, 0.5 * bytes, s)) return 1;
+        }
         hipLaunchKernelGGL(attn_bwd_kv_tiled_kernel<DH>, dim3((p.nk + p.n_mem + 63) / 64, p.heads, B), dim3(64), 0, s, p, ws);
         DM_CHECK_HIP(hipGetLastError());
+        if (timed && prof::end(s)) return 1;
         return 0;
     }
     if (attn_bwd_cached(p.nq, p.nk, p.n_mem)) {
         static LdsOptIn flagp;
         if (lds_opt_in(flagp, reinterpret_cast<const void*>(attn_bwd_pairs_kernel<DH>), 1)) return 1;
+        if (timed) {
+            snprintf(name, sizeof(name), "attn_bwd_pairs_kernel<%d>", DH);
+            if (prof::begin(name, 5.0 * mm, bytes, s)) return 1;
+        }
         hipLaunchKernelGGL(attn_bwd_pairs_kernel<DH>, dim3(p.heads, B), dim3(256), lds, s, p);
         DM_CHECK_HIP(hipGetLastError());
+        if (timed && prof::end(s)) return 1;
         return 0;
     }
     static LdsOptIn flag;
     if (lds_opt_in(flag, reinterpret_cast<const void*>(attn_bwd_kernel<DH>), 1)) return 1;
+    if (timed) {
+        snprintf(name, sizeof(name), "attn_bwd_kernel<%d>", DH);
+        if (prof::begin(name, 7.0 * mm, bytes, s)) return 1;
+    }
     hipLaunchKernelGGL(attn_bwd_kernel<DH>, dim3(p.heads, B), dim3(256), lds, s, p);
     DM_CHECK_HIP(hipGetLastError());
+    if (timed && prof::end(s)) return 1;
     return 0;
 }
 

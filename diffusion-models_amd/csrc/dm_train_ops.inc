@@ -292,6 +292,59 @@ int dm_op_attention_bwd(const float* x, const float* norm_g, const float* mem_kv
                        d_b_out, nullptr, B, C, H, W, heads, dim_head, stream);
 }
 
+/* The two attention cores of the training step on their own: the forward core as t_attn launches it (LinearAttention: with
+ * the key statistics), then the backward core and the column sum over the images as t_attn_bwd does.  qkv, dout, out and
+ * dqkv are token rows, the layout the kernels take, and every output the caller passes is written by the kernels
+ * themselves (no copy in between): a stray row or an unwritten column shows in the caller's buffer.  An output that is
+ * NULL lives in the NaN-filled arena instead. */
+int dm_op_linear_attention_core_bwd(const float* qkv, const float* mem_kv, const float* dout, float* out, float* ctx,
+                                    float* kstats, float* dqkv, float* dmem_part, float* d_mem_kv, int B, int n, int heads,
+                                    int dim_head, void* stream) {
+    DM_REQUIRE(qkv && mem_kv && dout, "null argument");
+    DM_REQUIRE(dim_head == 32 || dim_head == 64, "dim_head: the attention kernels support 32 and 64");
+    DM_REQUIRE(B > 0 && n > 0 && heads >= 1 && heads <= 16, "linear_attention_core_bwd: positive sizes, 1..16 heads");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return run_op(s, [&](Arena& A) -> int {
+        const size_t rows = (size_t)B * n, hidden = (size_t)heads * dim_head, nmem = 2 * hidden * 4;
+        float* o = out ? out : A.alloc(rows * hidden);
+        float* cx = ctx ? ctx : A.alloc((size_t)B * hidden * dim_head);
+        float* kst = kstats ? kstats : A.alloc((size_t)B * 2 * hidden);
+        float* dq = dqkv ? dqkv : A.alloc(rows * 3 * hidden);
+        float* dmem = dmem_part ? dmem_part : A.alloc((size_t)B * nmem);
+        float* dm_sum = d_mem_kv ? d_mem_kv : A.alloc(nmem);
+        float* cw = A.alloc(colsum_ws_floats(B, (int)nmem));
+        float* ws = A.alloc(linattn_bwd_ws_floats(B, n, heads, dim_head));
+        if (A.dry) return 0;
+        if (launch_linear_attention_core(qkv, mem_kv, cx, o, B, n, heads, dim_head, s, kst)) return 1;
+        if (launch_linear_attention_core_bwd(qkv, mem_kv, cx, dout, ws, dq, dmem, B, n, heads, dim_head, s, kst)) return 1;
+        return launch_colsum(dmem, B, (int)nmem, (int64_t)nmem, 1, cw, dm_sum, 0, s);
+    });
+}
+
+int dm_op_attention_core_bwd(const float* qkv, const float* mem_kv, const float* dout, float* out, float* dqkv,
+                             float* dmem_part, float* d_mem_kv, int B, int n, int heads, int dim_head, void* stream) {
+    DM_REQUIRE(qkv && mem_kv && dout, "null argument");
+    DM_REQUIRE(dim_head == 32 || dim_head == 64, "dim_head: the attention kernels support 32 and 64");
+    DM_REQUIRE(B > 0 && n > 0 && heads >= 1, "attention_core_bwd: positive sizes");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return run_op(s, [&](Arena& A) -> int {
+        const size_t rows = (size_t)B * n, hidden = (size_t)heads * dim_head, nmem = 2 * hidden * 4;
+        float* o = out ? out : A.alloc(rows * hidden);
+        float* dq = dqkv ? dqkv : A.alloc(rows * 3 * hidden);
+        float* dmem = dmem_part ? dmem_part : A.alloc((size_t)B * nmem);
+        float* dm_sum = d_mem_kv ? d_mem_kv : A.alloc(nmem);
+        float* cw = A.alloc(colsum_ws_floats(B, (int)nmem));
+        float* ws = A.alloc(attn_bwd_ws_floats(B, n, n, 4, heads, dim_head));
+        if (A.dry) return 0;
+        const int hid = (int)hidden;
+        if (launch_attention_core(qkv, 3 * hid, qkv + hid, qkv + 2 * hid, 3 * hid, mem_kv, mem_kv + hidden * 4, 4, o, hid, B, n, n,
+                                  heads, dim_head, 1.0f / sqrtf((float)dim_head), s))
+            return 1;
+        if (launch_attention_core_bwd(qkv, mem_kv, dout, dq, dmem, ws, B, n, heads, dim_head, s)) return 1;
+        return launch_colsum(dmem, B, (int)nmem, (int64_t)nmem, 1, cw, dm_sum, 0, s);
+    });
+}
+
 /* CrossAttention (DD/denoising_diffusion_text_conditional.py:54-78) as the text-conditional U-Net runs it: the forward is
  * run_cross (one-token algebra included), the backward t_cross then t_cross_bwd (always the general path; y_out is its
  * forward result).  The forward sits here, next to its backward, because both build the layer on an OpTrain handle. */

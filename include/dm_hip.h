@@ -534,6 +534,18 @@ int dm_op_linear_attention_bwd(const float* x, const float* norm_g, const float*
 int dm_op_attention_bwd(const float* x, const float* norm_g, const float* mem_kv, const float* w_qkv, const float* w_out,
                         const float* b_out, const float* dy, float* dx, float* d_norm_g, float* d_mem_kv, float* d_w_qkv,
                         float* d_w_out, float* d_b_out, int B, int C, int H, int W, int heads, int dim_head, void* stream);
+/* The attention cores of the training step alone (no norm, no projection): the forward core as the training forward runs
+ * it, the backward core, and the sum of the per-image memory-token gradients.  Token rows, not NCHW:
+ * qkv, dqkv (B, n, 3*heads*dim_head) = [q(h,d) | k(h,d) | v(h,d)] per token;  dout, out (B, n, heads*dim_head).
+ * LinearAttention: mem_kv, d_mem_kv (2, heads, dim_head, 4); ctx (B, heads, dim_head, dim_head); kstats (B, heads, 2, dim_head)
+ * = per column of k the maximum over the n + 4 tokens and the sum of exp(k - max); dmem_part (B, 2, heads, dim_head, 4).
+ * Attention: mem_kv, d_mem_kv (2, heads, 4, dim_head); dmem_part (B, 2, heads, 4, dim_head).
+ * Every output is optional (NULL) and is written by the kernels directly, without a copy. */
+int dm_op_linear_attention_core_bwd(const float* qkv, const float* mem_kv, const float* dout, float* out, float* ctx,
+                                    float* kstats, float* dqkv, float* dmem_part, float* d_mem_kv, int B, int n, int heads,
+                                    int dim_head, void* stream);
+int dm_op_attention_core_bwd(const float* qkv, const float* mem_kv, const float* dout, float* out, float* dqkv,
+                             float* dmem_part, float* d_mem_kv, int B, int n, int heads, int dim_head, void* stream);
 /* CrossAttention of the text-conditional U-Net (DD/denoising_diffusion_text_conditional.py:54-78), forward and backward,
  * through the code the models run (4 heads, as there).  x, dy, out, y_out, dx (B, C, H, W); ctx (B, m, E); weights in the
  * reference layout: w_q (4*dim_head, C), w_k / w_v (4*dim_head, E), w_out (C, 4*dim_head), b_out (C), out_g (C).

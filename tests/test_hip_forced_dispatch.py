@@ -96,16 +96,22 @@ def test_training_goldens_with_one_launch_per_layer():
 def test_attention_backward_tiled_form_on_every_shape():
     """The operator-level attention backward cases and the text-conditional training step (mid_attn + CrossAttention) with the
     tiled kernels forced on the short sequences the LDS-resident kernel normally takes; and the LDS-resident kernel without
-    its score cache (the thread-per-query form longer sequences take)."""
+    its score cache (the thread-per-query form longer sequences take).  Both children also run the core-level cases of
+    tests/test_hip_attn_cores.py, whose tables hold the kernels expected under these switches, and the module-level
+    hard-input backward cases."""
+    cores = os.path.join(ROOT, "tests", "test_hip_attn_cores.py")
+    core_tests = "test_hip_attn_cores"  # -k also matches the module's name: every test of the core-level file
     env0 = dict(os.environ, DM_ATTN_BWD_NO_CACHE="1")
-    r0 = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_hip_train_ops.py"), "-q", "-x",
-                         "-m", "gpu", "-k", "test_attention_bwd", "-p", "no:cacheprovider"],
+    r0 = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_hip_train_ops.py"), cores, "-q", "-x",
+                         "-m", "gpu", "-k", "test_attention_bwd or test_linear_attention_bwd_hard_inputs or " + core_tests,
+                         "-p", "no:cacheprovider"],
                         cwd=ROOT, env=env0, capture_output=True, text=True, timeout=600)
     assert r0.returncode == 0, r0.stdout[-4000:] + r0.stderr[-2000:]
     env = dict(os.environ, DM_ATTN_BWD_TILED="1", DM_ATTN_TILED="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_hip_train_ops.py"),
-                        os.path.join(ROOT, "tests", "test_hip_train.py"), "-q", "-x", "-m", "gpu", "-k",
-                        "test_attention_bwd or test_text_conditional_training_step", "-p", "no:cacheprovider"],
+                        os.path.join(ROOT, "tests", "test_hip_train.py"), cores, "-q", "-x", "-m", "gpu", "-k",
+                        "test_attention_bwd or test_text_conditional_training_step or " + core_tests,
+                        "-p", "no:cacheprovider"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
 

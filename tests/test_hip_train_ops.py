@@ -212,6 +212,55 @@ def test_attention_bwd(case):
     assert max(errs.values()) < TOL, errs
 
 
+def _attn_bwd_hard(full, case):
+    """x scaled by 8 and mem_kv by 4, as tests/test_hip_ops.py::test_*_hard_inputs do for the forward: saturated softmaxes in
+    the recomputing backward.  The oracle module in fp64 is the reference; per gradient tensor the limit is the rule of that
+    file's _hard_limit with this file's floor: max(TOL, 4 x the error of the same oracle in fp32 against fp64)."""
+    B, C, H, W = case
+    fn = uo.full_attention if full else uo.linear_attention
+    sd = {k: v.detach() for k, v in _attn_params(C, full, 20 if full else 10).items()}
+    sd["a.mem_kv"] = sd["a.mem_kv"] * 4
+    x, dy = seeded((B, C, H, W), 1, 8.0), seeded((B, C, H, W), 2)
+    names = ["a.norm.g", "a.mem_kv", "a.to_qkv.weight"]
+    names += ["a.to_out.weight", "a.to_out.bias"] if full else ["a.to_out.0.weight", "a.to_out.0.bias", "a.to_out.1.g"]
+
+    def grads(dtype):
+        p = {k: v.to(dtype).requires_grad_(True) for k, v in sd.items()}
+        xx = x.to(dtype).requires_grad_(True)
+        fn(p, "a", xx, 4, 32).backward(dy.to(dtype))
+        return {"dx": xx.grad, **{k: p[k].grad for k in names}}
+
+    ref, f32 = grads(torch.float64), grads(torch.float32)
+    lib = _lib.load()
+    ins = [dev(x)] + [dev(sd[k]) for k in names] + [dev(dy)]
+    dx = torch.empty(x.shape, device=DEV)
+    outs = [torch.empty(sd[k].shape, device=DEV) for k in names]
+    op = lib.dm_op_attention_bwd if full else lib.dm_op_linear_attention_bwd
+    _lib.check(op(*[_lib.ptr(t) for t in ins], _lib.ptr(dx), *[_lib.ptr(t) for t in outs], B, C, H, W, 4, 32, None))
+    got = {"dx": dx.cpu(), **{k: o.cpu() for k, o in zip(names, outs)}}
+    bad = {}
+    for k in got:
+        err, floor = rel_l2(got[k].double(), ref[k]), rel_l2(f32[k].double(), ref[k])
+        lim = max(TOL, 4 * floor)
+        print(f"{'attention' if full else 'linear_attention'} bwd hard {case} {k}: kernel {err:.3g}  fp32 oracle {floor:.3g}  "
+              f"limit {lim:.3g}")
+        if not err <= lim:
+            bad[k] = (err, lim)
+    assert not bad, bad
+
+
+# one shape per backward form: score cache (60 tokens), thread per query (256), tiled pair (575)
+@pytest.mark.parametrize("case", [(2, 64, 6, 10), (1, 128, 16, 16), (1, 32, 23, 25)])
+def test_attention_bwd_hard_inputs(case):
+    _attn_bwd_hard(True, case)
+
+
+# 256 tokens (4 blocks, 8 waves in the context kernel) and 35 (one ragged block)
+@pytest.mark.parametrize("case", [(2, 64, 16, 16), (2, 32, 5, 7)])
+def test_linear_attention_bwd_hard_inputs(case):
+    _attn_bwd_hard(False, case)
+
+
 def test_conv_backward_random_shapes():
     """Seeded random shapes through the weight-gradient kernel's tiling (ragged pixel blocks, several cin / cout tiles,
     K splits) and through whichever forward kernel the input-gradient convolution dispatches to."""
