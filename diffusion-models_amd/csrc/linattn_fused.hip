@@ -20,6 +20,9 @@
 //      k and P only (C/2 + C/2 MFMAs per 32-token tile instead of C/2 + C/2 + 16) and W'_v is applied once per image.
 //   2. linattn_out_fused_kernel  (token block, image): q = W_q x^, softmax over dim_head, z = M q + b,
 //      RMSNorm(z) * g, + x, one store.
+//   2'. linattn_out_headsum_kernel  (run of token windows, image): the form of kernel 2 from B = 32 on
+//      (la_out_headsum_form).  The waves exchange the softmaxed q through LDS and the sum over heads runs as one MFMA
+//      chain per output column tile; the operands stay in registers over a run of windows.
 //
 // MFMA bookkeeping (v_mfma_f32_32x32x2_f32, wave = head): the accumulator of one product is used DIRECTLY as an
 // operand of the next one, without any data movement: accumulator register e of lane (l, half) is element
@@ -30,6 +33,7 @@
 #include "conv_device.h"
 
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace dm {
@@ -250,16 +254,16 @@ __global__ __launch_bounds__(256) void linattn_ctx_reduce_kernel(const float* __
 // ---------------------------------------------------------------------------------------
 // The per-image form of kernel 1: one workgroup of 8 waves walks ALL tokens of its image, wave = (head, token half).
 // ---------------------------------------------------------------------------------------
-// x rows [t0, t0 + LA_TOKI) of one image -> registers.  Rows past the image read the image's last row (always in
-// bounds) and are zeroed, so the LDS window never holds anything but finite numbers.
-template <int C>
+// x rows [t0, t0 + TOK) of one image -> registers of a workgroup of NT threads.  Rows past the image read the image's
+// last row (always in bounds) and are zeroed, so the LDS window never holds anything but finite numbers.
+template <int C, int TOK = LA_TOKI, int NT = 512>
 __device__ __forceinline__ void la_image_load(const float* __restrict__ xb, int t0, int n,
-                                              f32x4 (&pre)[LA_TOKI * (C / 4) / 512]) {
+                                              f32x4 (&pre)[TOK * (C / 4) / NT]) {
     constexpr int Q = C / 4;
     const int tid = threadIdx.x;
 #pragma unroll
-    for (int i = 0; i < LA_TOKI * Q / 512; ++i) {
-        const int it = tid + 512 * i;
+    for (int i = 0; i < TOK * Q / NT; ++i) {
+        const int it = tid + NT * i;
         const int row = it / Q, q = it - row * Q;
         const int t = t0 + row;
         const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (size_t)min(t, n - 1) * C + 4 * q);
@@ -267,14 +271,56 @@ __device__ __forceinline__ void la_image_load(const float* __restrict__ xb, int 
     }
 }
 
-// registers -> LDS window, rn[t] = 1 / max(||x_t||, 1e-12) (the Q lanes that hold one row are consecutive)
-template <int C>
-__device__ __forceinline__ void la_image_store(const f32x4 (&pre)[LA_TOKI * (C / 4) / 512], float* xs, float* rn) {
-    constexpr int XS = C + 4, Q = C / 4;
-    const int tid = threadIdx.x;
+// Sums over the Q consecutive lanes that hold one row, in every one of them, for N independent values.  The same pairs
+// in the same order as the __shfl_xor butterfly, so the same bits, but on the DPP path (one v_add_f32_dpp per step, no
+// LDS round trip): xor 1 and xor 2 are quad permutes, and once a group of 4 (8) lanes agrees, the mirrored lane of the
+// 8 (16) holds what lane ^ 4 (lane ^ 8) holds.  Only the step across 16-lane rows goes through ds_bpermute.  The steps
+// are the outer loop so that the N chains fill each other's DPP wait states.
+template <int CTRL, int N>
+__device__ __forceinline__ void la_dpp_add(float (&v)[N]) {
 #pragma unroll
-    for (int i = 0; i < LA_TOKI * Q / 512; ++i) {
-        const int it = tid + 512 * i;
+    for (int i = 0; i < N; ++i)
+        v[i] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[i]), CTRL, 0xF, 0xF, false));
+}
+template <int Q, int N>
+__device__ __forceinline__ void la_row_sums(float (&v)[N]) {
+    static_assert(Q == 16 || Q == 32, "a row is 16 or 32 lanes");
+    la_dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]
+    la_dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]
+    la_dpp_add<0x141>(v);  // row_half_mirror
+    la_dpp_add<0x140>(v);  // row_mirror
+    if (Q == 32) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], 16);
+    }
+}
+
+// registers -> LDS window, rn[t] = 1 / max(||x_t||, 1e-12) (the Q lanes that hold one row are consecutive); with SS
+// (kernel 2, head-sum form) rn[t] = ||x_t||^2 and the reader takes the root, once per tile instead of once per store
+template <int C, int TOK = LA_TOKI, int NT = 512, bool SS = false>
+__device__ __forceinline__ void la_image_store(const f32x4 (&pre)[TOK * (C / 4) / NT], float* xs, float* rn) {
+    constexpr int XS = C + 4, Q = C / 4, N = TOK * Q / NT;
+    const int tid = threadIdx.x;
+    if (SS) {
+        float ss[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int it = tid + NT * i;
+            const int row = it / Q, q = it - row * Q;
+            const f32x4 v = pre[i];
+            *reinterpret_cast<f32x4*>(xs + row * XS + 4 * q) = v;
+            ss[i] = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        }
+        la_row_sums<Q>(ss);
+        if (tid % Q == 0) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) rn[(tid + NT * i) / Q] = ss[i];
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int it = tid + NT * i;
         const int row = it / Q, q = it - row * Q;
         const f32x4 v = pre[i];
         *reinterpret_cast<f32x4*>(xs + row * XS + 4 * q) = v;
@@ -538,6 +584,194 @@ __global__ __launch_bounds__(256) void linattn_out_fused_kernel(const float* __r
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// The head-sum form of kernel 2: z = sum_h M_h p_h is ONE product with K = heads * 32, so the sum over heads runs on
+// the MFMA instead of through four C x 32 LDS buffers and the vector ALUs.
+// ---------------------------------------------------------------------------------------
+// A workgroup walks a run of token windows of one image (LA_OUTW floats of x per window: 64 tokens at C = 64, 32 at
+// C = 128) with every operand resident in registers: W'_q of its head, M of its output column tile for all four heads,
+// bias and gain.  Per window:
+//   A. wave h forms q_h = W'_q x^ and the softmax over d for each 32-token tile, as the other form does, and stores
+//      p_h to LDS as [head][tile][e >> 2][lane][e & 3]: 4 KB per head and tile, b128 stores and loads with the lanes
+//      contiguous (conflict-free without padding).                                                       -- barrier --
+//   B. wave w owns an output column tile instead of a head: mt = w at C = 128, (mt, tile) = (w & 1, w >> 1) at C = 64.
+//      It accumulates sum_h M_h[mt] p_h, 4 heads x 16 MFMAs into one accumulator that starts from the bias; step
+//      (h, e) takes the M register the other form takes and as B operand exactly the value lane (token, half) of wave
+//      h held in accumulator register e.  The MFMA count per token is unchanged.  The tile ends as channel rows on the
+//      registers and the token on the lane: the sum of squares over the tile's 32 channels (16 FMAs and one
+//      shfl_xor 32) goes to ssb[mt][token], and z to ONE [tokens][C + 4] buffer.  (At C = 64 that buffer lies over p behind one more barrier, which keeps
+//      the workgroup under 80 KB.)                                                                       -- barrier --
+//   C. all threads: RMSNorm over the channels with the column tiles' sums added in tile order, gain, + x, and the
+//      coalesced 16-byte row stores of the other form.
+// The rows of the next window are loaded into registers before A and written to the other LDS window after C, one
+// barrier per window, as linattn_ctx_image_kernel does.  Every token is computed for itself (there is no sum over
+// tokens in this kernel), in an order that is fixed by the code: the result of an image depends neither on the batch
+// nor on the run length nor on where the image sits.
+// Beside f32-input MFMAs every other instruction of a SIMD's waves costs issue time instead of filling gaps (DESIGN
+// section 6), so the loop is also kept short: the window holds ||x_t||^2 and root and reciprocal are taken once per
+// tile, the window store's row sums run on DPP, the softmax maximum is formed from the raw products, and whole
+// windows take paths without row clamps or masks.
+static constexpr int LA_OUTW = 4096;  // floats of x per LDS window of the head-sum form
+
+template <int C>
+__global__ __launch_bounds__(256, 2) void linattn_out_headsum_kernel(const float* __restrict__ x, const LinAttnFused w,
+                                                                     const float* __restrict__ mz,
+                                                                     float* __restrict__ y, int n, int run, int add_x,
+                                                                     float scale) {
+    constexpr int G = C / 8, XS = C + 4, MT = C / 32, Q = C / 4, TW = LA_OUTW / C, TILES = TW / 32, NP = TW * Q / 256;
+    constexpr int PB = LA_HEADS * TILES * 16 * 64;  // floats of p per window
+    constexpr bool ZALIAS = C == 64;
+    static_assert(!ZALIAS || TW * XS <= PB, "z does not fit over p");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* rnb = smem + 2 * TW * XS;                // [2][TW]
+    float* pb = rnb + 2 * TW;                       // [heads][TILES][4][64][4]
+    float* zb = ZALIAS ? pb : pb + PB;              // [TW][XS]
+    float* ssb = (ZALIAS ? pb + PB : zb + TW * XS);  // [MT][TW]
+    const int b = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int mt = ZALIAS ? (wv & 1) : wv, zt = ZALIAS ? (wv >> 1) : 0;  // phase B: column tile, token tile
+    const float* xb = x + (size_t)b * n * C;
+    const int nw = (n + TW - 1) / TW;
+    const int w0 = blockIdx.x * run, w1 = min(nw, w0 + run);
+
+    // resident operands, issued before anything waits
+    f32x4 wq[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) wq[g] = *reinterpret_cast<const f32x4*>(w.wq + (((size_t)wv * G + g) * 64 + lane) * 4);
+    f32x4 mreg[LA_HEADS][4];
+#pragma unroll
+    for (int hh = 0; hh < LA_HEADS; ++hh)
+#pragma unroll
+        for (int e4 = 0; e4 < 4; ++e4)
+            mreg[hh][e4] = *reinterpret_cast<const f32x4*>(
+                mz + ((((size_t)b * LA_HEADS + hh) * MT + mt) * 4 + e4) * 64 * 4 + lane * 4);
+    f32x16 bias;  // in the accumulator's order: the chain of phase B starts from it
+#pragma unroll
+    for (int m4 = 0; m4 < 4; ++m4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(w.bias + 32 * mt + 8 * m4 + 4 * lh);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) bias[4 * m4 + i] = v[i];
+    }
+    const int q4 = tid & (Q - 1);  // 256 is a multiple of Q: a thread keeps its channel quad in phase C
+    const f32x4 og = *reinterpret_cast<const f32x4*>(w.og + 4 * q4);
+
+    f32x4 pre[NP];
+    la_image_load<C, TW, 256>(xb, w0 * TW, n, pre);
+    la_image_store<C, TW, 256, true>(pre, smem, rnb);
+    __syncthreads();
+
+    for (int wi = w0; wi < w1; ++wi) {
+        const bool more = wi + 1 < w1;
+        if (more) {
+            if ((wi + 2) * TW <= n) {  // a whole window: nothing to clamp or to zero
+                const float* xw = xb + ((size_t)(wi + 1) * TW + tid / Q) * C + 4 * q4;
+#pragma unroll
+                for (int i = 0; i < NP; ++i) pre[i] = *reinterpret_cast<const f32x4*>(xw + (size_t)i * (256 / Q) * C);
+            } else {
+                la_image_load<C, TW, 256>(xb, (wi + 1) * TW, n, pre);
+            }
+        }
+        const int buf = (wi - w0) & 1;
+        const float* xs = smem + buf * TW * XS;
+        const float* rn = rnb + buf * TW;
+        const int t0 = wi * TW;
+        const int nt = min(TW, n - t0);
+
+        // A. q (d x tokens) = W'_q (d x C) x^T: A = weights in registers, B = x row of token l31 from LDS
+#pragma unroll
+        for (int st = 0; st < TILES; ++st) {
+            if (st * 32 >= nt) break;
+            f32x16 qacc;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) qacc[e] = 0.f;
+            const float* xr = xs + (st * 32 + l31) * XS + 4 * lh;
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(xr + 8 * g);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) qacc = __builtin_amdgcn_mfma_f32_32x32x2f32(wq[g][s], a[s], qacc, 0, 0, 0);
+            }
+            // softmax over d (:185) for token l31: 16 values here, 16 in the other lane half; then * scale (:188)
+            const float r = 1.0f / fmaxf(sqrtf(rn[st * 32 + l31]), 1e-12f);  // the window holds ||x_t||^2
+            float m = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) m = fmaxf(m, qacc[e]);
+            m = fmaxf(m, __shfl_xor(m, 32));
+            m *= r;  // = max_e fl(q_e r): r > 0 and rounding is monotonic, so the 16 products need not be formed for it
+            float ssum = 0.f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                qacc[e] = __expf(qacc[e] * r - m);
+                ssum += qacc[e];
+            }
+            ssum += __shfl_xor(ssum, 32);
+            const float inv = scale / ssum;
+            float* pw = pb + (size_t)(wv * TILES + st) * 16 * 64 + lane * 4;
+#pragma unroll
+            for (int e4 = 0; e4 < 4; ++e4)
+                *reinterpret_cast<f32x4*>(pw + e4 * 64 * 4) = make_f32x4(qacc[4 * e4] * inv, qacc[4 * e4 + 1] * inv,
+                                                                          qacc[4 * e4 + 2] * inv, qacc[4 * e4 + 3] * inv);
+        }
+        __syncthreads();
+
+        // B. z tile (32 channels x 32 tokens) = sum over heads and d of M p; token tiles past the image are skipped
+        const bool live = zt * 32 < nt;
+        f32x16 zacc;
+        float ss = 0.f;
+        if (live) {
+            zacc = bias;
+#pragma unroll
+            for (int hh = 0; hh < LA_HEADS; ++hh) {
+                const float* pr = pb + (size_t)(hh * TILES + zt) * 16 * 64 + lane * 4;
+#pragma unroll
+                for (int e4 = 0; e4 < 4; ++e4) {
+                    const f32x4 p = *reinterpret_cast<const f32x4*>(pr + e4 * 64 * 4);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        zacc = __builtin_amdgcn_mfma_f32_32x32x2f32(mreg[hh][e4][i], p[i], zacc, 0, 0, 0);
+                }
+            }
+            // register e = channel 32*mt + row_of(e, lh) of token zt*32 + l31
+#pragma unroll
+            for (int e = 0; e < 16; ++e) ss = fmaf(zacc[e], zacc[e], ss);
+            ss += __shfl_xor(ss, 32);
+        }
+        if (ZALIAS) __syncthreads();  // every wave has read p before z is written over it
+        if (live) {
+            float* zr = zb + (zt * 32 + l31) * XS + 32 * mt + 4 * lh;
+#pragma unroll
+            for (int m4 = 0; m4 < 4; ++m4)
+                *reinterpret_cast<f32x4*>(zr + 8 * m4) =
+                    make_f32x4(zacc[4 * m4], zacc[4 * m4 + 1], zacc[4 * m4 + 2], zacc[4 * m4 + 3]);
+            if (lh == 0) ssb[mt * TW + zt * 32 + l31] = ss;
+        }
+        __syncthreads();
+
+        // C. RMSNorm over channels (to_out[1], :170), + x, store
+        auto rows_out = [&](auto whole) {
+            float* yw = y + ((size_t)b * n + t0 + tid / Q) * C + 4 * q4;
+#pragma unroll
+            for (int i = 0; i < NP; ++i) {
+                const int tok = tid / Q + i * (256 / Q);
+                if (whole.value || tok < nt) {
+                    f32x4 z = *reinterpret_cast<const f32x4*>(zb + tok * XS + 4 * q4);
+                    float sq = ssb[tok];
+#pragma unroll
+                    for (int m = 1; m < MT; ++m) sq += ssb[m * TW + tok];
+                    z = z * fast_rsq(fmaxf(sq, 1e-24f)) * og;
+                    if (add_x) z += *reinterpret_cast<const f32x4*>(xs + tok * XS + 4 * q4);
+                    *reinterpret_cast<f32x4*>(yw + (size_t)i * (256 / Q) * C) = z;
+                }
+            }
+        };
+        if (nt == TW) rows_out(std::true_type{});  // a whole window: no row is masked
+        else rows_out(std::false_type{});
+        if (more) la_image_store<C, TW, 256, true>(pre, smem + (buf ^ 1) * TW * XS, rnb + (buf ^ 1) * TW);
+        __syncthreads();  // the next window is written; p, z and this window may be rewritten
+    }
+}
+
 template <int C, int TOK1>
 static int launch_ctx(const LinAttnFused& w, const float* x, float* ws, int B, int n, int nblk, hipStream_t s) {
     const size_t lds1 = (size_t)(TOK1 * (C + 4) + TOK1) * 4;
@@ -571,6 +805,50 @@ static int launch_ctx_image(const LinAttnFused& w, const float* x, float* mz, in
     static LdsOptIn lds_flag;
     if (lds_opt_in(lds_flag, reinterpret_cast<const void*>(linattn_ctx_image_kernel<C>), 1)) return 1;
     hipLaunchKernelGGL(linattn_ctx_image_kernel<C>, dim3(B), dim3(512), lds, s, x, w, mz, n);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// Which form of kernel 2 a layer takes.  Output kernel per launch in us on MI355X, linattn_out_fused_kernel |
+// linattn_out_headsum_kernel, event-timed through tools/linattn_out_time.py (profiles/linattn_out_dispatch_table.json,
+// two runs of each; the second run is within 0.3 us, or 4 % where the launch is longer than 90 us):
+//
+//   (C, tokens)   B = 8          B = 32         B = 64         B = 128        B = 256
+//   (64, 1024)     7.0 |  5.7    14.5 | 12.8    27.4 | 25.0    51.4 | 45.4    98.9 | 85.3
+//   (64, 256)      6.6 |  5.2     7.2 |  5.4     8.5 |  6.8    15.3 | 13.3    28.6 | 25.4
+//   (128, 256)    13.6 |  5.1    14.8 |  7.3    17.2 | 14.2    36.0 | 25.6    72.4 | 44.2
+//   (128, 64)     12.5 |  4.9    12.6 |  5.3    13.1 |  5.6    13.7 |  7.3    16.9 | 14.0
+//   (64, 4096)    14.2 | 12.6    49.1 | 45.6    96.1 | 85.2   195.6 |167.8   401.4 |342.8
+//
+// The head-sum form wins at every shape and batch that was measured.  It is taken from B = 32 on, not from 8: batches
+// below 8 are not measured, and a sampler's shards must equal the unsharded batch bit for bit
+// (tests/test_hip_configs.py compares a batch of 8 with its shards of 4, 3 and 2), so the two forms, which sum the heads
+// in different orders, may not change inside that range.  Batches between the measured ones run the same grid rule.
+static constexpr int LA_OUT_WGS = 512;  // two resident workgroups on each of the chip's 256 CUs
+static bool la_out_headsum_form(int B, int n, int C) {
+#ifdef DM_LA_OUT_FORM  // the two builds behind the table (tools/linattn_out_time.py): every layer on one form
+    return DM_LA_OUT_FORM;
+#else
+    return B >= 32;
+#endif
+}
+
+// Runs of windows: as few workgroups as still give every CU two (the operands are loaded once per workgroup), cut
+// into equal runs so that the grid is one scheduling round where the batch allows it.
+template <int C>
+static int launch_out_headsum(const LinAttnFused& w, const float* x, const float* mz, float* y, int B, int n, bool add_x,
+                              hipStream_t s) {
+    constexpr int TW = LA_OUTW / C, TILES = TW / 32;
+    constexpr bool ZALIAS = C == 64;
+    const size_t lds = (size_t)(2 * TW * (C + 4) + 2 * TW + LA_HEADS * TILES * 16 * 64 + (ZALIAS ? 0 : TW * (C + 4)) +
+                                (C / 32) * TW) * 4;
+    static LdsOptIn lds_flag;
+    if (lds_opt_in(lds_flag, reinterpret_cast<const void*>(linattn_out_headsum_kernel<C>), 1)) return 1;
+    const int nw = (n + TW - 1) / TW;
+    const int per_image = std::min(nw, std::max(1, (LA_OUT_WGS + B - 1) / B));
+    const int run = (nw + per_image - 1) / per_image;
+    hipLaunchKernelGGL(linattn_out_headsum_kernel<C>, dim3((nw + run - 1) / run, B), dim3(256), lds, s, x, w, mz, y, n,
+                       run, add_x ? 1 : 0, 1.0f / sqrtf((float)LA_DH));
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -611,12 +889,17 @@ static int launch_c(const LinAttnFused& w, const float* x, float* ws, float* y, 
         DM_CHECK_HIP(hipGetLastError());
         if (timed && prof::end(s)) return 1;
     }
-    if (timed && prof::begin("linattn_out_fused_kernel", 2.0 * tokens * (2.0 * LA_HID * C + LA_HID * LA_DH),
-                             8.0 * tokens * C, s))
+    const bool headsum = la_out_headsum_form(B, n, C);
+    if (timed && prof::begin(headsum ? "linattn_out_headsum_kernel" : "linattn_out_fused_kernel",
+                             2.0 * tokens * (2.0 * LA_HID * C + LA_HID * LA_DH), 8.0 * tokens * C, s))
         return 1;
-    hipLaunchKernelGGL(linattn_out_fused_kernel<C>, dim3((n + LA_TOK2 - 1) / LA_TOK2, B), dim3(256), lds2, s, x, w,
-                       ctxn, y, n, add_x ? 1 : 0, 1.0f / sqrtf((float)LA_DH));
-    DM_CHECK_HIP(hipGetLastError());
+    if (headsum) {
+        if (launch_out_headsum<C>(w, x, ctxn, y, B, n, add_x, s)) return 1;
+    } else {
+        hipLaunchKernelGGL(linattn_out_fused_kernel<C>, dim3((n + LA_TOK2 - 1) / LA_TOK2, B), dim3(256), lds2, s, x, w,
+                           ctxn, y, n, add_x ? 1 : 0, 1.0f / sqrtf((float)LA_DH));
+        DM_CHECK_HIP(hipGetLastError());
+    }
     if (timed && prof::end(s)) return 1;
     return 0;
 }
