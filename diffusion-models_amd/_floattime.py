@@ -5,11 +5,9 @@ subclass names its U-Net field (also its ``state_dict`` prefix) and its training
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from . import _lib
+from . import _lib, _loop
 
 
 class FloatTimeDiffusion:
@@ -73,17 +71,7 @@ class FloatTimeDiffusion:
         """(seed, start image, noise rows or None) of a sampling loop.  An injected ``noise`` callable is called once for
         the start image, then ``noise_rows`` times, the reference's order of draws; without one the start image is Philox
         draw 0 and the loop draws its rows on the device."""
-        if seed is None:
-            seed = _lib.default_seed()
-        if noise is not None:
-            x_init = noise(shape).to(self.device, torch.float32).contiguous()
-            rows = [noise(shape).to(torch.float32) for _ in range(noise_rows)]
-            noise_dev = torch.stack(rows, dim=0).to(self.device).contiguous() if rows else None
-        else:
-            x_init = self._randn(shape, seed, 0, sample_offset)
-            noise_dev = None
-        assert tuple(x_init.shape) == shape, "noise() must return tensors of the sampled shape"
-        return seed, x_init, noise_dev
+        return _loop.loop_start(self, shape, noise, seed, sample_offset, [True] * noise_rows)
 
     # -- training ----------------------------------------------------------------------------------
     def _trainable(self):
@@ -122,13 +110,4 @@ class FloatTimeDiffusion:
     def _loss_call(self, args, sync):
         """Run the training entry on ``args`` (``loss_out_host`` and ``stream`` are set here): the loss as a 0-dim CPU
         tensor, or with ``sync=False`` a 0-dim device tensor (nothing waited for)."""
-        unet = self._unet
-        loss = C.c_float(0.0)
-        args.loss_out_host = C.pointer(loss) if sync else None
-        args.stream = self._stream()
-        _lib.check(getattr(self._lib, self._train_entry)(unet._handle, C.byref(args)))
-        if sync:
-            return torch.tensor(loss.value, dtype=torch.float32)
-        val = torch.empty((), device=self.device, dtype=torch.float32)
-        _lib.check(self._lib.dm_unet_train_scalar(unet._handle, 0, _lib.ptr(val), args.stream))
-        return val
+        return _loop.loss_call(self, self._unet._handle, getattr(self._lib, self._train_entry), args, sync)

@@ -30,7 +30,7 @@ from typing import Dict, List, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, _loop
 from .diffusion import DenoisingDiffusion
 from .spec import ddpm_step_table
 
@@ -105,33 +105,12 @@ class ClassifierGuidedGaussianDiffusion(DenoisingDiffusion):
             return self._guided_loop(shape, return_all_timesteps, cond_fn, guidance_kwargs, noise, seed, sample_offset)
 
     def _guided_loop(self, shape, return_all_timesteps, cond_fn, guidance_kwargs, noise, seed, sample_offset):
-        shape = tuple(int(v) for v in shape)
-        B, Cc, H, W = shape
-        assert Cc == self.channels, f"shape has {Cc} channels, the model {self.channels}"
-        f = self.model.downsample_factor
-        assert B > 0 and H % f == 0 and W % f == 0, f"shape {shape}: the sides must be divisible by {f}"
+        shape = _loop.checked_shape(self, shape)
         times, coefs = cg_step_table(self._sched)
-        n_steps = len(times)
-        if seed is None:
-            seed = _lib.default_seed()
-        sample_offset = int(sample_offset)
-        if noise is not None:
-            x_T = noise(shape).to(self.device, torch.float32).contiguous()
-            rows = torch.zeros((n_steps,) + shape, dtype=torch.float32)
-            for i, t in enumerate(times):
-                if t > 0:
-                    rows[i] = noise(shape)
-            noise_dev = rows.to(self.device).contiguous()
-        else:
-            x_T = self._randn(shape, seed, 0, sample_offset)
-            noise_dev = None
-        assert tuple(x_T.shape) == shape, f"initial state {tuple(x_T.shape)} does not match {shape}"
-        out = torch.empty(shape, device=self.device, dtype=torch.float32)
-        all_steps = (torch.empty((n_steps + 1,) + shape, device=self.device, dtype=torch.float32)
-                     if return_all_timesteps else None)
+        start = _loop.loop_start(self, shape, noise, seed, sample_offset, [t > 0 for t in times])
         # what cond_fn sees and what it returns into: allocated once, outside any inference mode, reused by every step
         mean, grad = self._guide_buffers(shape)
-        t_dev = torch.zeros((B,), device=self.device, dtype=torch.long)
+        t_dev = torch.zeros((shape[0],), device=self.device, dtype=torch.long)
         stream = torch.cuda.current_stream(self.device)
         raised: List[BaseException] = []
 
@@ -145,26 +124,18 @@ class ClassifierGuidedGaussianDiffusion(DenoisingDiffusion):
                 raised.append(e)
                 return 1
 
+        def entry(handle, args):  # what the callback caught goes first: the library's own error only says that it returned 1
+            rc = self._lib.dm_sample_classifier_guided(handle, args)
+            if raised:
+                raise raised[0]
+            return rc
+
         cb = _lib.CondCallback(callback)
-        times_arr = (C.c_int64 * n_steps)(*times)
-        coefs = coefs.contiguous()
         a = _lib.CguideArgs()
-        a.objective, a.self_condition, a.n_steps = self._objective_id, int(bool(self.self_condition)), n_steps
-        a.times_host, a.table_host = C.cast(times_arr, C.POINTER(C.c_int64)), _lib.fptr(coefs)
-        a.x_T, a.noise, a.seed, a.sample_offset = _lib.ptr(x_T), _lib.ptr(noise_dev), seed, sample_offset
+        a.objective, a.self_condition, a.n_steps = self._objective_id, int(bool(self.self_condition)), len(times)
         a.mean, a.grad, a.cond_cb, a.user = _lib.ptr(mean), _lib.ptr(grad), cb, None
-        a.out, a.all_steps = _lib.ptr(out), _lib.ptr(all_steps)
-        a.B, a.H, a.W = B, H, W
-        a.unnormalize = self._unnormalize_flag
-        a.use_graph, a.stream = 1 if self.use_graph else 0, stream.cuda_stream
-        rc = self._lib.dm_sample_classifier_guided(self.model._handle, C.byref(a))
-        if raised:
-            raise raised[0]
-        _lib.check(rc)
-        if not return_all_timesteps:
-            return out
-        ret = all_steps.permute(1, 0, 2, 3, 4).contiguous()  # (B, n_steps + 1, C, H, W) like torch.stack(imgs, dim=1)
-        return self.unnormalize(ret)
+        return _loop.loop_call(self, a, entry, shape, start, sample_offset, times, coefs, "table_host", len(times) + 1,
+                               return_all_timesteps)
 
     def _guide_buffers(self, shape):
         """(mean, grad) of ``shape``, kept between calls: their addresses are kernel arguments of the captured halves, so a

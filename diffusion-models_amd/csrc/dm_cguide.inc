@@ -32,7 +32,6 @@ static int sample_cg_impl(dm_unet* u, const dm_cguide_args* a) {
                "classifier guidance takes no image condition: U-Net input channels != channels [* 2 with self-conditioning]");
     const int B = a->B, H = a->H, W = a->W, n_steps = a->n_steps, objective = a->objective;
     if (check_hw(u, H, W)) return 1;
-    DM_CHECK_HIP(hipSetDevice(u->device));
     const int C = u->cfg.channels;
     const int64_t per = (int64_t)C * H * W, n = (int64_t)B * per;
     DM_REQUIRE(per % 4 == 0, "C * H * W must be a multiple of 4");
@@ -40,39 +39,27 @@ static int sample_cg_impl(dm_unet* u, const dm_cguide_args* a) {
     float* all_steps = a->all_steps;
     float *mean = a->mean, *grad = a->grad;
 
-    SamplerRun r;
-    if (grow_tables(u, TAB_INT | TAB_FLOAT, n_steps, 1) || run_begin(r, u, a->stream, a->use_graph)) return 1;
-    hipStream_t s = r.s;
-    // workspace: [x | model output | [x_start | x] | x_start | result | forward arena]
-    float *xbuf, *eps, *xin, *xstart, *fin;
+    // workspace: [x | result | model output | [x_start | x] | x_start | forward arena]
+    TableLoop L;
+    float *eps, *xin, *xstart;
     auto layout = [&](Arena& A) {
-        xbuf = A.alloc(n);
         eps = A.alloc(n);
         xin = self_cond ? A.alloc(2 * n) : nullptr;  // [x_start | x] per image, what init_conv reads
         xstart = self_cond ? A.alloc(n) : nullptr;   // the unguided clamped x_0 estimate of the previous step
-        fin = A.alloc(n);  // what the last step leaves for `out`: the caller's pointer stays out of the captured graph
     };
-    if (run_workspace(r, layout, [&](Arena& dry) {
-            return unet_forward_impl(u, dry, nullptr, nullptr, u->times_dev, u->state_dev, nullptr, 0, nullptr, B, H, W, s);
-        }))
-        return 1;
-    if (run_upload(r, n_steps, a->times_host, nullptr, a->table_host, a->unnormalize ? 1 : 0, a->seed,
-                   a->sample_offset * (uint64_t)per))
-        return 1;
-    const float* tab = u->edm_tab_dev;
-
-    DM_CHECK_HIP(hipMemcpyAsync(xbuf, a->x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));  // img = randn(shape)
+    if (table_loop_begin(L, u, *a, n_steps, 1, a->sample_offset * (uint64_t)per, layout)) return 1;
+    hipStream_t s = L.s;
+    float* const xbuf = L.xbuf;
     if (self_cond) DM_CHECK_HIP(hipMemsetAsync(xstart, 0, n * sizeof(float), s));  // x_self_cond = None reads as zeros
-    if (all_steps) DM_CHECK_HIP(hipMemcpyAsync(all_steps, a->x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
 
     auto front = [&](hipStream_t st) -> int {
-        r.rewind();
+        L.r.rewind();
         if (self_cond && (launch_copy_channels(xstart, xin, B, C, 2 * C, 0, H * W, st) ||
                           launch_copy_channels(xbuf, xin, B, C, 2 * C, C, H * W, st)))
             return 1;
-        if (unet_forward_impl(u, r.A, self_cond ? xin : xbuf, nullptr, u->times_dev, u->state_dev, nullptr, 0, eps, B, H, W, st))
+        if (unet_forward_impl(u, L.r.A, self_cond ? xin : xbuf, nullptr, u->times_dev, u->state_dev, nullptr, 0, eps, B, H, W, st))
             return 1;
-        return launch_cg_mean(xbuf, eps, tab, u->state_dev, STEP_ROW_STEP, per, objective, mean, xstart, n, st);
+        return launch_cg_mean(xbuf, eps, L.tab, u->state_dev, STEP_ROW_STEP, per, objective, mean, xstart, n, st);
     };
     auto host = [&](int i) -> int {
         DM_CHECK_HIP(hipStreamSynchronize(s));  // the mean is complete before cond_fn reads it
@@ -83,18 +70,15 @@ static int sample_cg_impl(dm_unet* u, const dm_cguide_args* a) {
         return 0;
     };
     auto back = [&](hipStream_t st) -> int {
-        if (launch_cg_finish(mean, grad, noise, n, tab, u->state_dev, STEP_ROW_STEP, per, xbuf, all_steps, fin, nullptr, n, st))
+        if (launch_cg_finish(mean, grad, noise, n, L.tab, u->state_dev, STEP_ROW_STEP, per, xbuf, all_steps, L.fin, nullptr, n, st))
             return 1;
         return launch_step_advance(u->state_dev, st);
     };
-    dm_unet::GraphKey key;
-    key.kind = dm_unet::GK_CG;
-    key.B = B; key.H = H; key.W = W; key.objective = objective; key.self_cond = self_cond;
-    key.noise = noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.tab = u->edm_tab_dev;
-    key.cg_mean = mean; key.cg_grad = grad;
-    if (run_steps(r, key, n_steps, front, back, nullptr, host)) return 1;
-    DM_CHECK_HIP(hipMemcpyAsync(a->out, fin, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return run_finish(r);
+    L.key.kind = dm_unet::GK_CG;
+    L.key.objective = objective; L.key.self_cond = self_cond;
+    L.key.cg_mean = mean; L.key.cg_grad = grad;
+    if (run_steps(L.r, L.key, n_steps, front, back, nullptr, host)) return 1;
+    return table_loop_end(L, a->out);
 }
 
 }  // namespace dm
@@ -119,9 +103,7 @@ int dm_op_cg_finish(const float* mean, const float* grad, const float* z, const 
                     uint64_t element_offset, float* out, float* guided_out, int B, int64_t per, void* stream) {
     DM_REQUIRE(mean && grad && c_host && out, "null argument");
     DM_REQUIRE(B > 0 && per > 0, "empty tensor");
-    DM_REQUIRE(element_offset % 4 == 0, "Philox element offset must be a multiple of 4 (one counter serves 4 elements)");
-    DM_REQUIRE(z || draw >= 1, "Philox draw 0 is the initial noise: a step's draw is its index + 1");
-    DM_REQUIRE(draw < (uint64_t(1) << 30), "draw index out of range");
+    if (draw_args_ok(z, draw, element_offset)) return 1;
     return state_op(draw_state(z != nullptr, seed, draw, element_offset), c_host, 1, stream,
                     [&](const SamplerState* st, const float* cd, hipStream_t s) {
                         return launch_cg_finish(mean, grad, z, 0, cd, st, STEP_ROW_FIRST, per, out, nullptr, nullptr, guided_out,

@@ -64,5 +64,12 @@ static SamplerState draw_state(bool injected, uint64_t seed, uint64_t draw, uint
     st.off4 = element_offset / 4;
     return st;
 }
+// what a step pass of the integer-time classes asks of the arguments draw_state reads
+static int draw_args_ok(const float* z, uint64_t draw, uint64_t element_offset) {
+    DM_REQUIRE(element_offset % 4 == 0, "Philox element offset must be a multiple of 4 (one counter serves 4 elements)");
+    DM_REQUIRE(z || draw >= 1, "Philox draw 0 is the initial noise: a step's draw is its index + 1");
+    DM_REQUIRE(draw < (uint64_t(1) << 30), "draw index out of range");
+    return 0;
+}
 
 }  // namespace dm

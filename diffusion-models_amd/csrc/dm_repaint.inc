@@ -40,61 +40,48 @@ static int sample_repaint_impl(dm_unet* u, const dm_repaint_args* a) {
     DM_REQUIRE(!a->all_steps || a->n_frames > 0, "all_steps comes with its frame count");
     if (check_hw(u, H, W)) return 1;
     if (repaint_table_ok(a->table_host, n_rows, a->n_frames, a->all_steps != nullptr)) return 1;
-    DM_CHECK_HIP(hipSetDevice(u->device));
     const int64_t per = (int64_t)C * HW, n = (int64_t)B * per, n_mask = (int64_t)B * Cm * HW;
     const uint64_t elem_off = a->sample_offset * (uint64_t)per;
     DM_REQUIRE(elem_off % 4 == 0, "sample_offset * C * H * W must be a multiple of 4");
 
     // The default loop has about 3000 rows against the 1000 steps of a DDPM run.  The buffers grow in units of 4096 rows,
     // so that a change of the resampling settings keeps their addresses, and with them the captured graph.
-    SamplerRun r;
-    if (grow_tables(u, TAB_INT | TAB_FLOAT, n_rows, 4096) || run_begin(r, u, a->stream, a->use_graph)) return 1;
-    hipStream_t s = r.s;
-    // workspace: [x | eps | gt | result | mask | forward arena]
-    float *xbuf, *eps, *gt, *fin, *mask;
+    // workspace: [x | result | eps | gt | mask | forward arena]
+    TableLoop L;
+    float *eps, *gt, *mask;
     auto layout = [&](Arena& A) {
-        xbuf = A.alloc(n);
         eps = A.alloc(n);
         gt = A.alloc(n);
-        fin = A.alloc(n);  // what the last row leaves for `out`: the caller's pointer stays out of the captured graph
         mask = A.alloc(n_mask);
     };
-    if (run_workspace(r, layout, [&](Arena& dry) {
-            return unet_forward_impl(u, dry, nullptr, nullptr, u->times_dev, u->state_dev, nullptr, 0, nullptr, B, H, W, s);
-        }))
-        return 1;
-    if (run_upload(r, n_rows, a->times_host, nullptr, a->table_host, a->unnormalize ? 1 : 0, a->seed, elem_off)) return 1;
-    const float* tab = u->edm_tab_dev;
+    if (table_loop_begin(L, u, *a, n_rows, 4096, elem_off, layout)) return 1;
+    hipStream_t s = L.s;
+    float* const xbuf = L.xbuf;
+    const float* tab = L.tab;
     RepaintNoise z;
     if (a->noise) z = RepaintNoise{a->noise, a->noise + n, a->noise + 2 * n, 3 * n};
     float* all_steps = a->all_steps;
 
-    DM_CHECK_HIP(hipMemcpyAsync(xbuf, a->x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));  // img = randn(shape)
     DM_CHECK_HIP(hipMemcpyAsync(gt, a->gt, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     DM_CHECK_HIP(hipMemcpyAsync(mask, a->mask, n_mask * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (all_steps) DM_CHECK_HIP(hipMemcpyAsync(all_steps, a->x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     // prologue: the blend in front of row 0's model call
     if (launch_repaint_step(RP_BLEND, objective, xbuf, nullptr, z, tab, 0, u->state_dev, gt, mask, Cm, per, HW, xbuf, nullptr,
                             nullptr, nullptr, n, s))
         return 1;
 
     auto row = [&](hipStream_t st) -> int {
-        r.rewind();
-        if (unet_forward_impl(u, r.A, xbuf, nullptr, u->times_dev, u->state_dev, nullptr, 0, eps, B, H, W, st)) return 1;
+        L.r.rewind();
+        if (unet_forward_impl(u, L.r.A, xbuf, nullptr, u->times_dev, u->state_dev, nullptr, 0, eps, B, H, W, st)) return 1;
         if (launch_repaint_step(RP_AUTO, objective, xbuf, eps, z, tab, 0, u->state_dev, gt, mask, Cm, per, HW, xbuf, all_steps,
-                                fin, nullptr, n, st))
+                                L.fin, nullptr, n, st))
             return 1;
         return launch_step_advance(u->state_dev, st);
     };
-    dm_unet::GraphKey key;
-    key.kind = dm_unet::GK_REPAINT;
-    key.B = B; key.H = H; key.W = W;
-    key.objective = objective;
-    key.mask_channels = Cm;
-    key.noise = a->noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.tab = u->edm_tab_dev;
-    if (run_steps(r, key, n_rows, row)) return 1;
-    DM_CHECK_HIP(hipMemcpyAsync(a->out, fin, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return run_finish(r);
+    L.key.kind = dm_unet::GK_REPAINT;
+    L.key.objective = objective;
+    L.key.mask_channels = Cm;
+    if (run_steps(L.r, L.key, n_rows, row)) return 1;
+    return table_loop_end(L, a->out);
 }
 
 }  // namespace dm

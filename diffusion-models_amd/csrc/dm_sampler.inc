@@ -1,7 +1,12 @@
 // The scaffolding every sampling loop on the C ABI runs on -- handle checks, step-table growth, stream choice, workspace,
 // state upload, the eager / captured-graph loop driver -- and the DDPM / DDIM loop behind dm_sample*.  Included by
-// dm_api.hip before dm_edm.inc, dm_ct.inc and dm_repaint.inc, whose loops use the same pieces.  A loop keeps what is its
-// own: argument checks, buffer list, prologue, step, graph key and the kernel that writes `out`.
+// dm_api.hip before dm_edm.inc, dm_ct.inc, dm_repaint.inc, dm_learned.inc, dm_weighted.inc and dm_cguide.inc, whose loops
+// use the same pieces.  A loop keeps what is its own: argument checks, buffer list, prologue, step, graph key and the
+// kernel that writes `out`.  The last four are the table-driven integer-time loops: table_loop_begin / table_loop_end
+// run the pieces for them, and they keep their argument and U-Net checks, their extra buffers, a prologue kernel, their
+// step lambdas, their extra key fields and their run_steps call.  The EDM and continuous-time loops (float time, no
+// `times`, their own kernel that writes `out`) and sample_impl (the other table pair, guidance buffers) call the pieces
+// themselves.
 
 namespace dm {
 
@@ -190,6 +195,56 @@ static int run_finish(SamplerRun& r) {
     if (r.u->mark_done(r.s)) return 1;
     if (r.own_stream) DM_CHECK_HIP(hipStreamSynchronize(r.s));
     return 0;
+}
+
+// ---- the table-driven integer-time loops ------------------------------------------------------------------------------
+// What the learned-variance, weighted-objective, classifier-guided and RePaint loops share around their steps: the times
+// next to a 16-float step table in edm_tab_dev, a U-Net called as model(x, t), the image in `xbuf` and the last step's
+// result in `fin` (the caller's `out` stays out of the captured graph).
+namespace {
+struct TableLoop {
+    SamplerRun r;
+    hipStream_t s = nullptr;  // r.s
+    int64_t n = 0;            // B * C * H * W
+    float *xbuf = nullptr, *fin = nullptr;
+    const float* tab = nullptr;  // the uploaded table
+    dm_unet::GraphKey key;       // B, H, W, noise, all_steps, ws, times, tab; the loop adds its kind and its own fields
+};
+}  // namespace
+
+// From the device choice to frame 0: tables grown by `granule` rows, the stream, the workspace ([x | result | `layout`'s
+// buffers | forward arena]), the upload of `n_rows` rows and the state, x_T in xbuf and in all_steps.  `a`: the loop's
+// argument struct, read by the field names the four share; its checks have run.
+template <class Args>
+static int table_loop_begin(TableLoop& L, dm_unet* u, const Args& a, int n_rows, int granule, uint64_t elem_off,
+                            const std::function<void(Arena&)>& layout) {
+    DM_CHECK_HIP(hipSetDevice(u->device));
+    const int B = a.B, H = a.H, W = a.W;
+    L.n = (int64_t)B * u->cfg.channels * H * W;
+    if (grow_tables(u, TAB_INT | TAB_FLOAT, n_rows, granule) || run_begin(L.r, u, a.stream, a.use_graph)) return 1;
+    L.s = L.r.s;
+    auto buffers = [&](Arena& A) {
+        L.xbuf = A.alloc(L.n);
+        L.fin = A.alloc(L.n);
+        layout(A);
+    };
+    if (run_workspace(L.r, buffers, [&](Arena& dry) {
+            return unet_forward_impl(u, dry, nullptr, nullptr, u->times_dev, u->state_dev, nullptr, 0, nullptr, B, H, W, L.s);
+        }))
+        return 1;
+    if (run_upload(L.r, n_rows, a.times_host, nullptr, a.table_host, a.unnormalize ? 1 : 0, a.seed, elem_off)) return 1;
+    L.tab = u->edm_tab_dev;
+    DM_CHECK_HIP(hipMemcpyAsync(L.xbuf, a.x_T, L.n * sizeof(float), hipMemcpyDeviceToDevice, L.s));  // img = randn(shape)
+    if (a.all_steps) DM_CHECK_HIP(hipMemcpyAsync(a.all_steps, a.x_T, L.n * sizeof(float), hipMemcpyDeviceToDevice, L.s));
+    L.key.B = B; L.key.H = H; L.key.W = W;
+    L.key.noise = a.noise; L.key.all_steps = a.all_steps; L.key.ws = u->ws; L.key.times = u->times_dev; L.key.tab = u->edm_tab_dev;
+    return 0;
+}
+
+// after run_steps: the result to the caller, and the run is done
+static int table_loop_end(TableLoop& L, float* out) {
+    DM_CHECK_HIP(hipMemcpyAsync(out, L.fin, L.n * sizeof(float), hipMemcpyDeviceToDevice, L.s));
+    return run_finish(L.r);
 }
 
 // ---- DDPM / DDIM ------------------------------------------------------------------------------------------------------

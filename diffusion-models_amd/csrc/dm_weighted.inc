@@ -31,49 +31,28 @@ static int sample_wo_impl(dm_unet* u, const dm_wo_args* a) {
     if (wo_unet_ok(u)) return 1;
     const int B = a->B, H = a->H, W = a->W, n_steps = a->n_steps;
     if (check_hw(u, H, W)) return 1;
-    DM_CHECK_HIP(hipSetDevice(u->device));
     const int C = u->cfg.channels;
     const int64_t HW = (int64_t)H * W, per = C * HW, n = (int64_t)B * per, n_out = (int64_t)B * u->out_dim * HW;
     DM_REQUIRE(HW % 4 == 0, "H * W must be a multiple of 4");
     const float* noise = a->noise;
     float* all_steps = a->all_steps;
 
-    SamplerRun r;
-    if (grow_tables(u, TAB_INT | TAB_FLOAT, n_steps, 1) || run_begin(r, u, a->stream, a->use_graph)) return 1;
-    hipStream_t s = r.s;
-    // workspace: [x | model output ((2C + 2) / C * n) | result | forward arena]
-    float *xbuf, *mo, *fin;
-    auto layout = [&](Arena& A) {
-        xbuf = A.alloc(n);
-        mo = A.alloc(n_out);
-        fin = A.alloc(n);  // what the last step leaves for `out`: the caller's pointer stays out of the captured graph
-    };
-    if (run_workspace(r, layout, [&](Arena& dry) {
-            return unet_forward_impl(u, dry, nullptr, nullptr, u->times_dev, u->state_dev, nullptr, 0, nullptr, B, H, W, s);
-        }))
+    // workspace: [x | result | model output ((2C + 2) / C * n) | forward arena]
+    TableLoop L;
+    float* mo;
+    if (table_loop_begin(L, u, *a, n_steps, 1, a->sample_offset * (uint64_t)per, [&](Arena& A) { mo = A.alloc(n_out); }))
         return 1;
-    if (run_upload(r, n_steps, a->times_host, nullptr, a->table_host, a->unnormalize ? 1 : 0, a->seed,
-                   a->sample_offset * (uint64_t)per))
-        return 1;
-    const float* tab = u->edm_tab_dev;
-
-    DM_CHECK_HIP(hipMemcpyAsync(xbuf, a->x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));  // img = randn(shape)
-    if (all_steps) DM_CHECK_HIP(hipMemcpyAsync(all_steps, a->x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-
     auto step = [&](hipStream_t st) -> int {
-        r.rewind();
-        if (unet_forward_impl(u, r.A, xbuf, nullptr, u->times_dev, u->state_dev, nullptr, 0, mo, B, H, W, st)) return 1;
-        if (launch_wo_step(xbuf, mo, noise, n, tab, u->state_dev, STEP_ROW_STEP, B, C, HW, 1, xbuf, all_steps, fin, nullptr, nullptr, st))
+        L.r.rewind();
+        if (unet_forward_impl(u, L.r.A, L.xbuf, nullptr, u->times_dev, u->state_dev, nullptr, 0, mo, B, H, W, st)) return 1;
+        if (launch_wo_step(L.xbuf, mo, noise, n, L.tab, u->state_dev, STEP_ROW_STEP, B, C, HW, 1, L.xbuf, all_steps, L.fin, nullptr,
+                           nullptr, st))
             return 1;
         return launch_step_advance(u->state_dev, st);
     };
-    dm_unet::GraphKey key;
-    key.kind = dm_unet::GK_WO;
-    key.B = B; key.H = H; key.W = W;
-    key.noise = noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.tab = u->edm_tab_dev;
-    if (run_steps(r, key, n_steps, step)) return 1;
-    DM_CHECK_HIP(hipMemcpyAsync(a->out, fin, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return run_finish(r);
+    L.key.kind = dm_unet::GK_WO;
+    if (run_steps(L.r, L.key, n_steps, step)) return 1;
+    return table_loop_end(L, a->out);
 }
 
 // p_losses (DD/weighted_objective_gaussian_diffusion.py:51-74) and the backward pass, an entry of run_train: q_sample, the
@@ -136,9 +115,7 @@ int dm_op_wo_step(const float* x, const float* model_out, const float* z, const 
                   int64_t HW, void* stream) {
     DM_REQUIRE(x && model_out && c_host && out, "null argument");
     DM_REQUIRE(B > 0 && C > 0 && HW > 0, "empty tensor");
-    DM_REQUIRE(element_offset % 4 == 0, "Philox element offset must be a multiple of 4 (one counter serves 4 elements)");
-    DM_REQUIRE(z || draw >= 1, "Philox draw 0 is the initial noise: a step's draw is its index + 1");
-    DM_REQUIRE(draw < (uint64_t(1) << 30), "draw index out of range");
+    if (draw_args_ok(z, draw, element_offset)) return 1;
     return state_op(draw_state(z != nullptr, seed, draw, element_offset), c_host, 1, stream,
                     [&](const SamplerState* st, const float* cd, hipStream_t s) {
                         return launch_wo_step(x, model_out, z, 0, cd, st, STEP_ROW_FIRST, B, C, HW, clip_denoised, out, nullptr,

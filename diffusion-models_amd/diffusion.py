@@ -34,7 +34,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, _loop
 from .spec import SCHEDULE_BUFFERS, ddim_step_table, ddpm_step_table, make_schedule
 from .unet import check_guidance
 
@@ -195,71 +195,36 @@ class DenoisingDiffusion:
     def _randn(self, shape, seed: int, draw: int, sample_offset: int = 0) -> torch.Tensor:
         return _lib.randn(self._lib, self.device, shape, seed, draw, sample_offset)
 
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
     def _run(self, kind, shape, times, coefs, takes_noise: Sequence[bool], return_all_timesteps, noise, seed,
              text_emb=None, max_steps=None, cond=None, sample_offset=0, x_init=None, unnormalize=None, guidance=None):
         """guidance: None, or (cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac) of classifier-free
         guidance (TextConditionalDenoisingDiffusion), which the library applies to the model output of every step."""
-        shape = tuple(int(v) for v in shape)
-        B, Cc, H, W = shape
-        assert Cc == self.channels, f"shape has {Cc} channels, the model {self.channels}"
-        f = self.model.downsample_factor
-        assert B > 0 and H % f == 0 and W % f == 0, f"shape {shape}: the sides must be divisible by {f}"
+        shape = _loop.checked_shape(self, shape)
+        B, _, H, W = shape
+        start = _loop.loop_start(self, shape, noise, seed, sample_offset, list(takes_noise), x_init)
         n_steps = len(times)
-        if seed is None:
-            seed = _lib.default_seed()
-        sample_offset = int(sample_offset)
-        if noise is not None:
-            x_T = (noise(shape) if x_init is None else x_init).to(self.device, torch.float32).contiguous()
-            rows = []
-            zero = None
-            for flag in takes_noise:
-                if flag:
-                    rows.append(noise(shape).to(torch.float32))
-                else:
-                    zero = zero if zero is not None else torch.zeros(shape, dtype=torch.float32)
-                    rows.append(zero)
-            noise_dev = torch.stack(rows, dim=0).to(self.device).contiguous()
-        else:
-            x_T = (self._randn(shape, seed, 0, sample_offset) if x_init is None
-                   else x_init.to(self.device, torch.float32).contiguous())
-            noise_dev = None
-        assert tuple(x_T.shape) == shape, f"initial state {tuple(x_T.shape)} does not match {shape}"
-        assert noise_dev is None or tuple(noise_dev.shape[1:]) == shape, "noise() must return tensors of the sampled shape"
-        if max_steps is not None:  # bounded run (bench / smoke): first `max_steps` iterations only
+        if max_steps is not None:  # bounded run (bench / smoke): first `max_steps` iterations only, every flag drawn above
             n_steps = min(n_steps, int(max_steps))
         ctx, m = (None, 0)
         if text_emb is not None:
             ctx, m = self.model._ctx(text_emb, B)
-        out = torch.empty(shape, device=self.device, dtype=torch.float32)
-        all_steps = (torch.empty((n_steps + 1,) + shape, device=self.device, dtype=torch.float32)
-                     if return_all_timesteps else None)
-        times_arr = (C.c_int64 * n_steps)(*[int(t) for t in times[:n_steps]])
-        coefs = coefs[:n_steps].contiguous()
-        coefs_ptr = _lib.fptr(coefs)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         a = _lib.SampleArgs()
         a.kind, a.objective, a.self_condition, a.n_steps = kind, self._objective_id, int(bool(self.self_condition)), n_steps
-        a.times_host, a.coefs_host = C.cast(times_arr, C.POINTER(C.c_int64)), coefs_ptr
-        a.x_T, a.noise, a.seed, a.sample_offset = _lib.ptr(x_T), _lib.ptr(noise_dev), seed, sample_offset
         a.ctx, a.ctx_tokens = _lib.ptr(ctx), m
         if cond is not None:
             cond = cond.to(self.device, torch.float32).contiguous()
             assert cond.shape[0] == B and tuple(cond.shape[2:]) == (H, W), "batch / size mismatch between x and cond"
             a.cond, a.cond_channels = _lib.ptr(cond), int(cond.shape[1])
-        a.out, a.all_steps = _lib.ptr(out), _lib.ptr(all_steps)
-        a.B, a.H, a.W = B, H, W
-        a.unnormalize = self._unnormalize_flag if unnormalize is None else int(bool(unnormalize))
-        a.use_graph, a.stream = 1 if self.use_graph else 0, stream
         if guidance is not None:
             assert ctx is not None, "classifier-free guidance needs text_emb"
             a.cfg = 1
             a.cfg_scale, a.cfg_rescaled_phi, a.cfg_remove_parallel, a.cfg_keep_parallel_frac = (
                 float(guidance[0]), float(guidance[1]), int(bool(guidance[2])), float(guidance[3]))
-        _lib.check(self._lib.dm_sample_ex(self.model._handle, C.byref(a)))
-        if not return_all_timesteps:
-            return out
-        ret = all_steps.permute(1, 0, 2, 3, 4).contiguous()  # (B, n_steps+1, C, H, W) like torch.stack(imgs, dim=1)
-        return self.unnormalize(ret)
+        return _loop.loop_call(self, a, self._lib.dm_sample_ex, shape, start, sample_offset, times[:n_steps], coefs[:n_steps],
+                               "coefs_host", n_steps + 1, return_all_timesteps, unnormalize)
 
     # -- training half (denoising_diffusion.py:805-900): loss and gradients in libdm_hip.so --------------------------
     def train(self, mode: bool = True):
@@ -341,16 +306,9 @@ class DenoisingDiffusion:
             sc_mode = 2 if use else 1
         if not getattr(self.model, "_training", False):
             self.model.train()
-        x_start = x_start.to(self.device, torch.float32).contiguous()
+        x_start, noise = _loop.loss_inputs(self, x_start, t, noise)
         b, c, h, w = x_start.shape
-        f = self.model.downsample_factor
-        if c != self.channels or h % f or w % f:
-            raise RuntimeError(f"x_start {tuple(x_start.shape)}: expected {self.channels} channels and sides divisible by {f}")
-        noise = (noise.to(self.device, torch.float32).contiguous() if noise is not None
-                 else self._randn(x_start.shape, _lib.default_seed(), 0))
-        if noise.shape != x_start.shape or t.numel() != b:
-            raise RuntimeError(f"noise {tuple(noise.shape)} / t ({t.numel()} entries) do not match x_start {tuple(x_start.shape)}")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
+        stream = self._stream()
         if offset_noise_strength and offset_noise_strength > 0.0:
             offs = (offset_noise.to(self.device, torch.float32).contiguous() if offset_noise is not None
                     else self._randn((b, c), _lib.default_seed(), 3))
@@ -376,7 +334,6 @@ class DenoisingDiffusion:
             if keep.numel() != b:
                 raise RuntimeError(f"text_mask has {keep.numel()} entries for a batch of {b}")
             mask_arr = (C.c_int32 * b)(*[int(bool(v)) for v in keep.tolist()])
-        loss = C.c_float(0.0)
         out = torch.empty_like(x_start) if return_model_out else None
         t_arr = (C.c_int64 * b)(*[int(v) for v in t_cpu.tolist()])
         a = _lib.TrainArgs()
@@ -385,13 +342,12 @@ class DenoisingDiffusion:
         a.coef_host, a.coef_stride = _lib.fptr(coef), int(coef.shape[1])
         a.cond_channels, a.ctx_tokens, a.self_cond, a.objective = cc, m, sc_mode, self._objective_id
         a.loss_scale, a.accumulate = float(loss_scale), int(bool(accumulate))
-        a.loss_out_host = C.pointer(loss) if sync else None
-        a.model_out, a.B, a.H, a.W, a.stream = _lib.ptr(out), b, h, w, stream
+        a.model_out, a.B, a.H, a.W = _lib.ptr(out), b, h, w
         a.loss_terms = 1
-        def backward():  # an unmasked call is the entry point it always was; the KL term's second call passes the same mask
+        def backward(handle, args):  # an unmasked call is the entry point it always was; the KL term's second call passes the same mask
             if mask_arr is None:
-                return self._lib.dm_unet_loss_backward_ex(self.model._handle, C.byref(a))
-            return self._lib.dm_unet_loss_backward_masked(self.model._handle, C.byref(a), mask_arr)
+                return self._lib.dm_unet_loss_backward_ex(handle, args)
+            return self._lib.dm_unet_loss_backward_masked(handle, args, mask_arr)
 
         if self.hybrid_loss:
             if cond is not None:
@@ -401,24 +357,12 @@ class DenoisingDiffusion:
                                           "called without cond); not reproduced")
             a.kl_scale = hybrid_kl_scale(t_cpu)
             a.loss_terms = 3 if float(getattr(self.model, "dropout", 0.0) or 0.0) == 0.0 else 1
-        _lib.check(backward())
+        val = _loop.loss_call(self, self.model._handle, backward, a, sync)
         if self.hybrid_loss and a.loss_terms == 1:
-            # dropout: p_mean_variance's forward pass draws its own masks -- a second, accumulating call for the KL term
-            mse = C.c_float(loss.value)
-            if not sync:
-                mse_dev = torch.empty((), device=self.device, dtype=torch.float32)
-                _lib.check(self._lib.dm_unet_train_scalar(self.model._handle, 0, _lib.ptr(mse_dev), stream))
+            # dropout: p_mean_variance's forward pass draws its own masks -- a second, accumulating call for the KL term,
+            # whose loss is added to the first call's (on the host, or with sync=False on the device)
             a.loss_terms, a.accumulate, a.model_out = 2, 1, None
-            _lib.check(backward())
-            if sync:
-                loss = C.c_float(mse.value + loss.value)
-        if sync:
-            val = torch.tensor(loss.value, dtype=torch.float32)
-        else:
-            val = torch.empty((), device=self.device, dtype=torch.float32)
-            _lib.check(self._lib.dm_unet_train_scalar(self.model._handle, 0, _lib.ptr(val), stream))
-            if self.hybrid_loss and a.loss_terms == 2:
-                val = val + mse_dev
+            val = _loop.loss_call(self, self.model._handle, backward, a, sync) + val
         return (val, out) if return_model_out else val
 
     def forward(self, img, *args, **kwargs):

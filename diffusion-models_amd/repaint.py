@@ -22,7 +22,7 @@ from typing import Dict, List, NamedTuple
 
 import torch
 
-from . import _lib
+from . import _lib, _loop
 from .diffusion import DenoisingDiffusion
 from .spec import ddpm_step_table
 
@@ -148,50 +148,18 @@ class GaussianDiffusion(DenoisingDiffusion):
             return super().p_sample_loop(shape, return_all_timesteps, noise=noise, seed=seed, sample_offset=sample_offset, **kw)
         if kw:
             raise TypeError(f"unexpected keyword arguments with a mask: {sorted(kw)}")
-        shape = tuple(int(v) for v in shape)
-        B, Cc, H, W = shape
-        assert Cc == self.channels, f"shape has {Cc} channels, the model {self.channels}"
-        f = self.model.downsample_factor
-        assert B > 0 and H % f == 0 and W % f == 0, f"shape {shape}: the sides must be divisible by {f}"
+        shape = _loop.checked_shape(self, shape)
         gt, mask = self._masked_inputs(shape, gt, mask)
         tab = repaint_step_table(self._sched, resample, resample_iter, resample_jump, resample_every)
-        n_rows = len(tab.times)
-        if seed is None:
-            seed = _lib.default_seed()
-        sample_offset = int(sample_offset)
-        if noise is not None:
-            x_T = noise(shape).to(self.device, torch.float32).contiguous()
-            rows = torch.zeros((n_rows, 3) + shape, dtype=torch.float32)
-            for r in range(n_rows):
-                if tab.coefs[r, JUMP] != 0:
-                    rows[r, 0] = noise(shape)
-                rows[r, 1] = noise(shape)
-                if tab.coefs[r, 5] != 0:
-                    rows[r, 2] = noise(shape)
-            noise_dev = rows.to(self.device).contiguous()
-        else:
-            x_T = self._randn(shape, seed, 0, sample_offset)
-            noise_dev = None
-        out = torch.empty(shape, device=self.device, dtype=torch.float32)
-        all_steps = (torch.empty((tab.n_frames,) + shape, device=self.device, dtype=torch.float32)
-                     if return_all_timesteps else None)
-        times_arr = (C.c_int64 * n_rows)(*tab.times)
-        coefs = tab.coefs.contiguous()
+        slots = torch.stack([tab.coefs[:, JUMP] != 0, torch.ones(len(tab.times), dtype=torch.bool), tab.coefs[:, 5] != 0], dim=1)
+        start = _loop.loop_start(self, shape, noise, seed, sample_offset, slots)
         a = _lib.RepaintArgs()
-        a.objective, a.n_rows = self._objective_id, n_rows
-        a.times_host = C.cast(times_arr, C.POINTER(C.c_int64))
-        a.table_host = _lib.fptr(coefs)
-        a.x_T, a.noise, a.seed, a.sample_offset = _lib.ptr(x_T), _lib.ptr(noise_dev), seed, sample_offset
+        a.objective, a.n_rows, a.n_frames = self._objective_id, len(tab.times), tab.n_frames
         a.gt, a.mask, a.mask_channels = _lib.ptr(gt), _lib.ptr(mask), int(mask.shape[1])
-        a.unnormalize = 0 if return_all_timesteps else self._unnormalize_flag  # the frames are unnormalised together below
-        a.out, a.all_steps, a.n_frames = _lib.ptr(out), _lib.ptr(all_steps), tab.n_frames
-        a.B, a.H, a.W = B, H, W
-        a.use_graph, a.stream = 1 if self.use_graph else 0, torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.dm_sample_repaint(self.model._handle, C.byref(a)))
-        if not return_all_timesteps:
-            return out
-        ret = all_steps.permute(1, 0, 2, 3, 4).contiguous()  # (B, frames, C, H, W) like torch.stack(imgs, dim=1)
-        return self.unnormalize(ret)
+        # unnormalize=False with all frames: they are unnormalised together after the call
+        return _loop.loop_call(self, a, self._lib.dm_sample_repaint, shape, start, sample_offset, tab.times, tab.coefs,
+                               "table_host", tab.n_frames, return_all_timesteps,
+                               unnormalize=False if return_all_timesteps else None)
 
     @torch.inference_mode()
     def sample(self, batch_size=16, return_all_timesteps=False, gt=None, mask=None, resample=True, resample_iter=10,

@@ -29,7 +29,7 @@ from typing import Dict, List, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, _loop
 from .diffusion import DenoisingDiffusion
 
 COLS = _lib.DM_WO_COEFS
@@ -107,48 +107,16 @@ class WeightedObjectiveGaussianDiffusion(DenoisingDiffusion):
     def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0):
         """denoising_diffusion.py:647-664 over the p_mean_variance of :33-49 (the module docstring's deviation).  ``noise``
         (a callable ``shape -> cpu tensor``) is called in the reference's draw order: x_T, then one per step with t > 0."""
-        shape = tuple(int(v) for v in shape)
-        B, Cc, H, W = shape
-        assert Cc == self.channels, f"shape has {Cc} channels, the model {self.channels}"
-        f = self.model.downsample_factor
-        assert B > 0 and H % f == 0 and W % f == 0, f"shape {shape}: the sides must be divisible by {f}"
+        shape = _loop.checked_shape(self, shape)
         times = list(reversed(range(self.num_timesteps)))
         if max_steps is not None:  # bounded run: the first `max_steps` iterations only
             times = times[:max(int(max_steps), 0)]
         times, coefs = wo_step_table(self._sched, times)
-        n_steps = len(times)
-        if seed is None:
-            seed = _lib.default_seed()
-        sample_offset = int(sample_offset)
-        if noise is not None:
-            x_T = noise(shape).to(self.device, torch.float32).contiguous()
-            rows = torch.zeros((n_steps,) + shape, dtype=torch.float32)
-            for i, t in enumerate(times):
-                if t > 0:
-                    rows[i] = noise(shape)
-            noise_dev = rows.to(self.device).contiguous()
-        else:
-            x_T = self._randn(shape, seed, 0, sample_offset)
-            noise_dev = None
-        assert tuple(x_T.shape) == shape, f"initial state {tuple(x_T.shape)} does not match {shape}"
-        out = torch.empty(shape, device=self.device, dtype=torch.float32)
-        all_steps = (torch.empty((n_steps + 1,) + shape, device=self.device, dtype=torch.float32)
-                     if return_all_timesteps else None)
-        times_arr = (C.c_int64 * n_steps)(*times)
-        coefs = coefs.contiguous()
+        start = _loop.loop_start(self, shape, noise, seed, sample_offset, [t > 0 for t in times])
         a = _lib.WoArgs()
-        a.n_steps = n_steps
-        a.times_host, a.table_host = C.cast(times_arr, C.POINTER(C.c_int64)), _lib.fptr(coefs)
-        a.x_T, a.noise, a.seed, a.sample_offset = _lib.ptr(x_T), _lib.ptr(noise_dev), seed, sample_offset
-        a.out, a.all_steps = _lib.ptr(out), _lib.ptr(all_steps)
-        a.B, a.H, a.W = B, H, W
-        a.unnormalize = self._unnormalize_flag
-        a.use_graph, a.stream = 1 if self.use_graph else 0, torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.dm_sample_wo(self.model._handle, C.byref(a)))
-        if not return_all_timesteps:
-            return out
-        ret = all_steps.permute(1, 0, 2, 3, 4).contiguous()  # (B, n_steps + 1, C, H, W) like torch.stack(imgs, dim=1)
-        return self.unnormalize(ret)
+        a.n_steps = len(times)
+        return _loop.loop_call(self, a, self._lib.dm_sample_wo, shape, start, sample_offset, times, coefs, "table_host",
+                               len(times) + 1, return_all_timesteps)
 
     @torch.inference_mode()
     def sample(self, batch_size=16, return_all_timesteps=False, **kw):
@@ -211,19 +179,10 @@ class WeightedObjectiveGaussianDiffusion(DenoisingDiffusion):
         ``noise`` defaults to a draw of the device Philox stream."""
         if not getattr(self.model, "_training", False):
             self.model.train()
-        x_start = x_start.to(self.device, torch.float32).contiguous()
+        x_start, noise = _loop.loss_inputs(self, x_start, t, noise)
         b, c, h, w = x_start.shape
-        f = self.model.downsample_factor
-        if c != self.channels or h % f or w % f:
-            raise RuntimeError(f"x_start {tuple(x_start.shape)}: expected {self.channels} channels and sides divisible by {f}")
-        noise = (noise.to(self.device, torch.float32).contiguous() if noise is not None
-                 else self._randn(x_start.shape, _lib.default_seed(), 0))
-        if noise.shape != x_start.shape or t.numel() != b:
-            raise RuntimeError(f"noise {tuple(noise.shape)} / t ({t.numel()} entries) do not match x_start {tuple(x_start.shape)}")
         t_cpu = t.detach().to("cpu", torch.long).contiguous()
         coef = wo_train_table(self._sched, t_cpu)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        loss = C.c_float(0.0)
         out = torch.empty((b, 2 * c + 2, h, w), device=self.device, dtype=torch.float32) if return_model_out else None
         t_arr = (C.c_int64 * b)(*[int(v) for v in t_cpu.tolist()])
         a = _lib.WoTrainArgs()
@@ -233,14 +192,8 @@ class WeightedObjectiveGaussianDiffusion(DenoisingDiffusion):
         a.pred_noise_loss_weight = float(self.pred_noise_loss_weight)
         a.pred_x_start_loss_weight = float(self.pred_x_start_loss_weight)
         a.loss_scale, a.accumulate = float(loss_scale), int(bool(accumulate))
-        a.loss_out_host = C.pointer(loss) if sync else None
-        a.model_out, a.B, a.H, a.W, a.stream = _lib.ptr(out), b, h, w, stream
-        _lib.check(self._lib.dm_unet_loss_backward_wo(self.model._handle, C.byref(a)))
-        if sync:
-            val = torch.tensor(loss.value, dtype=torch.float32)
-        else:
-            val = torch.empty((), device=self.device, dtype=torch.float32)
-            _lib.check(self._lib.dm_unet_train_scalar(self.model._handle, 0, _lib.ptr(val), stream))
+        a.model_out, a.B, a.H, a.W = _lib.ptr(out), b, h, w
+        val = _loop.loss_call(self, self.model._handle, self._lib.dm_unet_loss_backward_wo, a, sync)
         return (val, out) if return_model_out else val
 
     def forward(self, img, *args, **kwargs):

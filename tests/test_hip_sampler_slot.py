@@ -1,10 +1,10 @@
-"""The four sampling loops on ONE handle: DDPM / DDIM, ElucidatedDiffusion (Heun, DPM-Solver++), continuous time and
-RePaint share the handle's workspace, step tables, sampler state and its single graph slot.
+"""The sampling loops on ONE handle: DDPM / DDIM, ElucidatedDiffusion (Heun, DPM-Solver++), continuous time, RePaint and
+the classifier-guided loop share the handle's workspace, step tables, sampler state and its graph slots.
 
 What is pinned here, and nowhere else: a loop that runs after another loop on the same handle gives the bits it gives on
-a fresh handle, captures exactly the graphs of its own kind (Heun two, every other loop one), and captures nothing when
-it is simply called again; tables that grow after a capture do not leave a stale graph behind; and the eager leg is the
-graph leg bit for bit and leaves the slot alone.
+a fresh handle, captures exactly the graphs of its own kind (Heun and the guided loop two, every other loop one), and
+captures nothing when it is simply called again; tables that grow after a capture do not leave a stale graph behind; and
+the eager leg is the graph leg bit for bit and leaves the slot alone.
 
 Networks and schedules are the tiny ones of the EDM / continuous-time and RePaint golden fixtures (dim 32, mults (1, 2),
 16 x 16, cosine betas), B = 2, at most 4 steps (RePaint: at most 12 rows).
@@ -78,6 +78,14 @@ def _int_calls():
         d = dm.RePaintGaussianDiffusion(net, use_graph=use_graph, **kw)
         return d.sample(gt=gt, mask=mask, seed=SEED, resample_iter=resample_iter, resample_jump=2)
 
+    guided = {}  # (handle, use_graph) -> the object: it owns the mean / grad tensors whose addresses the two graphs hold
+
+    def cguide(net, use_graph):
+        if (net, use_graph) not in guided:
+            guided[net, use_graph] = dm.ClassifierGuidedGaussianDiffusion(net, use_graph=use_graph, **kw)
+        return guided[net, use_graph].sample(batch_size=B, cond_fn=lambda mean, t, **k: 0.1 * mean, guidance_kwargs={},
+                                             seed=SEED)
+
     return {
         "ddpm": (lambda net, g=True: ddpm(net, g), 1),
         "ddpm2": (lambda net, g=True: ddpm(net, g, 2), 1),
@@ -85,6 +93,7 @@ def _int_calls():
         "repaint": (lambda net, g=True: repaint(net, g, mask_c), 1),
         "repaint_1ch": (lambda net, g=True: repaint(net, g, mask_1), 1),
         "repaint_12rows": (lambda net, g=True: repaint(net, g, mask_c, 2), 1),
+        "cguide": (lambda net, g=True: cguide(net, g), 2),
     }
 
 
@@ -129,7 +138,7 @@ def test_float_time_loops_share_one_handle(float_calls, fresh):
 
 
 def test_integer_time_loops_share_one_handle(int_calls, fresh):
-    _shared_sequence(_int_net(), int_calls, fresh, ["ddpm", "repaint", "ddim", "repaint_1ch", "ddpm"])
+    _shared_sequence(_int_net(), int_calls, fresh, ["ddpm", "cguide", "repaint", "ddim", "cguide", "repaint_1ch", "ddpm"])
 
 
 def test_tables_grow_after_a_capture(int_calls, fresh):
@@ -152,7 +161,7 @@ def test_tables_grow_after_a_capture(int_calls, fresh):
 @pytest.mark.parametrize("family", ["float", "int"])
 def test_eager_is_the_graph_and_leaves_the_slot_alone(family, float_calls, int_calls, fresh):
     calls, net = (float_calls, _float_net()) if family == "float" else (int_calls, _int_net())
-    names = ["heun", "dpmpp", "ct"] if family == "float" else ["ddpm", "ddim", "repaint"]
+    names = ["heun", "dpmpp", "ct"] if family == "float" else ["ddpm", "ddim", "repaint", "cguide"]
     for name in names:
         run = calls[name][0]
         graph = run(net)
