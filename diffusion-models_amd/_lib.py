@@ -58,6 +58,8 @@ EXPORTS = (
     "dm_unet_train_enable_ft", "dm_unet_loss_backward_edm",
     "dm_op_edm_noise_in", "dm_op_edm_loss", "dm_op_sinusoid_ft_bwd",
     "dm_sample_ct", "dm_unet_loss_backward_ct", "dm_op_ct_step", "dm_op_ct_noise_in", "dm_op_ct_loss",
+    "dm_unet_loss_backward_ct_ig", "dm_op_conv7_dgrad", "dm_op_sinusoid_ft_tgrad", "dm_op_ct_sched_reduce",
+    "dm_unet_optimizer_step_ex",
     "dm_sample_repaint", "dm_op_repaint_step",
     "dm_sample_lv", "dm_unet_loss_backward_lv", "dm_op_lv_step", "dm_op_lv_loss",
     "dm_sample_wo", "dm_unet_loss_backward_wo", "dm_op_wo_step", "dm_op_wo_loss",
@@ -143,6 +145,13 @@ class CtTrainArgs(C.Structure):
         ("images", C.c_void_p), ("noise", C.c_void_p), ("coef_host", C.POINTER(C.c_float)), ("coef_stride", C.c_int32),
         ("objective", C.c_int32), ("loss_scale", C.c_float), ("accumulate", C.c_int32), ("B", C.c_int32), ("H", C.c_int32),
         ("W", C.c_int32), ("normalize", C.c_int32), ("loss_out_host", C.POINTER(C.c_float)), ("stream", C.c_void_p),
+    ]
+
+
+class CtTrainIgArgs(C.Structure):
+    """dm_ct_train_ig_args (include/dm_hip.h): dm_ct_train_args, then the three outputs."""
+    _fields_ = CtTrainArgs._fields_ + [
+        ("sched_out_host", C.POINTER(C.c_float)), ("dx_out", C.c_void_p), ("dtime_out", C.c_void_p),
     ]
 
 
@@ -346,6 +355,12 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_ct_step.argtypes = [fp, fp, fp, C.POINTER(C.c_float), i32, i32, i32, u64, u64, u64, fp, fp, i32, i64, vp]
     lib.dm_op_ct_noise_in.argtypes = [fp, fp, C.POINTER(C.c_float), i32, i32, i32, fp, fp, i32, i64, vp]
     lib.dm_op_ct_loss.argtypes = [fp, fp, C.POINTER(C.c_float), C.c_float, fp, C.POINTER(C.c_float), i32, i64, vp]
+    lib.dm_unet_loss_backward_ct_ig.argtypes = [vp, C.POINTER(CtTrainIgArgs)]
+    lib.dm_op_conv7_dgrad.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, vp]
+    lib.dm_op_sinusoid_ft_tgrad.argtypes = [fp, fp, fp, fp, i32, i32, vp]
+    lib.dm_op_ct_sched_reduce.argtypes = [fp, fp, fp, fp, fp, fp, i32, fp, i32, i64, vp]
+    lib.dm_unet_optimizer_step_ex.argtypes = [vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_float,
+                                              C.POINTER(C.c_float), vp]
     lib.dm_sample_repaint.argtypes = [vp, C.POINTER(RepaintArgs)]
     lib.dm_op_repaint_step.argtypes = [i32, i32, fp, fp, fp, fp, i32, fp, fp, fp, C.POINTER(C.c_float), i32, u64, u64, u64, fp, fp,
                                        i32, i32, i32, vp]

@@ -14,7 +14,18 @@ the kernels hold no schedule logic.  This is deliberate: the cosine schedule's o
 when the same expressions are evaluated in fp64 -- at t = 1, ``cos(pi / 2) ** -2`` makes log-SNR ~ -33.9 a pure fp32
 rounding artefact -- so parity is with the reference's fp32 scalars, never with a cleaner formula.
 
-``noise_schedule='learned'`` (a trainable MLP whose gradient flows into the U-Net's time input) is not built.
+``noise_schedule='learned'`` (``learned_noise_schedule``: a monotonic MLP t -> log-SNR trained with the U-Net) keeps its six
+parameters on the host as a torch module, where B scalars through 1 -> 1 and 1 -> H -> 1 cost nothing.  Its gradient needs
+the loss differentiated with respect to the U-Net's INPUTS, which ``dm_unet_loss_backward_ct_ig`` returns reduced per image:
+``ga_b = sum dL/dx x0``, ``gs_b = sum dL/dx eps``, ``dt_b = dL/dtime_b`` and the unweighted ``l_b``.  With ``lambda =
+log_snr(times)`` under autograd and alpha, sigma, w the reference's expressions of it, the host back-propagates the surrogate
+
+    sum_b (ga_b alpha_b + gs_b sigma_b + dt_b lambda_b) + loss_scale * mean_b(l_b w_b)
+
+whose gradient is the loss's: x = alpha x0 + sigma eps gives dL/dalpha_b = ga_b and dL/dsigma_b = gs_b, the U-Net's time
+is lambda_b itself, and the loss weight multiplies l_b.  Every chain-rule factor (sqrt . sigmoid, clamp, the normalisation by
+net(0) / net(1), frac_gradient) is then torch's own.  ``p_losses_input_grads`` / ``forward_input_grads`` return dL/dx and
+dL/dtime next to the loss, for any schedule.
 
 Extensions (keyword-only): ``noise`` injects a source of N(0,1) draws called in the reference's order (the start image,
 then one draw per step except the last); ``seed`` / ``sample_offset`` select the device Philox stream and the index of the
@@ -31,9 +42,12 @@ import torch
 from torch import sqrt
 from torch.special import expm1
 
-from . import _lib
+from . import _lib, _loop
 from ._floattime import FloatTimeDiffusion
 from ._lib import default_seed as _default_seed, fptr as _fptr
+
+from torch import nn
+import torch.nn.functional as F
 
 COLS = _lib.DM_CT_COEFS
 # columns of a table row (csrc/ct.h)
@@ -57,12 +71,83 @@ def alpha_cosine_log_snr(t, s=0.008):
 SCHEDULES = {"linear": beta_linear_log_snr, "cosine": alpha_cosine_log_snr}
 
 
+class MonotonicLinear(nn.Module):
+    """:33-39: a Linear whose weight and bias enter as absolute values."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__()
+        self.net = nn.Linear(*args, **kwargs)
+
+    def forward(self, x):
+        return F.linear(x, self.net.weight.abs(), self.net.bias.abs())
+
+
+class _Residual(nn.Module):
+    def __init__(self, fn):
+        super().__init__()
+        self.fn = fn
+
+    def forward(self, x):
+        return x + self.fn(x)
+
+
+class _LastDim(nn.Module):
+    """'... -> ... 1' (add) and '... 1 -> ...' (drop): the two Rearrange layers of the reference's net; they hold no
+    parameter and keep the Sequential's indices, hence the state_dict keys net.1 / net.2."""
+
+    def __init__(self, add):
+        super().__init__()
+        self.add = add
+
+    def forward(self, x):
+        return x.unsqueeze(-1) if self.add else x.squeeze(-1)
+
+
+class learned_noise_schedule(nn.Module):
+    """:57-95 (sections H and I.2 of the Variational Diffusion Models supplement): a monotonic t -> log-SNR net, normalised
+    so that t = 0 / 1 map to log_snr_max / log_snr_min; ``frac_gradient`` of the gradient goes back.  A CPU module: same
+    construction order as the reference, so the same seed gives the same initialisation."""
+
+    def __init__(self, *, log_snr_max, log_snr_min, hidden_dim=1024, frac_gradient=1.):
+        super().__init__()
+        self.slope = log_snr_min - log_snr_max
+        self.intercept = log_snr_max
+        self.net = nn.Sequential(
+            _LastDim(True),
+            MonotonicLinear(1, 1),
+            _Residual(nn.Sequential(MonotonicLinear(1, hidden_dim), nn.Sigmoid(), MonotonicLinear(hidden_dim, 1))),
+            _LastDim(False),
+        )
+        self.frac_gradient = frac_gradient
+
+    def forward(self, x):
+        frac_gradient = self.frac_gradient
+        out_zero = self.net(torch.zeros_like(x))
+        out_one = self.net(torch.ones_like(x))
+        x = self.net(x)
+        normed = self.slope * ((x - out_zero) / (out_one - out_zero)) + self.intercept
+        return normed * frac_gradient + normed.detach() * (1 - frac_gradient)
+
+
+class _NoGrad:
+    """A schedule module as the plain function of t the step tables take."""
+
+    def __init__(self, module):
+        self.module = module
+
+    def __call__(self, t):
+        with torch.no_grad():
+            return self.module(t)
+
+
 def _schedule(schedule):
+    if isinstance(schedule, nn.Module):
+        return _NoGrad(schedule)
     if callable(schedule):
         return schedule
     if schedule == "learned":
-        raise NotImplementedError("noise_schedule='learned' (a trainable monotonic MLP whose gradient reaches the U-Net's "
-                                  "time input) is not built on the HIP path")
+        raise ValueError("noise_schedule='learned' names a module the diffusion object owns: pass that module "
+                         "(ContinuousTimeGaussianDiffusion(...).log_snr)")
     if schedule not in SCHEDULES:
         raise ValueError(f"unknown noise schedule {schedule}")
     return SCHEDULES[schedule]
@@ -112,6 +197,31 @@ def ct_train_table(times: torch.Tensor, schedule="linear", min_snr_loss_weight=F
     return tab
 
 
+def learned_train_terms(sched, times, min_snr_loss_weight=False, min_snr_gamma=5):
+    """(lambda, alpha, sigma, w) of ``q_sample`` / ``p_losses`` (:225-228, :247-248) for a schedule MODULE, as (B,) fp32
+    tensor expressions of ``lambda = sched(times)`` that carry its autograd graph, and the (B, DM_CT_COEFS) table of their
+    values the library reads."""
+    t = torch.as_tensor(times).detach().to("cpu", torch.float32).reshape(-1)
+    lam = sched(t)
+    alpha, sigma = sqrt(lam.sigmoid()), sqrt((-lam).sigmoid())
+    if min_snr_loss_weight:
+        snr = lam.exp()
+        weight = snr.clamp(min=min_snr_gamma) / snr
+    else:
+        weight = torch.ones_like(lam)
+    tab = torch.zeros((t.numel(), COLS), dtype=torch.float32)
+    tab[:, LOG_SNR], tab[:, ALPHA], tab[:, SIGMA], tab[:, LOSS_W] = lam.detach(), alpha.detach(), sigma.detach(), weight.detach()
+    return (lam, alpha, sigma, weight), tab
+
+
+def schedule_surrogate(terms, rows, loss_scale=1.0):
+    """The scalar whose gradient with respect to the schedule's parameters is the loss's: ``terms`` from
+    ``learned_train_terms``, ``rows`` the (B, 4) [ga, gs, dt, l] of ``dm_unet_loss_backward_ct_ig`` (constants here)."""
+    lam, alpha, sigma, weight = terms
+    ga, gs, dt, l = rows.detach().to(lam.dtype).unbind(dim=1)
+    return (ga * alpha + gs * sigma + dt * lam).sum() + float(loss_scale) * (l * weight).mean()
+
+
 class _ContinuousTimeBase(FloatTimeDiffusion):
     """What the two classes share; ``_objective`` and the schedule tell them apart."""
 
@@ -123,7 +233,7 @@ class _ContinuousTimeBase(FloatTimeDiffusion):
 
     def _init(self, model, image_size, channels, schedule, num_sample_steps, clip_sample_denoised, use_graph):
         self._init_unet(model, image_size, channels, use_graph, f"{type(self).__name__} calls model(x, log_snr) only")
-        self.log_snr = _schedule(schedule)
+        self.log_snr = _schedule(schedule) if not isinstance(schedule, nn.Module) else schedule
         self.num_sample_steps = num_sample_steps
         self.clip_sample_denoised = clip_sample_denoised
 
@@ -158,7 +268,8 @@ class _ContinuousTimeBase(FloatTimeDiffusion):
         row = ct_step_row(self.log_snr, time, time_next)
         row[SQRT_VAR] = 0.0
         mean, _ = self._step_op(x, row, None)
-        log_snr, log_snr_next = self.log_snr(time), self.log_snr(time_next)
+        f = _schedule(self.log_snr)
+        log_snr, log_snr_next = f(time), f(time_next)
         return mean, ((-log_snr_next).sigmoid() * -expm1(log_snr - log_snr_next)).to(self.device)
 
     def p_sample(self, x, time, time_next, *, noise=None):
@@ -217,25 +328,54 @@ class _ContinuousTimeBase(FloatTimeDiffusion):
         """:233-235: uniform on [0, 1); the (batch_size,) draw comes from torch's global CPU generator."""
         return self._draw_times(batch_size).to(self.device)
 
-    def _loss(self, images, times, noise, normalize, loss_scale, accumulate, sync):
+    @property
+    def learned_schedule(self):
+        """The schedule module when the schedule is trained, else None."""
+        return self.log_snr if isinstance(self.log_snr, nn.Module) else None
+
+    def _loss(self, images, times, noise, normalize, loss_scale, accumulate, sync, return_input_grads=False):
         model = self._trainable()
         b, c, h, w = images.shape
         assert c == self.channels, "mismatch of image channels"
+        sched = self.learned_schedule
+        if sched is not None and not sync:
+            raise ValueError("sync=False cannot serve a learned noise schedule: the per-image gradient rows have to come back "
+                             "to the host before its backward pass")
         if not getattr(model, "_training", False):
             self.train()
-        tab = ct_train_table(times, self.log_snr, self.min_snr_loss_weight, self.min_snr_gamma).contiguous()
+        if sched is None:
+            tab = ct_train_table(times, self.log_snr, self.min_snr_loss_weight, self.min_snr_gamma).contiguous()
+        else:
+            terms, tab = learned_train_terms(sched, times, self.min_snr_loss_weight, self.min_snr_gamma)
         if tab.shape[0] != b:
             raise RuntimeError(f"times has {tab.shape[0]} entries for a batch of {b}")
         images, noise = self._loss_inputs(images, noise)
-        a = _lib.CtTrainArgs()
+        ig = sched is not None or return_input_grads
+        a = _lib.CtTrainIgArgs() if ig else _lib.CtTrainArgs()
         a.images, a.noise, a.coef_host, a.coef_stride = _lib.ptr(images), _lib.ptr(noise), _fptr(tab), COLS
         a.objective, a.loss_scale, a.accumulate = self._objective, float(loss_scale), int(bool(accumulate))
         a.B, a.H, a.W, a.normalize = b, h, w, int(bool(normalize))
-        return self._loss_call(a, sync)
+        if not ig:
+            return self._loss_call(a, sync)
+        if not hasattr(self._lib, "dm_unet_loss_backward_ct_ig"):
+            raise NotImplementedError("this libdm_hip.so has no input-gradient entry (dm_unet_loss_backward_ct_ig)")
+        rows = torch.zeros((b, 4), dtype=torch.float32) if sched is not None else None
+        dx = torch.empty_like(images) if return_input_grads else None
+        dtime = torch.empty((b,), device=self.device, dtype=torch.float32) if return_input_grads else None
+        a.sched_out_host = _fptr(rows) if rows is not None else None
+        a.dx_out, a.dtime_out = _lib.ptr(dx), _lib.ptr(dtime)
+        loss = _loop.loss_call(self, model._handle, self._lib.dm_unet_loss_backward_ct_ig, a, sync)
+        if sched is not None:
+            if not accumulate:
+                for p in sched.parameters():
+                    p.grad = None
+            schedule_surrogate(terms, rows, loss_scale).backward()
+        return (loss, dx, dtime) if return_input_grads else loss
 
     def p_losses(self, x_start, times, noise=None, *, loss_scale=1.0, accumulate=False, sync=True):
         """:237-251 (v: :152-162) on ``x_start`` in [-1, 1]: the loss (0-dim CPU tensor; ``sync=False``: a 0-dim device
-        tensor, nothing waited for); the parameter gradients stay on the U-Net (``self.model.grad(name)`` / ``.grads()``)."""
+        tensor, nothing waited for); the parameter gradients stay on the U-Net (``self.model.grad(name)`` / ``.grads()``),
+        those of a learned schedule land in ``.grad`` of its six host parameters (``accumulate=False`` clears them first)."""
         return self._loss(x_start, times, noise, False, loss_scale, accumulate, sync)
 
     def forward(self, img, *, times=None, noise=None, loss_scale=1.0, accumulate=False, sync=True):
@@ -245,6 +385,51 @@ class _ContinuousTimeBase(FloatTimeDiffusion):
         assert h == self.image_size and w == self.image_size, f'height and width of image must be {self.image_size}'
         times = self._draw_times(b) if times is None else times
         return self._loss(img, times, noise, True, loss_scale, accumulate, sync)
+
+    def p_losses_input_grads(self, x_start, times, noise=None, *, loss_scale=1.0, accumulate=False):
+        """``p_losses`` on the same arguments, returning ``(loss, dL/dx, dL/dtime)``: the last two are device tensors
+        (B, C, H, W) and (B,), the gradient with respect to the noised image and to the log-SNR the U-Net was called with
+        (any schedule, both classes).  Loss and parameter gradients are those of ``p_losses``."""
+        return self._loss(x_start, times, noise, False, loss_scale, accumulate, True, return_input_grads=True)
+
+    def forward_input_grads(self, img, *, times=None, noise=None, loss_scale=1.0, accumulate=False):
+        """``forward`` returning ``(loss, dL/dx, dL/dtime)`` as ``p_losses_input_grads`` does."""
+        self._trainable()
+        b, c, h, w = img.shape
+        assert h == self.image_size and w == self.image_size, f'height and width of image must be {self.image_size}'
+        times = self._draw_times(b) if times is None else times
+        return self._loss(img, times, noise, True, loss_scale, accumulate, True, return_input_grads=True)
+
+    def _schedule_optimizer(self, lr, betas, eps):
+        """The ``torch.optim.Adam`` over the six host parameters of a learned schedule (made on first use), set to the
+        call's hyper-parameters: ``train_step`` steps it beside the library's Adam, the checkpoints carry its state."""
+        opt = self.__dict__.get("_sched_opt")
+        if opt is None:
+            opt = self._sched_opt = torch.optim.Adam(list(self.learned_schedule.parameters()), lr=lr, betas=tuple(betas), eps=eps)
+        g = opt.param_groups[0]
+        g["lr"], g["betas"], g["eps"] = lr, tuple(betas), eps
+        return opt
+
+    # -- module-ish surface with a trained schedule: the U-Net's parameters, then the six (the reference's registration order)
+    def parameters(self):
+        yield from self._unet.parameters()
+        if self.learned_schedule is not None:
+            yield from self.learned_schedule.parameters()
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if self.learned_schedule is not None:
+            sd.update({f"log_snr.{k}": v.detach().clone() for k, v in self.learned_schedule.state_dict().items()})
+        return sd
+
+    def load_state_dict(self, state_dict, strict=True):
+        sched = self.learned_schedule
+        own = {k[len("log_snr."):]: v for k, v in state_dict.items() if k.startswith("log_snr.")}
+        if sched is None:
+            return super().load_state_dict(state_dict, strict=strict)  # log_snr.* keys are unexpected there
+        super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("log_snr.")}, strict=strict)
+        sched.load_state_dict(own, strict=strict)
+        return self
 
     __call__ = forward
 
@@ -272,9 +457,26 @@ class ContinuousTimeGaussianDiffusion(_ContinuousTimeBase):
     ):
         if not isinstance(noise_schedule, str):
             raise ValueError(f'unknown noise schedule {noise_schedule}')
+        if noise_schedule == 'learned':
+            self._unet_for_learned(model)
+            log_snr_max, log_snr_min = [beta_linear_log_snr(torch.tensor([time])).item() for time in (0., 1.)]
+            noise_schedule = learned_noise_schedule(log_snr_max=log_snr_max, log_snr_min=log_snr_min,
+                                                    hidden_dim=learned_schedule_net_hidden_dim,
+                                                    frac_gradient=learned_noise_schedule_frac_gradient)
         self._init(model, image_size, channels, noise_schedule, num_sample_steps, clip_sample_denoised, use_graph)
         self.min_snr_loss_weight = min_snr_loss_weight
         self.min_snr_gamma = min_snr_gamma
+
+    @staticmethod
+    def _unet_for_learned(model):
+        """The learned schedule trains through the library's input-gradient entry: what ``_trainable()`` would refuse is
+        refused at construction."""
+        from .unet import Unet
+
+        if not isinstance(model, Unet) or getattr(model, "_handle", None) is None:
+            raise NotImplementedError("noise_schedule='learned': the learned noise schedule needs the library's input-gradient "
+                                      "entry (dm_unet_loss_backward_ct_ig), hence a library Unet with a handle; got "
+                                      f"{type(model).__name__}")
 
     def q_sample(self, x_start, times, noise=None):
         """:222-231: (x_noised, log_snr)."""

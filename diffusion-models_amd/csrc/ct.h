@@ -40,5 +40,9 @@ int launch_ct_noise_in(const float* img, const float* eps, StepRows r, int objec
 // tab: B device rows (w_b = column CT_LOSS_W); part: B floats of workspace
 int launch_ct_loss(const float* F, const float* target, const float* tab, float* dF, float* part, float* loss, int B,
                    int64_t per, float loss_scale, hipStream_t s);
+// Per image, for a trained schedule: out[b] = [sum dX x0, sum dX eps, dt[b] (0 when dt == nullptr), mean((F - target)^2)];
+// x0 = 2 img - 1 (normalize != 0) or img.  out: B rows of 4 device floats
+int launch_ct_sched_reduce(const float* dx, const float* img, const float* eps, const float* F, const float* target,
+                           const float* dt, int normalize, float* out, int B, int64_t per, hipStream_t s);
 
 }  // namespace dm

@@ -96,7 +96,58 @@ __global__ __launch_bounds__(256) void ct_loss_kernel(const float* __restrict__ 
     if (threadIdx.x == 0) part[b] = (float)(s / per) * w;
 }
 
+// What a schedule that is itself trained needs of one image, one workgroup per image, double sums in a fixed order
+// (block_sum256): with x = alpha_b x0 + sigma_b eps,
+//   out[b] = [ sum dX x0 | sum dX eps | dt[b] (0 without dt) | mean((F - target)^2) ]
+// are dL/d alpha_b, dL/d sigma_b through the noised image, the U-Net's time gradient, and the unweighted per-image loss.
+__global__ __launch_bounds__(256) void ct_sched_reduce_kernel(const float* __restrict__ dx, const float* __restrict__ img,
+                                                              const float* __restrict__ eps, const float* __restrict__ F,
+                                                              const float* __restrict__ target, const float* __restrict__ dt,
+                                                              int normalize, float* __restrict__ out, int per) {
+    __shared__ double red[256];
+    const int b = blockIdx.x;
+    const int64_t base = (int64_t)b * per;
+    double sa = 0.0, ss = 0.0, sl = 0.0;
+    for (int i = threadIdx.x * 4; i < per; i += 256 * 4) {
+        const float4 g4 = ld4(dx, base + i), im4 = ld4(img, base + i), e4 = ld4(eps, base + i);
+        const float4 f4 = ld4(F, base + i), t4 = ld4(target, base + i);
+        const float g[4] = {g4.x, g4.y, g4.z, g4.w}, im[4] = {im4.x, im4.y, im4.z, im4.w}, e[4] = {e4.x, e4.y, e4.z, e4.w};
+        const float f[4] = {f4.x, f4.y, f4.z, f4.w}, t[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float a = normalize ? im[j] * 2.0f - 1.0f : im[j];
+            const float d = f[j] - t[j];
+            sa += (double)g[j] * a;
+            ss += (double)g[j] * e[j];
+            sl += (double)d * d;
+        }
+    }
+    sa = block_sum256(sa, red);
+    __syncthreads();  // every thread has read red[0] before the next sum overwrites it
+    ss = block_sum256(ss, red);
+    __syncthreads();
+    sl = block_sum256(sl, red);
+    if (threadIdx.x == 0) {
+        float* o = out + (size_t)b * 4;
+        o[0] = (float)sa;
+        o[1] = (float)ss;
+        o[2] = dt ? dt[b] : 0.0f;
+        o[3] = (float)(sl / per);
+    }
+}
+
 #pragma clang fp contract(fast)
+
+int launch_ct_sched_reduce(const float* dx, const float* img, const float* eps, const float* F, const float* target,
+                           const float* dt, int normalize, float* out, int B, int64_t per, hipStream_t s) {
+    DM_REQUIRE(dx && img && eps && F && target && out && B > 0, "ct_sched_reduce: null tensor");
+    DM_REQUIRE(per > 0 && per % 4 == 0 && per < (int64_t(1) << 30), "ct_sched_reduce: C*H*W must be a multiple of 4");
+    if (vec4_ok("continuous-time", (int64_t)B * per, {dx, img, eps, F, target})) return 1;
+    hipLaunchKernelGGL(ct_sched_reduce_kernel, dim3(B), dim3(256), 0, s, dx, img, eps, F, target, dt, normalize ? 1 : 0, out,
+                       (int)per);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 
 int launch_ct_step(const float* x, const float* F, const float* noise, int64_t noise_step_stride, StepRows r, int objective,
                    int clip, float* out, float* x_start_out, int64_t n, hipStream_t s) {

@@ -178,6 +178,10 @@ bool init7_eligible(int Cout, int C0, int C1, int KH, int KW, int stride, int pa
 size_t init7_packed_floats(int Cin);
 void init7_pack_weights(const float* oihw, float* packed, int Cin);
 int init7_launch(const ConvParams& p, hipStream_t s);
+// Its input gradient (conv7_dgrad.hip): dX (B, C, H, W) NCHW from dY (B, H, W, Cout) NHWC and the (Cout, C, 7, 7) weight as
+// the parameter stores it; 1 <= C <= 8, any Cout; fixed accumulation order, no workspace
+int launch_conv7_dgrad(const float* dy_nhwc, const float* w_oihw, float* dx_nchw, int B, int H, int W, int Cout, int C,
+                       hipStream_t s);
 
 // 1x1 convolution as a register-direct GEMM (pw_mfma.hip): NHWC, one or two sources, C % 8 == 0, Cout % 64 == 0;
 // w = pw_pack_weights, chunks of 8 input channels.
@@ -498,7 +502,9 @@ int launch_rot_transpose(const float* w, float* out, int Cout, int Cin, int K, i
 int launch_s2d_transpose(const float* w, float* out, int Cout, int C, hipStream_t s);
 // table_dev: device array of {long long src_off; float* dst; long long n;}: dst[i] = param[src_off + i]
 int launch_scatter_copy(const float* param, const void* table_dev, int n_entries, long long max_n, hipStream_t s);
-int launch_grad_norm(const float* grads, int64_t n, double* part_ws, float max_norm, float* out2, hipStream_t s);
+// extra_sq: a squared norm of gradients held elsewhere, added to the sum before the square root (0: these alone)
+int launch_grad_norm(const float* grads, int64_t n, double* part_ws, float max_norm, float* out2, hipStream_t s,
+                     double extra_sq = 0.0);
 int launch_adam(float* p, const float* g, float* m, float* v, const double* coef, int64_t n, double lr, double b1, double b2,
                 double eps, int step, hipStream_t s);
 size_t linattn_bwd_ws_floats(int B, int n, int heads, int dh);

@@ -79,7 +79,15 @@ static int sample_ct_impl(dm_unet* u, const dm_ct_args* a) {
 
 // p_losses of both classes (+ forward's normalisation) and the backward pass: q_sample with the target, the tape forward
 // with log_snr_b as the float time, the weighted loss with its gradient, the backward pass (an entry of run_train).
-static int loss_backward_ct_impl(dm_unet* u, const dm_ct_train_args& a) {
+// ig (dm_unet_loss_backward_ct_ig): the same call, and behind it the gradient with respect to the U-Net's two inputs and
+// the per-image sums a trained schedule needs; only then does the arena hold dX, dt and the (B, 4) rows.
+struct CtInputGradOut {
+    float* sched_out_host;
+    float* dx_out;
+    float* dtime_out;
+};
+
+static int loss_backward_ct_impl(dm_unet* u, const dm_ct_train_args& a, const CtInputGradOut* ig = nullptr) {
     DM_REQUIRE(a.images && a.noise && a.coef_host, "null argument");
     DM_REQUIRE(a.objective == DM_CT_PRED_NOISE || a.objective == DM_CT_PRED_V, "unknown continuous-time objective");
     DM_REQUIRE(u->train && u->train->ft, "dm_unet_train_enable_ft has not been called");
@@ -93,6 +101,7 @@ static int loss_backward_ct_impl(dm_unet* u, const dm_ct_train_args& a) {
     TrainState& T = *u->train;
     const int64_t per = (int64_t)u->cfg.channels * H * W, n = (int64_t)B * per;
     DM_REQUIRE(per % 4 == 0, "C * H * W must be a multiple of 4");
+    float* sched = nullptr;  // (B, 4) rows [ga, gs, dt, l] in the handle's workspace
     auto run = [&](Arena& A, Tape& tp) -> int {
         const StepRows rows{T.coef_dev, nullptr, B > 1 ? STEP_ROW_IMAGE : STEP_ROW_FIRST, per};
         float* x = A.alloc(n);
@@ -100,16 +109,33 @@ static int loss_backward_ct_impl(dm_unet* u, const dm_ct_train_args& a) {
         float* F = A.alloc(n);
         float* dF = A.alloc(n);
         float* part = A.alloc(B);
+        InputGrad g{nullptr, nullptr};
+        if (ig) {
+            g.dx = A.alloc(n);
+            g.dt = A.alloc(B);
+            sched = A.alloc((size_t)B * 4);
+        }
         if (!A.dry && launch_ct_noise_in(a.images, a.noise, rows, objective, a.normalize, x, target, n, s)) return 1;
         if (unet_train_forward(u, A, x, nullptr, F, B, H, W, s, tp, nullptr, 0, nullptr, T.tf_dev)) return 1;
         if (!A.dry && launch_ct_loss(F, target, T.coef_dev, dF, part, T.loss_dev, B, per, a.loss_scale, s)) return 1;
-        return unet_train_backward(u, A, x, dF, B, H, W, s, tp, accumulate);
+        if (unet_train_backward(u, A, x, dF, B, H, W, s, tp, accumulate, ig ? &g : nullptr)) return 1;
+        if (!ig || A.dry) return 0;
+        if (launch_ct_sched_reduce(g.dx, a.images, a.noise, F, target, g.dt, a.normalize, sched, B, per, s)) return 1;
+        if (ig->dx_out) DM_CHECK_HIP(hipMemcpyAsync(ig->dx_out, g.dx, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (ig->dtime_out) DM_CHECK_HIP(hipMemcpyAsync(ig->dtime_out, g.dt, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return 0;
     };
     TrainRun r;
     r.entry = TRAIN_CT;
     r.B = B; r.H = H; r.W = W; r.stream = a.stream; r.loss_out_host = a.loss_out_host;
     r.coef_host = a.coef_host; r.cstride = cstride; r.width = DM_CT_COEFS; r.tf_col = CT_LOG_SNR;
-    return run_train(u, r, run);
+    r.sel[0] = ig ? 1 : 0;  // the two forms allocate differently
+    if (run_train(u, r, run)) return 1;
+    if (!ig || !ig->sched_out_host) return 0;
+    // the workspace stays the handle's: the rows are read back behind the call's own kernels, then the stream is waited for
+    DM_CHECK_HIP(hipMemcpyAsync(ig->sched_out_host, sched, (size_t)B * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+    DM_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
 }
 
 }  // namespace dm
@@ -124,6 +150,43 @@ int dm_sample_ct(dm_unet* u, const dm_ct_args* a) {
 int dm_unet_loss_backward_ct(dm_unet* u, const dm_ct_train_args* a) {
     DM_REQUIRE(u && a, "null argument");
     return loss_backward_ct_impl(u, *a);
+}
+
+int dm_unet_loss_backward_ct_ig(dm_unet* u, const dm_ct_train_ig_args* a) {
+    DM_REQUIRE(u && a, "null argument");
+    const dm_ct_train_args base{a->images, a->noise, a->coef_host, a->coef_stride, a->objective, a->loss_scale, a->accumulate,
+                                a->B, a->H, a->W, a->normalize, a->loss_out_host, a->stream};
+    const CtInputGradOut ig{a->sched_out_host, a->dx_out, a->dtime_out};
+    return loss_backward_ct_impl(u, base, &ig);
+}
+
+int dm_op_ct_sched_reduce(const float* dx, const float* images, const float* eps, const float* F, const float* target,
+                          const float* dt, int normalize, float* out, int B, int64_t per, void* stream) {
+    DM_REQUIRE(dx && images && eps && F && target && out, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (launch_ct_sched_reduce(dx, images, eps, F, target, dt, normalize, out, B, per, s)) return 1;
+    DM_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int dm_op_sinusoid_ft_tgrad(const float* de0, const float* e0, const float* freqs, float* dt, int B, int half, void* stream) {
+    DM_REQUIRE(de0 && e0 && freqs && dt && B > 0 && half > 0, "bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (launch_sinusoid_ft_tgrad(de0, e0, freqs, dt, B, half, s)) return 1;
+    DM_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int dm_op_conv7_dgrad(const float* dy_nchw, const float* weight, float* dx, int B, int H, int W, int Cout, int C, void* stream) {
+    DM_REQUIRE(dy_nchw && weight && dx, "null argument");
+    DM_REQUIRE(B > 0 && H > 0 && W > 0 && Cout > 0 && C >= 1 && C <= 8, "conv7_dgrad: 1..8 input channels");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return run_op(s, [&](Arena& A) -> int {
+        int e = 0;
+        float* g = to_nhwc(A, dy_nchw, B, Cout, H * W, s, &e);
+        if (e) return 1;
+        return A.dry ? 0 : launch_conv7_dgrad(g, weight, dx, B, H, W, Cout, C, s);
+    });
 }
 
 int dm_op_ct_step(const float* x, const float* F, const float* eps, const float* c_host, int rows, int objective, int clip,

@@ -117,6 +117,8 @@ struct TrainState {
     // float-time training (dm_unet_train_enable_ft: ElucidatedDiffusion): the U-Net's time is a float per image and the
     // embedding's `weights` take a gradient (exact zeros when frozen: random_fourier_features has requires_grad = False)
     bool ft = false, freqs_frozen = false;
+    float* init_w_raw = nullptr;  // ft: init_conv.weight as stored (a raw copy, redone after every optimiser step), which
+                                  // launch_conv7_dgrad reads when a call asks for the gradient of the U-Net's input
     std::vector<float> coef_stage;  // the call's coefficient rows at the device width, then its float times
     // workspace bytes per call (measured by a dry run, once): entry, B, H, W, bucketed, the entry's own TrainRun::sel
     std::map<std::array<long long, 9>, size_t> ws_need;
@@ -157,8 +159,12 @@ static int build_conv_bwd(dm_unet* u, TrainState& T, const ConvLayer& L, const s
     ConvBwd& B = T.conv[&L];
     B.kind = kind;
     T.conv_weights.insert(wname);
-    if (kind >= 3) return 0;
     const HostTensor& w = P(u, wname);
+    if (kind == 3 && T.ft) {
+        if (T.own.upload(w.data.data(), w.numel(), &T.init_w_raw)) return 1;
+        T.own.record_raw(wname, T.init_w_raw, w.numel());
+    }
+    if (kind >= 3) return 0;
     std::vector<float> wt;
     const int Cin = L.C0 + L.C1;
     PackSrc src;
@@ -874,9 +880,16 @@ static int upload_table(const std::vector<E>& host, std::vector<E>& cached, E*& 
     return 0;
 }
 
+// Where a call that differentiates through the U-Net's inputs wants them (float-time handles): dx (B, C, H, W), dt (B)
+struct InputGrad {
+    float* dx;
+    float* dt;
+};
+
 static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, const float* dout_nchw, int B, int H, int W,
                                     hipStream_t s, Tape& tp, int accumulate, std::vector<WgradJob>* jobs,
-                                    std::vector<WgradDesc>* wbatch, const std::function<int(int)>& phase_done) {
+                                    std::vector<WgradDesc>* wbatch, const std::function<int(int)>& phase_done,
+                                    const InputGrad* ig) {
     const dm_unet_cfg& cfg = u->cfg;
     const int td = u->time_dim, n_st = cfg.n_stages;
     TCtx t{u, &A, s, B, A.dry ? reinterpret_cast<const float*>(16) : tp.ss, u->ss_total};
@@ -987,10 +1000,14 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
         dcur = dprev;
         if (left_phase(n_st + 2 + (n_st - 1 - i))) return 1;
     }
-    // init_conv: weight / bias gradient only (its input is data)
+    // init_conv: weight / bias gradient; its input is data, so the input gradient runs only for a call that asks for it
     if (conv_wgrad(t, u->init_conv, u->train->conv.at(&u->init_conv), x_nchw, nullptr, dcur, H, W, "init_conv.weight",
                    "init_conv.bias", true))
         return 1;
+    if (ig && !A.dry) {
+        DM_REQUIRE(u->train->init_w_raw != nullptr, "the input gradient needs a handle armed by dm_unet_train_enable_ft");
+        if (launch_conv7_dgrad(dcur, u->train->init_w_raw, ig->dx, B, H, W, u->init_dim, cfg.input_channels, s)) return 1;
+    }
     // ResnetBlock.mlp (SiLU -> Linear), all 19 of them through the concatenated matrix, then (text_concat_proj, text_proj,)
     // time_mlp
     const bool text_concat = cfg.text_mode == DM_TEXT_CONCAT && tp.ctx != nullptr;
@@ -1085,6 +1102,7 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
         if (launch_sinusoid_ft_bwd(de0, tp.e0, t.grad("time_mlp.0.weights"), B, cfg.learned_sinusoidal_dim / 2,
                                    !u->train->freqs_frozen, t.acc, s))
             return 1;
+        if (ig && launch_sinusoid_ft_tgrad(de0, tp.e0, u->freqs, ig->dt, B, cfg.learned_sinusoidal_dim / 2, s)) return 1;
     }
     return 0;
 }
@@ -1094,7 +1112,7 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
 // launch at the end -- independent layers fill the chip, where a lone 64 -> 64 layer had to split its pixels 256 ways and
 // write 38 MB of partial sums -- followed by ONE launch that sums the remaining split-K partial tiles of every layer.
 static int unet_train_backward(dm_unet* u, Arena& A, const float* x_nchw, const float* dout_nchw, int B, int H, int W,
-                               hipStream_t s, Tape& tp, int accumulate) {
+                               hipStream_t s, Tape& tp, int accumulate, const InputGrad* ig = nullptr) {
     std::vector<WgradJob> jobs;
     std::vector<WgradDesc> batch[4];
     TrainState& T = *u->train;
@@ -1145,7 +1163,7 @@ static int unet_train_backward(dm_unet* u, Arena& A, const float* x_nchw, const 
             }
             return 0;
         };
-    if (unet_train_backward_impl(u, A, x_nchw, dout_nchw, B, H, W, s, tp, accumulate, &jobs, batch, phase_done)) return 1;
+    if (unet_train_backward_impl(u, A, x_nchw, dout_nchw, B, H, W, s, tp, accumulate, &jobs, batch, phase_done, ig)) return 1;
     if (flush()) return 1;
     if (!A.dry && T.bucketed && !T.buckets.empty()) DM_CHECK_HIP(hipEventRecord(T.buckets.back().ready, s));
     return 0;
@@ -1783,7 +1801,15 @@ int dm_unet_train_scalar(dm_unet* u, int which, float* out_dev, void* stream) {
 static int ensure_adam_state(TrainState& T);
 int dm_unet_optimizer_step(dm_unet* u, double lr, double beta1, double beta2, double eps, float max_grad_norm,
                            float* grad_norm_out_host, void* stream) {
+    return dm_unet_optimizer_step_ex(u, lr, beta1, beta2, eps, max_grad_norm, 0.0f, grad_norm_out_host, stream);
+}
+
+/* The same step when parameters outside the handle share the clip (a trained noise schedule on the host): extra_sq_norm,
+ * the squared norm of their gradients, joins the sum before the coefficient is formed; the norm returned is the combined one. */
+int dm_unet_optimizer_step_ex(dm_unet* u, double lr, double beta1, double beta2, double eps, float max_grad_norm,
+                              float extra_sq_norm, float* grad_norm_out_host, void* stream) {
     DM_REQUIRE(u && u->train, "dm_unet_train_enable has not been called");
+    DM_REQUIRE(extra_sq_norm >= 0.0f || extra_sq_norm != extra_sq_norm, "extra_sq_norm is a squared norm");
     DM_CHECK_HIP(hipSetDevice(u->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     TrainState& T = *u->train;
@@ -1791,7 +1817,7 @@ int dm_unet_optimizer_step(dm_unet* u, double lr, double beta1, double beta2, do
         if (!T.param && upload_master(u)) return 1;
         if (ensure_adam_state(T)) return 1;
         if (u->order_after_previous(s)) return 1;  // the previous call on this handle may have used another stream
-        if (launch_grad_norm(T.grad, (int64_t)T.grad_floats, T.norm_ws, max_grad_norm, T.clip2, s)) return 1;
+        if (launch_grad_norm(T.grad, (int64_t)T.grad_floats, T.norm_ws, max_grad_norm, T.clip2, s, (double)extra_sq_norm)) return 1;
         T.adam_step += 1;
         if (launch_adam(T.param, T.grad, T.adam_m, T.adam_v, T.norm_ws, (int64_t)T.grad_floats, lr, beta1, beta2, eps,
                         (int)T.adam_step, s))

@@ -64,5 +64,8 @@ int launch_edm_loss(const float* noised, const float* F, const float* x0, const 
 // width 2 half + 1; learned == false writes zeros (random_fourier_features)
 int launch_sinusoid_ft_bwd(const float* de0, const float* e0, float* dw, int B, int half, bool learned, int accumulate,
                            hipStream_t s);
+// The same embedding's gradient with respect to its float time, from the same taped rows (frozen weights pass it on too):
+// dt[b] = de0[b][0] + 2 pi sum_k w_k (de_sin[b][k] cos[b][k] - de_cos[b][k] sin[b][k]), k ascending, summed in double
+int launch_sinusoid_ft_tgrad(const float* de0, const float* e0, const float* freqs, float* dt, int B, int half, hipStream_t s);
 
 }  // namespace dm

@@ -217,6 +217,22 @@ __global__ void sinusoid_ft_bwd_kernel(const float* __restrict__ de0, const floa
     dw[k] = accumulate ? dw[k] + (float)s : (float)s;
 }
 
+// The same module with respect to its input t (:98-100: freqs = t w 2 pi; cat(t, sin, cos)), from the same taped rows:
+//   dt[b] = de0[b][0] + 2 pi sum_k w_k (de_sin[b][k] cos[b][k] - de_cos[b][k] sin[b][k]),   k in order, in double
+// (one thread per image).  It does not ask whether `weights` is trainable: a frozen embedding still passes the gradient on.
+__global__ void sinusoid_ft_tgrad_kernel(const float* __restrict__ de0, const float* __restrict__ e0,
+                                         const float* __restrict__ freqs, float* __restrict__ dt, int B, int half) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int wdt = 2 * half + 1;
+    const float* e = e0 + (size_t)b * wdt;
+    const float* d = de0 + (size_t)b * wdt;
+    double s = 0.0;
+    for (int k = 0; k < half; ++k)
+        s += (double)freqs[k] * ((double)d[1 + k] * (double)e[1 + half + k] - (double)d[1 + half + k] * (double)e[1 + k]);
+    dt[b] = (float)((double)d[0] + 6.283185307179586 * s);
+}
+
 #pragma clang fp contract(fast)
 
 int launch_sinusoid_ft(const float* t, int t_stride, const SamplerState* st, const float* freqs, float* e, int R, int half,
@@ -303,6 +319,13 @@ int launch_sinusoid_ft_bwd(const float* de0, const float* e0, float* dw, int B, 
     DM_REQUIRE(de0 && e0 && dw && B > 0 && half > 0, "sinusoid_ft_bwd: bad argument");
     hipLaunchKernelGGL(sinusoid_ft_bwd_kernel, dim3((half + 63) / 64), dim3(64), 0, s, de0, e0, dw, B, half, learned ? 1 : 0,
                        accumulate ? 1 : 0);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_sinusoid_ft_tgrad(const float* de0, const float* e0, const float* freqs, float* dt, int B, int half, hipStream_t s) {
+    DM_REQUIRE(de0 && e0 && freqs && dt && B > 0 && half > 0, "sinusoid_ft_tgrad: bad argument");
+    hipLaunchKernelGGL(sinusoid_ft_tgrad_kernel, dim3((B + 63) / 64), dim3(64), 0, s, de0, e0, freqs, dt, B, half);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -1222,7 +1222,7 @@ __global__ void sumsq_partial_kernel(const float* __restrict__ x, int64_t n, dou
 // out2 = (norm, coefficient) as floats for the caller; part[0] receives the coefficient in double for adam_kernel (every
 // partial sum has been read by then).
 __global__ __launch_bounds__(64) void clip_coef_kernel(double* __restrict__ part, int nparts, float max_norm,
-                                                       float* __restrict__ out2) {
+                                                       float* __restrict__ out2, double extra_sq) {
     __shared__ double red[64];
     double s = 0.0;
     for (int i = threadIdx.x; i < nparts; i += 64) s += part[i];
@@ -1233,7 +1233,7 @@ __global__ __launch_bounds__(64) void clip_coef_kernel(double* __restrict__ part
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const double norm = sqrt(red[0]);
+        const double norm = sqrt(extra_sq != 0.0 ? red[0] + extra_sq : red[0]);
         // clamp(max_norm / (norm + 1e-6), max = 1.0) keeps a NaN norm (fmin alone would return 1): one NaN gradient makes
         // every clipped gradient NaN, as clip_grad_norm_ does
         const double c = (double)max_norm / (norm + 1e-6);
@@ -1244,11 +1244,11 @@ __global__ __launch_bounds__(64) void clip_coef_kernel(double* __restrict__ part
     }
 }
 int launch_grad_norm(const float* grads, int64_t n, double* part_ws /* 1024 doubles */, float max_norm, float* out2,
-                     hipStream_t s) {
+                     hipStream_t s, double extra_sq) {
     const int nb = (int)std::min<int64_t>(1024, (n + 255) / 256);
     hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, s, grads, n, part_ws);
     DM_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(64), 0, s, part_ws, nb, max_norm, out2);
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(64), 0, s, part_ws, nb, max_norm, out2, extra_sq);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -18,6 +18,11 @@ from typing import Iterable, Optional
 import torch
 
 
+def _schedule_of(diffusion):
+    """The learned noise-schedule module of a continuous-time object (six host parameters), else None."""
+    return getattr(diffusion, "learned_schedule", None)
+
+
 def _unet_of(diffusion):
     """The U-Net of a diffusion object and its state-dict prefix: ``model`` (DenoisingDiffusion and its variants, the
     continuous-time classes) or ``net`` (ElucidatedDiffusion)."""
@@ -37,6 +42,12 @@ class EMA:
         self.initted = False
         self._ema_model = None
         self._ema_model_step = -1
+        # a learned noise schedule is averaged on the host by the same rules, in a module of the EMA's own
+        self._ema_sched = None
+        if _schedule_of(model) is not None:
+            import copy
+
+            self._ema_sched = copy.deepcopy(_schedule_of(model)).requires_grad_(False)
 
     def get_current_decay(self) -> float:
         epoch = max(self.step - self.update_after_step - 1, 0)
@@ -53,9 +64,22 @@ class EMA:
         unet = _unet_of(self.online_model)[0]
         if step <= self.update_after_step or not self.initted:
             unet.ema_update(0.0, copy=True)
+            self._update_schedule(None)
             self.initted = self.initted or step > self.update_after_step
             return
         unet.ema_update(self.get_current_decay(), copy=False)
+        self._update_schedule(self.get_current_decay())
+
+    @torch.no_grad()
+    def _update_schedule(self, decay):
+        """The six tensors of a learned schedule: a copy (``decay`` None), else ``ema.lerp_(online, 1 - decay)``."""
+        if self._ema_sched is None:
+            return
+        for avg, cur in zip(self._ema_sched.parameters(), _schedule_of(self.online_model).parameters()):
+            if decay is None:
+                avg.copy_(cur)
+            else:
+                avg.lerp_(cur, 1.0 - decay)
 
     def state_dict(self):
         """``ema_pytorch.EMA.state_dict()`` as ``Trainer.save`` stores it under ``'ema'`` (:1108): the averaged copy under
@@ -67,6 +91,8 @@ class EMA:
         online = diffusion_state_dict(d)
         out.update({"online_model." + k: v for k, v in online.items()})
         averaged = diffusion_state_dict(d, ema=True) if self.step > 0 else online
+        if self._ema_sched is not None and self.step > 0:
+            averaged.update({"log_snr." + k: v.detach().clone() for k, v in self._ema_sched.state_dict().items()})
         out.update({"ema_model." + k: v for k, v in averaged.items()})
         return out
 
@@ -82,6 +108,9 @@ class EMA:
         averaged = {k[len(pre):]: v for k, v in sd.items() if k.startswith(pre)}
         if not averaged:
             raise KeyError(f"state dict has no '{pre}*' entries")
+        if self._ema_sched is not None:
+            spre = "ema_model.log_snr."
+            self._ema_sched.load_state_dict({k[len(spre):]: v for k, v in sd.items() if k.startswith(spre)})
         if getattr(online, "_training", False):
             if self.step > 0:
                 online.load_ema_state_dict(averaged)
@@ -111,6 +140,8 @@ class EMA:
                         learned_sinusoidal_dim=cfg.learned_sinusoidal_dim, device=d.device)
             self._ema_model = copy.copy(d)
             setattr(self._ema_model, attr, unet)
+            if self._ema_sched is not None:
+                self._ema_model.log_snr = self._ema_sched  # its own schedule: the averages, not the online module
         return self._ema_model
 
     @property
@@ -146,6 +177,13 @@ def save_checkpoint(path, diffusion, *, step: int, ema: Optional[EMA] = None, lr
     opt = _unet_of(diffusion)[0].optimizer_state_dict(lr=lr, betas=betas, eps=eps)
     for st in opt["state"].values():
         st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].cpu(), st["exp_avg_sq"].cpu()
+    if _schedule_of(diffusion) is not None:
+        # the six schedule parameters follow the U-Net's in parameters(): their Adam state takes the next indices
+        n = len(opt["param_groups"][0]["params"])
+        own = diffusion._schedule_optimizer(lr, betas, eps).state_dict()
+        for i, st in own["state"].items():
+            opt["state"][n + i] = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in st.items()}
+        opt["param_groups"][0]["params"] = list(range(n + len(own["param_groups"][0]["params"])))
     data = {"step": int(step), "model": diffusion_state_dict(diffusion), "opt": opt,
             "ema": ema.state_dict() if ema is not None else None, "scaler": None, "version": version}
     torch.save(data, str(path))
@@ -159,7 +197,17 @@ def load_checkpoint(path, diffusion, *, ema: Optional[EMA] = None):
     data = torch.load(str(path), map_location="cpu", weights_only=True)
     diffusion.load_state_dict(data["model"])
     diffusion.train()
-    hyper = _unet_of(diffusion)[0].load_optimizer_state_dict(data["opt"])
+    opt = data["opt"]
+    if _schedule_of(diffusion) is not None:
+        group = dict(opt["param_groups"][0])
+        n = len(group["params"]) - len(list(_schedule_of(diffusion).parameters()))
+        own = diffusion._schedule_optimizer(group["lr"], group["betas"], group["eps"])
+        mine = own.state_dict()
+        mine["state"] = {i - n: st for i, st in opt["state"].items() if i >= n}
+        own.load_state_dict(mine)
+        group["params"] = group["params"][:n]
+        opt = {"state": {i: st for i, st in opt["state"].items() if i < n}, "param_groups": [group]}
+    hyper = _unet_of(diffusion)[0].load_optimizer_state_dict(opt)
     if ema is not None and data.get("ema") is not None:
         ema.load_state_dict(data["ema"])
     return int(data["step"]), hyper
@@ -204,6 +252,10 @@ def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, bet
     if sigmas is not None and not edm:
         raise ValueError("sigmas= is the draw of an ElucidatedDiffusion; this object takes t=")
     # by default on RCCL with more than one rank (gloo stages every collective through pinned host memory: nothing to overlap)
+    sched = _schedule_of(diffusion)
+    if sched is not None and parallel and dist.get_world_size(group) > 1:
+        raise NotImplementedError("a learned noise schedule under more than one rank: averaging its six host gradients "
+                                  "across the ranks is not built")
     overlap = parallel and bucketed is not False and hasattr(unet, "grad_buckets") and (
         bucketed or (dist.get_world_size(group) > 1 and dist.get_backend(group) == "nccl"))
     if overlap != getattr(unet, "_bucketed", False) and hasattr(unet, "grad_buckets"):
@@ -265,6 +317,20 @@ def train_step(diffusion, micro_batches: Iterable[torch.Tensor], *, lr=1e-4, bet
         if ev is not None:
             ev[1].record()
             timing.setdefault("allreduce_events", []).append(ev)
+    if sched is not None:
+        # the six host parameters share the clip: their squared norm joins the library's, the host applies the same
+        # coefficient (clip_grad_norm_: max_norm / (total + 1e-6), capped at 1) and takes the same Adam step
+        grads = [p.grad for p in sched.parameters() if p.grad is not None]
+        sq = float(sum(float(g.double().pow(2).sum()) for g in grads))
+        norm = unet.optimizer_step(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, extra_sq_norm=sq)
+        if max_grad_norm:
+            coef = min(1.0, max_grad_norm / (norm + 1e-6))
+            for g in grads:
+                g.mul_(coef)
+        diffusion._schedule_optimizer(lr, betas, eps).step()
+        if ema is not None:
+            ema.update()
+        return total, norm
     norm = unet.optimizer_step(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, **lazy)
     if ema is not None:
         ema.update()

@@ -253,16 +253,22 @@ class Unet:
         off, cnt = C.c_int64(0), C.c_int64(0)
         _lib.check(self._lib.dm_unet_train_bucket(self._handle, i, C.byref(off), C.byref(cnt), 1, stream.cuda_stream))
 
-    def optimizer_step(self, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, sync=True):
+    def optimizer_step(self, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, max_grad_norm=1.0, sync=True, extra_sq_norm=0.0):
         """``clip_grad_norm_(max_grad_norm)`` + ``Adam(lr, betas).step()`` of ``Trainer.train``
         (denoising_diffusion.py:1006, :1178-1183) on the device-resident parameters; every packed weight buffer is then
         rebuilt on the device.  Returns the total gradient norm (before clipping): a float, or with ``sync=False`` a
-        0-dim device tensor (``clip_grad_norm_`` returns one too) without waiting for the GPU."""
+        0-dim device tensor (``clip_grad_norm_`` returns one too) without waiting for the GPU.  ``extra_sq_norm``: the
+        squared gradient norm of parameters held outside the handle (a learned noise schedule's) that share the clip; the
+        norm returned is then the combined one (``dm_unet_optimizer_step_ex``)."""
         norm = C.c_float(0.0)
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(self._lib.dm_unet_optimizer_step(self._handle, lr, betas[0], betas[1], eps,
-                                                    max_grad_norm if max_grad_norm else 0.0, C.byref(norm) if sync else None,
-                                                    stream))
+        clip = max_grad_norm if max_grad_norm else 0.0
+        out_norm = C.byref(norm) if sync else None
+        if extra_sq_norm:
+            _lib.check(self._lib.dm_unet_optimizer_step_ex(self._handle, lr, betas[0], betas[1], eps, clip, float(extra_sq_norm),
+                                                           out_norm, stream))
+        else:
+            _lib.check(self._lib.dm_unet_optimizer_step(self._handle, lr, betas[0], betas[1], eps, clip, out_norm, stream))
         if sync:
             return float(norm.value)
         out = torch.empty((), device=self.device, dtype=torch.float32)

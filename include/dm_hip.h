@@ -453,6 +453,12 @@ int dm_unet_loss_backward_masked(dm_unet* u, const dm_train_args* a, const int32
  *   dm_unet_check_device_pack: self-check, number of packed buffers whose device packer differs from the host packer */
 int dm_unet_optimizer_step(dm_unet* u, double lr, double beta1, double beta2, double eps, float max_grad_norm,
                            float* grad_norm_out_host, void* stream);
+/* The same step when parameters OUTSIDE the handle share the clip (the six host parameters of a learned noise schedule):
+ * extra_sq_norm, the squared L2 norm of their gradients, is added to the handle's squared gradient norm before the clip
+ * coefficient min(1, max_grad_norm / (norm + 1e-6)) is formed; *grad_norm_out_host is the combined norm, from which the caller
+ * forms the same coefficient for its own parameters.  extra_sq_norm == 0 is dm_unet_optimizer_step. */
+int dm_unet_optimizer_step_ex(dm_unet* u, double lr, double beta1, double beta2, double eps, float max_grad_norm,
+                              float extra_sq_norm, float* grad_norm_out_host, void* stream);
 /* The loop's scalars without a host round trip (the reference's loss is a device tensor until Trainer calls loss.item(),
  * DD/denoising_diffusion.py:1173): with loss_out_host == NULL dm_unet_loss_backward, and with grad_norm_out_host == NULL
  * dm_unet_optimizer_step, return as soon as their kernels are enqueued; dm_unet_train_scalar copies the loss of the last
@@ -769,6 +775,47 @@ int dm_op_ct_noise_in(const float* images, const float* eps, const float* c_host
                       float* x, float* target, int B, int64_t per, void* stream);
 int dm_op_ct_loss(const float* F, const float* target, const float* c_host, float loss_scale, float* dF,
                   float* loss_out_host, int B, int64_t per, void* stream);
+
+/* The same call, and behind it the gradient of the loss with respect to the U-Net's INPUTS -- what a learned noise schedule
+ * (DD/continuous_time_gaussian_diffusion.py:57-95: log_snr_b = net(t_b) reaches the loss through x = alpha_b x0 + sigma_b eps,
+ * through the U-Net's time and through the loss weight) or any other differentiate-through-the-denoiser use needs:
+ *   dX = dL/dx (B,C,H,W): the 7x7 input gradient of init_conv;   dt_b = dL/d(log_snr_b) through the time embedding;
+ *   sched_out_host  (B, 4) floats, written after the call's own stream wait (NULL: not read back, nothing waited for it):
+ *                   [ ga_b = sum dX x0 | gs_b = sum dX eps | dt_b | l_b = mean((F - target)^2), unweighted ]
+ *                   (x0 the normalised image when normalize != 0).  With alpha, sigma, w functions of log_snr on the host,
+ *                   d loss / d log_snr_b = ga_b alpha' + gs_b sigma' + dt_b + loss_scale l_b w' / B.
+ *   dx_out, dtime_out   optional DEVICE buffers (B,C,H,W) / (B) that receive dX / dt.
+ * The first 13 fields are dm_ct_train_args, field for field; loss, dF and every parameter gradient are what
+ * dm_unet_loss_backward_ct produces on them.  The input-gradient kernels and their workspace exist in this entry only. */
+typedef struct dm_ct_train_ig_args {
+    const float* images;
+    const float* noise;
+    const float* coef_host;
+    int32_t coef_stride;
+    int32_t objective;
+    float loss_scale;
+    int32_t accumulate;
+    int32_t B, H, W;
+    int32_t normalize;
+    float* loss_out_host;
+    void* stream;
+    float* sched_out_host;  /* (B, 4) host floats or NULL */
+    float* dx_out;          /* device (B,C,H,W) or NULL */
+    float* dtime_out;       /* device (B) or NULL */
+} dm_ct_train_ig_args;
+int dm_unet_loss_backward_ct_ig(dm_unet* u, const dm_ct_train_ig_args* args);
+
+/* The three input-gradient passes on their own (tests); device tensors, each call waits for its result.
+ *   conv7_dgrad:       dx (B,C,H,W) = input gradient of a 7x7 / pad 3 convolution from dy (B,Cout,H,W) and its
+ *                      (Cout,C,7,7) weight; 1 <= C <= 8, any Cout; fp32, fixed accumulation order, every element of dx written.
+ *   sinusoid_ft_tgrad: dt[b] = de0[b][0] + 2 pi sum_k freqs[k] (de_sin[b][k] cos[b][k] - de_cos[b][k] sin[b][k]) from the
+ *                      taped rows e0[b] = [t | sin | cos] of width 2 half + 1 (layout of dm_op_sinusoid_ft_bwd).
+ *   ct_sched_reduce:   out (B, 4) DEVICE rows [sum dx x0 | sum dx eps | dt[b], 0 when dt == NULL | mean((F - target)^2)],
+ *                      x0 = 2 images - 1 (normalize != 0) or images; per % 4 == 0, 16-byte aligned tensors. */
+int dm_op_conv7_dgrad(const float* dy_nchw, const float* weight, float* dx, int B, int H, int W, int Cout, int C, void* stream);
+int dm_op_sinusoid_ft_tgrad(const float* de0, const float* e0, const float* freqs, float* dt, int B, int half, void* stream);
+int dm_op_ct_sched_reduce(const float* dx, const float* images, const float* eps, const float* F, const float* target,
+                          const float* dt, int normalize, float* out, int B, int64_t per, void* stream);
 
 /* ---- RePaint inpainting (arXiv 2201.09865 as DD/repaint.py:614-681 has it): the DDPM loop over a trained U-Net with the
  * pixels where mask == 1 taken from a ground-truth image and the rest generated, and with "resampling" jumps back up the
