@@ -92,9 +92,13 @@ struct HostTensor {
 
 // Recipe of one packed weight buffer (recorded while the host packs it): which parameter it comes from and which packer
 // made it, so that the training loop can re-pack it on the DEVICE from the flat master parameters (pack_kernels.hip).
+enum PackSrcKind {
+    PS_STORED,  // the parameter as stored
+    PS_ROT,     // rotated / transposed rows [c_lo, c_lo + c_n) of a (sCout, sCin, sK, sK) parameter (input-gradient convolution)
+    PS_S2D_T,   // Downsample input-gradient transpose of a (sCout, 4 sCin) parameter
+};
 struct PackSrc {
-    int kind = 0;  // 0: the parameter as stored; 1: rotated / transposed rows [c_lo, c_lo + c_n) of a (sCout, sCin, sK, sK)
-                   // parameter (input-gradient convolution); 2: Downsample input-gradient transpose of a (sCout, 4 sCin) parameter
+    PackSrcKind kind = PS_STORED;
     std::string wname, bname;
     int sCout = 0, sCin = 0, sK = 0, c_lo = 0, c_n = 0;
 };
@@ -117,8 +121,7 @@ struct DeviceOwner {
     bool refreshing = false;
     size_t cursor = 0;
     std::vector<PackOp>* rec = nullptr;  // when set, make_conv / up1 append the recipe of every buffer they upload
-    PackSrc src;                         // the source of the convolution being packed (set by the caller of make_conv)
-    void record(int kind, float* dst, size_t n, int Cout, int C0, int C1, int KH, int KW) {
+    void record(int kind, float* dst, size_t n, int Cout, int C0, int C1, int KH, int KW, const PackSrc& src) {
         if (rec && !refreshing) rec->push_back(PackOp{kind, dst, n, Cout, C0, C1, KH, KW, src, std::string()});
     }
     void record_raw(const std::string& name, float* dst, size_t n) {
@@ -231,6 +234,8 @@ struct Arena {
     }
 };
 
+#include "conv_family.inc"
+
 struct ConvLayer {
     int C0 = 0, C1 = 0, Cout = 0, KH = 1, KW = 1, stride = 1, pad = 0;
     int pad_w = -1;     // zero columns left / right when they differ from `pad` rows (1x7 / 7x1 convs of InceptionV3); -1: pad
@@ -238,17 +243,14 @@ struct ConvLayer {
     bool up = false;    // nearest x2 in front of the conv (Upsample, DD/denoising_diffusion.py:48-52)
     bool fold = false;  // ... executed as four 2x2 parity convs on the source grid (ConvParams::fold)
     int fold_w_stride = 0;
-    float* w = nullptr;
-    float* ww = nullptr;  // Winograd-transformed weights (winograd_mfma.hip) when the layer is eligible
-    float* ww4 = nullptr;  // F(4x4,3x3) transformed weights (wino4_mfma.hip)
-    float* wwu = nullptr;  // transformed weights of the upsample + 3x3 algorithm (upwino_mfma.hip)
-    float* wpw = nullptr;  // lane-ordered weights of the 1x1 GEMM kernel (pw_mfma.hip)
-    float* wi7 = nullptr;  // weights of the 7x7 first-conv kernel (init7_mfma.hip)
-    float* wraw = nullptr;  // (Cout, Cin) weights of a 1x1 conv with Cout <= 8 (pointwise_small_kernel)
+    float* packed[CONV_KINDS] = {};  // the weights in the layout of every family the layer is eligible for (conv_family.inc)
     float* bias = nullptr;
+    PackSrc src;  // the parameters the layer is packed from: weight and bias name (empty: anonymous weights of a single
+                  // operator); an input-gradient layer also says which rotated / transposed part of the weight it holds
 };
 
 struct ResBlock {
+    std::string prefix;  // parameter-name prefix of the block (as for AttnLayer and CrossLayer: set where the layer is built)
     ConvLayer c1, c2, res;
     bool has_res = false;
     float *g1 = nullptr, *g2 = nullptr;
@@ -256,6 +258,7 @@ struct ResBlock {
 };
 
 struct AttnLayer {
+    std::string prefix;
     bool full = false;
     int dim = 0, heads = 0;  // heads: attn_heads of the layer's stage (cast_tuple(attn_heads, num_stages), :294)
     float *norm_g = nullptr, *mem_kv = nullptr, *out_g = nullptr;
@@ -267,6 +270,7 @@ struct AttnLayer {
 };
 
 struct CrossLayer {
+    std::string prefix;
     ConvLayer q, out;
     float *wk = nullptr, *wv = nullptr, *g = nullptr;
     float* wo_raw = nullptr;  // to_out.0.weight as stored (dim, inner): the one-context-token path runs it per image
@@ -407,22 +411,19 @@ static void expect_resnet(dm_unet* u, const std::string& p, int din, int dout) {
 // attn_heads of stage i (Unet(attn_heads = (..)), :294: cast_tuple over the stages; mid_attn takes the last stage's, :324)
 static int stage_heads(const dm_unet_cfg& cfg, int i) { return cfg.attn_heads_stage[i] > 0 ? cfg.attn_heads_stage[i] : cfg.attn_heads; }
 
+// the output projection of an attention layer: Attention.to_out is a convolution, LinearAttention.to_out is
+// Sequential(convolution, RMSNorm)
+static std::string attn_out_param(const std::string& p, bool full) { return p + (full ? ".to_out" : ".to_out.0"); }
+
 static void expect_attn(dm_unet* u, const std::string& p, int dim, bool full, int heads) {
     int hidden = heads * u->dh;
-    if (full) {
-        expect(u, p + ".mem_kv", {2, heads, 4, u->dh});
-        expect(u, p + ".norm.g", {1, dim, 1, 1});
-        expect(u, p + ".to_qkv.weight", {3 * hidden, dim, 1, 1});
-        expect(u, p + ".to_out.weight", {dim, hidden, 1, 1});
-        expect(u, p + ".to_out.bias", {dim});
-    } else {
-        expect(u, p + ".mem_kv", {2, heads, u->dh, 4});
-        expect(u, p + ".norm.g", {1, dim, 1, 1});
-        expect(u, p + ".to_qkv.weight", {3 * hidden, dim, 1, 1});
-        expect(u, p + ".to_out.0.weight", {dim, hidden, 1, 1});
-        expect(u, p + ".to_out.0.bias", {dim});
-        expect(u, p + ".to_out.1.g", {1, dim, 1, 1});
-    }
+    const std::string out = attn_out_param(p, full);
+    expect(u, p + ".mem_kv", full ? std::vector<int64_t>{2, heads, 4, u->dh} : std::vector<int64_t>{2, heads, u->dh, 4});
+    expect(u, p + ".norm.g", {1, dim, 1, 1});
+    expect(u, p + ".to_qkv.weight", {3 * hidden, dim, 1, 1});
+    expect(u, out + ".weight", {dim, hidden, 1, 1});
+    expect(u, out + ".bias", {dim});
+    if (!full) expect(u, p + ".to_out.1.g", {1, dim, 1, 1});
 }
 
 static void expect_cross(dm_unet* u, const std::string& p, int dim) {
@@ -439,18 +440,20 @@ static void expect_cross(dm_unet* u, const std::string& p, int dim) {
 static std::string idx(const std::string& a, int i) { return a + "." + std::to_string(i); }
 
 // ---- weight upload ----------------------------------------------------------------------
+// Pack an OIHW weight into the layout of every kernel family the layer is eligible for (conv_family.inc) and upload those
+// and the bias.  The recorded recipes take their source from L.src, which the caller has set (default: anonymous).
 static int make_conv(DeviceOwner& own, ConvLayer& L, const float* oihw, const float* bias, int Cout, int C0, int C1, int KH,
                      int KW, int stride, int pad, bool up, int pad_hi = 0) {
     L.C0 = C0; L.C1 = C1; L.Cout = Cout; L.KH = KH; L.KW = KW; L.stride = stride; L.pad = pad; L.up = up;
     L.pad_hi = pad_hi;
-    L.fold = up && KH == 3 && KW == 3 && stride == 1 && pad == 1;
-    std::vector<float> packed;
+    L.fold = conv_folds(KH, KW, stride, pad, up);
+    std::fill(L.packed, L.packed + CONV_KINDS, nullptr);
     if (L.fold) {
         // nearest x2 then conv3x3 == one 2x2 conv per output parity with summed taps:
         //   parity 0 along an axis: source offsets {-1, 0} <- taps {0}, {1,2};  parity 1: {0, +1} <- taps {0,1}, {2}
         const int Cin = C0 + C1;
         const size_t per = conv_packed_floats(Cout, C0, C1, 2, 2);
-        packed.resize(4 * per);
+        std::vector<float> packed(4 * per);
         std::vector<float> w2((size_t)Cout * Cin * 4);
         auto taps = [](int parity, int a, int* lo, int* hi) {
             if (parity == 0) { *lo = a == 0 ? 0 : 1; *hi = a == 0 ? 0 : 2; }
@@ -472,62 +475,21 @@ static int make_conv(DeviceOwner& own, ConvLayer& L, const float* oihw, const fl
                 conv_pack_weights(w2.data(), packed.data() + (size_t)(py * 2 + px) * per, Cout, C0, C1, 2, 2);
             }
         L.fold_w_stride = (int)per;
-    } else {
-        packed.resize(conv_packed_floats(Cout, C0, C1, KH, KW));
-        conv_pack_weights(oihw, packed.data(), Cout, C0, C1, KH, KW);
+        if (own.upload(packed.data(), packed.size(), &L.packed[CONV_DIRECT])) return 1;
+        own.record(PK_FOLD, L.packed[CONV_DIRECT], packed.size(), Cout, C0, C1, KH, KW, L.src);
     }
-    if (own.upload(packed.data(), packed.size(), &L.w)) return 1;
-    own.record(L.fold ? PK_FOLD : PK_DIRECT, L.w, packed.size(), Cout, C0, C1, KH, KW);
-    L.ww = nullptr;
-    if (wino_eligible(Cout, C0, C1, KH, KW, stride, pad, up)) {
-        std::vector<float> wp(wino_packed_floats(Cout, C0, C1));
-        wino_pack_weights(oihw, wp.data(), Cout, C0, C1);
-        if (own.upload(wp.data(), wp.size(), &L.ww)) return 1;
-        own.record(PK_WINO, L.ww, wp.size(), Cout, C0, C1, KH, KW);
-    }
-    L.ww4 = nullptr;
-    if (wino4_eligible(Cout, C0, C1, KH, KW, stride, pad, up)) {
-        std::vector<float> wp(wino4_packed_floats(Cout, C0, C1));
-        wino4_pack_weights(oihw, wp.data(), Cout, C0, C1);
-        if (own.upload(wp.data(), wp.size(), &L.ww4)) return 1;
-        own.record(PK_WINO4, L.ww4, wp.size(), Cout, C0, C1, KH, KW);
-    }
-    L.wwu = nullptr;
-    if (upwino_eligible(Cout, C0, C1, KH, KW, stride, pad, up)) {
-        std::vector<float> wp(upwino_packed_floats(Cout, C0, C1));
-        upwino_pack_weights(oihw, wp.data(), Cout, C0, C1);
-        if (own.upload(wp.data(), wp.size(), &L.wwu)) return 1;
-        own.record(PK_UPWINO, L.wwu, wp.size(), Cout, C0, C1, KH, KW);
-    }
-    L.wpw = nullptr;
-    if (pw_eligible(Cout, C0, C1, KH, KW, stride, pad, up)) {
-        std::vector<float> wp(pw_packed_floats(Cout, C0, C1));
-        pw_pack_weights(oihw, wp.data(), Cout, C0, C1);
-        if (own.upload(wp.data(), wp.size(), &L.wpw)) return 1;
-        own.record(PK_PW, L.wpw, wp.size(), Cout, C0, C1, KH, KW);
-    }
-    if (pw_s2d_eligible(Cout, C0, C1, KH, KW, stride, pad, up)) {
-        std::vector<float> wp((size_t)4 * C0 * Cout);
-        pw_pack_weights_s2d(oihw, wp.data(), Cout, C0);
-        if (own.upload(wp.data(), wp.size(), &L.wpw)) return 1;
-        own.record(PK_PW_S2D, L.wpw, wp.size(), Cout, C0, C1, KH, KW);
-    }
-    L.wi7 = nullptr;
-    if (init7_eligible(Cout, C0, C1, KH, KW, stride, pad, up)) {
-        std::vector<float> wp(init7_packed_floats(C0));
-        init7_pack_weights(oihw, wp.data(), C0);
-        if (own.upload(wp.data(), wp.size(), &L.wi7)) return 1;
-        own.record(PK_INIT7, L.wi7, wp.size(), Cout, C0, C1, KH, KW);
-    }
-    L.wraw = nullptr;
-    if (KH == 1 && KW == 1 && stride == 1 && pad == 0 && !up && Cout <= 8 && C1 == 0 && C0 % 4 == 0) {
-        if (own.upload(oihw, (size_t)Cout * C0, &L.wraw)) return 1;
-        own.record(PK_RAW_W, L.wraw, (size_t)Cout * C0, Cout, C0, C1, KH, KW);
-    }
+    for (int k = 0; k < CONV_KINDS; ++k)
+        for (const ConvRecipe& R : conv_families[k].recipe) {
+            if (!R.eligible || !R.eligible(Cout, C0, C1, KH, KW, stride, pad, up)) continue;
+            std::vector<float> wp(R.floats(Cout, C0, C1, KH, KW));
+            R.pack(oihw, wp.data(), Cout, C0, C1, KH, KW);
+            if (own.upload(wp.data(), wp.size(), &L.packed[k])) return 1;
+            own.record(R.pk, L.packed[k], wp.size(), Cout, C0, C1, KH, KW, L.src);
+        }
     L.bias = nullptr;
     if (bias) {
         if (own.upload(bias, Cout, &L.bias)) return 1;
-        own.record(PK_RAW_B, L.bias, Cout, Cout, C0, C1, KH, KW);
+        own.record(PK_RAW_B, L.bias, Cout, Cout, C0, C1, KH, KW, L.src);
     }
     return 0;
 }
@@ -540,11 +502,20 @@ static int up1(dm_unet* u, const std::string& n, float** out) {
     u->own.record_raw(n, *out, t.data.size());
     return 0;
 }
-// the parameters make_conv is about to pack (for the device-side re-packing recipe)
-static void conv_src(dm_unet* u, const std::string& wname, const std::string& bname) {
-    u->own.src = PackSrc();
-    u->own.src.wname = wname;
-    u->own.src.bname = bname;
+// a layer of the handle from its parameters; the layer keeps their names (bname empty: no bias) for the device-side
+// re-packing recipes and for the backward pass
+static int make_conv(dm_unet* u, ConvLayer& L, const std::string& wname, const std::string& bname, int Cout, int C0, int C1,
+                     int KH, int KW, int stride, int pad, bool up, int pad_hi = 0) {
+    L.src = PackSrc();
+    L.src.wname = wname;
+    L.src.bname = bname;
+    return make_conv(u->own, L, P(u, wname).data.data(), bname.empty() ? nullptr : P(u, bname).data.data(), Cout, C0, C1, KH,
+                     KW, stride, pad, up, pad_hi);
+}
+// the parameters of the resample layer of stage q: Sequential(Rearrange / Upsample, conv) in every stage but the last,
+// where it is a plain 3x3 convolution
+static std::string resample_param(const std::string& q, bool last_stage, const char* leaf) {
+    return q + (last_stage ? ".3." : ".3.1.") + leaf;
 }
 
 // One weight group = everything packed from the parameters under one name prefix.  First build: run `build` and
@@ -581,26 +552,17 @@ static int weight_group(dm_unet* u, const std::string& prefix, F build) {
 static int build_resnet(dm_unet* u, ResBlock& R, const std::string& p, int C0, int C1, int dout, int& ss_off) {
     // the mlp (SiLU -> Linear) of every ResnetBlock is one row block of the concatenated [ss_total][time_dim] matrix
     // assembled by build_scale_shift
+    R.prefix = p;
     R.dout = dout;
     R.ss_off = ss_off;
     ss_off += 2 * dout;
     if (!u->own.refreshing) u->resnets.emplace_back(p, &R);
     return weight_group(u, p, [&]() -> int {
-        int din = C0 + C1;
-        conv_src(u, p + ".block1.proj.weight", p + ".block1.proj.bias");
-        if (make_conv(u->own, R.c1, P(u, p + ".block1.proj.weight").data.data(), P(u, p + ".block1.proj.bias").data.data(),
-                      dout, C0, C1, 3, 3, 1, 1, false)) return 1;
-        conv_src(u, p + ".block2.proj.weight", p + ".block2.proj.bias");
-        if (make_conv(u->own, R.c2, P(u, p + ".block2.proj.weight").data.data(), P(u, p + ".block2.proj.bias").data.data(),
-                      dout, dout, 0, 3, 3, 1, 1, false)) return 1;
+        if (make_conv(u, R.c1, p + ".block1.proj.weight", p + ".block1.proj.bias", dout, C0, C1, 3, 3, 1, 1, false)) return 1;
+        if (make_conv(u, R.c2, p + ".block2.proj.weight", p + ".block2.proj.bias", dout, dout, 0, 3, 3, 1, 1, false)) return 1;
         if (up1(u, p + ".block1.norm.g", &R.g1) || up1(u, p + ".block2.norm.g", &R.g2)) return 1;
-        R.has_res = din != dout;
-        if (R.has_res) {
-            conv_src(u, p + ".res_conv.weight", p + ".res_conv.bias");
-            if (make_conv(u->own, R.res, P(u, p + ".res_conv.weight").data.data(), P(u, p + ".res_conv.bias").data.data(),
-                          dout, C0, C1, 1, 1, 1, 0, false)) return 1;
-        }
-        return 0;
+        R.has_res = C0 + C1 != dout;
+        return R.has_res ? make_conv(u, R.res, p + ".res_conv.weight", p + ".res_conv.bias", dout, C0, C1, 1, 1, 1, 0, false) : 0;
     });
 }
 
@@ -653,35 +615,30 @@ static int fuse_linattn(DeviceOwner& own, AttnLayer& A, const float* w_qkv, cons
 }
 
 static int build_attn_body(dm_unet* u, AttnLayer& A, const std::string& p, int dim, bool full, int heads) {
+    A.prefix = p;
     A.full = full;
     A.dim = dim;
     A.heads = heads;
     int hidden = heads * u->dh;
     if (up1(u, p + ".norm.g", &A.norm_g) || up1(u, p + ".mem_kv", &A.mem_kv)) return 1;
-    conv_src(u, p + ".to_qkv.weight", "");
-    if (make_conv(u->own, A.qkv, P(u, p + ".to_qkv.weight").data.data(), nullptr, 3 * hidden, dim, 0, 1, 1, 1, 0, false))
-        return 1;
+    const std::string out = attn_out_param(p, full);
+    if (make_conv(u, A.qkv, p + ".to_qkv.weight", "", 3 * hidden, dim, 0, 1, 1, 1, 0, false)) return 1;
+    if (make_conv(u, A.out, out + ".weight", out + ".bias", dim, hidden, 0, 1, 1, 1, 0, false)) return 1;
     if (full) {
-        conv_src(u, p + ".to_out.weight", p + ".to_out.bias");
-        if (make_conv(u->own, A.out, P(u, p + ".to_out.weight").data.data(), P(u, p + ".to_out.bias").data.data(), dim,
-                      hidden, 0, 1, 1, 1, 0, false)) return 1;
         A.has16 = false;
         if (attn16_eligible(dim, heads, u->dh)) {
             std::vector<float> wp, wo;
             attn16_pack(P(u, p + ".to_qkv.weight").data.data(), P(u, p + ".norm.g").data.data(),
-                        P(u, p + ".to_out.weight").data.data(), dim, wp, wo);
+                        P(u, out + ".weight").data.data(), dim, wp, wo);
             float *dwp, *dwo;
             if (u->own.upload(wp.data(), wp.size(), &dwp) || u->own.upload(wo.data(), wo.size(), &dwo)) return 1;
             A.a16 = Attn16{dim, dwp, dwo, A.out.bias, A.mem_kv};
             A.has16 = true;
         }
     } else {
-        conv_src(u, p + ".to_out.0.weight", p + ".to_out.0.bias");
-        if (make_conv(u->own, A.out, P(u, p + ".to_out.0.weight").data.data(), P(u, p + ".to_out.0.bias").data.data(),
-                      dim, hidden, 0, 1, 1, 1, 0, false)) return 1;
         if (up1(u, p + ".to_out.1.g", &A.out_g)) return 1;
         if (fuse_linattn(u->own, A, P(u, p + ".to_qkv.weight").data.data(), P(u, p + ".norm.g").data.data(),
-                         P(u, p + ".to_out.0.weight").data.data(), P(u, p + ".mem_kv").data.data(),
+                         P(u, out + ".weight").data.data(), P(u, p + ".mem_kv").data.data(),
                          P(u, p + ".to_out.1.g").data.data(), dim, heads, u->dh))
             return 1;
     }
@@ -694,12 +651,10 @@ static int build_attn(dm_unet* u, AttnLayer& A, const std::string& p, int dim, b
 
 static int build_cross_body(dm_unet* u, CrossLayer& C, const std::string& p, int dim) {
     int inner = 4 * u->dh;
+    C.prefix = p;
     // nn.Linear weights [out, in] are 1x1 conv weights (out, in, 1, 1)
-    conv_src(u, p + ".to_q.weight", "");
-    if (make_conv(u->own, C.q, P(u, p + ".to_q.weight").data.data(), nullptr, inner, dim, 0, 1, 1, 1, 0, false)) return 1;
-    conv_src(u, p + ".to_out.0.weight", p + ".to_out.0.bias");
-    if (make_conv(u->own, C.out, P(u, p + ".to_out.0.weight").data.data(), P(u, p + ".to_out.0.bias").data.data(), dim,
-                  inner, 0, 1, 1, 1, 0, false)) return 1;
+    if (make_conv(u, C.q, p + ".to_q.weight", "", inner, dim, 0, 1, 1, 1, 0, false)) return 1;
+    if (make_conv(u, C.out, p + ".to_out.0.weight", p + ".to_out.0.bias", dim, inner, 0, 1, 1, 1, 0, false)) return 1;
     if (up1(u, p + ".to_k.weight", &C.wk) || up1(u, p + ".to_v.weight", &C.wv) || up1(u, p + ".to_out.1.g", &C.g) ||
         up1(u, p + ".to_out.0.weight", &C.wo_raw))
         return 1;
@@ -734,9 +689,8 @@ static int build_all(dm_unet* u) {
         }))
         return 1;
     if (weight_group(u, "init_conv", [&]() -> int {
-            conv_src(u, "init_conv.weight", "init_conv.bias");
-            return make_conv(u->own, u->init_conv, P(u, "init_conv.weight").data.data(), P(u, "init_conv.bias").data.data(),
-                             u->init_dim, cfg.input_channels, 0, 7, 7, 1, 3, false);
+            return make_conv(u, u->init_conv, "init_conv.weight", "init_conv.bias", u->init_dim, cfg.input_channels, 0, 7, 7, 1,
+                             3, false);
         }))
         return 1;
     int ss_off = 0;
@@ -750,14 +704,11 @@ static int build_all(dm_unet* u) {
         if (build_resnet(u, S.b2, q + ".1", din, 0, din, ss_off)) return 1;
         if (build_attn(u, S.attn, q + ".2", din, cfg.full_attn[i] != 0, stage_heads(cfg, i))) return 1;
         if (weight_group(u, q + ".3", [&]() -> int {
-                conv_src(u, i < n - 1 ? q + ".3.1.weight" : q + ".3.weight", i < n - 1 ? q + ".3.1.bias" : q + ".3.bias");
-                if (i < n - 1) {
-                    // pixel-unshuffle + 1x1  ==  2x2 stride-2 conv: W'[o][c][p1][p2] = W[o][c*4 + p1*2 + p2]
-                    return make_conv(u->own, S.resample, P(u, q + ".3.1.weight").data.data(),
-                                     P(u, q + ".3.1.bias").data.data(), dout, din, 0, 2, 2, 2, 0, false);
-                }
-                return make_conv(u->own, S.resample, P(u, q + ".3.weight").data.data(), P(u, q + ".3.bias").data.data(),
-                                 dout, din, 0, 3, 3, 1, 1, false);
+                const bool last = i == n - 1;
+                const std::string w = resample_param(q, last, "weight"), b = resample_param(q, last, "bias");
+                if (last) return make_conv(u, S.resample, w, b, dout, din, 0, 3, 3, 1, 1, false);
+                // pixel-unshuffle + 1x1  ==  2x2 stride-2 conv: W'[o][c][p1][p2] = W[o][c*4 + p1*2 + p2]
+                return make_conv(u, S.resample, w, b, dout, din, 0, 2, 2, 2, 0, false);
             }))
             return 1;
     }
@@ -773,20 +724,16 @@ static int build_all(dm_unet* u) {
         if (build_resnet(u, S.b2, q + ".1", dout, din, dout, ss_off)) return 1;
         if (build_attn(u, S.attn, q + ".2", dout, cfg.full_attn[n - 1 - j] != 0, stage_heads(cfg, n - 1 - j))) return 1;
         if (weight_group(u, q + ".3", [&]() -> int {
-                conv_src(u, j < n - 1 ? q + ".3.1.weight" : q + ".3.weight", j < n - 1 ? q + ".3.1.bias" : q + ".3.bias");
-                if (j < n - 1)
-                    return make_conv(u->own, S.resample, P(u, q + ".3.1.weight").data.data(),
-                                     P(u, q + ".3.1.bias").data.data(), din, dout, 0, 3, 3, 1, 1, /*up=*/true);
-                return make_conv(u->own, S.resample, P(u, q + ".3.weight").data.data(), P(u, q + ".3.bias").data.data(),
-                                 din, dout, 0, 3, 3, 1, 1, false);
+                const bool last = j == n - 1;
+                return make_conv(u, S.resample, resample_param(q, last, "weight"), resample_param(q, last, "bias"), din, dout, 0,
+                                 3, 3, 1, 1, /*up=*/!last);
             }))
             return 1;
     }
     if (build_resnet(u, u->final_res, "final_res_block", u->init_dim, u->init_dim, u->init_dim, ss_off)) return 1;
     if (weight_group(u, "final_conv", [&]() -> int {
-            conv_src(u, "final_conv.weight", "final_conv.bias");
-            return make_conv(u->own, u->final_conv, P(u, "final_conv.weight").data.data(),
-                             P(u, "final_conv.bias").data.data(), u->out_dim, u->init_dim, 0, 1, 1, 1, 0, false);
+            return make_conv(u, u->final_conv, "final_conv.weight", "final_conv.bias", u->out_dim, u->init_dim, 0, 1, 1, 1, 0,
+                             false);
         }))
         return 1;
     u->ss_total = ss_off;
@@ -830,9 +777,11 @@ struct ResParts {
 struct PlannedConv {
     ConvParams p;      // everything but the tensor pointers
     int out_h, out_w;  // dims of the output tensor
-    int kind;          // 0 direct, 1 Winograd F(2x2,3x3), 2 F(4x4,3x3), 3 upsample algorithm, 4 one thread per pixel, 5 1x1 GEMM, 7 7x7 first conv
+    ConvKind kind;     // the kernel family (conv_family.inc)
     bool in_kernel;    // the epilogue runs inside the conv kernel (else: partial sums + landing kernel)
 };
+// the convolution leaves K-split / multi-tile partial sums that a landing pass (its own or a consumer's) has to sum
+static bool plan_leaves_partials(const PlannedConv& P) { return !P.in_kernel && conv_families[P.kind].partials; }
 
 // Which kernel and tiling a convolution takes; a function of the layer, the batch and the image size only.
 static int plan_conv(const Ctx& c, const ConvLayer& L, bool has_in1, int Hin, int Win, int epi, bool in_nchw, bool out_nchw,
@@ -844,7 +793,7 @@ static int plan_conv(const Ctx& c, const ConvLayer& L, bool has_in1, int Hin, in
     p.chunks0 = (L.C0 + CK - 1) / CK;
     p.n_chunks = p.chunks0 + (L.C1 ? (L.C1 + CK - 1) / CK : 0);
     p.in_nchw = in_nchw ? 1 : 0;
-    p.w = L.w; p.bias = L.bias;
+    p.bias = L.bias;
     p.Cout = L.Cout; p.stride = L.stride; p.pad = L.pad;
     const int padw = L.pad_w >= 0 ? L.pad_w : L.pad;
     p.pad_w = padw;
@@ -852,8 +801,17 @@ static int plan_conv(const Ctx& c, const ConvLayer& L, bool has_in1, int Hin, in
     p.out_nchw = out_nchw ? 1 : 0;
     p.ss_stride = c.ss_stride;
     const bool want_norm = (epi & EPI_NORM) != 0;
-    P.kind = 0;
-    const bool upwino = L.up && L.wwu && !in_nchw && !out_nchw && !has_in1 && Hin % 2 == 0 && Win % 2 == 0 &&
+    // the family takes the layer: its packed weights and, where the layout has K chunks of its own width, their counts
+    auto take = [&](ConvKind kind) {
+        P.kind = kind;
+        p.w = L.packed[kind];
+        if (const int kc = conv_families[kind].k_chunk) {
+            p.chunks0 = L.C0 / kc;
+            p.n_chunks = (L.C0 + L.C1) / kc;
+        }
+    };
+    take(CONV_DIRECT);
+    const bool upwino = L.up && L.packed[CONV_UPWINO] && !in_nchw && !out_nchw && !has_in1 && Hin % 2 == 0 && Win % 2 == 0 &&
                         upwino_shape_ok(c.B, Hin / 2, Win / 2, L.Cout, L.C0, L.C1);
     if (upwino) {
         // (Hin, Win) is the upsampled size the caller sees; the kernel works on the source grid (upwino_mfma.hip)
@@ -862,10 +820,8 @@ static int plan_conv(const Ctx& c, const ConvLayer& L, bool has_in1, int Hin, in
         p.Hin = Hin / 2; p.Win = Win / 2;
         p.Ho = Hin; p.Wo = Win;
         P.out_h = Hin; P.out_w = Win;
-        p.w = L.wwu;
-        p.chunks0 = p.n_chunks = L.C0 / 8;
+        take(CONV_UPWINO);
         p.geo = upwino_plan(c.B, p.Hin, p.Win, L.Cout, L.C0, L.C1, true);
-        P.kind = 3;
     } else if (L.fold) {
         // (Hin, Win) is the upsampled size the caller sees; the four parity convs run on the source grid
         DM_REQUIRE(!out_nchw && !in_nchw, "folded upsample conv is NHWC");
@@ -884,11 +840,11 @@ static int plan_conv(const Ctx& c, const ConvLayer& L, bool has_in1, int Hin, in
         p.Hin = p.Ho; p.Win = p.Wo;
         p.chunks0 = p.n_chunks = 4 * (L.C0 / 16);
         P.out_h = p.Ho; P.out_w = p.Wo;
-        if (L.wpw && !out_nchw && pw_shape_ok(c.B, p.Ho, p.Wo, L.Cout, 4 * L.C0, 0)) {
-            // the 1x1 GEMM kernel in space-to-depth mode (pw_mfma.hip)
-            p.w = L.wpw;
+        if (L.packed[CONV_PW] && !out_nchw && pw_shape_ok(c.B, p.Ho, p.Wo, L.Cout, 4 * L.C0, 0)) {
+            // the 1x1 GEMM kernel in space-to-depth mode (pw_mfma.hip): the K chunks run over (cin chunk, tap) as above
+            P.kind = CONV_PW;
+            p.w = L.packed[CONV_PW];
             p.geo = pw_plan(c.B, p.Ho, p.Wo, L.Cout, 4 * L.C0, 0, true);
-            P.kind = 5;
             P.in_kernel = p.geo.splits == 1 && (!want_norm || p.geo.fused_norm);
             return 0;
         }
@@ -904,45 +860,36 @@ static int plan_conv(const Ctx& c, const ConvLayer& L, bool has_in1, int Hin, in
         p.geo = conv_plan(c.B, p.Ho, p.Wo, L.Cout, L.KH, L.KW, L.stride, L.C0, L.C1, want_norm && !out_nchw,
                           !out_nchw);
     }
-    if (P.kind == 0 && L.wi7 && in_nchw && !out_nchw && !has_in1 && epi == 0 && L.pad_hi == 0 && padw == L.pad &&
+    const bool direct = P.kind == CONV_DIRECT;  // no family has taken the layer yet
+    if (direct && L.packed[CONV_INIT7] && in_nchw && !out_nchw && !has_in1 && epi == 0 && L.pad_hi == 0 && padw == L.pad &&
         (size_t)c.B * p.Ho * p.Wo < (1u << 24)) {
-        p.w = L.wi7;
-        P.kind = 7;
+        take(CONV_INIT7);
         P.in_kernel = true;
         return 0;
     }
-    if (L.wraw && out_nchw && !in_nchw && !has_in1 && epi == 0) {
+    if (L.packed[CONV_THIN] && out_nchw && !in_nchw && !has_in1 && epi == 0) {
         // a handful of output channels (final_conv): one pixel per thread instead of a 64-column MFMA tile
-        P.kind = 4;
+        take(CONV_THIN);
         P.in_kernel = true;
         return 0;
     }
     // 3x3 / stride 1 convolutions run as Winograd F(4x4,3x3) on power-of-two images, else as F(2x2,3x3), when the layer
     // has transformed weights
-    const bool wino4 = P.kind == 0 && L.ww4 && !L.fold && !in_nchw && !out_nchw && padw == L.pad &&
+    const bool wino4 = direct && L.packed[CONV_WINO4] && !L.fold && !in_nchw && !out_nchw && padw == L.pad &&
                        wino4_shape_ok(c.B, p.Ho, p.Wo, L.Cout, L.C0, L.C1);
-    const bool wino = P.kind == 0 && !wino4 && L.ww && !L.fold && !in_nchw && !out_nchw && padw == L.pad &&
+    const bool wino = direct && !wino4 && L.packed[CONV_WINO] && !L.fold && !in_nchw && !out_nchw && padw == L.pad &&
                       wino_shape_ok(c.B, p.Ho, p.Wo, L.Cout, L.C0, L.C1);
-    const bool pw = P.kind == 0 && L.wpw && !L.fold && !p.s2d && !in_nchw && !out_nchw && L.pad_hi == 0 && padw == 0 &&
+    const bool pw = direct && L.packed[CONV_PW] && !L.fold && !p.s2d && !in_nchw && !out_nchw && L.pad_hi == 0 && padw == 0 &&
                     pw_shape_ok(c.B, p.Ho, p.Wo, L.Cout, L.C0, L.C1);
     if (pw) {
-        p.w = L.wpw;
-        p.chunks0 = L.C0 / 16;
-        p.n_chunks = (L.C0 + L.C1) / 16;
+        take(CONV_PW);
         p.geo = pw_plan(c.B, p.Ho, p.Wo, L.Cout, L.C0, L.C1, true);
-        P.kind = 5;
     } else if (wino4) {
-        p.w = L.ww4;
-        p.chunks0 = L.C0 / 8;
-        p.n_chunks = (L.C0 + L.C1) / 8;
+        take(CONV_WINO4);
         p.geo = wino4_plan(c.B, p.Ho, p.Wo, L.Cout, L.C0, L.C1, true);
-        P.kind = 2;
     } else if (wino) {
-        p.w = L.ww;
-        p.chunks0 = L.C0 / 8;
-        p.n_chunks = (L.C0 + L.C1) / 8;
+        take(CONV_WINO);
         p.geo = wino_plan(c.B, p.Ho, p.Wo, L.Cout, L.C0, L.C1, true, want_norm);
-        P.kind = 1;
     }
     P.in_kernel = p.geo.splits == 1 && (!want_norm || p.geo.fused_norm);
     return 0;
@@ -950,14 +897,7 @@ static int plan_conv(const Ctx& c, const ConvLayer& L, bool has_in1, int Hin, in
 
 static int launch_planned(const PlannedConv& P, const ConvParams& q, hipStream_t s, dm_unet* u = nullptr) {
     if (u && u->train && ensure_packed(u, q.w, s)) return 1;  // training loop: weights re-packed on the device when stale
-    switch (P.kind) {
-        case 7: return init7_launch(q, s);
-        case 5: return pw_launch(q, s);
-        case 3: return upwino_launch(q, s);
-        case 2: return wino4_launch(q, s);
-        case 1: return wino_launch(q, s);
-        default: return conv_launch(q, s);
-    }
+    return conv_families[P.kind].launch(q, s);
 }
 
 static int run_conv(Ctx& c, const ConvLayer& L, const float* in0, const float* in1, int Hin, int Win, float* out,
@@ -972,12 +912,6 @@ static int run_conv(Ctx& c, const ConvLayer& L, const float* in0, const float* i
     ConvParams& p = P.p;
     p.in0 = in0; p.in1 = in1;
     p.residual = residual; p.g = g; p.scale = scale;
-    if (P.kind == 4) {
-        if (c.dry()) return 0;
-        if (c.u && c.u->train && ensure_packed(c.u, L.wraw, c.s)) return 1;
-        return launch_pointwise_small(in0, L.wraw, L.bias, out, (int64_t)c.B * p.Ho * p.Wo, L.C0, L.Cout, p.Ho * p.Wo,
-                                      c.s);
-    }
     const int full_epi = epi | (L.bias ? EPI_BIAS : 0);
     if (P.in_kernel) {
         DM_REQUIRE(!res_parts, "residual partial sums need the landing pass");
@@ -994,14 +928,10 @@ static int run_conv(Ctx& c, const ConvLayer& L, const float* in0, const float* i
     }
     p.out = part; p.partial = 1; p.epi = 0;
     if (launch_planned(P, p, c.s, c.u)) return 1;
-    int rc;
-    if (res_parts)
-        rc = launch_norm_act(part, p.geo.splits, (int64_t)(M * L.Cout), L.bias, g, scale, c.ss_stride, P.out_h * P.out_w,
-                             res_parts->part, out, (int64_t)M, L.Cout, full_epi | EPI_RESIDUAL, c.s, res_parts->nsplit,
-                             res_parts->stride, res_parts->bias);
-    else
-        rc = launch_norm_act(part, p.geo.splits, (int64_t)(M * L.Cout), L.bias, g, scale, c.ss_stride, P.out_h * P.out_w,
-                             residual, out, (int64_t)M, L.Cout, full_epi, c.s);
+    const ResParts res = res_parts ? *res_parts : ResParts{residual, 1, 0, nullptr};  // a plain tensor is one "split"
+    const int rc = launch_norm_act(part, p.geo.splits, (int64_t)(M * L.Cout), L.bias, g, scale, c.ss_stride, P.out_h * P.out_w,
+                                   res.part, out, (int64_t)M, L.Cout, full_epi | (res_parts ? EPI_RESIDUAL : 0), c.s, res.nsplit,
+                                   res.stride, res.bias);
     c.A->release(part);
     return rc;
 }
@@ -1012,7 +942,7 @@ static int run_conv_partial(Ctx& c, const ConvLayer& L, const float* in0, const 
                             int* nsplit) {
     PlannedConv P;
     if (plan_conv(c, L, in1 != nullptr, Hin, Win, 0, false, false, P)) return 1;
-    DM_REQUIRE(P.kind != 4, "partial sums of a pointwise-small layer");
+    DM_REQUIRE(conv_families[P.kind].partials, "partial sums of a layer whose kernel writes none");
     ConvParams& p = P.p;
     p.in0 = in0; p.in1 = in1;
     const size_t M = (size_t)c.B * P.out_h * P.out_w;
@@ -1042,7 +972,7 @@ static int run_resnet(Ctx& c, const ResBlock& R, const float* x0, const float* x
     if (R.has_res) {
         if (plan_conv(c, R.c2, false, H, W, EPI_NORM | EPI_SILU, false, false, P2)) return 1;
         if (plan_conv(c, R.res, x1 != nullptr, H, W, EPI_RESIDUAL, false, false, Pr)) return 1;
-        merged = merge && !P2.in_kernel && !Pr.in_kernel && Pr.kind != 4;
+        merged = merge && plan_leaves_partials(P2) && plan_leaves_partials(Pr);
     }
     ResParts rp{};
     float* rpart = nullptr;
@@ -1418,13 +1348,9 @@ int dm_unet_create(const dm_unet_cfg* cfg, int device, dm_unet** out) {
         expect_resnet(p, q + ".0", din, din);
         expect_resnet(p, q + ".1", din, din);
         expect_attn(p, q + ".2", din, cfg->full_attn[i] != 0, stage_heads(*cfg, i));
-        if (i < n - 1) {
-            expect(p, q + ".3.1.weight", {dout, din * 4, 1, 1});
-            expect(p, q + ".3.1.bias", {dout});
-        } else {
-            expect(p, q + ".3.weight", {dout, din, 3, 3});
-            expect(p, q + ".3.bias", {dout});
-        }
+        const bool last = i == n - 1;
+        expect(p, resample_param(q, last, "weight"), last ? std::vector<int64_t>{dout, din, 3, 3} : std::vector<int64_t>{dout, din * 4, 1, 1});
+        expect(p, resample_param(q, last, "bias"), {dout});
     }
     for (int j = 0; j < n; ++j) {
         int din = u->dims[n - 1 - j], dout = u->dims[n - j];
@@ -1432,13 +1358,8 @@ int dm_unet_create(const dm_unet_cfg* cfg, int device, dm_unet** out) {
         expect_resnet(p, q + ".0", dout + din, dout);
         expect_resnet(p, q + ".1", dout + din, dout);
         expect_attn(p, q + ".2", dout, cfg->full_attn[n - 1 - j] != 0, stage_heads(*cfg, n - 1 - j));
-        if (j < n - 1) {
-            expect(p, q + ".3.1.weight", {din, dout, 3, 3});
-            expect(p, q + ".3.1.bias", {din});
-        } else {
-            expect(p, q + ".3.weight", {din, dout, 3, 3});
-            expect(p, q + ".3.bias", {din});
-        }
+        expect(p, resample_param(q, j == n - 1, "weight"), {din, dout, 3, 3});
+        expect(p, resample_param(q, j == n - 1, "bias"), {din});
     }
     int mid = u->dims.back();
     expect_resnet(p, "mid_block1", mid, mid);

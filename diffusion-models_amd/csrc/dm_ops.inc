@@ -70,7 +70,7 @@ int dm_op_conv2d(const float* in0, int C0, const float* in1, int C1, const float
     return run_op(s, [&](Arena& A) -> int {
         int rc = 0;
         Ctx c{&dummy, &A, s, B, nullptr, 0};
-        if (L.wi7 && !in1 && !residual && !up2) {
+        if (L.packed[CONV_INIT7] && !in1 && !residual && !up2) {
             // the U-Net's first conv reads the NCHW image directly (unet_forward_impl): same call here
             float* o = A.alloc((size_t)B * Ho * Wo * Cout);
             if (run_conv(c, L, in0, nullptr, Hin, Win, o, 0, nullptr, nullptr, nullptr, /*in_nchw=*/true)) return 1;

@@ -24,11 +24,28 @@ static int guarded(F f) {  // nothing throws across the C ABI
 }
 
 // what the backward pass needs of one convolution layer
+enum ConvBwdKind {
+    CB_3X3,    // 3x3 s1 p1 (fwd.up: on a nearest-x2 source)
+    CB_1X1,
+    CB_DOWN,   // Downsample (2x2 s2)
+    CB_INIT7,  // init_conv: 7x7 over the NCHW image, no input-gradient layer
+    CB_FINAL,  // final_conv: thin 1x1 to the NCHW output, no input-gradient layer
+};
 struct ConvBwd {
-    int kind = 0;      // 0: 3x3 s1 p1 (fwd.up: on a nearest-x2 source), 1: 1x1, 2: Downsample (2x2 s2), 3: init 7x7, 4: final 1x1
+    ConvBwdKind kind = CB_3X3;
     ConvLayer d0, d1;  // dY -> d(in0), d(in1): rotated / transposed weights through make_conv
     bool has1 = false;
 };
+
+// Modes of the weight-gradient kernels (wgrad_mfma.hip).  The values are kernel arguments and the N of the profile rows
+// `wgrad m<N>`: they stay as they are.
+enum WgradMode { WG_3X3 = 0, WG_1X1 = 1, WG_DOWN = 2, WG_WINO = 3, WG_MODES = 4 };  // WG_WINO: 3x3 in the Winograd domain
+// products per weight element and 2x2 output tile (`taps`) and the input channels of one weight row
+static void wgrad_dims(WgradMode mode, const ConvLayer& L, int* taps, int* cin_w) {
+    static const int kTaps[WG_MODES] = {9, 1, 4, 16};
+    *taps = kTaps[mode];
+    *cin_w = mode == WG_DOWN ? L.C0 : L.C0 + L.C1;
+}
 
 struct TrainState {
     DeviceOwner own;  // dgrad weights
@@ -73,9 +90,9 @@ struct TrainState {
     // Device tables of the grouped weight-gradient launches and of the split-K sums behind them, one set per FLUSH of a
     // backward pass (one flush at the end of the pass; one per gradient bucket when data-parallel bucketing is on)
     struct FlushTables {
-        WgradParams* wtab_dev[4] = {nullptr, nullptr, nullptr, nullptr};
-        size_t wtab_cap[4] = {0, 0, 0, 0};
-        std::vector<WgradParams> wtab_host[4];
+        WgradParams* wtab_dev[WG_MODES] = {};
+        size_t wtab_cap[WG_MODES] = {};
+        std::vector<WgradParams> wtab_host[WG_MODES];
         WgradJob* jobs_dev = nullptr;
         size_t jobs_cap = 0;
         std::vector<WgradJob> jobs_host;
@@ -128,7 +145,7 @@ struct TrainState {
                         (void*)big_tmp})
             if (q) (void)hipFree(q);
         for (FlushTables& f : flush) {
-            for (int m = 0; m < 4; ++m)
+            for (int m = 0; m < WG_MODES; ++m)
                 if (f.wtab_dev[m]) (void)hipFree(f.wtab_dev[m]);
             if (f.jobs_dev) (void)hipFree(f.jobs_dev);
         }
@@ -155,25 +172,27 @@ static void rot_transpose(const float* w, int Cout, int Cin, int K, int c_lo, in
                         w[(((size_t)o * Cin + c_lo + c) * K + (K - 1 - ky)) * K + (K - 1 - kx)];
 }
 
-static int build_conv_bwd(dm_unet* u, TrainState& T, const ConvLayer& L, const std::string& wname, int kind) {
+// the backward half of layer L (built by the named make_conv: it knows its weight)
+static int build_conv_bwd(dm_unet* u, TrainState& T, const ConvLayer& L, ConvBwdKind kind) {
     ConvBwd& B = T.conv[&L];
     B.kind = kind;
+    const std::string& wname = L.src.wname;
     T.conv_weights.insert(wname);
     const HostTensor& w = P(u, wname);
-    if (kind == 3 && T.ft) {
+    if (kind == CB_INIT7 && T.ft) {
         if (T.own.upload(w.data.data(), w.numel(), &T.init_w_raw)) return 1;
         T.own.record_raw(wname, T.init_w_raw, w.numel());
     }
-    if (kind >= 3) return 0;
+    if (kind == CB_INIT7 || kind == CB_FINAL) return 0;
     std::vector<float> wt;
     const int Cin = L.C0 + L.C1;
     PackSrc src;
     src.wname = wname;
     src.sCout = L.Cout;
-    if (kind == 2) {
-        src.kind = 2;
+    if (kind == CB_DOWN) {
+        src.kind = PS_S2D_T;
         src.sCin = L.C0;
-        T.own.src = src;
+        B.d0.src = src;
         // Downsample: out[o] = sum_{c,sub} W[o][c*4 + sub] x[2y+p1][2x+p2][c]; the input gradient in space-to-depth order
         // t[(sub*C + c)] = sum_o W[o][c*4 + sub] dY[o] is a 1x1 convolution Cout -> 4C, then a depth-to-space copy
         const int C = L.C0, Cout = L.Cout;
@@ -183,34 +202,32 @@ static int build_conv_bwd(dm_unet* u, TrainState& T, const ConvLayer& L, const s
                 for (int o = 0; o < Cout; ++o) wt[((size_t)sub * C + c) * Cout + o] = w.data[(size_t)o * 4 * C + c * 4 + sub];
         return make_conv(T.own, B.d0, wt.data(), nullptr, 4 * C, Cout, 0, 1, 1, 1, 0, false);
     }
-    const int K = kind == 0 ? 3 : 1;
-    src.kind = 1;
+    const int K = kind == CB_3X3 ? 3 : 1;
+    src.kind = PS_ROT;
     src.sCin = Cin;
     src.sK = K;
     src.c_lo = 0;
     src.c_n = L.C0;
-    T.own.src = src;
+    B.d0.src = src;
     rot_transpose(w.data.data(), L.Cout, Cin, K, 0, L.C0, wt);
     if (make_conv(T.own, B.d0, wt.data(), nullptr, L.C0, L.Cout, 0, K, K, 1, K / 2, false)) return 1;
     B.has1 = L.C1 > 0;
     if (B.has1) {
         src.c_lo = L.C0;
         src.c_n = L.C1;
-        T.own.src = src;
+        B.d1.src = src;
         rot_transpose(w.data.data(), L.Cout, Cin, K, L.C0, L.C1, wt);
         if (make_conv(T.own, B.d1, wt.data(), nullptr, L.C1, L.Cout, 0, K, K, 1, K / 2, false)) return 1;
     }
     return 0;
 }
 
-static int build_resnet_bwd(dm_unet* u, TrainState& T, const ResBlock& R, const std::string& p) {
-    if (build_conv_bwd(u, T, R.c1, p + ".block1.proj.weight", 0) || build_conv_bwd(u, T, R.c2, p + ".block2.proj.weight", 0))
-        return 1;
-    return R.has_res ? build_conv_bwd(u, T, R.res, p + ".res_conv.weight", 1) : 0;
+static int build_resnet_bwd(dm_unet* u, TrainState& T, const ResBlock& R) {
+    if (build_conv_bwd(u, T, R.c1, CB_3X3) || build_conv_bwd(u, T, R.c2, CB_3X3)) return 1;
+    return R.has_res ? build_conv_bwd(u, T, R.res, CB_1X1) : 0;
 }
-static int build_attn_bwd(dm_unet* u, TrainState& T, const AttnLayer& A, const std::string& p) {
-    return build_conv_bwd(u, T, A.qkv, p + ".to_qkv.weight", 1) ||
-           build_conv_bwd(u, T, A.out, p + (A.full ? ".to_out.weight" : ".to_out.0.weight"), 1);
+static int build_attn_bwd(dm_unet* u, TrainState& T, const AttnLayer& A) {
+    return build_conv_bwd(u, T, A.qkv, CB_1X1) || build_conv_bwd(u, T, A.out, CB_1X1);
 }
 
 // (re)build every dgrad layer from the host copies of the parameters
@@ -221,35 +238,21 @@ static int build_train(dm_unet* u) {
     T.ops.clear();
     T.own.rec = &T.ops;
     const int n = u->cfg.n_stages;
-    if (build_conv_bwd(u, T, u->init_conv, "init_conv.weight", 3)) return 1;
-    for (int i = 0; i < n; ++i) {
-        const std::string q = idx("downs", i);
-        Stage& S = u->downs[i];
-        if (build_resnet_bwd(u, T, S.b1, q + ".0") || build_resnet_bwd(u, T, S.b2, q + ".1") ||
-            build_attn_bwd(u, T, S.attn, q + ".2"))
-            return 1;
-        if (build_conv_bwd(u, T, S.resample, i < n - 1 ? q + ".3.1.weight" : q + ".3.weight", i < n - 1 ? 2 : 0)) return 1;
-    }
-    if (build_resnet_bwd(u, T, u->mid1, "mid_block1") || build_attn_bwd(u, T, u->mid_attn, "mid_attn") ||
-        build_resnet_bwd(u, T, u->mid2, "mid_block2"))
-        return 1;
-    for (int j = 0; j < n; ++j) {
-        const std::string q = idx("ups", j);
-        Stage& S = u->ups[j];
-        if (build_resnet_bwd(u, T, S.b1, q + ".0") || build_resnet_bwd(u, T, S.b2, q + ".1") ||
-            build_attn_bwd(u, T, S.attn, q + ".2"))
-            return 1;
-        if (build_conv_bwd(u, T, S.resample, j < n - 1 ? q + ".3.1.weight" : q + ".3.weight", 0)) return 1;
-    }
-    if (build_resnet_bwd(u, T, u->final_res, "final_res_block")) return 1;
-    if (build_conv_bwd(u, T, u->final_conv, "final_conv.weight", 4)) return 1;
+    auto stage = [&](const Stage& S, ConvBwdKind resample) -> int {
+        return build_resnet_bwd(u, T, S.b1) || build_resnet_bwd(u, T, S.b2) || build_attn_bwd(u, T, S.attn) ||
+               build_conv_bwd(u, T, S.resample, resample);
+    };
+    if (build_conv_bwd(u, T, u->init_conv, CB_INIT7)) return 1;
+    for (int i = 0; i < n; ++i)
+        if (stage(u->downs[i], i < n - 1 ? CB_DOWN : CB_3X3)) return 1;
+    if (build_resnet_bwd(u, T, u->mid1) || build_attn_bwd(u, T, u->mid_attn) || build_resnet_bwd(u, T, u->mid2)) return 1;
+    for (int j = 0; j < n; ++j)
+        if (stage(u->ups[j], CB_3X3)) return 1;
+    if (build_resnet_bwd(u, T, u->final_res)) return 1;
+    if (build_conv_bwd(u, T, u->final_conv, CB_FINAL)) return 1;
     if (u->cfg.text_mode == DM_TEXT_CROSS)
-        for (auto& pr : {std::make_pair(&u->cross_mid, "cross_attn"), std::make_pair(&u->cross_down, "cross_attn_down"),
-                         std::make_pair(&u->cross_up, "cross_attn_up")}) {
-            const std::string q = pr.second;
-            if (build_conv_bwd(u, T, pr.first->q, q + ".to_q.weight", 1) || build_conv_bwd(u, T, pr.first->out, q + ".to_out.0.weight", 1))
-                return 1;
-        }
+        for (const CrossLayer* C : {&u->cross_mid, &u->cross_down, &u->cross_up})
+            if (build_conv_bwd(u, T, C->q, CB_1X1) || build_conv_bwd(u, T, C->out, CB_1X1)) return 1;
     // the host has just packed every buffer: nothing is stale, and the buffer -> recipe index is rebuilt on next use
     T.op_of.clear();
     T.n_copies = 0;
@@ -361,7 +364,7 @@ static int t_block(TCtx& t, const ConvLayer& L, const float* x0, const float* x1
     PlannedConv P;
     if (plan_conv(c, L, x1 != nullptr, H, W, 0, false, false, P)) return 1;
     const int flags = EPI_NORM | EPI_SILU | (scale ? EPI_SCALE_SHIFT : 0);
-    if (!P.in_kernel && P.kind != 4 && !no_fuse) {
+    if (plan_leaves_partials(P) && !no_fuse) {
         // K-split / multi-tile convolution: ONE landing pass sums the partial tiles, adds the bias, keeps u and writes y
         float* part = nullptr;
         int nsplit = 0;
@@ -429,10 +432,10 @@ static int t_attn(TCtx& t, const AttnLayer& At, const float* x, int H, int W, At
                            EPI_NORM | EPI_RESIDUAL, t.s);
 }
 
-static int conv_wgrad(TCtx& t, const ConvLayer& L, const ConvBwd& Bw, const float* x0, const float* x1, const float* dy,
-                      int Ho, int Wo, const std::string& wname, const std::string& bname, bool bias_from_colsum);
-static int conv_dgrad(TCtx& t, const ConvLayer& L, const ConvBwd& Bw, const float* dy, int Hin, int Win, const float* add0,
-                      const float* add1, float** dx0, float** dx1);
+static int conv_wgrad(TCtx& t, const ConvLayer& L, const float* x0, const float* x1, const float* dy, int Ho, int Wo,
+                      bool bias_from_colsum);
+static int conv_dgrad(TCtx& t, const ConvLayer& L, const float* dy, int Hin, int Win, const float* add0, const float* add1,
+                      float** dx0, float** dx1);
 
 // CrossAttention.forward (DD/denoising_diffusion_text_conditional.py:54-78) in tape mode, general path (m context tokens);
 // the result REPLACES x (:173-177): no residual.  mask (per-image caption dropout): the layer is skipped for rows with
@@ -467,9 +470,9 @@ static int t_cross(TCtx& t, const CrossLayer& Cr, const float* x, int H, int W, 
 // mask (per-image caption dropout): rows with mask 0 kept the layer's input, so their gradient bypasses the layer -- the
 // layer receives exact zeros for them (every parameter gradient is linear in it) and *dx_out is dy for those rows
 static int t_cross_bwd(TCtx& t, const CrossLayer& Cr, const CrossTape& ct, const float* dy_in, int H, int W, const float* ctx, int m,
-                       const std::string& p, float** dx_out, const int32_t* mask) {
+                       float** dx_out, const int32_t* mask) {
     dm_unet* u = t.u;
-    TrainState& T = *u->train;
+    const std::string& p = Cr.prefix;
     const int n = H * W, inner = 4 * u->dh, dim = Cr.out.Cout, E = u->cfg.text_emb_dim;
     const size_t rows = (size_t)t.B * n;
     const int64_t per = (int64_t)n * dim;
@@ -485,9 +488,9 @@ static int t_cross_bwd(TCtx& t, const CrossLayer& Cr, const CrossTape& ct, const
     if (!t.dry() && launch_norm_act_bwd(dy, ct.y0, Cr.g, nullptr, 0, n, dy0, ws, t.grad(p + ".to_out.1.g"),
                                         t.grad(p + ".to_out.0.bias"), nullptr, 0, t.B, dim, EPI_NORM, t.acc, t.s, t.rdefer()))
         return 1;
-    if (conv_wgrad(t, Cr.out, T.conv.at(&Cr.out), ct.o, nullptr, dy0, H, W, p + ".to_out.0.weight", "", false)) return 1;
+    if (conv_wgrad(t, Cr.out, ct.o, nullptr, dy0, H, W, false)) return 1;
     float *dO = nullptr, *none = nullptr;
-    if (conv_dgrad(t, Cr.out, T.conv.at(&Cr.out), dy0, H, W, nullptr, nullptr, &dO, &none)) return 1;
+    if (conv_dgrad(t, Cr.out, dy0, H, W, nullptr, nullptr, &dO, &none)) return 1;
     float* dq = t.A->alloc(rows * inner);
     float* dk = t.A->alloc((size_t)t.B * m * inner);
     float* dv = t.A->alloc((size_t)t.B * m * inner);
@@ -497,8 +500,8 @@ static int t_cross_bwd(TCtx& t, const CrossLayer& Cr, const CrossTape& ct, const
         if (launch_linear_wgrad(dk, inner, ctx, E, t.grad(p + ".to_k.weight"), t.B * m, E, inner, 0, t.acc, t.s)) return 1;
         if (launch_linear_wgrad(dv, inner, ctx, E, t.grad(p + ".to_v.weight"), t.B * m, E, inner, 0, t.acc, t.s)) return 1;
     }
-    if (conv_wgrad(t, Cr.q, T.conv.at(&Cr.q), ct.x, nullptr, dq, H, W, p + ".to_q.weight", "", false)) return 1;
-    if (conv_dgrad(t, Cr.q, T.conv.at(&Cr.q), dq, H, W, nullptr, nullptr, dx_out, &none)) return 1;
+    if (conv_wgrad(t, Cr.q, ct.x, nullptr, dq, H, W, false)) return 1;
+    if (conv_dgrad(t, Cr.q, dq, H, W, nullptr, nullptr, dx_out, &none)) return 1;
     if (mask && !t.dry()) return launch_route_rows(*dx_out, per, *dx_out, per, dy_in, per, mask, t.B, per, t.s);
     return 0;
 }
@@ -622,28 +625,32 @@ static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const i
 }
 
 // ---- backward pieces ---------------------------------------------------------------------------------------------------
-// weight (+ bias) gradient of one convolution; dy = gradient of its output (NHWC unless the layer is the NCHW final_conv)
-static int conv_wgrad(TCtx& t, const ConvLayer& L, const ConvBwd& Bw, const float* x0, const float* x1, const float* dy,
-                      int Ho, int Wo, const std::string& wname, const std::string& bname, bool bias_from_colsum) {
+// weight (+ bias, from the column sums of dy) gradient of one convolution, into the gradient slots of the parameters the
+// layer was built from; dy = gradient of its output (NHWC unless the layer is the NCHW final_conv)
+static int conv_wgrad(TCtx& t, const ConvLayer& L, const float* x0, const float* x1, const float* dy, int Ho, int Wo,
+                      bool bias_from_colsum) {
+    const ConvBwdKind kind = t.u->train->conv.at(&L).kind;
+    const std::string &wname = L.src.wname, &bname = L.src.bname;
     const int Cin = L.C0 + L.C1;
     const int64_t rows = (int64_t)t.B * Ho * Wo;
-    if (Bw.kind == 3 || Bw.kind == 4) {
+    if (kind == CB_INIT7 || kind == CB_FINAL) {
         int splits;
         float* ws = t.A->alloc(wgrad_naive_ws_floats(t.B, Ho, L.Cout, Cin, L.KH, L.KW, &splits));
-        float* cw = (bias_from_colsum && Bw.kind == 3) ? t.A->alloc(colsum_ws_floats(rows, L.Cout)) : nullptr;
+        float* cw = (bias_from_colsum && kind == CB_INIT7) ? t.A->alloc(colsum_ws_floats(rows, L.Cout)) : nullptr;
         if (t.dry()) return 0;
-        if (launch_wgrad_naive(x0, Bw.kind == 3, dy, Bw.kind == 4, Cin, L.Cout, L.KH, L.KW, L.pad, t.B, Ho, Wo, ws,
+        if (launch_wgrad_naive(x0, kind == CB_INIT7, dy, kind == CB_FINAL, Cin, L.Cout, L.KH, L.KW, L.pad, t.B, Ho, Wo, ws,
                                t.grad(wname), t.acc, t.s, t.defer()))
             return 1;
         if (!bias_from_colsum) return 0;
-        if (Bw.kind == 4) return launch_colsum_nchw(dy, t.B, L.Cout, Ho * Wo, t.grad(bname), t.acc, t.s);
+        if (kind == CB_FINAL) return launch_colsum_nchw(dy, t.B, L.Cout, Ho * Wo, t.grad(bname), t.acc, t.s);
         return launch_colsum(dy, rows, L.Cout, L.Cout, 1, cw, t.grad(bname), t.acc, t.s, t.cdefer());
     }
-    // 3x3 on even image sizes: Winograd-domain weight gradient (mode 3, 16 instead of 36 products per 2x2 tile)
+    // 3x3 on even image sizes: Winograd-domain weight gradient (16 instead of 36 products per 2x2 tile)
     static const bool no_wino = env_flag("DM_WGRAD_NO_WINO") || winograd_off();
-    const int mode = Bw.kind == 0 ? ((!no_wino && Ho % 2 == 0 && Wo % 2 == 0) ? 3 : 0) : (Bw.kind == 1 ? 1 : 2);
-    const int T = mode == 0 ? 9 : (mode == 1 ? 1 : (mode == 2 ? 4 : 16));
-    const int cin_w = mode == 2 ? L.C0 : Cin;
+    const WgradMode mode = kind == CB_1X1 ? WG_1X1 : kind == CB_DOWN ? WG_DOWN
+                           : (!no_wino && Ho % 2 == 0 && Wo % 2 == 0) ? WG_WINO : WG_3X3;
+    int T, cin_w;
+    wgrad_dims(mode, L, &T, &cin_w);
     if (t.wbatch) {  // runs with every other layer of its mode at the end of the backward pass (unet_train_backward)
         t.wbatch[mode].push_back(WgradDesc{x0, x1, dy, t.dry() ? nullptr : t.grad(wname), L.C0, L.C1, L.Cout, t.B, Ho, Wo,
                                            L.up ? 1 : 0, t.acc});
@@ -661,10 +668,11 @@ static int conv_wgrad(TCtx& t, const ConvLayer& L, const ConvBwd& Bw, const floa
 }
 
 // input gradient(s) of one convolution: *dx0 = dgrad0(dy) [+ add0], *dx1 = dgrad1(dy) [+ add1]; (Hin, Win) = input size
-static int conv_dgrad(TCtx& t, const ConvLayer& L, const ConvBwd& Bw, const float* dy, int Hin, int Win, const float* add0,
-                      const float* add1, float** dx0, float** dx1) {
+static int conv_dgrad(TCtx& t, const ConvLayer& L, const float* dy, int Hin, int Win, const float* add0, const float* add1,
+                      float** dx0, float** dx1) {
+    const ConvBwd& Bw = t.u->train->conv.at(&L);
     Ctx c{t.u, t.A, t.s, t.B, nullptr, 0};
-    if (Bw.kind == 2) {  // Downsample: 1x1 to 4C channels at the output size, then depth-to-space
+    if (Bw.kind == CB_DOWN) {  // Downsample: 1x1 to 4C channels at the output size, then depth-to-space
         const int Ho = Hin / 2, Wo = Win / 2;
         float* tmp = t.A->alloc((size_t)t.B * Ho * Wo * 4 * L.C0);
         if (run_conv(c, Bw.d0, dy, nullptr, Ho, Wo, tmp, 0, nullptr, nullptr, nullptr)) return 1;
@@ -698,13 +706,14 @@ struct DyParts {
     float* owned = nullptr;  // partial-sum buffer to release once the consumer has been enqueued
 };
 // input gradient of a single-input, stride-1 convolution for a consumer that can sum partial tiles itself
-static int conv_dgrad_parts(TCtx& t, const ConvLayer& L, const ConvBwd& Bw, const float* dy, int H, int W, DyParts* out) {
+static int conv_dgrad_parts(TCtx& t, const ConvLayer& L, const float* dy, int H, int W, DyParts* out) {
+    const ConvBwd& Bw = t.u->train->conv.at(&L);
     const bool no_fuse = train_landing_fuse_off();
     Ctx c{t.u, t.A, t.s, t.B, nullptr, 0};
     PlannedConv P;
-    const bool plain = (Bw.kind == 0 || Bw.kind == 1) && !L.up && !Bw.has1 && !no_fuse;
+    const bool plain = (Bw.kind == CB_3X3 || Bw.kind == CB_1X1) && !L.up && !Bw.has1 && !no_fuse;
     if (plain && plan_conv(c, Bw.d0, false, H, W, 0, false, false, P)) return 1;
-    if (plain && !P.in_kernel && P.kind != 4) {
+    if (plain && plan_leaves_partials(P)) {
         float* part = nullptr;
         if (run_conv_partial(c, Bw.d0, dy, nullptr, H, W, &part, &out->nsplit)) return 1;
         out->p = out->owned = part;
@@ -712,7 +721,7 @@ static int conv_dgrad_parts(TCtx& t, const ConvLayer& L, const ConvBwd& Bw, cons
         return 0;
     }
     float *dx = nullptr, *none = nullptr;
-    if (conv_dgrad(t, L, Bw, dy, H, W, nullptr, nullptr, &dx, &none)) return 1;
+    if (conv_dgrad(t, L, dy, H, W, nullptr, nullptr, &dx, &none)) return 1;
     *out = DyParts{dx, 1, 0, nullptr};
     return 0;
 }
@@ -732,21 +741,21 @@ static int t_block_bwd(TCtx& t, const ConvLayer& L, const BlockTape& bt, const D
                                         dy.nsplit, dy.stride))
         return 1;
     if (dy.owned) t.A->release(dy.owned);
-    if (conv_wgrad(t, L, t.u->train->conv.at(&L), bt.x0, bt.x1, du, H, W, p + ".proj.weight", "", false)) return 1;
+    if (conv_wgrad(t, L, bt.x0, bt.x1, du, H, W, false)) return 1;
     *du_out = du;
     return 0;
 }
 
 // ResnetBlock backward: dout -> d(x0) [+ extra0], d(x1)
 static int t_resnet_bwd(TCtx& t, const ResBlock& R, const ResTape& rt, const float* dout, int H, int W, float* dss,
-                        const std::string& p, const float* extra0, float** dx0, float** dx1) {
+                        const float* extra0, float** dx0, float** dx1) {
     TrainState& T = *t.u->train;
     const float* scale = t.ss + R.ss_off;
     float *du2 = nullptr, *du1 = nullptr;
     DyParts dh1;
-    if (t_block_bwd(t, R.c2, rt.b2, DyParts{dout}, H, W, R.g2, nullptr, 0, nullptr, p + ".block2", &du2)) return 1;
-    if (conv_dgrad_parts(t, R.c2, T.conv.at(&R.c2), du2, H, W, &dh1)) return 1;
-    if (t_block_bwd(t, R.c1, rt.b1, dh1, H, W, R.g1, scale, R.ss_off, dss, p + ".block1", &du1)) return 1;
+    if (t_block_bwd(t, R.c2, rt.b2, DyParts{dout}, H, W, R.g2, nullptr, 0, nullptr, R.prefix + ".block2", &du2)) return 1;
+    if (conv_dgrad_parts(t, R.c2, du2, H, W, &dh1)) return 1;
+    if (t_block_bwd(t, R.c1, rt.b1, dh1, H, W, R.g1, scale, R.ss_off, dss, R.prefix + ".block1", &du1)) return 1;
     const size_t n0 = (size_t)t.B * H * W * R.c1.C0;
     *dx1 = nullptr;
     if (!R.has_res) {  // + x: the output gradient flows straight into d(x0)
@@ -756,11 +765,10 @@ static int t_resnet_bwd(TCtx& t, const ResBlock& R, const ResTape& rt, const flo
             if (!t.dry() && launch_add3(dout, extra0, nullptr, sum, (int64_t)n0, t.s)) return 1;
             add = sum;
         }
-        return conv_dgrad(t, R.c1, T.conv.at(&R.c1), du1, H, W, add, nullptr, dx0, dx1);
+        return conv_dgrad(t, R.c1, du1, H, W, add, nullptr, dx0, dx1);
     }
-    const ConvBwd& Br = T.conv.at(&R.res);
-    if (conv_wgrad(t, R.res, Br, rt.b1.x0, rt.b1.x1, dout, H, W, p + ".res_conv.weight", p + ".res_conv.bias", true)) return 1;
-    const ConvBwd& Bc = T.conv.at(&R.c1);
+    if (conv_wgrad(t, R.res, rt.b1.x0, rt.b1.x1, dout, H, W, true)) return 1;
+    const ConvBwd &Br = T.conv.at(&R.res), &Bc = T.conv.at(&R.c1);
     // d(x) = dgrad_c1(du1) + dgrad_res(dout), per concat half.  Where block1's input gradient leaves K-split partial tiles for a
     // landing pass anyway, res_conv's input gradient stays partial tiles too and that ONE landing sums both (what run_resnet
     // does for block2 + res_conv in the forward pass): two launches per half instead of four.
@@ -770,7 +778,7 @@ static int t_resnet_bwd(TCtx& t, const ResBlock& R, const ResTape& rt, const flo
         *done = false;
         PlannedConv Pc, Pr;
         if (plan_conv(c, Lc, false, H, W, EPI_RESIDUAL, false, false, Pc) || plan_conv(c, Lr, false, H, W, 0, false, false, Pr)) return 1;
-        if (Pc.in_kernel || Pc.kind == 4 || Pr.kind == 4) return 0;
+        if (!plan_leaves_partials(Pc) || !conv_families[Pr.kind].partials) return 0;
         ResParts rp{};
         float* rpart = nullptr;
         if (run_conv_partial(c, Lr, dout, nullptr, H, W, &rpart, &rp.nsplit)) return 1;
@@ -783,7 +791,7 @@ static int t_resnet_bwd(TCtx& t, const ResBlock& R, const ResTape& rt, const flo
         *done = true;
         return 0;
     };
-    if (!no_merge && !extra0 && Bc.kind == 0 && Br.kind == 1 && !R.c1.up && Bc.has1 == Br.has1) {
+    if (!no_merge && !extra0 && Bc.kind == CB_3X3 && Br.kind == CB_1X1 && !R.c1.up && Bc.has1 == Br.has1) {
         bool d0 = false, d1 = !Bc.has1;
         if (half(Bc.d0, Br.d0, R.c1.C0, dx0, &d0)) return 1;
         if (Bc.has1 && d0 && half(Bc.d1, Br.d1, R.c1.C1, dx1, &d1)) return 1;
@@ -797,15 +805,15 @@ static int t_resnet_bwd(TCtx& t, const ResBlock& R, const ResTape& rt, const flo
         }
     }
     float *r0 = nullptr, *r1 = nullptr;
-    if (conv_dgrad(t, R.res, Br, dout, H, W, extra0, nullptr, &r0, &r1)) return 1;
-    return conv_dgrad(t, R.c1, Bc, du1, H, W, r0, r1, dx0, dx1);
+    if (conv_dgrad(t, R.res, dout, H, W, extra0, nullptr, &r0, &r1)) return 1;
+    return conv_dgrad(t, R.c1, du1, H, W, r0, r1, dx0, dx1);
 }
 
 // (attn(x) + x) backward: dy -> dx
-static int t_attn_bwd(TCtx& t, const AttnLayer& At, const AttnTape& at, const float* dy, int H, int W, const std::string& p,
-                      float** dx_out, bool add_x = true) {
+static int t_attn_bwd(TCtx& t, const AttnLayer& At, const AttnTape& at, const float* dy, int H, int W, float** dx_out,
+                      bool add_x = true) {
     dm_unet* u = t.u;
-    TrainState& T = *u->train;
+    const std::string& p = At.prefix;
     const int n = H * W, heads = At.heads, hidden = heads * u->dh;
     const size_t rows = (size_t)t.B * n;
     const float* dyo = dy;  // gradient of the to_out convolution's output
@@ -813,14 +821,13 @@ static int t_attn_bwd(TCtx& t, const AttnLayer& At, const AttnTape& at, const fl
         float* dy0 = t.A->alloc(rows * At.dim);
         float* ws = t.A->alloc(norm_act_bwd_ws_floats(t.B, n, At.dim));
         if (!t.dry() && launch_norm_act_bwd(dy, at.y0, At.out_g, nullptr, 0, n, dy0, ws, t.grad(p + ".to_out.1.g"),
-                                            t.grad(p + ".to_out.0.bias"), nullptr, 0, t.B, At.dim, EPI_NORM, t.acc, t.s, t.rdefer()))
+                                            t.grad(At.out.src.bname), nullptr, 0, t.B, At.dim, EPI_NORM, t.acc, t.s, t.rdefer()))
             return 1;
         dyo = dy0;
     }
-    const std::string wo = p + (At.full ? ".to_out.weight" : ".to_out.0.weight");
-    if (conv_wgrad(t, At.out, T.conv.at(&At.out), at.o, nullptr, dyo, H, W, wo, p + ".to_out.bias", At.full)) return 1;
+    if (conv_wgrad(t, At.out, at.o, nullptr, dyo, H, W, At.full)) return 1;
     float *dO = nullptr, *none = nullptr;
-    if (conv_dgrad(t, At.out, T.conv.at(&At.out), dyo, H, W, nullptr, nullptr, &dO, &none)) return 1;
+    if (conv_dgrad(t, At.out, dyo, H, W, nullptr, nullptr, &dO, &none)) return 1;
     float* dqkv = t.A->alloc(rows * 3 * hidden);
     const size_t nmem = (size_t)2 * heads * u->dh * 4;
     float* dmem = t.A->alloc((size_t)t.B * nmem);
@@ -837,9 +844,9 @@ static int t_attn_bwd(TCtx& t, const AttnLayer& At, const AttnTape& at, const fl
     }
     if (!t.dry() && launch_colsum(dmem, t.B, (int)nmem, (int64_t)nmem, 1, cw, t.grad(p + ".mem_kv"), t.acc, t.s, t.cdefer()))
         return 1;
-    if (conv_wgrad(t, At.qkv, T.conv.at(&At.qkv), at.xn, nullptr, dqkv, H, W, p + ".to_qkv.weight", "", false)) return 1;
+    if (conv_wgrad(t, At.qkv, at.xn, nullptr, dqkv, H, W, false)) return 1;
     DyParts dxn;
-    if (conv_dgrad_parts(t, At.qkv, T.conv.at(&At.qkv), dqkv, H, W, &dxn)) return 1;
+    if (conv_dgrad_parts(t, At.qkv, dqkv, H, W, &dxn)) return 1;
     float* dxa = t.A->alloc(rows * At.dim);
     float* ws2 = t.A->alloc(norm_act_bwd_ws_floats(t.B, n, At.dim));
     // (attn(x) + x): the residual branch's gradient dy joins in the kernel's store
@@ -854,11 +861,10 @@ static int t_attn_bwd(TCtx& t, const AttnLayer& At, const AttnTape& at, const fl
 
 // plain convolution (resample convs, final_conv): weight / bias gradient, input gradient [+ add]
 static int t_conv_bwd(TCtx& t, const ConvLayer& L, const float* x, const float* dy, int Hin, int Win, int Ho, int Wo,
-                      const std::string& wname, const std::string& bname, const float* add, float** dx) {
-    const ConvBwd& Bw = t.u->train->conv.at(&L);
-    if (conv_wgrad(t, L, Bw, x, nullptr, dy, Ho, Wo, wname, bname, true)) return 1;
+                      const float* add, float** dx) {
+    if (conv_wgrad(t, L, x, nullptr, dy, Ho, Wo, true)) return 1;
     float* none = nullptr;
-    return conv_dgrad(t, L, Bw, dy, Hin, Win, add, nullptr, dx, &none);
+    return conv_dgrad(t, L, dy, Hin, Win, add, nullptr, dx, &none);
 }
 
 // a table that is a function of the shapes only: uploaded when it differs from the one already on the device
@@ -907,32 +913,31 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     float* dfr = A.alloc((size_t)B * h * w * u->init_dim);
     {
         const ConvLayer& L = u->final_conv;
-        DM_REQUIRE(L.wraw != nullptr, "training: final_conv must be the thin pointwise layer (out_dim <= 8)");
+        const float* wraw = L.packed[CONV_THIN];
+        DM_REQUIRE(wraw != nullptr, "training: final_conv must be the thin pointwise layer (out_dim <= 8)");
         static const bool no_fuse = env_flag("DM_TRAIN_NO_FINAL_FUSE");
         if (!no_fuse && thin_out_bwd_ok(L.Cout, h * w)) {  // dw, db and dx in one pass over the block's output
             float* ws = A.alloc(thin_out_bwd_ws_floats(B, h, w, L.Cout, L.C0));
             if (!A.dry) {
-                if (ensure_packed(u, L.wraw, s)) return 1;
+                if (ensure_packed(u, wraw, s)) return 1;
                 WgradJob *jw = t.defer(), *jb = nullptr;
                 if (jw) {  // (the second emplace_back may move the first)
                     jb = t.defer();
                     jw = jb - 1;
                 }
-                if (launch_thin_out_bwd(tp.fin.out, dout_nchw, L.wraw, dfr, ws, t.grad("final_conv.weight"),
-                                        t.grad("final_conv.bias"), B, h, w, L.C0, L.Cout, t.acc, s, jw, jb))
+                if (launch_thin_out_bwd(tp.fin.out, dout_nchw, wraw, dfr, ws, t.grad(L.src.wname), t.grad(L.src.bname), B, h,
+                                        w, L.C0, L.Cout, t.acc, s, jw, jb))
                     return 1;
             }
         } else {
-            if (conv_wgrad(t, L, u->train->conv.at(&L), tp.fin.out, nullptr, dout_nchw, h, w, "final_conv.weight",
-                           "final_conv.bias", true))
-                return 1;
-            if (!A.dry && ensure_packed(u, L.wraw, s)) return 1;
-            if (!A.dry && launch_pointwise_small_dgrad(dout_nchw, L.wraw, dfr, (int64_t)B * h * w, L.C0, L.Cout, h * w, s))
+            if (conv_wgrad(t, L, tp.fin.out, nullptr, dout_nchw, h, w, true)) return 1;
+            if (!A.dry && ensure_packed(u, wraw, s)) return 1;
+            if (!A.dry && launch_pointwise_small_dgrad(dout_nchw, wraw, dfr, (int64_t)B * h * w, L.C0, L.Cout, h * w, s))
                 return 1;
         }
     }
     float *dcur = nullptr, *dr = nullptr;
-    if (t_resnet_bwd(t, u->final_res, tp.fin, dfr, h, w, dss, "final_res_block", nullptr, &dcur, &dr)) return 1;
+    if (t_resnet_bwd(t, u->final_res, tp.fin, dfr, h, w, dss, nullptr, &dcur, &dr)) return 1;
     auto left_phase = [&](int phase) -> int { return t.phase_done ? t.phase_done(phase) : 0; };  // phases: grad_phase()
     if (left_phase(0)) return 1;
     // up path, last stage first; the skip gradients wait for the down path
@@ -941,17 +946,13 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     for (int j = n_st - 1; j >= 0; --j) {
         Stage& S = u->ups[j];
         StageTape& st = tp.ups[j];
-        const std::string q = idx("ups", j);
-        const bool last = j == n_st - 1;
         float* dat = nullptr;
-        if (t_conv_bwd(t, S.resample, st.at.y, dcur, st.h, st.w, h, w, last ? q + ".3.weight" : q + ".3.1.weight",
-                       last ? q + ".3.bias" : q + ".3.1.bias", nullptr, &dat))
-            return 1;
+        if (t_conv_bwd(t, S.resample, st.at.y, dcur, st.h, st.w, h, w, nullptr, &dat)) return 1;
         h = st.h; w = st.w;
         float *db2 = nullptr, *da = nullptr, *dsk2 = nullptr, *dsk1 = nullptr, *dprev = nullptr;
-        if (t_attn_bwd(t, S.attn, st.at, dat, h, w, q + ".2", &db2)) return 1;
-        if (t_resnet_bwd(t, S.b2, st.r2, db2, h, w, dss, q + ".1", nullptr, &da, &dsk2)) return 1;
-        if (t_resnet_bwd(t, S.b1, st.r1, da, h, w, dss, q + ".0", nullptr, &dprev, &dsk1)) return 1;
+        if (t_attn_bwd(t, S.attn, st.at, dat, h, w, &db2)) return 1;
+        if (t_resnet_bwd(t, S.b2, st.r2, db2, h, w, dss, nullptr, &da, &dsk2)) return 1;
+        if (t_resnet_bwd(t, S.b1, st.r1, da, h, w, dss, nullptr, &dprev, &dsk1)) return 1;
         up_skips[j] = {dsk1, dsk2};
         dcur = dprev;
         if (left_phase(1 + (n_st - 1 - j))) return 1;
@@ -961,20 +962,19 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
         const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && tp.ctx != nullptr;
         float *d2 = nullptr, *da = nullptr, *d1 = nullptr, *none = nullptr, *dx = nullptr;
         if (text_cross) {
-            if (t_cross_bwd(t, u->cross_up, tp.cup, dcur, h, w, tp.ctx, tp.ctx_tokens, "cross_attn_up", &dx, tp.mask)) return 1;
+            if (t_cross_bwd(t, u->cross_up, tp.cup, dcur, h, w, tp.ctx, tp.ctx_tokens, &dx, tp.mask)) return 1;
             dcur = dx;
         }
-        if (t_resnet_bwd(t, u->mid2, tp.mid2, dcur, h, w, dss, "mid_block2", nullptr, &d2, &none)) return 1;
-        if (t_attn_bwd(t, u->mid_attn, tp.mid_attn, d2, h, w, "mid_attn", &da)) return 1;
+        if (t_resnet_bwd(t, u->mid2, tp.mid2, dcur, h, w, dss, nullptr, &d2, &none)) return 1;
+        if (t_attn_bwd(t, u->mid_attn, tp.mid_attn, d2, h, w, &da)) return 1;
         if (text_cross) {
-            if (t_cross_bwd(t, u->cross_mid, tp.cmid, da, h, w, tp.ctx, tp.ctx_tokens, "cross_attn", &dx, tp.mask)) return 1;
+            if (t_cross_bwd(t, u->cross_mid, tp.cmid, da, h, w, tp.ctx, tp.ctx_tokens, &dx, tp.mask)) return 1;
             da = dx;
         }
-        if (t_resnet_bwd(t, u->mid1, tp.mid1, da, h, w, dss, "mid_block1", nullptr, &d1, &none)) return 1;
+        if (t_resnet_bwd(t, u->mid1, tp.mid1, da, h, w, dss, nullptr, &d1, &none)) return 1;
         dcur = d1;
         if (text_cross) {
-            if (t_cross_bwd(t, u->cross_down, tp.cdown, dcur, h, w, tp.ctx, tp.ctx_tokens, "cross_attn_down", &dx, tp.mask))
-                return 1;
+            if (t_cross_bwd(t, u->cross_down, tp.cdown, dcur, h, w, tp.ctx, tp.ctx_tokens, &dx, tp.mask)) return 1;
             dcur = dx;
         }
         if (left_phase(n_st + 1)) return 1;
@@ -984,26 +984,22 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     for (int i = n_st - 1; i >= 0; --i) {
         Stage& S = u->downs[i];
         StageTape& st = tp.downs[i];
-        const std::string q = idx("downs", i);
         const bool last = i == n_st - 1;
         float* d_at_skip = up_skips[n_st - 1 - i].first;
         float* d_r1_skip = up_skips[n_st - 1 - i].second;
         float* dat = nullptr;
-        if (t_conv_bwd(t, S.resample, st.at.y, dcur, st.h, st.w, last ? st.h : st.h / 2, last ? st.w : st.w / 2,
-                       last ? q + ".3.weight" : q + ".3.1.weight", last ? q + ".3.bias" : q + ".3.1.bias", d_at_skip, &dat))
+        if (t_conv_bwd(t, S.resample, st.at.y, dcur, st.h, st.w, last ? st.h : st.h / 2, last ? st.w : st.w / 2, d_at_skip, &dat))
             return 1;
         h = st.h; w = st.w;
         float *db2 = nullptr, *da = nullptr, *dprev = nullptr, *none = nullptr;
-        if (t_attn_bwd(t, S.attn, st.at, dat, h, w, q + ".2", &db2)) return 1;
-        if (t_resnet_bwd(t, S.b2, st.r2, db2, h, w, dss, q + ".1", d_r1_skip, &da, &none)) return 1;
-        if (t_resnet_bwd(t, S.b1, st.r1, da, h, w, dss, q + ".0", i == 0 ? dr : nullptr, &dprev, &none)) return 1;
+        if (t_attn_bwd(t, S.attn, st.at, dat, h, w, &db2)) return 1;
+        if (t_resnet_bwd(t, S.b2, st.r2, db2, h, w, dss, d_r1_skip, &da, &none)) return 1;
+        if (t_resnet_bwd(t, S.b1, st.r1, da, h, w, dss, i == 0 ? dr : nullptr, &dprev, &none)) return 1;
         dcur = dprev;
         if (left_phase(n_st + 2 + (n_st - 1 - i))) return 1;
     }
     // init_conv: weight / bias gradient; its input is data, so the input gradient runs only for a call that asks for it
-    if (conv_wgrad(t, u->init_conv, u->train->conv.at(&u->init_conv), x_nchw, nullptr, dcur, H, W, "init_conv.weight",
-                   "init_conv.bias", true))
-        return 1;
+    if (conv_wgrad(t, u->init_conv, x_nchw, nullptr, dcur, H, W, true)) return 1;
     if (ig && !A.dry) {
         DM_REQUIRE(u->train->init_w_raw != nullptr, "the input gradient needs a handle armed by dm_unet_train_enable_ft");
         if (launch_conv7_dgrad(dcur, u->train->init_w_raw, ig->dx, B, H, W, u->init_dim, cfg.input_channels, s)) return 1;
@@ -1114,7 +1110,7 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
 static int unet_train_backward(dm_unet* u, Arena& A, const float* x_nchw, const float* dout_nchw, int B, int H, int W,
                                hipStream_t s, Tape& tp, int accumulate, const InputGrad* ig = nullptr) {
     std::vector<WgradJob> jobs;
-    std::vector<WgradDesc> batch[4];
+    std::vector<WgradDesc> batch[WG_MODES];
     TrainState& T = *u->train;
     int n_flush = 0;
     // run what has been recorded since the last flush: the grouped weight-gradient launches (one per mode) and the launch
@@ -1123,7 +1119,7 @@ static int unet_train_backward(dm_unet* u, Arena& A, const float* x_nchw, const 
         const int fi = n_flush++;
         if ((int)T.flush.size() <= fi) T.flush.resize(fi + 1);
         TrainState::FlushTables& F = T.flush[fi];
-        for (int mode = 0; mode < 4; ++mode) {
+        for (int mode = 0; mode < WG_MODES; ++mode) {
             if (batch[mode].empty()) continue;
             std::vector<int> splits;
             std::vector<size_t> wsf;
@@ -1187,45 +1183,33 @@ static int run_pack_op(dm_unet* u, TrainState& T, const PackOp& op, hipStream_t 
     }
     // the OIHW tensor the packer reads: the parameter itself, or its rotated / transposed form in T.pack_tmp
     const float* w = param(op.src.wname);
-    if (op.src.kind == 1) {
+    if (op.src.kind == PS_ROT) {
         const size_t n = (size_t)op.src.c_n * op.src.sCout * op.src.sK * op.src.sK;
         DM_REQUIRE(n <= T.pack_tmp_floats, "device re-pack: temporary too small");
         if (launch_rot_transpose(w, T.pack_tmp, op.src.sCout, op.src.sCin, op.src.sK, op.src.c_lo, op.src.c_n, s)) return 1;
         w = T.pack_tmp;
-    } else if (op.src.kind == 2) {
+    } else if (op.src.kind == PS_S2D_T) {
         const size_t n = (size_t)4 * op.src.sCin * op.src.sCout;
         DM_REQUIRE(n <= T.pack_tmp_floats, "device re-pack: temporary too small");
         if (launch_s2d_transpose(w, T.pack_tmp, op.src.sCout, op.src.sCin, s)) return 1;
         w = T.pack_tmp;
     }
-    const int Cin = op.C0 + op.C1;
-    switch (op.kind) {
-        case PK_RAW_W:
-            DM_CHECK_HIP(hipMemcpyAsync(op.dst, w, op.n * sizeof(float), hipMemcpyDeviceToDevice, s));
-            return 0;
-        case PK_DIRECT: return launch_pack_direct(w, op.dst, op.Cout, op.C0, op.C1, op.KH, op.KW, s);
-        case PK_FOLD: {
-            // four 2x2 parity convolutions, each packed like a direct convolution; the taps are summed into the second
-            // half of the temporary
-            const size_t per = conv_packed_floats(op.Cout, op.C0, op.C1, 2, 2);
-            const size_t w2n = (size_t)op.Cout * Cin * 4;
-            DM_REQUIRE(op.src.kind == 0 && w2n <= T.pack_tmp_floats, "device re-pack: folded upsample conv");
-            for (int q = 0; q < 4; ++q) {
-                if (launch_fold_taps(w, T.pack_tmp, op.Cout, Cin, q >> 1, q & 1, s)) return 1;
-                if (launch_pack_direct(T.pack_tmp, op.dst + q * per, op.Cout, op.C0, op.C1, 2, 2, s)) return 1;
-            }
-            return 0;
+    if (op.kind == PK_FOLD) {
+        // four 2x2 parity convolutions, each packed like a direct convolution; the taps are summed into the second
+        // half of the temporary
+        const int Cin = op.C0 + op.C1;
+        const size_t per = conv_packed_floats(op.Cout, op.C0, op.C1, 2, 2);
+        const size_t w2n = (size_t)op.Cout * Cin * 4;
+        DM_REQUIRE(op.src.kind == PS_STORED && w2n <= T.pack_tmp_floats, "device re-pack: folded upsample conv");
+        for (int q = 0; q < 4; ++q) {
+            if (launch_fold_taps(w, T.pack_tmp, op.Cout, Cin, q >> 1, q & 1, s)) return 1;
+            if (launch_pack_direct(T.pack_tmp, op.dst + q * per, op.Cout, op.C0, op.C1, 2, 2, s)) return 1;
         }
-        case PK_WINO: return launch_pack_wino(w, op.dst, op.Cout, Cin, s);
-        case PK_WINO4: return launch_pack_wino4(w, op.dst, op.Cout, Cin, s);
-        case PK_UPWINO: return launch_pack_upwino(w, op.dst, op.Cout, Cin, s);
-        case PK_PW: return launch_pack_pw(w, op.dst, op.Cout, Cin, 0, s);
-        case PK_PW_S2D: return launch_pack_pw(w, op.dst, op.Cout, 4 * op.C0, op.C0, s);
-        case PK_INIT7: return launch_pack_init7(w, op.dst, op.C0, s);
-        default: break;
+        return 0;
     }
-    set_error("device re-pack: unknown packing kind");
-    return 1;
+    const ConvRecipe* R = conv_recipe_of(op.kind);
+    DM_REQUIRE(R, "device re-pack: unknown packing kind");
+    return R->device_pack(w, op.dst, op.Cout, op.C0, op.C1, op.KH, op.KW, s);
 }
 
 static bool is_raw_copy(const PackOp& op) { return op.kind == PK_RAW_NAME || op.kind == PK_RAW_B; }
@@ -1270,51 +1254,38 @@ static int index_pack_ops(dm_unet* u) {
 // the grouped form of run_pack_op for the layouts pack_jobs_kernel knows: level-0 job (rotated / transposed source into
 // `tmp`) and level-1 job (the pack); false: the recipe stays on the lazy path
 static bool pack_jobs_of(TrainState& T, const PackOp& op, float* tmp, size_t* tmp_floats, std::vector<PackJob>* lv) {
-    int kind;
-    switch (op.kind) {
-        case PK_RAW_W: kind = PJ_COPY; break;
-        case PK_WINO: kind = PJ_WINO; break;
-        case PK_WINO4: kind = PJ_WINO4; break;
-        case PK_UPWINO: kind = PJ_UPWINO; break;
-        case PK_PW: case PK_PW_S2D: kind = PJ_PW; break;
-        default: return false;
-    }
-    {   // the grouped kernel walks the packed layout: whole chunks / cout tiles only (what the kernels' dispatch requires anyway)
-        const int Cin = op.kind == PK_PW_S2D ? 4 * op.C0 : op.C0 + op.C1;
-        if (kind == PJ_WINO && Cin % 8 != 0) return false;
-        if ((kind == PJ_WINO4 || kind == PJ_UPWINO) && (Cin % 8 != 0 || op.Cout % 64 != 0)) return false;
-        if (kind == PJ_PW && (Cin % 16 != 0 || op.Cout % 16 != 0)) return false;
-    }
+    const ConvFamily* F = nullptr;
+    const ConvRecipe* R = conv_recipe_of(op.kind, &F);
+    if (!R || F->pj < 0) return false;
+    const int kind = F->pj;
+    const int Cin = R->s2d ? 4 * op.C0 : op.C0 + op.C1;
+    // the grouped kernel walks the packed layout: whole chunks / cout tiles only (what the kernels' dispatch requires anyway)
+    if (Cin % F->cin_mult != 0 || op.Cout % F->cout_mult != 0) return false;
     auto it = T.off.find(op.src.wname);
     if (it == T.off.end()) return false;
     const float* w = T.param + it->second;
     *tmp_floats = 0;
     static const bool rot_tmp = env_flag("DM_REPACK_ROT_TMP");  // A/B: materialise the rotated weights first
     int rs = 0, rc = 0;
-    if (op.src.kind == 1 && !rot_tmp &&
-        (((kind == PJ_WINO || kind == PJ_WINO4 || kind == PJ_UPWINO) && op.src.sK == 3) ||
-         (kind == PJ_PW && op.kind == PK_PW && op.src.sK == 1))) {
+    if (op.src.kind == PS_ROT && !rot_tmp && !R->s2d && op.src.sK == F->rot_k) {
         rs = op.src.sCin;  // the pack reads the rotated pair in place
         rc = op.src.c_lo;
-    } else if (op.src.kind == 1) {
+    } else if (op.src.kind == PS_ROT) {
         const long long n = (long long)op.src.c_n * op.src.sCout * op.src.sK * op.src.sK;
         if (lv) lv[0].push_back(PackJob{w, tmp, n, PJ_ROT, op.src.sCout, op.src.sCin, op.src.sK, op.src.c_lo, 0});
         *tmp_floats = (size_t)n;
         w = tmp;
-    } else if (op.src.kind == 2) {
+    } else if (op.src.kind == PS_S2D_T) {
         const long long n = (long long)4 * op.src.sCin * op.src.sCout;
         if (lv) lv[0].push_back(PackJob{w, tmp, n, PJ_S2D_T, op.src.sCout, op.src.sCin, 0, 0, 0});
         *tmp_floats = (size_t)n;
         w = tmp;
     }
     if (!lv) return true;
-    const int Cin = op.C0 + op.C1;
     if (kind == PJ_COPY)
         lv[1].push_back(PackJob{w, op.dst, (long long)op.n, PJ_COPY, 0, 0, 0, 0, 0});
-    else if (op.kind == PK_PW_S2D)
-        lv[1].push_back(PackJob{w, op.dst, (long long)op.Cout * 4 * op.C0, PJ_PW, op.Cout, 4 * op.C0, op.C0, 0, 0});
     else
-        lv[1].push_back(PackJob{w, op.dst, (long long)op.Cout * Cin, kind, op.Cout, Cin, 0, 0, 0, rs, rc});
+        lv[1].push_back(PackJob{w, op.dst, (long long)op.Cout * Cin, kind, op.Cout, Cin, R->s2d ? op.C0 : 0, 0, 0, rs, rc});
     return true;
 }
 
@@ -2024,7 +1995,11 @@ int dm_unet_check_device_pack(dm_unet* u) {
     }
     if (bad) {
         std::string msg = "device packers differ from the host packers:";
-        for (auto& kv : by_kind) msg += " kind " + std::to_string(kv.first) + " x" + std::to_string(kv.second);
+        for (auto& kv : by_kind) {
+            const ConvFamily* F = nullptr;
+            const char* name = conv_recipe_of(kv.first, &F) ? F->name : (kv.first == PK_FOLD ? "folded upsample" : "raw copy");
+            msg += std::string(" ") + name + " x" + std::to_string(kv.second);
+        }
         set_error(msg + "; " + first);
     }
     return bad;

@@ -61,8 +61,7 @@ static int cross_op_layer(OpTrain& op, CrossLayer& Cr, const float* w_q, const f
     if (build_cross_body(&op.u, Cr, "c", C)) return 1;
     if (!train) return 0;
     if (op.alloc_grads()) return 1;
-    return build_conv_bwd(&op.u, *op.u.train, Cr.q, "c.to_q.weight", 1) ||
-           build_conv_bwd(&op.u, *op.u.train, Cr.out, "c.to_out.0.weight", 1);
+    return build_conv_bwd(&op.u, *op.u.train, Cr.q, CB_1X1) || build_conv_bwd(&op.u, *op.u.train, Cr.out, CB_1X1);
 }
 
 static bool cross_op_args_ok(int B, int C, int H, int W, int m, int E, int dim_head) {
@@ -84,9 +83,11 @@ int dm_op_conv2d_bwd(const float* in0, int C0, const float* in1, int C1, const f
         OpTrain op(4, 32);
         const int C1e = in1 ? C1 : 0;
         if (op.param("w", weight, {Cout, C0 + C1e, ksize, ksize}) || op.param("b", nullptr, {Cout}) || op.alloc_grads(true)) return 1;
-        ConvLayer L;
+        ConvLayer L;  // packed without its bias (no forward runs here); "b" is only the slot of the bias gradient
+        L.src.wname = "w";
+        L.src.bname = "b";
         if (make_conv(op.u.own, L, op.u.params["w"].data.data(), nullptr, Cout, C0, C1e, ksize, ksize, 1, pad, up2 != 0)) return 1;
-        if (build_conv_bwd(&op.u, *op.u.train, L, "w", ksize == 3 ? 0 : 1)) return 1;
+        if (build_conv_bwd(&op.u, *op.u.train, L, ksize == 3 ? CB_3X3 : CB_1X1)) return 1;
         const int Ho = up2 ? 2 * H : H, Wo = up2 ? 2 * W : W;
         int rc = run_op(s, [&](Arena& A) -> int {
             int e = 0;
@@ -95,10 +96,9 @@ int dm_op_conv2d_bwd(const float* in0, int C0, const float* in1, int C1, const f
             float* a1 = in1 ? to_nhwc(A, in1, B, C1, H * W, s, &e) : nullptr;
             float* g = to_nhwc(A, dy, B, Cout, Ho * Wo, s, &e);
             if (e) return 1;
-            const ConvBwd& Bw = op.u.train->conv.at(&L);
-            if (conv_wgrad(t, L, Bw, a0, a1, g, Ho, Wo, "w", "b", true)) return 1;
+            if (conv_wgrad(t, L, a0, a1, g, Ho, Wo, true)) return 1;
             float *dx0 = nullptr, *dx1 = nullptr;
-            if (conv_dgrad(t, L, Bw, g, H, W, nullptr, nullptr, &dx0, &dx1)) return 1;
+            if (conv_dgrad(t, L, g, H, W, nullptr, nullptr, &dx0, &dx1)) return 1;
             if (from_nhwc(A, dx0, d_in0, B, C0, H * W, s)) return 1;
             if (in1 && from_nhwc(A, dx1, d_in1, B, C1, H * W, s)) return 1;
             if (!A.dry && (op.out("w", d_weight, s) || op.out("b", d_bias, s))) return 1;
@@ -116,9 +116,11 @@ int dm_op_downsample_bwd(const float* in, int C, const float* weight, const floa
     return guarded([&]() -> int {
         OpTrain op(4, 32);
         if (op.param("w", weight, {Cout, 4 * C, 1, 1}) || op.param("b", nullptr, {Cout}) || op.alloc_grads(true)) return 1;
-        ConvLayer L;
+        ConvLayer L;  // (as in dm_op_conv2d_bwd)
+        L.src.wname = "w";
+        L.src.bname = "b";
         if (make_conv(op.u.own, L, op.u.params["w"].data.data(), nullptr, Cout, C, 0, 2, 2, 2, 0, false)) return 1;
-        if (build_conv_bwd(&op.u, *op.u.train, L, "w", 2)) return 1;
+        if (build_conv_bwd(&op.u, *op.u.train, L, CB_DOWN)) return 1;
         return run_op(s, [&](Arena& A) -> int {
             int e = 0;
             TCtx t{&op.u, &A, s, B, nullptr, 0};
@@ -126,7 +128,7 @@ int dm_op_downsample_bwd(const float* in, int C, const float* weight, const floa
             float* g = to_nhwc(A, dy, B, Cout, (H / 2) * (W / 2), s, &e);
             if (e) return 1;
             float* dx = nullptr;
-            if (t_conv_bwd(t, L, a0, g, H, W, H / 2, W / 2, "w", "b", nullptr, &dx)) return 1;
+            if (t_conv_bwd(t, L, a0, g, H, W, H / 2, W / 2, nullptr, &dx)) return 1;
             if (from_nhwc(A, dx, d_in, B, C, H * W, s)) return 1;
             if (!A.dry && (op.out("w", d_weight, s) || op.out("b", d_bias, s))) return 1;
             return 0;
@@ -146,10 +148,8 @@ int dm_op_block_bwd(const float* x, int Cin, const float* weight, const float* b
             op.param("blk.norm.g", g, {1, Cout, 1, 1}) || op.alloc_grads(true))
             return 1;
         ConvLayer L;
-        if (make_conv(op.u.own, L, op.u.params["blk.proj.weight"].data.data(), op.u.params["blk.proj.bias"].data.data(), Cout,
-                      Cin, 0, 3, 3, 1, 1, false))
-            return 1;
-        if (build_conv_bwd(&op.u, *op.u.train, L, "blk.proj.weight", 0)) return 1;
+        if (make_conv(&op.u, L, "blk.proj.weight", "blk.proj.bias", Cout, Cin, 0, 3, 3, 1, 1, false)) return 1;
+        if (build_conv_bwd(&op.u, *op.u.train, L, CB_3X3)) return 1;
         op.u.ss_total = 2 * Cout;
         return run_op(s, [&](Arena& A) -> int {
             int e = 0;
@@ -175,7 +175,7 @@ int dm_op_block_bwd(const float* x, int Cin, const float* weight, const float* b
             float* du = nullptr;
             if (t_block_bwd(t, L, bt, DyParts{gy}, H, W, g, scale ? t.ss : nullptr, 0, dss, "blk", &du)) return 1;
             float *d0 = nullptr, *none = nullptr;
-            if (conv_dgrad(t, L, op.u.train->conv.at(&L), du, H, W, nullptr, nullptr, &d0, &none)) return 1;
+            if (conv_dgrad(t, L, du, H, W, nullptr, nullptr, &d0, &none)) return 1;
             if (from_nhwc(A, d0, dx, B, Cin, H * W, s)) return 1;
             if (A.dry) return 0;
             if (op.out("blk.proj.weight", d_weight, s) || op.out("blk.proj.bias", d_bias, s) || op.out("blk.norm.g", d_g, s))
@@ -245,17 +245,16 @@ static int attn_bwd_op(bool full, const float* x, const float* norm_g, const flo
             op.param(bo, b_out, {C}) || (!full && op.param("a.to_out.1.g", out_g, {1, C, 1, 1})) || op.alloc_grads())
             return 1;
         AttnLayer At;
+        At.prefix = "a";
         At.full = full;
         At.dim = C;
         At.heads = heads;
         At.norm_g = const_cast<float*>(norm_g);
         At.mem_kv = const_cast<float*>(mem_kv);
         At.out_g = const_cast<float*>(out_g);
-        if (make_conv(op.u.own, At.qkv, op.u.params["a.to_qkv.weight"].data.data(), nullptr, 3 * hidden, C, 0, 1, 1, 1, 0, false))
-            return 1;
-        if (make_conv(op.u.own, At.out, op.u.params[wo].data.data(), op.u.params[bo].data.data(), C, hidden, 0, 1, 1, 1, 0, false))
-            return 1;
-        if (build_attn_bwd(&op.u, *op.u.train, At, "a")) return 1;
+        if (make_conv(&op.u, At.qkv, "a.to_qkv.weight", "", 3 * hidden, C, 0, 1, 1, 1, 0, false)) return 1;
+        if (make_conv(&op.u, At.out, wo, bo, C, hidden, 0, 1, 1, 1, 0, false)) return 1;
+        if (build_attn_bwd(&op.u, *op.u.train, At)) return 1;
         return run_op(s, [&](Arena& A) -> int {
             int e = 0;
             TCtx t{&op.u, &A, s, B, nullptr, 0};
@@ -265,7 +264,7 @@ static int attn_bwd_op(bool full, const float* x, const float* norm_g, const flo
             AttnTape at;
             if (t_attn(t, At, a, H, W, at)) return 1;
             float* d = nullptr;
-            if (t_attn_bwd(t, At, at, gy, H, W, "a", &d, /*add_x=*/false)) return 1;  // the module alone, no "+ x"
+            if (t_attn_bwd(t, At, at, gy, H, W, &d, /*add_x=*/false)) return 1;  // the module alone, no "+ x"
             if (from_nhwc(A, d, dx, B, C, H * W, s)) return 1;
             if (A.dry) return 0;
             if (op.out("a.norm.g", d_norm_g, s) || op.out("a.mem_kv", d_mem_kv, s) || op.out("a.to_qkv.weight", d_w_qkv, s) ||
@@ -392,7 +391,7 @@ int dm_op_cross_attention_bwd(const float* x, const float* ctx, const float* w_q
             if (t_cross(t, Cr, a, H, W, ctx, m, ct, text_mask)) return 1;
             if (from_nhwc(A, ct.y, y_out, B, C, H * W, s)) return 1;
             float* d = nullptr;
-            if (t_cross_bwd(t, Cr, ct, gy, H, W, ctx, m, "c", &d, text_mask)) return 1;
+            if (t_cross_bwd(t, Cr, ct, gy, H, W, ctx, m, &d, text_mask)) return 1;
             if (from_nhwc(A, d, dx, B, C, H * W, s)) return 1;
             if (A.dry) return 0;
             if (op.out("c.to_q.weight", d_w_q, s) || op.out("c.to_k.weight", d_w_k, s) || op.out("c.to_v.weight", d_w_v, s) ||

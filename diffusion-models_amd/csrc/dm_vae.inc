@@ -132,8 +132,7 @@ static void vexpect_attn(dm_unet* u, const std::string& p, int c) {
     }
 }
 static int vconv(dm_unet* u, ConvLayer& L, const std::string& p, int cout, int cin, int k, int pad, bool up) {
-    return make_conv(u->own, L, P(u, p + ".weight").data.data(), P(u, p + ".bias").data.data(), cout, cin, 0, k, k, 1,
-                     pad, up);
+    return make_conv(u, L, p + ".weight", p + ".bias", cout, cin, 0, k, k, 1, pad, up);
 }
 static int vbuild_res(dm_unet* u, VaeRes& R, const std::string& p, int cin, int cout) {
     R.cin = cin;
@@ -580,8 +579,8 @@ int dm_encoder_finalize(dm_encoder* d) {
         L.has_up = lvl != cfg.n_levels - 1;
         if (L.has_up) {
             const std::string q = p + ".downsample.conv";
-            if (make_conv(u->own, L.up, P(u, q + ".weight").data.data(), P(u, q + ".bias").data.data(), block_in, block_in, 0,
-                          3, 3, /*stride=*/2, /*pad=*/0, false, /*pad_hi=*/1))
+            if (make_conv(u, L.up, q + ".weight", q + ".bias", block_in, block_in, 0, 3, 3, /*stride=*/2, /*pad=*/0, false,
+                          /*pad_hi=*/1))
                 return 1;
             curr_res /= 2;
         }

@@ -93,6 +93,18 @@ def test_training_goldens_with_one_launch_per_layer():
                        DM_REPACK_ROT_TMP="1"))
 
 
+def test_grouped_repack_of_the_forced_families():
+    """The grouped re-pack after an optimiser step covers only the buffers a training step has used, and under the default
+    thresholds no small shape uses the F(4x4) or the upsample-Winograd buffers.  With the thresholds lowered the two nets of
+    test_device_packers_match_host_packers (dim 64 at 32x32, dim 32 at 16x16, B = 2) train through those kernels, so their
+    grouped jobs are compared with the host packers bit for bit as well."""
+    env = dict(os.environ, DM_WINO4_MIN_WGS="1", DM_WINO4_MIN_K="1", DM_UPWINO_MIN_WGS="1", DM_UPWINO_MIN_K="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_hip_train.py"), "-q", "-x", "-m",
+                        "gpu", "-k", "test_device_packers_match_host_packers", "-p", "no:cacheprovider"],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
+
+
 def test_attention_backward_tiled_form_on_every_shape():
     """The operator-level attention backward cases and the text-conditional training step (mid_attn + CrossAttention) with the
     tiled kernels forced on the short sequences the LDS-resident kernel normally takes; and the LDS-resident kernel without
