@@ -54,7 +54,8 @@ def cg_step_table(sched: Dict[str, torch.Tensor], times=None) -> Tuple[List[int]
 
 class ClassifierGuidedGaussianDiffusion(DenoisingDiffusion):
     """``guided_diffusion.GaussianDiffusion`` (guided_diffusion.py:380-727): the reference's constructor signature and
-    defaults, plus ``use_graph``.  Training (``p_losses``, ``forward``) is the base class's."""
+    defaults, plus ``use_graph``.  Training (``p_losses``, ``forward``) is the base class's.  So is ``dpm_solver_sample``:
+    it takes no ``cond_fn`` and samples unguided, as this class's ``ddim_sample`` does."""
 
     def __init__(
         self,

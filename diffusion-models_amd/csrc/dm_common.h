@@ -290,6 +290,11 @@ int launch_sampler_update(int kind, const float* x, const float* eps, const floa
                           float* final_out, int64_t n, hipStream_t s, int objective = 0, float* xstart_out = nullptr,
                           float* dup_out = nullptr);
 // (dup_out: a second copy of `out`, the null half of a guided step's 2B input)
+// One DPM-Solver++ (2M) update on a row of dpmpp_step_table: hist is the previous step's clamped x_0 estimate and receives
+// this step's (in place); a row with c[4] == 0 does not read it.  state_dev == nullptr: row 0, a stand-alone update.
+int launch_dpmpp_update(const float* x, const float* model_out, float* hist, const float* coefs_dev,
+                        const SamplerState* state_dev, float* out, float* all_steps, float* dup_out, int64_t n, hipStream_t s,
+                        int objective = 0);
 // element e of the tensor uses Philox counter ((element_offset + e) / 4, draw); element_offset % 4 == 0
 int launch_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t element_offset, hipStream_t s);
 int launch_step_advance(SamplerState* state_dev, hipStream_t s);

@@ -282,6 +282,16 @@ int dm_op_sampler_update(int kind, int objective, const float* x, const float* e
     }, DM_COEFS);
 }
 
+int dm_op_dpmpp_update(int objective, const float* x, const float* model_out, float* x0_hist, const float* coef_host,
+                       float* out, int64_t n, void* stream) {
+    DM_REQUIRE(x && model_out && x0_hist && coef_host && out, "null argument");
+    DM_REQUIRE(n > 0, "empty tensor");
+    DM_REQUIRE(objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "unknown objective");
+    return table_op(coef_host, 1, stream, [&](const float* cd, hipStream_t s) {
+        return launch_dpmpp_update(x, model_out, x0_hist, cd, nullptr, out, nullptr, nullptr, n, s, objective);
+    }, DM_COEFS);
+}
+
 int dm_op_cfg_combine(const float* cond, const float* null_out, float* out, int B, int64_t per_sample, float cond_scale,
                       float rescaled_phi, int remove_parallel_component, float keep_parallel_frac, void* stream) {
     DM_REQUIRE(cond && null_out && out, "null argument");

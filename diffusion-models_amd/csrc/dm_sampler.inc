@@ -264,7 +264,8 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
                        int self_cond = 0, const CfgParams* guide = nullptr) {
     DM_REQUIRE(u && times_host && coefs_host && x_T && out, "null argument");
     if (handle_ready(u)) return 1;
-    DM_REQUIRE(kind == DM_SAMPLER_DDPM || kind == DM_SAMPLER_DDIM, "unknown sampler kind");
+    DM_REQUIRE(kind == DM_SAMPLER_DDPM || kind == DM_SAMPLER_DDIM || kind == DM_SAMPLER_DPMPP, "unknown sampler kind");
+    const bool dpmpp = kind == DM_SAMPLER_DPMPP;
     DM_REQUIRE(n_steps > 0 && B > 0, "empty run");
     DM_REQUIRE(u->out_dim == u->cfg.channels, "sampler needs out_dim == channels (DD/denoising_diffusion.py:456)");
     DM_REQUIRE((cond == nullptr) == (cond_channels == 0) && cond_channels >= 0, "cond and cond_channels come together");
@@ -308,7 +309,9 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
         eps = A.alloc(n);
         eps2 = guided ? A.alloc(2 * n) : nullptr;  // model output of the conditioned and the null half
         xin = wide ? A.alloc(n_in) : nullptr;      // [x | cond] or [x_start | x] per image, what init_conv reads
-        xstart = self_cond ? A.alloc(n) : nullptr;  // clamped x_0 estimate of the previous step
+        // clamped x_0 estimate of the previous step: what self-conditioning feeds back and what DPM-Solver++ (2M)
+        // extrapolates from, one buffer for both
+        xstart = self_cond || dpmpp ? A.alloc(n) : nullptr;
         ctxbuf = ctx ? A.alloc(guided ? 2 * n_ctx : n_ctx) : nullptr;
         tmask = guided ? reinterpret_cast<int32_t*>(A.alloc(2 * B)) : nullptr;
         gpar = guided ? A.alloc(4) : nullptr;  // CfgParams: device data, so a captured step serves any guidance scale
@@ -337,7 +340,7 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
         DM_CHECK_HIP(hipMemcpyAsync(ctxbuf + n_ctx, ctx, n_ctx * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     if (cond && launch_copy_channels(cond, xin, B, cond_channels, C + cond_channels, C, H * W, s)) return 1;
-    if (self_cond) DM_CHECK_HIP(hipMemsetAsync(xstart, 0, n * sizeof(float), s));  // x_self_cond = zeros_like(x) (:353)
+    if (xstart) DM_CHECK_HIP(hipMemsetAsync(xstart, 0, n * sizeof(float), s));  // x_self_cond = zeros_like(x) (:353)
     if (all_steps) DM_CHECK_HIP(hipMemcpyAsync(all_steps, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
 
     auto one_step = [&](hipStream_t st) -> int {
@@ -356,15 +359,17 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
             return 1;
         }
         // guided: x_{t-1} goes to both halves of the next step's input
-        if (launch_sampler_update(kind, xbuf, eps, noise, u->coefs_dev, u->state_dev, n, xbuf, all_steps, nullptr, n, st,
-                                  objective, xstart, guided ? xbuf + n : nullptr))
+        float* const dup = guided ? xbuf + n : nullptr;
+        if (dpmpp ? launch_dpmpp_update(xbuf, eps, xstart, u->coefs_dev, u->state_dev, xbuf, all_steps, dup, n, st, objective)
+                  : launch_sampler_update(kind, xbuf, eps, noise, u->coefs_dev, u->state_dev, n, xbuf, all_steps, nullptr, n, st,
+                                          objective, xstart, dup))
             return 1;
         return launch_step_advance(u->state_dev, st);
     };
     // profiling leg: park the GPU while the host enqueues, so that event intervals are kernel times (<= 8 steps)
     if (!use_graph && prof::enabled() && n_steps <= 8 && launch_spin(8.0 * n_steps, s)) return 1;
     dm_unet::GraphKey key;
-    key.kind = kind == DM_SAMPLER_DDPM ? dm_unet::GK_DDPM : dm_unet::GK_DDIM;
+    key.kind = dpmpp ? dm_unet::GK_DPMPP : kind == DM_SAMPLER_DDPM ? dm_unet::GK_DDPM : dm_unet::GK_DDIM;
     key.B = B; key.H = H; key.W = W; key.ctx_tokens = ctx_tokens; key.cond_channels = cond_channels;
     key.objective = objective; key.self_cond = self_cond; key.guided = guided;
     key.noise = noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.coefs = u->coefs_dev;

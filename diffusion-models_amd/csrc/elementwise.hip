@@ -599,6 +599,39 @@ __global__ void sampler_update_kernel(int kind, int objective, const float* __re
         if (final_out && step == n_steps - 1) final_out[i] = unnormalize ? (r + 1.0f) * 0.5f : r;
     }
 }
+// One DPM-Solver++ update (arXiv 2211.01095, Algorithm 2: multistep, data prediction) on a row of dpmpp_step_table:
+//   x0 = ddpm_x_start (c[0], c[1] / c[6], c[7] by objective, clamped as in the DDIM branch above)
+//   D  = x0 + c[4] * (x0 - hist)            c[4] = h / (2 h_last); 0 at order 1, at the first and at the last step
+//   r  = c[2] * x + c[3] * D                c[2] = sigma_next / sigma_t, c[3] = -alpha_next * expm1(-h)
+//   r  = x0 where c[5] == 0 (t_next < 0, as DDIM's last step, :686-689)
+// hist holds the previous step's x0 and receives this step's: a thread reads and writes its own elements only, so the
+// update is in place.  With c[4] == 0 hist is not read: whatever it holds (NaN, uninitialised memory) stays out of r.
+__global__ void dpmpp_update_kernel(int objective, const float* __restrict__ x, const float* __restrict__ model_out,
+                                    float* __restrict__ hist, const float* __restrict__ coefs,
+                                    const SamplerState* __restrict__ st, float* __restrict__ out,
+                                    float* __restrict__ all_steps, float* __restrict__ dup_out, int64_t n) {
+    const int step = st ? st->step : 0;
+    const float* c = coefs + (size_t)step * 8;
+    const DdpmCoefs dc = ddpm_coefs(c);
+    const bool flag = c[5] != 0.0f;
+    const bool second = dc.c4 != 0.0f;
+    const int64_t i4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i4 * 4 >= n) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t i = i4 * 4 + j;
+        if (i >= n) break;
+        const float xv = x[i];
+        const float x0 = ddpm_x_start(dc, objective, xv, model_out[i]);
+        float d = x0;
+        if (second) d = x0 + dc.c4 * (x0 - hist[i]);
+        const float r = flag ? dc.c2 * xv + dc.c3 * d : x0;
+        hist[i] = x0;
+        out[i] = r;
+        if (dup_out) dup_out[i] = r;
+        if (all_steps) all_steps[(size_t)(step + 1) * n + i] = r;
+    }
+}
 // out = x or (x + 1) / 2: `unnormalize` at the end of a loop (DD/denoising_diffusion.py:663,:707)
 __global__ void finalize_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n, int unnormalize) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -621,6 +654,17 @@ int launch_sampler_update(int kind, const float* x, const float* eps, const floa
     int64_t n4 = (n + 3) / 4;
     hipLaunchKernelGGL(sampler_update_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, kind, objective, x, eps, noise,
                        coefs_dev, state_dev, noise_step_stride, out, all_steps, final_out, xstart_out, dup_out, n);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_dpmpp_update(const float* x, const float* model_out, float* hist, const float* coefs_dev,
+                        const SamplerState* state_dev, float* out, float* all_steps, float* dup_out, int64_t n, hipStream_t s,
+                        int objective) {
+    DM_REQUIRE(hist != nullptr, "the DPM-Solver++ update needs its history buffer");
+    int64_t n4 = (n + 3) / 4;
+    hipLaunchKernelGGL(dpmpp_update_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, objective, x, model_out, hist, coefs_dev,
+                       state_dev, out, all_steps, dup_out, n);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -35,10 +35,17 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, _loop
-from .spec import SCHEDULE_BUFFERS, ddim_step_table, ddpm_step_table, make_schedule
+from .spec import SCHEDULE_BUFFERS, ddim_step_table, ddpm_step_table, dpmpp_step_table, make_schedule
 from .unet import check_guidance
 
-DDPM, DDIM = 0, 1
+DDPM, DDIM, DPMPP = 0, 1, 2  # DM_SAMPLER_* of include/dm_hip.h
+
+
+def _solver(solver):
+    """``solver=`` of ``sample()``: None (the reference's dispatch on ``sampling_timesteps``) or 'dpmpp'."""
+    if solver not in (None, "dpmpp"):
+        raise ValueError(f"unknown solver {solver!r}: None (DDPM / DDIM by sampling_timesteps) or 'dpmpp'")
+    return solver
 
 
 def _identity(t, *a, **k):
@@ -392,11 +399,32 @@ class DenoisingDiffusion:
         return self._run(DDIM, shape, times, coefs, takes, return_all_timesteps, noise, seed, text_emb, max_steps,
                          sample_offset=sample_offset, guidance=_guidance)
 
+    def _dpmpp_tables(self, sampling_timesteps, order) -> Tuple[List[int], torch.Tensor]:
+        if sampling_timesteps is None:
+            sampling_timesteps = self.sampling_timesteps if self.is_ddim_sampling else 20
+        return dpmpp_step_table(self._sched, sampling_timesteps, order)
+
     @torch.inference_mode()
-    def sample(self, batch_size=16, return_all_timesteps=False, **kw):
+    def dpm_solver_sample(self, shape, sampling_timesteps=None, order=2, return_all_timesteps=False, *, noise=None, seed=None,
+                          max_steps=None, text_emb=None, sample_offset=0, _guidance=None):
+        """DPM-Solver++ (Lu et al., arXiv 2211.01095, Algorithm 2: multistep, data prediction) on the time grid of
+        ``ddim_sample``; not in the reference.  ``order=2`` is the 2M solver, ``order=1`` is DDIM with eta = 0 in another
+        arrangement of the same terms.  x_start is clamped at every step as ``ddim_sample`` clamps it.
+        ``sampling_timesteps`` defaults to the constructor's when that selects DDIM sampling, else to 20.  No noise is drawn
+        after x_T: an injected ``noise`` callable is called once."""
+        times, coefs = self._dpmpp_tables(sampling_timesteps, order)
+        return self._run(DPMPP, shape, times, coefs, [], return_all_timesteps, noise, seed, text_emb, max_steps,
+                         sample_offset=sample_offset, guidance=_guidance)
+
+    @torch.inference_mode()
+    def sample(self, batch_size=16, return_all_timesteps=False, *, solver=None, order=2, **kw):
+        """:779-783; ``solver='dpmpp'`` (an extension) samples with ``dpm_solver_sample`` at ``order``."""
         (h, w), channels = self.image_size, self.channels
+        shape = (batch_size, channels, h, w)
+        if _solver(solver):
+            return self.dpm_solver_sample(shape, order=order, return_all_timesteps=return_all_timesteps, **kw)
         sample_fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
-        return sample_fn((batch_size, channels, h, w), return_all_timesteps=return_all_timesteps, **kw)
+        return sample_fn(shape, return_all_timesteps=return_all_timesteps, **kw)
 
     @torch.inference_mode()
     def interpolate(self, x1, x2, t=None, lam=0.5, *, noise=None, seed=None):
@@ -661,10 +689,26 @@ class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
         return super().ddim_sample(shape, sampling_timesteps, return_all_timesteps, text_emb=text_emb, _guidance=g, **kw)
 
     @torch.inference_mode()
+    def dpm_solver_sample(self, shape, save_path_for_text=None, sampling_timesteps=None, order=2,
+                          return_all_timesteps=False, *, text_emb=None, cond_scale=1.0, rescaled_phi=0.0,
+                          remove_parallel_component=True, keep_parallel_frac=0.0, **kw):
+        """The parent's DPM-Solver++ loop with the caption embeddings and the guidance keywords of ``ddim_sample``."""
+        g = self._guidance(cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
+        text_emb = self._text(shape[0], save_path_for_text, text_emb)
+        return super().dpm_solver_sample(shape, sampling_timesteps, order, return_all_timesteps, text_emb=text_emb,
+                                         _guidance=g, **kw)
+
+    def _sample_fn(self, solver, order):
+        """The loop ``sample()`` runs, called as fn(shape, save_path_for_text, **keywords)."""
+        if _solver(solver):
+            return lambda shape, path, **kw: self.dpm_solver_sample(shape, path, order=order, **kw)
+        return self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
+
+    @torch.inference_mode()
     def sample(self, batch_size=16, save_path_for_text=None, return_all_timesteps=False, *, cond_scale=1.0,
-               rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, **kw):
+               rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, solver=None, order=2, **kw):
         (h, w), channels = self.image_size, self.channels
-        sample_fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
+        sample_fn = self._sample_fn(solver, order)
         return sample_fn((batch_size, channels, h, w), save_path_for_text, return_all_timesteps=return_all_timesteps,
                          cond_scale=cond_scale, rescaled_phi=rescaled_phi,
                          remove_parallel_component=remove_parallel_component, keep_parallel_frac=keep_parallel_frac, **kw)
@@ -797,9 +841,23 @@ class ImageConditionalDenoisingDiffusion(DenoisingDiffusion):
                          None, max_steps, cond=cond, sample_offset=sample_offset)
 
     @torch.inference_mode()
-    def sample(self, batch_size=16, return_condition_image=False, return_all_timesteps=False, *, cond=None, **kw):
+    def dpm_solver_sample(self, shape, sampling_timesteps=None, order=2, cond=None, return_condition_image=False,
+                          return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0):
+        """The parent's DPM-Solver++ loop with the condition image behind x at every step, as in ``ddim_sample``."""
+        times, coefs = self._dpmpp_tables(sampling_timesteps, order)
+        cond = self._cond(shape[0], cond)
+        ret = self._run(DPMPP, shape, times, coefs, [], return_all_timesteps, noise, seed, None, max_steps, cond=cond,
+                        sample_offset=sample_offset)
+        return (cond, ret) if return_condition_image else ret
+
+    @torch.inference_mode()
+    def sample(self, batch_size=16, return_condition_image=False, return_all_timesteps=False, *, cond=None, solver=None,
+               order=2, **kw):
         (h, w), channels = self.image_size, self.channels
         shape = (batch_size, channels, h, w)
+        if _solver(solver):
+            return self.dpm_solver_sample(shape, order=order, cond=cond, return_condition_image=return_condition_image,
+                                          return_all_timesteps=return_all_timesteps, **kw)
         if not self.is_ddim_sampling:
             return self.p_sample_loop(shape, return_condition_image, return_all_timesteps, cond=cond, **kw)
         cond = self._cond(batch_size, cond)
@@ -866,10 +924,14 @@ class LatentDiffusion(DenoisingDiffusion):
     __call__ = forward
 
     @torch.inference_mode()
-    def sample(self, batch_size=16, return_all_timesteps=False, **kw):
+    def sample(self, batch_size=16, return_all_timesteps=False, *, solver=None, order=2, **kw):
+        """``solver='dpmpp'``: the latents come from ``dpm_solver_sample`` (the parent's, on latents) and are decoded."""
         (h, w), channels = self.image_size, self.channels
+        shape = (batch_size, channels, h, w)
+        if _solver(solver):
+            return self.decode(self.dpm_solver_sample(shape, order=order, return_all_timesteps=return_all_timesteps, **kw))
         sample_fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
-        latents = sample_fn((batch_size, channels, h, w), return_all_timesteps=return_all_timesteps, **kw)
+        latents = sample_fn(shape, return_all_timesteps=return_all_timesteps, **kw)
         return self.decode(latents)
 
 
@@ -903,9 +965,10 @@ class TextConditionalLatentDiffusion(TextConditionalDenoisingDiffusion):
 
     @torch.inference_mode()
     def sample(self, batch_size=16, save_path_for_text=None, return_all_timesteps=False, *, cond_scale=1.0,
-               rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, **kw):
+               rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, solver=None, order=2, **kw):
+        """``solver='dpmpp'``: the latents come from ``dpm_solver_sample`` (the parent's, on latents) and are decoded."""
         (h, w), channels = self.image_size, self.channels
-        sample_fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
+        sample_fn = self._sample_fn(solver, order)
         latents = sample_fn((batch_size, channels, h, w), save_path_for_text,
                             return_all_timesteps=return_all_timesteps, cond_scale=cond_scale, rescaled_phi=rescaled_phi,
                             remove_parallel_component=remove_parallel_component, keep_parallel_frac=keep_parallel_frac,
@@ -967,11 +1030,23 @@ class ImageConditionalLatentDiffusion(ImageConditionalDenoisingDiffusion):
         return super().ddim_sample(shape, sampling_timesteps, self.encode(cond, cond=True), return_all_timesteps, **kw)
 
     @torch.inference_mode()
-    def sample(self, batch_size=16, return_condition_image=False, return_all_timesteps=False, *, cond=None, **kw):
+    def dpm_solver_sample(self, shape, sampling_timesteps=None, order=2, cond=None, return_condition_image=False,
+                          return_all_timesteps=False, **kw):
+        """``cond`` is the condition IMAGE (encoded here), as in this class's ``ddim_sample``; the result is the latents."""
+        cond = self._cond(shape[0], cond)
+        ret = super().dpm_solver_sample(shape, sampling_timesteps, order, self.encode(cond, cond=True), False,
+                                        return_all_timesteps, **kw)
+        return (cond, ret) if return_condition_image else ret
+
+    @torch.inference_mode()
+    def sample(self, batch_size=16, return_condition_image=False, return_all_timesteps=False, *, cond=None, solver=None,
+               order=2, **kw):
         (h, w), channels = self.image_size, self.channels
         shape = (batch_size, channels, h, w)
         cond = self._cond(batch_size, cond)
-        if not self.is_ddim_sampling:
+        if _solver(solver):
+            lat = self.dpm_solver_sample(shape, order=order, cond=cond, return_all_timesteps=return_all_timesteps, **kw)
+        elif not self.is_ddim_sampling:
             lat = self.p_sample_loop(shape, False, return_all_timesteps, cond=cond, **kw)
         else:
             lat = self.ddim_sample(shape, None, cond, return_all_timesteps, **kw)

@@ -100,6 +100,11 @@ class LearnedGaussianDiffusion(DenoisingDiffusion):
     def ddim_sample_guided(self, *args, **kwargs):
         raise NotImplementedError(_NO_PATH.format("ddim_sample_guided (it calls model_predictions)"))
 
+    def dpm_solver_sample(self, *args, **kwargs):
+        raise NotImplementedError("LearnedGaussianDiffusion has no dpm_solver_sample: the model output is (prediction, "
+                                  "variance interpolation), not the plain prediction DPM-Solver++ steps on, and the class has "
+                                  "no model_predictions")
+
     # -- sampling ---------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0):

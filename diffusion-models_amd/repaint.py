@@ -96,7 +96,8 @@ def repaint_step_table(sched: Dict[str, torch.Tensor], resample=True, resample_i
 
 class GaussianDiffusion(DenoisingDiffusion):
     """``repaint.GaussianDiffusion`` (repaint.py:423-840): the reference's constructor signature and defaults, plus
-    ``use_graph``."""
+    ``use_graph``.  ``dpm_solver_sample`` is the parent's, inherited as ``ddim_sample`` is: it takes no ``gt`` / ``mask``
+    and samples unmasked; inpainting is the DDPM loop only."""
 
     def __init__(
         self,

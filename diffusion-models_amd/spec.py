@@ -367,6 +367,45 @@ def ddim_step_table(sched: Dict[str, torch.Tensor], sampling_timesteps: int, eta
     return [p[0] for p in pairs], c
 
 
+def dpmpp_step_table(sched: Dict[str, torch.Tensor], sampling_timesteps: int, order: int = 2) -> Tuple[List[int], torch.Tensor]:
+    """Per-step scalars of DPM-Solver++ (Lu et al., arXiv 2211.01095, Algorithm 2: multistep, data prediction) on the DDIM
+    time grid.  With alpha = sqrt(ac), sigma = sqrt(1 - ac), lambda = log(alpha / sigma) and h = lambda_next - lambda_t,
+    row i: [sqrt_recip_ac[t], sqrt_recipm1_ac[t], sigma_next / sigma_t, -alpha_next * expm1(-h), g, t_next>=0, sqrt_ac[t],
+    sqrt_1m_ac[t]], g = h / (2 h_last) at order 2 from the second step on, else 0.  The step is
+    x_next = c2 x + c3 (x0 + g (x0 - x0_prev)); order 1 is DDIM with eta = 0.  The last row (t_next = -1: alpha_next = 1,
+    sigma_next = 0, h = inf) is the limit c2 = 0, c3 = 1, g = 0 with flag 0: img = x_start, as in ddim_step_table.
+
+    lambda, h, c2, c3 and g are float64 from the schedule's betas and rounded to fp32 once: ``1 - alphas_cumprod`` of the fp32
+    buffer keeps about four digits near t = 0, where sigma_next / sigma_t needs them."""
+    T = int(sched["betas"].shape[0])
+    if order not in (1, 2):
+        raise ValueError(f"DPM-Solver++ order must be 1 or 2, got {order!r}")
+    if isinstance(sampling_timesteps, bool) or not isinstance(sampling_timesteps, int) or not 1 <= sampling_timesteps <= T:
+        raise ValueError(f"sampling_timesteps must be an integer in [1, {T}], got {sampling_timesteps!r}")
+    pairs = ddim_time_pairs(T, sampling_timesteps)
+    ac = torch.cumprod(1.0 - sched["betas"].to(torch.float64), dim=0)
+    alpha, sigma = ac.sqrt(), (1.0 - ac).sqrt()
+    lam = torch.log(alpha / sigma)
+    c = torch.zeros(len(pairs), DM_COEFS, dtype=torch.float64)
+    h_last = None
+    for i, (t, tn) in enumerate(pairs):
+        c[i, 0] = sched["sqrt_recip_alphas_cumprod"][t]
+        c[i, 1] = sched["sqrt_recipm1_alphas_cumprod"][t]
+        c[i, 6] = sched["sqrt_alphas_cumprod"][t]
+        c[i, 7] = sched["sqrt_one_minus_alphas_cumprod"][t]
+        if tn < 0:
+            c[i, 3] = 1.0
+            continue
+        h = lam[tn] - lam[t]
+        c[i, 2] = sigma[tn] / sigma[t]
+        c[i, 3] = -alpha[tn] * torch.expm1(-h)
+        if order == 2 and h_last is not None:
+            c[i, 4] = h / (2.0 * h_last)
+        c[i, 5] = 1.0
+        h_last = h
+    return [p[0] for p in pairs], c.to(torch.float32)
+
+
 # ----------------------------------------------------------------------------
 # VAE decoder (LDM)
 # ----------------------------------------------------------------------------

@@ -102,6 +102,10 @@ class WeightedObjectiveGaussianDiffusion(DenoisingDiffusion):
     def ddim_sample_guided(self, *args, **kwargs):
         raise NotImplementedError(_NO_DDIM.format("ddim_sample_guided"))
 
+    def dpm_solver_sample(self, *args, **kwargs):
+        raise NotImplementedError(_NO_DDIM.format("dpm_solver_sample (the model output is a softmax blend of two predictions, "
+                                                  "not the plain prediction DPM-Solver++ steps on)"))
+
     # -- sampling ---------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0):

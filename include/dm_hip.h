@@ -124,6 +124,13 @@ int dm_unet_forward_masked(dm_unet* u, const float* x, const int64_t* time, cons
  *                                 c[4]=exp(0.5*posterior_log_variance_clipped[t])   c[5]= (t>0) ? 1 : 0
  *   DDIM step i (t, t_next):      c[0], c[1] as above  c[2]=sqrt(alpha_next)  c[3]=c  c[4]=sigma
  *                                 c[5]= (t_next<0) ? 0 : 1   (0: img = x_start, :686-689)
+ *   DPM-Solver++ step i (t, t_next) on the DDIM time grid (arXiv 2211.01095, Algorithm 2; not in the reference), with
+ *   alpha = sqrt(alphas_cumprod), sigma = sqrt(1 - alphas_cumprod), lambda = log(alpha / sigma), h = lambda_next - lambda_t,
+ *   every term in float64 and rounded to fp32 once:
+ *                                 c[0], c[1], c[6], c[7] as for DDIM  c[2]=sigma_next/sigma_t  c[3]=-alpha_next*expm1(-h)
+ *                                 c[4]=h/(2 h_last) at order 2 (0 at order 1, at the first and at the last step)
+ *                                 c[5]= (t_next<0) ? 0 : 1   (0: img = x_start, as DDIM)
+ *     x_next = c[2] x + c[3] (x0 + c[4] (x0 - x0_prev)),  x0 the clamped x_start of the step; no noise after x_T
  * coefs_host has n_steps rows of DM_COEFS floats.
  *
  *   x_T        (B,C,H,W) start noise (draw #0 of the reference)
@@ -143,6 +150,7 @@ int dm_unet_forward_masked(dm_unet* u, const float* x, const int64_t* time, cons
 #define DM_COEFS 8
 #define DM_SAMPLER_DDPM 0
 #define DM_SAMPLER_DDIM 1
+#define DM_SAMPLER_DPMPP 2
 /* what the U-Net output means (`objective` of DenoisingDiffusion.__init__, DD/denoising_diffusion.py:443; branches of
  * model_predictions :607-624).  pred_v reads c[6]=sqrt_alphas_cumprod[t], c[7]=sqrt_one_minus_alphas_cumprod[t]
  * (predict_start_from_v :588-592) from the step table. */
@@ -296,6 +304,10 @@ int dm_op_attention(const float* x, const float* norm_g, const float* mem_kv, co
  * floats (host); x_start (optional) receives the clamped x_0 estimate of the step (pred_x_start of model_predictions) */
 int dm_op_sampler_update(int kind, int objective, const float* x, const float* eps, const float* noise,
                          const float* c_host, float* out, float* x_start, int64_t n, void* stream);
+/* one DPM-Solver++ update (DM_SAMPLER_DPMPP) on (n) elements: coef_host is one row of DM_COEFS floats (host), x0_hist
+ * (device) holds the previous step's clamped x_0 estimate and receives this step's; with c[4] == 0 it is not read */
+int dm_op_dpmpp_update(int objective, const float* x, const float* model_out, float* x0_hist, const float* coef_host,
+                       float* out, int64_t n, void* stream);
 /* The guidance combine of dm_sample_args.cfg on its own: out[b] = guided(cond[b], null_out[b]) for B rows of
  * per_sample floats (DD/classifier_free_guidance.py:355-369 with project :49-60).  Device pointers, out distinct from
  * both inputs. */
