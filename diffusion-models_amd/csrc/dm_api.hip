@@ -283,6 +283,7 @@ struct Stage {
 };
 
 struct TrainState;  // dm_train.inc
+struct UnetGraph;   // unet_graph.inc
 
 }  // namespace dm
 
@@ -307,6 +308,7 @@ struct dm_unet {
     ResBlock mid1, mid2, final_res;
     AttnLayer mid_attn;
     CrossLayer cross_down, cross_mid, cross_up;
+    std::vector<dm::UnetGraph> graphs;  // the order the layers run in, per form of the network (unet_graph.inc)
     float *freqs = nullptr, *tw1 = nullptr, *tb1 = nullptr, *tw2 = nullptr, *tb2 = nullptr;
     float *ss_w = nullptr, *ss_b = nullptr;
     int ss_total = 0;
@@ -438,6 +440,8 @@ static void expect_cross(dm_unet* u, const std::string& p, int dim) {
 }
 
 static std::string idx(const std::string& a, int i) { return a + "." + std::to_string(i); }
+
+#include "unet_graph.inc"
 
 // ---- weight upload ----------------------------------------------------------------------
 // Pack an OIHW weight into the layout of every kernel family the layer is eligible for (conv_family.inc) and upload those
@@ -752,6 +756,7 @@ static int build_all(dm_unet* u) {
             build_cross(u, u->cross_up, "cross_attn_up", mid))
             return 1;
     }
+    if (!u->own.refreshing) build_unet_graphs(u);
     return 0;
 }
 
@@ -1007,6 +1012,25 @@ static int run_resnet(Ctx& c, const ResBlock& R, const float* x0, const float* x
     return 0;
 }
 
+// The front of an unfused attention layer, shared by the inference form (run_attn) and the tape form (t_attn), into the
+// caller's buffers: pre-norm -> to_qkv, then the attention core.  Two calls, because a LinearAttention caller allocates the
+// core's buffers between them.  ctxws / kst: LinearAttention only; kst (the key statistics) only for the tape.
+static int attn_qkv(Ctx& c, const AttnLayer& At, const float* x, int H, int W, float* xn, float* qkv) {
+    const int n = H * W;
+    if (!c.dry() && launch_norm_act(x, 1, 0, nullptr, At.norm_g, nullptr, 0, n, nullptr, xn, (int64_t)c.B * n, At.dim, EPI_NORM, c.s))
+        return 1;
+    return run_conv(c, At.qkv, xn, nullptr, H, W, qkv, 0, nullptr, nullptr, nullptr);
+}
+static int attn_core(Ctx& c, const AttnLayer& At, const float* qkv, int n, float* o, float* ctxws, float* kst) {
+    if (c.dry()) return 0;
+    const int heads = At.heads, dh = c.u->dh, hidden = heads * dh;
+    if (!At.full) return launch_linear_attention_core(qkv, At.mem_kv, ctxws, o, c.B, n, heads, dh, c.s, kst);
+    const float* mk = At.mem_kv;
+    const float* mv = At.mem_kv + (size_t)heads * 4 * dh;
+    return launch_attention_core(qkv, 3 * hidden, qkv + hidden, qkv + 2 * hidden, 3 * hidden, mk, mv, 4, o, hidden, c.B, n, n,
+                                 heads, dh, 1.0f / sqrtf((float)dh), c.s);
+}
+
 // attn(x) + x  (LinearAttention DD/denoising_diffusion.py:173-193, Attention :215-229)
 static int run_attn(Ctx& c, const AttnLayer& At, const float* x, int H, int W, float** out, bool add_x = true) {
     const int res_flag = add_x ? EPI_RESIDUAL : 0;
@@ -1032,22 +1056,13 @@ static int run_attn(Ctx& c, const AttnLayer& At, const float* x, int H, int W, f
     float* qkv = c.A->alloc(rows * 3 * hidden);
     float* o = c.A->alloc(rows * hidden);
     float* y = c.A->alloc(rows * At.dim);
-    if (!c.dry() && launch_norm_act(x, 1, 0, nullptr, At.norm_g, nullptr, 0, n, nullptr, xn, (int64_t)rows, At.dim,
-                                    EPI_NORM, c.s))
-        return 1;
-    if (run_conv(c, At.qkv, xn, nullptr, H, W, qkv, 0, nullptr, nullptr, nullptr)) return 1;
+    if (attn_qkv(c, At, x, H, W, xn, qkv)) return 1;
     if (At.full) {
-        if (!c.dry()) {
-            const float* mk = At.mem_kv;
-            const float* mv = At.mem_kv + (size_t)heads * 4 * u->dh;
-            if (launch_attention_core(qkv, 3 * hidden, qkv + hidden, qkv + 2 * hidden, 3 * hidden, mk, mv, 4, o,
-                                      hidden, c.B, n, n, heads, u->dh, 1.0f / sqrtf((float)u->dh), c.s))
-                return 1;
-        }
+        if (attn_core(c, At, qkv, n, o, nullptr, nullptr)) return 1;
         if (run_conv(c, At.out, o, nullptr, H, W, y, res_flag, nullptr, nullptr, xres)) return 1;
     } else {
         float* ctxws = c.A->alloc((size_t)c.B * heads * u->dh * u->dh);
-        if (!c.dry() && launch_linear_attention_core(qkv, At.mem_kv, ctxws, o, c.B, n, heads, u->dh, c.s)) return 1;
+        if (attn_core(c, At, qkv, n, o, ctxws, nullptr)) return 1;
         if (run_conv(c, At.out, o, nullptr, H, W, y, EPI_NORM | res_flag, At.out_g, nullptr, xres)) return 1;
         c.A->release(ctxws);
     }
@@ -1062,6 +1077,18 @@ static int run_attn(Ctx& c, const AttnLayer& At, const float* x, int H, int W, f
 static bool cross1_off() {
     static const bool off = env_flag("DM_NO_CROSS1");
     return off;
+}
+
+// The front of the general CrossAttention path (m context tokens), shared by run_cross and the tape form t_cross, into the
+// caller's buffers: to_q over the pixels, to_k / to_v over the context rows, the attention core
+static int cross_front(Ctx& c, const CrossLayer& Cr, const float* x, int H, int W, const float* ctx, int m, float* q, float* k,
+                       float* v, float* o) {
+    const int n = H * W, dh = c.u->dh, inner = 4 * dh, E = c.u->cfg.text_emb_dim;
+    if (run_conv(c, Cr.q, x, nullptr, H, W, q, 0, nullptr, nullptr, nullptr)) return 1;
+    if (c.dry()) return 0;
+    if (launch_linear_rows(ctx, E, Cr.wk, nullptr, k, inner, c.B * m, E, inner, 0, 0, c.s)) return 1;
+    if (launch_linear_rows(ctx, E, Cr.wv, nullptr, v, inner, c.B * m, E, inner, 0, 0, c.s)) return 1;
+    return launch_attention_core(q, inner, k, v, inner, nullptr, nullptr, 0, o, inner, c.B, n, m, 4, dh, 1.0f / sqrtf((float)dh), c.s);
 }
 
 // CrossAttention.forward (DD/denoising_diffusion_text_conditional.py:54-78); the result REPLACES x (:173-177)
@@ -1104,14 +1131,7 @@ static int run_cross(Ctx& c, const CrossLayer& Cr, const float* x, int H, int W,
     float* v = c.A->alloc((size_t)c.B * m * inner);
     float* o = c.A->alloc(rows * inner);
     float* y = c.A->alloc(rows * dim);
-    if (run_conv(c, Cr.q, x, nullptr, H, W, q, 0, nullptr, nullptr, nullptr)) return 1;
-    if (!c.dry()) {
-        if (launch_linear_rows(ctx, E, Cr.wk, nullptr, k, inner, c.B * m, E, inner, 0, 0, c.s)) return 1;
-        if (launch_linear_rows(ctx, E, Cr.wv, nullptr, v, inner, c.B * m, E, inner, 0, 0, c.s)) return 1;
-        if (launch_attention_core(q, inner, k, v, inner, nullptr, nullptr, 0, o, inner, c.B, n, m, 4, u->dh,
-                                  1.0f / sqrtf((float)u->dh), c.s))
-            return 1;
-    }
+    if (cross_front(c, Cr, x, H, W, ctx, m, q, k, v, o)) return 1;
     if (run_conv(c, Cr.out, o, nullptr, H, W, y, EPI_NORM, Cr.g, nullptr, nullptr)) return 1;
     if (keep_null_rows(y)) return 1;
     c.A->release(q);
@@ -1139,7 +1159,7 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
     const bool text_concat = cfg.text_mode == DM_TEXT_CONCAT && ctx != nullptr;
     const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && ctx != nullptr;
     // one context token: the three CrossAttention layers ignore their image input (run_cross), which makes everything
-    // between the last skip connection and cross_attn_up dead code (DM_NO_CROSS1 computes it anyway)
+    // between the last skip connection and the last of them dead code (DM_NO_CROSS1 computes it anyway)
     // (not with a text mask: the null rows need the bottleneck)
     const bool dead_bottleneck = text_cross && ctx_tokens == 1 && !cross1_off() && !tmask;
     // the time embedding is one row when the whole batch shares t (samplers), else one row per sample
@@ -1193,7 +1213,6 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
     c.ss = A.dry ? reinterpret_cast<const float*>(16) : ss;  // non-null marker in dry mode
     c.ss_stride = Bt == 1 ? 0 : u->ss_total;
 
-    const int n_st = cfg.n_stages;
     float* x = A.alloc((size_t)B * H * W * u->init_dim);
     if (run_conv(c, u->init_conv, x_nchw, nullptr, H, W, x, 0, nullptr, nullptr, nullptr, /*in_nchw=*/true)) return 1;
     if (cat) A.release(cat);
@@ -1202,74 +1221,37 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
     A.release(e0);
     A.release(e1);
     A.release(temb);
-    const float* r = x;  // Unet.forward's `r = x.clone()`: read again by final_res_block, never released before
-    auto rel = [&](const float* t) {
-        if (t != r) A.release(t);
-    };
-    std::vector<const float*> skips;
-    int h = H, w = W;
-    float* cur = x;
-    for (int i = 0; i < n_st; ++i) {
-        Stage& S = u->downs[i];
-        float *a, *b2, *at;
-        if (run_resnet(c, S.b1, cur, nullptr, h, w, &a)) return 1;
-        rel(cur);
-        skips.push_back(a);
-        if (run_resnet(c, S.b2, a, nullptr, h, w, &b2)) return 1;
-        if (run_attn(c, S.attn, b2, h, w, &at)) return 1;
-        rel(b2);
-        skips.push_back(at);
-        int ho = (i < n_st - 1) ? h / 2 : h, wo = (i < n_st - 1) ? w / 2 : w;
-        if (i == n_st - 1 && dead_bottleneck) {  // its only consumer is a CrossAttention that ignores x (see below)
-            cur = nullptr;
+    // the layers between init_conv and final_conv, in the order of the node list (unet_graph.inc).  A tensor is released
+    // behind the node that reads it last -- Unet.forward's `r = x.clone()` (value 0) behind the last node.
+    const UnetGraph& G = u->graphs[dead_bottleneck ? GRAPH_CROSS1 : text_cross ? GRAPH_CROSS : GRAPH_PLAIN];
+    std::vector<float*> val(G.n_values(), nullptr);
+    val[0] = x;
+    for (size_t k = 0; k < G.nodes.size(); ++k) {
+        const UnetNode& N = G.nodes[k];
+        const float* in0 = N.in0 >= 0 ? val[N.in0] : nullptr;
+        const float* in1 = N.in1 >= 0 ? val[N.in1] : nullptr;
+        const int hi = H >> N.lin, wi = W >> N.lin, ho = H >> N.lout, wo = W >> N.lout;
+        switch (N.kind) {
+        case NODE_RESNET:
+            if (run_resnet(c, N.res(), in0, in1, hi, wi, &val[N.out])) return 1;
+            break;
+        case NODE_ATTN:
+            if (run_attn(c, N.attn(), in0, hi, wi, &val[N.out])) return 1;
+            break;
+        case NODE_CROSS:
+            if (run_cross(c, N.cross(), in0, hi, wi, ctx, ctx_tokens, &val[N.out], tmask)) return 1;
+            break;
+        case NODE_CONV:
+            val[N.out] = A.alloc((size_t)B * ho * wo * N.conv().Cout);
+            // an Upsample conv sees the (virtually) upsampled tensor: it is given the output size
+            if (run_conv(c, N.conv(), in0, nullptr, std::max(hi, ho), std::max(wi, wo), val[N.out], 0, nullptr, nullptr, nullptr)) return 1;
             break;
         }
-        float* d = A.alloc((size_t)B * ho * wo * S.resample.Cout);
-        if (run_conv(c, S.resample, at, nullptr, h, w, d, 0, nullptr, nullptr, nullptr)) return 1;
-        cur = d; h = ho; w = wo;
+        for (int v : {N.in0, N.in1})
+            if (v >= 0 && G.last_use[v] == (int)k) A.release(val[v]);
     }
-    float* t0;
-    if (dead_bottleneck) {
-        // CrossAttention REPLACES x (:173-177, :187-191, :199-203), and with one context token its output does not depend
-        // on x at all (run_cross): cross_attn_down discards the last down conv, cross_attn discards mid_block1,
-        // cross_attn_up discards mid_attn and mid_block2.  None of that work can reach the output, so the up path starts
-        // from cross_attn_up(ctx); the skip connections carry the image signal, exactly as in the reference.
-        if (run_cross(c, u->cross_up, nullptr, h, w, ctx, ctx_tokens, &t0)) return 1;
-        cur = t0;
-    } else {
-        if (text_cross) { if (run_cross(c, u->cross_down, cur, h, w, ctx, ctx_tokens, &t0, tmask)) return 1; rel(cur); cur = t0; }
-        if (run_resnet(c, u->mid1, cur, nullptr, h, w, &t0)) return 1; rel(cur); cur = t0;
-        if (text_cross) { if (run_cross(c, u->cross_mid, cur, h, w, ctx, ctx_tokens, &t0, tmask)) return 1; rel(cur); cur = t0; }
-        if (run_attn(c, u->mid_attn, cur, h, w, &t0)) return 1; rel(cur); cur = t0;
-        if (run_resnet(c, u->mid2, cur, nullptr, h, w, &t0)) return 1; rel(cur); cur = t0;
-        if (text_cross) { if (run_cross(c, u->cross_up, cur, h, w, ctx, ctx_tokens, &t0, tmask)) return 1; rel(cur); cur = t0; }
-    }
-    for (int j = 0; j < n_st; ++j) {
-        Stage& S = u->ups[j];
-        float *a, *b2, *at;
-        const float* sk = skips.back(); skips.pop_back();
-        if (run_resnet(c, S.b1, cur, sk, h, w, &a)) return 1;
-        rel(cur);
-        rel(sk);
-        sk = skips.back(); skips.pop_back();
-        if (run_resnet(c, S.b2, a, sk, h, w, &b2)) return 1;
-        rel(a);
-        rel(sk);
-        if (run_attn(c, S.attn, b2, h, w, &at)) return 1;
-        rel(b2);
-        bool last = j == n_st - 1;
-        int ho = last ? h : h * 2, wo = last ? w : w * 2;
-        float* d = A.alloc((size_t)B * ho * wo * S.resample.Cout);
-        // the conv sees the (virtually) upsampled tensor
-        if (run_conv(c, S.resample, at, nullptr, ho, wo, d, 0, nullptr, nullptr, nullptr)) return 1;
-        rel(at);
-        cur = d; h = ho; w = wo;
-    }
-    float* fr;
-    if (run_resnet(c, u->final_res, cur, r, h, w, &fr)) return 1;
-    rel(cur);
-    A.release(r);
-    if (run_conv(c, u->final_conv, fr, nullptr, h, w, out_nchw, 0, nullptr, nullptr, nullptr, false, /*out_nchw=*/true))
+    float* fr = val[G.out()];
+    if (run_conv(c, u->final_conv, fr, nullptr, H, W, out_nchw, 0, nullptr, nullptr, nullptr, false, /*out_nchw=*/true))
         return 1;
     A.release(fr);
     A.release(ss);

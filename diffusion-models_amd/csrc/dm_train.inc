@@ -275,15 +275,14 @@ struct AttnTape {
     const float* x = nullptr;
     float *xn = nullptr, *qkv = nullptr, *ctx = nullptr, *kst = nullptr, *o = nullptr, *y0 = nullptr, *y = nullptr;
 };
-struct StageTape {
-    ResTape r1, r2;
-    AttnTape at;
-    float* rs_out = nullptr;
-    int h = 0, w = 0;
-};
 struct CrossTape {
     const float* x = nullptr;
     float *q = nullptr, *k = nullptr, *v = nullptr, *o = nullptr, *y0 = nullptr, *y = nullptr;
+};
+struct NodeTape {  // what one node of the graph keeps: the member of its kind (a resample convolution keeps only its output)
+    ResTape res;
+    AttnTape attn;
+    CrossTape cross;
 };
 struct Tape {
     float *e0 = nullptr, *h1pre = nullptr, *h1 = nullptr, *temb = nullptr, *ss = nullptr;
@@ -295,12 +294,9 @@ struct Tape {
     const float* ctx = nullptr;
     int ctx_tokens = 0;
     const int32_t* mask = nullptr;  // per-image caption dropout: rows with mask 0 took the text_emb = None path
-    CrossTape cdown, cmid, cup;
-    float* x0 = nullptr;
-    std::vector<StageTape> downs, ups;
-    ResTape mid1, mid2, fin;
-    AttnTape mid_attn;
-    int hm = 0, wm = 0;
+    const UnetGraph* graph = nullptr;  // the node list the forward pass ran (unet_graph.inc)
+    std::vector<NodeTape> nodes;       // one entry per node
+    std::vector<float*> val;           // the tensor of every value id; val[0] is init_conv's output
 };
 
 // DM_TRAIN_NO_LANDING_FUSE: every K-split convolution of the training step lands its partial tiles in a pass of its own
@@ -407,25 +403,15 @@ static int t_attn(TCtx& t, const AttnLayer& At, const float* x, int H, int W, At
     at.o = t.A->alloc(rows * hidden);
     at.y = t.A->alloc(rows * At.dim);
     Ctx c = t.conv();
-    if (!t.dry() && launch_norm_act(x, 1, 0, nullptr, At.norm_g, nullptr, 0, n, nullptr, at.xn, (int64_t)rows, At.dim,
-                                    EPI_NORM, t.s))
-        return 1;
-    if (run_conv(c, At.qkv, at.xn, nullptr, H, W, at.qkv, 0, nullptr, nullptr, nullptr)) return 1;
+    if (attn_qkv(c, At, x, H, W, at.xn, at.qkv)) return 1;
     if (At.full) {
-        if (!t.dry()) {
-            const float* mk = At.mem_kv;
-            const float* mv = At.mem_kv + (size_t)heads * 4 * u->dh;
-            if (launch_attention_core(at.qkv, 3 * hidden, at.qkv + hidden, at.qkv + 2 * hidden, 3 * hidden, mk, mv, 4, at.o,
-                                      hidden, t.B, n, n, heads, u->dh, 1.0f / sqrtf((float)u->dh), t.s))
-                return 1;
-        }
+        if (attn_core(c, At, at.qkv, n, at.o, nullptr, nullptr)) return 1;
         return run_conv(c, At.out, at.o, nullptr, H, W, at.y, EPI_RESIDUAL, nullptr, nullptr, x);
     }
     at.ctx = t.A->alloc((size_t)t.B * heads * u->dh * u->dh);
     at.kst = t.A->alloc((size_t)t.B * heads * 2 * u->dh);  // the key statistics the backward pass starts from
     at.y0 = t.A->alloc(rows * At.dim);
-    if (!t.dry() && launch_linear_attention_core(at.qkv, At.mem_kv, at.ctx, at.o, t.B, n, heads, u->dh, t.s, at.kst))
-        return 1;
+    if (attn_core(c, At, at.qkv, n, at.o, at.ctx, at.kst)) return 1;
     if (run_conv(c, At.out, at.o, nullptr, H, W, at.y0, 0, nullptr, nullptr, nullptr)) return 1;
     if (t.dry()) return 0;
     return launch_norm_act(at.y0, 1, 0, nullptr, At.out_g, nullptr, 0, n, x, at.y, (int64_t)rows, At.dim,
@@ -442,8 +428,7 @@ static int conv_dgrad(TCtx& t, const ConvLayer& L, const float* dy, int Hin, int
 // mask 0 (text_emb is None, :173/:183/:194), so those rows of the result are x -- the select of dm_unet_forward_masked
 static int t_cross(TCtx& t, const CrossLayer& Cr, const float* x, int H, int W, const float* ctx, int m, CrossTape& ct,
                    const int32_t* mask) {
-    dm_unet* u = t.u;
-    const int n = H * W, inner = 4 * u->dh, dim = Cr.out.Cout, E = u->cfg.text_emb_dim;
+    const int n = H * W, inner = 4 * t.u->dh, dim = Cr.out.Cout;
     const size_t rows = (size_t)t.B * n;
     ct.x = x;
     ct.q = t.A->alloc(rows * inner);
@@ -453,14 +438,7 @@ static int t_cross(TCtx& t, const CrossLayer& Cr, const float* x, int H, int W, 
     ct.y0 = t.A->alloc(rows * dim);
     ct.y = t.A->alloc(rows * dim);
     Ctx c = t.conv();
-    if (run_conv(c, Cr.q, x, nullptr, H, W, ct.q, 0, nullptr, nullptr, nullptr)) return 1;
-    if (!t.dry()) {
-        if (launch_linear_rows(ctx, E, Cr.wk, nullptr, ct.k, inner, t.B * m, E, inner, 0, 0, t.s)) return 1;
-        if (launch_linear_rows(ctx, E, Cr.wv, nullptr, ct.v, inner, t.B * m, E, inner, 0, 0, t.s)) return 1;
-        if (launch_attention_core(ct.q, inner, ct.k, ct.v, inner, nullptr, nullptr, 0, ct.o, inner, t.B, n, m, 4, u->dh,
-                                  1.0f / sqrtf((float)u->dh), t.s))
-            return 1;
-    }
+    if (cross_front(c, Cr, x, H, W, ctx, m, ct.q, ct.k, ct.v, ct.o)) return 1;
     if (run_conv(c, Cr.out, ct.o, nullptr, H, W, ct.y0, 0, nullptr, nullptr, nullptr)) return 1;
     if (t.dry()) return 0;
     if (launch_norm_act(ct.y0, 1, 0, nullptr, Cr.g, nullptr, 0, n, nullptr, ct.y, (int64_t)rows, dim, EPI_NORM, t.s)) return 1;
@@ -511,7 +489,7 @@ static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const i
                               int W, hipStream_t s, Tape& tp, const float* ctx = nullptr, int ctx_tokens = 0,
                               const int32_t* mask = nullptr, const float* tf_dev = nullptr) {
     const dm_unet_cfg& cfg = u->cfg;
-    const int td = u->time_dim, n_st = cfg.n_stages;
+    const int td = u->time_dim;
     const bool text_concat = cfg.text_mode == DM_TEXT_CONCAT && ctx != nullptr;
     const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && ctx != nullptr;
     tp.ctx = ctx;
@@ -565,63 +543,39 @@ static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const i
     t.ss = A.dry ? reinterpret_cast<const float*>(16) : tp.ss;
     t.ss_stride = u->ss_total;
     Ctx c = t.conv();
-    tp.x0 = A.alloc((size_t)B * H * W * u->init_dim);
-    if (run_conv(c, u->init_conv, x_nchw, nullptr, H, W, tp.x0, 0, nullptr, nullptr, nullptr, /*in_nchw=*/true)) return 1;
-    tp.downs.assign(n_st, StageTape{});
-    tp.ups.assign(n_st, StageTape{});
-    std::vector<const float*> skips;
-    const float* cur = tp.x0;
-    int h = H, w = W;
-    for (int i = 0; i < n_st; ++i) {
-        Stage& S = u->downs[i];
-        StageTape& st = tp.downs[i];
-        st.h = h; st.w = w;
-        if (t_resnet(t, S.b1, cur, nullptr, h, w, st.r1)) return 1;
-        skips.push_back(st.r1.out);
-        if (t_resnet(t, S.b2, st.r1.out, nullptr, h, w, st.r2)) return 1;
-        if (t_attn(t, S.attn, st.r2.out, h, w, st.at)) return 1;
-        skips.push_back(st.at.y);
-        const int ho = i < n_st - 1 ? h / 2 : h, wo = i < n_st - 1 ? w / 2 : w;
-        st.rs_out = A.alloc((size_t)B * ho * wo * S.resample.Cout);
-        if (run_conv(c, S.resample, st.at.y, nullptr, h, w, st.rs_out, 0, nullptr, nullptr, nullptr)) return 1;
-        cur = st.rs_out; h = ho; w = wo;
+    const UnetGraph& G = u->graphs[text_cross ? GRAPH_CROSS : GRAPH_PLAIN];
+    tp.graph = &G;
+    tp.nodes.assign(G.nodes.size(), NodeTape{});
+    tp.val.assign(G.n_values(), nullptr);
+    tp.val[0] = A.alloc((size_t)B * H * W * u->init_dim);
+    if (run_conv(c, u->init_conv, x_nchw, nullptr, H, W, tp.val[0], 0, nullptr, nullptr, nullptr, /*in_nchw=*/true)) return 1;
+    // the node list of the inference walk (unet_graph.inc), with everything kept: nothing is released
+    for (size_t k = 0; k < G.nodes.size(); ++k) {
+        const UnetNode& N = G.nodes[k];
+        NodeTape& nt = tp.nodes[k];
+        const float* in0 = tp.val[N.in0];
+        const float* in1 = N.in1 >= 0 ? tp.val[N.in1] : nullptr;
+        const int hi = H >> N.lin, wi = W >> N.lin, ho = H >> N.lout, wo = W >> N.lout;
+        switch (N.kind) {
+        case NODE_RESNET:
+            if (t_resnet(t, N.res(), in0, in1, hi, wi, nt.res)) return 1;
+            tp.val[N.out] = nt.res.out;
+            break;
+        case NODE_ATTN:
+            if (t_attn(t, N.attn(), in0, hi, wi, nt.attn)) return 1;
+            tp.val[N.out] = nt.attn.y;
+            break;
+        case NODE_CROSS:  // the text hooks around the bottleneck (DD/denoising_diffusion_text_conditional.py:173-203)
+            if (t_cross(t, N.cross(), in0, hi, wi, ctx, ctx_tokens, nt.cross, mask)) return 1;
+            tp.val[N.out] = nt.cross.y;
+            break;
+        case NODE_CONV:
+            tp.val[N.out] = A.alloc((size_t)B * ho * wo * N.conv().Cout);
+            if (run_conv(c, N.conv(), in0, nullptr, std::max(hi, ho), std::max(wi, wo), tp.val[N.out], 0, nullptr, nullptr, nullptr)) return 1;
+            break;
+        }
     }
-    tp.hm = h; tp.wm = w;
-    // text hooks around the bottleneck (DD/denoising_diffusion_text_conditional.py:173-203): each CrossAttention REPLACES x
-    if (text_cross) {
-        if (t_cross(t, u->cross_down, cur, h, w, ctx, ctx_tokens, tp.cdown, mask)) return 1;
-        cur = tp.cdown.y;
-    }
-    if (t_resnet(t, u->mid1, cur, nullptr, h, w, tp.mid1)) return 1;
-    cur = tp.mid1.out;
-    if (text_cross) {
-        if (t_cross(t, u->cross_mid, cur, h, w, ctx, ctx_tokens, tp.cmid, mask)) return 1;
-        cur = tp.cmid.y;
-    }
-    if (t_attn(t, u->mid_attn, cur, h, w, tp.mid_attn)) return 1;
-    if (t_resnet(t, u->mid2, tp.mid_attn.y, nullptr, h, w, tp.mid2)) return 1;
-    cur = tp.mid2.out;
-    if (text_cross) {
-        if (t_cross(t, u->cross_up, cur, h, w, ctx, ctx_tokens, tp.cup, mask)) return 1;
-        cur = tp.cup.y;
-    }
-    for (int j = 0; j < n_st; ++j) {
-        Stage& S = u->ups[j];
-        StageTape& st = tp.ups[j];
-        st.h = h; st.w = w;
-        const float* sk = skips.back(); skips.pop_back();
-        if (t_resnet(t, S.b1, cur, sk, h, w, st.r1)) return 1;
-        sk = skips.back(); skips.pop_back();
-        if (t_resnet(t, S.b2, st.r1.out, sk, h, w, st.r2)) return 1;
-        if (t_attn(t, S.attn, st.r2.out, h, w, st.at)) return 1;
-        const bool last = j == n_st - 1;
-        const int ho = last ? h : 2 * h, wo = last ? w : 2 * w;
-        st.rs_out = A.alloc((size_t)B * ho * wo * S.resample.Cout);
-        if (run_conv(c, S.resample, st.at.y, nullptr, ho, wo, st.rs_out, 0, nullptr, nullptr, nullptr)) return 1;
-        cur = st.rs_out; h = ho; w = wo;
-    }
-    if (t_resnet(t, u->final_res, cur, tp.x0, h, w, tp.fin)) return 1;
-    return run_conv(c, u->final_conv, tp.fin.out, nullptr, h, w, out_nchw, 0, nullptr, nullptr, nullptr, false, /*out_nchw=*/true);
+    return run_conv(c, u->final_conv, tp.val[G.out()], nullptr, H, W, out_nchw, 0, nullptr, nullptr, nullptr, false, /*out_nchw=*/true);
 }
 
 // ---- backward pieces ---------------------------------------------------------------------------------------------------
@@ -897,7 +851,8 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
                                     std::vector<WgradDesc>* wbatch, const std::function<int(int)>& phase_done,
                                     const InputGrad* ig) {
     const dm_unet_cfg& cfg = u->cfg;
-    const int td = u->time_dim, n_st = cfg.n_stages;
+    const int td = u->time_dim;
+    const UnetGraph& G = *tp.graph;
     TCtx t{u, &A, s, B, A.dry ? reinterpret_cast<const float*>(16) : tp.ss, u->ss_total};
     t.acc = accumulate;
     t.jobs = jobs;
@@ -909,7 +864,7 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
     t.cjobs = &cjobs;
     float* dss = A.alloc((size_t)B * u->ss_total);
     // final_conv (NCHW gradient, 64 -> out_dim)
-    int h = H, w = W;
+    const int h = H, w = W;
     float* dfr = A.alloc((size_t)B * h * w * u->init_dim);
     {
         const ConvLayer& L = u->final_conv;
@@ -925,79 +880,49 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
                     jb = t.defer();
                     jw = jb - 1;
                 }
-                if (launch_thin_out_bwd(tp.fin.out, dout_nchw, wraw, dfr, ws, t.grad(L.src.wname), t.grad(L.src.bname), B, h,
+                if (launch_thin_out_bwd(tp.val[G.out()], dout_nchw, wraw, dfr, ws, t.grad(L.src.wname), t.grad(L.src.bname), B, h,
                                         w, L.C0, L.Cout, t.acc, s, jw, jb))
                     return 1;
             }
         } else {
-            if (conv_wgrad(t, L, tp.fin.out, nullptr, dout_nchw, h, w, true)) return 1;
+            if (conv_wgrad(t, L, tp.val[G.out()], nullptr, dout_nchw, h, w, true)) return 1;
             if (!A.dry && ensure_packed(u, wraw, s)) return 1;
             if (!A.dry && launch_pointwise_small_dgrad(dout_nchw, wraw, dfr, (int64_t)B * h * w, L.C0, L.Cout, h * w, s))
                 return 1;
         }
     }
-    float *dcur = nullptr, *dr = nullptr;
-    if (t_resnet_bwd(t, u->final_res, tp.fin, dfr, h, w, dss, nullptr, &dcur, &dr)) return 1;
-    auto left_phase = [&](int phase) -> int { return t.phase_done ? t.phase_done(phase) : 0; };  // phases: grad_phase()
-    if (left_phase(0)) return 1;
-    // up path, last stage first; the skip gradients wait for the down path
-    std::vector<float*> dskips;  // in the order the forward popped them
-    std::vector<std::pair<float*, float*>> up_skips(n_st);
-    for (int j = n_st - 1; j >= 0; --j) {
-        Stage& S = u->ups[j];
-        StageTape& st = tp.ups[j];
-        float* dat = nullptr;
-        if (t_conv_bwd(t, S.resample, st.at.y, dcur, st.h, st.w, h, w, nullptr, &dat)) return 1;
-        h = st.h; w = st.w;
-        float *db2 = nullptr, *da = nullptr, *dsk2 = nullptr, *dsk1 = nullptr, *dprev = nullptr;
-        if (t_attn_bwd(t, S.attn, st.at, dat, h, w, &db2)) return 1;
-        if (t_resnet_bwd(t, S.b2, st.r2, db2, h, w, dss, nullptr, &da, &dsk2)) return 1;
-        if (t_resnet_bwd(t, S.b1, st.r1, da, h, w, dss, nullptr, &dprev, &dsk1)) return 1;
-        up_skips[j] = {dsk1, dsk2};
-        dcur = dprev;
-        if (left_phase(1 + (n_st - 1 - j))) return 1;
-    }
-    // middle (with the text hooks: a CrossAttention replaced x, so the gradient reaches its input only through to_q)
-    {
-        const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && tp.ctx != nullptr;
-        float *d2 = nullptr, *da = nullptr, *d1 = nullptr, *none = nullptr, *dx = nullptr;
-        if (text_cross) {
-            if (t_cross_bwd(t, u->cross_up, tp.cup, dcur, h, w, tp.ctx, tp.ctx_tokens, &dx, tp.mask)) return 1;
-            dcur = dx;
+    // The node list in reverse, with the gradient of every value.  A node finds in grad[in0] what a consumer that ran later in
+    // the forward pass has already left there (a skip connection's gradient from the up path, x0's from the last node) and
+    // adds it to its own; the kernels have no slot for such a gradient on a second input or in front of an attention layer.
+    std::vector<float*> grad(G.n_values(), nullptr);
+    grad[G.out()] = dfr;
+    for (int k = (int)G.nodes.size() - 1; k >= 0; --k) {
+        const UnetNode& N = G.nodes[k];
+        const NodeTape& nt = tp.nodes[k];
+        const int hi = H >> N.lin, wi = W >> N.lin, ho = H >> N.lout, wo = W >> N.lout;
+        float *d0 = nullptr, *d1 = nullptr;
+        switch (N.kind) {
+        case NODE_RESNET:
+            DM_REQUIRE(N.in1 < 0 || !grad[N.in1], "backward: a gradient is already waiting for a ResnetBlock's second input");
+            if (t_resnet_bwd(t, N.res(), nt.res, grad[N.out], hi, wi, dss, grad[N.in0], &d0, &d1)) return 1;
+            if (N.in1 >= 0) grad[N.in1] = d1;
+            break;
+        case NODE_ATTN:
+        case NODE_CROSS:  // a CrossAttention replaced x, so the gradient reaches its input only through to_q
+            DM_REQUIRE(!grad[N.in0], "backward: a gradient is already waiting for an attention layer's input");
+            if (N.kind == NODE_ATTN ? t_attn_bwd(t, N.attn(), nt.attn, grad[N.out], hi, wi, &d0)
+                                    : t_cross_bwd(t, N.cross(), nt.cross, grad[N.out], hi, wi, tp.ctx, tp.ctx_tokens, &d0, tp.mask))
+                return 1;
+            break;
+        case NODE_CONV:
+            if (t_conv_bwd(t, N.conv(), tp.val[N.in0], grad[N.out], hi, wi, ho, wo, grad[N.in0], &d0)) return 1;
+            break;
         }
-        if (t_resnet_bwd(t, u->mid2, tp.mid2, dcur, h, w, dss, nullptr, &d2, &none)) return 1;
-        if (t_attn_bwd(t, u->mid_attn, tp.mid_attn, d2, h, w, &da)) return 1;
-        if (text_cross) {
-            if (t_cross_bwd(t, u->cross_mid, tp.cmid, da, h, w, tp.ctx, tp.ctx_tokens, &dx, tp.mask)) return 1;
-            da = dx;
-        }
-        if (t_resnet_bwd(t, u->mid1, tp.mid1, da, h, w, dss, nullptr, &d1, &none)) return 1;
-        dcur = d1;
-        if (text_cross) {
-            if (t_cross_bwd(t, u->cross_down, tp.cdown, dcur, h, w, tp.ctx, tp.ctx_tokens, &dx, tp.mask)) return 1;
-            dcur = dx;
-        }
-        if (left_phase(n_st + 1)) return 1;
+        grad[N.in0] = d0;
+        // the walk leaves a phase (grad_phase(): a stage): bucketed flush point
+        if ((k == 0 || G.nodes[k - 1].phase != N.phase) && t.phase_done && t.phase_done(N.phase)) return 1;
     }
-    // down path.  Forward pushed (r1.out, at.y) per stage; up stage j popped at.y of down stage n-1-j first (its block1),
-    // then r1.out (its block2).
-    for (int i = n_st - 1; i >= 0; --i) {
-        Stage& S = u->downs[i];
-        StageTape& st = tp.downs[i];
-        const bool last = i == n_st - 1;
-        float* d_at_skip = up_skips[n_st - 1 - i].first;
-        float* d_r1_skip = up_skips[n_st - 1 - i].second;
-        float* dat = nullptr;
-        if (t_conv_bwd(t, S.resample, st.at.y, dcur, st.h, st.w, last ? st.h : st.h / 2, last ? st.w : st.w / 2, d_at_skip, &dat))
-            return 1;
-        h = st.h; w = st.w;
-        float *db2 = nullptr, *da = nullptr, *dprev = nullptr, *none = nullptr;
-        if (t_attn_bwd(t, S.attn, st.at, dat, h, w, &db2)) return 1;
-        if (t_resnet_bwd(t, S.b2, st.r2, db2, h, w, dss, d_r1_skip, &da, &none)) return 1;
-        if (t_resnet_bwd(t, S.b1, st.r1, da, h, w, dss, i == 0 ? dr : nullptr, &dprev, &none)) return 1;
-        dcur = dprev;
-        if (left_phase(n_st + 2 + (n_st - 1 - i))) return 1;
-    }
+    float* dcur = grad[0];
     // init_conv: weight / bias gradient; its input is data, so the input gradient runs only for a call that asks for it
     if (conv_wgrad(t, u->init_conv, x_nchw, nullptr, dcur, H, W, true)) return 1;
     if (ig && !A.dry) {
@@ -1497,19 +1422,6 @@ static int run_train(dm_unet* u, const TrainRun& r, const std::function<int(Aren
 }  // namespace dm
 
 extern "C" {
-
-// Phase of the backward pass in which a parameter's stage is left (the order unet_train_backward_impl walks the network):
-// 0 final_res_block / final_conv, 1 .. n the up stages (last first), n + 1 the middle, n + 2 .. 2n + 1 the down stages
-// (last first), 2n + 2 what only the end of the pass completes (init_conv, the time / text MLPs)
-static int grad_phase(const dm_unet* u, const std::string& name) {
-    const int n = u->cfg.n_stages;
-    auto starts = [&](const char* p) { return name.compare(0, std::strlen(p), p) == 0; };
-    if (starts("final_res_block.") || starts("final_conv.")) return 0;
-    if (starts("ups.")) return 1 + (n - 1 - std::atoi(name.c_str() + 4));
-    if (starts("mid_") || starts("cross_attn")) return n + 1;
-    if (starts("downs.")) return n + 2 + (n - 1 - std::atoi(name.c_str() + 6));
-    return 2 * n + 2;
-}
 
 // ft: the handle is armed for float-time training (dm_unet_train_enable_ft) instead of the integer-time p_losses path
 static int train_enable_impl(dm_unet* u, bool ft) {
