@@ -65,6 +65,7 @@ EXPORTS = (
     "dm_sample_wo", "dm_unet_loss_backward_wo", "dm_op_wo_step", "dm_op_wo_loss",
     "dm_sample_classifier_guided", "dm_op_cg_mean", "dm_op_cg_finish",
     "dm_op_dpmpp_update",
+    "dm_unet_cond_forward", "dm_unet_cond_backward", "dm_op_deferred_reduce",
 )
 
 
@@ -227,6 +228,25 @@ class WoTrainArgs(C.Structure):
 OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}
 
 
+COND_WALK_INFER, COND_WALK_TRAIN = 0, 1
+COND_TIME_INT, COND_TIME_FLOAT, COND_TIME_INT_SHARED, COND_TIME_FLOAT_SHARED = 0, 1, 2, 3
+REDUCE_NORM_BWD, REDUCE_COLSUM = 0, 1
+
+
+class CondBufs(C.Structure):
+    """dm_cond_bufs (include/dm_hip.h): the intermediates of the conditioning head, device pointers or None."""
+    _fields_ = [(n, C.c_void_p) for n in ("e0", "h1pre", "h1", "temb", "te0pre", "te0", "cat", "tfinal", "tact", "ss")]
+
+
+class ReduceLayer(C.Structure):
+    """dm_reduce_layer (include/dm_hip.h): one layer of dm_op_deferred_reduce."""
+    _fields_ = [("kind", C.c_int32), ("C", C.c_int32), ("silu", C.c_int32), ("ss_stride", C.c_int32),
+                ("dss_stride", C.c_int32), ("reserved", C.c_int32),
+                ("rows", C.c_int64), ("row_stride", C.c_int64), ("col_stride", C.c_int64),
+                ("dy", C.c_void_p), ("u", C.c_void_p), ("g", C.c_void_p), ("ss", C.c_void_p), ("x", C.c_void_p),
+                ("du", C.c_void_p), ("dg", C.c_void_p), ("dbias", C.c_void_p), ("dss", C.c_void_p), ("out", C.c_void_p)]
+
+
 class ProfileRow(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("total_flops", C.c_double), ("total_bytes", C.c_double)]
@@ -380,6 +400,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_wo_loss.argtypes = [fp, fp, fp, fp, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, fp, C.POINTER(C.c_float),
                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, i64, vp]
     lib.dm_profile_read.argtypes = [C.POINTER(ProfileRow), i32, C.POINTER(i32)]
+    lib.dm_unet_cond_forward.argtypes = [vp, i32, i32, vp, fp, vp, C.POINTER(CondBufs), i32, vp]
+    lib.dm_unet_cond_backward.argtypes = [vp, C.POINTER(CondBufs), fp, vp, fp, fp, i32, i32, vp]
+    lib.dm_op_deferred_reduce.argtypes = [C.POINTER(ReduceLayer), i32, i32, i32, i32, vp]
 
 
 class TrainArgs(C.Structure):

@@ -1142,36 +1142,31 @@ static int run_cross(Ctx& c, const CrossLayer& Cr, const float* x, int H, int W,
     return 0;
 }
 
-// Unet.forward (DD/denoising_diffusion.py:349-390; text hooks DD/denoising_diffusion_text_conditional.py:131-214)
-static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const int64_t* t_dev,
-                             const int64_t* step_times, const SamplerState* step_dev, const float* ctx, int ctx_tokens,
-                             float* out_nchw, int B, int H, int W, hipStream_t s, const int32_t* tmask = nullptr,
-                             const float* tf = nullptr, int tf_stride = 0) {
-    // tf: a REAL-valued time instead of t_dev / step_times (ElucidatedDiffusion's c_noise(sigma)): one value per image, or
-    // with step_dev the value tf[step * tf_stride] of the EDM step table for the whole batch
-    // tmask: per-image text mask (device int32, B entries, or nullptr = every image as `ctx` says).  Image b is
-    // conditioned iff tmask[b] != 0; the others take the model's null path (text_emb = None).  Every row of ctx is
-    // read, the masked-out ones included, and their values do not reach the output.
+// The conditioning head of the inference walk: time -> (sinusoid -> time_mlp) -> [text concat] -> the [Bt][ss_total] scale /
+// shift rows of every ResnetBlock (DD/denoising_diffusion.py:349-361; DD/denoising_diffusion_text_conditional.py:146-152).
+// What it allocates stays allocated until cond_release.  unet_forward_impl and dm_unet_cond_forward run this one function.
+struct CondHead {
+    int Rt = 0, Bt = 0, fdim = 0;  // rows of the sinusoid / time_mlp, rows of ss, width of e0
+    float *e0 = nullptr, *e1 = nullptr, *temb = nullptr, *ss = nullptr;
+    float *cat = nullptr, *tf0 = nullptr, *t2 = nullptr;  // text concat only
+    const float* tfinal = nullptr;                        // what the ResnetBlock.mlp layers see: temb or t2
+};
+static int cond_forward(dm_unet* u, Arena& A, const int64_t* t_dev, const int64_t* step_times, const SamplerState* step_dev,
+                        const float* ctx, int ctx_tokens, int B, hipStream_t s, const int32_t* tmask, const float* tf,
+                        int tf_stride, CondHead& h) {
     const dm_unet_cfg& cfg = u->cfg;
-    DM_REQUIRE(!tmask || (ctx && cfg.text_mode != DM_TEXT_NONE), "a text mask needs a text-conditional U-Net and a context");
-    Ctx c{u, &A, s, B, nullptr, 0};
     const int td = u->time_dim;
     const bool text_concat = cfg.text_mode == DM_TEXT_CONCAT && ctx != nullptr;
-    const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && ctx != nullptr;
-    // one context token: the three CrossAttention layers ignore their image input (run_cross), which makes everything
-    // between the last skip connection and the last of them dead code (DM_NO_CROSS1 computes it anyway)
-    // (not with a text mask: the null rows need the bottleneck)
-    const bool dead_bottleneck = text_cross && ctx_tokens == 1 && !cross1_off() && !tmask;
     // the time embedding is one row when the whole batch shares t (samplers), else one row per sample
     const bool shared_t = step_times || (tf && step_dev);
-    const int Bt = (shared_t && !text_concat) ? 1 : B;
-    const int Rt = shared_t ? 1 : B;  // rows of the sinusoid / time_mlp
+    const int Bt = h.Bt = (shared_t && !text_concat) ? 1 : B;
+    const int Rt = h.Rt = shared_t ? 1 : B;  // rows of the sinusoid / time_mlp
     const int lsd = cfg.learned_sinusoidal_dim;  // > 0: cat(t, sin(t w 2 pi), cos(t w 2 pi)) of width lsd + 1 (:96-101)
-    const int fdim = lsd > 0 ? lsd + 1 : cfg.dim;
-    float* e0 = A.alloc((size_t)Rt * fdim);
-    float* e1 = A.alloc((size_t)Rt * td);
-    float* temb = A.alloc((size_t)B * td);
-    float* ss = A.alloc((size_t)Bt * u->ss_total);
+    const int fdim = h.fdim = lsd > 0 ? lsd + 1 : cfg.dim;
+    float* e0 = h.e0 = A.alloc((size_t)Rt * fdim);
+    float* e1 = h.e1 = A.alloc((size_t)Rt * td);
+    float* temb = h.temb = A.alloc((size_t)B * td);
+    float* ss = h.ss = A.alloc((size_t)Bt * u->ss_total);
     if (!A.dry) {
         if (tf) {
             if (launch_sinusoid_ft(tf, tf_stride, step_dev, u->freqs, e0, Rt, (lsd > 0 ? lsd : cfg.dim) / 2, s, lsd > 0)) return 1;
@@ -1181,14 +1176,13 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
         if (launch_linear_rows(e0, fdim, u->tw1, u->tb1, e1, td, Rt, fdim, td, 0, 2, s)) return 1;
         if (launch_linear_rows(e1, td, u->tw2, u->tb2, temb, td, Rt, td, td, 0, 0, s)) return 1;
     }
-    const float* tfinal = temb;
-    float *cat = nullptr, *tf0 = nullptr;
+    h.tfinal = temb;
     if (text_concat) {
         // t = text_concat_proj(cat(t, text_proj(text_emb)))  (:146-152); ctx is (B, 1, E) or (B, E)
         DM_REQUIRE(ctx_tokens == 1, "text concat conditioning takes one pooled embedding per sample");
-        cat = A.alloc((size_t)B * 2 * td);
-        tf0 = A.alloc((size_t)B * td);
-        float* t2 = A.alloc((size_t)B * td);
+        float* cat = h.cat = A.alloc((size_t)B * 2 * td);
+        float* tf0 = h.tf0 = A.alloc((size_t)B * td);
+        float* t2 = h.t2 = A.alloc((size_t)B * td);
         if (!A.dry) {
             // left half: the time embedding of every row (one broadcast launch when the batch shares t)
             if (Rt == 1) {
@@ -1204,23 +1198,51 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
             // null rows: the raw time embedding (:146-152 skipped when text_emb is None)
             if (tmask && launch_select_rows(t2, temb, Rt == 1 ? 0 : td, tmask, B, td, s)) return 1;
         }
-        tfinal = t2;
+        h.tfinal = t2;
     }
     if (!A.dry) {
         // every ResnetBlock.mlp (SiLU -> Linear) in one launch
-        if (launch_linear_rows(tfinal, td, u->ss_w, u->ss_b, ss, u->ss_total, Bt, td, u->ss_total, 1, 0, s)) return 1;
+        if (launch_linear_rows(h.tfinal, td, u->ss_w, u->ss_b, ss, u->ss_total, Bt, td, u->ss_total, 1, 0, s)) return 1;
     }
+    return 0;
+}
+// everything of the head but ss, which the ResnetBlocks read until the walk ends
+static void cond_release(Arena& A, const CondHead& h) {
+    if (h.cat) A.release(h.cat);
+    if (h.tf0) A.release(h.tf0);
+    if (h.t2) A.release(h.t2);
+    A.release(h.e0);
+    A.release(h.e1);
+    A.release(h.temb);
+}
+
+// Unet.forward (DD/denoising_diffusion.py:349-390; text hooks DD/denoising_diffusion_text_conditional.py:131-214)
+static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const int64_t* t_dev,
+                             const int64_t* step_times, const SamplerState* step_dev, const float* ctx, int ctx_tokens,
+                             float* out_nchw, int B, int H, int W, hipStream_t s, const int32_t* tmask = nullptr,
+                             const float* tf = nullptr, int tf_stride = 0) {
+    // tf: a REAL-valued time instead of t_dev / step_times (ElucidatedDiffusion's c_noise(sigma)): one value per image, or
+    // with step_dev the value tf[step * tf_stride] of the EDM step table for the whole batch
+    // tmask: per-image text mask (device int32, B entries, or nullptr = every image as `ctx` says).  Image b is
+    // conditioned iff tmask[b] != 0; the others take the model's null path (text_emb = None).  Every row of ctx is
+    // read, the masked-out ones included, and their values do not reach the output.
+    const dm_unet_cfg& cfg = u->cfg;
+    DM_REQUIRE(!tmask || (ctx && cfg.text_mode != DM_TEXT_NONE), "a text mask needs a text-conditional U-Net and a context");
+    Ctx c{u, &A, s, B, nullptr, 0};
+    const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && ctx != nullptr;
+    // one context token: the three CrossAttention layers ignore their image input (run_cross), which makes everything
+    // between the last skip connection and the last of them dead code (DM_NO_CROSS1 computes it anyway)
+    // (not with a text mask: the null rows need the bottleneck)
+    const bool dead_bottleneck = text_cross && ctx_tokens == 1 && !cross1_off() && !tmask;
+    CondHead h;
+    if (cond_forward(u, A, t_dev, step_times, step_dev, ctx, ctx_tokens, B, s, tmask, tf, tf_stride, h)) return 1;
+    float* ss = h.ss;
     c.ss = A.dry ? reinterpret_cast<const float*>(16) : ss;  // non-null marker in dry mode
-    c.ss_stride = Bt == 1 ? 0 : u->ss_total;
+    c.ss_stride = h.Bt == 1 ? 0 : u->ss_total;
 
     float* x = A.alloc((size_t)B * H * W * u->init_dim);
     if (run_conv(c, u->init_conv, x_nchw, nullptr, H, W, x, 0, nullptr, nullptr, nullptr, /*in_nchw=*/true)) return 1;
-    if (cat) A.release(cat);
-    if (tf0) A.release(tf0);
-    if (tfinal != temb) A.release(tfinal);
-    A.release(e0);
-    A.release(e1);
-    A.release(temb);
+    cond_release(A, h);
     // the layers between init_conv and final_conv, in the order of the node list (unet_graph.inc).  A tensor is released
     // behind the node that reads it last -- Unet.forward's `r = x.clone()` (value 0) behind the last node.
     const UnetGraph& G = u->graphs[dead_bottleneck ? GRAPH_CROSS1 : text_cross ? GRAPH_CROSS : GRAPH_PLAIN];

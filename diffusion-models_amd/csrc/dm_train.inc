@@ -484,18 +484,14 @@ static int t_cross_bwd(TCtx& t, const CrossLayer& Cr, const CrossTape& ct, const
     return 0;
 }
 
-// Unet.forward (DD/denoising_diffusion.py:349-390) with per-sample times and everything kept for the backward pass
-static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const int64_t* t_dev, float* out_nchw, int B, int H,
-                              int W, hipStream_t s, Tape& tp, const float* ctx = nullptr, int ctx_tokens = 0,
-                              const int32_t* mask = nullptr, const float* tf_dev = nullptr) {
+// The conditioning head of the training forward: as cond_forward (dm_api.hip), one row per image, with every activation a
+// pass of its own so that the backward head (cond_backward) finds its inputs in the tape.  unet_train_forward and
+// dm_unet_cond_forward run this one function.
+static int cond_train_forward(dm_unet* u, Arena& A, const int64_t* t_dev, const float* tf_dev, const float* ctx, int ctx_tokens,
+                              const int32_t* mask, int B, hipStream_t s, Tape& tp) {
     const dm_unet_cfg& cfg = u->cfg;
     const int td = u->time_dim;
     const bool text_concat = cfg.text_mode == DM_TEXT_CONCAT && ctx != nullptr;
-    const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && ctx != nullptr;
-    tp.ctx = ctx;
-    tp.ctx_tokens = ctx_tokens;
-    tp.mask = ctx ? mask : nullptr;
-    TCtx t{u, &A, s, B, nullptr, 0};
     // tf_dev: a float time per image (ElucidatedDiffusion's c_noise(sigma)) through cat(t, sin(t w 2 pi), cos(t w 2 pi))
     const int fdim = tp.e0_dim = tf_dev ? cfg.learned_sinusoidal_dim + 1 : cfg.dim;
     tp.e0 = A.alloc((size_t)B * fdim);
@@ -540,6 +536,20 @@ static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const i
     if (!A.dry && (launch_act_fwd(tp.tfinal, tact, (int64_t)B * td, 1, s) ||
                    launch_linear_rows(tact, td, u->ss_w, u->ss_b, tp.ss, u->ss_total, B, td, u->ss_total, 0, 0, s)))
         return 1;
+    return 0;
+}
+
+// Unet.forward (DD/denoising_diffusion.py:349-390) with per-sample times and everything kept for the backward pass
+static int unet_train_forward(dm_unet* u, Arena& A, const float* x_nchw, const int64_t* t_dev, float* out_nchw, int B, int H,
+                              int W, hipStream_t s, Tape& tp, const float* ctx = nullptr, int ctx_tokens = 0,
+                              const int32_t* mask = nullptr, const float* tf_dev = nullptr) {
+    const dm_unet_cfg& cfg = u->cfg;
+    const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && ctx != nullptr;
+    tp.ctx = ctx;
+    tp.ctx_tokens = ctx_tokens;
+    tp.mask = ctx ? mask : nullptr;
+    TCtx t{u, &A, s, B, nullptr, 0};
+    if (cond_train_forward(u, A, t_dev, tf_dev, ctx, ctx_tokens, mask, B, s, tp)) return 1;
     t.ss = A.dry ? reinterpret_cast<const float*>(16) : tp.ss;
     t.ss_stride = u->ss_total;
     Ctx c = t.conv();
@@ -840,18 +850,128 @@ static int upload_table(const std::vector<E>& host, std::vector<E>& cached, E*& 
     return 0;
 }
 
+// The per-image / per-channel reductions behind every norm_act_bwd_kernel of a backward pass (dss is complete after them)
+// and every bias / mem_kv column sum of it, as collected in TCtx::rjobs / TCtx::cjobs: two launches each.  The tables are
+// given their block prefixes (the column sums: partial-pass jobs first) and uploaded here.
+static int flush_deferred_reductions(TrainState& T, std::vector<RowgradJob>& rjobs, std::vector<ColsumJob>& cjobs, hipStream_t s) {
+    if (!rjobs.empty()) {
+        int ib = 0, fb = 0;
+        rowgrad_jobs_prefix(rjobs, &ib, &fb);
+        if (upload_table(rjobs, T.rjobs_host, T.rjobs_dev, T.rjobs_cap, s)) return 1;
+        if (launch_rowgrad_jobs(T.rjobs_dev, (int)rjobs.size(), ib, fb, s)) return 1;
+    }
+    if (!cjobs.empty()) {
+        int pb = 0, fb = 0;
+        colsum_jobs_prefix(cjobs, &pb, &fb);
+        int n_part = 0;
+        for (const ColsumJob& j : cjobs) n_part += j.nb > 0;
+        if (upload_table(cjobs, T.cjobs_host, T.cjobs_dev, T.cjobs_cap, s)) return 1;
+        if (launch_colsum_jobs(T.cjobs_dev, (int)cjobs.size(), n_part, pb, fb, s)) return 1;
+    }
+    return 0;
+}
+
 // Where a call that differentiates through the U-Net's inputs wants them (float-time handles): dx (B, C, H, W), dt (B)
 struct InputGrad {
     float* dx;
     float* dt;
 };
 
+// The backward of the conditioning head (cond_train_forward) from dss (B, ss_total), the gradient of the scale / shift rows:
+// ResnetBlock.mlp (SiLU -> Linear), all 19 of them through the concatenated matrix, then (text_concat_proj, text_proj,)
+// time_mlp, and on a float-time handle the embedding's weights and ig->dt.  unet_train_backward_impl and
+// dm_unet_cond_backward run this one function.
+static int cond_backward(TCtx& t, const Tape& tp, const float* dss, const InputGrad* ig) {
+    dm_unet* u = t.u;
+    Arena& A = *t.A;
+    hipStream_t s = t.s;
+    const int B = t.B;
+    const dm_unet_cfg& cfg = u->cfg;
+    const int td = u->time_dim;
+    const bool text_concat = cfg.text_mode == DM_TEXT_CONCAT && tp.ctx != nullptr;
+    float* dtf0 = A.alloc((size_t)B * td);
+    float* dtf = A.alloc((size_t)B * td);
+    float* dcat = text_concat ? A.alloc((size_t)B * 2 * td) : nullptr;
+    float* dte0 = text_concat ? A.alloc((size_t)B * td) : nullptr;
+    float* dte0pre = text_concat ? A.alloc((size_t)B * td) : nullptr;
+    float* dtc_kept = text_concat && tp.mask ? A.alloc((size_t)B * td) : nullptr;
+    float* dh1 = A.alloc((size_t)B * td);
+    float* dh1pre = A.alloc((size_t)B * td);
+    float* cw = A.alloc(colsum_ws_floats(B, std::max(u->ss_total, 2 * td)));
+    float* dgw = A.alloc(linear_dgrad_ws_floats(B, td, u->ss_total));
+    const bool ft = u->train->ft;  // the embedding has a parameter: the pass goes on through time_mlp.1 into e0
+    float* de0 = ft ? A.alloc((size_t)B * tp.e0_dim) : nullptr;
+    if (A.dry) return 0;
+    {   // every ResnetBlock.mlp weight / bias gradient in one launch (row table built once)
+        TrainState& T = *u->train;
+        if (!T.mlp_rows) {
+            std::vector<float*> rows(2 * (size_t)u->ss_total);
+            for (auto& pr : u->resnets) {
+                const ResBlock& R = *pr.second;
+                float* gw = t.grad(pr.first + ".mlp.1.weight");
+                float* gb = t.grad(pr.first + ".mlp.1.bias");
+                for (int o = 0; o < 2 * R.dout; ++o) {
+                    rows[R.ss_off + o] = gw + (size_t)o * td;
+                    rows[u->ss_total + R.ss_off + o] = gb + o;
+                }
+            }
+            DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.mlp_rows), rows.size() * sizeof(float*)));
+            DM_CHECK_HIP(hipMemcpy(T.mlp_rows, rows.data(), rows.size() * sizeof(float*), hipMemcpyHostToDevice));
+        }
+        if (launch_mlp_rows_wgrad(dss, u->ss_total, tp.tfinal, td, T.mlp_rows, T.mlp_rows + u->ss_total, B, td, u->ss_total,
+                                  t.acc, s, tp.tact))
+            return 1;
+    }
+    if (launch_linear_dgrad(dss, u->ss_total, u->ss_w, dtf0, td, B, td, u->ss_total, dgw, s)) return 1;  // d silu(tfinal)
+    if (launch_act_bwd(dtf0, tp.tfinal, dtf, (int64_t)B * td, 1, s)) return 1;
+    const float* dtemb = dtf;  // gradient of time_mlp's output, rows ldt floats apart
+    int ldt = td;
+    if (text_concat) {
+        const int E = cfg.text_emb_dim;
+        const float* dtc = dtf;  // what text_concat_proj's output receives
+        if (tp.mask) {
+            // per-image caption dropout: rows with mask 0 took the raw time embedding, so their gradient bypasses the text
+            // branch -- the branch receives exact zeros for them, and below they take dtf itself as time_mlp's gradient
+            if (launch_route_rows(dtc_kept, td, dtf, td, nullptr, 0, tp.mask, B, td, s)) return 1;
+            dtc = dtc_kept;
+        }
+        if (launch_linear_wgrad(dtc, td, tp.cat, 2 * td, t.grad("text_concat_proj.weight"), B, 2 * td, td, 0, t.acc, s)) return 1;
+        if (launch_colsum(dtc, B, td, td, 1, cw, t.grad("text_concat_proj.bias"), t.acc, s)) return 1;
+        if (launch_linear_dgrad(dtc, td, u->tc_w, dcat, 2 * td, B, 2 * td, td, nullptr, s)) return 1;
+        if (tp.mask && launch_route_rows(dcat, 2 * td, dcat, 2 * td, dtf, td, tp.mask, B, td, s)) return 1;  // the left half
+        const float* dte = dcat + td;  // right half: text_proj's output
+        if (launch_linear_wgrad(dte, 2 * td, tp.te0, td, t.grad("text_proj.2.weight"), B, td, td, 0, t.acc, s)) return 1;
+        if (launch_colsum(dte, B, td, 2 * td, 1, cw, t.grad("text_proj.2.bias"), t.acc, s)) return 1;
+        if (launch_linear_dgrad(dte, 2 * td, u->tp_w2, dte0, td, B, td, td, nullptr, s)) return 1;
+        if (launch_act_bwd(dte0, tp.te0pre, dte0pre, (int64_t)B * td, 2, s)) return 1;
+        if (launch_linear_wgrad(dte0pre, td, tp.ctx, E, t.grad("text_proj.0.weight"), B, E, td, 0, t.acc, s)) return 1;
+        if (launch_colsum(dte0pre, B, td, td, 1, cw, t.grad("text_proj.0.bias"), t.acc, s)) return 1;
+        dtemb = dcat;  // left half
+        ldt = 2 * td;
+    }
+    if (launch_linear_wgrad(dtemb, ldt, tp.h1, td, t.grad("time_mlp.3.weight"), B, td, td, 0, t.acc, s)) return 1;
+    if (launch_colsum(dtemb, B, td, ldt, 1, cw, t.grad("time_mlp.3.bias"), t.acc, s)) return 1;
+    if (launch_linear_dgrad(dtemb, ldt, u->tw2, dh1, td, B, td, td, nullptr, s)) return 1;
+    if (launch_act_bwd(dh1, tp.h1pre, dh1pre, (int64_t)B * td, 2, s)) return 1;
+    const int fdim = tp.e0_dim;
+    if (launch_linear_wgrad(dh1pre, td, tp.e0, fdim, t.grad("time_mlp.1.weight"), B, fdim, td, 0, t.acc, s)) return 1;
+    if (launch_colsum(dh1pre, B, td, td, 1, cw, t.grad("time_mlp.1.bias"), t.acc, s)) return 1;
+    if (ft) {
+        // fdim = learned_sinusoidal_dim + 1 is odd: launch_linear_dgrad takes its scalar kernel (rows_gemm_nn_ok wants I % 64 == 0)
+        if (launch_linear_dgrad(dh1pre, td, u->tw1, de0, fdim, B, fdim, td, nullptr, s)) return 1;
+        if (launch_sinusoid_ft_bwd(de0, tp.e0, t.grad("time_mlp.0.weights"), B, cfg.learned_sinusoidal_dim / 2,
+                                   !u->train->freqs_frozen, t.acc, s))
+            return 1;
+        if (ig && launch_sinusoid_ft_tgrad(de0, tp.e0, u->freqs, ig->dt, B, cfg.learned_sinusoidal_dim / 2, s)) return 1;
+    }
+    return 0;
+}
+
 static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, const float* dout_nchw, int B, int H, int W,
                                     hipStream_t s, Tape& tp, int accumulate, std::vector<WgradJob>* jobs,
                                     std::vector<WgradDesc>* wbatch, const std::function<int(int)>& phase_done,
                                     const InputGrad* ig) {
     const dm_unet_cfg& cfg = u->cfg;
-    const int td = u->time_dim;
     const UnetGraph& G = *tp.graph;
     TCtx t{u, &A, s, B, A.dry ? reinterpret_cast<const float*>(16) : tp.ss, u->ss_total};
     t.acc = accumulate;
@@ -929,103 +1049,9 @@ static int unet_train_backward_impl(dm_unet* u, Arena& A, const float* x_nchw, c
         DM_REQUIRE(u->train->init_w_raw != nullptr, "the input gradient needs a handle armed by dm_unet_train_enable_ft");
         if (launch_conv7_dgrad(dcur, u->train->init_w_raw, ig->dx, B, H, W, u->init_dim, cfg.input_channels, s)) return 1;
     }
-    // ResnetBlock.mlp (SiLU -> Linear), all 19 of them through the concatenated matrix, then (text_concat_proj, text_proj,)
-    // time_mlp
-    const bool text_concat = cfg.text_mode == DM_TEXT_CONCAT && tp.ctx != nullptr;
-    float* dtf0 = A.alloc((size_t)B * td);
-    float* dtf = A.alloc((size_t)B * td);
-    float* dcat = text_concat ? A.alloc((size_t)B * 2 * td) : nullptr;
-    float* dte0 = text_concat ? A.alloc((size_t)B * td) : nullptr;
-    float* dte0pre = text_concat ? A.alloc((size_t)B * td) : nullptr;
-    float* dtc_kept = text_concat && tp.mask ? A.alloc((size_t)B * td) : nullptr;
-    float* dh1 = A.alloc((size_t)B * td);
-    float* dh1pre = A.alloc((size_t)B * td);
-    float* cw = A.alloc(colsum_ws_floats(B, std::max(u->ss_total, 2 * td)));
-    float* dgw = A.alloc(linear_dgrad_ws_floats(B, td, u->ss_total));
-    const bool ft = u->train->ft;  // the embedding has a parameter: the pass goes on through time_mlp.1 into e0
-    float* de0 = ft ? A.alloc((size_t)B * tp.e0_dim) : nullptr;
-    if (A.dry) return 0;
-    {   // the per-image / per-channel reductions behind every norm_act_bwd_kernel (dss is complete after them) and every
-        // bias / mem_kv column sum of the pass: two launches each
-        TrainState& T = *u->train;
-        if (!rjobs.empty()) {
-            int ib = 0, fb = 0;
-            rowgrad_jobs_prefix(rjobs, &ib, &fb);
-            if (upload_table(rjobs, T.rjobs_host, T.rjobs_dev, T.rjobs_cap, s)) return 1;
-            if (launch_rowgrad_jobs(T.rjobs_dev, (int)rjobs.size(), ib, fb, s)) return 1;
-        }
-        if (!cjobs.empty()) {
-            int pb = 0, fb = 0;
-            colsum_jobs_prefix(cjobs, &pb, &fb);
-            int n_part = 0;
-            for (const ColsumJob& j : cjobs) n_part += j.nb > 0;
-            if (upload_table(cjobs, T.cjobs_host, T.cjobs_dev, T.cjobs_cap, s)) return 1;
-            if (launch_colsum_jobs(T.cjobs_dev, (int)cjobs.size(), n_part, pb, fb, s)) return 1;
-        }
-    }
-    {   // every ResnetBlock.mlp weight / bias gradient in one launch (row table built once)
-        TrainState& T = *u->train;
-        if (!T.mlp_rows) {
-            std::vector<float*> rows(2 * (size_t)u->ss_total);
-            for (auto& pr : u->resnets) {
-                const ResBlock& R = *pr.second;
-                float* gw = t.grad(pr.first + ".mlp.1.weight");
-                float* gb = t.grad(pr.first + ".mlp.1.bias");
-                for (int o = 0; o < 2 * R.dout; ++o) {
-                    rows[R.ss_off + o] = gw + (size_t)o * td;
-                    rows[u->ss_total + R.ss_off + o] = gb + o;
-                }
-            }
-            DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&T.mlp_rows), rows.size() * sizeof(float*)));
-            DM_CHECK_HIP(hipMemcpy(T.mlp_rows, rows.data(), rows.size() * sizeof(float*), hipMemcpyHostToDevice));
-        }
-        if (launch_mlp_rows_wgrad(dss, u->ss_total, tp.tfinal, td, T.mlp_rows, T.mlp_rows + u->ss_total, B, td, u->ss_total,
-                                  t.acc, s, tp.tact))
-            return 1;
-    }
-    if (launch_linear_dgrad(dss, u->ss_total, u->ss_w, dtf0, td, B, td, u->ss_total, dgw, s)) return 1;  // d silu(tfinal)
-    if (launch_act_bwd(dtf0, tp.tfinal, dtf, (int64_t)B * td, 1, s)) return 1;
-    const float* dtemb = dtf;  // gradient of time_mlp's output, rows ldt floats apart
-    int ldt = td;
-    if (text_concat) {
-        const int E = cfg.text_emb_dim;
-        const float* dtc = dtf;  // what text_concat_proj's output receives
-        if (tp.mask) {
-            // per-image caption dropout: rows with mask 0 took the raw time embedding, so their gradient bypasses the text
-            // branch -- the branch receives exact zeros for them, and below they take dtf itself as time_mlp's gradient
-            if (launch_route_rows(dtc_kept, td, dtf, td, nullptr, 0, tp.mask, B, td, s)) return 1;
-            dtc = dtc_kept;
-        }
-        if (launch_linear_wgrad(dtc, td, tp.cat, 2 * td, t.grad("text_concat_proj.weight"), B, 2 * td, td, 0, t.acc, s)) return 1;
-        if (launch_colsum(dtc, B, td, td, 1, cw, t.grad("text_concat_proj.bias"), t.acc, s)) return 1;
-        if (launch_linear_dgrad(dtc, td, u->tc_w, dcat, 2 * td, B, 2 * td, td, nullptr, s)) return 1;
-        if (tp.mask && launch_route_rows(dcat, 2 * td, dcat, 2 * td, dtf, td, tp.mask, B, td, s)) return 1;  // the left half
-        const float* dte = dcat + td;  // right half: text_proj's output
-        if (launch_linear_wgrad(dte, 2 * td, tp.te0, td, t.grad("text_proj.2.weight"), B, td, td, 0, t.acc, s)) return 1;
-        if (launch_colsum(dte, B, td, 2 * td, 1, cw, t.grad("text_proj.2.bias"), t.acc, s)) return 1;
-        if (launch_linear_dgrad(dte, 2 * td, u->tp_w2, dte0, td, B, td, td, nullptr, s)) return 1;
-        if (launch_act_bwd(dte0, tp.te0pre, dte0pre, (int64_t)B * td, 2, s)) return 1;
-        if (launch_linear_wgrad(dte0pre, td, tp.ctx, E, t.grad("text_proj.0.weight"), B, E, td, 0, t.acc, s)) return 1;
-        if (launch_colsum(dte0pre, B, td, td, 1, cw, t.grad("text_proj.0.bias"), t.acc, s)) return 1;
-        dtemb = dcat;  // left half
-        ldt = 2 * td;
-    }
-    if (launch_linear_wgrad(dtemb, ldt, tp.h1, td, t.grad("time_mlp.3.weight"), B, td, td, 0, t.acc, s)) return 1;
-    if (launch_colsum(dtemb, B, td, ldt, 1, cw, t.grad("time_mlp.3.bias"), t.acc, s)) return 1;
-    if (launch_linear_dgrad(dtemb, ldt, u->tw2, dh1, td, B, td, td, nullptr, s)) return 1;
-    if (launch_act_bwd(dh1, tp.h1pre, dh1pre, (int64_t)B * td, 2, s)) return 1;
-    const int fdim = tp.e0_dim;
-    if (launch_linear_wgrad(dh1pre, td, tp.e0, fdim, t.grad("time_mlp.1.weight"), B, fdim, td, 0, t.acc, s)) return 1;
-    if (launch_colsum(dh1pre, B, td, td, 1, cw, t.grad("time_mlp.1.bias"), t.acc, s)) return 1;
-    if (ft) {
-        // fdim = learned_sinusoidal_dim + 1 is odd: launch_linear_dgrad takes its scalar kernel (rows_gemm_nn_ok wants I % 64 == 0)
-        if (launch_linear_dgrad(dh1pre, td, u->tw1, de0, fdim, B, fdim, td, nullptr, s)) return 1;
-        if (launch_sinusoid_ft_bwd(de0, tp.e0, t.grad("time_mlp.0.weights"), B, cfg.learned_sinusoidal_dim / 2,
-                                   !u->train->freqs_frozen, t.acc, s))
-            return 1;
-        if (ig && launch_sinusoid_ft_tgrad(de0, tp.e0, u->freqs, ig->dt, B, cfg.learned_sinusoidal_dim / 2, s)) return 1;
-    }
-    return 0;
+    // dss is complete once the deferred reductions have run
+    if (!A.dry && flush_deferred_reductions(*u->train, rjobs, cjobs, s)) return 1;
+    return cond_backward(t, tp, dss, ig);
 }
 
 // The backward pass records the MFMA weight gradients instead of running them: they depend only on tensors that stay alive

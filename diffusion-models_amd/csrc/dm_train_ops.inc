@@ -2,6 +2,8 @@
 // parity tests can check each against the reference module's autograd at shapes the U-Net does not produce (odd sizes,
 // two-source inputs, upsampled sources, any channel count that is a multiple of 4).  Same plumbing as dm_ops.inc: weights
 // arrive as DEVICE pointers in the reference layout, are packed on the host per call, every call synchronises.
+// The conditioning head (dm_unet_cond_forward / dm_unet_cond_backward, on a real handle) and the deferred reduction tables
+// (dm_op_deferred_reduce) are not restated here: these entry points call the functions the walks call.
 // Textually included after dm_train.inc.
 namespace dm {
 
@@ -66,6 +68,20 @@ static int cross_op_layer(OpTrain& op, CrossLayer& Cr, const float* w_q, const f
 
 static bool cross_op_args_ok(int B, int C, int H, int W, int m, int E, int dim_head) {
     return B > 0 && C > 0 && H > 0 && W > 0 && m > 0 && E > 0 && (dim_head == 32 || dim_head == 64);
+}
+
+// what dm_unet_cond_forward / dm_unet_cond_backward ask of the handle and the conditioning arguments
+static int cond_args_ok(dm_unet* u, const float* ctx, const int32_t* text_mask, int B) {
+    DM_REQUIRE(u->finalized, "dm_unet_finalize has not been called");
+    DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
+    DM_REQUIRE(B > 0, "empty batch");
+    DM_REQUIRE(!ctx || u->cfg.text_mode != DM_TEXT_NONE, "the U-Net was built without text conditioning");
+    DM_REQUIRE(!text_mask || ctx, "a text mask needs a text-conditional U-Net and a pooled caption");
+    return 0;
+}
+static int copy_out(float* dst, const float* src, size_t n, hipStream_t s) {
+    if (dst && src) DM_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
 }
 
 }  // namespace dm
@@ -192,8 +208,10 @@ int dm_op_block_bwd(const float* x, int Cin, const float* weight, const float* b
 }
 
 /* nn.Linear backward (time_mlp :280-285, ResnetBlock.mlp :127-130 without the SiLU): dx = dy W, dW (+)= dy^T x,
- * db (+)= column sums of dy; x (R, I), weight (O, I), dy (R, O), all row-major device pointers.  Goes through the same
- * launchers as the training step (the MFMA GEMMs of small_gemm.hip where the shapes allow, else the VALU kernels). */
+ * db (+)= column sums of dy; x (R, I), weight (O, I), dy (R, O), all row-major device pointers.  Goes through the
+ * launchers of the training step (the MFMA GEMMs of small_gemm.hip where the shapes allow, else the VALU kernels) in
+ * their contiguous form only (ldx = I, ldy = O, one weight block, immediate column sum); the strided, row-pointer-table
+ * and shared forms the step uses are reached by dm_unet_cond_backward, its deferred reductions by dm_op_deferred_reduce. */
 int dm_op_linear_bwd(const float* x, const float* weight, const float* dy, float* dx, float* d_weight, float* d_bias, int R,
                      int I, int O, int accumulate, void* stream) {
     DM_REQUIRE(x && weight && dy && R > 0 && I > 0 && O > 0, "bad argument");
@@ -399,6 +417,158 @@ int dm_op_cross_attention_bwd(const float* x, const float* ctx, const float* w_q
                 op.out("c.to_out.1.g", d_out_g, s))
                 return 1;
             return 0;
+        });
+    });
+}
+
+/* The conditioning head on its own, on a finalized handle: the function the chosen walk itself runs (cond_forward of the
+ * inference walk, cond_train_forward of the training forward), in a NaN-filled workspace, then a copy of every
+ * intermediate the caller asked for. */
+int dm_unet_cond_forward(dm_unet* u, int walk, int time_kind, const void* time, const float* ctx, const int32_t* text_mask,
+                         const dm_cond_bufs* out, int B, void* stream) {
+    DM_REQUIRE(u && time && out, "null argument");
+    DM_REQUIRE(walk == DM_COND_WALK_INFER || walk == DM_COND_WALK_TRAIN, "walk: DM_COND_WALK_INFER or DM_COND_WALK_TRAIN");
+    DM_REQUIRE(time_kind >= DM_COND_TIME_INT && time_kind <= DM_COND_TIME_FLOAT_SHARED, "unknown time kind");
+    if (cond_args_ok(u, ctx, text_mask, B)) return 1;
+    const bool is_float = time_kind == DM_COND_TIME_FLOAT || time_kind == DM_COND_TIME_FLOAT_SHARED;
+    const bool shared = time_kind == DM_COND_TIME_INT_SHARED || time_kind == DM_COND_TIME_FLOAT_SHARED;
+    const int lsd = u->cfg.learned_sinusoidal_dim;
+    DM_REQUIRE(!is_float || lsd > 0, "a real-valued time needs a learned / random sinusoidal U-Net");
+    const bool train = walk == DM_COND_WALK_TRAIN;
+    DM_REQUIRE(!train || !shared, "the training forward has one time per image");
+    DM_REQUIRE(!train || is_float == (lsd > 0), "the training forward embeds an integer time with the fixed sinusoid and a "
+                                                "real-valued time with the learned / random one");
+    DM_REQUIRE(train || !(out->h1pre || out->te0pre || out->tact),
+               "h1pre, te0pre and tact exist in the training forward only: the inference walk fuses the activations");
+    DM_CHECK_HIP(hipSetDevice(u->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t* ti = is_float ? nullptr : static_cast<const int64_t*>(time);
+    const float* tf = is_float ? static_cast<const float*>(time) : nullptr;
+    const int td = u->time_dim, ctx_tokens = ctx ? 1 : 0;
+    const bool text_concat = u->cfg.text_mode == DM_TEXT_CONCAT && ctx != nullptr;
+    SamplerState* st_dev = nullptr;  // the shared time is entry `step` = 0 of a sampler's table
+    if (shared) {
+        const SamplerState st{};
+        DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&st_dev), sizeof(SamplerState)));
+        if (hipMemcpy(st_dev, &st, sizeof(st), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(st_dev);
+            set_error("hipMemcpy of the sampler state failed");
+            return 1;
+        }
+    }
+    const int rc = guarded([&]() -> int {
+        return run_op(s, [&](Arena& A) -> int {
+            if (train) {
+                Tape tp;
+                if (cond_train_forward(u, A, ti, tf, ctx, ctx_tokens, text_mask, B, s, tp)) return 1;
+                if (A.dry) return 0;
+                const size_t n = (size_t)B * td;
+                return copy_out(out->e0, tp.e0, (size_t)B * tp.e0_dim, s) || copy_out(out->h1pre, tp.h1pre, n, s) ||
+                       copy_out(out->h1, tp.h1, n, s) || copy_out(out->temb, tp.temb, n, s) ||
+                       copy_out(out->te0pre, tp.te0pre, n, s) || copy_out(out->te0, tp.te0, n, s) ||
+                       copy_out(out->cat, tp.cat, 2 * n, s) || copy_out(out->tfinal, tp.tfinal, n, s) ||
+                       copy_out(out->tact, tp.tact, n, s) || copy_out(out->ss, tp.ss, (size_t)B * u->ss_total, s);
+            }
+            CondHead h;
+            if (cond_forward(u, A, shared ? nullptr : ti, shared ? ti : nullptr, st_dev, ctx, ctx_tokens, B, s, text_mask, tf,
+                             shared ? 1 : 0, h))
+                return 1;
+            if (A.dry) return 0;
+            const size_t n = (size_t)B * td, nt = (size_t)h.Rt * td;
+            return copy_out(out->e0, h.e0, (size_t)h.Rt * h.fdim, s) || copy_out(out->h1, h.e1, nt, s) ||
+                   copy_out(out->temb, h.temb, nt, s) || copy_out(out->te0, h.tf0, n, s) || copy_out(out->cat, h.cat, 2 * n, s) ||
+                   copy_out(out->tfinal, h.tfinal, text_concat ? n : nt, s) ||
+                   copy_out(out->ss, h.ss, (size_t)h.Bt * u->ss_total, s);
+        });
+    });
+    if (st_dev) (void)hipFree(st_dev);
+    return rc;
+}
+
+/* The backward of the conditioning head on its own, on an armed handle: cond_backward, the function the backward walk ends
+ * with, on the caller's tape and dss, in a NaN-filled workspace. */
+int dm_unet_cond_backward(dm_unet* u, const dm_cond_bufs* tape, const float* ctx, const int32_t* text_mask, const float* dss,
+                          float* dt, int B, int accumulate, void* stream) {
+    DM_REQUIRE(u && tape && dss, "null argument");
+    if (cond_args_ok(u, ctx, text_mask, B)) return 1;
+    DM_REQUIRE(u->train, "dm_unet_train_enable / dm_unet_train_enable_ft has not been called");
+    const bool text_concat = u->cfg.text_mode == DM_TEXT_CONCAT && ctx != nullptr;
+    DM_REQUIRE(tape->e0 && tape->h1pre && tape->h1 && tape->tfinal && tape->tact, "the tape of a training forward: e0, h1pre, h1, "
+                                                                                "tfinal and tact");
+    DM_REQUIRE(!text_concat || (tape->te0pre && tape->te0 && tape->cat), "text concat: the tape holds te0pre, te0 and cat too");
+    DM_REQUIRE(!dt || u->train->ft, "dt needs a handle armed by dm_unet_train_enable_ft");
+    DM_CHECK_HIP(hipSetDevice(u->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&]() -> int {
+        if (u->order_after_previous(s)) return 1;
+        Tape tp;
+        tp.e0 = tape->e0; tp.h1pre = tape->h1pre; tp.h1 = tape->h1; tp.temb = tape->temb; tp.ss = tape->ss;
+        tp.tact = tape->tact; tp.te0pre = tape->te0pre; tp.te0 = tape->te0; tp.cat = tape->cat; tp.tfinal = tape->tfinal;
+        tp.e0_dim = u->train->ft ? u->cfg.learned_sinusoidal_dim + 1 : u->cfg.dim;
+        tp.ctx = ctx;
+        tp.ctx_tokens = ctx ? 1 : 0;
+        tp.mask = ctx ? text_mask : nullptr;
+        const InputGrad ig{nullptr, dt};
+        if (run_op(s, [&](Arena& A) -> int {
+                TCtx t{u, &A, s, B, nullptr, 0};
+                t.acc = accumulate;
+                return cond_backward(t, tp, dss, dt ? &ig : nullptr);
+            }))
+            return 1;
+        return u->mark_done(s);
+    });
+}
+
+/* The deferred reductions of a backward pass on their own: every layer is launched as the walk launches it -- with
+ * deferred != 0 into the two job tables (TCtx::rdefer / TCtx::cdefer), which flush_deferred_reductions then runs, the
+ * function the walk calls; with deferred == 0 through the immediate kernels.  Outputs are written by the kernels
+ * themselves into the caller's buffers; the workspaces live in a NaN-filled arena. */
+int dm_op_deferred_reduce(const dm_reduce_layer* layers, int n_layers, int B, int deferred, int accumulate, void* stream) {
+    DM_REQUIRE(layers && n_layers > 0 && B > 0, "bad argument");
+    for (int i = 0; i < n_layers; ++i) {
+        const dm_reduce_layer& L = layers[i];
+        if (L.kind == DM_REDUCE_NORM_BWD) {
+            DM_REQUIRE(L.dy && L.u && L.g && L.du && L.dg, "norm backward: dy, u, g, du and dg");
+            DM_REQUIRE(L.C % 4 == 0 && L.C >= 4 && L.C <= 1024, "norm backward: C must be a multiple of 4, at most 1024");
+            DM_REQUIRE(L.rows > 0, "norm backward: rows is the pixels per image");
+            DM_REQUIRE((L.ss == nullptr) == (L.dss == nullptr), "norm backward: ss and dss come together");
+            DM_REQUIRE(!L.ss || (L.ss_stride >= 2 * L.C && L.ss_stride % 4 == 0 && L.dss_stride >= 2 * L.C),
+                       "norm backward: a (scale | shift) row is 2 C floats, rows a multiple of 4 apart");
+        } else {
+            DM_REQUIRE(L.kind == DM_REDUCE_COLSUM, "unknown layer kind");
+            DM_REQUIRE(L.x && L.out && L.rows > 0 && L.C > 0 && L.row_stride > 0 && L.col_stride > 0, "column sum: x, out, sizes");
+        }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return guarded([&]() -> int {
+        OpTrain op(4, 32);
+        std::vector<RowgradJob> rjobs;
+        std::vector<ColsumJob> cjobs;
+        return run_op(s, [&](Arena& A) -> int {
+            TCtx t{&op.u, &A, s, B, nullptr, 0};
+            t.acc = accumulate;
+            rjobs.clear();
+            cjobs.clear();
+            if (deferred) {
+                t.rjobs = &rjobs;
+                t.cjobs = &cjobs;
+            }
+            for (int i = 0; i < n_layers; ++i) {
+                const dm_reduce_layer& L = layers[i];
+                if (L.kind == DM_REDUCE_NORM_BWD) {
+                    float* ws = A.alloc(norm_act_bwd_ws_floats(B, (int)L.rows, L.C));
+                    const int flags = EPI_NORM | (L.silu ? EPI_SILU : 0) | (L.ss ? EPI_SCALE_SHIFT : 0);
+                    if (!A.dry && launch_norm_act_bwd(L.dy, L.u, L.g, L.ss, L.ss_stride, (int)L.rows, L.du, ws, L.dg, L.dbias, L.dss,
+                                                      L.dss_stride, B, L.C, flags, t.acc, s, t.rdefer()))
+                        return 1;
+                } else {
+                    float* ws = A.alloc(colsum_ws_floats(L.rows, L.C));
+                    if (!A.dry && launch_colsum(L.x, L.rows, L.C, L.row_stride, L.col_stride, ws, L.out, t.acc, s, t.cdefer()))
+                        return 1;
+                }
+            }
+            if (A.dry || !deferred) return 0;
+            return flush_deferred_reductions(*op.u.train, rjobs, cjobs, s);
         });
     });
 }

@@ -579,6 +579,56 @@ int dm_op_cross_attention_bwd(const float* x, const float* ctx, const float* w_q
                               float* d_w_out, float* d_b_out, float* d_out_g, int B, int C, int H, int W, int m, int E,
                               int dim_head, void* stream);
 
+/* The conditioning head of the U-Net on its own: time [+ pooled caption] -> the (B, ss_total) scale / shift rows every
+ * ResnetBlock reads (Unet.forward, DD/denoising_diffusion.py:349-361; DD/denoising_diffusion_text_conditional.py:146-152),
+ * through the very functions the walks call, in a NaN-filled workspace.  Row-major device buffers, every one optional
+ * (NULL = not wanted); td = 4 * dim, fdim = dim or learned_sinusoidal_dim + 1:
+ *   e0 (R, fdim) the sinusoidal embedding; h1pre (R, td) time_mlp.1's output; h1 (R, td) = GELU(h1pre); temb (R, td) time_mlp's
+ *   output; te0pre (B, td) text_proj.0's output; te0 (B, td) = GELU(te0pre); cat (B, 2 td) = [temb | text_proj(caption)];
+ *   tfinal what the ResnetBlock.mlp layers see -- temb (R, td) or, with a caption, text_concat_proj(cat) (B, td), rows with
+ *   text_mask 0 holding temb; tact = SiLU(tfinal); ss (Bs, ss_total).
+ * R = Bs = B with one time per image.  A shared time (the samplers) gives R = 1, and Bs = 1 unless there is a caption.
+ * h1pre, te0pre and tact exist in the training forward only (the inference walk fuses the activations): they must be NULL
+ * for DM_COND_WALK_INFER. */
+typedef struct dm_cond_bufs {
+    float *e0, *h1pre, *h1, *temb, *te0pre, *te0, *cat, *tfinal, *tact, *ss;
+} dm_cond_bufs;
+#define DM_COND_WALK_INFER 0 /* the head of dm_unet_forward / the samplers */
+#define DM_COND_WALK_TRAIN 1 /* the head of the training forward: fills the tape dm_unet_cond_backward reads */
+#define DM_COND_TIME_INT 0          /* time: B device int64 */
+#define DM_COND_TIME_FLOAT 1        /* time: B device floats (needs learned_sinusoidal_dim > 0) */
+#define DM_COND_TIME_INT_SHARED 2   /* time: one device int64 for the whole batch (inference walk only) */
+#define DM_COND_TIME_FLOAT_SHARED 3 /* time: one device float for the whole batch (inference walk only) */
+/* ctx: (B, text_emb_dim) pooled caption or NULL; text_mask: B device int32 or NULL (needs ctx).  The training walk embeds an
+ * integer time with the fixed sinusoid and a float time with the learned / random one, as the training step does. */
+int dm_unet_cond_forward(dm_unet* u, int walk, int time_kind, const void* time, const float* ctx, const int32_t* text_mask,
+                         const dm_cond_bufs* out, int B, void* stream);
+/* Its backward on a handle armed by dm_unet_train_enable / dm_unet_train_enable_ft: `tape` holds the outputs of a
+ * DM_COND_WALK_TRAIN forward (e0, h1pre, h1, tfinal, tact; with a caption te0pre, te0, cat too), dss (B, ss_total) is the
+ * gradient of ss.  Parameter gradients go to the handle's slots ((+)= with accumulate; dm_unet_get_grad reads them):
+ * every *.mlp.1.{weight,bias}, time_mlp.{1,3}.*, text_proj.*, text_concat_proj.*, time_mlp.0.weights (float-time handles).
+ * dt (B, optional): the gradient of a float time. */
+int dm_unet_cond_backward(dm_unet* u, const dm_cond_bufs* tape, const float* ctx, const int32_t* text_mask, const float* dss,
+                          float* dt, int B, int accumulate, void* stream);
+
+/* The reductions a training backward pass defers to its end, on their own.  Every layer is launched as the pass launches
+ * it: with deferred != 0 it is recorded in the pass's two job tables, which are then run by the function the pass calls
+ * (four launches for all layers); with deferred == 0 each layer runs its immediate kernels.  One B for all layers.
+ *   DM_REDUCE_NORM_BWD: the backward of y = [SiLU](RMSNorm(u) * g [* (scale + 1) + shift]); dy, u, du (B * rows, C) token rows
+ *     (rows = pixels per image), g, dg, dbias (C) (dbias = column sums of du, optional), ss / dss (B rows, ss_stride /
+ *     dss_stride floats apart, (scale | shift) in the first 2 C columns; both or neither).  C % 4 == 0, C <= 1024.
+ *   DM_REDUCE_COLSUM: out[c] = sum_r x[r * row_stride + c * col_stride], c < C.
+ * dg, dbias and out are (+)= with accumulate; the kernels write into the caller's buffers directly. */
+#define DM_REDUCE_NORM_BWD 0
+#define DM_REDUCE_COLSUM 1
+typedef struct dm_reduce_layer {
+    int32_t kind, C, silu, ss_stride, dss_stride, reserved;
+    int64_t rows, row_stride, col_stride;
+    const float *dy, *u, *g, *ss, *x;
+    float *du, *dg, *dbias, *dss, *out;
+} dm_reduce_layer;
+int dm_op_deferred_reduce(const dm_reduce_layer* layers, int n_layers, int B, int deferred, int accumulate, void* stream);
+
 /* ---- measurement (bench.py's roofline leg; not part of the reference surface) -------------
  * While enabled, every convolution / fused-attention launch is bracketed by two HIP events recorded on
  * the stream the kernel is launched on.  Do not combine with use_graph.  dm_profile_enable(1) first

@@ -159,3 +159,13 @@ def test_conv_families_on_the_forced_and_the_alternative_forms():
                             "-x", "-m", "gpu", "-p", "no:cacheprovider"],
                            cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, (extra, r.stdout[-4000:] + r.stderr[-2000:])
+
+
+def test_conditioning_head_on_the_valu_kernels():
+    """tests/test_hip_cond_ops.py once more, at its own limits, with the MFMA row GEMMs off: linear_rows8_kernel,
+    linear_wgrad_kernel, mlp_rows_wgrad_kernel and linear_dgrad_kernel (with its 16 shares on the wide head) take the
+    batches that rows_gemm_nt / tn / nn take by default."""
+    env = dict(os.environ, DM_NO_SMALL_GEMM="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_hip_cond_ops.py"), "-q", "-x", "-m", "gpu",
+                        "-p", "no:cacheprovider"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
