@@ -5,7 +5,9 @@ for); import it as ``diffusion_models_amd`` through the shim at the repo root.
 """
 from .spec import (  # noqa: F401
     DecoderConfig,
+    EncoderConfig,
     UnetConfig,
+    autoencoder_kl_param_spec,
     ddim_time_pairs,
     decoder_param_spec,
     encoder_param_spec,
@@ -32,7 +34,8 @@ from .repaint import GaussianDiffusion as RePaintGaussianDiffusion, RepaintTable
 from .learned import LearnedGaussianDiffusion, lv_step_table, lv_train_table  # noqa: F401
 from .weighted import WeightedObjectiveGaussianDiffusion, wo_step_table, wo_train_table  # noqa: F401
 from .classifier_guidance import ClassifierGuidedGaussianDiffusion, cg_step_table  # noqa: F401
-from .vae import VQDecoder, VQEncoder, VQModel  # noqa: F401
+from .vae import (AutoencoderKL, DiagonalGaussianDistribution, KLEncoder, VQDecoder, VQEncoder, VQModel,  # noqa: F401
+                  VQModelInterface)
 from .dist import gather_shards, sample_global, sample_sharded, shard_bounds, shared_seed  # noqa: F401
 from .checkpoint import load_trainer_checkpoint, load_vae_checkpoint  # noqa: F401
 from .train import EMA, diffusion_state_dict, load_checkpoint, save_checkpoint, train_step  # noqa: F401
@@ -57,6 +60,10 @@ __all__ = [
     "VQDecoder",
     "VQEncoder",
     "VQModel",
+    "VQModelInterface",
+    "AutoencoderKL",
+    "KLEncoder",
+    "DiagonalGaussianDistribution",
     "InceptionV3",
     "FIDEvaluation",
     "InceptionScoreEvaluation",
@@ -68,6 +75,8 @@ __all__ = [
     "DecoderConfig",
     "unet_param_spec",
     "decoder_param_spec",
+    "EncoderConfig",
+    "autoencoder_kl_param_spec",
     "make_schedule",
     "ddim_time_pairs",
     "edm_sigmas",

@@ -38,9 +38,11 @@ EXPORTS = (
     "dm_decoder_finalize", "dm_decoder_forward",
     "dm_encoder_create", "dm_encoder_destroy", "dm_encoder_set_param", "dm_encoder_missing_params",
     "dm_encoder_finalize", "dm_encoder_forward",
+    "dm_encoder_forward_kl", "dm_encoder_quantize", "dm_encoder_embed_code",
     "dm_op_conv2d", "dm_op_downsample", "dm_op_rmsnorm", "dm_op_block", "dm_op_linear_attention",
     "dm_op_attention", "dm_op_sampler_update", "dm_op_cfg_combine",
     "dm_op_group_norm", "dm_op_vae_attention", "dm_op_vq_nearest",
+    "dm_op_vq_nearest_nchw", "dm_op_kl_posterior", "dm_op_embed_code",
     "dm_conv_create", "dm_conv_destroy", "dm_conv_forward", "dm_op_pool2d", "dm_op_resize_bilinear",
     "dm_op_copy_channels_nhwc", "dm_op_global_avgpool", "dm_op_linear",
     "dm_unet_train_enable", "dm_unet_grad_floats", "dm_unet_grads_flat", "dm_unet_train_buckets", "dm_unet_train_bucket", "dm_unet_get_grad", "dm_unet_loss_backward", "dm_unet_loss_backward_ex", "dm_unet_loss_backward_masked", "dm_op_q_sample", "dm_op_linear_bwd",
@@ -225,6 +227,9 @@ class WoTrainArgs(C.Structure):
     ]
 
 
+KL_NCHW, KL_ROWS = 0, 1  # DM_KL_* of dm_op_kl_posterior
+
+
 OBJECTIVES = {"pred_noise": 0, "pred_x0": 1, "pred_v": 2}
 
 
@@ -294,6 +299,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_encoder_missing_params.argtypes = [vp]
     lib.dm_encoder_finalize.argtypes = [vp]
     lib.dm_encoder_forward.argtypes = [vp, fp, fp, fp, vp, i32, i32, i32, vp]
+    lib.dm_encoder_forward_kl.argtypes = [vp, fp, fp, fp, fp, fp, u64, u64, u64, i32, i32, i32, i32, vp]
+    lib.dm_encoder_quantize.argtypes = [vp, fp, fp, vp, i32, i32, i32, vp]
+    lib.dm_encoder_embed_code.argtypes = [vp, vp, fp, i32, i32, i32, vp]
     lib.dm_op_conv2d.argtypes = [fp, i32, fp, i32, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.dm_op_downsample.argtypes = [fp, i32, fp, fp, fp, i32, i32, i32, i32, vp]
     lib.dm_op_rmsnorm.argtypes = [fp, fp, fp, i32, i32, i32, i32, vp]
@@ -306,6 +314,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_group_norm.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, C.c_float, i32, vp]
     lib.dm_op_vae_attention.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, vp]
     lib.dm_op_vq_nearest.argtypes = [fp, fp, fp, vp, i64, i32, i32, i32, vp]
+    lib.dm_op_vq_nearest_nchw.argtypes = [fp, fp, fp, vp, i64, i32, i32, i32, vp]
+    lib.dm_op_kl_posterior.argtypes = [fp, i32, fp, u64, u64, u64, i32, fp, fp, fp, i32, i32, i32, vp]
+    lib.dm_op_embed_code.argtypes = [vp, i32, fp, fp, i64, i32, i32, i32, vp]
     lib.dm_conv_create.argtypes = [fp, fp, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
     lib.dm_conv_destroy.argtypes = [vp]
     lib.dm_conv_destroy.restype = None

@@ -269,6 +269,16 @@ int launch_group_stats_fast(const float* x, float* stats, double* acc, int B, in
 // GroupNorm(32 groups) + optional swish, NHWC; stats_ws holds B*groups*2 floats + B*groups*2 doubles
 int launch_group_norm(const float* x, const float* w, const float* b, float* y, float* stats_ws, int B, int HW,
                       int C, int groups, float eps, int swish, hipStream_t s);
+// KL first stage (kl_kernels.hip).  Posterior of DiagonalGaussianDistribution: moments (B, 2E, hw) as pixel rows (rows = 1)
+// or NCHW (rows = 0) -> z = mean + std * eps (sample != 0; eps injected, or the Philox draw of dm_randn when eps == nullptr)
+// or mean, the moments in NCHW, kl (B); each output optional.  kl_ws: kl_posterior_ws_floats(B, E, hw) floats, 8-byte aligned.
+size_t kl_posterior_ws_floats(int B, int E, int hw);
+int launch_kl_posterior(const float* moments, int rows, const float* eps, uint64_t seed, uint64_t draw,
+                        uint64_t element_offset, int sample, float* z, float* moments_nchw, float* kl, float* kl_ws, int B,
+                        int E, int hw, hipStream_t s);
+// out_nchw[b][c][sp] = codebook[indices[b * hw + sp]][c]; *bad (device) becomes 1 when an index is outside [0, n_embed)
+int launch_embed_code(const void* indices, int index_bytes, const float* codebook, float* out_nchw, int* bad, int64_t pixels,
+                      int E, int n_embed, int hw, hipStream_t s);
 int launch_add(const float* a, const float* b, float* y, int64_t n, hipStream_t s);
 // consumer-side ops (consumer_ops.hip): NHWC pooling (mode 0 max, 1 avg counting the padding, 2 avg over valid pixels),
 // bilinear resize (align_corners = False) NCHW -> NHWC with a per-channel affine map, channel-slice copy, global mean

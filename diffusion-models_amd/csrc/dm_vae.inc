@@ -364,7 +364,9 @@ int dm_decoder_forward(dm_decoder* d, const float* z, float* out, int B, int h, 
 namespace dm {
 
 // One wavefront per latent pixel: lane l scans codes l, l+64, ...; ties resolve to the lowest index (torch.argmin).
-// z: (pixels, E) rows; e: (n_embed, E); e2[j] = sum_c e[j][c]^2; zq_nchw (B, E, hw); idx (pixels) or nullptr.
+// z: (pixels, E) rows, or (B, E, hw) NCHW when NCHW (the sampler's latents; the same arithmetic in the same order on the
+// same values); e: (n_embed, E); e2[j] = sum_c e[j][c]^2; zq_nchw (B, E, hw); idx (pixels) or nullptr.
+template <bool NCHW>
 __global__ __launch_bounds__(256) void vq_nearest_kernel(const float* __restrict__ z, const float* __restrict__ e,
                                                          const float* __restrict__ e2, float* __restrict__ zq_nchw,
                                                          int* __restrict__ idx, int64_t pixels, int E, int n_embed,
@@ -372,14 +374,16 @@ __global__ __launch_bounds__(256) void vq_nearest_kernel(const float* __restrict
     const int lane = threadIdx.x & 63;
     const int64_t pix = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (pix >= pixels) return;
-    const float* zr = z + pix * E;
+    const int64_t b = pix / hw, sp = pix - b * hw;
+    const float* zr = NCHW ? z + b * E * hw + sp : z + pix * E;
+    const int64_t cs = NCHW ? hw : 1;  // distance between two channels of a pixel
     float z2 = 0.f;
-    for (int c = 0; c < E; ++c) z2 += zr[c] * zr[c];
+    for (int c = 0; c < E; ++c) z2 += zr[c * cs] * zr[c * cs];
     float best = INFINITY;
     int bi = 0x7fffffff;
     for (int j = lane; j < n_embed; j += 64) {
         float dot = 0.f;
-        for (int c = 0; c < E; ++c) dot += zr[c] * e[(size_t)j * E + c];
+        for (int c = 0; c < E; ++c) dot += zr[c * cs] * e[(size_t)j * E + c];
         const float d = z2 + e2[j] - 2.0f * dot;
         if (d < best) {
             best = d;
@@ -395,21 +399,23 @@ __global__ __launch_bounds__(256) void vq_nearest_kernel(const float* __restrict
             bi = oi;
         }
     }
-    const int64_t b = pix / hw, sp = pix - b * hw;
     for (int c = lane; c < E; c += 64) {
-        const float zv = zr[c];
+        const float zv = zr[c * cs];
         zq_nchw[(b * E + c) * hw + sp] = zv + (e[(size_t)bi * E + c] - zv);  // z + (z_q - z).detach(), as the reference forms it
     }
     if (idx && lane == 0) idx[pix] = bi;
 }
 
 static int launch_vq_nearest(const float* z, const float* e, const float* e2, float* zq_nchw, int* idx, int64_t pixels,
-                             int E, int n_embed, int hw, hipStream_t s) {
+                             int E, int n_embed, int hw, hipStream_t s, bool in_nchw = false) {
     DM_REQUIRE(pixels > 0 && E > 0 && n_embed > 0 && hw > 0, "VQ: empty input");
     DM_REQUIRE(pixels % hw == 0, "VQ: pixels is a whole number of images of hw pixels");
     DM_REQUIRE((pixels + 3) / 4 <= 0x7fffffff, "VQ: too many pixels for one launch");
-    hipLaunchKernelGGL(vq_nearest_kernel, dim3((unsigned)((pixels + 3) / 4)), dim3(256), 0, s, z, e, e2, zq_nchw, idx,
-                       pixels, E, n_embed, hw);
+    const dim3 grid((unsigned)((pixels + 3) / 4));
+    if (in_nchw)
+        hipLaunchKernelGGL(vq_nearest_kernel<true>, grid, dim3(256), 0, s, z, e, e2, zq_nchw, idx, pixels, E, n_embed, hw);
+    else
+        hipLaunchKernelGGL(vq_nearest_kernel<false>, grid, dim3(256), 0, s, z, e, e2, zq_nchw, idx, pixels, E, n_embed, hw);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -437,13 +443,16 @@ struct dm_encoder {
     VaeAttn mid_attn;
     std::vector<VaeLevel> levels;  // VaeLevel::up holds the level's Downsample conv here
     float *now = nullptr, *nob = nullptr, *codebook = nullptr, *code_sq = nullptr;
+    float* bad_index = nullptr;  // one int: raised by embed_code_kernel
     int block_in_final = 0;
+    bool kl() const { return cfg.n_embed == 0; }  // AutoencoderKL: quant_conv yields 2 * embed_dim moments, no codebook
 };
 
 namespace dm {
 
-static int encoder_forward_impl(dm_encoder* d, Arena& A, const float* x, float* zq, float* pre_quant, int* indices, int B,
-                                int H, int W, hipStream_t s) {
+// Encoder.forward -> quant_conv: *pq_out = the quant_conv output as pixel rows (B * h * w, quant_conv.Cout) in the arena
+static int encoder_trunk(dm_encoder* d, Arena& A, const float* x, int B, int H, int W, hipStream_t s, float** pq_out,
+                         int* h_out, int* w_out) {
     const dm_encoder_cfg& cfg = d->cfg;
     Ctx c{&d->holder, &A, s, B, nullptr, 0};
     float* stats = A.alloc(group_stats_ws_floats(B, 32));  // (mean, rstd) + per-block partial sums (launch_group_norm)
@@ -471,8 +480,20 @@ static int encoder_forward_impl(dm_encoder* d, Arena& A, const float* x, float* 
     if (!A.dry && launch_group_norm(cur, d->now, d->nob, a, stats, B, h * w, d->block_in_final, 32, 1e-6f, 1, s)) return 1;
     float* hz = A.alloc((size_t)B * h * w * d->conv_out.Cout);
     if (run_conv(c, d->conv_out, a, nullptr, h, w, hz, 0, nullptr, nullptr, nullptr)) return 1;
-    float* pq = A.alloc((size_t)B * h * w * cfg.embed_dim);
+    float* pq = A.alloc((size_t)B * h * w * d->quant_conv.Cout);
     if (run_conv(c, d->quant_conv, hz, nullptr, h, w, pq, 0, nullptr, nullptr, nullptr)) return 1;
+    *pq_out = pq;
+    *h_out = h;
+    *w_out = w;
+    return 0;
+}
+
+static int encoder_forward_impl(dm_encoder* d, Arena& A, const float* x, float* zq, float* pre_quant, int* indices, int B,
+                                int H, int W, hipStream_t s) {
+    const dm_encoder_cfg& cfg = d->cfg;
+    float* pq;
+    int h, w;
+    if (encoder_trunk(d, A, x, B, H, W, s, &pq, &h, &w)) return 1;
     if (A.dry) return 0;
     if (pre_quant && launch_nhwc_to_nchw(pq, pre_quant, B, cfg.embed_dim, h * w, s)) return 1;
     if (zq) {
@@ -483,6 +504,19 @@ static int encoder_forward_impl(dm_encoder* d, Arena& A, const float* x, float* 
     return 0;
 }
 
+// AutoencoderKL.encode (+ sample / mode / kl of the posterior): the trunk, then one pass over the moment rows
+static int encoder_forward_kl_impl(dm_encoder* d, Arena& A, const float* x, float* moments_nchw, float* z, float* kl,
+                                   const float* eps, uint64_t seed, uint64_t draw, uint64_t element_offset, int sample, int B,
+                                   int H, int W, hipStream_t s) {
+    float* pq;
+    int h, w;
+    if (encoder_trunk(d, A, x, B, H, W, s, &pq, &h, &w)) return 1;
+    float* ws = kl ? A.alloc(kl_posterior_ws_floats(B, d->cfg.embed_dim, h * w)) : nullptr;
+    if (A.dry) return 0;
+    return launch_kl_posterior(pq, /*rows=*/1, eps, seed, draw, element_offset, sample, z, moments_nchw, kl, ws, B,
+                               d->cfg.embed_dim, h * w, s);
+}
+
 }  // namespace dm
 
 extern "C" {
@@ -491,7 +525,8 @@ int dm_encoder_create(const dm_encoder_cfg* cfg, int device, dm_encoder** out) {
     DM_REQUIRE(cfg && out, "null argument");
     DM_REQUIRE(cfg->n_levels >= 1 && cfg->n_levels <= DM_MAX_STAGES, "n_levels out of range");
     DM_REQUIRE(cfg->ch % 32 == 0, "GroupNorm(32) needs ch % 32 == 0");
-    DM_REQUIRE(cfg->n_embed > 0 && cfg->embed_dim > 0, "codebook shape");
+    DM_REQUIRE(cfg->n_embed >= 0 && cfg->embed_dim > 0, "codebook shape");
+    DM_REQUIRE(cfg->n_embed > 0 || cfg->double_z != 0, "an encoder without a codebook (n_embed == 0, AutoencoderKL) needs double_z");
     int ndev = 0;
     DM_CHECK_HIP(hipGetDeviceCount(&ndev));
     DM_REQUIRE(device >= 0 && device < ndev, "no such HIP device");
@@ -529,9 +564,10 @@ int dm_encoder_create(const dm_encoder_cfg* cfg, int device, dm_encoder** out) {
     const int zc = cfg->double_z ? 2 * cfg->z_channels : cfg->z_channels;
     expect(u, "encoder.conv_out.weight", {zc, block_in, 3, 3});
     expect(u, "encoder.conv_out.bias", {zc});
-    expect(u, "quant_conv.weight", {cfg->embed_dim, zc, 1, 1});
-    expect(u, "quant_conv.bias", {cfg->embed_dim});
-    expect(u, "quantize.embedding.weight", {cfg->n_embed, cfg->embed_dim});
+    const int qc = cfg->n_embed == 0 ? 2 * cfg->embed_dim : cfg->embed_dim;  // LD/models/autoencoder.py:356 / :40
+    expect(u, "quant_conv.weight", {qc, zc, 1, 1});
+    expect(u, "quant_conv.bias", {qc});
+    if (cfg->n_embed > 0) expect(u, "quantize.embedding.weight", {cfg->n_embed, cfg->embed_dim});
     *out = d.release();
     return 0;
 }
@@ -592,11 +628,15 @@ int dm_encoder_finalize(dm_encoder* d) {
     if (up1(u, "encoder.norm_out.weight", &d->now) || up1(u, "encoder.norm_out.bias", &d->nob)) return 1;
     const int zc = cfg.double_z ? 2 * cfg.z_channels : cfg.z_channels;
     if (vconv(u, d->conv_out, "encoder.conv_out", zc, block_in, 3, 1, false)) return 1;
-    if (vconv(u, d->quant_conv, "quant_conv", cfg.embed_dim, zc, 1, 0, false)) return 1;
-    const HostTensor& cb = P(u, "quantize.embedding.weight");
-    const std::vector<float> sq = code_sq_host(cb.data.data(), cfg.n_embed, cfg.embed_dim);
-    if (u->own.upload(cb.data.data(), cb.data.size(), &d->codebook) || u->own.upload(sq.data(), sq.size(), &d->code_sq))
-        return 1;
+    if (vconv(u, d->quant_conv, "quant_conv", d->kl() ? 2 * cfg.embed_dim : cfg.embed_dim, zc, 1, 0, false)) return 1;
+    if (!d->kl()) {
+        const HostTensor& cb = P(u, "quantize.embedding.weight");
+        const std::vector<float> sq = code_sq_host(cb.data.data(), cfg.n_embed, cfg.embed_dim);
+        const float zero = 0.f;
+        if (u->own.upload(cb.data.data(), cb.data.size(), &d->codebook) || u->own.upload(sq.data(), sq.size(), &d->code_sq) ||
+            u->own.upload(&zero, 1, &d->bad_index))
+            return 1;
+    }
     for (auto& kv : u->params) std::vector<float>().swap(kv.second.data);
     d->finalized = true;
     return 0;
@@ -606,6 +646,7 @@ int dm_encoder_forward(dm_encoder* d, const float* x, float* zq, float* pre_quan
                        void* stream) {
     DM_REQUIRE(d && x && (zq || pre_quant), "null argument");
     DM_REQUIRE(d->finalized, "dm_encoder_finalize has not been called");
+    DM_REQUIRE(!d->kl(), "this handle has no codebook (n_embed == 0): use dm_encoder_forward_kl");
     DM_REQUIRE(B > 0 && H > 0 && W > 0, "empty input");
     const int f = 1 << (d->cfg.n_levels - 1);
     DM_REQUIRE(H % f == 0 && W % f == 0, "image size must be divisible by the encoder's downsampling factor");
@@ -619,6 +660,63 @@ int dm_encoder_forward(dm_encoder* d, const float* x, float* zq, float* pre_quan
     A.base = d->holder.ws;
     A.cap = d->holder.ws_cap;
     return encoder_forward_impl(d, A, x, zq, pre_quant, indices, B, H, W, s);
+}
+
+int dm_encoder_forward_kl(dm_encoder* d, const float* x, float* moments_nchw, float* z, float* kl, const float* eps,
+                          uint64_t seed, uint64_t draw, uint64_t element_offset, int sample, int B, int H, int W, void* stream) {
+    DM_REQUIRE(d && x && (moments_nchw || z || kl), "null argument");
+    DM_REQUIRE(d->finalized, "dm_encoder_finalize has not been called");
+    DM_REQUIRE(d->kl(), "this handle quantises (n_embed > 0): use dm_encoder_forward");
+    DM_REQUIRE(B > 0 && H > 0 && W > 0, "empty input");
+    const int f = 1 << (d->cfg.n_levels - 1);
+    DM_REQUIRE(H % f == 0 && W % f == 0, "image size must be divisible by the encoder's downsampling factor");
+    if (z && sample && !eps) {  // refused here, before the encoder has run
+        DM_REQUIRE((int64_t)d->cfg.embed_dim * (H / f) * (W / f) % 4 == 0,
+                   "Philox noise needs embed_dim * h * w % 4 == 0 (one counter serves four elements)");
+        DM_REQUIRE(element_offset % 4 == 0, "Philox element offset must be a multiple of 4 (one counter serves 4 elements)");
+    }
+    DM_CHECK_HIP(hipSetDevice(d->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Arena dry;
+    dry.dry = true;
+    if (encoder_forward_kl_impl(d, dry, x, moments_nchw, z, kl, eps, seed, draw, element_offset, sample, B, H, W, s)) return 1;
+    if (ensure_workspace(&d->holder, dry.off)) return 1;
+    Arena A;
+    A.base = d->holder.ws;
+    A.cap = d->holder.ws_cap;
+    return encoder_forward_kl_impl(d, A, x, moments_nchw, z, kl, eps, seed, draw, element_offset, sample, B, H, W, s);
+}
+
+int dm_encoder_quantize(dm_encoder* d, const float* h_nchw, float* zq, int32_t* indices, int B, int h, int w, void* stream) {
+    DM_REQUIRE(d && h_nchw && zq, "null argument");
+    DM_REQUIRE(d->finalized, "dm_encoder_finalize has not been called");
+    DM_REQUIRE(!d->kl(), "this handle has no codebook (n_embed == 0)");
+    DM_REQUIRE(B > 0 && h > 0 && w > 0, "empty input");
+    DM_CHECK_HIP(hipSetDevice(d->device));
+    return launch_vq_nearest(h_nchw, d->codebook, d->code_sq, zq, indices, (int64_t)B * h * w, d->cfg.embed_dim,
+                             d->cfg.n_embed, h * w, static_cast<hipStream_t>(stream), /*in_nchw=*/true);
+}
+
+// the flag of embed_code_kernel, read after the stream has drained: an index outside the codebook is the caller's error
+static int embed_code_verdict(int rc, const int* bad_dev, hipStream_t s) {
+    if (rc) return rc;
+    int bad = 0;
+    DM_CHECK_HIP(hipMemcpyAsync(&bad, bad_dev, sizeof(int), hipMemcpyDeviceToHost, s));
+    DM_CHECK_HIP(hipStreamSynchronize(s));
+    DM_REQUIRE(bad == 0, "embed_code: an index lies outside [0, n_embed)");
+    return 0;
+}
+
+int dm_encoder_embed_code(dm_encoder* d, const int64_t* indices, float* out, int B, int h, int w, void* stream) {
+    DM_REQUIRE(d && indices && out, "null argument");
+    DM_REQUIRE(d->finalized, "dm_encoder_finalize has not been called");
+    DM_REQUIRE(!d->kl(), "this handle has no codebook (n_embed == 0)");
+    DM_REQUIRE(B > 0 && h > 0 && w > 0, "empty input");
+    DM_CHECK_HIP(hipSetDevice(d->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int* bad = reinterpret_cast<int*>(d->bad_index);
+    return embed_code_verdict(launch_embed_code(indices, 8, d->codebook, out, bad, (int64_t)B * h * w, d->cfg.embed_dim,
+                                                d->cfg.n_embed, h * w, s), bad, s);
 }
 
 }  // extern "C"
@@ -682,6 +780,50 @@ int dm_op_vq_nearest(const float* z_rows, const float* codebook, float* zq_nchw,
     }
     int rc = launch_vq_nearest(z_rows, codebook, e2, zq_nchw, indices, pixels, E, n_embed, hw, s);
     return finish_vae_op(rc, s, e2);
+}
+
+int dm_op_vq_nearest_nchw(const float* z_nchw, const float* codebook, float* zq_nchw, int32_t* indices, int64_t pixels, int E,
+                          int n_embed, int hw, void* stream) {
+    DM_REQUIRE(z_nchw && codebook && zq_nchw, "null argument");
+    DM_REQUIRE(pixels > 0 && E > 0 && n_embed > 0 && hw > 0, "empty input");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<float> cb;
+    if (d2h(codebook, (size_t)n_embed * E, cb)) return 1;
+    const std::vector<float> sq = code_sq_host(cb.data(), n_embed, E);
+    float* e2 = nullptr;
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&e2), sq.size() * sizeof(float)));
+    hipError_t e = hipMemcpy(e2, sq.data(), sq.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(e2);
+        DM_CHECK_HIP(e);
+    }
+    int rc = launch_vq_nearest(z_nchw, codebook, e2, zq_nchw, indices, pixels, E, n_embed, hw, s, /*in_nchw=*/true);
+    return finish_vae_op(rc, s, e2);
+}
+
+int dm_op_kl_posterior(const float* moments, int layout, const float* eps, uint64_t seed, uint64_t draw,
+                       uint64_t element_offset, int sample, float* z, float* moments_nchw, float* kl, int B, int E, int hw,
+                       void* stream) {
+    DM_REQUIRE(moments && (z || moments_nchw || kl), "null argument");
+    DM_REQUIRE(layout == DM_KL_NCHW || layout == DM_KL_ROWS, "layout: DM_KL_NCHW or DM_KL_ROWS");
+    DM_REQUIRE(B > 0 && B <= 65535 && E > 0 && hw > 0, "empty input, or B > 65535");  // before the workspace is sized
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* ws = nullptr;
+    if (kl) DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&ws), kl_posterior_ws_floats(B, E, hw) * sizeof(float)));
+    int rc = launch_kl_posterior(moments, layout == DM_KL_ROWS, eps, seed, draw, element_offset, sample, z, moments_nchw, kl,
+                                 ws, B, E, hw, s);
+    return finish_vae_op(rc, s, ws);
+}
+
+int dm_op_embed_code(const void* indices, int index_bytes, const float* codebook, float* out_nchw, int64_t pixels, int E,
+                     int n_embed, int hw, void* stream) {
+    DM_REQUIRE(indices && codebook && out_nchw, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int* bad = nullptr;
+    DM_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&bad), sizeof(int)));
+    int rc = embed_code_verdict(launch_embed_code(indices, index_bytes, codebook, out_nchw, bad, pixels, E, n_embed, hw, s),
+                                bad, s);
+    return finish_vae_op(rc, s, bad);
 }
 
 }  // extern "C"

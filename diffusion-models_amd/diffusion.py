@@ -896,6 +896,20 @@ class ImageConditionalDenoisingDiffusion(DenoisingDiffusion):
         return self._p_sample(x, t, noise, {"cond": cond}, x_self_cond)
 
 
+def _first_stage_latents(vae, images):
+    """What the latent classes diffuse on, for every first stage ``encode`` of this package returns: a tensor
+    (``VQModelInterface``), a tuple whose head is the latent (``VQModel``), or a posterior.  A posterior yields its
+    sample -- through ``encode_sample``, one library call, where the VAE has it (``AutoencoderKL``), else through the
+    object's ``sample()``.  This goes beyond the reference, whose ``LatentDiffusion.encode`` passes the posterior object
+    on (latent_diffusion.py:33-40)."""
+    if hasattr(vae, "encode_sample"):
+        return vae.encode_sample(images)
+    latents = vae.encode(images)
+    if hasattr(latents, "sample"):
+        return latents.sample()
+    return latents[0] if isinstance(latents, tuple) else latents
+
+
 class LatentDiffusion(DenoisingDiffusion):
     """Diffusion on VAE latents, then decode (latent_diffusion.py:9-66)."""
 
@@ -914,8 +928,7 @@ class LatentDiffusion(DenoisingDiffusion):
 
     def encode(self, images):
         """latent_diffusion.py:33-40: the (frozen) VAE's latents of a batch of images."""
-        latents = self.vae.encode(images)
-        return latents[0] if isinstance(latents, tuple) else latents
+        return _first_stage_latents(self.vae, images)
 
     def forward(self, real_images, *args, **kwargs):
         """latent_diffusion.py:51-56: the training loss on the VAE latents of the images."""
@@ -951,8 +964,7 @@ class TextConditionalLatentDiffusion(TextConditionalDenoisingDiffusion):
         self._unnormalize_flag = 0
 
     def encode(self, images):
-        latents = self.vae.encode(images)
-        return latents[0] if isinstance(latents, tuple) else latents
+        return _first_stage_latents(self.vae, images)
 
     def decode(self, latents):
         return self.vae.decode(latents)
@@ -995,8 +1007,7 @@ class ImageConditionalLatentDiffusion(ImageConditionalDenoisingDiffusion):
         self.latent_channels = latent_shape[0]
 
     def encode(self, images, cond=False):
-        latents = (self.cond_vae if cond else self.vae).encode(images)
-        return latents[0] if isinstance(latents, tuple) else latents
+        return _first_stage_latents(self.cond_vae if cond else self.vae, images)
 
     def decode(self, latents, cond=False):
         return (self.cond_vae if cond else self.vae).decode(latents)

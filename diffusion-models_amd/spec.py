@@ -522,7 +522,9 @@ class EncoderConfig:
 
 def encoder_param_spec(cfg: EncoderConfig, prefix: str = "") -> ParamSpec:
     """Parameters of ``VQModel.encoder`` + ``quant_conv`` + ``quantize.embedding`` in ``state_dict()`` order of the
-    Encoder (down.{l}.block.*, down.{l}.attn.*, down.{l}.downsample, mid, norm_out, conv_out)."""
+    Encoder (down.{l}.block.*, down.{l}.attn.*, down.{l}.downsample, mid, norm_out, conv_out).  ``n_embed == 0`` is the
+    KL first stage (``AutoencoderKL``, autoencoder.py:356): ``quant_conv`` yields ``2 * embed_dim`` moments and there is
+    no codebook."""
     p = prefix
     spec: ParamSpec = [
         (f"{p}encoder.conv_in.weight", (cfg.ch, cfg.in_channels, 3, 3)),
@@ -556,9 +558,24 @@ def encoder_param_spec(cfg: EncoderConfig, prefix: str = "") -> ParamSpec:
         (f"{p}encoder.norm_out.bias", (block_in,)),
         (f"{p}encoder.conv_out.weight", (zc, block_in, 3, 3)),
         (f"{p}encoder.conv_out.bias", (zc,)),
+    ]
+    if cfg.n_embed == 0:
+        assert cfg.double_z, "the KL first stage needs double_z"
+        return spec + [(f"{p}quant_conv.weight", (2 * cfg.embed_dim, zc, 1, 1)), (f"{p}quant_conv.bias", (2 * cfg.embed_dim,))]
+    spec += [
         (f"{p}quant_conv.weight", (cfg.embed_dim, zc, 1, 1)),
         (f"{p}quant_conv.bias", (cfg.embed_dim,)),
         (f"{p}quantize.embedding.weight", (cfg.n_embed, cfg.embed_dim)),
     ]
     return spec
 
+
+
+def autoencoder_kl_param_spec(ecfg: EncoderConfig, dcfg: DecoderConfig, prefix: str = "") -> ParamSpec:
+    """Parameters of ``AutoencoderKL`` (latent-diffusion/ldm/models/autoencoder.py:351-357) in its ``state_dict()`` order:
+    encoder, decoder, quant_conv, post_quant_conv (``ecfg.n_embed == 0``; the loss network is not part of it)."""
+    assert ecfg.n_embed == 0, "the KL first stage has no codebook"
+    enc, dec = encoder_param_spec(ecfg, prefix), decoder_param_spec(dcfg, prefix)
+    q, pq = f"{prefix}quant_conv.", f"{prefix}post_quant_conv."
+    return ([e for e in enc if not e[0].startswith(q)] + [e for e in dec if not e[0].startswith(pq)]
+            + [e for e in enc if e[0].startswith(q)] + [e for e in dec if e[0].startswith(pq)])

@@ -273,6 +273,29 @@ int dm_encoder_finalize(dm_encoder* e);
  * zq may be NULL when only pre_quant is wanted. */
 int dm_encoder_forward(dm_encoder* e, const float* x, float* zq, float* pre_quant, int32_t* indices, int B, int H, int W,
                        void* stream);
+/* The KL first stage (AutoencoderKL, LD/models/autoencoder.py:339-396) on the same handle type: a cfg with n_embed == 0 has
+ * no codebook.  It needs double_z != 0, takes "quant_conv.weight" as (2 * embed_dim, 2 * z_channels, 1, 1) (:356) and no
+ * "quantize.embedding.weight"; dm_encoder_forward, dm_encoder_quantize and dm_encoder_embed_code refuse such a handle, and
+ * dm_encoder_forward_kl refuses one with a codebook.
+ * x (B, in_channels, H, W) -> Encoder -> quant_conv -> the posterior of DiagonalGaussianDistribution
+ * (LD/modules/distributions/distributions.py:24-62), in one call on the handle's workspace: no host synchronisation, and no
+ * allocation after the first call of a shape.  Outputs, each optional (NULL: not written), at least one:
+ *   moments_nchw (B, 2 * embed_dim, h, w)  the quant_conv output, log-variance unclamped (`parameters`)
+ *   z            (B, embed_dim, h, w)      sample != 0: mean + exp(0.5 * clamp(logvar, -30, 20)) * eps;  0: the mean (mode)
+ *   kl           (B)                       0.5 * sum(mean^2 + exp(logvar) - 1 - logvar) over (embed_dim, h, w), logvar clamped
+ * eps (B, embed_dim, h, w) injects the noise; eps == NULL draws it from the library's Philox stream, element e of z using
+ * counter ((element_offset + e) / 4, draw) under key seed, i.e. the values of dm_randn for that shape (needs
+ * embed_dim * h * w % 4 == 0 and element_offset % 4 == 0).  kl is a fixed-order sum: two calls give the same bits. */
+int dm_encoder_forward_kl(dm_encoder* e, const float* x, float* moments_nchw, float* z, float* kl, const float* eps,
+                          uint64_t seed, uint64_t draw, uint64_t element_offset, int sample, int B, int H, int W, void* stream);
+/* VectorQuantizer on a pre-quantisation latent held in NCHW (VQModelInterface.decode, autoencoder.py:329-336): h_nchw
+ * (B, embed_dim, h, w) -> zq (same shape) = h + (nearest code - h) and indices (B*h*w, may be NULL), the search of
+ * dm_encoder_forward on the handle's device codebook. */
+int dm_encoder_quantize(dm_encoder* e, const float* h_nchw, float* zq, int32_t* indices, int B, int h, int w, void* stream);
+/* quantize.embed_code + the "b h w c -> b c h w" permute of VQModel.decode_code (autoencoder.py:118-121): indices (B*h*w)
+ * int64 -> out (B, embed_dim, h, w).  Synchronises the stream: an index outside [0, n_embed) is an error (it is never used as
+ * an address). */
+int dm_encoder_embed_code(dm_encoder* e, const int64_t* indices, float* out, int B, int h, int w, void* stream);
 
 /* ---- single operators (the kernels behind the calls above, exposed so that parity tests
  *      can check each one against the reference module it replaces) -------------------------
@@ -326,6 +349,21 @@ int dm_op_vae_attention(const float* q, const float* k, const float* v, float* o
 /* The codebook search of VQModel.encode: z_rows (pixels, E), codebook (n_embed, E) -> zq_nchw (pixels / hw, E, hw) =
  * z + (nearest code - z) and indices (pixels, may be NULL); ties go to the lower index. */
 int dm_op_vq_nearest(const float* z_rows, const float* codebook, float* zq_nchw, int32_t* indices, int64_t pixels, int E,
+                     int n_embed, int hw, void* stream);
+/* The same search on a latent in NCHW, z_nchw (pixels / hw, E, hw): the kernel behind dm_encoder_quantize. */
+int dm_op_vq_nearest_nchw(const float* z_nchw, const float* codebook, float* zq_nchw, int32_t* indices, int64_t pixels, int E,
+                          int n_embed, int hw, void* stream);
+/* The posterior kernel of dm_encoder_forward_kl on its own.  moments (B, 2E, hw) in NCHW (layout DM_KL_NCHW) or as pixel rows
+ * (B * hw, 2E) (DM_KL_ROWS); eps, seed, draw, element_offset, sample and the three optional outputs as there (Philox noise
+ * needs E * hw % 4 == 0, injected noise has no such restriction). */
+#define DM_KL_NCHW 0
+#define DM_KL_ROWS 1
+int dm_op_kl_posterior(const float* moments, int layout, const float* eps, uint64_t seed, uint64_t draw,
+                       uint64_t element_offset, int sample, float* z, float* moments_nchw, float* kl, int B, int E, int hw,
+                       void* stream);
+/* The code gather of dm_encoder_embed_code on its own: indices (pixels) of index_bytes 4 (int32) or 8 (int64), codebook
+ * (n_embed, E) -> out_nchw (pixels / hw, E, hw).  An index outside [0, n_embed) is an error. */
+int dm_op_embed_code(const void* indices, int index_bytes, const float* codebook, float* out_nchw, int64_t pixels, int E,
                      int n_embed, int hw, void* stream);
 
 /* ---- sample consumer: the InceptionV3 feature extractor behind the reference's FID and
