@@ -27,6 +27,7 @@ DM_WO_COEFS = 16
 DM_WO_TRAIN_COEFS = 12
 DM_CG_COEFS = 16
 ABI_VERSION = 9
+DDIM_NO_CLAMP, DDIM_RAW_NOISE = 1, 2  # DM_DDIM_* of include/dm_hip.h
 
 # every symbol include/dm_hip.h declares (tests check the library exports all of them)
 EXPORTS = (
@@ -41,6 +42,7 @@ EXPORTS = (
     "dm_encoder_forward_kl", "dm_encoder_quantize", "dm_encoder_embed_code",
     "dm_op_conv2d", "dm_op_downsample", "dm_op_rmsnorm", "dm_op_block", "dm_op_linear_attention",
     "dm_op_attention", "dm_op_sampler_update", "dm_op_cfg_combine",
+    "dm_op_sampler_update_ex", "dm_op_conv1d", "dm_op_block1d",
     "dm_op_group_norm", "dm_op_vae_attention", "dm_op_vq_nearest",
     "dm_op_vq_nearest_nchw", "dm_op_kl_posterior", "dm_op_embed_code",
     "dm_conv_create", "dm_conv_destroy", "dm_conv_forward", "dm_op_pool2d", "dm_op_resize_bilinear",
@@ -79,6 +81,7 @@ class UnetCfg(C.Structure):
         ("attn_heads", C.c_int32), ("attn_dim_head", C.c_int32),
         ("text_mode", C.c_int32), ("text_emb_dim", C.c_int32), ("sinusoidal_theta", C.c_float),
         ("learned_sinusoidal_dim", C.c_int32), ("attn_heads_stage", C.c_int32 * DM_MAX_STAGES),
+        ("seq1d", C.c_int32),
     ]
 
 
@@ -108,7 +111,7 @@ class SampleArgs(C.Structure):
         ("ctx", C.c_void_p), ("ctx_tokens", C.c_int32), ("cond_channels", C.c_int32), ("cond", C.c_void_p),
         ("out", C.c_void_p), ("all_steps", C.c_void_p),
         ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("unnormalize", C.c_int32), ("use_graph", C.c_int32),
-        ("reserved_", C.c_int32), ("stream", C.c_void_p),
+        ("ddim_flags", C.c_int32), ("stream", C.c_void_p),
         ("cfg", C.c_int32), ("cfg_scale", C.c_float), ("cfg_rescaled_phi", C.c_float),
         ("cfg_keep_parallel_frac", C.c_float), ("cfg_remove_parallel", C.c_int32), ("cfg_reserved_", C.c_int32),
     ]
@@ -309,6 +312,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_linear_attention.argtypes = [fp, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
     lib.dm_op_attention.argtypes = [fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, vp]
     lib.dm_op_sampler_update.argtypes = [i32, i32, fp, fp, fp, C.POINTER(C.c_float), fp, fp, i64, vp]
+    lib.dm_op_sampler_update_ex.argtypes = [i32, i32, i32, fp, fp, fp, C.POINTER(C.c_float), fp, fp, i64, vp]
+    lib.dm_op_conv1d.argtypes = [fp, i32, fp, i32, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.dm_op_block1d.argtypes = [fp, i32, fp, i32, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, vp]
     lib.dm_op_dpmpp_update.argtypes = [i32, fp, fp, fp, C.POINTER(C.c_float), fp, i64, vp]
     lib.dm_op_cfg_combine.argtypes = [fp, fp, fp, i32, i64, C.c_float, C.c_float, i32, C.c_float, vp]
     lib.dm_op_group_norm.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, C.c_float, i32, vp]

@@ -19,6 +19,9 @@ def checked_shape(diff, shape):
     B, Cc, H, W = shape
     assert Cc == diff.channels, f"shape has {Cc} channels, the model {diff.channels}"
     f = diff.model.downsample_factor
+    if getattr(diff.model, "seq1d", False):  # a sequence (B, C, L) arrives as its one-row view (B, C, 1, L)
+        assert B > 0 and H == 1 and W % f == 0, f"shape {shape}: one row, its length divisible by {f}"
+        return shape
     assert B > 0 and H % f == 0 and W % f == 0, f"shape {shape}: the sides must be divisible by {f}"
     return shape
 

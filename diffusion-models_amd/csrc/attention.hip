@@ -42,19 +42,19 @@ __device__ __forceinline__ float wave_sum64(float v) {
 // so a lane loads ONE dword of k and ONE of v per step and 32-row tile (lanes 0-31 / 32-63 read the 128 contiguous bytes of
 // two consecutive tokens) and each 32x32 tile of the context accumulates in 16 registers (one tile at DH = 32, 2 x 2 at 64).
 // grid (heads, B), NW waves; each wave takes 1 / NW of the tokens, the partial contexts meet in LDS.  The 4 memory tokens
-// are two extra steps.
+// are two extra steps (NMEM = 4); the sequence model's layers have none (NMEM = 0, mem_kv is not read).
 // ---------------------------------------------------------------------------------------
 using f32x16_t = __attribute__((ext_vector_type(16))) float;
 
 // NW waves per (image, head): the token loop is a chain of load round trips (8 loads in flight per lane and tile, then the
 // MFMAs), so with heads x B workgroups and nothing else to overlap, the kernel's time is one wave's chain; 16 waves on the
 // 1024 tokens of a 32x32 stage make that chain 8 rounds instead of 32 (45 -> about 15 us in the B = 64 training step).
-template <int NW, int DH>
+template <int NW, int DH, int NMEM = 4>
 __global__ __launch_bounds__(64 * NW) void linattn_ctx_mfma_kernel(const float* __restrict__ qkv,
                                                                    const float* __restrict__ mem_kv,
                                                                    float* __restrict__ ctx, float* __restrict__ kstats,
                                                                    int n, int heads) {
-    constexpr int NMEM = 4;
+    static_assert(NMEM == 0 || NMEM == 4, "memory key / values: 4, or none");
     constexpr int NT = DH / 32;  // 32-wide tiles per side of the context
     const int h = blockIdx.x, b = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -62,8 +62,8 @@ __global__ __launch_bounds__(64 * NW) void linattn_ctx_mfma_kernel(const float* 
     const int ld = 3 * heads * DH;
     const float* kb = qkv + (size_t)b * n * ld + heads * DH + h * DH + c;
     const float* vb = qkv + (size_t)b * n * ld + 2 * heads * DH + h * DH + c;
-    const float* mk = mem_kv + (size_t)h * DH * NMEM;            // [d][j]
-    const float* mv = mem_kv + (size_t)(heads + h) * DH * NMEM;  // [e][j]
+    const float* mk = NMEM > 0 ? mem_kv + (size_t)h * DH * NMEM : nullptr;            // [d][j]
+    const float* mv = NMEM > 0 ? mem_kv + (size_t)(heads + h) * DH * NMEM : nullptr;  // [e][j]
     __shared__ float red[NW][DH];
     __shared__ float kmax_s[DH], ksum_s[DH];
     // partial-context slots: at DH = 32, 16 waves fold in two rounds (64 KB of static LDS would not fit with the rest); a
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(64 * NW) void linattn_ctx_mfma_kernel(const float* 
 #pragma unroll
             for (int I = 0; I < NT; ++I) m[I] = fmaxf(m[I], kb[(size_t)t * ld + 32 * I]);
     }
-    if (wave == 0) {
+    if (NMEM > 0 && wave == 0) {
 #pragma unroll
         for (int I = 0; I < NT; ++I) {
             m[I] = fmaxf(m[I], mk[(32 * I + c) * NMEM + half]);
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(64 * NW) void linattn_ctx_mfma_kernel(const float* 
     float ksum[NT];
 #pragma unroll
     for (int I = 0; I < NT; ++I) ksum[I] = 0.f;
-    if (wave == 0) {
+    if (NMEM > 0 && wave == 0) {
 #pragma unroll
         for (int j = 0; j < NMEM; j += 2) {
             float a[NT], bv[NT];
@@ -327,14 +327,28 @@ static int linear_attention_core(const float* qkv, const float* mem_kv, float* c
                                  hipStream_t s, float* kstats) {
     // waves per (image, head) by the sequence length alone, so that a sample's result does not depend on its batch
     const int nw = n >= 1024 ? 16 : n >= 256 ? 8 : 4;
+    const int nmem = mem_kv ? 4 : 0;
     const bool timed = prof::enabled();
     char name[64];
     if (timed) {
         // (n + 4) tokens x DH x DH multiply-adds per (image, head); k and v read once, the context written once
-        snprintf(name, sizeof(name), "linattn_ctx_mfma_kernel<%d,%d>", nw, DH);
-        if (prof::begin(name, 2.0 * B * heads * (n + 4.0) * DH * DH, 4.0 * B * heads * (2.0 * n * DH + DH * DH), s)) return 1;
+        if (mem_kv) snprintf(name, sizeof(name), "linattn_ctx_mfma_kernel<%d,%d>", nw, DH);
+        else snprintf(name, sizeof(name), "linattn_ctx_mfma_kernel<%d,%d,0>", nw, DH);
+        if (prof::begin(name, 2.0 * B * heads * (n + (double)nmem) * DH * DH, 4.0 * B * heads * (2.0 * n * DH + DH * DH), s))
+            return 1;
     }
-    if (nw == 16)
+    if (!mem_kv) {
+        DM_REQUIRE(n >= 1, "LinearAttention without memory key / values needs a token");
+        if (nw == 16)
+            hipLaunchKernelGGL((linattn_ctx_mfma_kernel<16, DH, 0>), dim3(heads, B), dim3(1024), 0, s, qkv, nullptr, ctx_ws,
+                               kstats, n, heads);
+        else if (nw == 8)
+            hipLaunchKernelGGL((linattn_ctx_mfma_kernel<8, DH, 0>), dim3(heads, B), dim3(512), 0, s, qkv, nullptr, ctx_ws,
+                               kstats, n, heads);
+        else
+            hipLaunchKernelGGL((linattn_ctx_mfma_kernel<4, DH, 0>), dim3(heads, B), dim3(256), 0, s, qkv, nullptr, ctx_ws,
+                               kstats, n, heads);
+    } else if (nw == 16)
         hipLaunchKernelGGL((linattn_ctx_mfma_kernel<16, DH>), dim3(heads, B), dim3(1024), 0, s, qkv, mem_kv, ctx_ws, kstats,
                            n, heads);
     else if (nw == 8)

@@ -96,6 +96,8 @@ enum PackSrcKind {
     PS_STORED,  // the parameter as stored
     PS_ROT,     // rotated / transposed rows [c_lo, c_lo + c_n) of a (sCout, sCin, sK, sK) parameter (input-gradient convolution)
     PS_S2D_T,   // Downsample input-gradient transpose of a (sCout, 4 sCin) parameter
+    PS_UP1D,    // the sequence model's Upsample packing of a (sCout, sCin, 3) parameter: the layer holds 2 sCout rows
+                // (make_upsample1d).  No device re-pack mirrors it yet: a sequence handle does not train.
 };
 struct PackSrc {
     PackSrcKind kind = PS_STORED;
@@ -261,7 +263,8 @@ struct AttnLayer {
     std::string prefix;
     bool full = false;
     int dim = 0, heads = 0;  // heads: attn_heads of the layer's stage (cast_tuple(attn_heads, num_stages), :294)
-    float *norm_g = nullptr, *mem_kv = nullptr, *out_g = nullptr;
+    int dh = 0;              // head width when it is not the handle's (the sequence model's stages: 32 whatever mid_attn has)
+    float *norm_g = nullptr, *mem_kv = nullptr, *out_g = nullptr;  // mem_kv == nullptr: no memory key / values (Unet1D)
     ConvLayer qkv, out;
     bool has_fused = false;  // LinearAttention as two fused kernels (linattn_fused.hip)
     bool has16 = false;      // full attention over 16 tokens as one kernel (attn16_fused.hip)
@@ -288,6 +291,8 @@ struct UnetGraph;   // unet_graph.inc
 }  // namespace dm
 
 using namespace dm;
+
+static_assert(DDIM_NO_CLAMP == DM_DDIM_NO_CLAMP && DDIM_RAW_NOISE == DM_DDIM_RAW_NOISE, "dm_common.h and dm_hip.h disagree");
 
 struct dm_unet {
     dm_unet_cfg cfg{};
@@ -329,6 +334,7 @@ struct dm_unet {
     enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT, GK_LV, GK_CG, GK_WO, GK_DPMPP };
     struct GraphKey {
         int kind = GK_NONE, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
+        int ddim_flags = 0;     // DM_DDIM_*: kernel arguments of the captured DDIM update
         int edm_clamp = 0;      // ElucidatedDiffusion: the clamp flag, a kernel argument of the captured Heun step
         int ct_clip = 0;        // continuous time: the clip flag of the captured ct_step
         int mask_channels = 0;  // RePaint: 1 or C
@@ -338,7 +344,7 @@ struct dm_unet {
         bool operator==(const GraphKey& o) const {
             return kind == o.kind && B == o.B && H == o.H && W == o.W && ctx_tokens == o.ctx_tokens &&
                    cond_channels == o.cond_channels && objective == o.objective && self_cond == o.self_cond &&
-                   guided == o.guided && edm_clamp == o.edm_clamp && ct_clip == o.ct_clip && mask_channels == o.mask_channels &&
+                   guided == o.guided && ddim_flags == o.ddim_flags && edm_clamp == o.edm_clamp && ct_clip == o.ct_clip && mask_channels == o.mask_channels &&
                    noise == o.noise && all_steps == o.all_steps && ws == o.ws && times == o.times && coefs == o.coefs &&
                    tab == o.tab && cg_mean == o.cg_mean && cg_grad == o.cg_grad;
         }
@@ -441,6 +447,75 @@ static void expect_cross(dm_unet* u, const std::string& p, int dim) {
 
 static std::string idx(const std::string& a, int i) { return a + "." + std::to_string(i); }
 
+// ---- Unet1D (DD/denoising_diffusion_1d.py:219-308): the same tree over nn.Conv1d, so rank-3 weights (Cout, Cin, K) and
+// gains (1, C, 1), no mem_kv, and every attention wrapped as Residual(PreNorm(dim, fn)): body `.fn.fn`, pre-norm `.fn.norm`
+enum { SEQ1D_STAGE_HEADS = 4, SEQ1D_STAGE_DH = 32 };  // LinearAttention(dim) of the stages takes its defaults (:165, :285, :300)
+static void expect_resnet1d(dm_unet* u, const std::string& p, int din, int dout) {
+    int td = u->time_dim;
+    expect(u, p + ".mlp.1.weight", {2 * dout, td});
+    expect(u, p + ".mlp.1.bias", {2 * dout});
+    expect(u, p + ".block1.proj.weight", {dout, din, 3});
+    expect(u, p + ".block1.proj.bias", {dout});
+    expect(u, p + ".block1.norm.g", {1, dout, 1});
+    expect(u, p + ".block2.proj.weight", {dout, dout, 3});
+    expect(u, p + ".block2.proj.bias", {dout});
+    expect(u, p + ".block2.norm.g", {1, dout, 1});
+    if (din != dout) {
+        expect(u, p + ".res_conv.weight", {dout, din, 1});
+        expect(u, p + ".res_conv.bias", {dout});
+    }
+}
+static void expect_attn1d(dm_unet* u, const std::string& p, int dim, bool full, int heads, int dh) {
+    const int hidden = heads * dh;
+    const std::string body = p + ".fn.fn", out = attn_out_param(body, full);
+    expect(u, body + ".to_qkv.weight", {3 * hidden, dim, 1});
+    expect(u, out + ".weight", {dim, hidden, 1});
+    expect(u, out + ".bias", {dim});
+    if (!full) expect(u, body + ".to_out.1.g", {1, dim, 1});
+    expect(u, p + ".fn.norm.g", {1, dim, 1});
+}
+// the resample layer of stage q: Downsample is a plain Conv1d(4, 2, 1) (:62-63), Upsample is Sequential(nn.Upsample, Conv1d)
+static std::string resample_param1d(const std::string& q, bool up, bool last_stage, const char* leaf) {
+    return q + (up && !last_stage ? ".3.1." : ".3.") + leaf;
+}
+static void expect_unet1d(dm_unet* u) {
+    const dm_unet_cfg& cfg = u->cfg;
+    const int n = cfg.n_stages, td = u->time_dim;
+    expect(u, "init_conv.weight", {u->init_dim, cfg.input_channels, 7});
+    expect(u, "init_conv.bias", {u->init_dim});
+    if (cfg.learned_sinusoidal_dim > 0) expect(u, "time_mlp.0.weights", {cfg.learned_sinusoidal_dim / 2});
+    expect(u, "time_mlp.1.weight", {td, cfg.learned_sinusoidal_dim > 0 ? cfg.learned_sinusoidal_dim + 1 : cfg.dim});
+    expect(u, "time_mlp.1.bias", {td});
+    expect(u, "time_mlp.3.weight", {td, td});
+    expect(u, "time_mlp.3.bias", {td});
+    for (int i = 0; i < n; ++i) {
+        const int din = u->dims[i], dout = u->dims[i + 1];
+        const std::string q = idx("downs", i);
+        const bool last = i == n - 1;
+        expect_resnet1d(u, q + ".0", din, din);
+        expect_resnet1d(u, q + ".1", din, din);
+        expect_attn1d(u, q + ".2", din, false, SEQ1D_STAGE_HEADS, SEQ1D_STAGE_DH);
+        expect(u, resample_param1d(q, false, last, "weight"), {dout, din, last ? 3 : 4});
+        expect(u, resample_param1d(q, false, last, "bias"), {dout});
+    }
+    for (int j = 0; j < n; ++j) {
+        const int din = u->dims[n - 1 - j], dout = u->dims[n - j];
+        const std::string q = idx("ups", j);
+        expect_resnet1d(u, q + ".0", dout + din, dout);
+        expect_resnet1d(u, q + ".1", dout + din, dout);
+        expect_attn1d(u, q + ".2", dout, false, SEQ1D_STAGE_HEADS, SEQ1D_STAGE_DH);
+        expect(u, resample_param1d(q, true, j == n - 1, "weight"), {din, dout, 3});
+        expect(u, resample_param1d(q, true, j == n - 1, "bias"), {din});
+    }
+    const int mid = u->dims.back();
+    expect_resnet1d(u, "mid_block1", mid, mid);
+    expect_attn1d(u, "mid_attn", mid, true, cfg.attn_heads, cfg.attn_dim_head);
+    expect_resnet1d(u, "mid_block2", mid, mid);
+    expect_resnet1d(u, "final_res_block", 2 * u->init_dim, u->init_dim);
+    expect(u, "final_conv.weight", {u->out_dim, u->init_dim, 1});
+    expect(u, "final_conv.bias", {u->out_dim});
+}
+
 #include "unet_graph.inc"
 
 // ---- weight upload ----------------------------------------------------------------------
@@ -516,6 +591,38 @@ static int make_conv(dm_unet* u, ConvLayer& L, const std::string& wname, const s
     return make_conv(u->own, L, P(u, wname).data.data(), bname.empty() ? nullptr : P(u, bname).data.data(), Cout, C0, C1, KH,
                      KW, stride, pad, up, pad_hi);
 }
+// A K-tap convolution of the handle: K x K with `pad` rows and columns, or in the sequence model 1 x K over the (B, 1, L, C)
+// view of a (B, L, C) tensor with `pad` columns.
+static int make_conv_k(dm_unet* u, ConvLayer& L, const std::string& wname, const std::string& bname, int Cout, int C0, int C1,
+                       int K, int stride, int pad) {
+    if (!u->cfg.seq1d) return make_conv(u, L, wname, bname, Cout, C0, C1, K, K, stride, pad, false);
+    if (make_conv(u, L, wname, bname, Cout, C0, C1, 1, K, stride, 0, false)) return 1;
+    L.pad_w = pad;
+    return 0;
+}
+// Upsample of the sequence model, nearest x2 then Conv1d(K = 3, padding 1) (DD/denoising_diffusion_1d.py:56-60), as ONE K = 3
+// convolution on the source grid with 2 Cout output channels: output 2i reads x[i-1], x[i], x[i] and output 2i + 1 reads
+// x[i], x[i], x[i+1], so rows [0, Cout) hold the taps {w0, w1 + w2, 0} and rows [Cout, 2 Cout) hold {0, w0 + w1, w2}, the
+// bias twice.  The (B, L, 2 Cout) result is the (B, 2L, Cout) tensor in memory.  w (Cout, Cin, 3) -> w2 (2 Cout, Cin, 3).
+static void upsample1d_pack(const float* w, const float* bias, int Cout, int Cin, std::vector<float>& w2, std::vector<float>& b2) {
+    w2.assign((size_t)2 * Cout * Cin * 3, 0.f);
+    b2.assign((size_t)2 * Cout, 0.f);
+    for (size_t oc = 0; oc < (size_t)Cout * Cin; ++oc) {
+        const float *t = w + oc * 3;
+        float* even = w2.data() + oc * 3;
+        float* odd = w2.data() + ((size_t)Cout * Cin + oc) * 3;
+        even[0] = t[0]; even[1] = t[1] + t[2]; even[2] = 0.f;
+        odd[0] = 0.f; odd[1] = t[0] + t[1]; odd[2] = t[2];
+    }
+    for (int o = 0; o < Cout; ++o) b2[o] = b2[Cout + o] = bias ? bias[o] : 0.f;
+}
+static int make_upsample1d(DeviceOwner& own, ConvLayer& L, const float* w, const float* bias, int Cout, int Cin) {
+    std::vector<float> w2, b2;
+    upsample1d_pack(w, bias, Cout, Cin, w2, b2);
+    if (make_conv(own, L, w2.data(), bias ? b2.data() : nullptr, 2 * Cout, Cin, 0, 1, 3, 1, 0, false)) return 1;
+    L.pad_w = 1;
+    return 0;
+}
 // the parameters of the resample layer of stage q: Sequential(Rearrange / Upsample, conv) in every stage but the last,
 // where it is a plain 3x3 convolution
 static std::string resample_param(const std::string& q, bool last_stage, const char* leaf) {
@@ -562,11 +669,11 @@ static int build_resnet(dm_unet* u, ResBlock& R, const std::string& p, int C0, i
     ss_off += 2 * dout;
     if (!u->own.refreshing) u->resnets.emplace_back(p, &R);
     return weight_group(u, p, [&]() -> int {
-        if (make_conv(u, R.c1, p + ".block1.proj.weight", p + ".block1.proj.bias", dout, C0, C1, 3, 3, 1, 1, false)) return 1;
-        if (make_conv(u, R.c2, p + ".block2.proj.weight", p + ".block2.proj.bias", dout, dout, 0, 3, 3, 1, 1, false)) return 1;
+        if (make_conv_k(u, R.c1, p + ".block1.proj.weight", p + ".block1.proj.bias", dout, C0, C1, 3, 1, 1)) return 1;
+        if (make_conv_k(u, R.c2, p + ".block2.proj.weight", p + ".block2.proj.bias", dout, dout, 0, 3, 1, 1)) return 1;
         if (up1(u, p + ".block1.norm.g", &R.g1) || up1(u, p + ".block2.norm.g", &R.g2)) return 1;
         R.has_res = C0 + C1 != dout;
-        return R.has_res ? make_conv(u, R.res, p + ".res_conv.weight", p + ".res_conv.bias", dout, C0, C1, 1, 1, 1, 0, false) : 0;
+        return R.has_res ? make_conv_k(u, R.res, p + ".res_conv.weight", p + ".res_conv.bias", dout, C0, C1, 1, 1, 0) : 0;
     });
 }
 
@@ -649,6 +756,25 @@ static int build_attn_body(dm_unet* u, AttnLayer& A, const std::string& p, int d
     return 0;
 }
 
+// An attention layer of the sequence model: no memory key / values, so the fused kernels (which bake the memory rows in) do
+// not apply and the layer runs as pre-norm, to_qkv, core, to_out.
+static int build_attn1d(dm_unet* u, AttnLayer& A, const std::string& p, int dim, bool full, int heads, int dh) {
+    return weight_group(u, p, [&]() -> int {
+        const std::string body = p + ".fn.fn", out = attn_out_param(body, full);
+        A.prefix = p;
+        A.full = full;
+        A.dim = dim;
+        A.heads = heads;
+        A.dh = dh;
+        A.mem_kv = nullptr;
+        A.has_fused = A.has16 = false;
+        if (up1(u, p + ".fn.norm.g", &A.norm_g)) return 1;
+        if (make_conv_k(u, A.qkv, body + ".to_qkv.weight", "", 3 * heads * dh, dim, 0, 1, 1, 0)) return 1;
+        if (make_conv_k(u, A.out, out + ".weight", out + ".bias", dim, heads * dh, 0, 1, 1, 0)) return 1;
+        return full ? 0 : up1(u, body + ".to_out.1.g", &A.out_g);
+    });
+}
+
 static int build_attn(dm_unet* u, AttnLayer& A, const std::string& p, int dim, bool full, int heads) {
     return weight_group(u, p, [&]() -> int { return build_attn_body(u, A, p, dim, full, heads); });
 }
@@ -693,8 +819,7 @@ static int build_all(dm_unet* u) {
         }))
         return 1;
     if (weight_group(u, "init_conv", [&]() -> int {
-            return make_conv(u, u->init_conv, "init_conv.weight", "init_conv.bias", u->init_dim, cfg.input_channels, 0, 7, 7, 1,
-                             3, false);
+            return make_conv_k(u, u->init_conv, "init_conv.weight", "init_conv.bias", u->init_dim, cfg.input_channels, 0, 7, 1, 3);
         }))
         return 1;
     int ss_off = 0;
@@ -706,9 +831,14 @@ static int build_all(dm_unet* u) {
         Stage& S = u->downs[i];
         if (build_resnet(u, S.b1, q + ".0", din, 0, din, ss_off)) return 1;
         if (build_resnet(u, S.b2, q + ".1", din, 0, din, ss_off)) return 1;
-        if (build_attn(u, S.attn, q + ".2", din, cfg.full_attn[i] != 0, stage_heads(cfg, i))) return 1;
+        if (cfg.seq1d ? build_attn1d(u, S.attn, q + ".2", din, false, SEQ1D_STAGE_HEADS, SEQ1D_STAGE_DH)
+                      : build_attn(u, S.attn, q + ".2", din, cfg.full_attn[i] != 0, stage_heads(cfg, i)))
+            return 1;
         if (weight_group(u, q + ".3", [&]() -> int {
                 const bool last = i == n - 1;
+                if (cfg.seq1d)  // Conv1d(4, 2, 1), or in the last stage Conv1d(3, padding 1) (:286)
+                    return make_conv_k(u, S.resample, resample_param1d(q, false, last, "weight"),
+                                       resample_param1d(q, false, last, "bias"), dout, din, 0, last ? 3 : 4, last ? 1 : 2, 1);
                 const std::string w = resample_param(q, last, "weight"), b = resample_param(q, last, "bias");
                 if (last) return make_conv(u, S.resample, w, b, dout, din, 0, 3, 3, 1, 1, false);
                 // pixel-unshuffle + 1x1  ==  2x2 stride-2 conv: W'[o][c][p1][p2] = W[o][c*4 + p1*2 + p2]
@@ -718,7 +848,9 @@ static int build_all(dm_unet* u) {
     }
     int mid = u->dims.back();
     if (build_resnet(u, u->mid1, "mid_block1", mid, 0, mid, ss_off)) return 1;
-    if (build_attn(u, u->mid_attn, "mid_attn", mid, true, stage_heads(cfg, n - 1))) return 1;
+    if (cfg.seq1d ? build_attn1d(u, u->mid_attn, "mid_attn", mid, true, cfg.attn_heads, cfg.attn_dim_head)
+                  : build_attn(u, u->mid_attn, "mid_attn", mid, true, stage_heads(cfg, n - 1)))
+        return 1;
     if (build_resnet(u, u->mid2, "mid_block2", mid, 0, mid, ss_off)) return 1;
     for (int j = 0; j < n; ++j) {
         int din = u->dims[n - 1 - j], dout = u->dims[n - j];
@@ -726,9 +858,21 @@ static int build_all(dm_unet* u) {
         Stage& S = u->ups[j];
         if (build_resnet(u, S.b1, q + ".0", dout, din, dout, ss_off)) return 1;
         if (build_resnet(u, S.b2, q + ".1", dout, din, dout, ss_off)) return 1;
-        if (build_attn(u, S.attn, q + ".2", dout, cfg.full_attn[n - 1 - j] != 0, stage_heads(cfg, n - 1 - j))) return 1;
+        if (cfg.seq1d ? build_attn1d(u, S.attn, q + ".2", dout, false, SEQ1D_STAGE_HEADS, SEQ1D_STAGE_DH)
+                      : build_attn(u, S.attn, q + ".2", dout, cfg.full_attn[n - 1 - j] != 0, stage_heads(cfg, n - 1 - j)))
+            return 1;
         if (weight_group(u, q + ".3", [&]() -> int {
                 const bool last = j == n - 1;
+                if (cfg.seq1d) {
+                    const std::string w = resample_param1d(q, true, last, "weight"), b = resample_param1d(q, true, last, "bias");
+                    if (last) return make_conv_k(u, S.resample, w, b, din, dout, 0, 3, 1, 1);
+                    S.resample.src = PackSrc();
+                    S.resample.src.kind = PS_UP1D;
+                    S.resample.src.wname = w;
+                    S.resample.src.bname = b;
+                    S.resample.src.sCout = din; S.resample.src.sCin = dout; S.resample.src.sK = 3;
+                    return make_upsample1d(u->own, S.resample, P(u, w).data.data(), P(u, b).data.data(), din, dout);
+                }
                 return make_conv(u, S.resample, resample_param(q, last, "weight"), resample_param(q, last, "bias"), din, dout, 0,
                                  3, 3, 1, 1, /*up=*/!last);
             }))
@@ -736,8 +880,7 @@ static int build_all(dm_unet* u) {
     }
     if (build_resnet(u, u->final_res, "final_res_block", u->init_dim, u->init_dim, u->init_dim, ss_off)) return 1;
     if (weight_group(u, "final_conv", [&]() -> int {
-            return make_conv(u, u->final_conv, "final_conv.weight", "final_conv.bias", u->out_dim, u->init_dim, 0, 1, 1, 1, 0,
-                             false);
+            return make_conv_k(u, u->final_conv, "final_conv.weight", "final_conv.bias", u->out_dim, u->init_dim, 0, 1, 1, 0);
         }))
         return 1;
     u->ss_total = ss_off;
@@ -1021,14 +1164,15 @@ static int attn_qkv(Ctx& c, const AttnLayer& At, const float* x, int H, int W, f
         return 1;
     return run_conv(c, At.qkv, xn, nullptr, H, W, qkv, 0, nullptr, nullptr, nullptr);
 }
+static int attn_dh(const dm_unet* u, const AttnLayer& At) { return At.dh ? At.dh : u->dh; }
 static int attn_core(Ctx& c, const AttnLayer& At, const float* qkv, int n, float* o, float* ctxws, float* kst) {
     if (c.dry()) return 0;
-    const int heads = At.heads, dh = c.u->dh, hidden = heads * dh;
+    const int heads = At.heads, dh = attn_dh(c.u, At), hidden = heads * dh;
     if (!At.full) return launch_linear_attention_core(qkv, At.mem_kv, ctxws, o, c.B, n, heads, dh, c.s, kst);
     const float* mk = At.mem_kv;
-    const float* mv = At.mem_kv + (size_t)heads * 4 * dh;
-    return launch_attention_core(qkv, 3 * hidden, qkv + hidden, qkv + 2 * hidden, 3 * hidden, mk, mv, 4, o, hidden, c.B, n, n,
-                                 heads, dh, 1.0f / sqrtf((float)dh), c.s);
+    const float* mv = At.mem_kv ? At.mem_kv + (size_t)heads * 4 * dh : nullptr;
+    return launch_attention_core(qkv, 3 * hidden, qkv + hidden, qkv + 2 * hidden, 3 * hidden, mk, mv, At.mem_kv ? 4 : 0, o, hidden,
+                                 c.B, n, n, heads, dh, 1.0f / sqrtf((float)dh), c.s);
 }
 
 // attn(x) + x  (LinearAttention DD/denoising_diffusion.py:173-193, Attention :215-229)
@@ -1036,7 +1180,7 @@ static int run_attn(Ctx& c, const AttnLayer& At, const float* x, int H, int W, f
     const int res_flag = add_x ? EPI_RESIDUAL : 0;
     const float* xres = add_x ? x : nullptr;
     dm_unet* u = c.u;
-    const int n = H * W, heads = At.heads, hidden = heads * u->dh;
+    const int n = H * W, heads = At.heads, dh = attn_dh(u, At), hidden = heads * dh;
     const size_t rows = (size_t)c.B * n;
     if (!At.full && At.has_fused) {
         float* ws = c.A->alloc(linattn_fused_ws_floats(c.B, n));
@@ -1061,7 +1205,7 @@ static int run_attn(Ctx& c, const AttnLayer& At, const float* x, int H, int W, f
         if (attn_core(c, At, qkv, n, o, nullptr, nullptr)) return 1;
         if (run_conv(c, At.out, o, nullptr, H, W, y, res_flag, nullptr, nullptr, xres)) return 1;
     } else {
-        float* ctxws = c.A->alloc((size_t)c.B * heads * u->dh * u->dh);
+        float* ctxws = c.A->alloc((size_t)c.B * heads * dh * dh);
         if (attn_core(c, At, qkv, n, o, ctxws, nullptr)) return 1;
         if (run_conv(c, At.out, o, nullptr, H, W, y, EPI_NORM | res_flag, At.out_g, nullptr, xres)) return 1;
         c.A->release(ctxws);
@@ -1252,7 +1396,8 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
         const UnetNode& N = G.nodes[k];
         const float* in0 = N.in0 >= 0 ? val[N.in0] : nullptr;
         const float* in1 = N.in1 >= 0 ? val[N.in1] : nullptr;
-        const int hi = H >> N.lin, wi = W >> N.lin, ho = H >> N.lout, wo = W >> N.lout;
+        // a sequence is a one-row image at every level
+        const int hi = cfg.seq1d ? 1 : H >> N.lin, wi = W >> N.lin, ho = cfg.seq1d ? 1 : H >> N.lout, wo = W >> N.lout;
         switch (N.kind) {
         case NODE_RESNET:
             if (run_resnet(c, N.res(), in0, in1, hi, wi, &val[N.out])) return 1;
@@ -1264,6 +1409,13 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
             if (run_cross(c, N.cross(), in0, hi, wi, ctx, ctx_tokens, &val[N.out], tmask)) return 1;
             break;
         case NODE_CONV:
+            if (cfg.seq1d) {
+                // the Upsample layer runs on the source grid with 2 Cout channels (make_upsample1d): (B, wi, 2 Cout) is
+                // (B, wo, Cout); the other resample layers compute their own output length
+                val[N.out] = A.alloc((size_t)B * (wo > wi ? wi : wo) * N.conv().Cout);
+                if (run_conv(c, N.conv(), in0, nullptr, 1, wi, val[N.out], 0, nullptr, nullptr, nullptr)) return 1;
+                break;
+            }
             val[N.out] = A.alloc((size_t)B * ho * wo * N.conv().Cout);
             // an Upsample conv sees the (virtually) upsampled tensor: it is given the output size
             if (run_conv(c, N.conv(), in0, nullptr, std::max(hi, ho), std::max(wi, wo), val[N.out], 0, nullptr, nullptr, nullptr)) return 1;
@@ -1296,6 +1448,15 @@ static int ensure_workspace(dm_unet* u, size_t bytes) {
 
 static int check_hw(dm_unet* u, int H, int W) {
     int f = 1 << (u->cfg.n_stages - 1);
+    if (u->cfg.seq1d) {
+        DM_REQUIRE(H == 1, "a sequence model takes (B, C, L) as H = 1, W = L");
+        if (W <= 0 || W % f) {
+            set_error("your sequence length (" + std::to_string(W) + ") needs to be divisible by " + std::to_string(f) +
+                      ", given the unet");
+            return 1;
+        }
+        return 0;
+    }
     if (H % f || W % f) {
         set_error("your input dimensions (" + std::to_string(H) + ", " + std::to_string(W) +
                   ") need to be divisible by " + std::to_string(f) + ", given the unet");
@@ -1339,6 +1500,12 @@ int dm_unet_create(const dm_unet_cfg* cfg, int device, dm_unet** out) {
     for (int i = 0; i < cfg->n_stages; ++i) u->dims.push_back(cfg->dim * cfg->dim_mults[i]);
     dm_unet* p = u.get();
     const int n = cfg->n_stages, td = u->time_dim;
+    if (cfg->seq1d) {
+        DM_REQUIRE(cfg->text_mode == DM_TEXT_NONE, "the sequence model (seq1d) has no text condition");
+        expect_unet1d(p);
+        *out = u.release();
+        return 0;
+    }
     expect(p, "init_conv.weight", {u->init_dim, cfg->input_channels, 7, 7});
     expect(p, "init_conv.bias", {u->init_dim});
     if (cfg->learned_sinusoidal_dim > 0) expect(p, "time_mlp.0.weights", {cfg->learned_sinusoidal_dim / 2});

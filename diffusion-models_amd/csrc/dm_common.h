@@ -295,10 +295,12 @@ int launch_pointwise_small(const float* x, const float* w_oc, const float* bias,
                            int Cout, int HW, hipStream_t s);
 
 // state_dev == nullptr: one stand-alone update (step 0 of 1, no Philox noise, no unnormalize)
+// ddim_flags of the DDIM update (DM_DDIM_* of include/dm_hip.h)
+enum { DDIM_NO_CLAMP = 1, DDIM_RAW_NOISE = 2 };
 int launch_sampler_update(int kind, const float* x, const float* eps, const float* noise, const float* coefs_dev,
                           const SamplerState* state_dev, int64_t noise_step_stride, float* out, float* all_steps,
                           float* final_out, int64_t n, hipStream_t s, int objective = 0, float* xstart_out = nullptr,
-                          float* dup_out = nullptr);
+                          float* dup_out = nullptr, int ddim_flags = 0);
 // (dup_out: a second copy of `out`, the null half of a guided step's 2B input)
 // One DPM-Solver++ (2M) update on a row of dpmpp_step_table: hist is the previous step's clamped x_0 estimate and receives
 // this step's (in place); a row with c[4] == 0 does not read it.  state_dev == nullptr: row 0, a stand-alone update.

@@ -165,7 +165,7 @@ int dm_op_block(const float* x, int Cin, const float* weight, const float* bias,
 static int attn_op(bool full, const float* x, const float* norm_g, const float* mem_kv, const float* w_qkv,
                    const float* w_out, const float* b_out, const float* out_g, float* out, int B, int C, int H,
                    int W, int heads, int dim_head, void* stream) {
-    DM_REQUIRE(x && norm_g && mem_kv && w_qkv && w_out && b_out && out, "null argument");
+    DM_REQUIRE(x && norm_g && w_qkv && w_out && b_out && out, "null argument");  // mem_kv == NULL: no memory key / values
     DM_REQUIRE(dim_head == 32 || dim_head == 64, "dim_head: the attention kernels support 32 and 64");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int hidden = heads * dim_head;
@@ -182,7 +182,7 @@ static int attn_op(bool full, const float* x, const float* norm_g, const float* 
     At.out_g = const_cast<float*>(out_g);
     if (make_conv(dummy.own, At.qkv, wq.data(), nullptr, 3 * hidden, C, 0, 1, 1, 1, 0, false)) return 1;
     if (make_conv(dummy.own, At.out, wo.data(), bo.data(), C, hidden, 0, 1, 1, 1, 0, false)) return 1;
-    if (!full) {
+    if (!full && mem_kv) {
         // the layer as the U-Net builds it: the fused kernels where they are eligible
         std::vector<float> ng, mk, og;
         if (d2h(norm_g, C, ng) || d2h(mem_kv, (size_t)2 * hidden * 4, mk) || d2h(out_g, C, og)) return 1;
@@ -280,6 +280,105 @@ int dm_op_sampler_update(int kind, int objective, const float* x, const float* e
     return table_op(c_host, 1, stream, [&](const float* cd, hipStream_t s) {
         return launch_sampler_update(kind, x, eps, noise, cd, nullptr, 0, out, nullptr, nullptr, n, s, objective, x_start);
     }, DM_COEFS);
+}
+
+int dm_op_sampler_update_ex(int kind, int objective, int ddim_flags, const float* x, const float* eps, const float* noise,
+                            const float* c_host, float* out, float* x_start, int64_t n, void* stream) {
+    DM_REQUIRE(x && eps && c_host && out, "null argument");
+    DM_REQUIRE(objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "unknown objective");
+    return table_op(c_host, 1, stream, [&](const float* cd, hipStream_t s) {
+        return launch_sampler_update(kind, x, eps, noise, cd, nullptr, 0, out, nullptr, nullptr, n, s, objective, x_start,
+                                     nullptr, ddim_flags);
+    }, DM_COEFS);
+}
+
+// a layer of the sequence model from device weights (Cout, Cin, K): 1 x K over the (B, 1, L, C) view, or the Upsample packing
+static int op_conv1d_layer(dm_unet& dummy, ConvLayer& L, const float* weight, const float* bias, int Cout, int C0, int C1, int K,
+                           int stride, int pad, int up2) {
+    std::vector<float> wh, bh;
+    if (d2h(weight, (size_t)Cout * (C0 + C1) * K, wh)) return 1;
+    if (bias && d2h(bias, Cout, bh)) return 1;
+    if (up2) {
+        DM_REQUIRE(K == 3 && stride == 1 && pad == 1 && C1 == 0, "Upsample of the sequence model is nearest x2 + Conv1d(3, padding 1)");
+        return make_upsample1d(dummy.own, L, wh.data(), bias ? bh.data() : nullptr, Cout, C0);
+    }
+    if (make_conv(dummy.own, L, wh.data(), bias ? bh.data() : nullptr, Cout, C0, C1, 1, K, stride, 0, false)) return 1;
+    L.pad_w = pad;
+    return 0;
+}
+
+int dm_op_conv1d(const float* in0, int C0, const float* in1, int C1, const float* weight, const float* bias,
+                 const float* residual, float* out, int B, int L, int Cout, int K, int stride, int pad, int up2,
+                 void* stream) {
+    DM_REQUIRE(in0 && weight && out, "null argument");
+    DM_REQUIRE(B > 0 && L > 0 && Cout > 0 && C0 > 0 && K >= 1 && (stride == 1 || stride == 2) && pad >= 0 && L + 2 * pad >= K,
+               "bad convolution shape");
+    DM_REQUIRE(!up2 || !residual, "the Upsample layer has no residual");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!in1) C1 = 0;
+    dm_unet dummy;
+    init_dummy(dummy, 4, 32);
+    ConvLayer Lc;
+    if (op_conv1d_layer(dummy, Lc, weight, bias, Cout, C0, C1, K, stride, pad, up2)) return 1;
+    const int Lo = up2 ? 2 * L : (L + 2 * pad - K) / stride + 1;
+    return run_op(s, [&](Arena& A) -> int {
+        int rc = 0;
+        Ctx c{&dummy, &A, s, B, nullptr, 0};
+        float* o = A.alloc((size_t)B * Lo * Cout);
+        if (C1 == 0 && C0 <= 8 && !residual && !up2 && stride == 1) {
+            // init_conv reads the (B, C, L) tensor as it is (unet_forward_impl): same call here
+            if (run_conv(c, Lc, in0, nullptr, 1, L, o, 0, nullptr, nullptr, nullptr, /*in_nchw=*/true)) return 1;
+            if (!A.dry && launch_nhwc_to_nchw(o, out, B, Cout, Lo, s)) return 1;
+            return 0;
+        }
+        float* a0 = to_nhwc(A, in0, B, C0, L, s, &rc);
+        float* a1 = C1 ? to_nhwc(A, in1, B, C1, L, s, &rc) : nullptr;
+        float* r = residual ? to_nhwc(A, residual, B, Cout, Lo, s, &rc) : nullptr;
+        if (rc) return 1;
+        // the Upsample layer's (B, L, 2 Cout) result is the (B, 2L, Cout) tensor
+        if (run_conv(c, Lc, a0, a1, 1, L, o, residual ? EPI_RESIDUAL : 0, nullptr, nullptr, r)) return 1;
+        if (!A.dry && launch_nhwc_to_nchw(o, out, B, Cout, Lo, s)) return 1;
+        return 0;
+    });
+}
+
+int dm_op_block1d(const float* x0, int C0, const float* x1, int C1, const float* weight, const float* bias, const float* g,
+                  const float* scale, const float* shift, const float* residual, float* out, int B, int L, int Cout,
+                  void* stream) {
+    DM_REQUIRE(x0 && weight && bias && g && out, "null argument");
+    DM_REQUIRE((scale == nullptr) == (shift == nullptr), "scale and shift come together");
+    DM_REQUIRE(B > 0 && L > 0 && Cout > 0 && C0 > 0, "bad block shape");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!x1) C1 = 0;
+    dm_unet dummy;
+    init_dummy(dummy, 4, 32);
+    ConvLayer Lc;
+    if (op_conv1d_layer(dummy, Lc, weight, bias, Cout, C0, C1, 3, 1, 1, 0)) return 1;
+    return run_op(s, [&](Arena& A) -> int {
+        int rc = 0;
+        Ctx c{&dummy, &A, s, B, nullptr, 0};
+        float* a0 = to_nhwc(A, x0, B, C0, L, s, &rc);
+        float* a1 = C1 ? to_nhwc(A, x1, B, C1, L, s, &rc) : nullptr;
+        float* r = residual ? to_nhwc(A, residual, B, Cout, L, s, &rc) : nullptr;
+        float* ss = nullptr;
+        if (scale) {
+            ss = A.alloc((size_t)B * 2 * Cout);
+            if (!A.dry) {
+                DM_CHECK_HIP(hipMemcpy2DAsync(ss, 2 * Cout * sizeof(float), scale, Cout * sizeof(float),
+                                              Cout * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+                DM_CHECK_HIP(hipMemcpy2DAsync(ss + Cout, 2 * Cout * sizeof(float), shift, Cout * sizeof(float),
+                                              Cout * sizeof(float), B, hipMemcpyDeviceToDevice, s));
+            }
+            c.ss_stride = 2 * Cout;
+        }
+        float* o = A.alloc((size_t)B * L * Cout);
+        if (rc) return 1;
+        const float* sc = scale ? (A.dry ? reinterpret_cast<const float*>(16) : ss) : nullptr;
+        const float* rr = residual ? (A.dry ? reinterpret_cast<const float*>(16) : r) : nullptr;
+        if (run_block(c, Lc, a0, a1, 1, L, g, sc, rr, o)) return 1;
+        if (!A.dry && launch_nhwc_to_nchw(o, out, B, Cout, L, s)) return 1;
+        return 0;
+    });
 }
 
 int dm_op_dpmpp_update(int objective, const float* x, const float* model_out, float* x0_hist, const float* coef_host,

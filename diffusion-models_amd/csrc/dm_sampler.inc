@@ -20,7 +20,14 @@ static int handle_ready(dm_unet* u) {
 }
 
 // the U-Net maps x to x with no text condition; text_msg: the caller's own message for the text half
+// the sequence model is pinned for dm_unet_forward and the DDPM / DDIM loop of dm_sample_ex; the other loops refuse its handle
+static int image_unet_only(dm_unet* u) {
+    DM_REQUIRE(!u->cfg.seq1d, "this loop is not available for the sequence model (seq1d): it samples through dm_sample_ex");
+    return 0;
+}
+
 static int plain_unet_ok(dm_unet* u, const char* msg, const char* text_msg = nullptr) {
+    if (image_unet_only(u)) return 1;
     DM_REQUIRE(u->cfg.text_mode == DM_TEXT_NONE, text_msg ? text_msg : msg);
     DM_REQUIRE(u->out_dim == u->cfg.channels && u->cfg.input_channels == u->cfg.channels, msg);
     return 0;
@@ -218,6 +225,7 @@ struct TableLoop {
 template <class Args>
 static int table_loop_begin(TableLoop& L, dm_unet* u, const Args& a, int n_rows, int granule, uint64_t elem_off,
                             const std::function<void(Arena&)>& layout) {
+    if (image_unet_only(u)) return 1;
     DM_CHECK_HIP(hipSetDevice(u->device));
     const int B = a.B, H = a.H, W = a.W;
     L.n = (int64_t)B * u->cfg.channels * H * W;
@@ -261,12 +269,15 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
                        const float* x_T, const float* noise, uint64_t seed, uint64_t sample_offset, const float* ctx,
                        int ctx_tokens, const float* cond, int cond_channels, float* out, float* all_steps, int B, int H,
                        int W, int unnormalize, int use_graph, void* stream, int objective = DM_OBJ_PRED_NOISE,
-                       int self_cond = 0, const CfgParams* guide = nullptr) {
+                       int self_cond = 0, const CfgParams* guide = nullptr, int ddim_flags = 0) {
     DM_REQUIRE(u && times_host && coefs_host && x_T && out, "null argument");
     if (handle_ready(u)) return 1;
     DM_REQUIRE(kind == DM_SAMPLER_DDPM || kind == DM_SAMPLER_DDIM || kind == DM_SAMPLER_DPMPP, "unknown sampler kind");
     const bool dpmpp = kind == DM_SAMPLER_DPMPP;
+    DM_REQUIRE(!(dpmpp && u->cfg.seq1d), "DPM-Solver++ is not pinned for the sequence model (seq1d) yet");
     DM_REQUIRE(n_steps > 0 && B > 0, "empty run");
+    DM_REQUIRE(ddim_flags == 0 || kind == DM_SAMPLER_DDIM, "ddim_flags belong to the DDIM loop");
+    DM_REQUIRE((ddim_flags & ~(DM_DDIM_NO_CLAMP | DM_DDIM_RAW_NOISE)) == 0, "unknown ddim_flags");
     DM_REQUIRE(u->out_dim == u->cfg.channels, "sampler needs out_dim == channels (DD/denoising_diffusion.py:456)");
     DM_REQUIRE((cond == nullptr) == (cond_channels == 0) && cond_channels >= 0, "cond and cond_channels come together");
     DM_REQUIRE(objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "unknown objective");
@@ -362,7 +373,7 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
         float* const dup = guided ? xbuf + n : nullptr;
         if (dpmpp ? launch_dpmpp_update(xbuf, eps, xstart, u->coefs_dev, u->state_dev, xbuf, all_steps, dup, n, st, objective)
                   : launch_sampler_update(kind, xbuf, eps, noise, u->coefs_dev, u->state_dev, n, xbuf, all_steps, nullptr, n, st,
-                                          objective, xstart, dup))
+                                          objective, xstart, dup, ddim_flags))
             return 1;
         return launch_step_advance(u->state_dev, st);
     };
@@ -372,6 +383,7 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
     key.kind = dpmpp ? dm_unet::GK_DPMPP : kind == DM_SAMPLER_DDPM ? dm_unet::GK_DDPM : dm_unet::GK_DDIM;
     key.B = B; key.H = H; key.W = W; key.ctx_tokens = ctx_tokens; key.cond_channels = cond_channels;
     key.objective = objective; key.self_cond = self_cond; key.guided = guided;
+    key.ddim_flags = ddim_flags;
     key.noise = noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.coefs = u->coefs_dev;
     if (run_steps(r, key, n_steps, one_step)) return 1;
     if (launch_finalize(xbuf, out, n, unnormalize, s)) return 1;  // out = x_0 [ (x + 1) / 2 ]
@@ -405,7 +417,8 @@ int dm_sample_ex(dm_unet* u, const dm_sample_args* a) {
     const CfgParams g{a->cfg_scale, a->cfg_rescaled_phi, a->cfg_keep_parallel_frac, (float)a->cfg_remove_parallel};
     return sample_impl(u, a->kind, a->n_steps, a->times_host, a->coefs_host, a->x_T, a->noise, a->seed, a->sample_offset,
                        a->ctx, a->ctx_tokens, a->cond, a->cond_channels, a->out, a->all_steps, a->B, a->H, a->W,
-                       a->unnormalize, a->use_graph, a->stream, a->objective, a->self_condition, a->cfg ? &g : nullptr);
+                       a->unnormalize, a->use_graph, a->stream, a->objective, a->self_condition, a->cfg ? &g : nullptr,
+                       a->ddim_flags);
 }
 
 }  // extern "C"

@@ -1134,6 +1134,7 @@ static int run_pack_op(dm_unet* u, TrainState& T, const PackOp& op, hipStream_t 
     }
     // the OIHW tensor the packer reads: the parameter itself, or its rotated / transposed form in T.pack_tmp
     const float* w = param(op.src.wname);
+    DM_REQUIRE(op.src.kind != PS_UP1D, "device re-pack: the sequence model's Upsample packing has no device mirror");
     if (op.src.kind == PS_ROT) {
         const size_t n = (size_t)op.src.c_n * op.src.sCout * op.src.sK * op.src.sK;
         DM_REQUIRE(n <= T.pack_tmp_floats, "device re-pack: temporary too small");
@@ -1451,6 +1452,8 @@ extern "C" {
 
 // ft: the handle is armed for float-time training (dm_unet_train_enable_ft) instead of the integer-time p_losses path
 static int train_enable_impl(dm_unet* u, bool ft) {
+    DM_REQUIRE(!u->cfg.seq1d, "training the sequence model (Unet1D: loss, backward pass, Trainer1D) is not on the HIP path yet: "
+                              "a seq1d handle serves dm_unet_forward and the sampling loops");
     DM_CHECK_HIP(hipSetDevice(u->device));
     if (u->train) {
         DM_REQUIRE(u->train->ft == ft, "the handle is already in training mode through the other entry "

@@ -545,6 +545,9 @@ int launch_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t e
 // One sampler update (elementwise, layout-agnostic).  Restates, for objective pred_noise:
 //   DDPM  DD/denoising_diffusion.py:570-574 (x0), :633 (clamp), :594-598 (posterior mean), :643-644 (ddpm_update, step_device.h)
 //   DDIM  DD/denoising_diffusion.py:607-613 (x0, clamp, re-derived eps), :686-701
+// ddim_flags (DDIM_*, kind 1 only; 0 is the loop above): the sequence class's ddim_sample calls model_predictions without
+// rederive_pred_noise and with clip_x_start = clip_denoised (DD/denoising_diffusion_1d.py:577), so DDIM_NO_CLAMP leaves
+// x_start as predicted and DDIM_RAW_NOISE takes the U-Net output itself as pred_noise under objective pred_noise.
 // Contraction is off so that the expression tree rounds exactly like the reference's tensor ops.
 // ---------------------------------------------------------------------------------------
 #pragma clang fp contract(off)
@@ -555,7 +558,8 @@ __global__ void sampler_update_kernel(int kind, int objective, const float* __re
                                       const float* __restrict__ coefs, const SamplerState* __restrict__ st,
                                       int64_t noise_step_stride, float* __restrict__ out,
                                       float* __restrict__ all_steps, float* __restrict__ final_out,
-                                      float* __restrict__ xstart_out, float* __restrict__ dup_out, int64_t n) {
+                                      float* __restrict__ xstart_out, float* __restrict__ dup_out, int64_t n,
+                                      int ddim_flags) {
     // everything that changes between two sample() calls of one shape is read from the device-side state, so a
     // captured step graph stays valid across calls (seed, Philox offset, step count, unnormalize)
     const int step = st ? st->step : 0;
@@ -584,13 +588,14 @@ __global__ void sampler_update_kernel(int kind, int objective, const float* __re
         int64_t i = i4 * 4 + j;
         if (i >= n) break;
         float xv = x[i], ev = eps[i];
-        const float x0 = ddpm_x_start(dc, objective, xv, ev);
+        const float x0 = kind != 0 && (ddim_flags & DDIM_NO_CLAMP) ? ddpm_x_start_raw(dc, objective, xv, ev)
+                                                                      : ddpm_x_start(dc, objective, xv, ev);
         if (xstart_out) xstart_out[i] = x0;
         float r;
         if (kind == 0) {
             r = ddpm_update(dc, x0, xv, flag, z[j]);
         } else {
-            float e2 = (dc.c0 * xv - x0) / dc.c1;
+            float e2 = (ddim_flags & DDIM_RAW_NOISE) && objective == 0 ? ev : (dc.c0 * xv - x0) / dc.c1;
             r = flag ? (x0 * dc.c2 + dc.c3 * e2) + dc.c4 * z[j] : x0;
         }
         out[i] = r;
@@ -650,10 +655,13 @@ int launch_finalize(const float* x, float* out, int64_t n, int unnormalize, hipS
 int launch_sampler_update(int kind, const float* x, const float* eps, const float* noise, const float* coefs_dev,
                           const SamplerState* state_dev, int64_t noise_step_stride, float* out, float* all_steps,
                           float* final_out, int64_t n, hipStream_t s, int objective, float* xstart_out,
-                          float* dup_out) {
+                          float* dup_out, int ddim_flags) {
+    DM_REQUIRE(ddim_flags == 0 || kind == 1, "ddim_flags belong to the DDIM update");
+    DM_REQUIRE((ddim_flags & ~(DDIM_NO_CLAMP | DDIM_RAW_NOISE)) == 0, "unknown ddim_flags");
     int64_t n4 = (n + 3) / 4;
     hipLaunchKernelGGL(sampler_update_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, kind, objective, x, eps, noise,
-                       coefs_dev, state_dev, noise_step_stride, out, all_steps, final_out, xstart_out, dup_out, n);
+                       coefs_dev, state_dev, noise_step_stride, out, all_steps, final_out, xstart_out, dup_out, n,
+                       ddim_flags);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -70,13 +70,17 @@ struct DdpmCoefs {
 static __device__ __forceinline__ DdpmCoefs ddpm_coefs(const float* c) { return {c[0], c[1], c[2], c[3], c[4], c[6], c[7]}; }
 
 #pragma clang fp contract(off)
-// x_start from the model output by objective (0 pred_noise, 1 pred_x0, 2 pred_v), clamped (:633)
-static __device__ __forceinline__ float ddpm_x_start(const DdpmCoefs& c, int objective, float xv, float ev) {
+// x_start from the model output by objective (0 pred_noise, 1 pred_x0, 2 pred_v), as predicted
+static __device__ __forceinline__ float ddpm_x_start_raw(const DdpmCoefs& c, int objective, float xv, float ev) {
     float x0;
     if (objective == 0) x0 = c.c0 * xv - c.c1 * ev;  // predict_start_from_noise DD/denoising_diffusion.py:570-574
     else if (objective == 1) x0 = ev;                 // the model predicts x_0 :614-617
     else x0 = c.c6 * xv - c.c7 * ev;                  // predict_start_from_v :588-592
-    return clamp1(x0);
+    return x0;
+}
+// ... and clamped (:633)
+static __device__ __forceinline__ float ddpm_x_start(const DdpmCoefs& c, int objective, float xv, float ev) {
+    return clamp1(ddpm_x_start_raw(c, objective, xv, ev));
 }
 // The DDPM update from that x_start: posterior mean (:594-598) plus the noise term (:643-644).  The noise-free row keeps
 // `c4 * 0.0f`: noise = 0. at t == 0 still meets a NaN / Inf c4, as in the reference.

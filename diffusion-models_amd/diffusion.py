@@ -206,9 +206,11 @@ class DenoisingDiffusion:
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def _run(self, kind, shape, times, coefs, takes_noise: Sequence[bool], return_all_timesteps, noise, seed,
-             text_emb=None, max_steps=None, cond=None, sample_offset=0, x_init=None, unnormalize=None, guidance=None):
+             text_emb=None, max_steps=None, cond=None, sample_offset=0, x_init=None, unnormalize=None, guidance=None,
+             ddim_flags=0):
         """guidance: None, or (cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac) of classifier-free
-        guidance (TextConditionalDenoisingDiffusion), which the library applies to the model output of every step."""
+        guidance (TextConditionalDenoisingDiffusion), which the library applies to the model output of every step.
+        ddim_flags: DM_DDIM_* of the sequence class's DDIM loop (seq1d.py); 0 is this class's loop."""
         shape = _loop.checked_shape(self, shape)
         B, _, H, W = shape
         start = _loop.loop_start(self, shape, noise, seed, sample_offset, list(takes_noise), x_init)
@@ -220,7 +222,7 @@ class DenoisingDiffusion:
             ctx, m = self.model._ctx(text_emb, B)
         a = _lib.SampleArgs()
         a.kind, a.objective, a.self_condition, a.n_steps = kind, self._objective_id, int(bool(self.self_condition)), n_steps
-        a.ctx, a.ctx_tokens = _lib.ptr(ctx), m
+        a.ctx, a.ctx_tokens, a.ddim_flags = _lib.ptr(ctx), m, int(ddim_flags)
         if cond is not None:
             cond = cond.to(self.device, torch.float32).contiguous()
             assert cond.shape[0] == B and tuple(cond.shape[2:]) == (H, W), "batch / size mismatch between x and cond"

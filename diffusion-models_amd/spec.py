@@ -579,3 +579,142 @@ def autoencoder_kl_param_spec(ecfg: EncoderConfig, dcfg: DecoderConfig, prefix: 
     q, pq = f"{prefix}quant_conv.", f"{prefix}post_quant_conv."
     return ([e for e in enc if not e[0].startswith(q)] + [e for e in dec if not e[0].startswith(pq)]
             + [e for e in enc if e[0].startswith(q)] + [e for e in dec if e[0].startswith(pq)])
+
+
+# ----------------------------------------------------------------------------
+# Unet1D: the model of sequences (B, C, L)
+# ----------------------------------------------------------------------------
+
+SEQ1D_STAGE_HEADS, SEQ1D_STAGE_DIM_HEAD = 4, 32  # LinearAttention(dim) of every stage takes its defaults (denoising_diffusion_1d.py:165)
+
+
+@dataclass(frozen=True)
+class Unet1DConfig:
+    """Constructor arguments of the reference ``Unet1D`` (denoising_diffusion_1d.py:219-236).  ``dropout`` is accepted and
+    unused at inference, as in ``UnetConfig``.  ``attn_dim_head`` / ``attn_heads`` shape ``mid_attn`` alone (:291): the
+    stages build ``LinearAttention(dim)`` with four 32-wide heads whatever they are (:285, :300)."""
+
+    dim: int = 64
+    init_dim: Optional[int] = None
+    out_dim: Optional[int] = None
+    dim_mults: Tuple[int, ...] = (1, 2, 4, 8)
+    channels: int = 3
+    dropout: float = 0.0
+    self_condition: bool = False
+    learned_variance: bool = False
+    learned_sinusoidal_cond: bool = False
+    random_fourier_features: bool = False
+    learned_sinusoidal_dim: int = 16
+    sinusoidal_pos_emb_theta: float = 10000.0
+    attn_dim_head: int = 32
+    attn_heads: int = 4
+
+    @property
+    def init_dim_(self) -> int:
+        return self.init_dim if self.init_dim is not None else self.dim
+
+    @property
+    def input_channels(self) -> int:
+        return self.channels * (2 if self.self_condition else 1)
+
+    @property
+    def out_dim_(self) -> int:
+        return self.out_dim if self.out_dim is not None else self.channels * (2 if self.learned_variance else 1)
+
+    @property
+    def time_dim(self) -> int:
+        return self.dim * 4
+
+    @property
+    def random_or_learned_sinusoidal_cond(self) -> bool:
+        return self.learned_sinusoidal_cond or self.random_fourier_features
+
+    @property
+    def fourier_dim(self) -> int:
+        return self.learned_sinusoidal_dim + 1 if self.random_or_learned_sinusoidal_cond else self.dim
+
+    @property
+    def dims(self) -> List[int]:
+        return [self.init_dim_, *[self.dim * m for m in self.dim_mults]]
+
+    @property
+    def in_out(self) -> List[Tuple[int, int]]:
+        d = self.dims
+        return list(zip(d[:-1], d[1:]))
+
+    @property
+    def num_stages(self) -> int:
+        return len(self.dim_mults)
+
+    @property
+    def downsample_factor(self) -> int:
+        return 2 ** (self.num_stages - 1)
+
+
+def _resnet1d_spec(prefix: str, din: int, dout: int, time_dim: int) -> ParamSpec:
+    s: ParamSpec = [
+        (f"{prefix}.mlp.1.weight", (dout * 2, time_dim)),
+        (f"{prefix}.mlp.1.bias", (dout * 2,)),
+        (f"{prefix}.block1.proj.weight", (dout, din, 3)),
+        (f"{prefix}.block1.proj.bias", (dout,)),
+        (f"{prefix}.block1.norm.g", (1, dout, 1)),
+        (f"{prefix}.block2.proj.weight", (dout, dout, 3)),
+        (f"{prefix}.block2.proj.bias", (dout,)),
+        (f"{prefix}.block2.norm.g", (1, dout, 1)),
+    ]
+    if din != dout:
+        s += [(f"{prefix}.res_conv.weight", (dout, din, 1)), (f"{prefix}.res_conv.bias", (dout,))]
+    return s
+
+
+def _attn1d_spec(prefix: str, dim: int, full: bool, heads: int, dim_head: int) -> ParamSpec:
+    """``Residual(PreNorm(dim, fn))`` (:37-45, :73-81): the body sits under ``.fn.fn`` and is registered before the
+    pre-norm gain ``.fn.norm.g``; no memory key / values."""
+    hidden = heads * dim_head
+    body = f"{prefix}.fn.fn"
+    s: ParamSpec = [(f"{body}.to_qkv.weight", (hidden * 3, dim, 1))]
+    if full:
+        s += [(f"{body}.to_out.weight", (dim, hidden, 1)), (f"{body}.to_out.bias", (dim,))]
+    else:
+        s += [(f"{body}.to_out.0.weight", (dim, hidden, 1)), (f"{body}.to_out.0.bias", (dim,)),
+              (f"{body}.to_out.1.g", (1, dim, 1))]
+    return s + [(f"{prefix}.fn.norm.g", (1, dim, 1))]
+
+
+def unet1d_param_spec(cfg: Unet1DConfig, prefix: str = "") -> ParamSpec:
+    """(name, shape) of every ``Unet1D`` parameter, in ``state_dict()`` order (``downs`` and ``ups`` are registered before
+    the mid blocks, :275-276)."""
+    p = prefix
+    td = cfg.time_dim
+    spec: ParamSpec = [
+        (f"{p}init_conv.weight", (cfg.init_dim_, cfg.input_channels, 7)),
+        (f"{p}init_conv.bias", (cfg.init_dim_,)),
+        *([(f"{p}time_mlp.0.weights", (cfg.learned_sinusoidal_dim // 2,))] if cfg.random_or_learned_sinusoidal_cond else []),
+        (f"{p}time_mlp.1.weight", (td, cfg.fourier_dim)),
+        (f"{p}time_mlp.1.bias", (td,)),
+        (f"{p}time_mlp.3.weight", (td, td)),
+        (f"{p}time_mlp.3.bias", (td,)),
+    ]
+    n = len(cfg.in_out)
+    h, dh = SEQ1D_STAGE_HEADS, SEQ1D_STAGE_DIM_HEAD
+    for i, (din, dout) in enumerate(cfg.in_out):
+        last = i >= n - 1
+        spec += _resnet1d_spec(f"{p}downs.{i}.0", din, din, td)
+        spec += _resnet1d_spec(f"{p}downs.{i}.1", din, din, td)
+        spec += _attn1d_spec(f"{p}downs.{i}.2", din, False, h, dh)
+        # Downsample is a plain Conv1d(4, 2, 1) (:62-63); the last stage keeps the length with Conv1d(3, padding 1)
+        spec += [(f"{p}downs.{i}.3.weight", (dout, din, 3 if last else 4)), (f"{p}downs.{i}.3.bias", (dout,))]
+    for j, (din, dout) in enumerate(reversed(cfg.in_out)):
+        last = j == n - 1
+        spec += _resnet1d_spec(f"{p}ups.{j}.0", dout + din, dout, td)
+        spec += _resnet1d_spec(f"{p}ups.{j}.1", dout + din, dout, td)
+        spec += _attn1d_spec(f"{p}ups.{j}.2", dout, False, h, dh)
+        leaf = f"{p}ups.{j}.3" if last else f"{p}ups.{j}.3.1"  # Sequential(nn.Upsample, Conv1d) in every stage but the last
+        spec += [(f"{leaf}.weight", (din, dout, 3)), (f"{leaf}.bias", (din,))]
+    mid = cfg.dims[-1]
+    spec += _resnet1d_spec(f"{p}mid_block1", mid, mid, td)
+    spec += _attn1d_spec(f"{p}mid_attn", mid, True, cfg.attn_heads, cfg.attn_dim_head)
+    spec += _resnet1d_spec(f"{p}mid_block2", mid, mid, td)
+    spec += _resnet1d_spec(f"{p}final_res_block", cfg.init_dim_ * 2, cfg.init_dim_, td)
+    spec += [(f"{p}final_conv.weight", (cfg.out_dim_, cfg.init_dim_, 1)), (f"{p}final_conv.bias", (cfg.out_dim_,))]
+    return spec

@@ -81,9 +81,23 @@ class Unet:
             text_emb_dim=text_emb_dim,
         )
         cfg = self.cfg
-        self.channels = channels
+        c = self._attach(cfg, dropout, device, text_condition=text_condition, use_cross_attn=use_cross_attn)
+        for i, f in enumerate(cfg.full_attn_):
+            c.full_attn[i] = int(f)
+        c.attn_heads, c.attn_dim_head = cfg.attn_heads_[0], cfg.attn_dim_head
+        for i, hd in enumerate(cfg.attn_heads_):
+            c.attn_heads_stage[i] = hd
+        c.text_mode = 0 if not text_condition else (2 if use_cross_attn else 1)
+        c.text_emb_dim = text_emb_dim
+        self._create(c)
+
+    def _attach(self, cfg, dropout, device, text_condition=False, use_cross_attn=False):
+        """What every handle-backed U-Net of this module holds (``Unet`` and the sequence model ``Unet1D``), and the
+        ``dm_unet_cfg`` fields the two configurations share; the caller fills in the rest and calls ``_create``."""
+        self.cfg = cfg
+        self.channels = cfg.channels
         self.dropout = float(dropout)  # nn.Dropout(p) of every Block: training mode only (eval / sampling: identity)
-        self.self_condition = self_condition
+        self.self_condition = bool(cfg.self_condition)
         self.out_dim = cfg.out_dim_
         self.text_condition = text_condition
         self.use_cross_attn = use_cross_attn
@@ -95,21 +109,16 @@ class Unet:
         self._loaded = False
         self._bucketed = False  # data-parallel gradient buckets (grad_buckets)
         self._comm_stream = None
-
         c = _lib.UnetCfg()
         c.dim, c.init_dim, c.out_dim = cfg.dim, cfg.init_dim or 0, cfg.out_dim_
         c.channels, c.input_channels, c.n_stages = cfg.channels, cfg.input_channels, cfg.num_stages
         for i, m in enumerate(cfg.dim_mults):
             c.dim_mults[i] = m
-        for i, f in enumerate(cfg.full_attn_):
-            c.full_attn[i] = int(f)
-        c.attn_heads, c.attn_dim_head = cfg.attn_heads_[0], cfg.attn_dim_head
-        for i, hd in enumerate(cfg.attn_heads_):
-            c.attn_heads_stage[i] = hd
-        c.text_mode = 0 if not text_condition else (2 if use_cross_attn else 1)
-        c.text_emb_dim = text_emb_dim
-        c.sinusoidal_theta = float(sinusoidal_pos_emb_theta)
+        c.sinusoidal_theta = float(cfg.sinusoidal_pos_emb_theta)
         c.learned_sinusoidal_dim = cfg.learned_sinusoidal_dim if cfg.random_or_learned_sinusoidal_cond else 0
+        return c
+
+    def _create(self, c):
         _lib.check(self._lib.dm_unet_create(C.byref(c), self._dev_index, C.byref(self._handle)))
 
     # -- lifecycle -------------------------------------------------------------------------

@@ -56,6 +56,13 @@ typedef struct dm_unet_cfg {
                                        dm_unet_forward only: DenoisingDiffusion refuses such a U-Net (:456-457) */
     int32_t attn_heads_stage[DM_MAX_STAGES]; /* Unet(attn_heads = (h0, h1, ..)): heads of stage i's attention (:294, :310,
                                                 :327; mid_attn takes the last stage's, :324); 0 = attn_heads */
+    int32_t seq1d; /* 0: the image U-Net above.  != 0: Unet1D (DD/denoising_diffusion_1d.py:219-349), the model of sequences
+                      (B, C, L): every entry that takes H, W is called with H = 1, W = L; the parameters have the 1D
+                      module's names and rank-3 shapes (conv weights (Cout, Cin, K), gains (1, C, 1), no mem_kv, the
+                      attention bodies under `.fn.fn`); every stage's attention is LinearAttention(heads 4, dim_head 32)
+                      and mid_attn is Attention(attn_heads, attn_dim_head) (:285, :291, :300), so full_attn and
+                      attn_heads_stage are ignored; text_mode must be DM_TEXT_NONE; inference and sampling only
+                      (dm_unet_train_enable* refuse the handle) */
 } dm_unet_cfg;
 
 typedef struct dm_unet dm_unet;
@@ -151,6 +158,13 @@ int dm_unet_forward_masked(dm_unet* u, const float* x, const int64_t* time, cons
 #define DM_SAMPLER_DDPM 0
 #define DM_SAMPLER_DDIM 1
 #define DM_SAMPLER_DPMPP 2
+/* The DDIM loop of DenoisingDiffusion1D (DD/denoising_diffusion_1d.py:562-596) calls model_predictions(img, t, self_cond,
+ * clip_x_start = clip_denoised) without rederive_pred_noise, unlike the image class (DD/denoising_diffusion.py:684):
+ *   DM_DDIM_NO_CLAMP   x_start is not clamped to [-1, 1] (clip_denoised = False)
+ *   DM_DDIM_RAW_NOISE  under DM_OBJ_PRED_NOISE the update's pred_noise is the U-Net output itself, not re-derived from the
+ *                      (clamped) x_start; the other objectives derive it from x_start either way (:515-524) */
+#define DM_DDIM_NO_CLAMP 1
+#define DM_DDIM_RAW_NOISE 2
 /* what the U-Net output means (`objective` of DenoisingDiffusion.__init__, DD/denoising_diffusion.py:443; branches of
  * model_predictions :607-624).  pred_v reads c[6]=sqrt_alphas_cumprod[t], c[7]=sqrt_one_minus_alphas_cumprod[t]
  * (predict_start_from_v :588-592) from the step table. */
@@ -196,7 +210,7 @@ typedef struct dm_sample_args {
     int32_t B, H, W;
     int32_t unnormalize;
     int32_t use_graph;
-    int32_t reserved_;
+    int32_t ddim_flags; /* DM_DDIM_*; 0 (the zero-initialised struct): the image classes' loop.  kind DM_SAMPLER_DDIM only */
     void* stream;
     /* classifier-free guidance (Unet.forward_with_cond_scale, DD/classifier_free_guidance.py:339-369); cfg == 0 (the
      * zero-initialised struct): no guidance, the other cfg_* fields are ignored.  cfg != 0: every step runs the U-Net
@@ -315,7 +329,8 @@ int dm_op_rmsnorm(const float* x, const float* g, float* out, int B, int C, int 
 /* Block.forward (DD/denoising_diffusion.py:113-122); scale/shift (B,Cout) or NULL */
 int dm_op_block(const float* x, int Cin, const float* weight, const float* bias, const float* g,
                 const float* scale, const float* shift, float* out, int B, int H, int W, int Cout, void* stream);
-/* LinearAttention.forward (DD/denoising_diffusion.py:173-193) */
+/* LinearAttention.forward (DD/denoising_diffusion.py:173-193); mem_kv == NULL: the layer without memory key / values of the
+ * sequence model (DD/denoising_diffusion_1d.py:164-215), here and in dm_op_attention */
 int dm_op_linear_attention(const float* x, const float* norm_g, const float* mem_kv, const float* w_qkv,
                            const float* w_out, const float* b_out, const float* out_g, float* out, int B, int C,
                            int H, int W, int heads, int dim_head, void* stream);
@@ -327,6 +342,22 @@ int dm_op_attention(const float* x, const float* norm_g, const float* mem_kv, co
  * floats (host); x_start (optional) receives the clamped x_0 estimate of the step (pred_x_start of model_predictions) */
 int dm_op_sampler_update(int kind, int objective, const float* x, const float* eps, const float* noise,
                          const float* c_host, float* out, float* x_start, int64_t n, void* stream);
+/* the same update with ddim_flags (DM_DDIM_*; kind DM_SAMPLER_DDIM only): 0 is dm_op_sampler_update */
+int dm_op_sampler_update_ex(int kind, int objective, int ddim_flags, const float* x, const float* eps, const float* noise,
+                            const float* c_host, float* out, float* x_start, int64_t n, void* stream);
+/* nn.Conv1d forward on (B, C, L) tensors through the layer forms of Unet1D (DD/denoising_diffusion_1d.py):
+ *   in = cat(in0, in1) along C (in1 may be NULL);  weight (Cout, C0 + C1, K);  stride 1 or 2;  residual (B, Cout, Lo) or NULL
+ *   up2: Upsample = nearest x2 + Conv1d(K = 3, padding 1) (:56-60), executed as one K = 3 convolution with 2 Cout output
+ *        channels on the source grid (even outputs: taps {w0, w1 + w2, 0}; odd outputs: {0, w0 + w1, w2}); out (B, Cout, 2L)
+ *   Lo = (L + 2 pad - K) / stride + 1 */
+int dm_op_conv1d(const float* in0, int C0, const float* in1, int C1, const float* weight, const float* bias,
+                 const float* residual, float* out, int B, int L, int Cout, int K, int stride, int pad, int up2,
+                 void* stream);
+/* Block.forward of the sequence model (DD/denoising_diffusion_1d.py:127-136) with an optional residual added behind the
+ * SiLU (ResnetBlock's `h + x`); x = cat(x0, x1); scale/shift (B, Cout) or NULL; residual (B, Cout, L) or NULL */
+int dm_op_block1d(const float* x0, int C0, const float* x1, int C1, const float* weight, const float* bias, const float* g,
+                  const float* scale, const float* shift, const float* residual, float* out, int B, int L, int Cout,
+                  void* stream);
 /* one DPM-Solver++ update (DM_SAMPLER_DPMPP) on (n) elements: coef_host is one row of DM_COEFS floats (host), x0_hist
  * (device) holds the previous step's clamped x_0 estimate and receives this step's; with c[4] == 0 it is not read */
 int dm_op_dpmpp_update(int objective, const float* x, const float* model_out, float* x0_hist, const float* coef_host,
