@@ -30,8 +30,8 @@ from .diffusion import (  # noqa: F401
 from .elucidated import (ElucidatedDiffusion, edm_dpmpp_table, edm_heun_table, edm_sigmas,  # noqa: F401
                          edm_train_table)
 from .continuous import (ContinuousTimeGaussianDiffusion, VParamContinuousTimeGaussianDiffusion,  # noqa: F401
-                         MonotonicLinear, alpha_cosine_log_snr, beta_linear_log_snr, ct_step_table, ct_train_table,
-                         learned_noise_schedule)
+                         MonotonicLinear, alpha_cosine_log_snr, beta_linear_log_snr, ct_dpmpp_nodes, ct_dpmpp_table, ct_step_table,
+                         ct_train_table, learned_noise_schedule)
 from .repaint import GaussianDiffusion as RePaintGaussianDiffusion, RepaintTable, repaint_step_table  # noqa: F401
 from .learned import LearnedGaussianDiffusion, lv_step_table, lv_train_table  # noqa: F401
 from .weighted import WeightedObjectiveGaussianDiffusion, wo_step_table, wo_train_table  # noqa: F401
@@ -93,6 +93,8 @@ __all__ = [
     "beta_linear_log_snr",
     "alpha_cosine_log_snr",
     "ct_step_table",
+    "ct_dpmpp_table",
+    "ct_dpmpp_nodes",
     "ct_train_table",
     "learned_noise_schedule",
     "MonotonicLinear",

@@ -63,6 +63,7 @@ EXPORTS = (
     "dm_op_edm_noise_in", "dm_op_edm_loss", "dm_op_sinusoid_ft_bwd",
     "dm_sample_ct", "dm_unet_loss_backward_ct", "dm_op_ct_step", "dm_op_ct_noise_in", "dm_op_ct_loss",
     "dm_unet_loss_backward_ct_ig", "dm_op_conv7_dgrad", "dm_op_sinusoid_ft_tgrad", "dm_op_ct_sched_reduce",
+    "dm_sample_ct_dpmpp", "dm_op_ct_dpmpp_step",
     "dm_unet_optimizer_step_ex",
     "dm_sample_repaint", "dm_op_repaint_step",
     "dm_sample_lv", "dm_unet_loss_backward_lv", "dm_op_lv_step", "dm_op_lv_loss",
@@ -143,6 +144,15 @@ class CtArgs(C.Structure):
         ("x_init", C.c_void_p), ("noise", C.c_void_p), ("seed", C.c_uint64), ("sample_offset", C.c_uint64),
         ("out", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("use_graph", C.c_int32),
         ("stream", C.c_void_p),
+    ]
+
+
+class CtDpmppArgs(C.Structure):
+    """dm_ct_dpmpp_args (include/dm_hip.h)."""
+    _fields_ = [
+        ("objective", C.c_int32), ("clip", C.c_int32), ("n_steps", C.c_int32), ("table_host", C.POINTER(C.c_float)),
+        ("x_init", C.c_void_p), ("out", C.c_void_p), ("x_out", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("use_graph", C.c_int32), ("stream", C.c_void_p),
     ]
 
 
@@ -390,6 +400,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_edm_loss.argtypes = [fp, fp, fp, C.POINTER(C.c_float), C.c_float, fp, fp, C.POINTER(C.c_float), i32, i64, vp]
     lib.dm_op_sinusoid_ft_bwd.argtypes = [fp, fp, fp, i32, i32, i32, i32, vp]
     lib.dm_sample_ct.argtypes = [vp, C.POINTER(CtArgs)]
+    lib.dm_sample_ct_dpmpp.argtypes = [vp, C.POINTER(CtDpmppArgs)]
+    lib.dm_op_ct_dpmpp_step.argtypes = [fp, fp, fp, C.POINTER(C.c_float), i32, i32, i32, fp, i32, i64, vp]
     lib.dm_unet_loss_backward_ct.argtypes = [vp, C.POINTER(CtTrainArgs)]
     lib.dm_op_ct_step.argtypes = [fp, fp, fp, C.POINTER(C.c_float), i32, i32, i32, u64, u64, u64, fp, fp, i32, i64, vp]
     lib.dm_op_ct_noise_in.argtypes = [fp, fp, C.POINTER(C.c_float), i32, i32, i32, fp, fp, i32, i64, vp]

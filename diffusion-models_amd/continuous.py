@@ -29,7 +29,10 @@ dL/dtime next to the loss, for any schedule.
 
 Extensions (keyword-only): ``noise`` injects a source of N(0,1) draws called in the reference's order (the start image,
 then one draw per step except the last); ``seed`` / ``sample_offset`` select the device Philox stream and the index of the
-call's first sample in a global batch.  Training: ``train()`` arms the U-Net through ``dm_unet_train_enable_ft``;
+call's first sample in a global batch.  ``dpm_solver_sample`` / ``sample(solver='dpmpp')`` is DPM-Solver++ (2M) in front of
+``dm_sample_ct_dpmpp``: the solver's lambda is ``log_snr / 2``, so its nodes are log-SNR values the U-Net is fed as they
+are, uniform in log-SNR by default (``ct_dpmpp_nodes``); its coefficients are float64 on those fp32 nodes, rounded once
+(``ct_dpmpp_table``) -- there is no reference expression to follow.  Training: ``train()`` arms the U-Net through ``dm_unet_train_enable_ft``;
 ``p_losses`` / ``forward`` are one ``dm_unet_loss_backward_ct`` call -- loss and every parameter gradient; ``times`` /
 ``noise`` inject the two draws, ``loss_scale`` / ``accumulate`` / ``sync`` are as on ``ElucidatedDiffusion.forward``.
 """
@@ -52,6 +55,8 @@ import torch.nn.functional as F
 COLS = _lib.DM_CT_COEFS
 # columns of a table row (csrc/ct.h)
 LOG_SNR, ALPHA, SIGMA, ALPHA_NEXT, C_, ONE_M_C, SQRT_VAR, AN_OVER_A, C_SIGMA, LOSS_W = range(10)
+DPM_CX, DPM_CD, DPM_G = 10, 11, 12  # rows of ct_dpmpp_table only
+SPACINGS = ("logsnr", "time")
 
 
 def _log(t, eps=1e-20):
@@ -180,6 +185,64 @@ def ct_step_table(num_sample_steps, schedule="linear") -> torch.Tensor:
     return torch.stack([ct_step_row(schedule, steps[i], steps[i + 1]) for i in range(n)])
 
 
+def ct_dpmpp_nodes(num_sample_steps, schedule="linear", spacing="logsnr", log_snr_min=None) -> torch.Tensor:
+    """The N + 1 fp32 log-SNR nodes ``l_0 < ... < l_N`` of the DPM-Solver++ loop; the U-Net is fed ``l_i`` itself.
+
+    ``spacing='logsnr'``: uniform in log-SNR (so in the solver's lambda = log_snr / 2) between the schedule's own fp32
+    ``log_snr(1.)`` and ``log_snr(0.)``, which the end nodes equal exactly; ``log_snr_min`` raises the first node to
+    ``max(log_snr(1.), log_snr_min)`` (the cosine schedule's ~ -33.9 is an fp32 rounding artefact: a floor of -12 .. -20
+    spends the steps where the signal is).  ``spacing='time'``: ``log_snr(linspace(1, 0, N + 1)[i])``, the nodes of
+    ``p_sample_loop`` -- kept for comparison; its lambda steps at both ends are many times their neighbours, which makes
+    the second-order method worse than the first up to about 40 steps (DESIGN, the grid table)."""
+    n = num_sample_steps
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"num_sample_steps must be a positive integer, got {n!r}")
+    if spacing not in SPACINGS:
+        raise ValueError(f"unknown spacing {spacing!r}: one of {SPACINGS}")
+    f = _schedule(schedule)
+    if spacing == "time":
+        steps = torch.linspace(1., 0., n + 1)
+        nodes = torch.stack([f(steps[i]).reshape(()) for i in range(n + 1)]).to(torch.float32)
+        if log_snr_min is not None:
+            raise ValueError("log_snr_min belongs to spacing='logsnr': the time grid starts at log_snr(1.)")
+    else:
+        first, last = (f(torch.tensor(t)).to(torch.float32).reshape(()) for t in (1., 0.))
+        if log_snr_min is not None:
+            first = torch.maximum(first, torch.tensor(float(log_snr_min), dtype=torch.float32))
+        nodes = torch.linspace(float(first), float(last), n + 1, dtype=torch.float64).to(torch.float32)
+        nodes[0], nodes[-1] = first, last
+    if not bool((nodes[1:] > nodes[:-1]).all()):
+        raise ValueError(f"the log-SNR nodes must increase strictly from {float(nodes[0])} to {float(nodes[-1])}"
+                         + (f" (log_snr_min = {log_snr_min})" if log_snr_min is not None else ""))
+    return nodes
+
+
+def ct_dpmpp_rows(nodes: torch.Tensor, order=2) -> torch.Tensor:
+    """(N, DM_CT_COEFS) float64 rows of DPM-Solver++ (2M; arXiv 2211.01095, Algorithm 2) on N + 1 log-SNR nodes, with
+    lambda = l / 2, alpha = sqrt(sigmoid(l)), sigma = sqrt(sigmoid(-l)), h_i = lambda_{i+1} - lambda_i:
+    ``c_x = sigma_{i+1} / sigma_i``, ``c_D = -alpha_{i+1} expm1(-h_i)``, ``g = h_i / (2 h_{i-1})`` (0 on row 0 and at
+    order 1), so that ``c_D + c_x alpha_i = alpha_{i+1}`` and ``c_x sigma_i = sigma_{i+1}``."""
+    if isinstance(order, bool) or not isinstance(order, int) or order not in (1, 2):
+        raise ValueError(f"order must be 1 or 2, got {order!r}")
+    l = nodes.detach().to("cpu", torch.float64).reshape(-1)
+    alpha, sigma = sqrt(l.sigmoid()), sqrt((-l).sigmoid())
+    h = (l[1:] - l[:-1]) / 2
+    rows = torch.zeros((l.numel() - 1, COLS), dtype=torch.float64)
+    rows[:, LOG_SNR], rows[:, ALPHA], rows[:, SIGMA] = l[:-1], alpha[:-1], sigma[:-1]
+    rows[:, DPM_CX] = sigma[1:] / sigma[:-1]
+    rows[:, DPM_CD] = -alpha[1:] * expm1(-h)
+    if order == 2:
+        rows[1:, DPM_G] = h[1:] / (2 * h[:-1])
+    return rows
+
+
+def ct_dpmpp_table(num_sample_steps, schedule="linear", order=2, spacing="logsnr", log_snr_min=None) -> torch.Tensor:
+    """(N, DM_CT_COEFS) fp32 step table of ``dpm_solver_sample`` (``dm_sample_ct_dpmpp``): the nodes of
+    ``ct_dpmpp_nodes``, every coefficient evaluated in float64 on them (``ct_dpmpp_rows``) and rounded to fp32 once;
+    the layout is documented in include/dm_hip.h."""
+    return ct_dpmpp_rows(ct_dpmpp_nodes(num_sample_steps, schedule, spacing, log_snr_min), order).to(torch.float32)
+
+
 def ct_train_table(times: torch.Tensor, schedule="linear", min_snr_loss_weight=False, min_snr_gamma=5) -> torch.Tensor:
     """(B, DM_CT_COEFS) fp32 rows of ``q_sample`` / ``p_losses`` (:222-251), one per image: log_snr, alpha, sigma as
     tensor expressions on the (B,) ``times``; column 9 the loss weight (1, or ``snr.clamp(min = gamma) / snr``)."""
@@ -300,10 +363,41 @@ class _ContinuousTimeBase(FloatTimeDiffusion):
         _lib.check(self._lib.dm_sample_ct(self.model._handle, C.byref(a)))
         return out
 
-    def sample(self, batch_size=16, *, noise=None, seed=None, sample_offset=0):
-        """:216-217."""
-        return self.p_sample_loop((batch_size, self.channels, self.image_size, self.image_size), noise=noise, seed=seed,
-                                  sample_offset=sample_offset)
+    def dpm_solver_sample(self, shape, num_sample_steps=20, order=2, *, spacing='logsnr', log_snr_min=None, noise=None,
+                          seed=None, sample_offset=0, unnormalize=True):
+        """An extension: DPM-Solver++ (2M; ``order=1``: DDIM at eta = 0) on ``num_sample_steps`` U-Net evaluations, one
+        ``dm_sample_ct_dpmpp`` call over ``ct_dpmpp_table`` (grid: ``ct_dpmpp_nodes``).  Deterministic after the start
+        image, which ``noise`` / ``seed`` / ``sample_offset`` choose exactly as in ``p_sample_loop`` (an injected
+        ``noise`` is called once).  ``unnormalize=False`` returns the final iterate as it is: no clamp, no map to [0, 1]."""
+        shape = tuple(int(v) for v in shape)
+        f = self.model.downsample_factor
+        assert shape[0] > 0 and shape[2] % f == 0 and shape[3] % f == 0, f"shape {shape}: the sides must be divisible by {f}"
+        table = ct_dpmpp_table(num_sample_steps, self.log_snr, order, spacing, log_snr_min).contiguous()
+        _, x_init, _ = self._start(shape, noise, 0, seed, sample_offset)
+        out = torch.empty(shape, device=self.device, dtype=torch.float32)
+        x_out = None if unnormalize else torch.empty_like(out)
+        a = _lib.CtDpmppArgs()
+        a.objective, a.clip = self._objective, int(bool(self.clip_sample_denoised))
+        a.n_steps, a.table_host = table.shape[0], _fptr(table)
+        a.x_init, a.out, a.x_out = _lib.ptr(x_init), _lib.ptr(out), _lib.ptr(x_out)
+        a.B, a.H, a.W = shape[0], shape[2], shape[3]
+        a.use_graph, a.stream = 1 if self.use_graph else 0, self._stream()
+        _lib.check(self._lib.dm_sample_ct_dpmpp(self.model._handle, C.byref(a)))
+        return out if unnormalize else x_out
+
+    def sample(self, batch_size=16, *, solver=None, order=2, num_sample_steps=None, spacing='logsnr', log_snr_min=None,
+               noise=None, seed=None, sample_offset=0):
+        """:216-217.  ``solver='dpmpp'`` (an extension) samples with ``dpm_solver_sample`` at ``order`` on
+        ``num_sample_steps`` steps -- 20 unless given, never the constructor's 500, which is the ancestral loop's."""
+        shape = (batch_size, self.channels, self.image_size, self.image_size)
+        if solver == "dpmpp":
+            return self.dpm_solver_sample(shape, 20 if num_sample_steps is None else num_sample_steps, order, spacing=spacing,
+                                          log_snr_min=log_snr_min, noise=noise, seed=seed, sample_offset=sample_offset)
+        if solver is not None:
+            raise ValueError(f"unknown solver {solver!r}: None (the ancestral p_sample_loop) or 'dpmpp'")
+        if num_sample_steps is not None:
+            raise ValueError("num_sample_steps= belongs to solver='dpmpp': p_sample_loop runs the object's num_sample_steps")
+        return self.p_sample_loop(shape, noise=noise, seed=seed, sample_offset=sample_offset)
 
     # -- training ----------------------------------------------------------------------------------
     def _q_sample(self, x_start, times, noise):

@@ -19,6 +19,10 @@ enum CtCol : int {
     CT_AN_OVER_A = 7,   // alpha_next / alpha   (noise objective without clipping)
     CT_C_SIGMA = 8,     // c * sigma            (noise objective without clipping)
     CT_LOSS_W = 9,      // training rows only: 1, or clamp(snr, min = gamma) / snr (min-SNR weighting)
+    // DPM-Solver++ rows only (ct_dpmpp_table: columns 0..2 as above, 3..9 zero); h = (log_snr_next - log_snr) / 2
+    CT_DPM_CX = 10,     // sigma_next / sigma
+    CT_DPM_CD = 11,     // -alpha_next * expm1(-h)
+    CT_DPM_G = 12,      // h / (2 h_last); 0 at order 1 and on the first row
     CT_NCOLS = 16,
 };
 enum CtObjective : int { CT_PRED_NOISE = 0, CT_PRED_V = 1 };
@@ -32,6 +36,12 @@ enum CtObjective : int { CT_PRED_NOISE = 0, CT_PRED_V = 1 };
 //   st->seed when noise == nullptr; a row with sqrt_var == 0 reads and draws nothing.  out may be x.
 int launch_ct_step(const float* x, const float* F, const float* noise, int64_t noise_step_stride, StepRows r, int objective,
                    int clip, float* out, float* x_start_out, int64_t n, hipStream_t s);
+// One DPM-Solver++ (2M, data prediction; arXiv 2211.01095, Algorithm 2) step on a row with columns CT_DPM_*:
+//   x_start as in launch_ct_step (v: alpha x - sigma F; noise: (x - sigma F) / alpha), clamped when clip
+//   D = x_start + g (x_start - hist)   (g == 0: hist is not read, whatever it holds);   out = c_x x + c_D D
+// hist receives x_start.  out may be x; hist aliases neither.  A thread touches its own 4 elements only.
+int launch_ct_dpmpp_step(const float* x, const float* F, float* hist, StepRows r, int objective, int clip, float* out,
+                         int64_t n, hipStream_t s);
 // q_sample + regression target: x0 = 2 img - 1 (normalize != 0) or img; x = x0 alpha_b + eps sigma_b;
 // target = eps (noise) or alpha_b eps - sigma_b x0 (v)
 int launch_ct_noise_in(const float* img, const float* eps, StepRows r, int objective, int normalize, float* x, float* target,

@@ -12,6 +12,13 @@ namespace dm {
 
 #pragma clang fp contract(off)
 
+// x_start of one element from the model output by objective (p_mean_variance of both classes), clamped when clip: the one
+// formation the ancestral step and the DPM-Solver++ step share
+static __device__ __forceinline__ float ct_x_start(int objective, int clip, float alpha, float sigma, float xv, float f) {
+    const float xs = objective == CT_PRED_V ? alpha * xv - sigma * f : (xv - sigma * f) / alpha;
+    return clip ? clamp1(xs) : xs;
+}
+
 // p_mean_variance + p_sample; out may alias x (each thread reads its 4 values before it writes them)
 __global__ __launch_bounds__(256) void ct_step_kernel(const float* x, const float* __restrict__ F,
                                                       const float* __restrict__ noise, int64_t noise_step_stride, StepRows r,
@@ -32,8 +39,7 @@ __global__ __launch_bounds__(256) void ct_step_kernel(const float* x, const floa
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            xs[j] = objective == CT_PRED_V ? alpha * xv[j] - sigma * f[j] : (xv[j] - sigma * f[j]) / alpha;
-            if (clip) xs[j] = clamp1(xs[j]);
+            xs[j] = ct_x_start(objective, clip, alpha, sigma, xv[j], f[j]);
             o[j] = alpha_next * (xv[j] * omc / alpha + cc * xs[j]);
         }
         if (x_start_out) st4(x_start_out, i, make_float4(xs[0], xs[1], xs[2], xs[3]));
@@ -44,6 +50,33 @@ __global__ __launch_bounds__(256) void ct_step_kernel(const float* x, const floa
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = o[j] + sqrt_var * z[j];
     }
+    st4(out, i, make_float4(o[0], o[1], o[2], o[3]));
+}
+
+// One DPM-Solver++ (2M) step (ct.h): hist holds the previous step's x_start and receives this step's; a thread reads and
+// writes its own elements only, so out may alias x.  A thread's 4 elements share one row (per % 4 == 0): on a row with
+// g == 0 (the first step, order 1) it never loads hist, which may be uninitialised memory there.
+__global__ __launch_bounds__(256) void ct_dpmpp_step_kernel(const float* x, const float* __restrict__ F,
+                                                            float* __restrict__ hist, StepRows r, int objective, int clip,
+                                                            float* out, int64_t n) {
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i >= n) return;
+    const float* c = step_row<CT_NCOLS>(r, i);
+    const float alpha = c[CT_ALPHA], sigma = c[CT_SIGMA], c_x = c[CT_DPM_CX], c_d = c[CT_DPM_CD], g = c[CT_DPM_G];
+    const float4 x4 = ld4(x, i), f4 = ld4(F, i);
+    const float xv[4] = {x4.x, x4.y, x4.z, x4.w}, f[4] = {f4.x, f4.y, f4.z, f4.w};
+    float xs[4], D[4], o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) D[j] = xs[j] = ct_x_start(objective, clip, alpha, sigma, xv[j], f[j]);
+    if (g != 0.0f) {
+        const float4 h4 = ld4(hist, i);
+        const float h[4] = {h4.x, h4.y, h4.z, h4.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) D[j] = xs[j] + g * (xs[j] - h[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = c_x * xv[j] + c_d * D[j];
+    st4(hist, i, make_float4(xs[0], xs[1], xs[2], xs[3]));
     st4(out, i, make_float4(o[0], o[1], o[2], o[3]));
 }
 
@@ -160,6 +193,18 @@ int launch_ct_step(const float* x, const float* F, const float* noise, int64_t n
     if (rows_ok(r, n, "null coefficient table")) return 1;
     hipLaunchKernelGGL(ct_step_kernel, grid4(n), dim3(256), 0, s, x, F, noise, noise_step_stride, r, objective, clip ? 1 : 0,
                        out, x_start_out, n);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_ct_dpmpp_step(const float* x, const float* F, float* hist, StepRows r, int objective, int clip, float* out,
+                         int64_t n, hipStream_t s) {
+    DM_REQUIRE(x && F && hist && out, "ct_dpmpp_step: null tensor (the solver needs its history buffer)");
+    DM_REQUIRE(objective == CT_PRED_NOISE || objective == CT_PRED_V, "ct_dpmpp_step: unknown objective");
+    DM_REQUIRE(hist != x && hist != out && hist != F, "ct_dpmpp_step: the history buffer aliases another tensor");
+    if (vec4_ok("continuous-time", n, {x, F, hist, out})) return 1;
+    if (rows_ok(r, n, "null coefficient table")) return 1;
+    hipLaunchKernelGGL(ct_dpmpp_step_kernel, grid4(n), dim3(256), 0, s, x, F, hist, r, objective, clip ? 1 : 0, out, n);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -331,7 +331,8 @@ struct dm_unet {
     std::vector<std::pair<std::string, ResBlock*>> resnets;  // in ss_off order
     // the instantiated graph of one denoise step, reused while the key (shape, kind, every captured pointer) holds.  The
     // slot serves every sampling loop of the handle (dm_sampler.inc: run_steps); the kind says whose graph it holds.
-    enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT, GK_LV, GK_CG, GK_WO, GK_DPMPP };
+    enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT, GK_LV, GK_CG, GK_WO, GK_DPMPP,
+                     GK_CT_DPMPP };
     struct GraphKey {
         int kind = GK_NONE, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
         int ddim_flags = 0;     // DM_DDIM_*: kernel arguments of the captured DDIM update

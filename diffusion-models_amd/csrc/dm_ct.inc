@@ -16,10 +16,28 @@ static int ct_unet_ok(dm_unet* u) {
                          "continuous-time diffusion calls model(x, log_snr) only: no text-conditional U-Net");
 }
 
+// The two loops of the continuous-time classes as one argument list: dm_ct_args, or dm_ct_dpmpp_args with dpmpp set
+// (then nothing is drawn: noise, seed and sample_offset stay 0).
+struct CtLoop {
+    int objective, clip, n_steps;
+    const float* table_host;
+    const float* x_init;
+    const float* noise;
+    uint64_t seed, sample_offset;
+    float* out;
+    float* x_out;  // DPM-Solver++ only (optional): the final iterate in front of the finalize pass
+    int B, H, W, use_graph;
+    void* stream;
+    bool dpmpp;
+};
+
 // p_sample_loop of DD/continuous_time_gaussian_diffusion.py:199-213 (and the v class, :115-129).  One step -- the forward
 // at log_snr(t_i), ct_step, the step counter -- is one linear chain that reads everything that differs between two calls
 // of one shape (table, step counter, seed, Philox offset) as device data, so it is captured once per shape.
-static int sample_ct_impl(dm_unet* u, const dm_ct_args* a) {
+// dpmpp: the DPM-Solver++ (2M) loop on a ct_dpmpp_table instead -- the same chain with ct_dpmpp_step in the place of ct_step
+// and one more buffer, the previous step's x_start, which the first row (g == 0) leaves unread.  N, order and node spacing
+// are table data, so its graph (a kind of its own) serves them all.
+static int sample_ct_impl(dm_unet* u, const CtLoop* a) {
     DM_REQUIRE(a->objective == DM_CT_PRED_NOISE || a->objective == DM_CT_PRED_V, "unknown continuous-time objective");
     DM_REQUIRE(a->table_host && a->x_init && a->out, "null argument");
     DM_REQUIRE(a->n_steps > 0 && a->B > 0, "empty run");
@@ -31,20 +49,24 @@ static int sample_ct_impl(dm_unet* u, const dm_ct_args* a) {
     const int C = u->cfg.channels;
     const int64_t per = (int64_t)C * H * W, n = (int64_t)B * per;
     DM_REQUIRE(per % 4 == 0, "C * H * W must be a multiple of 4");
+    const bool dpmpp = a->dpmpp;
     const float* noise = a->noise;
     const float* tab_host = a->table_host;
     // the noise tensor has n_steps - 1 rows: the step that would read row n_steps - 1 must be the one that adds none
     DM_REQUIRE(!noise || tab_host[(size_t)(n_steps - 1) * DM_CT_COEFS + CT_SQRT_VAR] == 0.0f,
                "with a noise tensor the last table row must have c[6] == 0 (time_next == 0 adds no noise)");
+    DM_REQUIRE(!dpmpp || tab_host[CT_DPM_G] == 0.0f,
+               "the first DPM-Solver++ row must have c[12] == 0: there is no earlier x_start to extrapolate from");
 
     SamplerRun r;
     if (grow_tables(u, TAB_FLOAT, n_steps, 1) || run_begin(r, u, a->stream, a->use_graph)) return 1;
     hipStream_t s = r.s;
-    // workspace: [x | F | forward arena]
-    float *x, *F;
+    // workspace: [x | F | forward arena], DPM-Solver++ [x | F | hist | forward arena]
+    float *x, *F, *hist;
     auto layout = [&](Arena& A) {
         x = A.alloc(n);
         F = A.alloc(n);
+        hist = dpmpp ? A.alloc(n) : nullptr;
     };
     const float* tf_marker = reinterpret_cast<const float*>(16);
     if (run_workspace(r, layout, [&](Arena& dry) {
@@ -63,16 +85,19 @@ static int sample_ct_impl(dm_unet* u, const dm_ct_args* a) {
         if (unet_forward_impl(u, r.A, x, nullptr, nullptr, u->state_dev, nullptr, 0, F, B, H, W, st, nullptr, tab + CT_LOG_SNR,
                               DM_CT_COEFS))
             return 1;
-        if (launch_ct_step(x, F, noise, n, rows, objective, clip, x, nullptr, n, st)) return 1;
+        if (dpmpp ? launch_ct_dpmpp_step(x, F, hist, rows, objective, clip, x, n, st)
+                  : launch_ct_step(x, F, noise, n, rows, objective, clip, x, nullptr, n, st))
+            return 1;
         return launch_step_advance(u->state_dev, st);
     };
     dm_unet::GraphKey key;
-    key.kind = dm_unet::GK_CT;
+    key.kind = dpmpp ? dm_unet::GK_CT_DPMPP : dm_unet::GK_CT;
     key.B = B; key.H = H; key.W = W;
     key.objective = objective;
     key.ct_clip = clip;
     key.noise = noise; key.ws = u->ws; key.tab = u->edm_tab_dev;
     if (run_steps(r, key, n_steps, step)) return 1;
+    if (a->x_out) DM_CHECK_HIP(hipMemcpyAsync(a->x_out, x, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (launch_edm_finalize(x, a->out, n, s)) return 1;
     return run_finish(r);
 }
@@ -144,7 +169,16 @@ extern "C" {
 
 int dm_sample_ct(dm_unet* u, const dm_ct_args* a) {
     DM_REQUIRE(u && a, "null argument");
-    return sample_ct_impl(u, a);
+    const CtLoop l{a->objective, a->clip, a->n_steps, a->table_host, a->x_init, a->noise, a->seed, a->sample_offset, a->out,
+                   nullptr, a->B, a->H, a->W, a->use_graph, a->stream, false};
+    return sample_ct_impl(u, &l);
+}
+
+int dm_sample_ct_dpmpp(dm_unet* u, const dm_ct_dpmpp_args* a) {
+    DM_REQUIRE(u && a, "null argument");
+    const CtLoop l{a->objective, a->clip, a->n_steps, a->table_host, a->x_init, nullptr, 0, 0, a->out,
+                   a->x_out, a->B, a->H, a->W, a->use_graph, a->stream, true};
+    return sample_ct_impl(u, &l);
 }
 
 int dm_unet_loss_backward_ct(dm_unet* u, const dm_ct_train_args* a) {
@@ -202,6 +236,16 @@ int dm_op_ct_step(const float* x, const float* F, const float* eps, const float*
                         r.st = st;
                         return launch_ct_step(x, F, eps, 0, r, objective, clip ? 1 : 0, out, x_start_out, (int64_t)B * per, s);
                     });
+}
+
+int dm_op_ct_dpmpp_step(const float* x, const float* F, float* hist, const float* c_host, int rows, int objective, int clip,
+                        float* out, int B, int64_t per, void* stream) {
+    DM_REQUIRE(x && F && hist && out, "null argument");
+    return table_op(c_host, rows, stream, [&](const float* cd, hipStream_t s) {
+        StepRows r;
+        if (edm_rows(cd, rows, B, per, &r)) return 1;
+        return launch_ct_dpmpp_step(x, F, hist, r, objective, clip ? 1 : 0, out, (int64_t)B * per, s);
+    });
 }
 
 int dm_op_ct_noise_in(const float* images, const float* eps, const float* c_host, int rows, int objective, int normalize,

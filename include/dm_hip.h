@@ -869,6 +869,37 @@ typedef struct dm_ct_args {
 } dm_ct_args;
 int dm_sample_ct(dm_unet* u, const dm_ct_args* args);
 
+/* DPM-Solver++ (2M: multistep, data prediction; arXiv 2211.01095, Algorithm 2) for the same two classes: a deterministic
+ * few-step sampler of a model trained with dm_unet_loss_backward_ct.  The solver's half-log-SNR is lambda = log_snr / 2, so
+ * the nodes l_0 > ... are log-SNR values themselves and the U-Net is fed the node; no inverse of the schedule is needed.
+ * The HOST evaluates every scalar in float64 and rounds it to fp32 once; row i of the n_steps rows (DM_CT_COEFS floats) is
+ *   c[0]=l_i   c[1]=alpha_i=sqrt(sigmoid(l_i))   c[2]=sigma_i=sqrt(sigmoid(-l_i))        (the meaning they have above)
+ *   c[10]=c_x=sigma_{i+1} / sigma_i      c[11]=c_D=-alpha_{i+1} expm1(-h)      c[12]=g=h / (2 h_{i-1})
+ *   with h = (l_{i+1} - l_i) / 2; g is 0 at order 1 and on row 0 (required); every other entry is 0.
+ * Step i runs Unet(x, c[0]) and one elementwise pass:
+ *   x_start = c[1] x - c[2] F (v) or (x - c[2] F) / c[1] (noise), clamped to [-1, 1] when clip
+ *   D = x_start + c[12] (x_start - x_start of step i - 1)      (c[12] == 0: the history is not read)
+ *   x <- c[10] x + c[11] D
+ * so c[11] + c[10] alpha_i = alpha_{i+1} and c[10] sigma_i = sigma_{i+1}: with g == 0 the step is DDIM at eta = 0.  Nothing
+ * is drawn after x_init; there is no special last row (log_snr(0) is finite, the last step lands on l_N).
+ *   out        (clamp(x, -1, 1) + 1) / 2, as dm_sample_ct;   x_out (optional): the final x in front of that pass
+ *   use_graph  one step is captured per (objective, clip, B, H, W) and serves any n_steps, order and node spacing; the
+ *              graph is a kind of its own in the handle's slot, so dm_sample_ct's is captured again when the loops alternate.
+ * The handle checks are those of dm_sample_ct (float time, no text or image condition, no sequence model). */
+typedef struct dm_ct_dpmpp_args {
+    int32_t objective;  /* DM_CT_PRED_* */
+    int32_t clip;
+    int32_t n_steps;
+    const float* table_host;
+    const float* x_init;
+    float* out;
+    float* x_out;       /* device (B,C,H,W) or NULL */
+    int32_t B, H, W;
+    int32_t use_graph;
+    void* stream;
+} dm_ct_dpmpp_args;
+int dm_sample_ct_dpmpp(dm_unet* u, const dm_ct_dpmpp_args* args);
+
 /* One p_losses (+ the normalisation of forward) and its backward pass on a handle armed by dm_unet_train_enable_ft:
  *   x0 = 2 images - 1 (normalize != 0: forward on images in [0, 1]) or images (normalize == 0: p_losses on x_start);
  *   x = x0 alpha_b + noise sigma_b;  F = Unet(x, log_snr_b);
@@ -892,13 +923,17 @@ typedef struct dm_ct_train_args {
 } dm_ct_train_args;
 int dm_unet_loss_backward_ct(dm_unet* u, const dm_ct_train_args* args);
 
-/* The three passes on their own (tests).  c_host: rows == 1 (every image) or rows == B (row b for image b) in the layout
+/* The passes on their own (tests).  c_host: rows == 1 (every image) or rows == B (row b for image b) in the layout
  * above; tensors are B * per floats, per % 4 == 0, 16-byte aligned; each call waits for its result.
  *   step:      as above on (x, F).  eps NULL: Philox draw `draw` (>= 1) under `seed`; a row with c[6] == 0 reads neither.
  *              x_start_out (optional) = x_start; it must be NULL for noise prediction without clipping.
  *   noise_in:  x0 = 2 images - 1 (normalize != 0) or images;  x = x0 c[1] + eps c[2];  target as above.
  *   loss:      c_host holds B rows.  *loss_out_host = loss_scale * mean_b(c[9] mean((F - target)^2));
- *              dF = loss_scale * c[9] * 2 (F - target) / (B * per). */
+ *              dF = loss_scale * c[9] * 2 (F - target) / (B * per).
+ *   dpmpp_step: one pass of dm_sample_ct_dpmpp on (x, F) and a row with c[10..12]: out = the new x, hist (B * per device
+ *              floats, aliasing no other tensor) = the new x_start; hist is read only where c[12] != 0. */
+int dm_op_ct_dpmpp_step(const float* x, const float* F, float* hist, const float* c_host, int rows, int objective, int clip,
+                        float* out, int B, int64_t per, void* stream);
 int dm_op_ct_step(const float* x, const float* F, const float* eps, const float* c_host, int rows, int objective, int clip,
                   uint64_t seed, uint64_t draw, uint64_t element_offset, float* out, float* x_start_out, int B, int64_t per,
                   void* stream);
