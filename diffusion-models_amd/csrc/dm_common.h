@@ -262,6 +262,11 @@ int launch_sinusoid(const int64_t* t, const int64_t* step_times, const SamplerSt
 // VAE kernels (vae_kernels.hip): MFMA flash attention of AttnBlock, coalesced GroupNorm statistics
 bool vae_attn_mfma_ok(int n, int C);
 int launch_vae_attn_mfma(const float* q, const float* k, const float* v, float* out, int B, int n, int C, hipStream_t s);
+// the same attention, one query row per wavefront: any n and C % 4 == 0 with 4 * (C + n) floats of LDS
+int launch_attention_rows(const float* q, const float* k, const float* v, float* out, int B, int n, int C, hipStream_t s);
+// nearest codebook row of every pixel: z (pixels, E) rows, or (B, E, hw) when in_nchw; e2[j] = |e[j]|^2 -> zq_nchw, idx
+int launch_vq_nearest(const float* z, const float* e, const float* e2, float* zq_nchw, int* idx, int64_t pixels, int E,
+                      int n_embed, int hw, hipStream_t s, bool in_nchw = false);
 bool group_sums_ok(int C, int groups);
 size_t group_stats_ws_floats(int B, int groups);
 int launch_group_stats_fast(const float* x, float* stats, double* acc, int B, int HW, int C, int groups, float eps,

@@ -1,6 +1,6 @@
 // Kernels of the VAE decoder / encoder (latent-diffusion/ldm/modules/diffusionmodules/model.py) that are not
-// convolutions: the single-head n x n attention of AttnBlock (:195-219) on the f32 MFMA, and GroupNorm(32, eps 1e-6)
-// statistics (:55-56).  gfx950 only.
+// convolutions: the single-head n x n attention of AttnBlock (:195-219) on the f32 MFMA or one row per wavefront, the
+// codebook search of the quantiser, and GroupNorm(32, eps 1e-6) statistics (:55-56).  gfx950 only.
 #include "conv_device.h"
 
 #include <algorithm>
@@ -172,8 +172,126 @@ int launch_vae_attn_mfma(const float* q, const float* k, const float* v, float* 
     return 0;
 }
 
+// single-head attention over n tokens of C channels (AttnBlock, model.py:203-215): one query row
+// per wavefront; keys/values stream from L2.  q,k,v,out: (B, n, C) rows.
+__global__ __launch_bounds__(256) void attention_rows_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                             const float* __restrict__ v, float* __restrict__ out,
+                                                             int n, int C, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * 4 + wave;
+    float* qs = sm + wave * (C + n);
+    float* ps = qs + C;
+    if (i >= n) return;
+    const float* qb = q + ((size_t)b * n + i) * C;
+    for (int c = lane; c < C; c += 64) qs[c] = qb[c];
+    __builtin_amdgcn_wave_barrier();
+    float mx = -INFINITY;
+    for (int j = lane; j < n; j += 64) {
+        const float* kr = k + ((size_t)b * n + j) * C;
+        float acc = 0.f;
+        for (int c = 0; c < C; c += 4) {
+            float4 kk = *reinterpret_cast<const float4*>(kr + c);
+            acc += qs[c] * kk.x + qs[c + 1] * kk.y + qs[c + 2] * kk.z + qs[c + 3] * kk.w;
+        }
+        acc *= scale;
+        ps[j] = acc;
+        mx = fmaxf(mx, acc);
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
+    float sum = 0.f;
+    for (int j = lane; j < n; j += 64) {
+        float e = __expf(ps[j] - mx);
+        ps[j] = e;
+        sum += e;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
+    __builtin_amdgcn_wave_barrier();
+    const float inv = 1.0f / sum;
+    float* ob = out + ((size_t)b * n + i) * C;
+    for (int c = lane; c < C; c += 64) {
+        float acc = 0.f;
+        const float* vb = v + (size_t)b * n * C + c;
+        for (int j = 0; j < n; ++j) acc += ps[j] * vb[(size_t)j * C];
+        ob[c] = acc * inv;
+    }
+}
+
+int launch_attention_rows(const float* q, const float* k, const float* v, float* out, int B, int n, int C, hipStream_t s) {
+    DM_REQUIRE(C % 4 == 0, "VAE attention needs C % 4 == 0");
+    size_t lds = 4 * (size_t)(C + n) * sizeof(float);
+    DM_REQUIRE(lds <= 160 * 1024, "VAE attention: too many tokens for this kernel");  // n + C <= 10240
+    static LdsOptIn lds_flag;
+    if (lds_opt_in(lds_flag, reinterpret_cast<const void*>(attention_rows_kernel), 1)) return 1;
+    hipLaunchKernelGGL(attention_rows_kernel, dim3((n + 3) / 4, B), dim3(256), lds, s, q, k, v, out, n, C,
+                       1.0f / sqrtf((float)C));
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// The codebook search of VQModel.encode (dm_vae.inc).
+// One wavefront per latent pixel: lane l scans codes l, l+64, ...; ties resolve to the lowest index (torch.argmin).
+// z: (pixels, E) rows, or (B, E, hw) NCHW when NCHW (the sampler's latents; the same arithmetic in the same order on the
+// same values); e: (n_embed, E); e2[j] = sum_c e[j][c]^2; zq_nchw (B, E, hw); idx (pixels) or nullptr.
+template <bool NCHW>
+__global__ __launch_bounds__(256) void vq_nearest_kernel(const float* __restrict__ z, const float* __restrict__ e,
+                                                         const float* __restrict__ e2, float* __restrict__ zq_nchw,
+                                                         int* __restrict__ idx, int64_t pixels, int E, int n_embed,
+                                                         int hw) {
+    const int lane = threadIdx.x & 63;
+    const int64_t pix = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pix >= pixels) return;
+    const int64_t b = pix / hw, sp = pix - b * hw;
+    const float* zr = NCHW ? z + b * E * hw + sp : z + pix * E;
+    const int64_t cs = NCHW ? hw : 1;  // distance between two channels of a pixel
+    float z2 = 0.f;
+    for (int c = 0; c < E; ++c) z2 += zr[c * cs] * zr[c * cs];
+    float best = INFINITY;
+    int bi = 0x7fffffff;
+    for (int j = lane; j < n_embed; j += 64) {
+        float dot = 0.f;
+        for (int c = 0; c < E; ++c) dot += zr[c * cs] * e[(size_t)j * E + c];
+        const float d = z2 + e2[j] - 2.0f * dot;
+        if (d < best) {
+            best = d;
+            bi = j;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ob = __shfl_xor(best, m);
+        const int oi = __shfl_xor(bi, m);
+        if (ob < best || (ob == best && oi < bi)) {
+            best = ob;
+            bi = oi;
+        }
+    }
+    for (int c = lane; c < E; c += 64) {
+        const float zv = zr[c * cs];
+        zq_nchw[(b * E + c) * hw + sp] = zv + (e[(size_t)bi * E + c] - zv);  // z + (z_q - z).detach(), as the reference forms it
+    }
+    if (idx && lane == 0) idx[pix] = bi;
+}
+
+int launch_vq_nearest(const float* z, const float* e, const float* e2, float* zq_nchw, int* idx, int64_t pixels, int E,
+                      int n_embed, int hw, hipStream_t s, bool in_nchw) {
+    DM_REQUIRE(pixels > 0 && E > 0 && n_embed > 0 && hw > 0, "VQ: empty input");
+    DM_REQUIRE(pixels % hw == 0, "VQ: pixels is a whole number of images of hw pixels");
+    DM_REQUIRE((pixels + 3) / 4 <= 0x7fffffff, "VQ: too many pixels for one launch");
+    const dim3 grid((unsigned)((pixels + 3) / 4));
+    if (in_nchw)
+        hipLaunchKernelGGL(vq_nearest_kernel<true>, grid, dim3(256), 0, s, z, e, e2, zq_nchw, idx, pixels, E, n_embed, hw);
+    else
+        hipLaunchKernelGGL(vq_nearest_kernel<false>, grid, dim3(256), 0, s, z, e, e2, zq_nchw, idx, pixels, E, n_embed, hw);
+    DM_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------
-// GroupNorm statistics, NHWC, deterministic.  Stage 1: one block per (image, slab of pixel rows) reads whole pixel rows
+// GroupNorm statistics, NHWC, deterministic. Stage 1: one block per (image, slab of pixel rows) reads whole pixel rows
 // (16 bytes per lane, coalesced), keeps per-lane channel sums in DOUBLE over its rows (x * x is exact there, so that
 // E[x^2] - mean^2 keeps ten digits where the mean is a thousand times the spread; fp32 sums lost the variance at
 // mean / std of a few hundred, tests/test_hip_vae_ops.py), folds a lane's quad, combines

@@ -17,25 +17,21 @@ from .spec import (DecoderConfig, EncoderConfig, autoencoder_kl_param_spec, deco
 from .unet import _device_index
 
 
-class VQDecoder:
-    """``vae = VQDecoder(ddconfig, embed_dim); vae.load_state_dict(vqmodel_state_dict); vae.decode(z)``.
+class _Net:
+    """What ``VQDecoder`` and ``VQEncoder`` share: one handle of libdm_hip.so, made from the ddconfig fields that both
+    networks have and filled by ``load_state_dict``.  A subclass names its cfg struct and its four library functions."""
 
-    ``load_state_dict`` takes the ``state_dict`` of the reference ``VQModel`` (or a Lightning
-    checkpoint's ``state_dict``) and uses the ``post_quant_conv.*`` and ``decoder.*`` entries."""
+    _Cfg = _create = _destroy = _set_param = _finalize = None
 
-    def __init__(self, ddconfig: Dict, embed_dim: int, device="cuda:0"):
-        self.cfg = DecoderConfig(
-            ch=ddconfig["ch"], out_ch=ddconfig["out_ch"], ch_mult=tuple(ddconfig["ch_mult"]),
-            num_res_blocks=ddconfig["num_res_blocks"], attn_resolutions=tuple(ddconfig.get("attn_resolutions", ())),
-            resolution=ddconfig["resolution"], z_channels=ddconfig["z_channels"], embed_dim=embed_dim,
-        )
-        cfg = self.cfg
+    def _open(self, cfg, device, **own):
+        """``own``: the fields of the cfg struct that only this network has."""
+        self.cfg = cfg
         self.device = torch.device(device)
         self._lib = _lib.load()
         self._handle = C.c_void_p()
         self._loaded = False
-        c = _lib.DecoderCfg()
-        c.ch, c.out_ch, c.n_levels = cfg.ch, cfg.out_ch, cfg.num_resolutions
+        c = self._Cfg()
+        c.ch, c.n_levels = cfg.ch, cfg.num_resolutions
         for i, m in enumerate(cfg.ch_mult):
             c.ch_mult[i] = m
         c.num_res_blocks = cfg.num_res_blocks
@@ -43,12 +39,14 @@ class VQDecoder:
         for i, r in enumerate(cfg.attn_resolutions):
             c.attn_resolutions[i] = r
         c.resolution, c.z_channels, c.embed_dim = cfg.resolution, cfg.z_channels, cfg.embed_dim
-        _lib.check(self._lib.dm_decoder_create(C.byref(c), _device_index(device), C.byref(self._handle)))
+        for k, v in own.items():
+            setattr(c, k, v)
+        _lib.check(getattr(self._lib, self._create)(C.byref(c), _device_index(device), C.byref(self._handle)))
 
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:
-            self._lib.dm_decoder_destroy(h)
+            getattr(self._lib, self._destroy)(h)
             h.value = None
 
     def eval(self):
@@ -57,23 +55,43 @@ class VQDecoder:
     def parameters(self):
         return iter(())
 
-    def param_spec(self):
-        return decoder_param_spec(self.cfg)
-
     def load_state_dict(self, state_dict, strict: bool = True):
         spec = dict(self.param_spec())
         missing = [k for k in spec if k not in state_dict]
         if missing:
             raise RuntimeError(f"Error(s) in loading state_dict: missing {missing[:5]}")
+        set_param = getattr(self._lib, self._set_param)
         for name, shape in spec.items():
             t = state_dict[name].detach().to(device="cpu", dtype=torch.float32).contiguous()
             if tuple(t.shape) != tuple(shape):
                 raise RuntimeError(f"size mismatch for {name}: {tuple(t.shape)} vs {tuple(shape)}")
             shp = (C.c_int64 * t.dim())(*t.shape)
-            _lib.check(self._lib.dm_decoder_set_param(self._handle, name.encode(), t.data_ptr(), shp, t.dim()))
-        _lib.check(self._lib.dm_decoder_finalize(self._handle))
+            _lib.check(set_param(self._handle, name.encode(), t.data_ptr(), shp, t.dim()))
+        _lib.check(getattr(self._lib, self._finalize)(self._handle))
         self._loaded = True
         return self
+
+
+class VQDecoder(_Net):
+    """``vae = VQDecoder(ddconfig, embed_dim); vae.load_state_dict(vqmodel_state_dict); vae.decode(z)``.
+
+    ``load_state_dict`` takes the ``state_dict`` of the reference ``VQModel`` (or a Lightning
+    checkpoint's ``state_dict``) and uses the ``post_quant_conv.*`` and ``decoder.*`` entries."""
+
+    _Cfg = _lib.DecoderCfg
+    _create, _destroy = "dm_decoder_create", "dm_decoder_destroy"
+    _set_param, _finalize = "dm_decoder_set_param", "dm_decoder_finalize"
+
+    def __init__(self, ddconfig: Dict, embed_dim: int, device="cuda:0"):
+        cfg = DecoderConfig(
+            ch=ddconfig["ch"], out_ch=ddconfig["out_ch"], ch_mult=tuple(ddconfig["ch_mult"]),
+            num_res_blocks=ddconfig["num_res_blocks"], attn_resolutions=tuple(ddconfig.get("attn_resolutions", ())),
+            resolution=ddconfig["resolution"], z_channels=ddconfig["z_channels"], embed_dim=embed_dim,
+        )
+        self._open(cfg, device, out_ch=cfg.out_ch)
+
+    def param_spec(self):
+        return decoder_param_spec(self.cfg)
 
     def decoded_shape(self, latent_chw):
         """(C, H, W) of ``decode`` for one latent of shape (embed_dim, h, w)."""
@@ -95,64 +113,26 @@ class VQDecoder:
         return out
 
 
-class VQEncoder:
+class VQEncoder(_Net):
     """Mirror of ``VQModel.encode`` / ``encode_to_prequant`` (autoencoder.py:102-111): ``Encoder`` -> ``quant_conv`` ->
     nearest-codebook quantisation, executed by ``dm_encoder_forward``.  ``load_state_dict`` takes the ``VQModel``
     state dict and uses its ``encoder.*``, ``quant_conv.*`` and ``quantize.embedding.weight`` entries."""
 
+    _Cfg = _lib.EncoderCfg
+    _create, _destroy = "dm_encoder_create", "dm_encoder_destroy"
+    _set_param, _finalize = "dm_encoder_set_param", "dm_encoder_finalize"
+
     def __init__(self, ddconfig: Dict, embed_dim: int, n_embed: int, device="cuda:0"):
-        self.cfg = EncoderConfig(
+        cfg = EncoderConfig(
             ch=ddconfig["ch"], in_channels=ddconfig.get("in_channels", 3), ch_mult=tuple(ddconfig["ch_mult"]),
             num_res_blocks=ddconfig["num_res_blocks"], attn_resolutions=tuple(ddconfig.get("attn_resolutions", ())),
             resolution=ddconfig["resolution"], z_channels=ddconfig["z_channels"], embed_dim=embed_dim, n_embed=n_embed,
             double_z=bool(ddconfig.get("double_z", False)),
         )
-        cfg = self.cfg
-        self.device = torch.device(device)
-        self._lib = _lib.load()
-        self._handle = C.c_void_p()
-        self._loaded = False
-        c = _lib.EncoderCfg()
-        c.ch, c.in_channels, c.n_levels = cfg.ch, cfg.in_channels, cfg.num_resolutions
-        for i, m in enumerate(cfg.ch_mult):
-            c.ch_mult[i] = m
-        c.num_res_blocks = cfg.num_res_blocks
-        c.n_attn_res = len(cfg.attn_resolutions)
-        for i, r in enumerate(cfg.attn_resolutions):
-            c.attn_resolutions[i] = r
-        c.resolution, c.z_channels, c.embed_dim, c.n_embed = cfg.resolution, cfg.z_channels, cfg.embed_dim, cfg.n_embed
-        c.double_z = int(cfg.double_z)
-        _lib.check(self._lib.dm_encoder_create(C.byref(c), _device_index(device), C.byref(self._handle)))
-
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            self._lib.dm_encoder_destroy(h)
-            h.value = None
-
-    def eval(self):
-        return self
-
-    def parameters(self):
-        return iter(())
+        self._open(cfg, device, in_channels=cfg.in_channels, n_embed=cfg.n_embed, double_z=int(cfg.double_z))
 
     def param_spec(self):
         return encoder_param_spec(self.cfg)
-
-    def load_state_dict(self, state_dict, strict: bool = True):
-        spec = dict(self.param_spec())
-        missing = [k for k in spec if k not in state_dict]
-        if missing:
-            raise RuntimeError(f"Error(s) in loading state_dict: missing {missing[:5]}")
-        for name, shape in spec.items():
-            t = state_dict[name].detach().to(device="cpu", dtype=torch.float32).contiguous()
-            if tuple(t.shape) != tuple(shape):
-                raise RuntimeError(f"size mismatch for {name}: {tuple(t.shape)} vs {tuple(shape)}")
-            shp = (C.c_int64 * t.dim())(*t.shape)
-            _lib.check(self._lib.dm_encoder_set_param(self._handle, name.encode(), t.data_ptr(), shp, t.dim()))
-        _lib.check(self._lib.dm_encoder_finalize(self._handle))
-        self._loaded = True
-        return self
 
     def _run(self, x, want_quant: bool):
         if not self._loaded:
@@ -332,28 +312,19 @@ class DiagonalGaussianDistribution:
         return 0.5 * torch.sum(logtwopi + self.logvar + torch.pow(sample - self.mean, 2) / self.var, dim=dims)
 
 
-class VQModel:
-    """``VQModel`` of the reference restricted to inference: ``encode`` / ``encode_to_prequant`` / ``decode`` over one
-    ``state_dict`` (autoencoder.py:14-121)."""
+class _FirstStage:
+    """What ``VQModel`` and ``AutoencoderKL`` share: an encoder and a ``VQDecoder`` over one ``state_dict``."""
 
-    def __init__(self, ddconfig: Dict, lossconfig=None, n_embed: int = None, embed_dim: int = None, ckpt_path=None,
-                 ignore_keys=(), image_key="image", colorize_nlabels=None, monitor=None, batch_resize_range=None,
-                 scheduler_config=None, lr_g_factor=1.0, remap=None, sane_index_shape=False, use_ema=False, *,
-                 device="cuda:0"):
-        """The reference's positional order (autoencoder.py:15-31: ddconfig, lossconfig, n_embed, embed_dim, ...).  The loss
-        network, the Lightning / EMA / scheduler options are training-only and ignored; ``ckpt_path`` loads the state dict
-        (``load_vae_checkpoint``: ``weights_only=True``) minus the keys that start with one of ``ignore_keys``."""
-        assert n_embed is not None and embed_dim is not None, "n_embed and embed_dim are required"
-        assert remap is None and not sane_index_shape, "remap / sane_index_shape are not on the HIP path"
+    def _open(self, encoder, ddconfig, embed_dim, device, image_key, ckpt_path, ignore_keys):
         self.image_key = image_key
-        self.encoder = VQEncoder(ddconfig, embed_dim, n_embed, device=device)
+        self.encoder = encoder
         self.decoder = VQDecoder(ddconfig, embed_dim, device=device)
         self.device = torch.device(device)
         if ckpt_path is not None:
             self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
 
     def init_from_ckpt(self, path, ignore_keys=()):
-        """autoencoder.py:78-91 through the safe loader of checkpoint.py."""
+        """autoencoder.py:78-91 / :363-372 through the safe loader of checkpoint.py."""
         from .checkpoint import load_vae_checkpoint
 
         sd = {k: v for k, v in load_vae_checkpoint(path).items() if not any(k.startswith(ik) for ik in ignore_keys)}
@@ -366,9 +337,6 @@ class VQModel:
     def parameters(self):
         return iter(())
 
-    def param_spec(self):
-        return self.encoder.param_spec() + self.decoder.param_spec()
-
     def load_state_dict(self, state_dict, strict: bool = True):
         self.encoder.load_state_dict(state_dict, strict)
         self.decoder.load_state_dict(state_dict, strict)
@@ -377,11 +345,34 @@ class VQModel:
     def encode(self, x):
         return self.encoder.encode(x)
 
-    def encode_to_prequant(self, x):
-        return self.encoder.encode_to_prequant(x)
-
     def decode(self, quant):
         return self.decoder.decode(quant)
+
+    def decoded_shape(self, latent_chw):
+        return self.decoder.decoded_shape(latent_chw)
+
+
+class VQModel(_FirstStage):
+    """``VQModel`` of the reference restricted to inference: ``encode`` / ``encode_to_prequant`` / ``decode`` over one
+    ``state_dict`` (autoencoder.py:14-121)."""
+
+    def __init__(self, ddconfig: Dict, lossconfig=None, n_embed: int = None, embed_dim: int = None, ckpt_path=None,
+                 ignore_keys=(), image_key="image", colorize_nlabels=None, monitor=None, batch_resize_range=None,
+                 scheduler_config=None, lr_g_factor=1.0, remap=None, sane_index_shape=False, use_ema=False, *,
+                 device="cuda:0"):
+        """The reference's positional order (autoencoder.py:15-31: ddconfig, lossconfig, n_embed, embed_dim, ...).  The loss
+        network, the Lightning / EMA / scheduler options are training-only and ignored; ``ckpt_path`` loads the state dict
+        (``load_vae_checkpoint``: ``weights_only=True``) minus the keys that start with one of ``ignore_keys``."""
+        assert n_embed is not None and embed_dim is not None, "n_embed and embed_dim are required"
+        assert remap is None and not sane_index_shape, "remap / sane_index_shape are not on the HIP path"
+        self._open(VQEncoder(ddconfig, embed_dim, n_embed, device=device), ddconfig, embed_dim, device, image_key, ckpt_path,
+                   ignore_keys)
+
+    def param_spec(self):
+        return self.encoder.param_spec() + self.decoder.param_spec()
+
+    def encode_to_prequant(self, x):
+        return self.encoder.encode_to_prequant(x)
 
     def decode_code(self, code_b):
         """autoencoder.py:118-121: codes (B, h, w) -> their codebook rows as a latent -> ``decode``."""
@@ -395,10 +386,6 @@ class VQModel:
         return (dec, diff, ind) if return_pred_indices else (dec, diff)
 
     __call__ = forward
-
-    def decoded_shape(self, latent_chw):
-        return self.decoder.decoded_shape(latent_chw)
-
 
 
 class VQModelInterface(VQModel):
@@ -427,7 +414,7 @@ class VQModelInterface(VQModel):
     __call__ = forward
 
 
-class AutoencoderKL:
+class AutoencoderKL(_FirstStage):
     """``AutoencoderKL`` of the reference restricted to inference (autoencoder.py:339-396): ``encode`` returns the
     posterior, ``decode`` is ``post_quant_conv`` -> ``Decoder`` (the ``VQDecoder`` of this module), ``forward`` returns
     ``(dec, posterior)``.  ``encode_sample`` is the latent in one library call, the form the latent-diffusion classes
@@ -441,41 +428,15 @@ class AutoencoderKL:
         ``weights_only=True``) minus the keys that start with one of ``ignore_keys``."""
         assert embed_dim is not None, "embed_dim is required"
         assert ddconfig["double_z"]
-        self.image_key = image_key
         self.embed_dim = embed_dim
         if monitor is not None:
             self.monitor = monitor
-        self.encoder = KLEncoder(ddconfig, embed_dim, device=device)
-        self.decoder = VQDecoder(ddconfig, embed_dim, device=device)
-        self.device = torch.device(device)
-        if ckpt_path is not None:
-            self.init_from_ckpt(ckpt_path, ignore_keys=ignore_keys)
-
-    def init_from_ckpt(self, path, ignore_keys=()):
-        """autoencoder.py:363-372 through the safe loader of checkpoint.py."""
-        from .checkpoint import load_vae_checkpoint
-
-        sd = {k: v for k, v in load_vae_checkpoint(path).items() if not any(k.startswith(ik) for ik in ignore_keys)}
-        self.load_state_dict(sd, strict=False)
-        return self
-
-    def eval(self):
-        return self
-
-    def parameters(self):
-        return iter(())
+        self._open(KLEncoder(ddconfig, embed_dim, device=device), ddconfig, embed_dim, device, image_key, ckpt_path,
+                   ignore_keys)
 
     def param_spec(self):
         """``state_dict()`` order of the reference: encoder, decoder, quant_conv, post_quant_conv."""
         return autoencoder_kl_param_spec(self.encoder.cfg, self.decoder.cfg)
-
-    def load_state_dict(self, state_dict, strict: bool = True):
-        self.encoder.load_state_dict(state_dict, strict)
-        self.decoder.load_state_dict(state_dict, strict)
-        return self
-
-    def encode(self, x):
-        return self.encoder.encode(x)
 
     def encode_sample(self, x, *, sample_posterior=True, noise=None, seed=None, return_kl=False):
         """``encode(x).sample()`` (``.mode()`` with ``sample_posterior=False``) without the round trip through the moments:
@@ -483,15 +444,9 @@ class AutoencoderKL:
         _, z, kl = self.encoder.forward_kl(x, want_z=True, want_kl=return_kl, sample=sample_posterior, noise=noise, seed=seed)
         return (z, kl) if return_kl else z
 
-    def decode(self, z):
-        return self.decoder.decode(z)
-
     def forward(self, input, sample_posterior=True):
         posterior = self.encode(input)
         z = posterior.sample() if sample_posterior else posterior.mode()
         return self.decode(z), posterior
 
     __call__ = forward
-
-    def decoded_shape(self, latent_chw):
-        return self.decoder.decoded_shape(latent_chw)

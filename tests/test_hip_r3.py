@@ -279,6 +279,26 @@ def test_vqmodel_with_groups_that_straddle_channel_quads():
     assert float((idx == widx.reshape(-1)).float().mean()) > 0.99
 
 
+def test_vqmodel_with_attention_on_two_levels_and_equal_multipliers():
+    """``ch_mult=(1, 1, 2)`` with ``attn_resolutions=(16, 8)`` and ``num_res_blocks=2``: attention blocks on two levels at
+    once, level blocks with and without ``nin_shortcut`` in one network, three blocks plus three attentions per decoder
+    level (301 parameters, 12 attention blocks, 2 shortcuts).  Decode and encode_to_prequant against the oracle."""
+    from oracle import vae_oracle as vo
+
+    common = dict(ch=32, ch_mult=(1, 1, 2), num_res_blocks=2, resolution=16, z_channels=4, embed_dim=4,
+                  attn_resolutions=(16, 8))
+    ecfg, dcfg = EncoderConfig(n_embed=256, **common), DecoderConfig(**common)
+    sd = dm.synth_state_dict(encoder_param_spec(ecfg) + dm.decoder_param_spec(dcfg), salt=59)
+    vae = dm.VQModel(dict(out_ch=3, in_channels=3, double_z=False, **{k: v for k, v in common.items() if k != "embed_dim"}),
+                     n_embed=256, embed_dim=4, device=DEV)
+    vae.load_state_dict(sd)
+    g = torch.Generator().manual_seed(4)
+    z = torch.randn((2, 4, 4, 4), generator=g)
+    img = torch.rand((2, 3, 16, 16), generator=g) * 2 - 1
+    with torch.inference_mode():
+        assert rel_l2(vae.decode(z).cpu(), vo.vq_decode(sd, dcfg, z)) < FWD_TOL
+        assert rel_l2(vae.encode_to_prequant(img).cpu(), vo.vq_encode_to_prequant(sd, ecfg, img)) < FWD_TOL
+
 
 def test_vqmodel_mid_attention_over_4096_tokens_with_32_channels():
     """A single-level VQModel (``ch_mult=(1,)``) at resolution 64 runs its mid-block attention over 64 x 64 = 4096 tokens of
