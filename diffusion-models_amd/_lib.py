@@ -70,6 +70,7 @@ EXPORTS = (
     "dm_sample_wo", "dm_unet_loss_backward_wo", "dm_op_wo_step", "dm_op_wo_loss",
     "dm_sample_classifier_guided", "dm_op_cg_mean", "dm_op_cg_finish",
     "dm_op_dpmpp_update",
+    "dm_sample_ex_dyn", "dm_op_dyn_threshold", "dm_op_sampler_update_dyn", "dm_op_dpmpp_update_dyn",
     "dm_unet_cond_forward", "dm_unet_cond_backward", "dm_op_deferred_reduce",
 )
 
@@ -116,6 +117,11 @@ class SampleArgs(C.Structure):
         ("cfg", C.c_int32), ("cfg_scale", C.c_float), ("cfg_rescaled_phi", C.c_float),
         ("cfg_keep_parallel_frac", C.c_float), ("cfg_remove_parallel", C.c_int32), ("cfg_reserved_", C.c_int32),
     ]
+
+
+class SampleDynArgs(C.Structure):
+    """dm_sample_dyn_args (include/dm_hip.h): dynamic thresholding, behind dm_sample_args in dm_sample_ex_dyn."""
+    _fields_ = [("dyn_threshold", C.c_int32), ("dyn_percentile", C.c_float)]
 
 
 class EdmArgs(C.Structure):
@@ -297,6 +303,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_sample_cond.argtypes = [vp, i32, i32, C.POINTER(i64), C.POINTER(C.c_float), fp, fp, u64, u64, fp, i32, fp,
                                    i32, fp, fp, i32, i32, i32, i32, i32, vp]
     lib.dm_sample_ex.argtypes = [vp, C.POINTER(SampleArgs)]
+    lib.dm_sample_ex_dyn.argtypes = [vp, C.POINTER(SampleArgs), C.POINTER(SampleDynArgs)]
     lib.dm_randn.argtypes = [fp, i64, u64, u64, u64, vp]
     lib.dm_decoder_create.argtypes = [C.POINTER(DecoderCfg), i32, C.POINTER(vp)]
     lib.dm_decoder_destroy.argtypes = [vp]
@@ -326,6 +333,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_conv1d.argtypes = [fp, i32, fp, i32, fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.dm_op_block1d.argtypes = [fp, i32, fp, i32, fp, fp, fp, fp, fp, fp, fp, i32, i32, i32, vp]
     lib.dm_op_dpmpp_update.argtypes = [i32, fp, fp, fp, C.POINTER(C.c_float), fp, i64, vp]
+    lib.dm_op_dyn_threshold.argtypes = [i32, fp, fp, C.POINTER(C.c_float), i32, i64, C.c_double, fp, vp]
+    lib.dm_op_sampler_update_dyn.argtypes = [i32, i32, fp, fp, fp, C.POINTER(C.c_float), fp, i32, i64, fp, fp, vp]
+    lib.dm_op_dpmpp_update_dyn.argtypes = [i32, fp, fp, fp, C.POINTER(C.c_float), fp, i32, i64, fp, vp]
     lib.dm_op_cfg_combine.argtypes = [fp, fp, fp, i32, i64, C.c_float, C.c_float, i32, C.c_float, vp]
     lib.dm_op_group_norm.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, C.c_float, i32, vp]
     lib.dm_op_vae_attention.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, vp]

@@ -91,6 +91,8 @@ class ClassifierGuidedGaussianDiffusion(DenoisingDiffusion):
         grad.copy_(g.detach().float())
         return grad
 
+    _dyn_refusal = NotImplementedError  # dynamic_threshold: this class's loop has its own update kernel
+
     # -- the loop -----------------------------------------------------------------------------------------------------------
     def p_sample_loop(self, shape, return_all_timesteps=False, cond_fn=None, guidance_kwargs=None, *, noise=None, seed=None,
                       sample_offset=0, **kw):
@@ -98,6 +100,7 @@ class ClassifierGuidedGaussianDiffusion(DenoisingDiffusion):
         ``shape -> cpu tensor``) is called in the reference's draw order: x_T, then one per step with t > 0.  ``cond_fn``
         receives the (B, C, H, W) fp32 device mean and ``t`` as a (B,) int64 device tensor; both are reused by every step,
         so a ``cond_fn`` that keeps them clones them."""
+        self._dyn(kw.get("dynamic_threshold"))
         if cond_fn is None or guidance_kwargs is None:
             return super().p_sample_loop(shape, return_all_timesteps, noise=noise, seed=seed, sample_offset=sample_offset, **kw)
         if kw:

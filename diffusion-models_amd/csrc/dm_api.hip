@@ -336,6 +336,7 @@ struct dm_unet {
     struct GraphKey {
         int kind = GK_NONE, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
         int ddim_flags = 0;     // DM_DDIM_*: kernel arguments of the captured DDIM update
+        int dyn = 0;            // dynamic thresholding: one more kernel in the captured step (the percentile is device data)
         int edm_clamp = 0;      // ElucidatedDiffusion: the clamp flag, a kernel argument of the captured Heun step
         int ct_clip = 0;        // continuous time: the clip flag of the captured ct_step
         int mask_channels = 0;  // RePaint: 1 or C
@@ -345,7 +346,7 @@ struct dm_unet {
         bool operator==(const GraphKey& o) const {
             return kind == o.kind && B == o.B && H == o.H && W == o.W && ctx_tokens == o.ctx_tokens &&
                    cond_channels == o.cond_channels && objective == o.objective && self_cond == o.self_cond &&
-                   guided == o.guided && ddim_flags == o.ddim_flags && edm_clamp == o.edm_clamp && ct_clip == o.ct_clip && mask_channels == o.mask_channels &&
+                   guided == o.guided && ddim_flags == o.ddim_flags && dyn == o.dyn && edm_clamp == o.edm_clamp && ct_clip == o.ct_clip && mask_channels == o.mask_channels &&
                    noise == o.noise && all_steps == o.all_steps && ws == o.ws && times == o.times && coefs == o.coefs &&
                    tab == o.tab && cg_mean == o.cg_mean && cg_grad == o.cg_grad;
         }

@@ -305,13 +305,29 @@ enum { DDIM_NO_CLAMP = 1, DDIM_RAW_NOISE = 2 };
 int launch_sampler_update(int kind, const float* x, const float* eps, const float* noise, const float* coefs_dev,
                           const SamplerState* state_dev, int64_t noise_step_stride, float* out, float* all_steps,
                           float* final_out, int64_t n, hipStream_t s, int objective = 0, float* xstart_out = nullptr,
-                          float* dup_out = nullptr, int ddim_flags = 0);
+                          float* dup_out = nullptr, int ddim_flags = 0, const float* dyn_s = nullptr, int64_t per = 0);
 // (dup_out: a second copy of `out`, the null half of a guided step's 2B input)
+// (dyn_s: the dynamic threshold of every image, n / per floats written by launch_dyn_threshold: x_start is
+//  clamp(raw, -s_b, s_b) / s_b in place of clamp(raw, -1, 1); nullptr: the static clamp.  Not combined with ddim_flags.)
 // One DPM-Solver++ (2M) update on a row of dpmpp_step_table: hist is the previous step's clamped x_0 estimate and receives
 // this step's (in place); a row with c[4] == 0 does not read it.  state_dev == nullptr: row 0, a stand-alone update.
 int launch_dpmpp_update(const float* x, const float* model_out, float* hist, const float* coefs_dev,
                         const SamplerState* state_dev, float* out, float* all_steps, float* dup_out, int64_t n, hipStream_t s,
-                        int objective = 0);
+                        int objective = 0, const float* dyn_s = nullptr, int64_t per = 0);
+// Dynamic thresholding (dynthresh.hip; Imagen, arXiv 2205.11487, section 2.3).  The rank and the interpolation weight of
+// the quantile, formed on the host in float64 for one image size: pos = p (per - 1), lo = floor(pos), frac = pos - lo.
+// Device data of the captured step, like CfgParams: a graph of one shape serves any percentile.  on == 0: s[b] = 1.
+struct DynParams {
+    int32_t on, lo;
+    float frac;
+    int32_t pad_;
+};
+DynParams dyn_params(double percentile, int64_t per);
+// s[b] = max(1, quantile_p(|x_start_raw| over image b)) for B images of `per` values; x_start_raw from x, the model output
+// and the coefficient row of state_dev->step (row 0 without a state), as the update kernels form it.  params_dev overrides `p`.
+int launch_dyn_threshold(int objective, const float* x, const float* model_out, const float* coefs_dev,
+                         const SamplerState* state_dev, const DynParams* params_dev, DynParams p, int B, int64_t per,
+                         float* s_out, hipStream_t s);
 // element e of the tensor uses Philox counter ((element_offset + e) / 4, draw); element_offset % 4 == 0
 int launch_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t element_offset, hipStream_t s);
 int launch_step_advance(SamplerState* state_dev, hipStream_t s);

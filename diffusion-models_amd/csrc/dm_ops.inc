@@ -391,6 +391,42 @@ int dm_op_dpmpp_update(int objective, const float* x, const float* model_out, fl
     }, DM_COEFS);
 }
 
+int dm_op_dyn_threshold(int objective, const float* x, const float* model_out, const float* c_host, int B, int64_t per,
+                        double percentile, float* s_out, void* stream) {
+    DM_REQUIRE(x && model_out && c_host && s_out, "null argument");
+    DM_REQUIRE(B > 0 && per > 0, "empty tensor");
+    DM_REQUIRE(objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "unknown objective");
+    DM_REQUIRE(percentile > 0.0 && percentile <= 1.0, "the percentile of dynamic thresholding lies in (0, 1]");
+    return table_op(c_host, 1, stream, [&](const float* cd, hipStream_t s) {
+        return launch_dyn_threshold(objective, x, model_out, cd, nullptr, nullptr, dyn_params(percentile, per), B, per, s_out, s);
+    }, DM_COEFS);
+}
+
+int dm_op_sampler_update_dyn(int kind, int objective, const float* x, const float* eps, const float* noise,
+                             const float* c_host, const float* s, int B, int64_t per, float* out, float* x_start,
+                             void* stream) {
+    DM_REQUIRE(x && eps && c_host && s && out, "null argument");
+    DM_REQUIRE(B > 0 && per > 0, "empty tensor");
+    DM_REQUIRE(kind == DM_SAMPLER_DDPM || kind == DM_SAMPLER_DDIM, "the update of the DDPM or the DDIM loop");
+    DM_REQUIRE(objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "unknown objective");
+    const int64_t n = (int64_t)B * per;
+    return table_op(c_host, 1, stream, [&](const float* cd, hipStream_t st) {
+        return launch_sampler_update(kind, x, eps, noise, cd, nullptr, 0, out, nullptr, nullptr, n, st, objective, x_start,
+                                     nullptr, 0, s, per);
+    }, DM_COEFS);
+}
+
+int dm_op_dpmpp_update_dyn(int objective, const float* x, const float* model_out, float* x0_hist, const float* coef_host,
+                           const float* s, int B, int64_t per, float* out, void* stream) {
+    DM_REQUIRE(x && model_out && x0_hist && coef_host && s && out, "null argument");
+    DM_REQUIRE(B > 0 && per > 0, "empty tensor");
+    DM_REQUIRE(objective >= DM_OBJ_PRED_NOISE && objective <= DM_OBJ_PRED_V, "unknown objective");
+    const int64_t n = (int64_t)B * per;
+    return table_op(coef_host, 1, stream, [&](const float* cd, hipStream_t st) {
+        return launch_dpmpp_update(x, model_out, x0_hist, cd, nullptr, out, nullptr, nullptr, n, st, objective, s, per);
+    }, DM_COEFS);
+}
+
 int dm_op_cfg_combine(const float* cond, const float* null_out, float* out, int B, int64_t per_sample, float cond_scale,
                       float rescaled_phi, int remove_parallel_component, float keep_parallel_frac, void* stream) {
     DM_REQUIRE(cond && null_out && out, "null argument");

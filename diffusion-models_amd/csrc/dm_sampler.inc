@@ -269,7 +269,8 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
                        const float* x_T, const float* noise, uint64_t seed, uint64_t sample_offset, const float* ctx,
                        int ctx_tokens, const float* cond, int cond_channels, float* out, float* all_steps, int B, int H,
                        int W, int unnormalize, int use_graph, void* stream, int objective = DM_OBJ_PRED_NOISE,
-                       int self_cond = 0, const CfgParams* guide = nullptr, int ddim_flags = 0) {
+                       int self_cond = 0, const CfgParams* guide = nullptr, int ddim_flags = 0,
+                       const dm_sample_dyn_args* dyn_args = nullptr) {
     DM_REQUIRE(u && times_host && coefs_host && x_T && out, "null argument");
     if (handle_ready(u)) return 1;
     DM_REQUIRE(kind == DM_SAMPLER_DDPM || kind == DM_SAMPLER_DDIM || kind == DM_SAMPLER_DPMPP, "unknown sampler kind");
@@ -294,6 +295,14 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
         DM_REQUIRE(!self_cond, "classifier-free guidance is not combined with self-conditioning");
         DM_REQUIRE(cond == nullptr, "classifier-free guidance is not combined with an image condition");
     }
+    // dynamic thresholding: one select per step between the model output and the update, which then reads s[b]
+    const bool dyn = dyn_args && dyn_args->dyn_threshold != 0;
+    if (dyn) {
+        DM_REQUIRE(dyn_args->dyn_percentile > 0.0f && dyn_args->dyn_percentile <= 1.0f,
+                   "the percentile of dynamic thresholding lies in (0, 1]");
+        DM_REQUIRE(!u->cfg.seq1d, "dynamic thresholding is not available for the sequence model (seq1d)");
+        DM_REQUIRE(ddim_flags == 0, "dynamic thresholding is not combined with ddim_flags");
+    }
     const int Bf = guided ? 2 * B : B;  // batch of the U-Net forward
     if (check_hw(u, H, W)) return 1;
     DM_CHECK_HIP(hipSetDevice(u->device));
@@ -311,9 +320,10 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
     if (grow_tables(u, TAB_INT, n_steps, 1) || run_begin(r, u, stream, use_graph)) return 1;
     hipStream_t s = r.s;
     // workspace: [x | eps | [x | cond] | ctx | forward arena]; guided: [x | x copy | eps | 2B model output | ctx | ctx copy |
-    // text mask | guidance parameters | forward arena]
+    // text mask | guidance parameters | forward arena]; with dynamic thresholding s (B) and its parameters in front of
+    // the forward arena
     const int64_t n_ws = guided ? 2 * n : n;
-    float *xbuf, *eps, *eps2, *xin, *xstart, *ctxbuf, *gpar;
+    float *xbuf, *eps, *eps2, *xin, *xstart, *ctxbuf, *gpar, *dyn_s, *dpar;
     int32_t* tmask;
     auto layout = [&](Arena& A) {
         xbuf = A.alloc(n_ws);  // guided: [x | x], the U-Net input of both halves
@@ -326,6 +336,8 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
         ctxbuf = ctx ? A.alloc(guided ? 2 * n_ctx : n_ctx) : nullptr;
         tmask = guided ? reinterpret_cast<int32_t*>(A.alloc(2 * B)) : nullptr;
         gpar = guided ? A.alloc(4) : nullptr;  // CfgParams: device data, so a captured step serves any guidance scale
+        dyn_s = dyn ? A.alloc(B) : nullptr;
+        dpar = dyn ? A.alloc(4) : nullptr;  // DynParams: device data, so a captured step serves any percentile
     };
     const float* ctx_marker = ctx ? reinterpret_cast<const float*>(16) : nullptr;
     const int32_t* mask_marker = guided ? reinterpret_cast<const int32_t*>(16) : nullptr;
@@ -343,6 +355,8 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
         DM_CHECK_HIP(hipMemcpyAsync(tmask, tmask_host.data(), 2 * B * sizeof(int32_t), hipMemcpyHostToDevice, s));
         DM_CHECK_HIP(hipMemcpyAsync(gpar, guide, sizeof(CfgParams), hipMemcpyHostToDevice, s));
     }
+    const DynParams dyn_host = dyn ? dyn_params((double)dyn_args->dyn_percentile, n / B) : DynParams{};
+    if (dyn) DM_CHECK_HIP(hipMemcpyAsync(dpar, &dyn_host, sizeof(DynParams), hipMemcpyHostToDevice, s));
     DM_CHECK_HIP(hipStreamSynchronize(s));  // the host tables and the host state may go away when this function returns
     DM_CHECK_HIP(hipMemcpyAsync(xbuf, x_T, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (ctx) DM_CHECK_HIP(hipMemcpyAsync(ctxbuf, ctx, n_ctx * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -369,11 +383,15 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
                                      B, H, W, st)) {
             return 1;
         }
+        if (dyn && launch_dyn_threshold(objective, xbuf, eps, u->coefs_dev, u->state_dev, reinterpret_cast<const DynParams*>(dpar),
+                                        DynParams{}, B, n / B, dyn_s, st))
+            return 1;
         // guided: x_{t-1} goes to both halves of the next step's input
         float* const dup = guided ? xbuf + n : nullptr;
-        if (dpmpp ? launch_dpmpp_update(xbuf, eps, xstart, u->coefs_dev, u->state_dev, xbuf, all_steps, dup, n, st, objective)
+        if (dpmpp ? launch_dpmpp_update(xbuf, eps, xstart, u->coefs_dev, u->state_dev, xbuf, all_steps, dup, n, st, objective,
+                                        dyn_s, n / B)
                   : launch_sampler_update(kind, xbuf, eps, noise, u->coefs_dev, u->state_dev, n, xbuf, all_steps, nullptr, n, st,
-                                          objective, xstart, dup, ddim_flags))
+                                          objective, xstart, dup, ddim_flags, dyn_s, n / B))
             return 1;
         return launch_step_advance(u->state_dev, st);
     };
@@ -384,6 +402,7 @@ static int sample_impl(dm_unet* u, int kind, int n_steps, const int64_t* times_h
     key.B = B; key.H = H; key.W = W; key.ctx_tokens = ctx_tokens; key.cond_channels = cond_channels;
     key.objective = objective; key.self_cond = self_cond; key.guided = guided;
     key.ddim_flags = ddim_flags;
+    key.dyn = dyn;
     key.noise = noise; key.all_steps = all_steps; key.ws = u->ws; key.times = u->times_dev; key.coefs = u->coefs_dev;
     if (run_steps(r, key, n_steps, one_step)) return 1;
     if (launch_finalize(xbuf, out, n, unnormalize, s)) return 1;  // out = x_0 [ (x + 1) / 2 ]
@@ -411,14 +430,16 @@ int dm_sample_cond(dm_unet* u, int kind, int n_steps, const int64_t* times_host,
                        cond_channels, out, all_steps, B, H, W, unnormalize, use_graph, stream);
 }
 
-int dm_sample_ex(dm_unet* u, const dm_sample_args* a) {
+int dm_sample_ex(dm_unet* u, const dm_sample_args* a) { return dm_sample_ex_dyn(u, a, nullptr); }
+
+int dm_sample_ex_dyn(dm_unet* u, const dm_sample_args* a, const dm_sample_dyn_args* dyn) {
     DM_REQUIRE(u && a, "null argument");
     DM_REQUIRE(a->cfg_remove_parallel == 0 || a->cfg_remove_parallel == 1, "cfg_remove_parallel is 0 or 1");
     const CfgParams g{a->cfg_scale, a->cfg_rescaled_phi, a->cfg_keep_parallel_frac, (float)a->cfg_remove_parallel};
     return sample_impl(u, a->kind, a->n_steps, a->times_host, a->coefs_host, a->x_T, a->noise, a->seed, a->sample_offset,
                        a->ctx, a->ctx_tokens, a->cond, a->cond_channels, a->out, a->all_steps, a->B, a->H, a->W,
                        a->unnormalize, a->use_graph, a->stream, a->objective, a->self_condition, a->cfg ? &g : nullptr,
-                       a->ddim_flags);
+                       a->ddim_flags, dyn);
 }
 
 }  // extern "C"

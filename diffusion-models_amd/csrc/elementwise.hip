@@ -553,13 +553,16 @@ int launch_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t e
 #pragma clang fp contract(off)
 // objective (what the U-Net output `eps` means, :603-626): 0 pred_noise, 1 pred_x0, 2 pred_v.  x_start (clamped, the
 // value both loops hand to the next step as x_self_cond, :657 / :683) is also written to xstart_out when given.
+// DYN: x_start is thresholded by dyn_s[image] (ddpm_x_start_dyn) wherever the static clamp stands; images are `per` long.
+// The instantiation without DYN is the kernel as it was: dyn_s and per are not read.
+template <bool DYN>
 __global__ void sampler_update_kernel(int kind, int objective, const float* __restrict__ x,
                                       const float* __restrict__ eps, const float* __restrict__ noise,
                                       const float* __restrict__ coefs, const SamplerState* __restrict__ st,
                                       int64_t noise_step_stride, float* __restrict__ out,
                                       float* __restrict__ all_steps, float* __restrict__ final_out,
                                       float* __restrict__ xstart_out, float* __restrict__ dup_out, int64_t n,
-                                      int ddim_flags) {
+                                      int ddim_flags, const float* __restrict__ dyn_s, int64_t per) {
     // everything that changes between two sample() calls of one shape is read from the device-side state, so a
     // captured step graph stays valid across calls (seed, Philox offset, step count, unnormalize)
     const int step = st ? st->step : 0;
@@ -588,8 +591,10 @@ __global__ void sampler_update_kernel(int kind, int objective, const float* __re
         int64_t i = i4 * 4 + j;
         if (i >= n) break;
         float xv = x[i], ev = eps[i];
-        const float x0 = kind != 0 && (ddim_flags & DDIM_NO_CLAMP) ? ddpm_x_start_raw(dc, objective, xv, ev)
-                                                                      : ddpm_x_start(dc, objective, xv, ev);
+        float x0;
+        if (DYN) x0 = ddpm_x_start_dyn(dc, objective, xv, ev, dyn_s[i / per]);
+        else x0 = kind != 0 && (ddim_flags & DDIM_NO_CLAMP) ? ddpm_x_start_raw(dc, objective, xv, ev)
+                                                            : ddpm_x_start(dc, objective, xv, ev);
         if (xstart_out) xstart_out[i] = x0;
         float r;
         if (kind == 0) {
@@ -611,10 +616,13 @@ __global__ void sampler_update_kernel(int kind, int objective, const float* __re
 //   r  = x0 where c[5] == 0 (t_next < 0, as DDIM's last step, :686-689)
 // hist holds the previous step's x0 and receives this step's: a thread reads and writes its own elements only, so the
 // update is in place.  With c[4] == 0 hist is not read: whatever it holds (NaN, uninitialised memory) stays out of r.
+// DYN: as in sampler_update_kernel; the history then holds thresholded estimates.
+template <bool DYN>
 __global__ void dpmpp_update_kernel(int objective, const float* __restrict__ x, const float* __restrict__ model_out,
                                     float* __restrict__ hist, const float* __restrict__ coefs,
                                     const SamplerState* __restrict__ st, float* __restrict__ out,
-                                    float* __restrict__ all_steps, float* __restrict__ dup_out, int64_t n) {
+                                    float* __restrict__ all_steps, float* __restrict__ dup_out, int64_t n,
+                                    const float* __restrict__ dyn_s, int64_t per) {
     const int step = st ? st->step : 0;
     const float* c = coefs + (size_t)step * 8;
     const DdpmCoefs dc = ddpm_coefs(c);
@@ -627,7 +635,8 @@ __global__ void dpmpp_update_kernel(int objective, const float* __restrict__ x, 
         const int64_t i = i4 * 4 + j;
         if (i >= n) break;
         const float xv = x[i];
-        const float x0 = ddpm_x_start(dc, objective, xv, model_out[i]);
+        const float x0 = DYN ? ddpm_x_start_dyn(dc, objective, xv, model_out[i], dyn_s[i / per])
+                             : ddpm_x_start(dc, objective, xv, model_out[i]);
         float d = x0;
         if (second) d = x0 + dc.c4 * (x0 - hist[i]);
         const float r = flag ? dc.c2 * xv + dc.c3 * d : x0;
@@ -655,24 +664,28 @@ int launch_finalize(const float* x, float* out, int64_t n, int unnormalize, hipS
 int launch_sampler_update(int kind, const float* x, const float* eps, const float* noise, const float* coefs_dev,
                           const SamplerState* state_dev, int64_t noise_step_stride, float* out, float* all_steps,
                           float* final_out, int64_t n, hipStream_t s, int objective, float* xstart_out,
-                          float* dup_out, int ddim_flags) {
+                          float* dup_out, int ddim_flags, const float* dyn_s, int64_t per) {
     DM_REQUIRE(ddim_flags == 0 || kind == 1, "ddim_flags belong to the DDIM update");
     DM_REQUIRE((ddim_flags & ~(DDIM_NO_CLAMP | DDIM_RAW_NOISE)) == 0, "unknown ddim_flags");
+    DM_REQUIRE(!dyn_s || ddim_flags == 0, "dynamic thresholding is not combined with ddim_flags");
+    DM_REQUIRE(!dyn_s || (per > 0 && n % per == 0), "dynamic thresholding needs the image size: a divisor of the element count");
     int64_t n4 = (n + 3) / 4;
-    hipLaunchKernelGGL(sampler_update_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, kind, objective, x, eps, noise,
-                       coefs_dev, state_dev, noise_step_stride, out, all_steps, final_out, xstart_out, dup_out, n,
-                       ddim_flags);
+    const auto kernel = dyn_s ? sampler_update_kernel<true> : sampler_update_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, kind, objective, x, eps, noise, coefs_dev, state_dev,
+                       noise_step_stride, out, all_steps, final_out, xstart_out, dup_out, n, ddim_flags, dyn_s, per);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 int launch_dpmpp_update(const float* x, const float* model_out, float* hist, const float* coefs_dev,
                         const SamplerState* state_dev, float* out, float* all_steps, float* dup_out, int64_t n, hipStream_t s,
-                        int objective) {
+                        int objective, const float* dyn_s, int64_t per) {
     DM_REQUIRE(hist != nullptr, "the DPM-Solver++ update needs its history buffer");
+    DM_REQUIRE(!dyn_s || (per > 0 && n % per == 0), "dynamic thresholding needs the image size: a divisor of the element count");
     int64_t n4 = (n + 3) / 4;
-    hipLaunchKernelGGL(dpmpp_update_kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, objective, x, model_out, hist, coefs_dev,
-                       state_dev, out, all_steps, dup_out, n);
+    const auto kernel = dyn_s ? dpmpp_update_kernel<true> : dpmpp_update_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((n4 + 255) / 256), dim3(256), 0, s, objective, x, model_out, hist, coefs_dev, state_dev, out,
+                       all_steps, dup_out, n, dyn_s, per);
     DM_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -82,6 +82,11 @@ static __device__ __forceinline__ float ddpm_x_start_raw(const DdpmCoefs& c, int
 static __device__ __forceinline__ float ddpm_x_start(const DdpmCoefs& c, int objective, float xv, float ev) {
     return clamp1(ddpm_x_start_raw(c, objective, xv, ev));
 }
+// ... and dynamically thresholded (dynthresh.hip): clamp(raw, -s, s) / s with the image's s >= 1.  s == 1 gives the bits
+// of ddpm_x_start (a division by one is exact); s = NaN (an image that holds a NaN) gives NaN.
+static __device__ __forceinline__ float ddpm_x_start_dyn(const DdpmCoefs& c, int objective, float xv, float ev, float s) {
+    return fminf(fmaxf(ddpm_x_start_raw(c, objective, xv, ev), -s), s) / s;
+}
 // The DDPM update from that x_start: posterior mean (:594-598) plus the noise term (:643-644).  The noise-free row keeps
 // `c4 * 0.0f`: noise = 0. at t == 0 still meets a NaN / Inf c4, as in the reference.
 static __device__ __forceinline__ float ddpm_update(const DdpmCoefs& c, float x0, float xv, bool noisy, float z) {

@@ -79,6 +79,15 @@ def hybrid_kl_scale(t_cpu: torch.Tensor, kl_weight: float = 0.001) -> float:
     return float(torch.tensor(kl_weight, dtype=torch.float32) / (mask_sum + 1e-8))
 
 
+def check_dynamic_threshold(p):
+    """``dynamic_threshold``: None (the static clamp to [-1, 1]) or the percentile of dynamic thresholding, in (0, 1]."""
+    if p is None:
+        return None
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < float(p) <= 1.0:
+        raise ValueError(f"dynamic_threshold is None or a percentile in (0, 1], got {p!r}")
+    return float(p)
+
+
 class DenoisingDiffusion:
     def __init__(
         self,
@@ -207,10 +216,12 @@ class DenoisingDiffusion:
 
     def _run(self, kind, shape, times, coefs, takes_noise: Sequence[bool], return_all_timesteps, noise, seed,
              text_emb=None, max_steps=None, cond=None, sample_offset=0, x_init=None, unnormalize=None, guidance=None,
-             ddim_flags=0):
+             ddim_flags=0, dynamic_threshold=None):
         """guidance: None, or (cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac) of classifier-free
         guidance (TextConditionalDenoisingDiffusion), which the library applies to the model output of every step.
-        ddim_flags: DM_DDIM_* of the sequence class's DDIM loop (seq1d.py); 0 is this class's loop."""
+        ddim_flags: DM_DDIM_* of the sequence class's DDIM loop (seq1d.py); 0 is this class's loop.
+        dynamic_threshold: None, or the percentile of the per-image threshold that replaces the clamp of x_start."""
+        dyn = self._dyn(dynamic_threshold)
         shape = _loop.checked_shape(self, shape)
         B, _, H, W = shape
         start = _loop.loop_start(self, shape, noise, seed, sample_offset, list(takes_noise), x_init)
@@ -232,8 +243,52 @@ class DenoisingDiffusion:
             a.cfg = 1
             a.cfg_scale, a.cfg_rescaled_phi, a.cfg_remove_parallel, a.cfg_keep_parallel_frac = (
                 float(guidance[0]), float(guidance[1]), int(bool(guidance[2])), float(guidance[3]))
-        return _loop.loop_call(self, a, self._lib.dm_sample_ex, shape, start, sample_offset, times[:n_steps], coefs[:n_steps],
+        entry = self._lib.dm_sample_ex
+        if dyn is not None:
+            d = _lib.SampleDynArgs(1, dyn)
+            entry = lambda handle, args: self._lib.dm_sample_ex_dyn(handle, args, C.byref(d))  # noqa: E731
+        return _loop.loop_call(self, a, entry, shape, start, sample_offset, times[:n_steps], coefs[:n_steps],
                                "coefs_host", n_steps + 1, return_all_timesteps, unnormalize)
+
+    # -- dynamic thresholding (Imagen, arXiv 2205.11487, section 2.3; not in the reference) ---------------------------
+    _dyn_refusal = None  # the exception of the classes whose loops do not threshold
+    _DYN_REFUSALS = {
+        ValueError: "dynamic_threshold is for pixel-space models: the latents of {} are not bounded to [-1, 1]",
+        NotImplementedError: "dynamic_threshold is not built for {}: it belongs to the DDPM, DDIM and DPM-Solver++ loops of "
+                             "DenoisingDiffusion and its text- and image-conditional classes",
+    }
+
+    def _dyn(self, dynamic_threshold):
+        """The checked percentile, or None; raises in the classes that refuse the keyword."""
+        p = check_dynamic_threshold(dynamic_threshold)
+        if p is not None and self._dyn_refusal is not None:
+            raise self._dyn_refusal(self._DYN_REFUSALS[self._dyn_refusal].format(type(self).__name__))
+        return p
+
+    def _dyn_kw(self, dynamic_threshold):
+        """The keyword of ``_run`` for a checked percentile; nothing for None."""
+        p = self._dyn(dynamic_threshold)
+        return {} if p is None else {"dynamic_threshold": p}
+
+    def _dyn_s(self, objective_id, x, model_out, coef, p):
+        """s (B,) of ``dm_op_dyn_threshold``: max(1, quantile_p |x_start_raw|) per image."""
+        b = x.shape[0]
+        s = torch.empty((b,), device=self.device, dtype=torch.float32)
+        _lib.check(self._lib.dm_op_dyn_threshold(objective_id, _lib.ptr(x), _lib.ptr(model_out), coef, b, x[0].numel(), p,
+                                                 _lib.ptr(s), self._stream()))
+        return s
+
+    def _dyn_clip(self, raw, p):
+        """clamp(raw, -s_b, s_b) / s_b of an unclamped x_start, through the kernels of the loops: the estimate enters as a
+        pred_x0 model output, and the DDIM update of a last step (c[5] == 0) returns x_start."""
+        raw = raw.contiguous()
+        b = raw.shape[0]
+        coef = (C.c_float * _lib.DM_COEFS)(*([0.0] * _lib.DM_COEFS))
+        s = self._dyn_s(1, raw, raw, coef, p)
+        out, x_start = torch.empty_like(raw), torch.empty_like(raw)
+        _lib.check(self._lib.dm_op_sampler_update_dyn(DDIM, 1, _lib.ptr(raw), _lib.ptr(raw), None, coef, _lib.ptr(s), b,
+                                                      raw[0].numel(), _lib.ptr(out), _lib.ptr(x_start), self._stream()))
+        return x_start
 
     # -- training half (denoising_diffusion.py:805-900): loss and gradients in libdm_hip.so --------------------------
     def train(self, mode: bool = True):
@@ -385,21 +440,21 @@ class DenoisingDiffusion:
 
     @torch.inference_mode()
     def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, text_emb=None,
-                      sample_offset=0, _guidance=None):
+                      sample_offset=0, _guidance=None, dynamic_threshold=None):
         times, coefs = self._ddpm_tables()
         takes = [t > 0 for t in times]
         return self._run(DDPM, shape, times, coefs, takes, return_all_timesteps, noise, seed, text_emb, max_steps,
-                         sample_offset=sample_offset, guidance=_guidance)
+                         sample_offset=sample_offset, guidance=_guidance, **self._dyn_kw(dynamic_threshold))
 
     @torch.inference_mode()
     def ddim_sample(self, shape, sampling_timesteps=None, return_all_timesteps=False, *, noise=None, seed=None,
-                    max_steps=None, text_emb=None, sample_offset=0, _guidance=None):
+                    max_steps=None, text_emb=None, sample_offset=0, _guidance=None, dynamic_threshold=None):
         if sampling_timesteps is None:
             sampling_timesteps = self.sampling_timesteps
         times, coefs = self._ddim_tables(sampling_timesteps)
         takes = [bool(c[5] != 0) for c in coefs]
         return self._run(DDIM, shape, times, coefs, takes, return_all_timesteps, noise, seed, text_emb, max_steps,
-                         sample_offset=sample_offset, guidance=_guidance)
+                         sample_offset=sample_offset, guidance=_guidance, **self._dyn_kw(dynamic_threshold))
 
     def _dpmpp_tables(self, sampling_timesteps, order) -> Tuple[List[int], torch.Tensor]:
         if sampling_timesteps is None:
@@ -408,21 +463,26 @@ class DenoisingDiffusion:
 
     @torch.inference_mode()
     def dpm_solver_sample(self, shape, sampling_timesteps=None, order=2, return_all_timesteps=False, *, noise=None, seed=None,
-                          max_steps=None, text_emb=None, sample_offset=0, _guidance=None):
+                          max_steps=None, text_emb=None, sample_offset=0, _guidance=None, dynamic_threshold=None):
         """DPM-Solver++ (Lu et al., arXiv 2211.01095, Algorithm 2: multistep, data prediction) on the time grid of
         ``ddim_sample``; not in the reference.  ``order=2`` is the 2M solver, ``order=1`` is DDIM with eta = 0 in another
-        arrangement of the same terms.  x_start is clamped at every step as ``ddim_sample`` clamps it.
+        arrangement of the same terms.  x_start is clamped at every step as ``ddim_sample`` clamps it, or thresholded
+        per image with ``dynamic_threshold`` (a percentile in (0, 1]), the remedy the paper names for guided sampling.
         ``sampling_timesteps`` defaults to the constructor's when that selects DDIM sampling, else to 20.  No noise is drawn
         after x_T: an injected ``noise`` callable is called once."""
         times, coefs = self._dpmpp_tables(sampling_timesteps, order)
         return self._run(DPMPP, shape, times, coefs, [], return_all_timesteps, noise, seed, text_emb, max_steps,
-                         sample_offset=sample_offset, guidance=_guidance)
+                         sample_offset=sample_offset, guidance=_guidance, **self._dyn_kw(dynamic_threshold))
 
     @torch.inference_mode()
-    def sample(self, batch_size=16, return_all_timesteps=False, *, solver=None, order=2, **kw):
-        """:779-783; ``solver='dpmpp'`` (an extension) samples with ``dpm_solver_sample`` at ``order``."""
+    def sample(self, batch_size=16, return_all_timesteps=False, *, solver=None, order=2, dynamic_threshold=None, **kw):
+        """:779-783; ``solver='dpmpp'`` (an extension) samples with ``dpm_solver_sample`` at ``order``.
+        ``dynamic_threshold`` (an extension; None or a percentile in (0, 1], Imagen uses 0.95): every step's x_start is
+        clamp(x, -s, s) / s with s = max(1, that quantile of |x_start| over the image) in place of clamp(x, -1, 1)."""
         (h, w), channels = self.image_size, self.channels
         shape = (batch_size, channels, h, w)
+        if self._dyn(dynamic_threshold) is not None:
+            kw = dict(kw, dynamic_threshold=dynamic_threshold)
         if _solver(solver):
             return self.dpm_solver_sample(shape, order=order, return_all_timesteps=return_all_timesteps, **kw)
         sample_fn = self.p_sample_loop if not self.is_ddim_sampling else self.ddim_sample
@@ -503,8 +563,18 @@ class DenoisingDiffusion:
         return mean, self._ext("posterior_variance", t, x_t), self._ext("posterior_log_variance_clipped", t, x_t)
 
     @torch.inference_mode()
-    def model_predictions(self, x, t, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False, **cond_kw):
-        """:603-626: ``ModelPrediction(pred_noise, pred_x_start)`` for per-sample timesteps ``t`` (a (B,) tensor, or an int)."""
+    def model_predictions(self, x, t, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False, *,
+                          dynamic_threshold=None, **cond_kw):
+        """:603-626: ``ModelPrediction(pred_noise, pred_x_start)`` for per-sample timesteps ``t`` (a (B,) tensor, or an int).
+        With ``clip_x_start`` and ``dynamic_threshold`` the clip is the per-image dynamic threshold."""
+        dyn = self._dyn(dynamic_threshold) if clip_x_start else None
+        if dyn is not None:
+            raw = DenoisingDiffusion.model_predictions(self, x, t, x_self_cond, False, False, **cond_kw)
+            x_start = self._dyn_clip(raw.pred_x_start, dyn)
+            if self.objective == "pred_noise" and not rederive_pred_noise:
+                return ModelPrediction(raw.pred_noise, x_start)
+            x = x.to(self.device, torch.float32).contiguous()
+            return ModelPrediction(self.predict_noise_from_start(x, self._bt(t, x.shape[0]), x_start), x_start)
         x = x.to(self.device, torch.float32).contiguous()
         bt = self._bt(t, x.shape[0])
         if self.self_condition:
@@ -527,10 +597,11 @@ class DenoisingDiffusion:
         return ModelPrediction(pred_noise, x_start)
 
     @torch.inference_mode()
-    def p_mean_variance(self, x, t, x_self_cond=None, clip_denoised=True, **cond_kw):
+    def p_mean_variance(self, x, t, x_self_cond=None, clip_denoised=True, *, dynamic_threshold=None, **cond_kw):
         """:628-636: (model_mean, posterior_variance, posterior_log_variance, x_start)."""
         x = x.to(self.device, torch.float32).contiguous()
-        x_start = self.model_predictions(x, t, x_self_cond, clip_x_start=bool(clip_denoised), **cond_kw).pred_x_start
+        x_start = self.model_predictions(x, t, x_self_cond, clip_x_start=bool(clip_denoised),
+                                         dynamic_threshold=dynamic_threshold, **cond_kw).pred_x_start
         mean, var, logvar = self.q_posterior(x_start, x, t)
         return mean, var, logvar, x_start
 
@@ -595,8 +666,9 @@ class DenoisingDiffusion:
         """The U-Net call of ``model_predictions`` (:603-606); subclasses thread their condition through ``cond_kw``."""
         return self.model(x, bt, **cond_kw)
 
-    def _p_sample(self, x, t: int, noise, cond_kw, x_self_cond=None):
+    def _p_sample(self, x, t: int, noise, cond_kw, x_self_cond=None, dynamic_threshold=None):
         """One reverse step (denoising_diffusion.py:638-645): (pred_img, x_start); the update runs in sampler_update_kernel."""
+        dyn = self._dyn(dynamic_threshold)
         b = x.shape[0]
         t = int(t)
         x = x.to(self.device, torch.float32).contiguous()
@@ -620,14 +692,20 @@ class DenoisingDiffusion:
                  else self._randn(x.shape, _lib.default_seed(), 1))
         out = torch.empty_like(x)
         x_start = torch.empty_like(x)
+        if dyn is not None:
+            thr = self._dyn_s(self._objective_id, x, eps, coef, dyn)
+            _lib.check(self._lib.dm_op_sampler_update_dyn(DDPM, self._objective_id, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(z),
+                                                          coef, _lib.ptr(thr), b, x[0].numel(), _lib.ptr(out),
+                                                          _lib.ptr(x_start), stream))
+            return out, x_start
         _lib.check(self._lib.dm_op_sampler_update(DDPM, self._objective_id, _lib.ptr(x), _lib.ptr(eps), _lib.ptr(z), coef,
                                                   _lib.ptr(out), _lib.ptr(x_start), x.numel(), stream))
         return out, x_start
 
     @torch.inference_mode()
-    def p_sample(self, x, t: int, x_self_cond=None, *, noise=None):
+    def p_sample(self, x, t: int, x_self_cond=None, *, noise=None, dynamic_threshold=None):
         """:638-645.  Returns (pred_img, x_start)."""
-        return self._p_sample(x, t, noise, {}, x_self_cond)
+        return self._p_sample(x, t, noise, {}, x_self_cond, dynamic_threshold)
 
 
 class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
@@ -677,28 +755,32 @@ class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
 
     @torch.inference_mode()
     def p_sample_loop(self, shape, save_path_for_text=None, return_all_timesteps=False, *, text_emb=None, cond_scale=1.0,
-                      rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, **kw):
+                      rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, dynamic_threshold=None, **kw):
         g = self._guidance(cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
+        dyn = self._dyn(dynamic_threshold)
         text_emb = self._text(shape[0], save_path_for_text, text_emb)
-        return super().p_sample_loop(shape, return_all_timesteps, text_emb=text_emb, _guidance=g, **kw)
+        return super().p_sample_loop(shape, return_all_timesteps, text_emb=text_emb, _guidance=g, dynamic_threshold=dyn, **kw)
 
     @torch.inference_mode()
     def ddim_sample(self, shape, save_path_for_text=None, sampling_timesteps=None, return_all_timesteps=False, *,
                     text_emb=None, cond_scale=1.0, rescaled_phi=0.0, remove_parallel_component=True,
-                    keep_parallel_frac=0.0, **kw):
+                    keep_parallel_frac=0.0, dynamic_threshold=None, **kw):
         g = self._guidance(cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
+        dyn = self._dyn(dynamic_threshold)
         text_emb = self._text(shape[0], save_path_for_text, text_emb)
-        return super().ddim_sample(shape, sampling_timesteps, return_all_timesteps, text_emb=text_emb, _guidance=g, **kw)
+        return super().ddim_sample(shape, sampling_timesteps, return_all_timesteps, text_emb=text_emb, _guidance=g,
+                                   dynamic_threshold=dyn, **kw)
 
     @torch.inference_mode()
     def dpm_solver_sample(self, shape, save_path_for_text=None, sampling_timesteps=None, order=2,
                           return_all_timesteps=False, *, text_emb=None, cond_scale=1.0, rescaled_phi=0.0,
-                          remove_parallel_component=True, keep_parallel_frac=0.0, **kw):
+                          remove_parallel_component=True, keep_parallel_frac=0.0, dynamic_threshold=None, **kw):
         """The parent's DPM-Solver++ loop with the caption embeddings and the guidance keywords of ``ddim_sample``."""
         g = self._guidance(cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
+        dyn = self._dyn(dynamic_threshold)
         text_emb = self._text(shape[0], save_path_for_text, text_emb)
         return super().dpm_solver_sample(shape, sampling_timesteps, order, return_all_timesteps, text_emb=text_emb,
-                                         _guidance=g, **kw)
+                                         _guidance=g, dynamic_threshold=dyn, **kw)
 
     def _sample_fn(self, solver, order):
         """The loop ``sample()`` runs, called as fn(shape, save_path_for_text, **keywords)."""
@@ -708,12 +790,14 @@ class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
 
     @torch.inference_mode()
     def sample(self, batch_size=16, save_path_for_text=None, return_all_timesteps=False, *, cond_scale=1.0,
-               rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, solver=None, order=2, **kw):
+               rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, dynamic_threshold=None,
+               solver=None, order=2, **kw):
         (h, w), channels = self.image_size, self.channels
         sample_fn = self._sample_fn(solver, order)
         return sample_fn((batch_size, channels, h, w), save_path_for_text, return_all_timesteps=return_all_timesteps,
                          cond_scale=cond_scale, rescaled_phi=rescaled_phi,
-                         remove_parallel_component=remove_parallel_component, keep_parallel_frac=keep_parallel_frac, **kw)
+                         remove_parallel_component=remove_parallel_component, keep_parallel_frac=keep_parallel_frac,
+                         dynamic_threshold=self._dyn(dynamic_threshold), **kw)
 
     def p_losses(self, x_start, t, text_emb=None, noise=None, offset_noise_strength=None, *, text_mask=None,
                  cond_drop_prob=None, **kw):
@@ -766,30 +850,33 @@ class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
 
     @torch.inference_mode()
     def model_predictions(self, x, t, text_emb=None, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False, *,
-                          cond_scale=1.0, rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0):
+                          cond_scale=1.0, rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0,
+                          dynamic_threshold=None):
         """denoising_diffusion_text_conditional.py:274-297 (positional order: x, t, text_emb, x_self_cond); with
         cond_scale != 1 the model output is the guided one of Unet.forward_with_cond_scale."""
         kw = self._cond_kw(text_emb, cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
-        return super().model_predictions(x, t, x_self_cond, clip_x_start, rederive_pred_noise, **kw)
+        return super().model_predictions(x, t, x_self_cond, clip_x_start, rederive_pred_noise,
+                                         dynamic_threshold=dynamic_threshold, **kw)
 
     @torch.inference_mode()
     def p_mean_variance(self, x, t, text_emb=None, x_self_cond=None, clip_denoised=True, *, cond_scale=1.0,
-                        rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0):
+                        rescaled_phi=0.0, remove_parallel_component=True, keep_parallel_frac=0.0, dynamic_threshold=None):
         """:299-307."""
         x = x.to(self.device, torch.float32).contiguous()
         x_start = self.model_predictions(x, t, text_emb, x_self_cond, clip_x_start=bool(clip_denoised),
                                          cond_scale=cond_scale, rescaled_phi=rescaled_phi,
                                          remove_parallel_component=remove_parallel_component,
-                                         keep_parallel_frac=keep_parallel_frac).pred_x_start
+                                         keep_parallel_frac=keep_parallel_frac,
+                                         dynamic_threshold=dynamic_threshold).pred_x_start
         mean, var, logvar = self.q_posterior(x_start, x, t)
         return mean, var, logvar, x_start
 
     @torch.inference_mode()
     def p_sample(self, x, t: int, text_emb=None, x_self_cond=None, *, noise=None, cond_scale=1.0, rescaled_phi=0.0,
-                 remove_parallel_component=True, keep_parallel_frac=0.0):
+                 remove_parallel_component=True, keep_parallel_frac=0.0, dynamic_threshold=None):
         """denoising_diffusion_text_conditional.py:310-317 (the reference's positional order: x, t, text_emb)."""
         kw = self._cond_kw(text_emb, cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
-        return self._p_sample(x, t, noise, kw, x_self_cond)
+        return self._p_sample(x, t, noise, kw, x_self_cond, dynamic_threshold)
 
 
 class ImageConditionalDenoisingDiffusion(DenoisingDiffusion):
@@ -824,39 +911,45 @@ class ImageConditionalDenoisingDiffusion(DenoisingDiffusion):
 
     @torch.inference_mode()
     def p_sample_loop(self, shape, return_condition_image=False, return_all_timesteps=False, *, cond=None, noise=None,
-                      seed=None, max_steps=None, sample_offset=0):
+                      seed=None, max_steps=None, sample_offset=0, dynamic_threshold=None):
         # the reference draws x_T first, then the condition (:159-163); the order only matters for its global RNG
+        dyn = self._dyn_kw(dynamic_threshold)
         times, coefs = self._ddpm_tables()
         cond = self._cond(shape[0], cond)
         ret = self._run(DDPM, shape, times, coefs, [t > 0 for t in times], return_all_timesteps, noise, seed, None,
-                        max_steps, cond=cond, sample_offset=sample_offset)
+                        max_steps, cond=cond, sample_offset=sample_offset, **dyn)
         return (cond, ret) if return_condition_image else ret
 
     @torch.inference_mode()
     def ddim_sample(self, shape, sampling_timesteps=None, cond=None, return_all_timesteps=False, *, noise=None,
-                    seed=None, max_steps=None, sample_offset=0):
+                    seed=None, max_steps=None, sample_offset=0, dynamic_threshold=None):
+        dyn = self._dyn_kw(dynamic_threshold)
         if sampling_timesteps is None:
             sampling_timesteps = self.sampling_timesteps
         times, coefs = self._ddim_tables(sampling_timesteps)
         cond = self._cond(shape[0], cond)
         return self._run(DDIM, shape, times, coefs, [bool(c[5] != 0) for c in coefs], return_all_timesteps, noise, seed,
-                         None, max_steps, cond=cond, sample_offset=sample_offset)
+                         None, max_steps, cond=cond, sample_offset=sample_offset, **dyn)
 
     @torch.inference_mode()
     def dpm_solver_sample(self, shape, sampling_timesteps=None, order=2, cond=None, return_condition_image=False,
-                          return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0):
+                          return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0,
+                          dynamic_threshold=None):
         """The parent's DPM-Solver++ loop with the condition image behind x at every step, as in ``ddim_sample``."""
+        dyn = self._dyn_kw(dynamic_threshold)
         times, coefs = self._dpmpp_tables(sampling_timesteps, order)
         cond = self._cond(shape[0], cond)
         ret = self._run(DPMPP, shape, times, coefs, [], return_all_timesteps, noise, seed, None, max_steps, cond=cond,
-                        sample_offset=sample_offset)
+                        sample_offset=sample_offset, **dyn)
         return (cond, ret) if return_condition_image else ret
 
     @torch.inference_mode()
     def sample(self, batch_size=16, return_condition_image=False, return_all_timesteps=False, *, cond=None, solver=None,
-               order=2, **kw):
+               order=2, dynamic_threshold=None, **kw):
         (h, w), channels = self.image_size, self.channels
         shape = (batch_size, channels, h, w)
+        if self._dyn(dynamic_threshold) is not None:
+            kw = dict(kw, dynamic_threshold=dynamic_threshold)
         if _solver(solver):
             return self.dpm_solver_sample(shape, order=order, cond=cond, return_condition_image=return_condition_image,
                                           return_all_timesteps=return_all_timesteps, **kw)
@@ -881,21 +974,23 @@ class ImageConditionalDenoisingDiffusion(DenoisingDiffusion):
         assert cond is not None, "the image-conditional U-Net needs cond="
         return self._interpolate(x1, x2, t, lam, noise, seed, cond=self._cond(x1.shape[0], cond))
 
-    def model_predictions(self, x, t, cond=None, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False):
+    def model_predictions(self, x, t, cond=None, x_self_cond=None, clip_x_start=False, rederive_pred_noise=False, *,
+                          dynamic_threshold=None):
         """denoising_diffusion_image_conditional.py:78-102 (positional order: x, t, cond, x_self_cond)."""
         assert cond is not None, "the image-conditional U-Net needs cond="
-        return super().model_predictions(x, t, x_self_cond, clip_x_start, rederive_pred_noise, cond=cond)
+        return super().model_predictions(x, t, x_self_cond, clip_x_start, rederive_pred_noise,
+                                         dynamic_threshold=dynamic_threshold, cond=cond)
 
-    def p_mean_variance(self, x, t, cond=None, x_self_cond=None, clip_denoised=True):
+    def p_mean_variance(self, x, t, cond=None, x_self_cond=None, clip_denoised=True, *, dynamic_threshold=None):
         """:104-112."""
         assert cond is not None, "the image-conditional U-Net needs cond="
-        return super().p_mean_variance(x, t, x_self_cond, clip_denoised, cond=cond)
+        return super().p_mean_variance(x, t, x_self_cond, clip_denoised, dynamic_threshold=dynamic_threshold, cond=cond)
 
     @torch.inference_mode()
-    def p_sample(self, x, t: int, cond=None, x_self_cond=None, *, noise=None):
+    def p_sample(self, x, t: int, cond=None, x_self_cond=None, *, noise=None, dynamic_threshold=None):
         """denoising_diffusion_image_conditional.py:114-120: ``cond`` is what the U-Net sees behind x."""
         assert cond is not None, "the image-conditional U-Net needs cond="
-        return self._p_sample(x, t, noise, {"cond": cond}, x_self_cond)
+        return self._p_sample(x, t, noise, {"cond": cond}, x_self_cond, dynamic_threshold)
 
 
 def _first_stage_latents(vae, images):
@@ -914,6 +1009,8 @@ def _first_stage_latents(vae, images):
 
 class LatentDiffusion(DenoisingDiffusion):
     """Diffusion on VAE latents, then decode (latent_diffusion.py:9-66)."""
+
+    _dyn_refusal = ValueError  # dynamic_threshold: latents are not bounded to [-1, 1]
 
     def __init__(self, model, vae, latent_shape, **kwargs):
         kwargs.setdefault("auto_normalize", True)
@@ -954,6 +1051,8 @@ class TextConditionalLatentDiffusion(TextConditionalDenoisingDiffusion):
     """``TextConditionalLatentDiffusion`` (latent-diffusion/ldm/models/latent_diffusion_text_conditional.py:11-99): the
     text-conditional loop on VAE latents (normalize / unnormalize are the identity, :36-37), then ``vae.decode``
     (:78-99)."""
+
+    _dyn_refusal = ValueError  # dynamic_threshold: latents are not bounded to [-1, 1]
 
     def __init__(self, model, vae, latent_shape, text_emb_dim=512, **kwargs):
         super().__init__(model=model, image_size=latent_shape[1], **kwargs)
@@ -996,6 +1095,8 @@ class ImageConditionalLatentDiffusion(ImageConditionalDenoisingDiffusion):
     through every step concatenated behind the latent; the result is decoded at the end.  The reference re-encodes the
     (loop-invariant) condition inside every one of its T iterations (:127); here it is encoded once -- the same value.
     normalize / unnormalize are the identity (:43-44)."""
+
+    _dyn_refusal = ValueError  # dynamic_threshold: latents are not bounded to [-1, 1]
 
     def __init__(self, model, vae, latent_shape, init_image_size, cond_vae=None, **kwargs):
         super().__init__(model, image_size=tuple(latent_shape[1:]), **kwargs)
@@ -1054,6 +1155,7 @@ class ImageConditionalLatentDiffusion(ImageConditionalDenoisingDiffusion):
     @torch.inference_mode()
     def sample(self, batch_size=16, return_condition_image=False, return_all_timesteps=False, *, cond=None, solver=None,
                order=2, **kw):
+        self._dyn(kw.get("dynamic_threshold"))
         (h, w), channels = self.image_size, self.channels
         shape = (batch_size, channels, h, w)
         cond = self._cond(batch_size, cond)

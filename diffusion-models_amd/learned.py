@@ -105,11 +105,15 @@ class LearnedGaussianDiffusion(DenoisingDiffusion):
                                   "variance interpolation), not the plain prediction DPM-Solver++ steps on, and the class has "
                                   "no model_predictions")
 
+    _dyn_refusal = NotImplementedError  # dynamic_threshold: this class's loop has its own update kernel
+
     # -- sampling ---------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
-    def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0):
+    def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0,
+                      dynamic_threshold=None):
         """denoising_diffusion.py:647-664 over the p_mean_variance of :93-111.  ``noise`` (a callable ``shape -> cpu
         tensor``) is called in the reference's draw order: x_T, then one per step with t > 0."""
+        self._dyn(dynamic_threshold)
         shape = _loop.checked_shape(self, shape)
         times = list(reversed(range(self.num_timesteps)))
         if max_steps is not None:  # bounded run: the first `max_steps` iterations only

@@ -139,12 +139,15 @@ class GaussianDiffusion(DenoisingDiffusion):
             raise ValueError(f"mask {tuple(mask.shape)} must be ({B}, 1 or {Cc}, {H}, {W})")
         return gt, mask
 
+    _dyn_refusal = NotImplementedError  # dynamic_threshold: this class's loop has its own update kernel
+
     # -- the loop ---------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
     def p_sample_loop(self, shape, return_all_timesteps=False, gt=None, mask=None, resample=True, resample_iter=10,
                       resample_jump=3, resample_every=50, *, noise=None, seed=None, sample_offset=0, **kw):
         """:644-681.  ``noise`` (a callable ``shape -> cpu tensor``) is called in the reference's draw order: x_T, then per
         row [z_jump], z_known, [z_step]."""
+        self._dyn(kw.get("dynamic_threshold"))
         if mask is None:
             return super().p_sample_loop(shape, return_all_timesteps, noise=noise, seed=seed, sample_offset=sample_offset, **kw)
         if kw:

@@ -143,9 +143,12 @@ class DenoisingDiffusion1D(DenoisingDiffusion):
     def sample_shape(self):
         return (self.channels, self.seq_length)
 
+    _dyn_refusal = NotImplementedError  # dynamic_threshold: this class's loop has its own update kernel
+
     # -- the loops: (B, C, L) at the surface, (B, C, 1, L) at the ABI -------------------------------------------------
     def _run(self, kind, shape, times, coefs, takes_noise, return_all_timesteps, noise, seed, text_emb=None, max_steps=None,
-             cond=None, sample_offset=0, x_init=None, unnormalize=None, guidance=None, ddim_flags=0):
+             cond=None, sample_offset=0, x_init=None, unnormalize=None, guidance=None, ddim_flags=0, dynamic_threshold=None):
+        self._dyn(dynamic_threshold)
         assert text_emb is None and cond is None and guidance is None, "the sequence model is unconditional"
         shape = tuple(int(v) for v in shape)
         assert len(shape) == 3, f"shape {shape}: (batch, channels, seq_length)"
@@ -160,15 +163,17 @@ class DenoisingDiffusion1D(DenoisingDiffusion):
         return out.squeeze(-2)
 
     @torch.inference_mode()
-    def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0):
+    def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0,
+                      dynamic_threshold=None):
         """:547-560."""
         return super().p_sample_loop(shape, return_all_timesteps, noise=noise, seed=seed, max_steps=max_steps,
-                                     sample_offset=sample_offset)
+                                     sample_offset=sample_offset, dynamic_threshold=dynamic_threshold)
 
     @torch.inference_mode()
     def ddim_sample(self, shape, clip_denoised=True, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None,
-                    sample_offset=0):
+                    sample_offset=0, dynamic_threshold=None):
         """:562-596: ``model_predictions(img, t, self_cond, clip_x_start=clip_denoised)`` without ``rederive_pred_noise``."""
+        self._dyn(dynamic_threshold)
         times, coefs = ddim_step_table(self._sched, self.sampling_timesteps, self.ddim_sampling_eta)
         takes = [bool(c[5] != 0) for c in coefs]
         flags = _lib.DDIM_RAW_NOISE | (0 if clip_denoised else _lib.DDIM_NO_CLAMP)

@@ -106,11 +106,15 @@ class WeightedObjectiveGaussianDiffusion(DenoisingDiffusion):
         raise NotImplementedError(_NO_DDIM.format("dpm_solver_sample (the model output is a softmax blend of two predictions, "
                                                   "not the plain prediction DPM-Solver++ steps on)"))
 
+    _dyn_refusal = NotImplementedError  # dynamic_threshold: this class's loop has its own update kernel
+
     # -- sampling ---------------------------------------------------------------------------------------------------------
     @torch.inference_mode()
-    def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0):
+    def p_sample_loop(self, shape, return_all_timesteps=False, *, noise=None, seed=None, max_steps=None, sample_offset=0,
+                      dynamic_threshold=None):
         """denoising_diffusion.py:647-664 over the p_mean_variance of :33-49 (the module docstring's deviation).  ``noise``
         (a callable ``shape -> cpu tensor``) is called in the reference's draw order: x_T, then one per step with t > 0."""
+        self._dyn(dynamic_threshold)
         shape = _loop.checked_shape(self, shape)
         times = list(reversed(range(self.num_timesteps)))
         if max_steps is not None:  # bounded run: the first `max_steps` iterations only

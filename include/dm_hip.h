@@ -229,6 +229,22 @@ typedef struct dm_sample_args {
 } dm_sample_args;
 int dm_sample_ex(dm_unet* u, const dm_sample_args* args);
 
+/* Dynamic thresholding of x_start (Imagen, arXiv 2205.11487, section 2.3) in the loop of dm_sample_ex, every kind:
+ *   s_b = max(1, quantile(|x_start_raw| over (C, H, W) of image b, dyn_percentile)),
+ *   x_start = clamp(x_start_raw, -s_b, s_b) / s_b   in place of clamp(x_start_raw, -1, 1),
+ * with torch.quantile's linear interpolation; where the quantile is <= 1 the step is bit-for-bit the static clamp.
+ * x_start is what the update, DDIM's re-derived pred_noise, the DPM-Solver++ history and the self-conditioning feedback
+ * read.  One more kernel per step (an exact radix select, one workgroup per image) between the U-Net and the update.
+ * dyn_threshold == 0 (the zero-initialised struct, or dyn == NULL): dm_sample_ex as it is.  dyn_threshold != 0 needs
+ * dyn_percentile in (0, 1]; refused on a seq1d handle and with ddim_flags != 0.  The rank and the interpolation weight
+ * are device data of the captured step graph: a new percentile reuses the graph of the same shape.
+ * These fields ride in a struct of their own behind dm_sample_args, whose layout stays as it is. */
+typedef struct dm_sample_dyn_args {
+    int32_t dyn_threshold;
+    float dyn_percentile;
+} dm_sample_dyn_args;
+int dm_sample_ex_dyn(dm_unet* u, const dm_sample_args* args, const dm_sample_dyn_args* dyn);
+
 /* N(0,1) noise from the library's Philox4x32-10 stream (what dm_sample uses when noise == NULL);
  * element e of the tensor of draw `draw` uses counter ((element_offset + e)/4, draw) under key `seed`
  * (element_offset % 4 == 0; draw 0 = x_T, draw i+1 = the noise of loop step i). */
@@ -362,6 +378,16 @@ int dm_op_block1d(const float* x0, int C0, const float* x1, int C1, const float*
  * (device) holds the previous step's clamped x_0 estimate and receives this step's; with c[4] == 0 it is not read */
 int dm_op_dpmpp_update(int objective, const float* x, const float* model_out, float* x0_hist, const float* coef_host,
                        float* out, int64_t n, void* stream);
+/* Dynamic thresholding on its own (dm_sample_ex_dyn).  s_out[b] = max(1, quantile(|x_start_raw|, percentile)) of image b
+ * for B images of `per` values; x_start_raw from x and model_out by `objective` with c_host, one row of DM_COEFS floats. */
+int dm_op_dyn_threshold(int objective, const float* x, const float* model_out, const float* c_host, int B, int64_t per,
+                        double percentile, float* s_out, void* stream);
+/* dm_op_sampler_update / dm_op_dpmpp_update on B images of `per` values with x_start thresholded by s (B floats, device) */
+int dm_op_sampler_update_dyn(int kind, int objective, const float* x, const float* eps, const float* noise,
+                             const float* c_host, const float* s, int B, int64_t per, float* out, float* x_start,
+                             void* stream);
+int dm_op_dpmpp_update_dyn(int objective, const float* x, const float* model_out, float* x0_hist, const float* coef_host,
+                           const float* s, int B, int64_t per, float* out, void* stream);
 /* The guidance combine of dm_sample_args.cfg on its own: out[b] = guided(cond[b], null_out[b]) for B rows of
  * per_sample floats (DD/classifier_free_guidance.py:355-369 with project :49-60).  Device pointers, out distinct from
  * both inputs. */
