@@ -39,7 +39,8 @@ from .seq1d import DenoisingDiffusion1D, Unet1D  # noqa: F401
 from .classifier_guidance import ClassifierGuidedGaussianDiffusion, cg_step_table  # noqa: F401
 from .vae import (AutoencoderKL, DiagonalGaussianDistribution, KLEncoder, VQDecoder, VQEncoder, VQModel,  # noqa: F401
                   VQModelInterface)
-from .dist import gather_shards, sample_global, sample_sharded, shard_bounds, shared_seed  # noqa: F401
+from .bpd import bpd_step_table, bpd_times  # noqa: F401
+from .dist import bpd_global, gather_shards, sample_global, sample_sharded, shard_bounds, shared_seed  # noqa: F401
 from .checkpoint import load_trainer_checkpoint, load_vae_checkpoint  # noqa: F401
 from .train import EMA, diffusion_state_dict, load_checkpoint, save_checkpoint, train_step  # noqa: F401
 from .inception import FIDEvaluation, InceptionScoreEvaluation, InceptionV3, calculate_frechet_distance  # noqa: F401
@@ -76,6 +77,7 @@ __all__ = [
     "InceptionScoreEvaluation",
     "sample_sharded",
     "sample_global",
+    "bpd_global",
     "gather_shards",
     "shard_bounds",
     "UnetConfig",
@@ -102,6 +104,8 @@ __all__ = [
     "RepaintTable",
     "lv_step_table",
     "lv_train_table",
+    "bpd_step_table",
+    "bpd_times",
     "wo_step_table",
     "wo_train_table",
     "synth_state_dict",

@@ -26,6 +26,8 @@ DM_LV_TRAIN_COEFS = 12
 DM_WO_COEFS = 16
 DM_WO_TRAIN_COEFS = 12
 DM_CG_COEFS = 16
+DM_BPD_COEFS = 16
+DM_BPD_CHUNK = 1024
 ABI_VERSION = 9
 DDIM_NO_CLAMP, DDIM_RAW_NOISE = 1, 2  # DM_DDIM_* of include/dm_hip.h
 
@@ -72,6 +74,7 @@ EXPORTS = (
     "dm_op_dpmpp_update",
     "dm_sample_ex_dyn", "dm_op_dyn_threshold", "dm_op_sampler_update_dyn", "dm_op_dpmpp_update_dyn",
     "dm_unet_cond_forward", "dm_unet_cond_backward", "dm_op_deferred_reduce",
+    "dm_eval_bpd", "dm_op_bpd_step_in", "dm_op_bpd_terms", "dm_op_bpd_prior",
 )
 
 
@@ -206,6 +209,18 @@ class LvTrainArgs(C.Structure):
         ("coef_stride", C.c_int32), ("noise", C.c_void_p), ("vb_loss_weight", C.c_float), ("clip_denoised", C.c_int32),
         ("loss_scale", C.c_float), ("accumulate", C.c_int32), ("loss_out_host", C.POINTER(C.c_float)),
         ("model_out", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("stream", C.c_void_p),
+    ]
+
+
+class BpdArgs(C.Structure):
+    """dm_bpd_args (include/dm_hip.h)."""
+    _fields_ = [
+        ("learned", C.c_int32), ("objective", C.c_int32), ("clip_denoised", C.c_int32), ("n_steps", C.c_int32),
+        ("times_host", C.POINTER(C.c_int64)), ("table_host", C.POINTER(C.c_float)),
+        ("x0", C.c_void_p), ("noise", C.c_void_p), ("seed", C.c_uint64), ("sample_offset", C.c_uint64),
+        ("ctx", C.c_void_p), ("ctx_tokens", C.c_int32), ("cond_channels", C.c_int32), ("cond", C.c_void_p),
+        ("prior_sqrt_ac", C.c_float), ("prior_logvar", C.c_float), ("terms_out", C.c_void_p), ("prior_out", C.c_void_p),
+        ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("use_graph", C.c_int32), ("stream", C.c_void_p),
     ]
 
 
@@ -438,6 +453,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_wo_step.argtypes = [fp, fp, fp, C.POINTER(C.c_float), i32, u64, u64, u64, fp, fp, fp, i32, i32, i64, vp]
     lib.dm_op_wo_loss.argtypes = [fp, fp, fp, fp, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, fp, C.POINTER(C.c_float),
                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, i64, vp]
+    lib.dm_eval_bpd.argtypes = [vp, C.POINTER(BpdArgs)]
+    lib.dm_op_bpd_step_in.argtypes = [fp, fp, C.POINTER(C.c_float), u64, u64, u64, fp, i32, i64, vp]
+    lib.dm_op_bpd_terms.argtypes = [fp, fp, fp, fp, C.POINTER(C.c_float), i32, i32, i32, C.POINTER(C.c_float), i32, i64, vp]
+    lib.dm_op_bpd_prior.argtypes = [fp, C.c_float, C.c_float, fp, i32, i64, vp]
     lib.dm_profile_read.argtypes = [C.POINTER(ProfileRow), i32, C.POINTER(i32)]
     lib.dm_unet_cond_forward.argtypes = [vp, i32, i32, vp, fp, vp, C.POINTER(CondBufs), i32, vp]
     lib.dm_unet_cond_backward.argtypes = [vp, C.POINTER(CondBufs), fp, vp, fp, fp, i32, i32, vp]

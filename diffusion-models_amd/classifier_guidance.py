@@ -92,6 +92,8 @@ class ClassifierGuidedGaussianDiffusion(DenoisingDiffusion):
         return grad
 
     _dyn_refusal = NotImplementedError  # dynamic_threshold: this class's loop has its own update kernel
+    _bpd_refusal = ("the guided reverse step shifts the mean by a classifier's gradient, which is no "
+                    "normalised posterior to bound with")
 
     # -- the loop -----------------------------------------------------------------------------------------------------------
     def p_sample_loop(self, shape, return_all_timesteps=False, cond_fn=None, guidance_kwargs=None, *, noise=None, seed=None,

@@ -10,6 +10,7 @@
 #include "learned.h"
 #include "weighted.h"
 #include "cguide.h"
+#include "bpd.h"
 
 #include <array>
 #include <cmath>
@@ -332,7 +333,7 @@ struct dm_unet {
     // the instantiated graph of one denoise step, reused while the key (shape, kind, every captured pointer) holds.  The
     // slot serves every sampling loop of the handle (dm_sampler.inc: run_steps); the kind says whose graph it holds.
     enum GraphKind { GK_NONE = -1, GK_DDPM, GK_DDIM, GK_EDM_HEUN, GK_EDM_DPMPP, GK_CT, GK_REPAINT, GK_LV, GK_CG, GK_WO, GK_DPMPP,
-                     GK_CT_DPMPP };
+                     GK_CT_DPMPP, GK_BPD };
     struct GraphKey {
         int kind = GK_NONE, B = 0, H = 0, W = 0, ctx_tokens = 0, cond_channels = 0, objective = 0, self_cond = 0, guided = 0;
         int ddim_flags = 0;     // DM_DDIM_*: kernel arguments of the captured DDIM update
@@ -340,13 +341,14 @@ struct dm_unet {
         int edm_clamp = 0;      // ElucidatedDiffusion: the clamp flag, a kernel argument of the captured Heun step
         int ct_clip = 0;        // continuous time: the clip flag of the captured ct_step
         int mask_channels = 0;  // RePaint: 1 or C
+        int bpd_flags = 0;      // bits per dim: learned variance (1), clip_denoised (2), kernel arguments of the captured term pass
         const void *noise = nullptr, *all_steps = nullptr, *ws = nullptr, *times = nullptr, *coefs = nullptr;
         const void* tab = nullptr;  // the 16-float-row table (edm_tab_dev) of the EDM, continuous-time and RePaint steps
         const void *cg_mean = nullptr, *cg_grad = nullptr;  // classifier guidance: the caller's tensors the two halves touch
         bool operator==(const GraphKey& o) const {
             return kind == o.kind && B == o.B && H == o.H && W == o.W && ctx_tokens == o.ctx_tokens &&
                    cond_channels == o.cond_channels && objective == o.objective && self_cond == o.self_cond &&
-                   guided == o.guided && ddim_flags == o.ddim_flags && dyn == o.dyn && edm_clamp == o.edm_clamp && ct_clip == o.ct_clip && mask_channels == o.mask_channels &&
+                   guided == o.guided && ddim_flags == o.ddim_flags && dyn == o.dyn && edm_clamp == o.edm_clamp && ct_clip == o.ct_clip && mask_channels == o.mask_channels && bpd_flags == o.bpd_flags &&
                    noise == o.noise && all_steps == o.all_steps && ws == o.ws && times == o.times && coefs == o.coefs &&
                    tab == o.tab && cg_mean == o.cg_mean && cg_grad == o.cg_grad;
         }
@@ -1759,3 +1761,4 @@ int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t eleme
 #include "dm_learned.inc"
 #include "dm_weighted.inc"
 #include "dm_cguide.inc"
+#include "dm_bpd.inc"

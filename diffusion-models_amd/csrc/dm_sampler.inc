@@ -1,8 +1,8 @@
 // The scaffolding every sampling loop on the C ABI runs on -- handle checks, step-table growth, stream choice, workspace,
 // state upload, the eager / captured-graph loop driver -- and the DDPM / DDIM loop behind dm_sample*.  Included by
-// dm_api.hip before dm_edm.inc, dm_ct.inc, dm_repaint.inc, dm_learned.inc, dm_weighted.inc and dm_cguide.inc, whose loops
-// use the same pieces.  A loop keeps what is its own: argument checks, buffer list, prologue, step, graph key and the
-// kernel that writes `out`.  The last four are the table-driven integer-time loops: table_loop_begin / table_loop_end
+// dm_api.hip before dm_edm.inc, dm_ct.inc, dm_repaint.inc, dm_learned.inc, dm_weighted.inc, dm_cguide.inc and dm_bpd.inc
+// (the bits-per-dim evaluation loop, which calls the pieces itself), whose loops use the same pieces.  A loop keeps what is its own: argument checks, buffer list, prologue, step, graph key and the
+// kernel that writes `out`.  dm_repaint.inc .. dm_cguide.inc are the table-driven integer-time loops: table_loop_begin / table_loop_end
 // run the pieces for them, and they keep their argument and U-Net checks, their extra buffers, a prologue kernel, their
 // step lambdas, their extra key fields and their run_steps call.  The EDM and continuous-time loops (float time, no
 // `times`, their own kernel that writes `out`) and sample_impl (the other table pair, guidance buffers) call the pieces

@@ -34,7 +34,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib, _loop
+from . import _lib, _loop, bpd as _bpd
 from .spec import SCHEDULE_BUFFERS, ddim_step_table, ddpm_step_table, dpmpp_step_table, make_schedule
 from .unet import check_guidance
 
@@ -707,6 +707,21 @@ class DenoisingDiffusion:
         """:638-645.  Returns (pred_img, x_start)."""
         return self._p_sample(x, t, noise, {}, x_self_cond, dynamic_threshold)
 
+    # -- bits per dim (Improved DDPM, arXiv 2102.09672: calc_bpd_loop; not in the reference) ---------------------------
+    _bpd_refusal = None  # the reason of the classes that have no bits-per-dim loop
+
+    @torch.inference_mode()
+    def calc_bpd_loop(self, img, clip_denoised=True, *, times=None, noise=None, seed=None, sample_offset=0):
+        """The variational bound of the images ``img`` (what ``forward`` takes), term by term, in bits per dimension: for
+        every timestep ``x_t = q_sample(x0, t, z)``, this class's ``p_mean_variance(x_t, t, clip_denoised)`` and the KL
+        between the true and the predicted posterior (``t > 0``) or the discretised decoder NLL (``t == 0``), with the
+        fixed variance ``posterior_log_variance_clipped``.  Returns a dict: ``vb`` / ``xstart_mse`` / ``mse`` (B, n_times),
+        ``prior_bpd`` (B,), ``total_bpd`` = ``vb.sum(1) + prior_bpd`` (None when ``times`` is a proper subset of the
+        timesteps) and ``times`` (default: all, descending).  ``noise`` (a callable ``shape -> cpu tensor``) is called once
+        per evaluated step; without it the device Philox stream under ``seed`` draws, keyed by the global element index
+        (``sample_offset``: the index of the first image in a sharded batch) and the step."""
+        return _bpd.calc_bpd_loop(self, img, clip_denoised, times=times, noise=noise, seed=seed, sample_offset=sample_offset)
+
 
 class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
     """Pipes ``text_emb`` through the U-Net at every step
@@ -878,6 +893,13 @@ class TextConditionalDenoisingDiffusion(DenoisingDiffusion):
         kw = self._cond_kw(text_emb, cond_scale, rescaled_phi, remove_parallel_component, keep_parallel_frac)
         return self._p_sample(x, t, noise, kw, x_self_cond, dynamic_threshold)
 
+    @torch.inference_mode()
+    def calc_bpd_loop(self, img, clip_denoised=True, *, text_emb=None, times=None, noise=None, seed=None, sample_offset=0):
+        """The parent's loop with the caption embeddings at every step (None: the model's null path).  The bound is that
+        of the conditional model: there are no guidance keywords."""
+        return _bpd.calc_bpd_loop(self, img, clip_denoised, times=times, noise=noise, seed=seed, sample_offset=sample_offset,
+                                  text_emb=text_emb)
+
 
 class ImageConditionalDenoisingDiffusion(DenoisingDiffusion):
     """``ImageConditionalDenoisingDiffusion`` (denoising_diffusion_image_conditional.py:62-229): the condition image
@@ -992,6 +1014,14 @@ class ImageConditionalDenoisingDiffusion(DenoisingDiffusion):
         assert cond is not None, "the image-conditional U-Net needs cond="
         return self._p_sample(x, t, noise, {"cond": cond}, x_self_cond, dynamic_threshold)
 
+    @torch.inference_mode()
+    def calc_bpd_loop(self, img, clip_denoised=True, *, cond=None, times=None, noise=None, seed=None, sample_offset=0):
+        """The parent's loop with the condition image behind x_t at every step."""
+        _bpd.refuse(self)
+        assert cond is not None, "the image-conditional U-Net needs cond="
+        return _bpd.calc_bpd_loop(self, img, clip_denoised, times=times, noise=noise, seed=seed, sample_offset=sample_offset,
+                                  cond=cond)
+
 
 def _first_stage_latents(vae, images):
     """What the latent classes diffuse on, for every first stage ``encode`` of this package returns: a tensor
@@ -1011,6 +1041,7 @@ class LatentDiffusion(DenoisingDiffusion):
     """Diffusion on VAE latents, then decode (latent_diffusion.py:9-66)."""
 
     _dyn_refusal = ValueError  # dynamic_threshold: latents are not bounded to [-1, 1]
+    _bpd_refusal = "the decoder term's 1/255 bins are those of 8-bit images, not of VAE latents"
 
     def __init__(self, model, vae, latent_shape, **kwargs):
         kwargs.setdefault("auto_normalize", True)
@@ -1053,6 +1084,7 @@ class TextConditionalLatentDiffusion(TextConditionalDenoisingDiffusion):
     (:78-99)."""
 
     _dyn_refusal = ValueError  # dynamic_threshold: latents are not bounded to [-1, 1]
+    _bpd_refusal = "the decoder term's 1/255 bins are those of 8-bit images, not of VAE latents"
 
     def __init__(self, model, vae, latent_shape, text_emb_dim=512, **kwargs):
         super().__init__(model=model, image_size=latent_shape[1], **kwargs)
@@ -1097,6 +1129,7 @@ class ImageConditionalLatentDiffusion(ImageConditionalDenoisingDiffusion):
     normalize / unnormalize are the identity (:43-44)."""
 
     _dyn_refusal = ValueError  # dynamic_threshold: latents are not bounded to [-1, 1]
+    _bpd_refusal = "the decoder term's 1/255 bins are those of 8-bit images, not of VAE latents"
 
     def __init__(self, model, vae, latent_shape, init_image_size, cond_vae=None, **kwargs):
         super().__init__(model, image_size=tuple(latent_shape[1:]), **kwargs)

@@ -114,3 +114,34 @@ def sample_global(diffusion, batch_size: int, seed=None, group=None, **sample_kw
                                 **_slice_batch_kwargs(sample_kw, batch_size, lo, hi))
 
     return sample_sharded(shard, batch_size, group)
+
+
+def bpd_global(diffusion, img, seed=None, group=None, **kw):
+    """``diffusion.calc_bpd_loop(img)`` with the rows of ``img`` sharded over the ranks of `group` and the per-image
+    results gathered.  Every rank draws the noise of ITS global image indices (``sample_offset``), so the dict holds the
+    same values for any world size, including 1.  Keyword tensors whose dim 0 equals the batch (``text_emb=``, ``cond=``)
+    are sliced to the rank's rows; an injected ``noise=`` callable sees the shard's shape and is not supported across
+    ranks.  A rank with an empty slice skips the library call and contributes (0, ...) tensors."""
+    from . import bpd as _bpd
+
+    _bpd.refuse(diffusion)
+    seed = shared_seed(seed, group)
+    batch = int(img.shape[0])
+    if not (dist.is_available() and dist.is_initialized()):
+        lo, hi = 0, batch
+    else:
+        lo, hi = shard_bounds(batch, dist.get_world_size(group), dist.get_rank(group))
+    times, full = _bpd.bpd_times(diffusion.num_timesteps, kw.get("times"))
+    if hi > lo:
+        # the normalised list, not the caller's object: an iterator is spent, and a tensor as long as the batch would be sliced
+        rest = {k: v for k, v in kw.items() if k != "times"}
+        local = diffusion.calc_bpd_loop(img[lo:hi], seed=seed, sample_offset=lo, times=times,
+                                        **_slice_batch_kwargs(rest, batch, lo, hi))
+    else:
+        dev = getattr(diffusion, "device", "cpu")
+        local = {k: torch.zeros((0, len(times)), dtype=torch.float32, device=dev) for k in _bpd.KEYS}
+        local["prior_bpd"] = torch.zeros((0,), dtype=torch.float32, device=dev)
+    out = {k: gather_shards(local[k], batch, group) for k in _bpd.KEYS + ("prior_bpd",)}
+    out["total_bpd"] = (out["vb"].double().sum(dim=1) + out["prior_bpd"].double()).float() if full else None
+    out["times"] = list(times)
+    return out

@@ -24,7 +24,7 @@ from typing import Dict, List, Tuple
 
 import torch
 
-from . import _lib, _loop
+from . import _lib, _loop, bpd as _bpd
 from .diffusion import DenoisingDiffusion
 
 COLS = _lib.DM_LV_COEFS
@@ -184,6 +184,14 @@ class LearnedGaussianDiffusion(DenoisingDiffusion):
                 seed = _lib.default_seed()
         out, _, _, x_start = self._step(x, t, None, z, seed)
         return out, x_start
+
+    @torch.inference_mode()
+    def calc_bpd_loop(self, img, clip_denoised=True, *, times=None, noise=None, seed=None, sample_offset=0):
+        """The variational bound of the images, term by term, in bits per dimension (bpd.py) with this class's
+        ``p_mean_variance`` (:93-111): the variance the model predicts, and the first half of its output read as noise.
+        The ``vb`` column of a timestep is the quantity ``p_losses`` weighs with ``vb_loss_weight``, at every t."""
+        return _bpd.calc_bpd_loop(self, img, clip_denoised, times=times, noise=noise, seed=seed, sample_offset=sample_offset,
+                                  learned=True)
 
     # -- training ---------------------------------------------------------------------------------------------------------
     def p_losses(self, x_start, t, noise=None, clip_denoised=False, *, loss_scale=1.0, accumulate=False, sync=True,

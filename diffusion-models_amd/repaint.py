@@ -140,6 +140,8 @@ class GaussianDiffusion(DenoisingDiffusion):
         return gt, mask
 
     _dyn_refusal = NotImplementedError  # dynamic_threshold: this class's loop has its own update kernel
+    _bpd_refusal = ("RePaint is an inpainting sampler over a mask and a known image; it defines no bound on "
+                    "data")
 
     # -- the loop ---------------------------------------------------------------------------------------------------------
     @torch.inference_mode()

@@ -144,6 +144,8 @@ class DenoisingDiffusion1D(DenoisingDiffusion):
         return (self.channels, self.seq_length)
 
     _dyn_refusal = NotImplementedError  # dynamic_threshold: this class's loop has its own update kernel
+    _bpd_refusal = ("the decoder term's 1/255 bins are those of 8-bit images, and the sequence model runs only "
+                    "its pinned DDPM / DDIM loops")
 
     # -- the loops: (B, C, L) at the surface, (B, C, 1, L) at the ABI -------------------------------------------------
     def _run(self, kind, shape, times, coefs, takes_noise, return_all_timesteps, noise, seed, text_emb=None, max_steps=None,

@@ -107,6 +107,8 @@ class WeightedObjectiveGaussianDiffusion(DenoisingDiffusion):
                                                   "not the plain prediction DPM-Solver++ steps on)"))
 
     _dyn_refusal = NotImplementedError  # dynamic_threshold: this class's loop has its own update kernel
+    _bpd_refusal = ("the weighted-objective p_mean_variance blends two predictions per pixel; Improved DDPM's "
+                    "bound is not defined for it here")
 
     # -- sampling ---------------------------------------------------------------------------------------------------------
     @torch.inference_mode()

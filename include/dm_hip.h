@@ -1312,6 +1312,76 @@ int dm_op_cg_mean(const float* x, const float* model_out, const float* c_host, i
 int dm_op_cg_finish(const float* mean, const float* grad, const float* z, const float* c_host, uint64_t seed, uint64_t draw,
                     uint64_t element_offset, float* out, float* guided_out, int B, int64_t per, void* stream);
 
+/* ---- Bits-per-dim evaluation: the variational bound of a batch of real images (Improved DDPM, arXiv 2102.09672:
+ * calc_bpd_loop / _vb_terms_bpd / _prior_bpd), written with the functions of DD/denoising_diffusion.py and
+ * DD/learned_gaussian_diffusion.py.  Not in the reference.  x0 is the normalised image.  The HOST gathers every per-step
+ * scalar in fp32 as `extract` does; row i is DM_BPD_COEFS floats at the step's time t_i:
+ *   c[0]=sqrt_recip_alphas_cumprod   c[1]=sqrt_recipm1_alphas_cumprod   c[2]=posterior_mean_coef1   c[3]=posterior_mean_coef2
+ *   c[4]=posterior_log_variance_clipped   c[5]=1 if t_i == 0 else 0   c[6]=sqrt_alphas_cumprod
+ *   c[7]=sqrt_one_minus_alphas_cumprod   c[8]=log(betas);  the rest 0.
+ * Step i, per image b (every step draws z, t_i == 0 included):
+ *   x_t = c[6] x0 + c[7] z;   model_out = Unet(x_t, t_i [, ctx] [, cond behind x_t])
+ *   pred = x_start by objective from (x_t, model_out) [clamped to [-1, 1] when clip_denoised];  model_mean = c[2] pred + c[3] x_t
+ *   logvar = c[4], or with `learned` (model_out = (eps | v), objective pred_noise) (v + 1) / 2 * c[8] + (1 - (v + 1) / 2) * c[4]
+ *   true_mean = c[2] x0 + c[3] x_t
+ *   terms_out[i][b][0] = meanflat(c[5] ? -discretized_gaussian_log_likelihood(x0, model_mean, 0.5 logvar)
+ *                                      : normal_kl(true_mean, c[4], model_mean, logvar)) / ln 2
+ *   terms_out[i][b][1] = meanflat((pred - x0)^2)
+ *   terms_out[i][b][2] = meanflat(((c[0] x_t - pred) / c[1] - z)^2)
+ * and once per call  prior_out[b] = meanflat(normal_kl(prior_sqrt_ac x0, prior_logvar, 0, 0)) / ln 2  (the caller passes
+ * sqrt_alphas_cumprod[T - 1] and log(1 - alphas_cumprod[T - 1])).
+ * Sums run in double in a fixed order, by image: a result does not depend on the batch around it, nor on use_graph.
+ * The prior term is formed in double as a whole (its fp32 expression cancels to the last ulp of expf).
+ *   learned        1: the U-Net of LearnedGaussianDiffusion (out_dim == 2 * channels);  0: out_dim == channels
+ *   objective      DM_OBJ_* (pred_noise with `learned`)
+ *   times_host     n_steps int64 times;  table_host  n_steps x DM_BPD_COEFS floats
+ *   x0             (B,C,H,W) device, C * H * W % 4 == 0
+ *   noise          NULL -> device Philox noise under `seed` (step i draws i + 1; counters are global element indices:
+ *                  sample_offset is the index of the call's first image in a global batch).  Else (n_steps, B,C,H,W).
+ *   ctx, cond      as in dm_sample_args (text context; the image condition behind x_t)
+ *   terms_out      (n_steps, B, 3) device;  prior_out  NULL or (B) device
+ *   use_graph      one step is captured as a hipGraph, cached on the handle per (B, H, W, learned, objective,
+ *                  clip_denoised, ctx_tokens, cond_channels, noise pointer) in the slot dm_sample uses, under a kind of its
+ *                  own; times, tables, step count, seed and offset are device data and do not re-capture. */
+#define DM_BPD_COEFS 16
+#define DM_BPD_CHUNK 1024 /* elements of an image that one workgroup of the term kernel sums */
+typedef struct dm_bpd_args {
+    int32_t learned;
+    int32_t objective;
+    int32_t clip_denoised;
+    int32_t n_steps;
+    const int64_t* times_host;
+    const float* table_host;
+    const float* x0;
+    const float* noise;
+    uint64_t seed;
+    uint64_t sample_offset;
+    const float* ctx;
+    int32_t ctx_tokens;
+    int32_t cond_channels;
+    const float* cond;
+    float prior_sqrt_ac;
+    float prior_logvar;
+    float* terms_out;
+    float* prior_out;
+    int32_t B, H, W;
+    int32_t use_graph;
+    void* stream;
+} dm_bpd_args;
+int dm_eval_bpd(dm_unet* u, const dm_bpd_args* args);
+
+/* The kernels on their own.  Tensors are on the device, B * per floats (model_out 2 * B * per with `learned`: image b's
+ * prediction half, then its variance half), per % 4 == 0, 16-byte aligned; c_host is one row of DM_BPD_COEFS floats on the host.
+ *   step_in:  x_t = c[6] x0 + c[7] z.  z NULL: Philox draw `draw` (>= 1) under `seed`, counters from element_offset.
+ *   terms:    terms_out_host (B, 3) on the host, as terms_out[i] above, from the given model_out, x0, x_t and z.
+ *   prior:    prior (B) on the device, as prior_out above; the call does not wait.
+ * step_in and terms wait for their result. */
+int dm_op_bpd_step_in(const float* x0, const float* z, const float* c_host, uint64_t seed, uint64_t draw, uint64_t element_offset,
+                      float* x_t, int B, int64_t per, void* stream);
+int dm_op_bpd_terms(const float* model_out, const float* x0, const float* x_t, const float* z, const float* c_host, int learned,
+                    int objective, int clip_denoised, float* terms_out_host, int B, int64_t per, void* stream);
+int dm_op_bpd_prior(const float* x0, float sqrt_ac, float logvar, float* prior, int B, int64_t per, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
