@@ -47,6 +47,7 @@ EXPORTS = (
     "dm_op_sampler_update_ex", "dm_op_conv1d", "dm_op_block1d",
     "dm_op_group_norm", "dm_op_vae_attention", "dm_op_vq_nearest",
     "dm_op_vq_nearest_nchw", "dm_op_kl_posterior", "dm_op_embed_code",
+    "dm_op_vae_conv", "dm_op_vae_resblock", "dm_op_vae_attn_block",
     "dm_conv_create", "dm_conv_destroy", "dm_conv_forward", "dm_op_pool2d", "dm_op_resize_bilinear",
     "dm_op_copy_channels_nhwc", "dm_op_global_avgpool", "dm_op_linear",
     "dm_unet_train_enable", "dm_unet_grad_floats", "dm_unet_grads_flat", "dm_unet_train_buckets", "dm_unet_train_bucket", "dm_unet_get_grad", "dm_unet_loss_backward", "dm_unet_loss_backward_ex", "dm_unet_loss_backward_masked", "dm_op_q_sample", "dm_op_linear_bwd",
@@ -354,6 +355,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_op_cfg_combine.argtypes = [fp, fp, fp, i32, i64, C.c_float, C.c_float, i32, C.c_float, vp]
     lib.dm_op_group_norm.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, C.c_float, i32, vp]
     lib.dm_op_vae_attention.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, vp]
+    lib.dm_op_vae_conv.argtypes = [fp] * 4 + [i32] * 12 + [vp]
+    lib.dm_op_vae_resblock.argtypes = [fp] * 12 + [i32] * 5 + [vp]
+    lib.dm_op_vae_attn_block.argtypes = [fp] * 12 + [i32] * 4 + [vp]
     lib.dm_op_vq_nearest.argtypes = [fp, fp, fp, vp, i64, i32, i32, i32, vp]
     lib.dm_op_vq_nearest_nchw.argtypes = [fp, fp, fp, vp, i64, i32, i32, i32, vp]
     lib.dm_op_kl_posterior.argtypes = [fp, i32, fp, u64, u64, u64, i32, fp, fp, fp, i32, i32, i32, vp]

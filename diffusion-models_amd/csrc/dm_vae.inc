@@ -28,9 +28,10 @@ struct VaeNode {
     std::string prefix;  // parameter-name prefix
     int cin, cout;
     int level;  // resolution level of the node's output, the reference's i_level: resolution >> level
-    // VAE_CONV: k x k taps; `up`: nearest x2 in front; in_nchw / out_nchw: the network's input / output tensor
+    // VAE_CONV: k x k taps; `up`: nearest x2 in front; in_nchw / out_nchw: the network's input / output tensor; every
+    // convolution of the networks has a bias (dm_op_vae_conv may leave it out)
     int k = 1, stride = 1, pad = 0, pad_hi = 0;
-    bool up = false, in_nchw = false, out_nchw = false;
+    bool up = false, in_nchw = false, out_nchw = false, bias = true;
     // the layer, by kind
     VaeRes res;
     VaeAttn attn;
@@ -178,7 +179,7 @@ static void expect_node(dm_unet* u, const VaeNode& N) {
         break;
     case VAE_CONV:
         expect(u, N.prefix + ".weight", {N.cout, N.cin, N.k, N.k});
-        expect(u, N.prefix + ".bias", {N.cout});
+        if (N.bias) expect(u, N.prefix + ".bias", {N.cout});
         break;
     }
 }
@@ -210,8 +211,8 @@ static int build_node(dm_unet* u, VaeNode& N) {
     case VAE_ATTN: return vbuild_attn(u, N.attn, N.prefix, N.cin);
     case VAE_NORM: return up1(u, N.prefix + ".weight", &N.nw) || up1(u, N.prefix + ".bias", &N.nb);
     case VAE_CONV:
-        return make_conv(u, N.conv, N.prefix + ".weight", N.prefix + ".bias", N.cout, N.cin, 0, N.k, N.k, N.stride, N.pad, N.up,
-                         N.pad_hi);
+        return make_conv(u, N.conv, N.prefix + ".weight", N.bias ? N.prefix + ".bias" : "", N.cout, N.cin, 0, N.k, N.k, N.stride,
+                         N.pad, N.up, N.pad_hi);
     }
     return 1;
 }
@@ -270,6 +271,16 @@ static int vrun_attn(Ctx& c, const VaeAttn& At, const float* x, int H, int W, fl
     return 0;
 }
 
+// One VAE_CONV node on `cur` of *h x *w pixels (run_trunk and dm_op_vae_conv): the output size into *h, *w; the output into
+// `out`, or into a buffer of the arena when there is none; *y is where it went.
+static int vrun_conv(Ctx& c, const VaeNode& N, const float* cur, int* h, int* w, float* out, float** y) {
+    const int hin = N.up ? 2 * *h : *h, win = N.up ? 2 * *w : *w;  // run_conv takes the size behind the nearest x2
+    *h = (hin + 2 * N.pad + N.pad_hi - N.k) / N.stride + 1;
+    *w = (win + 2 * N.pad + N.pad_hi - N.k) / N.stride + 1;
+    *y = out ? out : c.A->alloc((size_t)c.B * *h * *w * N.cout);
+    return run_conv(c, N.conv, cur, nullptr, hin, win, *y, 0, nullptr, nullptr, nullptr, N.in_nchw, N.out_nchw);
+}
+
 // The trunk on x of h x w pixels.  Every node's output is a buffer of the arena that nothing releases, except that the last
 // node writes to `out` when there is one.  *last, *h_out, *w_out (each may be null): the last node's output as pixel rows,
 // or `out`, and its size.
@@ -291,14 +302,9 @@ static int run_trunk(VaeHandle* d, Arena& A, const float* x, float* out, int B, 
             y = A.alloc((size_t)B * h * w * N.cin);
             if (!A.dry && launch_group_norm(cur, N.nw, N.nb, y, stats, B, h * w, N.cin, 32, 1e-6f, 1, s)) return 1;
             break;
-        case VAE_CONV: {  // run_conv takes the size behind the nearest x2
-            const int hin = N.up ? 2 * h : h, win = N.up ? 2 * w : w;
-            h = (hin + 2 * N.pad + N.pad_hi - N.k) / N.stride + 1;
-            w = (win + 2 * N.pad + N.pad_hi - N.k) / N.stride + 1;
-            y = out && &N == &d->trunk.back() ? out : A.alloc((size_t)B * h * w * N.cout);
-            if (run_conv(c, N.conv, cur, nullptr, hin, win, y, 0, nullptr, nullptr, nullptr, N.in_nchw, N.out_nchw)) return 1;
+        case VAE_CONV:
+            if (vrun_conv(c, N, cur, &h, &w, &N == &d->trunk.back() ? out : nullptr, &y)) return 1;
             break;
-        }
         }
         cur = y;
     }
@@ -566,9 +572,75 @@ static int vq_nearest_op(const float* z, const float* codebook, float* zq_nchw, 
     return finish_vae_op(rc, s, e2);
 }
 
+// One node of the trunk on its own (dm_op_vae_conv, dm_op_vae_resblock, dm_op_vae_attn_block).  `params`: the node's
+// parameters as device pointers in the order of expect_node; they go through the host into a handle of their own, which
+// build_node packs and uploads as it does for the networks.  `x` -> `out` in the layouts of the trunk.
+static int vae_node_op(VaeNode& N, std::initializer_list<const float*> params, const float* x, float* out, int B, int H, int W,
+                       void* stream) {
+    DM_REQUIRE(x && out, "null argument");
+    DM_REQUIRE(B > 0 && H > 0 && W > 0 && N.cin > 0 && N.cout > 0, "empty input");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    dm_unet dummy;
+    init_dummy(dummy, 4, 32);
+    expect_node(&dummy, N);
+    DM_REQUIRE(params.size() == dummy.order.size(), "parameter list of another node kind");
+    auto p = params.begin();
+    for (const std::string& name : dummy.order) {
+        DM_REQUIRE(*p, "null argument");
+        HostTensor& t = dummy.params[name];
+        if (d2h(*p++, t.numel(), t.data)) return 1;
+        t.set = true;
+    }
+    if (build_node(&dummy, N)) return 1;
+    return run_op(s, [&](Arena& A) -> int {
+        Ctx c{&dummy, &A, s, B, nullptr, 0};
+        float* y = nullptr;
+        int h = H, w = W;
+        if (N.kind == VAE_CONV) return vrun_conv(c, N, x, &h, &w, out, &y);
+        float* stats = A.alloc(group_stats_ws_floats(B, 32));
+        if (N.kind == VAE_RES ? vrun_res(c, N.res, x, H, W, stats, &y) : vrun_attn(c, N.attn, x, H, W, stats, &y)) return 1;
+        if (!A.dry)
+            DM_CHECK_HIP(hipMemcpyAsync(out, y, (size_t)B * H * W * N.cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+        return 0;
+    });
+}
+
 }  // namespace dm
 
 extern "C" {
+
+int dm_op_vae_conv(const float* in, const float* weight, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
+                   int k, int stride, int pad, int pad_hi, int up, int in_nchw, int out_nchw, void* stream) {
+    DM_REQUIRE(weight, "null argument");
+    DM_REQUIRE(k > 0 && stride > 0 && pad >= 0 && pad_hi >= 0, "VAE conv: k, stride > 0 and pad, pad_hi >= 0");
+    const int hin = up ? 2 * H : H, win = up ? 2 * W : W;
+    DM_REQUIRE(hin + 2 * pad + pad_hi >= k && win + 2 * pad + pad_hi >= k, "VAE conv: the kernel is larger than the padded image");
+    dm::VaeNode N{dm::VAE_CONV, "op", Cin, Cout, 0};
+    N.k = k; N.stride = stride; N.pad = pad; N.pad_hi = pad_hi;
+    N.up = up != 0; N.in_nchw = in_nchw != 0; N.out_nchw = out_nchw != 0; N.bias = bias != nullptr;
+    if (bias) return dm::vae_node_op(N, {weight, bias}, in, out, B, H, W, stream);
+    return dm::vae_node_op(N, {weight}, in, out, B, H, W, stream);
+}
+
+int dm_op_vae_resblock(const float* x, const float* norm1_w, const float* norm1_b, const float* conv1_w, const float* conv1_b,
+                       const float* norm2_w, const float* norm2_b, const float* conv2_w, const float* conv2_b,
+                       const float* nin_w, const float* nin_b, float* out, int B, int H, int W, int cin, int cout,
+                       void* stream) {
+    DM_REQUIRE((nin_w == nullptr) == (cin == cout) && (nin_b == nullptr) == (cin == cout),
+               "nin_shortcut is given exactly when cin != cout");
+    dm::VaeNode N{dm::VAE_RES, "op", cin, cout, 0};
+    if (cin == cout)
+        return dm::vae_node_op(N, {norm1_w, norm1_b, conv1_w, conv1_b, norm2_w, norm2_b, conv2_w, conv2_b}, x, out, B, H, W, stream);
+    return dm::vae_node_op(N, {norm1_w, norm1_b, conv1_w, conv1_b, norm2_w, norm2_b, conv2_w, conv2_b, nin_w, nin_b}, x, out, B,
+                           H, W, stream);
+}
+
+int dm_op_vae_attn_block(const float* x, const float* norm_w, const float* norm_b, const float* q_w, const float* q_b,
+                         const float* k_w, const float* k_b, const float* v_w, const float* v_b, const float* proj_w,
+                         const float* proj_b, float* out, int B, int H, int W, int C, void* stream) {
+    dm::VaeNode N{dm::VAE_ATTN, "op", C, C, 0};
+    return dm::vae_node_op(N, {norm_w, norm_b, q_w, q_b, k_w, k_b, v_w, v_b, proj_w, proj_b}, x, out, B, H, W, stream);
+}
 
 int dm_op_group_norm(const float* x_nhwc, const float* weight, const float* bias, float* y_nhwc, int B, int HW, int C,
                      int groups, float eps, int swish, void* stream) {

@@ -403,6 +403,25 @@ int dm_op_group_norm(const float* x_nhwc, const float* weight, const float* bias
  * (B, n, C) rows.  kernel 0: the kernel the model dispatches for (n, C); 1: the one-row-per-wavefront kernel. */
 int dm_op_vae_attention(const float* q, const float* k, const float* v, float* out, int B, int n, int C, int kernel,
                         void* stream);
+/* One node of the first-stage trunk on its own, through the code the decoder / encoder forward runs for it.  Parameters are
+ * DEVICE pointers in the reference layout (OIHW weights), packed per call; the operator workspace starts as NaNs; every
+ * call synchronises.
+ * A plain convolution node (k x k, stride, `pad` on every side and `pad_hi` more rows / columns of zeros below and right,
+ * `up`: nearest x2 in front; H, W: the size in front of it).  in (B, Cin, H, W) when in_nchw, else pixel rows (B * H * W,
+ * Cin); out (B, Cout, Ho, Wo) when out_nchw, else pixel rows; Ho = (H' + 2 pad + pad_hi - k) / stride + 1 with H' = 2 H
+ * behind `up`.  bias may be NULL. */
+int dm_op_vae_conv(const float* in, const float* weight, const float* bias, float* out, int B, int H, int W, int Cin, int Cout,
+                   int k, int stride, int pad, int pad_hi, int up, int in_nchw, int out_nchw, void* stream);
+/* ResnetBlock with temb = None (model.py:138-158) on pixel rows x (B * H * W, cin) -> out (B * H * W, cout); nin_w, nin_b
+ * (the 1x1 nin_shortcut) are NULL exactly when cin == cout. */
+int dm_op_vae_resblock(const float* x, const float* norm1_w, const float* norm1_b, const float* conv1_w, const float* conv1_b,
+                       const float* norm2_w, const float* norm2_b, const float* conv2_w, const float* conv2_b,
+                       const float* nin_w, const float* nin_b, float* out, int B, int H, int W, int cin, int cout,
+                       void* stream);
+/* AttnBlock (model.py:195-219) on pixel rows x, out (B * H * W, C); the weights of q, k, v, proj_out are (C, C, 1, 1). */
+int dm_op_vae_attn_block(const float* x, const float* norm_w, const float* norm_b, const float* q_w, const float* q_b,
+                         const float* k_w, const float* k_b, const float* v_w, const float* v_b, const float* proj_w,
+                         const float* proj_b, float* out, int B, int H, int W, int C, void* stream);
 /* The codebook search of VQModel.encode: z_rows (pixels, E), codebook (n_embed, E) -> zq_nchw (pixels / hw, E, hw) =
  * z + (nearest code - z) and indices (pixels, may be NULL); ties go to the lower index. */
 int dm_op_vq_nearest(const float* z_rows, const float* codebook, float* zq_nchw, int32_t* indices, int64_t pixels, int E,

@@ -31,15 +31,15 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_checks
 import conv_restate as cr
+from conv_checks import dev, family_input, nans, profiled_call, seeded
 from diffusion_models_amd import _lib
 from oracle import unet_oracle as uo
 
 pytestmark = pytest.mark.gpu
 TOL_FWD = 2e-5
 TOL_BWD = 5e-5
-FACTOR = 4.0
-DEV = "cuda:0"
 
 
 def config():
@@ -52,9 +52,6 @@ def config():
 
 
 CFG = config()
-PREFIX = {"conv": "conv<", "wino": "wino ", "wino4": "wino4<", "upwino": "upwino<", "pw": "pw<", "init7": "init7 "}
-KERNEL = {"conv": "conv_mfma", "wino": "wino_mfma", "wino4": "wino4_mfma", "upwino": "upwino_mfma", "pw": "pw_mfma",
-          "init7": "init7_mfma"}
 WGRAD_MODE = {"direct": 0, "1x1": 1, "s2d": 2, "wino": 3}
 COUNTS = collections.Counter()
 
@@ -69,33 +66,6 @@ def profiled():
     print(f"\nconv families [{CFG}]: cases per family / weight-gradient mode")
     for name, n in sorted(COUNTS.items()):
         print(f"  {name}: {n}")
-
-
-def seeded(shape, seed, scale=1.0):
-    return torch.randn(shape, generator=torch.Generator().manual_seed(seed)) * scale
-
-
-def dev(t):
-    return None if t is None else t.to(DEV).contiguous()
-
-
-def nans(*shape):
-    return torch.full(shape, float("nan"), device=DEV)
-
-
-def family_input(t, family, seed):
-    """randn: t as drawn.  offset: t + 4 (activations behind SiLU).  wide: channel c times exp(u_c), u spread evenly over
-    [-4.6, 4.6] and shuffled.  flat: 4 + 0.01 t (the F(4x4) input transform cancels)."""
-    if family == "randn":
-        return t
-    if family == "offset":
-        return t + 4
-    if family == "flat":
-        return 4 + 0.01 * t
-    assert family == "wide"
-    C = t.shape[1]
-    u = torch.linspace(-4.6, 4.6, C)[torch.randperm(C, generator=torch.Generator().manual_seed(seed))]
-    return t * torch.exp(u)[None, :, None, None]
 
 
 def expected(exp):
@@ -117,24 +87,8 @@ def runs_here(exp, wgrad=None):
     return any(t in exp["default"] for t in (" q1", " r1")) or wgrad == "wino"
 
 
-def profiled_call(fn):
-    _lib.profile_read()
-    fn()
-    return [r["kernel"] for r in _lib.profile_read()]
-
-
 def assert_row(label, rows, family, shape, tokens=()):
-    """A row of `family` (PREFIX) with the layer `shape` in its name; tokens: q1 / q2 / r1 / r4 literally, 'k>1' a K split."""
-    hits = [r for r in rows if r.startswith(PREFIX[family]) and shape in r]
-    assert hits, (label, f"no {KERNEL[family]} row with '{shape}'", rows)
-    for tok in tokens:
-        if tok == "k>1":
-            k = [int(m.group(1)) for r in hits for m in [re.search(r" k(\d+)", r)] if m]
-            assert k and max(k) > 1, (label, "no K split", hits)
-        else:
-            assert any(f" {tok}" in r for r in hits), (label, f"no row with {tok}", hits)
-    COUNTS[KERNEL[family]] += 1
-    return hits[0]
+    return conv_checks.assert_row(COUNTS, label, rows, family, shape, tokens)
 
 
 def assert_wgrad_row(label, rows, mode, shape, split):
@@ -147,35 +101,9 @@ def assert_wgrad_row(label, rows, mode, shape, split):
     return hits[0]
 
 
-def metrics(got, ref):
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
-    d = got - ref
-    return (float(d.norm() / ref.norm().clamp_min(1e-300)),
-            float(d.abs().max() / ref.pow(2).mean().sqrt().clamp_min(1e-300)))
-
-
-class Checker:
-    """Prints, then asserts at the end, every tensor of one case: no tensor hides behind the first failure."""
-
+class Checker(conv_checks.Checker):
     def __init__(self, label, family, bound):
-        self.label, self.family, self.bound, self.bad = label, family, bound, []
-
-    def __call__(self, tensor, kernel, got, ref64, floor32):
-        e = metrics(got, ref64)
-        f = metrics(floor32, ref64)
-        lim = [FACTOR * f[0], FACTOR * f[1]]
-        if self.family == "randn":
-            lim[0] = min(lim[0], self.bound)
-        print(f"conv_families[{CFG}] {self.label} {tensor} {kernel}: rel-L2 kernel {e[0]:.3g} floor {f[0]:.3g} limit "
-              f"{lim[0]:.3g} | max/rms kernel {e[1]:.3g} floor {f[1]:.3g} limit {lim[1]:.3g}")
-        if not torch.isfinite(got).all():
-            self.bad.append((tensor, "not finite", int((~torch.isfinite(got)).sum())))
-        elif e[0] > lim[0] or e[1] > lim[1]:
-            self.bad.append((tensor, kernel, e, lim))
-
-    def done(self):
-        COUNTS["cases run"] += 1
-        assert not self.bad, (self.label, self.bad)
+        super().__init__(f"conv_families[{CFG}]", COUNTS, label, family, bound)
 
 
 RESTATE = {"conv": "direct", "pw": "direct", "init7": "direct", "wino": "wino", "wino4": "wino4", "upwino": "upwino"}
