@@ -6,12 +6,14 @@ for); import it as ``diffusion_models_amd`` through the shim at the repo root.
 from .spec import (  # noqa: F401
     DecoderConfig,
     EncoderConfig,
+    KarrasUnetConfig,
     Unet1DConfig,
     UnetConfig,
     autoencoder_kl_param_spec,
     ddim_time_pairs,
     decoder_param_spec,
     encoder_param_spec,
+    karras_unet_param_spec,
     make_schedule,
     unet1d_param_spec,
     unet_param_spec,
@@ -36,6 +38,7 @@ from .repaint import GaussianDiffusion as RePaintGaussianDiffusion, RepaintTable
 from .learned import LearnedGaussianDiffusion, lv_step_table, lv_train_table  # noqa: F401
 from .weighted import WeightedObjectiveGaussianDiffusion, wo_step_table, wo_train_table  # noqa: F401
 from .seq1d import DenoisingDiffusion1D, Unet1D  # noqa: F401
+from .karras import KarrasUnet  # noqa: F401
 from .classifier_guidance import ClassifierGuidedGaussianDiffusion, cg_step_table  # noqa: F401
 from .vae import (AutoencoderKL, DiagonalGaussianDistribution, KLEncoder, VQDecoder, VQEncoder, VQModel,  # noqa: F401
                   VQModelInterface)
@@ -65,6 +68,9 @@ __all__ = [
     "DenoisingDiffusion1D",
     "Unet1DConfig",
     "unet1d_param_spec",
+    "KarrasUnet",
+    "KarrasUnetConfig",
+    "karras_unet_param_spec",
     "VQDecoder",
     "VQEncoder",
     "VQModel",

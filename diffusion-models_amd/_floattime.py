@@ -80,7 +80,8 @@ class FloatTimeDiffusion:
         from .unet import Unet
 
         unet = self._unet
-        if not isinstance(unet, Unet) or getattr(unet, "_handle", None) is None or not hasattr(self._lib, self._train_entry):
+        if (not isinstance(unet, Unet) or not unet.float_time_training or getattr(unet, "_handle", None) is None
+                or not hasattr(self._lib, self._train_entry)):
             raise NotImplementedError(f"{type(self).__name__} can train a library Unet only (dm_unet_train_enable_ft arms its "
                                       f"handle for the float-time training loss); got {type(unet).__name__}")
         return unet

@@ -76,6 +76,9 @@ EXPORTS = (
     "dm_sample_ex_dyn", "dm_op_dyn_threshold", "dm_op_sampler_update_dyn", "dm_op_dpmpp_update_dyn",
     "dm_unet_cond_forward", "dm_unet_cond_backward", "dm_op_deferred_reduce",
     "dm_eval_bpd", "dm_op_bpd_step_in", "dm_op_bpd_terms", "dm_op_bpd_prior",
+    "dm_kunet_create", "dm_kunet_set_class_labels",
+    "dm_op_kunet_pixelnorm", "dm_op_kunet_avgpool2", "dm_op_kunet_bilinear_up2", "dm_op_kunet_act", "dm_op_kunet_attention",
+    "dm_op_kunet_head", "dm_op_kunet_input_block", "dm_op_kunet_output_block", "dm_op_kunet_block",
 )
 
 
@@ -88,6 +91,29 @@ class UnetCfg(C.Structure):
         ("text_mode", C.c_int32), ("text_emb_dim", C.c_int32), ("sinusoidal_theta", C.c_float),
         ("learned_sinusoidal_dim", C.c_int32), ("attn_heads_stage", C.c_int32 * DM_MAX_STAGES),
         ("seq1d", C.c_int32),
+    ]
+
+
+class KunetCfg(C.Structure):
+    """dm_kunet_cfg (include/dm_hip.h)."""
+    _fields_ = [
+        ("image_size", C.c_int32), ("dim", C.c_int32), ("dim_max", C.c_int32), ("num_classes", C.c_int32),
+        ("channels", C.c_int32), ("input_channels", C.c_int32), ("num_downsamples", C.c_int32),
+        ("num_blocks_per_stage", C.c_int32), ("n_attn_res", C.c_int32), ("attn_res", C.c_int32 * DM_MAX_STAGES),
+        ("fourier_dim", C.c_int32), ("attn_dim_head", C.c_int32),
+        ("mp_cat_t", C.c_float), ("mp_add_emb_t", C.c_float), ("attn_res_mp_add_t", C.c_float), ("resnet_mp_add_t", C.c_float),
+    ]
+
+
+class KunetBlockOp(C.Structure):
+    """dm_kunet_block_op (include/dm_hip.h): one Encoder / Decoder of KarrasUnet on its own."""
+    _fields_ = [
+        ("decoder", C.c_int32), ("down", C.c_int32), ("up", C.c_int32), ("skip", C.c_int32), ("attn", C.c_int32),
+        ("din", C.c_int32), ("dout", C.c_int32), ("skip_channels", C.c_int32), ("dh", C.c_int32),
+        ("mp_cat_t", C.c_float), ("attn_res_mp_add_t", C.c_float), ("resnet_mp_add_t", C.c_float),
+        ("x", C.c_void_p), ("skip_x", C.c_void_p), ("emb_scale", C.c_void_p), ("down_w", C.c_void_p), ("w1", C.c_void_p),
+        ("w2", C.c_void_p), ("res_w", C.c_void_p), ("mem_kv", C.c_void_p), ("qkv_w", C.c_void_p), ("out_w", C.c_void_p),
+        ("out", C.c_void_p), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
     ]
 
 
@@ -465,6 +491,18 @@ def _declare(lib: C.CDLL) -> None:
     lib.dm_unet_cond_forward.argtypes = [vp, i32, i32, vp, fp, vp, C.POINTER(CondBufs), i32, vp]
     lib.dm_unet_cond_backward.argtypes = [vp, C.POINTER(CondBufs), fp, vp, fp, fp, i32, i32, vp]
     lib.dm_op_deferred_reduce.argtypes = [C.POINTER(ReduceLayer), i32, i32, i32, i32, vp]
+    lib.dm_kunet_create.argtypes = [C.POINTER(KunetCfg), i32, C.POINTER(vp)]
+    lib.dm_kunet_set_class_labels.argtypes = [vp, fp, i32]
+    lib.dm_op_kunet_pixelnorm.argtypes = [fp, fp, fp, i64, i32, C.c_float, vp]
+    lib.dm_op_kunet_avgpool2.argtypes = [fp, fp, i32, i32, i32, i32, vp]
+    lib.dm_op_kunet_bilinear_up2.argtypes = [fp, fp, fp, fp, i32, i32, i32, i32, C.c_float, vp]
+    lib.dm_op_kunet_act.argtypes = [fp, i32, C.c_float, fp, i32, C.c_float, fp, fp, C.c_float, i64, vp]
+    lib.dm_op_kunet_attention.argtypes = [fp, fp, fp, i32, i32, i32, i32, vp]
+    lib.dm_op_kunet_head.argtypes = [fp, fp, fp, fp, fp, fp, C.POINTER(C.c_int32), C.POINTER(C.c_float), i32, i32, i32, i32,
+                                     C.c_float, fp, i32, vp]
+    lib.dm_op_kunet_input_block.argtypes = [fp, fp, fp, i32, i32, i32, i32, i32, vp]
+    lib.dm_op_kunet_output_block.argtypes = [fp, fp, C.c_float, fp, i32, i32, i32, i32, i32, vp]
+    lib.dm_op_kunet_block.argtypes = [C.POINTER(KunetBlockOp), vp]
 
 
 class TrainArgs(C.Structure):

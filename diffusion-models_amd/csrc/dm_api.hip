@@ -12,6 +12,7 @@
 #include "cguide.h"
 #include "bpd.h"
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdlib>
@@ -288,6 +289,7 @@ struct Stage {
 
 struct TrainState;  // dm_train.inc
 struct UnetGraph;   // unet_graph.inc
+struct KUnet;       // dm_kunet.inc
 
 }  // namespace dm
 
@@ -305,6 +307,8 @@ struct dm_unet {
     bool finalized = false;
     bool poisoned = false;  // a refresh failed half-way: device weights are a mix of old and new values
     dm::TrainState* train = nullptr;  // dm_unet_train_enable: gradient buffers, dgrad weights, training workspace
+    dm::KUnet* kunet = nullptr;       // dm_kunet_create: the handle is a KarrasUnet (dm_kunet.inc); the image / sequence
+                                      // layers below stay empty, `params`, `own`, the workspace and the graph slot serve both
     std::vector<dm::PackOp> pack_ops;  // recipe of every buffer the convolutions / norms read (device-side re-packing)
     bool infer_stale = false;          // device-side optimiser steps since the fused inference-only packs were built
     DeviceOwner own;
@@ -393,6 +397,10 @@ struct dm_unet {
 namespace dm {
 
 void free_train(dm_unet* u);  // dm_train.inc
+void kunet_free(dm_unet* u);  // dm_kunet.inc
+static int kunet_build_all(dm_unet* u);
+static int kunet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const SamplerState* step_dev, float* out_nchw, int B,
+                              int H, int W, hipStream_t s, const float* tf, int tf_stride);
 static int ensure_packed(dm_unet* u, const float* w, hipStream_t s);
 static int build_train(dm_unet* u);
 static int upload_master_if_resident(dm_unet* u);
@@ -802,6 +810,7 @@ static int build_cross(dm_unet* u, CrossLayer& C, const std::string& p, int dim)
 // Pack every parameter into its kernel layout and upload it: the first build (dm_unet_finalize) and, with
 // own.refreshing set, the in-place refresh of changed parameters (dm_unet_refresh).
 static int build_all(dm_unet* u) {
+    if (u->kunet) return kunet_build_all(u);
     const dm_unet_cfg& cfg = u->cfg;
     const int n = cfg.n_stages;
     // sinusoid frequencies, fp32 as the reference computes them (DD/denoising_diffusion.py:79-81)
@@ -1376,6 +1385,10 @@ static int unet_forward_impl(dm_unet* u, Arena& A, const float* x_nchw, const in
     // read, the masked-out ones included, and their values do not reach the output.
     const dm_unet_cfg& cfg = u->cfg;
     DM_REQUIRE(!tmask || (ctx && cfg.text_mode != DM_TEXT_NONE), "a text mask needs a text-conditional U-Net and a context");
+    if (u->kunet) {
+        DM_REQUIRE(!ctx, "KarrasUnet has no text condition");
+        return kunet_forward_impl(u, A, x_nchw, step_dev, out_nchw, B, H, W, s, tf, tf_stride);
+    }
     Ctx c{u, &A, s, B, nullptr, 0};
     const bool text_cross = cfg.text_mode == DM_TEXT_CROSS && ctx != nullptr;
     // one context token: the three CrossAttention layers ignore their image input (run_cross), which makes everything
@@ -1450,8 +1463,13 @@ static int ensure_workspace(dm_unet* u, size_t bytes) {
     return 0;
 }
 
+static int kunet_image_size(const dm_unet* u);  // dm_kunet.inc
 static int check_hw(dm_unet* u, int H, int W) {
     int f = 1 << (u->cfg.n_stages - 1);
+    if (u->kunet) {  // KarrasUnet.forward asserts the square image_size it was built for (the attention layers are placed by it)
+        DM_REQUIRE(H == W && H == kunet_image_size(u), "KarrasUnet: the input must be image_size x image_size");
+        return 0;
+    }
     if (u->cfg.seq1d) {
         DM_REQUIRE(H == 1, "a sequence model takes (B, C, L) as H = 1, W = L");
         if (W <= 0 || W % f) {
@@ -1563,6 +1581,7 @@ void dm_unet_destroy(dm_unet* u) {
     if (!u) return;
     (void)hipSetDevice(u->device);
     if (u->train) free_train(u);
+    kunet_free(u);
     u->drop_graph();
     if (u->cap_stream) (void)hipStreamDestroy(u->cap_stream);
     if (u->done_ev) (void)hipEventDestroy(u->done_ev);
@@ -1700,6 +1719,7 @@ int dm_unet_forward(dm_unet* u, const float* x, const int64_t* time, const float
     DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
     DM_REQUIRE(!u->infer_stale, "parameters were updated on the device (dm_unet_optimizer_step): call dm_unet_train_sync "
                                 "before sampling from this handle");
+    DM_REQUIRE(!u->kunet, "a KarrasUnet handle takes a real-valued time: dm_unet_forward_ft and dm_sample_edm");
     DM_REQUIRE(B > 0, "empty batch");
     if (check_hw(u, H, W)) return 1;
     DM_CHECK_HIP(hipSetDevice(u->device));
@@ -1750,6 +1770,7 @@ int dm_randn(float* out, int64_t n, uint64_t seed, uint64_t draw, uint64_t eleme
 // single-operator entry points (dm_op_*) and the VAE decoder share the helpers above
 #include "dm_op_scaffold.inc"
 #include "dm_ops.inc"
+#include "dm_kunet.inc"
 #include "dm_vae.inc"
 #include "dm_consumer.inc"
 #include "dm_train.inc"

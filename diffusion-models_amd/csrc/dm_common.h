@@ -556,4 +556,29 @@ int launch_attention_core_bwd(const float* qkv, const float* mem_kv, const float
 int launch_cross_attention_core_bwd(const float* q, const float* k, const float* v, const float* dout, float* dq, float* dk,
                                     float* dv, float* ws, int B, int nq, int m, int heads, int dh, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------
+// KarrasUnet passes (karras.hip): NHWC fp32, channel counts that are multiples of 4.  Every output pointer is optional
+// where the comment says so; constants are the folded magnitude-preserving factors (dm_kunet.inc).
+// ---------------------------------------------------------------------------------------
+// y = x / max(||x||, 1e-4) sqrt(C) per row of C channels -> res_out = y res_scale, act_out = silu(y) (each optional)
+int launch_kunet_pixelnorm(const float* x, float* res_out, float* act_out, int64_t rows, int C, float res_scale, hipStream_t s);
+// the same norm along dh of every head's q, k and v of a (rows, 3 heads dh) to_qkv output, in place
+int launch_kunet_qkv_norm(float* qkv, int64_t rows, int heads, int dh, hipStream_t s);
+// the 2x2 mean: (B, H, W, C) -> (B, H/2, W/2, C)
+int launch_kunet_avgpool2(const float* x, float* y, int B, int H, int W, int C, hipStream_t s);
+// bilinear x2 (0.25 / 0.75 taps, edge clamp): (B, H, W, C) -> up_out = x_up, act_out = silu(x_up), res_out = x_up res_scale
+// (each optional), all (B, 2H, 2W, C)
+int launch_kunet_bilinear_up2(const float* x, float* up_out, float* act_out, float* res_out, int B, int H, int W, int C,
+                              float res_scale, hipStream_t s);
+// act_out (rows, Ca + Cb) = cat(silu(ca a), silu(cb b)) (b == nullptr: Cb = 0); copy_out (rows, Ca) = a copy_scale;
+// act_out is optional without a second source, copy_out always
+int launch_kunet_act(const float* a, int Ca, float ca, const float* b, int Cb, float cb, float* act_out, float* copy_out,
+                     float copy_scale, int64_t rows, hipStream_t s);
+// e (R, 2 half + n_labels) = [sqrt(2) sin(2 pi t w) | sqrt(2) cos(2 pi t w) | labels row]; t[r], or with `st` the entry
+// t[st->step * t_stride] for every row
+int launch_kunet_fourier(const float* t, int t_stride, const SamplerState* st, const float* w, const float* labels, int n_labels,
+                         float* e, int R, int half, hipStream_t s);
+// (B, C, HW) NCHW -> (B, HW, C + 1) NHWC with a channel of ones in front
+int launch_kunet_input(const float* x_nchw, float* y, int B, int C, int HW, hipStream_t s);
+
 }  // namespace dm

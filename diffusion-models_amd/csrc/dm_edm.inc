@@ -4,8 +4,8 @@
 
 namespace dm {
 
-static int edm_handle_ok(dm_unet* u) {
-    if (handle_ready(u)) return 1;
+static int edm_handle_ok(dm_unet* u, bool karras_ok = false) {
+    if (handle_ready(u, karras_ok)) return 1;
     DM_REQUIRE(u->cfg.learned_sinusoidal_dim > 0,
                "a real-valued time needs a learned / random sinusoidal U-Net (ElucidatedDiffusion asserts it)");
     return 0;
@@ -19,7 +19,7 @@ static int sample_edm_impl(dm_unet* u, const dm_edm_args* a) {
     DM_REQUIRE(a->kind == DM_EDM_HEUN || a->kind == DM_EDM_DPMPP, "unknown EDM sampler kind");
     DM_REQUIRE(a->table_host && a->x_init && a->out, "null argument");
     DM_REQUIRE(a->n_steps > 0 && a->B > 0, "empty run");
-    if (edm_handle_ok(u)) return 1;
+    if (edm_handle_ok(u, /*karras_ok=*/true)) return 1;
     if (plain_unet_ok(u,
                       "ElucidatedDiffusion needs a U-Net with out_dim == input channels == channels (no self-conditioning, no image "
                       "condition, no learned variance)",
@@ -146,7 +146,7 @@ extern "C" {
 int dm_unet_forward_ft(dm_unet* u, const float* x, const float* time, const float* ctx, int ctx_tokens, float* out, int B,
                        int H, int W, void* stream) {
     DM_REQUIRE(u && x && time && out, "null argument");
-    if (edm_handle_ok(u)) return 1;
+    if (edm_handle_ok(u, /*karras_ok=*/true)) return 1;
     DM_REQUIRE(B > 0, "empty batch");
     DM_REQUIRE((ctx == nullptr) == (ctx_tokens == 0), "ctx and ctx_tokens come together");
     if (check_hw(u, H, W)) return 1;

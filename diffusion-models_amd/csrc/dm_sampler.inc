@@ -11,11 +11,13 @@
 namespace dm {
 
 // ---- handle checks ----------------------------------------------------------------------------------------------------
-static int handle_ready(dm_unet* u) {
+// karras_ok: the caller runs a KarrasUnet handle too (the float-time forward and the EDM loops); every other loop refuses it
+static int handle_ready(dm_unet* u, bool karras_ok = false) {
     DM_REQUIRE(u->finalized, "dm_unet_finalize has not been called");
     DM_REQUIRE(!u->poisoned, "the last dm_unet_refresh failed: refresh again before running the model");
     DM_REQUIRE(!u->infer_stale, "parameters were updated on the device (dm_unet_optimizer_step): call dm_unet_train_sync "
                                 "before sampling from this handle");
+    DM_REQUIRE(karras_ok || !u->kunet, "a KarrasUnet handle runs dm_unet_forward_ft and dm_sample_edm only");
     return 0;
 }
 

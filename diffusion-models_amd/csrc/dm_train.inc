@@ -1454,6 +1454,8 @@ extern "C" {
 static int train_enable_impl(dm_unet* u, bool ft) {
     DM_REQUIRE(!u->cfg.seq1d, "training the sequence model (Unet1D: loss, backward pass, Trainer1D) is not on the HIP path yet: "
                               "a seq1d handle serves dm_unet_forward and the sampling loops");
+    DM_REQUIRE(!u->kunet, "training KarrasUnet (forced weight normalisation in the training forward, the backward of its "
+                          "operators) is not on the HIP path yet: the handle serves dm_unet_forward_ft and dm_sample_edm");
     DM_CHECK_HIP(hipSetDevice(u->device));
     if (u->train) {
         DM_REQUIRE(u->train->ft == ft, "the handle is already in training mode through the other entry "

@@ -427,6 +427,7 @@ int dm_op_cross_attention_bwd(const float* x, const float* ctx, const float* w_q
 int dm_unet_cond_forward(dm_unet* u, int walk, int time_kind, const void* time, const float* ctx, const int32_t* text_mask,
                          const dm_cond_bufs* out, int B, void* stream) {
     DM_REQUIRE(u && time && out, "null argument");
+    DM_REQUIRE(!u->kunet, "dm_unet_cond_forward: the conditioning head of the image U-Net; a KarrasUnet handle has its own");
     DM_REQUIRE(walk == DM_COND_WALK_INFER || walk == DM_COND_WALK_TRAIN, "walk: DM_COND_WALK_INFER or DM_COND_WALK_TRAIN");
     DM_REQUIRE(time_kind >= DM_COND_TIME_INT && time_kind <= DM_COND_TIME_FLOAT_SHARED, "unknown time kind");
     if (cond_args_ok(u, ctx, text_mask, B)) return 1;

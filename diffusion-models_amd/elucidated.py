@@ -8,6 +8,9 @@ the weighted denoising loss of :228-264 with its backward pass).  The per-step a
 the way the reference computes them -- preconditioning terms as fp32 tensor arithmetic, the churn terms as Python doubles
 rounded to fp32 once -- and handed to the library as a table; the kernels hold no schedule logic.
 
+Over a ``KarrasUnet`` (karras.py) both loops run too -- a stated deviation: the reference's constructor raises
+``AttributeError`` on that network -- and ``class_labels=`` carries the labels of a class-conditional one.
+
 Extensions (keyword-only, as on the other samplers): ``noise`` injects a source of N(0,1) draws called in the
 reference's order (the start image, then one draw per Heun step); ``seed`` / ``sample_offset`` select the device Philox
 stream and the index of the call's first sample in a global batch.
@@ -206,9 +209,9 @@ class ElucidatedDiffusion(FloatTimeDiffusion):
         return edm_sigmas(n, self.sigma_min, self.sigma_max, self.rho).to(self.device)
 
     # -- equation 7 --------------------------------------------------------------------------------
-    def preconditioned_network_forward(self, noised_images, sigma, self_cond=None, clamp=False):
+    def preconditioned_network_forward(self, noised_images, sigma, self_cond=None, clamp=False, *, class_labels=None):
         """:91-110.  ``sigma``: a float or a (B,) tensor.  The scalings run in dm_op_edm_churn_in / dm_op_edm_euler, the
-        network through the float-time forward."""
+        network through the float-time forward.  ``class_labels``: for a class-conditional network (``_labels``)."""
         if self_cond is not None:
             raise NotImplementedError("self-conditioning is not built on the HIP ElucidatedDiffusion path")
         x = noised_images.to(self.device, torch.float32).contiguous()
@@ -227,15 +230,28 @@ class ElucidatedDiffusion(FloatTimeDiffusion):
         xin = torch.empty_like(x)
         _lib.check(self._lib.dm_op_edm_churn_in(_lib.ptr(x), None, _fptr(tab), rows, 0, 1, 0, None, _lib.ptr(xin), b, per,
                                                 stream))
-        net_out = self.net(xin, tab[:, C_NOISE].expand(b).contiguous().to(self.device))
+        self._labels(class_labels, b)
+        kw = {} if class_labels is None else dict(class_labels=class_labels)
+        net_out = self.net(xin, tab[:, C_NOISE].expand(b).contiguous().to(self.device), **kw)
         out = torch.empty_like(x)
         _lib.check(self._lib.dm_op_edm_euler(_lib.ptr(x), _lib.ptr(net_out), _fptr(tab), rows, int(bool(clamp)),
                                              _lib.ptr(out), None, None, None, b, per, stream))
         return out
 
     # -- sampling ----------------------------------------------------------------------------------
-    def _run(self, kind, table, sigma_init, batch_size, clamp, noise, noise_rows, seed, sample_offset):
+    def _labels(self, class_labels, batch):
+        """The keyword extension ``class_labels=`` of the loops: required by a network with ``num_classes``
+        (``KarrasUnet``), refused by every other, as the network's own assert does.  The labels become device data of the
+        handle's conditioning head, so the captured step graph serves any labels."""
+        net = self.net
+        if not hasattr(net, "set_class_labels"):
+            assert class_labels is None, "class_labels= needs a class-conditional network (KarrasUnet(num_classes=...))"
+            return
+        net.set_class_labels(class_labels, batch)
+
+    def _run(self, kind, table, sigma_init, batch_size, clamp, noise, noise_rows, seed, sample_offset, class_labels=None):
         shape = (int(batch_size), self.channels, self.image_size, self.image_size)
+        self._labels(class_labels, shape[0])
         f = self.net.downsample_factor
         assert shape[0] > 0 and self.image_size % f == 0, f"shape {shape}: the sides must be divisible by {f}"
         seed, x_init, noise_dev = self._start(shape, noise, noise_rows, seed, sample_offset)
@@ -250,21 +266,23 @@ class ElucidatedDiffusion(FloatTimeDiffusion):
         _lib.check(self._lib.dm_sample_edm(self.net._handle, C.byref(a)))
         return out
 
-    def sample(self, batch_size=16, num_sample_steps=None, clamp=True, *, noise=None, seed=None, sample_offset=0):
+    def sample(self, batch_size=16, num_sample_steps=None, clamp=True, *, noise=None, seed=None, sample_offset=0,
+               class_labels=None):
         """:129-187, the stochastic Heun sampler (Algorithm 2).  The reference draws the churn noise at every step, so an
         injected ``noise`` source is called once per step whatever gamma is."""
         n = self.num_sample_steps if num_sample_steps is None else num_sample_steps
         table = edm_heun_table(n, self.sigma_min, self.sigma_max, self.sigma_data, self.rho, self.S_churn, self.S_tmin,
                                self.S_tmax, self.S_noise)
         sigma_init = edm_sigmas(n, self.sigma_min, self.sigma_max, self.rho)[0].item()
-        return self._run(_lib.EDM_HEUN, table, sigma_init, batch_size, clamp, noise, n, seed, sample_offset)
+        return self._run(_lib.EDM_HEUN, table, sigma_init, batch_size, clamp, noise, n, seed, sample_offset, class_labels)
 
-    def sample_using_dpmpp(self, batch_size=16, num_sample_steps=None, *, noise=None, seed=None, sample_offset=0):
+    def sample_using_dpmpp(self, batch_size=16, num_sample_steps=None, *, noise=None, seed=None, sample_offset=0,
+                           class_labels=None):
         """:189-224, DPM-Solver++(2M): one network evaluation per step, one draw (the start image)."""
         n = self.num_sample_steps if num_sample_steps is None else num_sample_steps
         table = edm_dpmpp_table(n, self.sigma_min, self.sigma_max, self.sigma_data, self.rho)
         sigma_init = edm_sigmas(n, self.sigma_min, self.sigma_max, self.rho)[0].item()
-        return self._run(_lib.EDM_DPMPP, table, sigma_init, batch_size, False, noise, 0, seed, sample_offset)
+        return self._run(_lib.EDM_DPMPP, table, sigma_init, batch_size, False, noise, 0, seed, sample_offset, class_labels)
 
     # -- training ----------------------------------------------------------------------------------
     def forward(self, images, *, sigmas=None, noise=None, loss_scale=1.0, accumulate=False, sync=True,

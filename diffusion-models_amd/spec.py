@@ -718,3 +718,145 @@ def unet1d_param_spec(cfg: Unet1DConfig, prefix: str = "") -> ParamSpec:
     spec += _resnet1d_spec(f"{p}final_res_block", cfg.init_dim_ * 2, cfg.init_dim_, td)
     spec += [(f"{p}final_conv.weight", (cfg.out_dim_, cfg.init_dim_, 1)), (f"{p}final_conv.bias", (cfg.out_dim_,))]
     return spec
+
+
+# ----------------------------------------------------------------------------
+# KarrasUnet: the EDM2 magnitude-preserving U-Net (karras_unet.py:374-595)
+# ----------------------------------------------------------------------------
+
+MP_SILU_GAIN = 1.0 / 0.596  # MPSiLU (karras_unet.py:24-26)
+
+
+@dataclass(frozen=True)
+class KarrasUnetConfig:
+    """Constructor arguments of the reference ``KarrasUnet`` (karras_unet.py:379-399).  ``attn_flash`` does not change the
+    arithmetic and ``dropout`` acts in training only: both are accepted and unused."""
+
+    image_size: int = 64
+    dim: int = 192
+    dim_max: int = 768
+    num_classes: Optional[int] = None
+    channels: int = 4
+    num_downsamples: int = 3
+    num_blocks_per_stage: int = 4
+    attn_res: Tuple[int, ...] = (16, 8)
+    fourier_dim: int = 16
+    attn_dim_head: int = 64
+    attn_flash: bool = False
+    mp_cat_t: float = 0.5
+    mp_add_emb_t: float = 0.5
+    attn_res_mp_add_t: float = 0.3
+    resnet_mp_add_t: float = 0.3
+    dropout: float = 0.1
+    self_condition: bool = False
+
+    @property
+    def input_channels(self) -> int:
+        return self.channels * (2 if self.self_condition else 1)
+
+    @property
+    def out_dim_(self) -> int:
+        return self.channels
+
+    @property
+    def emb_dim(self) -> int:
+        return self.dim * 4
+
+    @property
+    def downsample_factor(self) -> int:
+        return 2 ** self.num_downsamples
+
+    @property
+    def attn_res_(self) -> Tuple[int, ...]:
+        a = self.attn_res
+        return tuple(a) if isinstance(a, (tuple, list, set, frozenset)) else (a,)
+
+    def heads(self, dim_out: int) -> int:
+        """``max(ceil(dim_out / attn_dim_head), 2)`` (:213, :295)."""
+        return max(-(-dim_out // self.attn_dim_head), 2)
+
+
+@dataclass(frozen=True)
+class KarrasBlock:
+    """One ``Encoder`` / ``Decoder`` of the network: where it sits (``downs.3``), its widths, and what it does around its
+    two convolutions.  ``skip``: a decoder that takes the concatenated skip (``din`` is then twice the width of ``x``)."""
+
+    name: str
+    decoder: bool
+    din: int
+    dout: int
+    attn: bool = False
+    down: bool = False
+    up: bool = False
+    skip: bool = False
+
+    @property
+    def res_conv(self) -> bool:
+        return self.decoder and self.din != self.dout
+
+
+def karras_blocks(cfg: KarrasUnetConfig) -> Dict[str, List[KarrasBlock]]:
+    """The module lists ``downs`` / ``mids`` / ``ups`` in forward order, built as :461-513 builds them (``ups`` is filled by
+    prepending)."""
+    attn_res = set(cfg.attn_res_)
+    downs: List[tuple] = []
+    ups: List[tuple] = []
+    curr_dim, curr_res = cfg.dim, cfg.image_size
+    ups.insert(0, dict(din=cfg.dim * 2, dout=cfg.dim, skip=True))
+    for _ in range(cfg.num_blocks_per_stage):
+        downs.append(dict(din=curr_dim, dout=curr_dim))
+        ups.insert(0, dict(din=curr_dim * 2, dout=curr_dim, skip=True))
+    for _ in range(cfg.num_downsamples):
+        dim_out = min(cfg.dim_max, curr_dim * 2)
+        upsample = dict(din=dim_out, dout=curr_dim, attn=curr_res in attn_res, up=True)
+        curr_res //= 2
+        has_attn = curr_res in attn_res
+        downs.append(dict(din=curr_dim, dout=dim_out, down=True, attn=has_attn))
+        ups.insert(0, upsample)
+        ups.insert(0, dict(din=dim_out * 2, dout=dim_out, attn=has_attn, skip=True))
+        for _ in range(cfg.num_blocks_per_stage):
+            downs.append(dict(din=dim_out, dout=dim_out, attn=has_attn))
+            ups.insert(0, dict(din=dim_out * 2, dout=dim_out, attn=has_attn, skip=True))
+        curr_dim = dim_out
+    mid_attn = curr_res in attn_res
+    mids = [dict(din=curr_dim, dout=curr_dim, attn=mid_attn)] * 2
+    return {
+        "downs": [KarrasBlock(name=f"downs.{i}", decoder=False, **b) for i, b in enumerate(downs)],
+        "mids": [KarrasBlock(name=f"mids.{i}", decoder=True, **b) for i, b in enumerate(mids)],
+        "ups": [KarrasBlock(name=f"ups.{i}", decoder=True, **b) for i, b in enumerate(ups)],
+    }
+
+
+def _karras_block_spec(p: str, b: KarrasBlock, cfg: KarrasUnetConfig) -> ParamSpec:
+    s: ParamSpec = []
+    if b.down:
+        s.append((f"{p}.downsample_conv.weight", (b.dout, b.din, 1, 1)))
+    s += [(f"{p}.to_emb.0.weight", (b.dout, cfg.emb_dim)), (f"{p}.to_emb.1.gain", ())]
+    s += [(f"{p}.block1.1.weight", (b.dout, b.dout if b.down else b.din, 3, 3)), (f"{p}.block2.2.weight", (b.dout, b.dout, 3, 3))]
+    if b.res_conv:
+        s.append((f"{p}.res_conv.weight", (b.dout, b.din, 1, 1)))
+    if b.attn:
+        heads, dh = cfg.heads(b.dout), cfg.attn_dim_head
+        s += [(f"{p}.attn.mem_kv", (2, heads, NUM_MEM_KV, dh)), (f"{p}.attn.to_qkv.weight", (3 * heads * dh, b.dout, 1, 1)),
+              (f"{p}.attn.to_out.weight", (b.dout, heads * dh, 1, 1))]
+    return s
+
+
+def karras_unet_param_spec(cfg: KarrasUnetConfig, prefix: str = "") -> ParamSpec:
+    """(name, shape) of every ``KarrasUnet`` parameter, in ``state_dict()`` order: ``downs`` and ``ups`` are registered
+    before ``mids`` (:461-462, :510)."""
+    p = prefix
+    spec: ParamSpec = [
+        (f"{p}input_block.weight", (cfg.dim, cfg.input_channels + 1, 3, 3)),
+        (f"{p}output_block.0.weight", (cfg.channels, cfg.dim, 3, 3)),
+        (f"{p}output_block.1.gain", ()),
+        (f"{p}to_time_emb.0.weights", (cfg.fourier_dim // 2,)),
+        (f"{p}to_time_emb.1.weight", (cfg.emb_dim, cfg.fourier_dim)),
+    ]
+    if cfg.num_classes is not None:
+        spec.append((f"{p}to_class_emb.weight", (cfg.emb_dim, cfg.num_classes)))
+    blocks = karras_blocks(cfg)
+    for group in ("downs", "ups", "mids"):
+        for b in blocks[group]:
+            spec += _karras_block_spec(p + b.name, b, cfg)
+    return spec

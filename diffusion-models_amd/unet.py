@@ -33,6 +33,8 @@ class Unet:
     object is callable: ``eps = unet(x, time)``.
     """
 
+    float_time_training = True  # dm_unet_train_enable_ft arms the handle (a subclass whose handle cannot train says False)
+
     def __init__(
         self,
         dim,
@@ -172,7 +174,7 @@ class Unet:
             t = state_dict[name].detach().to(device="cpu", dtype=torch.float32).contiguous()
             if tuple(t.shape) != tuple(shape):
                 raise RuntimeError(f"size mismatch for {name}: {tuple(t.shape)} vs {tuple(shape)}")
-            shp = (C.c_int64 * t.dim())(*t.shape)
+            shp = (C.c_int64 * max(t.dim(), 1))(*t.shape)  # a 0-dim parameter (KarrasUnet's gains) still passes a pointer
             _lib.check(set_param(self._handle, name.encode(), t.data_ptr(), shp, t.dim()))
         if self._loaded:
             _lib.check(self._lib.dm_unet_refresh(self._handle))

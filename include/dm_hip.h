@@ -1401,6 +1401,96 @@ int dm_op_bpd_terms(const float* model_out, const float* x0, const float* x_t, c
                     int objective, int clip_denoised, float* terms_out_host, int B, int64_t per, void* stream);
 int dm_op_bpd_prior(const float* x0, float sqrt_ac, float logvar, float* prior, int B, int64_t per, void* stream);
 
+/* ---- KarrasUnet: the EDM2 magnitude-preserving U-Net (DD/karras_unet.py:374-595; arXiv 2312.02696, config G) ------------
+ *
+ * A second network body behind the dm_unet handle.  dm_kunet_create returns a handle that dm_unet_set_param,
+ * dm_unet_get_param_host, dm_unet_update_param, dm_unet_refresh, dm_unet_finalize, dm_unet_missing_params,
+ * dm_unet_workspace_bytes, dm_unet_graph_captures and dm_unet_destroy serve as they serve an image U-Net's; the parameter
+ * names and shapes are the reference's state_dict() ("input_block.weight" (dim, input_channels + 1, 3, 3),
+ * "downs.3.block1.1.weight", "downs.3.to_emb.1.gain" (), "ups.0.attn.mem_kv" (2, heads, 4, dh), "to_time_emb.0.weights", ...).
+ * The time of this network is real-valued: the handle runs dm_unet_forward_ft and dm_sample_edm (both kinds; the network
+ * must then have input_channels == channels).  dm_unet_forward, every other dm_sample* loop, dm_eval_bpd and
+ * dm_unet_train_enable* return an error and leave the handle usable.  H and W of every call are image_size.
+ *
+ * Every magnitude-preserving constant (forced weight normalisation, MPSiLU's 1 / 0.596, MPAdd, MPCat, Gain) is folded into
+ * the packed weights at dm_unet_finalize / dm_unet_refresh, on the host, in double. */
+typedef struct dm_kunet_cfg {
+    int32_t image_size;
+    int32_t dim;
+    int32_t dim_max;
+    int32_t num_classes;    /* 0 = no class condition */
+    int32_t channels;
+    int32_t input_channels; /* channels, or 2 channels with self-conditioning (the caller concatenates self_cond in front) */
+    int32_t num_downsamples;
+    int32_t num_blocks_per_stage;
+    int32_t n_attn_res;
+    int32_t attn_res[DM_MAX_STAGES]; /* resolutions whose blocks end in an attention layer */
+    int32_t fourier_dim;
+    int32_t attn_dim_head;  /* 32 or 64; heads of a layer = max(ceil(dim_out / attn_dim_head), 2) */
+    float mp_cat_t;
+    float mp_add_emb_t;
+    float attn_res_mp_add_t;
+    float resnet_mp_add_t;
+} dm_kunet_cfg;
+int dm_kunet_create(const dm_kunet_cfg* cfg, int device, dm_unet** out);
+/* The class labels of the next calls with batch B on a handle with num_classes: labels_dev (B, num_classes) device floats,
+ * ALREADY multiplied by sqrt(num_classes) (one-hot rows of integer labels, or soft labels).  They are copied into a buffer
+ * of the handle that the conditioning head reads as device data: a captured step graph serves any labels.  The call
+ * synchronises the device. */
+int dm_kunet_set_class_labels(dm_unet* u, const float* labels_dev, int B);
+
+/* The network's own kernels and blocks on their own (tests).  Device pointers; every call waits for its result.
+ * The row passes take tensors as the library holds them (NHWC: rows of C channels, C % 4 == 0):
+ *   pixelnorm:     y = x / max(||x||, 1e-4) sqrt(C) per row -> res_out = y res_scale, act_out = silu(y) (each may be NULL)
+ *   avgpool2:      (B, H, W, C) -> (B, H/2, W/2, C), the 2x2 mean
+ *   bilinear_up2:  (B, H, W, C) -> x_up (B, 2H, 2W, C) with 0.25 / 0.75 taps and edge clamp: up_out = x_up,
+ *                  act_out = silu(x_up), res_out = x_up res_scale (each may be NULL)
+ *   act:           act_out (rows, Ca + Cb) = cat(silu(ca a), silu(cb b)) (b NULL: Cb = 0), copy_out (rows, Ca) = a copy_scale
+ *   attention:     qkv (B, n, 3 heads dh) as to_qkv leaves it, mem_kv (2, heads, 4, dh) as stored -> out (B, n, heads dh):
+ *                  q, k, v and the memory rows pixel-normed along dh, softmax(q k^T dh^-0.5) v */
+int dm_op_kunet_pixelnorm(const float* x, float* res_out, float* act_out, int64_t rows, int C, float res_scale, void* stream);
+int dm_op_kunet_avgpool2(const float* x, float* y, int B, int H, int W, int C, void* stream);
+int dm_op_kunet_bilinear_up2(const float* x, float* up_out, float* act_out, float* res_out, int B, int H, int W, int C,
+                             float res_scale, void* stream);
+int dm_op_kunet_act(const float* a, int Ca, float ca, const float* b, int Cb, float cb, float* act_out, float* copy_out,
+                    float copy_scale, int64_t rows, void* stream);
+int dm_op_kunet_attention(const float* qkv, const float* mem_kv, float* out, int B, int n, int heads, int dh, void* stream);
+/* The conditioning head.  time (B) floats; labels (B, num_classes) already times sqrt(num_classes), or NULL with
+ * num_classes = 0 (then class_w is NULL too); fourier_w (fourier_dim / 2), time_w (emb_dim, fourier_dim), class_w
+ * (emb_dim, num_classes) as stored; to_emb_w: the to_emb.0.weight matrices of n_blocks blocks one behind the other
+ * ((sum dout, emb_dim) rows) with their widths dout_host and gains gain_host (host arrays).  out (B, 2 sum dout): per block
+ * dout values gain * to_emb(emb), then dout zeros -- the scale / shift rows the convolution epilogue reads. */
+int dm_op_kunet_head(const float* time, const float* labels, const float* fourier_w, const float* time_w, const float* class_w,
+                     const float* to_emb_w, const int32_t* dout_host, const float* gain_host, int n_blocks, int fourier_dim,
+                     int emb_dim, int num_classes, float mp_add_emb_t, float* out, int B, void* stream);
+/* input_block (x (B, C, H, W), weight (dim, C + 1, 3, 3)) and output_block (x (B, dim, H, W), weight (channels, dim, 3, 3),
+ * the gain): NCHW in and out, weights as stored. */
+int dm_op_kunet_input_block(const float* x, const float* weight, float* out, int B, int C, int H, int W, int dim, void* stream);
+int dm_op_kunet_output_block(const float* x, const float* weight, float gain, float* out, int B, int dim, int H, int W,
+                             int channels, void* stream);
+/* One Encoder (decoder = 0; down: the downsampling form) or Decoder (decoder = 1; up: the upsampling form; skip: it takes the
+ * skip tensor, whose skip_channels are the last of its din input channels), with attention behind it when attn != 0.  NCHW
+ * tensors, weights as stored (NULL where the form has none: down_w, res_w -- a Decoder has a res_conv iff din != dout --,
+ * mem_kv / qkv_w / out_w).  emb_scale (B, dout) = gain * to_emb(emb), as the head produces it.  out (B, dout, Ho, Wo). */
+typedef struct dm_kunet_block_op {
+    int32_t decoder, down, up, skip, attn;
+    int32_t din, dout, skip_channels, dh;
+    float mp_cat_t, attn_res_mp_add_t, resnet_mp_add_t;
+    const float* x;
+    const float* skip_x;
+    const float* emb_scale;
+    const float* down_w;
+    const float* w1;
+    const float* w2;
+    const float* res_w;
+    const float* mem_kv;
+    const float* qkv_w;
+    const float* out_w;
+    float* out;
+    int32_t B, H, W;
+} dm_kunet_block_op;
+int dm_op_kunet_block(const dm_kunet_block_op* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
